@@ -2,7 +2,7 @@
 """bench.py -- the DAzimSurfTomo hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--sources S] [--receivers R] [--no-cpu] [--workload s128|s256|s512]
-                    [--scaling weak|strong] [--dry-launch]
+                    [--scaling weak|strong] [--dry-launch] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over the S-256 synthetic batch: dispersion +
 depth kernels for every model column, 16 periods x S sources eikonal fields on the 256x256 grid,
@@ -35,6 +35,8 @@ Environment: DAZIM_OPTS=name=value,... sets library tuning options (tools/opt_sw
 multi-rank code path with a single rank; DAZIM_BENCH_REHEARSAL=1 runs N ranks on ONE GPU (gloo process group, the library's file
 transport): the whole N-rank path except RCCL, for boxes with one GPU (tests/test_multigpu_gpu.py, tests/test_rehearsal_gpu.py).
 `--dump PATH`: every rank writes PATH.<rank>.npz (x, predicted times, dispersion tables) after the timed steps.
+`--dump-outputs DIR`: after the timed steps, what the last timed step returned -- x and the LSMR info, the predicted times, the
+phase-velocity and depth-kernel tables -- as DIR/<name>.npy (see dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -458,6 +460,28 @@ def timed_small_forward(ctx, nsrc=20, nrcv=16):
         NX, NY, PERIODS = saved
 
 
+DUMP_OUTPUT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, rank, world):
+    """--dump-outputs: every array of `arrays` (torch tensors, float32 / float64) -> outdir/<name>.npy (rank r > 0 of a multi-rank
+    run: <name>.rank<r>.npy), DUMP_OUTPUT_BYTES in all (shared by the ranks).  The budget is shared out from the smallest array up,
+    each taking at most an even share of what is left: arrays within their share are written whole, larger ones as a fixed, seeded
+    choice of their elements (the same positions in every run, in increasing order)."""
+    import torch
+    left = DUMP_OUTPUT_BYTES // world
+    os.makedirs(outdir, exist_ok=True)
+    by_size = sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size())
+    for i, (name, t) in enumerate(by_size):
+        keep = min(t.numel(), left // (len(by_size) - i) // t.element_size())
+        left -= keep * t.element_size()
+        if keep < t.numel():
+            t = t.reshape(-1)
+            idx = np.sort(np.random.default_rng(20250929).choice(t.numel(), keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(outdir, name + (f".rank{rank}" if rank else "") + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -474,8 +498,15 @@ def main():
                                                   "(each launched as `bench.py --gpus N` with the other flags unchanged)")
     ap.add_argument("--dump", default=None, help="after the timed steps every rank writes <path>.<rank>.npz: x of the last solve, its "
                                                  "predicted times and their place in the ray list (tests: N ranks against one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (64 MB at most: a fixed, "
+                         "seeded sample of larger outputs)")
     ap.add_argument("--dry-launch", action="store_true", help="spawn the ranks and shard the work, no GPU (CPU test of the launch path)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.sweep and a.dump_outputs:
+        ap.error("--dump-outputs writes one run's outputs: it cannot be combined with --sweep")
     if a.sources is None:
         a.sources = 200 if a.workload == "s128" else 1000
     if a.receivers is None:
@@ -703,7 +734,7 @@ def main():
         stats["collectives_per_iteration"] = ctx.kernel_seconds("lsmr.collectives_per_iteration")   # counted by the library
         stats["collective_kind"] = ctx.kernel_seconds("lsmr.collective_kind")
         stats["host_syncs"] = ctx.kernel_seconds("lsmr.host_syncs")      # counted by the library around the iteration loop
-        last["x"], last["tpred"] = x, tpred
+        last["x"], last["tpred"], last["info"] = x, tpred, info
         stats["spmv_kind"], stats["spmvt_kind"] = ctx.kernel_seconds("spmv.kind"), ctx.kernel_seconds("spmvt.kind")
         stats["ax_idx_bytes"], stats["aty_idx_bytes"] = ctx.kernel_seconds("spmv.idx_bytes"), ctx.kernel_seconds("spmvt.idx_bytes")
         stats["lsmr_itn"] = info["itn"]
@@ -725,6 +756,11 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:      # (before the host-array steps below, which run the step again)
+        info = last["info"]
+        lsmr_info = torch.tensor([info[k] for k in ("istop", "itn", "normA", "condA", "normr", "normAr", "normx")], dtype=torch.float64)
+        dump_outputs(a.dump_outputs, {"x": last["x"], "lsmr_info": lsmr_info, "tpred": last["tpred"], "pv": d_pv, "sen_vs": d_sen[0],
+                                      "sen_vp": d_sen[1], "sen_rho": d_sen[2]}, rank, world)
     # ---- the same step through HOST arrays (outside the timed region; `value` above is device-resident): what a caller of the
     # C ABI pays who keeps his inputs and results in host memory like the Fortran program does -- model, source / receiver lists and
     # right-hand side go up, phase-velocity maps, predicted times and x come down every step (PCIe-inclusive); the intermediates

@@ -4,7 +4,7 @@ The reference's two main programs are compiled where they lie under /root/refere
 oracle/Makefile (-O2 -ffp-contract=off, no -march), into a temporary directory.  The only edit, made to a temporary COPY of each
 main program, is one added declaration `integer iargc` (both call the GNU extension iargc() under IMPLICIT NONE,
 inv/Main_Jt.f90:144, fwd/MainForward.f90:132; gfortran is not in the image) -- the same patch
-tests/test_reference_main_links.py applies.  No reference source enters the repository.
+INTEGRATION.md describes.  No reference source enters the repository.
 
   DAzimSurfTomo  (inv/Main_Jt.f90 + the files of inv/Makefile) is run with OMP_NUM_THREADS=1 (SAVE race) on
                  the input files held by tests/golden/inversion_iso_small.npz and inversion_joint_small.npz;

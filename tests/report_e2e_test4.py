@@ -1,11 +1,12 @@
 """Timing + parity report of the bundled test4_Yunnan example through the host-array API (not collected by pytest; run on the GPU box:
 python tests/report_e2e_test4.py).  Uses the oracle for the Tikhonov rows, hence lives under tests/."""
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import dazimsurftomo_amd as dz
 from oracle.pyoracle import Oracle
 from tests.test_rays_gpu import flatten
-d = np.load("tests/golden/test4_yunnan.npz"); ctx = dz.Context(0); orc = Oracle()
+d = np.load(os.path.join(ROOT, "tests", "golden", "test4_yunnan.npz")); ctx = dz.Context(0); orc = Oracle()
 nx, ny, nz = int(d["nx"]), int(d["ny"]), int(d["nz"]); goxd, gozd, dv, minthk = float(d["goxd"]), float(d["gozd"]), float(d["dv"]), float(d["minthk"])
 vel, depz, t = d["vel"], d["depz"], d["t"]
 for rep in range(2):

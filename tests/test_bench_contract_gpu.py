@@ -66,3 +66,54 @@ def test_bench_sweep_prints_one_line_per_count():
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     check(lines[0])
+
+
+def test_bench_dump_outputs_holds_the_last_timed_step(ctx, tmp_path):
+    """--dump-outputs DIR: one float32 / float64 .npy per array the timed step returns, and --steps timed steps in the JSON line.  Every
+    step of the bench starts from the same inputs (LSMR from x = 0), so the dumped arrays must be, bit for bit, the same step computed
+    here through the library with bench.py's own inputs and options -- not read back from the bench's buffers."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    import dazimsurftomo_amd as dz
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "s128",
+                          "--sources", "40", "--no-cpu", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = check(out.stdout, steps=2)
+    names = ("x", "lsmr_info", "tpred", "pv", "sen_vs", "sen_vp", "sen_rho")
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(f"{n}.npy" for n in names)
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in names}
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    # the step of bench.py's main(), one GPU, weak scaling
+    bench.set_workload("s128")
+    vel = bench.s256_model()
+    scx, scz, per, fray, rcx, rcz, _ = bench.rank_workload(types.SimpleNamespace(sources=40, receivers=16, scaling="weak"), 0, 1)
+    T = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to("cuda:0")
+    d_vel, d_scx, d_scz, d_per = T(vel), T(scx), T(scz), T(per)
+    c3, t_ir, t_ic, t_rw = bench.tikhonov_rows(bench.NX, bench.NY, len(bench.DEPZ), len(rcx), 2.0)
+    b = np.concatenate([(np.random.default_rng(3).standard_normal(len(rcx)) * 0.5).astype(np.float32), np.zeros(c3, np.float32)])
+    geo = (bench.NX, bench.NY, bench.GOXD, bench.GOZD, bench.DV, bench.DV)
+    ctx.set_option("disp.async", 1)
+    ctx.set_option("fmm.async", 1)
+    try:
+        pv, sen, nfail = ctx.depthkernel(d_vel, bench.DEPZ, bench.PERIODS, bench.MINTHK)
+        g, nf = dz.geometry(*geo), len(scx)
+        E = lambda shape, t=torch.float32: torch.empty(shape, dtype=t, device="cuda:0")
+        fields = ctx.fmm_batch(*geo, pv, d_scx, d_scz, d_per, veln=E((len(bench.PERIODS), g.nnx, g.nnz)), ttnr=E((nf, 129, 129)),
+                               nstsr=E((nf, 129, 129), torch.int32), boxes=E((nf, 12), torch.int32), status=E((nf,), torch.int32),
+                               keep_fields=True)
+        G, tpred, _ = ctx.rays_build_G(*geo, d_vel, fields, d_scx, d_scz, d_per, T(fray), T(rcx), T(rcz), sen)
+        G.append_coo(c3, t_ir, t_ic, t_rw)
+        x, info = ctx.lsmr(G, T(b), 0.01, 1e-9, 1e-9, 1e9, 20, 10)
+        G.free()
+    finally:
+        ctx.set_option("disp.async", 0)
+        ctx.set_option("fmm.async", 0)
+    want = {"x": x, "tpred": tpred, "pv": pv, "sen_vs": sen[0], "sen_vp": sen[1], "sen_rho": sen[2]}
+    for n, v in want.items():
+        v = v.cpu().numpy()
+        assert got[n].dtype == v.dtype and np.array_equal(got[n], v), n
+    lsmr_info = [info[k] for k in ("istop", "itn", "normA", "condA", "normr", "normAr", "normx")]
+    assert got["lsmr_info"].dtype == np.float64 and np.array_equal(got["lsmr_info"], np.array(lsmr_info, np.float64))
+    assert got["lsmr_info"][1] == d["lsmr_iterations"] == 20 and nfail == 0 and np.abs(got["x"]).max() > 0

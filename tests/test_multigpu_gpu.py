@@ -1,6 +1,7 @@
 """-m gpu: the row-sharded LSMR with more than one rank, one process per GPU under torch.distributed.run.
 
-`test_two_rank_*` needs a box with >= 2 GPUs and is skipped on the 1-GPU development boxes; `test_one_rank_*` runs the very
+`test_two_rank_*` needs a node with >= 2 GPUs and skips itself on one-GPU nodes (`test_all_gpus_*` takes every GPU there is, one
+on such a node); `test_one_rank_*` runs the very
 same worker with a single rank (RCCL communicator of size 1), so that every line of the worker and of the in-library RCCL path
 is executed wherever the GPU tests run.  Both compare with the single-process oracle LSMR on the unsharded system: same istop,
 itn within 3, x to 1e-3 -- and x identical on all ranks.
@@ -48,15 +49,15 @@ def test_one_rank_worker_native_and_python_driver(orc, tmp_path):
 def test_two_rank_rccl_native_and_python_driver(orc, tmp_path):
     import torch
     if torch.cuda.device_count() < 2:
-        pytest.skip("needs >= 2 GPUs (the round-end multi-GPU node); the 1-rank variant above runs everywhere")
+        pytest.skip(f"needs 2 GPUs, found {torch.cuda.device_count()} (RCCL puts one rank on each device); the 1-rank variant above runs everywhere")
     check(run_worker(2, tmp_path, 29552), orc, 2)
 
 
 def test_all_gpus_rccl_native(orc, tmp_path):
+    """the worker with one rank on every GPU of the node, however many it has (on a one-GPU node that is the very run of
+    test_one_rank_worker_native_and_python_driver and adds nothing to it; the test exists for nodes with three or more GPUs)"""
     import torch
     n = torch.cuda.device_count()
-    if n < 4:
-        pytest.skip("needs >= 4 GPUs")
     check(run_worker(n, tmp_path, 29553), orc, n)
 
 
@@ -65,7 +66,7 @@ def test_bench_two_gpus_strong_scaling_uses_the_in_library_rccl_solve():
     LSMR runs row-sharded inside the library with its own RCCL communicator of two ranks (VERDICT r3 #9)"""
     import torch
     if torch.cuda.device_count() < 2:
-        pytest.skip("needs >= 2 GPUs (the round-end multi-GPU node)")
+        pytest.skip(f"needs 2 GPUs, found {torch.cuda.device_count()} (RCCL puts one rank on each device)")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "s512", "--scaling", "strong",
                           "--sources", "64", "--steps", "1", "--warmup", "0", "--no-cpu"], capture_output=True, text=True,
@@ -107,17 +108,23 @@ def test_bench_two_and_three_ranks_rehearsed_on_one_gpu():
 
 
 def test_bench_sweep_over_all_gpus():
-    """`bench.py --sweep 1,2[,4,8]`: one JSON line per count, values that grow with the count (weak scaling, reduced batch)"""
+    """`bench.py --sweep 1,2[,4,8]`: one JSON line per count (weak scaling, reduced batch), the ranks over RCCL on the node's GPUs.
+    On a one-GPU node the sweep runs 1, 2, 4 with the ranks rehearsed on the one GPU (DAZIM_BENCH_REHEARSAL=1: gloo process group,
+    the library's file transport), so that the sweep's launch of `bench.py --gpus N` and its N-rank runs are exercised there too."""
     import torch
     n = torch.cuda.device_count()
-    if n < 2:
-        pytest.skip("needs >= 2 GPUs")
-    counts = [c for c in (1, 2, 4, 8) if c <= n]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    if n >= 2:
+        counts = [c for c in (1, 2, 4, 8) if c <= n]
+    else:
+        # (at most four ranks: with torch.distributed.run's agent and this pytest process, six processes hold the one GPU)
+        counts = [1, 2, 4]
+        env["DAZIM_BENCH_REHEARSAL"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sweep", ",".join(map(str, counts)), "--workload", "s128",
                           "--sources", "100", "--steps", "1", "--warmup", "1", "--no-cpu"], capture_output=True, text=True,
                          timeout=1800, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(ln) for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert [d["n_gpus"] for d in lines] == counts and all(d.get("value", 0) > 0 for d in lines)
-    assert all(d["lsmr"]["rccl_nranks"] == d["n_gpus"] for d in lines if d["n_gpus"] > 1)
+    assert all(d["lsmr"]["rccl_nranks"] == d["n_gpus"] and d["lsmr"]["collectives_per_iteration"] == 1 for d in lines if d["n_gpus"] > 1)
+    assert all(d["config"]["fields_per_gpu"] == 100 * 8 and abs(d["value"] * d["ms_per_step"] / 1e3 - d["n_gpus"] * 800) < 1e-3 for d in lines)

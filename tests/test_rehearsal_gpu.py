@@ -5,8 +5,8 @@ with N >= 2 in tests/test_multigpu_gpu.py where GPUs exist).
 * the model's dispersion / TI tables sharded over 2, 3 and 5 ranks inside the library (dazim_dispersion_kernels_sharded,
   dazim_ti_kernels_sharded: the reference's one parallel loop, OMP over the columns, inv/CalSurfG.f90:39-43, inv/depthkernelTI.f90)
   = the single-rank tables bit for bit, including ranks without a block and the deferred gather of the two-stream form;
-* BASELINE config 5 rehearsed: `bench.py --gpus 8 --workload s512 --scaling strong` (reduced sources) with eight ranks against the
-  same bench with one rank -- predicted times and tables bit for bit, x to the LSMR bar;
+* BASELINE config 5's shape rehearsed: `bench.py --gpus 5 --workload s512 --scaling strong` (reduced sources) with five ranks against
+  the same bench with one rank -- predicted times and tables bit for bit, x to the LSMR bar;
 * the RCCL transport and the file transport return the same bits (one rank: all a one-GPU box can run of RCCL)."""
 import json
 import os
@@ -53,25 +53,45 @@ def run_bench(tmp_path, tag, world, args, port, opts=""):
     dump = str(tmp_path / tag)
     common = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--no-cpu", "--dump", dump] + args
     if world == 1:
-        cmd = [sys.executable] + common
+        out = subprocess.run([sys.executable] + common, capture_output=True, text=True, timeout=2400, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        stdout = out.stdout
     else:
-        env["DAZIM_BENCH_REHEARSAL"] = "1"
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-               "--master-port", str(port)] + common
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=2400, env=env)
-    assert out.returncode == 0, out.stderr[-3000:]
-    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1
+        # the ranks are started here with the environment torch.distributed.run gives them (RANK, LOCAL_RANK, WORLD_SIZE, MASTER_*),
+        # not under its agent, which opens the GPU as well: five ranks and this pytest process are six processes on the one GPU
+        env.update(DAZIM_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world))
+        logs = [(open(tmp_path / f"{tag}.{r}.out", "w+"), open(tmp_path / f"{tag}.{r}.err", "w+")) for r in range(world)]
+        procs = [subprocess.Popen([sys.executable] + common, stdout=o, stderr=e, text=True, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)))
+                 for r, (o, e) in enumerate(logs)]
+        try:
+            for p in procs:
+                p.wait(timeout=2400)
+        finally:
+            for p in procs:
+                if p.poll() is None:
+                    p.kill()
+                    p.wait()
+        text = []
+        for o, e in logs:
+            o.seek(0), e.seek(0)
+            text.append((o.read(), e.read()))
+            o.close(), e.close()
+        assert all(p.returncode == 0 for p in procs), [(p.returncode, err[-3000:]) for p, (_, err) in zip(procs, text)]
+        stdout = "".join(t for t, _ in text)
+    lines = [ln for ln in stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1                                             # rank 0 alone prints
     return json.loads(lines[0]), [np.load(f"{dump}.{r}.npz") for r in range(world)]
 
 
 # (fmm.ts=1: time slicing also for these small shards, so that the ray pass does run beside the eikonal launch on every rank -- by
 # itself the library only does that for batches larger than the resident slots, the ones with a tail worth filling)
-@pytest.mark.parametrize("workload,world,sources,opts", [("s512", 8, 40, "fmm.ts=1"), ("s512", 8, 40, "fmm.ts=1,fmm.ts_stages=2"), ("s128", 4, 60, "fmm.ts=1"),
+# (S-512 with five ranks, not config 5's eight: run as one job on a GPU node that stops a job holding the GPU in more than six
+# processes, the eight-rank form -- eight ranks, the launcher's agent and pytest, ten processes -- was stopped there)
+@pytest.mark.parametrize("workload,world,sources,opts", [("s512", 5, 40, "fmm.ts=1"), ("s512", 5, 40, "fmm.ts=1,fmm.ts_stages=2"), ("s128", 4, 60, "fmm.ts=1"),
                                                         ("s128", 4, 60, "fmm.ts=1,comm.gather_now=1"), ("s128", 4, 60, "")])
 def test_bench_strong_scaling_n_ranks_against_one_rank(tmp_path, workload, world, sources, opts):
-    """BASELINE config 5's shape (s512, strong scaling, eight ranks; reduced source count) and a four-rank S-128, every rank on the one
-    GPU: the eight-rank run must reproduce the one-rank run of the same field list -- the dispersion tables (sharded by model rows,
+    """BASELINE config 5's shape (s512, strong scaling; five ranks, reduced source count) and a four-rank S-128, every rank on the one
+    GPU: the N-rank run must reproduce the one-rank run of the same field list -- the dispersion tables (sharded by model rows,
     joined inside the library) and every ray's predicted time bit for bit (each is computed by exactly one rank with the same
     kernels), the LSMR solution to the bar of tests/bars.py for identical (A, b) (the ranks' partial products are added in rank
     order instead of one pass over all rows)."""
@@ -79,7 +99,7 @@ def test_bench_strong_scaling_n_ranks_against_one_rank(tmp_path, workload, world
     d1, r1 = run_bench(tmp_path, "one", 1, args, 0)
     # (opts "comm.gather_now=1": the sharded depth-kernel tables gathered at once instead of behind the perturbed copies -- what
     # the library does by itself over RCCL from four ranks on, so that the ray call may run beside the asynchronous eikonal launch)
-    dn, rn = run_bench(tmp_path, "many", world, args, 29640 + world + len(opts), opts)
+    dn, rn = run_bench(tmp_path, "many", world, args, 29640 + world + len(opts) + (40 if workload == "s512" else 0), opts)
     if workload != "s512":    # (which heap form -- hence how many coarse stages, hence whether there is a tail worth filling -- a small S-512 shard gets is the library's choice)
         assert dn["rays_beside_eikonal_tail"] is ("fmm.ts=1" in opts)
     assert dn["n_gpus"] == world and dn["lsmr"]["rccl_nranks"] == world and dn["lsmr"]["collectives_per_iteration"] == 1

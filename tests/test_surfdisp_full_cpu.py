@@ -1,15 +1,13 @@
 """CPU: the oracle's whole surfdisp96 (oracle/surfdisp_full.c: Love / Rayleigh, water layer, higher modes, group velocity,
 flat / spherical) against golden vectors made by the reference subroutine itself (tests/golden/make_surfdisp_full_golden.py)
-and, where oracle/_ref exists (the build container), against the reference directly on seeded random models.  Bit-equal: both
+and against the reference's results on seeded random models (tests/golden/make_ref_crosscheck_golden.py).  Bit-equal: both
 are IEEE fp64 / fp32 in the same order with the same libm."""
 import os
 
 import numpy as np
-import pytest
-
-from oracle.pyoracle import Ref
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "surfdisp96_full.npz")
+REF_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_crosscheck.npz")
 
 
 def test_full_oracle_reproduces_the_reference_goldens(orc):
@@ -37,11 +35,12 @@ def test_hot_path_combination_equals_the_pinned_routine(orc):
         assert np.array_equal(orc.surfdisp96_full(*a, g["periods"]), orc.surfdisp96(*a, g["periods"]))
 
 
-@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref (flang build of the reference) is only present in the build container")
-def test_full_oracle_against_the_reference_on_random_models(orc):
-    ref = Ref()
+RANDOM_PERIODS = np.array([4, 6, 9, 13, 18, 25, 33, 45], float)
+RANDOM_COMBOS = ((0, 1, 1, 0), (1, 1, 2, 1), (1, 2, 1, 1), (0, 2, 3, 0), (1, 2, 2, 0), (1, 1, 1, 1))
+
+
+def random_models():
     rng = np.random.default_rng(77)
-    t = np.array([4, 6, 9, 13, 18, 25, 33, 45], float)
     for trial in range(24):
         n = int(rng.integers(3, 13))
         thk = rng.uniform(0.8, 9.0, n).astype(np.float32)
@@ -52,7 +51,13 @@ def test_full_oracle_against_the_reference_on_random_models(orc):
         rho = (np.float32(0.32) * vp + np.float32(0.77)).astype(np.float32)
         if trial % 4 == 0:
             vs[0], vp[0], rho[0] = 0.0, 1.5, 1.03
-        for s, w, m, q in ((0, 1, 1, 0), (1, 1, 2, 1), (1, 2, 1, 1), (0, 2, 3, 0), (1, 2, 2, 0), (1, 1, 1, 1)):
-            a = orc.surfdisp96_full(thk, vp, vs, rho, t, s, w, m, q)
-            b = ref.surfdisp96_full(thk, vp, vs, rho, t, s, w, m, q)
+        yield thk, vp, vs, rho
+
+
+def test_full_oracle_against_the_reference_on_random_models(orc):
+    ref = np.load(REF_GOLD)
+    for trial, (thk, vp, vs, rho) in enumerate(random_models()):
+        for s, w, m, q in RANDOM_COMBOS:
+            a = orc.surfdisp96_full(thk, vp, vs, rho, RANDOM_PERIODS, s, w, m, q)
+            b = ref[f"surfdisp_{trial}_{s}{w}{m}{q}"]
             assert np.array_equal(a, b), (trial, s, w, m, q, a, b)

@@ -1,7 +1,7 @@
 """Dispersion kernel alone: python tools/disp_only.py <nx> [<nx> ...]  (S-256 style model, 12 knots, 16 periods); prints kernel
 seconds and work items so that the effect of the last, partially filled round of workgroups can be seen."""
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 import dazimsurftomo_amd as dz
 ctx = dz.Context(0)
