@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the DAzimSurfTomo hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--sources S] [--receivers R] [--no-cpu] [--workload s128|s256|s512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--sources S] [--receivers R] [--full [--no-cpu]] [--workload s128|s256|s512]
                     [--scaling weak|strong] [--dry-launch] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over the S-256 synthetic batch: dispersion +
@@ -14,9 +14,12 @@ torch.distributed.run, one rank per GPU) every rank processes its own S sources 
 data-path collective in the forward pass).
 
 The JSON line also carries `roofline` for the dominant kernel (the eikonal kernel, bound by instruction
-issue: useful and issued VALU rates against the measured issue peak; its HBM fraction under `roofline.hbm`), `spmv` (the HBM-bound kernel the
-40 % target applies to) and `cpu_baseline` (the oracle = plain-C port of the reference, 1 thread, on
-a bounded sample of the same workload on this box's host cores).
+issue: useful and issued VALU rates against the measured issue peak; its HBM fraction under `roofline.hbm`) and `spmv` (the HBM-bound
+kernel the 40 % target applies to), both taken from the timed steps and the committed counter files.  A plain run does nothing else:
+it sets up, warms up, times the steps, writes --dump-outputs and prints the line.  `--full` (single GPU) adds, after the timed steps,
+the legs that take runs of their own: `value_host_api` (the step through host arrays) and `cpu_baseline` (the oracle = plain-C port
+of the reference, 1 thread and all host cores, on a bounded sample of the same workload, with `timed_small`, a complete S-128
+forward on the host and on the device); `--full --no-cpu` leaves them out again.
 
 Multi-GPU: `python bench.py --gpus N` with no WORLD_SIZE in the environment launches itself as N ranks under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU); started by
@@ -490,7 +493,9 @@ def main():
     ap.add_argument("--sources", type=int, default=None, help="sources per GPU (default: 1000; 200 for s128, SURVEY 8d)")
     ap.add_argument("--receivers", type=int, default=None, help="receivers per source (default: 32; 16 for s128)")
     ap.add_argument("--lsmr-iters", type=int, default=20)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the host-array step and the CPU baseline "
+                                                        "(single GPU; minutes, not seconds)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the host-array step and the CPU baseline out")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="s256")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --sources per GPU; strong: --sources in total, one field list sharded over the ranks")
@@ -767,7 +772,8 @@ def main():
     # (kernel tables, refined fields, G) stay in dazim_malloc'ed / library memory as in host/dazim_mod.f90's dazim_assemble_G.
     # coo_to_host_s: what handing G itself to the host as the reference's triplets costs on top (the CalSurfG drop-in's surface).
     host_api = None
-    if world == 1 and not a.no_cpu:      # (--no-cpu: the timed steps only -- profile passes, A/B scripts)
+    full = a.full and not a.no_cpu and world == 1      # (the legs that --full adds, on a single GPU only)
+    if full:
         h_b = d_b.cpu().numpy()
         keepG = {}
 
@@ -920,7 +926,7 @@ def main():
         }
         if host_api is not None:
             out["value_host_api"] = host_api
-        if not a.no_cpu and world == 1:      # the CPU baseline is timed on rank 0 of the single-GPU run only
+        if full:      # the CPU baseline is timed on rank 0 of the single-GPU run only
             out["cpu_baseline"] = cpu_baseline(vel, scx, scz, per, field_of_ray, rcx, rcz, nfield, rays_per_field)
             try:
                 out["cpu_baseline"]["timed_small"] = timed_small_forward(ctx)

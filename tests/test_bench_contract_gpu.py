@@ -41,6 +41,15 @@ def test_bench_single_process():
     check(out.stdout)
 
 
+def test_bench_plain_run_leaves_the_full_legs_out():
+    """without --full a run is set-up, warm-up, the timed steps and the line: no host-array step, no CPU baseline"""
+    args = [t for t in ARGS if t != "--no-cpu"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = check(out.stdout)
+    assert not {"value_host_api", "cpu_baseline", "forward_wall_s_per_step", "speedup_vs_cpu_1core_forward"} & set(d)
+
+
 def test_bench_under_torchrun_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",

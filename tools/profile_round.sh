@@ -4,7 +4,7 @@
 #   1. two counter passes (FETCH_SIZE, WRITE_SIZE; counters only)  -> gpurun_out/pmc_<tag>.md + profiles/pmc_traffic_<workload>.json
 #      (bench.py quotes `traffic` from that json while the kernel sources are the ones it was measured on)
 #   2. rocprofv3 --kernel-trace --stats of a 3-step run            -> gpurun_out/kstats_<tag>.md
-#   3. the default bench.py run (with the CPU baseline)            -> gpurun_out/bench_<tag>.json
+#   3. a bench.py --full run (with the CPU baseline)              -> bench_<tag>.json in the output folder
 # Copy kstats_<tag>.md, pmc_<tag>.md, pmc_traffic_<tag>.json (as profiles/pmc_traffic_<workload>.json) and bench_<tag>.json into profiles/.
 tag=${1:-x}
 wl=${2:-s256}                       # workload (bench.py --workload): s256 (the metric), s128, s512
@@ -20,7 +20,7 @@ python tools/pmc_summary.py $out/pmc_fetch_$tag $out/pmc_write_$tag --json $out/
 cp $out/pmc_traffic_$tag.json $root/profiles/pmc_traffic_$wl.json
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $out/prof_$tag -o bench -- python $root/bench.py --workload $wl --no-cpu --steps 3 --warmup 1 > $out/prof_$tag.log 2>&1
-timeout 900 python $root/bench.py --workload $wl 2> $out/bench_$tag.log | tail -1 > $out/bench_$tag.json
+timeout 900 python $root/bench.py --workload $wl --full 2> $out/bench_$tag.log | tail -1 > $out/bench_$tag.json
 cd $root
 python tools/rocpd_summary.py $(find $out/prof_$tag -name "*results.db" | head -1) > $out/kstats_$tag.md
 # keep the merged-back scratch small: the raw traces stay on the box
