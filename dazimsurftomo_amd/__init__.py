@@ -301,6 +301,49 @@ class Context:
         n = (nx - 2) * (ny - 2) * (nz - 1) * (1 if lsen is None else 3)
         return SparseMatrix(self, h, nray, n, nnz.value), tpred, nb.value
 
+    def rays_build_G_maps(self, nx, ny, goxd, gozd, dvxd, dvzd, fields, scx, scz, period_idx, field_of_ray, rcx, rcz,
+                          azim=False, tpred=None):
+        """map rows of the per-period phase-velocity (and, with `azim`, 2-psi a1/a2) inversion: the rows of rays_build_G / the
+        joint mode with unit depth kernels and nz = 2, the Frechet values fdm (, fdmc, fdms) themselves, one column block per period
+        (column blk*kmax*ncell + (period_idx-1)*ncell + (jj-1)*nvx + kk-1).  Returns (G, tpred, n_boundary)."""
+        kmax = fields["veln"].shape[0]
+        nfield = int(scx.shape[0])
+        nray = int(rcx.shape[0])
+        if tpred is None:
+            if _is_torch(rcx):
+                import torch
+                tpred = torch.empty(nray, dtype=torch.float32, device=rcx.device)
+            else:
+                tpred = np.zeros(nray, np.float32)
+        boxes = fields["boxes"]
+        bptr = C.c_void_p(boxes.data_ptr()) if _is_torch(boxes) else C.cast(boxes, C.c_void_p)
+        h = C.c_void_p()
+        nnz = C.c_int64(0)
+        nb = C.c_int(0)
+        rc = self.lib.dazim_rays_build_G_maps(self._h, nx, ny, C.c_float(goxd), C.c_float(gozd), C.c_float(dvxd), C.c_float(dvzd),
+                                              kmax, int(bool(azim)), nfield, _ptr(scx), _ptr(scz), _ptr(period_idx),
+                                              _ptr(fields["veln"]), _ptr(fields["ttn"]), _ptr(fields["ttnr"]), _ptr(fields["nstsr"]),
+                                              bptr, C.c_int64(nray), _ptr(field_of_ray), _ptr(rcx), _ptr(rcz), _ptr(tpred),
+                                              C.byref(h), C.byref(nnz), C.byref(nb))
+        self._check(rc)
+        n = (nx - 2) * (ny - 2) * kmax * (3 if azim else 1)
+        return SparseMatrix(self, h, nray, n, nnz.value), tpred, nb.value
+
+    def phase_map_update(self, nx, ny, pv, dm, minc, maxc, azim):
+        """clamped update of the per-period maps (dazim_phase_map_update): pv[kmax][ny*nx] fp64 (the fmm_batch maps) and dm (c | a1 |
+        a2 blocks) are updated in place (numpy).  Returns (a1, a2, stats[nblock][kmax][3]); a1, a2 [kmax][ny-2][nx-2] or None."""
+        kmax = pv.shape[0]
+        assert pv.size == kmax * nx * ny and pv.flags.c_contiguous
+        ncell = (nx - 2) * (ny - 2)
+        nblock = 3 if azim else 1
+        assert pv.dtype == np.float64 and dm.dtype == np.float32 and len(dm) == ncell * kmax * nblock
+        a1 = np.zeros((kmax, ny - 2, nx - 2), np.float32) if azim else None
+        a2 = np.zeros((kmax, ny - 2, nx - 2), np.float32) if azim else None
+        st = np.zeros((nblock, kmax, 3), np.float32)
+        self._check(self.lib.dazim_phase_map_update(self._h, nx, ny, kmax, int(bool(azim)), _ptr(pv), _ptr(dm), C.c_float(minc),
+                                                    C.c_float(maxc), _ptr(a1), _ptr(a2), _ptr(st)))
+        return a1, a2, st
+
     def ray_paths(self):
         """ray geometries of the last rays_build_G call made with option rays.keep_paths = 1: a list of [nrp][2] arrays
         (colatitude, longitude in rad; receiver first, source last) -- the reference's raypath_refmdl_<T>s.dat content"""
@@ -401,6 +444,15 @@ class SparseMatrix:
         w = np.ascontiguousarray(weights, np.float32)
         m0, z0 = C.c_int64(0), C.c_int64(0)
         self.ctx._check(self.ctx.lib.dazim_csr_append_tikhonov(self.ctx._h, self._h, nx, ny, nz, len(w), _ptr(w)))
+        self.ctx._check(self.ctx.lib.dazim_csr_dims(self._h, C.byref(m0), None, C.byref(z0)))
+        self.m, self.nnz = m0.value, z0.value
+
+    def append_laplacian2d(self, nx, ny, weights):
+        """2-D regularisation rows of the per-period maps generated on the device (dazim_csr_append_laplacian2d): one block of
+        (nx-2)(ny-2) rows per weight, map b regularising columns b*ncell .."""
+        w = np.ascontiguousarray(weights, np.float32)
+        m0, z0 = C.c_int64(0), C.c_int64(0)
+        self.ctx._check(self.ctx.lib.dazim_csr_append_laplacian2d(self.ctx._h, self._h, nx, ny, len(w), _ptr(w)))
         self.ctx._check(self.ctx.lib.dazim_csr_dims(self._h, C.byref(m0), None, C.byref(z0)))
         self.m, self.nnz = m0.value, z0.value
 

@@ -249,7 +249,9 @@ __device__ __forceinline__ void cbar() { asm volatile("" ::: "memory"); }  // co
 // 4x4 block currently being updated is cached in registers, LPR cells per lane, and written back when the ray
 // moves to another B-spline cell (every ~10 steps), so every cell still sees its contributions in the
 // reference's order (fdm = r1 + fdm).
-template <bool EMIT, bool AZIM, bool TILED>
+// MAP: the rows of the per-period map inversion (dazim_rays_build_G_maps) -- the Frechet values fdm (, fdmc, fdms) themselves,
+// one column block per period: what the 3-D rows are with unit depth kernels and nz = 2, the period folded into the column.
+template <bool EMIT, bool AZIM, bool TILED, bool MAP>
 #ifndef DZ_RAYS_MINW
 #define DZ_RAYS_MINW 4
 #endif
@@ -703,6 +705,10 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
     long cnt = 0;
     const long rstart = EMIT ? A.rowptr[ray] : 0;
     const int nparpi = nvx * nvz * (A.nz - 1);
+    // column blocks: dVs | Gc | Gs of nparpi columns each, or (MAP) c | a1 | a2 of kmax maps each, this field's map at poff
+    const int nlay = MAP ? 1 : A.nz - 1;
+    const int bstride = MAP ? A.kmax * nvx * nvz : nparpi;
+    const int poff = MAP ? (A.period[f] - 1) * nvx * nvz : 0;
     const bool lovf = nlist > LC;                       // list did not fit: sweep the whole grid instead (rare)
     const int ntot = lovf ? nvz * nvx : nlist;
     long cntd = 0;
@@ -732,7 +738,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
 #ifdef DZ_RAYS_NOROWCACHE
     const bool rowcache = false;
 #else
-    const bool rowcache = !lovf && ntot <= RC * GP && A.skern != nullptr && !A.dense;
+    const bool rowcache = !lovf && ntot <= RC * GP && (MAP || A.skern != nullptr) && !A.dense;
 #endif
     if (rowcache) {
       int sidx[RC], cbase[RC], fidx[RC];
@@ -750,9 +756,9 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
         const float *fsrc = blk == 0 ? gfdm : (blk == 1 ? gfdmc : gfdms);
 #pragma unroll
         for (int i = 0; i < RC; i++) fdv[i] = (i * GP + gl < ntot) ? fsrc[fidx[i]] : 0.0f;
-        for (int k = 1; k <= A.nz - 1; k++) {
+        for (int k = 1; k <= nlay; k++) {
           const size_t sk = ((size_t)(k - 1) * A.kmax + kslot) * ncol;
-          const int nk = blk * nparpi + (k - 1) * nvz * nvx;
+          const int nk = blk * bstride + poff + (k - 1) * nvz * nvx;
 #pragma unroll
           for (int i = 0; i < RC; i++) {
             if (i * GP >= ntot) break;                    // (per ray: the lanes of a group leave together)
@@ -760,7 +766,8 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
             float rowv = 0.0f;
             bool keep = false;
             if (cell) {
-              if (blk == 0) rowv = (float)(A.skern[sk + sidx[i]] * (double)fdv[i]);
+              if (MAP) rowv = fdv[i];                     // (= (float)(1.0 * (double)fdv) and 1.0f * fdv of the unit kernels)
+              else if (blk == 0) rowv = (float)(A.skern[sk + sidx[i]] * (double)fdv[i]);
               else rowv = A.lsen[sk + sidx[i]] * fdv[i];
               keep = A.keep_small ? (rowv != 0.0f) : (fabsf(rowv) > FTOL);
             }
@@ -776,7 +783,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
       }
     } else
     for (int blk = 0; blk < NG; blk++)   // dVs | Gc | Gs column blocks (inv/CalSurfGAniso_Joint.f90:728-738)
-      for (int k = 1; k <= A.nz - 1; k++) {
+      for (int k = 1; k <= nlay; k++) {
         for (int base = 0; base < ntot; base += GP) {
           const int li = base + gl;
           bool keep = false, keepd = false;
@@ -787,7 +794,11 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
           if (cell) c = lovf ? li : s_list[li];
           const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
           if (cell && lovf) cell = fabsf(gfdm[kk * ldf + jj]) >= FTOL;
-          if (cell) {
+          if (cell && MAP) {
+            rowv = (blk == 0 ? gfdm : (blk == 1 ? gfdmc : gfdms))[kk * ldf + jj];
+            keep = A.keep_small ? (rowv != 0.0f) : (fabsf(rowv) > FTOL);
+            nn = blk * bstride + poff + (jj - 1) * nvx + kk;
+          } else if (cell) {
             const size_t si = ((size_t)(k - 1) * A.kmax + kslot) * ncol + (size_t)jj * (nvx + 2) + kk;
             if (blk == 0) {
               const float fd = gfdm[kk * ldf + jj];
@@ -819,7 +830,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
             }
             keep = A.keep_small ? (rowv != 0.0f) : (fabsf(rowv) > FTOL);
             if (EMIT && A.dense == 1) keep = keepd;
-            nn = blk * nparpi + (k - 1) * nvz * nvx + (jj - 1) * nvx + kk;  // 1-based column of the reference
+            nn = blk * bstride + (k - 1) * nvz * nvx + (jj - 1) * nvx + kk;  // 1-based column of the reference
           }
           if (!EMIT && A.dense == 2) cntd += __popc((unsigned)((__ballot(keepd) >> gmask_shift) & GMASK));
           const unsigned m = (unsigned)((__ballot(keep) >> gmask_shift) & GMASK);
@@ -854,9 +865,14 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
                                   const float *ttn_u, const float *ttnr_u, const int *nstsr_u,
                                   const dazim_refbox *boxes_u, int64_t nray, const int *field_u, const float *rcx_u,
                                   const float *rcz_u, const double *svs_u, const double *svp_u, const double *srho_u,
-                                  const float *lsen_u, float *dsurf_u, dazim_csr **G, int64_t *nnz_out, int *n_boundary) {
+                                  const float *lsen_u, float *dsurf_u, dazim_csr **G, int64_t *nnz_out, int *n_boundary,
+                                  bool map = false, bool azim = false) {
   if (!ctx || !G) return DAZIM_E_BAD_ARG;
-  const bool joint = lsen_u != nullptr;
+  // map mode (dazim_rays_build_G_maps): no model, no depth kernels; nz = 2 stands for the one "layer" of a map
+  const bool joint = map ? azim : lsen_u != nullptr;
+  if (map) nz = 2;
+  if (map && ctx->opts.count("rays.dense_twin") && ctx->opts["rays.dense_twin"])
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G_maps: option rays.dense_twin serves the 3-D program's diagnostics only");
   dazim_geom g;
   if (dazim_geometry(nx, ny, goxd, gozd, dvxd, dvzd, &g)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad grid");
   if (nray < 0 || nfield < 1 || nz < 2 || kmax < 1 || (size_t)g.nvx * g.nvz > 65535u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_rays_build_G");
@@ -866,8 +882,8 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   const bool tiled = ttn_u == nullptr;
   if (tiled && (!ctx->fields.tiled || ctx->fields.nfield != nfield || ctx->fields.nnx != g.nnx || ctx->fields.nnz != g.nnz))
     return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G: ttn is NULL and the last dazim_fmm_batch call did not keep %d fields of this grid inside the library (call it with ttn = NULL)", nfield);
-  if (!vels_u || !scx_u || !scz_u || !period_u || !veln_u || !ttnr_u || !nstsr_u || !boxes_u || !svs_u || !svp_u ||
-      !srho_u || !dsurf_u || (nray > 0 && (!field_u || !rcx_u || !rcz_u)))
+  if (!scx_u || !scz_u || !period_u || !veln_u || !ttnr_u || !nstsr_u || !boxes_u || !dsurf_u ||
+      (!map && (!vels_u || !svs_u || !svp_u || !srho_u)) || (nray > 0 && (!field_u || !rcx_u || !rcz_u)))
     return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G: NULL array (the refined fields ttnr, nstsr and boxes of dazim_fmm_batch are required)");
   DZ_HIP(hipSetDevice(ctx->device));
   // An asynchronous eikonal call (option fmm.async) is still marching: the count pass goes to the context's third stream, where its
@@ -915,7 +931,7 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   DzBuf<dazim_refbox> boxes;
   DzBuf<double> svs, svp, srho;
   int rc;
-  if ((rc = vels.init(ctx, vels_u, (size_t)nz * ncol, true, false))) return rc;
+  if (!map && (rc = vels.init(ctx, vels_u, (size_t)nz * ncol, true, false))) return rc;
   if ((rc = scx.init(ctx, scx_u, nfield, true, false))) return rc;
   if ((rc = scz.init(ctx, scz_u, nfield, true, false))) return rc;
   if ((rc = period.init(ctx, period_u, nfield, true, false))) return rc;
@@ -929,12 +945,12 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   if ((rc = rcx.init(ctx, rcx_u, nray, true, false))) return rc;
   if ((rc = rcz.init(ctx, rcz_u, nray, true, false))) return rc;
   const size_t nk = (size_t)nz * kmax * ncol;
-  if ((rc = svs.init(ctx, svs_u, nk, true, false))) return rc;
-  if ((rc = svp.init(ctx, svp_u, nk, true, false))) return rc;
-  if ((rc = srho.init(ctx, srho_u, nk, true, false))) return rc;
+  if (!map && ((rc = svs.init(ctx, svs_u, nk, true, false)) || (rc = svp.init(ctx, svp_u, nk, true, false)) ||
+                (rc = srho.init(ctx, srho_u, nk, true, false))))
+    return rc;
   if ((rc = dsurf.init(ctx, dsurf_u, nray, false, true))) return rc;
   DzBuf<float> lsen;
-  if (joint && (rc = lsen.init(ctx, lsen_u, (size_t)(nz - 1) * kmax * ncol, true, false))) return rc;
+  if (joint && !map && (rc = lsen.init(ctx, lsen_u, (size_t)(nz - 1) * kmax * ncol, true, false))) return rc;
   // index conventions follow the reference: periods and kernel slots 1-based (periods(srcnum,knumi), knumi), field_of_ray 0-based
   if ((rc = dz_check_range(ctx, period.dev, nfield, 1, kmax, "period_idx"))) return rc;
   if ((rc = dz_check_range(ctx, kidx.dev, nfield, 1, kmax, "kernel_idx"))) return rc;
@@ -952,13 +968,14 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
     A.tslot = ctx->fields.tslot; A.tsh = ctx->fields.tsh; A.fstride = ctx->fields.stride;
   }
   ctx->ksec["rays.tiled_fields"] = tiled ? 1.0 : 0.0;
+  ctx->ksec["rays.map"] = map ? 1.0 : 0.0;
   ctx->ksec["rays.overlap"] = overlap ? 1.0 : 0.0;
   A.fdone = overlap ? ctx->fields.fdone : nullptr;
   A.defer_mark = nullptr;
   A.max_quads = 0;
   A.sweeps = 1;
   A.nstsr = nstsr.dev; A.boxes = boxes.dev; A.vels = vels.dev; A.svs = svs.dev; A.svp = svp.dev; A.srho = srho.dev;
-  A.lsen = joint ? lsen.dev : nullptr;
+  A.lsen = joint && !map ? lsen.dev : nullptr;
   A.skern = nullptr;
   {
     const unsigned d = (unsigned)g.nvx;
@@ -966,7 +983,7 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
     for (unsigned c = 0; c < 65536u; c++)   // (cell ids are 16-bit: the identity is checked for all of them, once per call)
       if ((unsigned)(((unsigned long long)c * A.nvx_magic) >> 32) != c / d) return dz_fail(ctx, DAZIM_E_BAD_ARG, "internal: reciprocal of nvx");
   }
-  if (!(ctx->opts.count("rays.skern") && !ctx->opts["rays.skern"])) {   // (option rays.skern = 0: every entry from the three kernels)
+  if (!map && !(ctx->opts.count("rays.skern") && !ctx->opts["rays.skern"])) {   // (option rays.skern = 0: every entry from the three kernels)
     void *pk;
     if ((rc = dz_scratch(ctx, "rays.skern", nk * sizeof(double), &pk))) return rc;
     hipLaunchKernelGGL(k_row_kernels, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, (long)nk, kmax, (long)ncol,
@@ -1041,7 +1058,8 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   // the caller may announce rows it is going to append (regularisation): the CSR arrays then get that much slack and
   // dazim_csr_append_coo writes behind the ray rows instead of reallocating and copying the matrix
   // By default: one regularisation row per model parameter with the 7-point stencil of inv/TikhRegul.f90 (a few MB).
-  int64_t res_rows = (int64_t)g.nvx * g.nvz * (nz - 1) * (joint ? 3 : 1), res_nnz = 7 * res_rows;
+  // (map mode: the 5-point stencil of dazim_csr_append_laplacian2d on every map)
+  int64_t res_rows = (int64_t)g.nvx * g.nvz * (map ? kmax : nz - 1) * (joint ? 3 : 1), res_nnz = (map ? 5 : 7) * res_rows;
   if (ctx->opts.count("csr.reserve_rows") && ctx->opts["csr.reserve_rows"] > res_rows) res_rows = ctx->opts["csr.reserve_rows"];
   if (ctx->opts.count("csr.reserve_nnz") && ctx->opts["csr.reserve_nnz"] > res_nnz) res_nnz = ctx->opts["csr.reserve_nnz"];
   { void *pp; if ((rc = dz_big_get(ctx, (size_t)(m + res_rows + 1) * 8, &pp))) return rc; rowptr = (int64_t *)pp; }
@@ -1054,14 +1072,18 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   A.val = nullptr;
   A.col = nullptr;
   const size_t lds = (size_t)A.lcap * 2 * RPW_MAX + 16;   // one cell list per ray of the wavefront
-  // the kernel of each pass: count / emit x iso / joint x column-major / tiled fields
+  // the kernel of each pass: count / emit x iso / joint x column-major / tiled fields x 3-D / map rows
   auto kern = [&](bool emit) -> const void * {
-    if (emit) {
-      if (joint) return tiled ? (const void *)rays_kernel<true, true, true> : (const void *)rays_kernel<true, true, false>;
-      return tiled ? (const void *)rays_kernel<true, false, true> : (const void *)rays_kernel<true, false, false>;
-    }
-    if (joint) return tiled ? (const void *)rays_kernel<false, true, true> : (const void *)rays_kernel<false, true, false>;
-    return tiled ? (const void *)rays_kernel<false, false, true> : (const void *)rays_kernel<false, false, false>;
+    static const void *const tab[16] = {
+        (const void *)rays_kernel<false, false, false, false>, (const void *)rays_kernel<false, false, false, true>,
+        (const void *)rays_kernel<false, false, true, false>,  (const void *)rays_kernel<false, false, true, true>,
+        (const void *)rays_kernel<false, true, false, false>,  (const void *)rays_kernel<false, true, false, true>,
+        (const void *)rays_kernel<false, true, true, false>,   (const void *)rays_kernel<false, true, true, true>,
+        (const void *)rays_kernel<true, false, false, false>,  (const void *)rays_kernel<true, false, false, true>,
+        (const void *)rays_kernel<true, false, true, false>,   (const void *)rays_kernel<true, false, true, true>,
+        (const void *)rays_kernel<true, true, false, false>,   (const void *)rays_kernel<true, true, false, true>,
+        (const void *)rays_kernel<true, true, true, false>,    (const void *)rays_kernel<true, true, true, true>};
+    return tab[(emit ? 8 : 0) + (joint ? 4 : 0) + (tiled ? 2 : 0) + (map ? 1 : 0)];
   };
   auto launch = [&](bool emit, const RayArgs &R, long nwg_) -> int {
     RayArgs args = R;
@@ -1265,7 +1287,7 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   if ((rc = dsurf.finish())) return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   if (err) return err;
-  const int64_t n = (int64_t)g.nvx * g.nvz * (nz - 1) * (joint ? 3 : 1);
+  const int64_t n = (int64_t)g.nvx * g.nvz * (map ? kmax : nz - 1) * (joint ? 3 : 1);
   arrays.keep = true;   // adopted (dz_csr_adopt_cap frees them itself if it fails)
   if ((rc = dz_csr_adopt_cap(ctx, m, n, nnz, rowptr, col, val, m + res_rows, cap_nnz, G))) return rc;
   if (twin) {
@@ -1304,6 +1326,20 @@ extern "C" int dazim_rays_build_G_joint(dazim_ctx *ctx, int nx, int ny, int nz, 
   if (!lsen) return dz_fail(ctx, DAZIM_E_BAD_ARG, "joint mode needs Lsen_Gsc");
   return rays_build_impl(ctx, nx, ny, nz, goxd, gozd, dvxd, dvzd, kmax, vels, nfield, scx, scz, period, kidx, veln, ttn, ttnr,
                          nstsr, boxes, nray, field, rcx, rcz, svs, svp, srho, lsen, dsurf, G, nnz_out, n_boundary);
+}
+
+// Map rows (the per-period phase-velocity / 2-psi map inversion): the same receiver loop with the Frechet values themselves as the
+// row entries -- fdm (, fdmc, fdms when azim) -- in one column block per period: what dazim_rays_build_G / _joint emit with unit
+// depth kernels (sen_vs = 1, sen_vp = sen_rho = 0, Lsen_Gsc = 1) and nz = 2, bit for bit, with the period folded into the column
+// blk*kmax*ncell + (period_idx-1)*ncell + (jj-1)*nvx + kk-1.  No model, no depth-kernel tables.
+extern "C" int dazim_rays_build_G_maps(dazim_ctx *ctx, int nx, int ny, float goxd, float gozd, float dvxd, float dvzd, int kmax,
+                                       int azim, int nfield, const float *scx, const float *scz, const int *period,
+                                       const float *veln, const float *ttn, const float *ttnr, const int *nstsr,
+                                       const dazim_refbox *boxes, int64_t nray, const int *field, const float *rcx,
+                                       const float *rcz, float *dsurf, dazim_csr **G, int64_t *nnz_out, int *n_boundary) {
+  return rays_build_impl(ctx, nx, ny, 2, goxd, gozd, dvxd, dvzd, kmax, nullptr, nfield, scx, scz, period, nullptr, veln, ttn, ttnr,
+                         nstsr, boxes, nray, field, rcx, rcz, nullptr, nullptr, nullptr, nullptr, dsurf, G, nnz_out, n_boundary,
+                         true, azim != 0);
 }
 
 // The ray geometries of the last dazim_rays_build_G[_joint] call made with option "rays.keep_paths" = 1: what the reference

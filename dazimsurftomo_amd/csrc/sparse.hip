@@ -1298,6 +1298,39 @@ __global__ void k_tikh_fill(int64_t r0, int64_t nrow, int maxvp, int nvx, int nv
     }
   }
 }
+// The 2-D analogue for the per-period maps (dazim_csr_append_laplacian2d): rows in map, j, i order; a cell on an edge of the map
+// gets 2w, an inner cell the 5-point Laplacian 4w, -w x 4 (ascending columns)
+__device__ __forceinline__ bool lap2d_edge(int cell, int nvx, int nvz) {
+  const int j = cell / nvx, i = cell - j * nvx;
+  return i == 0 || i == nvx - 1 || j == 0 || j == nvz - 1;
+}
+__global__ void k_lap2d_count(int64_t nrow, int ncell, int nvx, int nvz, long *cnt) {
+  const int64_t r = (int64_t)blockIdx.x * VB + threadIdx.x;
+  if (r > nrow) return;
+  cnt[r] = r == nrow ? 0 : (lap2d_edge((int)(r % ncell), nvx, nvz) ? 1 : 5);
+}
+__global__ void k_lap2d_fill(int64_t nrow, int ncell, int nvx, int nvz, const long *off, int64_t nnz0, const float *__restrict__ w,
+                             int64_t *__restrict__ rowptr, int *__restrict__ col, float *__restrict__ val) {
+  const int64_t r = (int64_t)blockIdx.x * VB + threadIdx.x;
+  if (r > nrow) return;
+  rowptr[r] = nnz0 + off[r];
+  if (r == nrow) return;
+  const int b = (int)(r / ncell), cell = (int)(r - (int64_t)b * ncell);
+  const float wt = w[b];
+  const int c = b * ncell + cell;
+  const int64_t p = nnz0 + off[r];
+  if (lap2d_edge(cell, nvx, nvz)) {
+    col[p] = c;
+    val[p] = 2.0f * wt;
+  } else {
+    const int d[5] = {-nvx, -1, 0, 1, nvx};
+#pragma unroll
+    for (int q = 0; q < 5; q++) {
+      col[p + q] = c + d[q];
+      val[p + q] = q == 2 ? 4.0f * wt : -1.0f * wt;
+    }
+  }
+}
 // res = obst - dsyn ; rel = |res / obst|   (inv/Main_Jt.f90:432-435, inv/CalSigamNorm.f90:20-23)
 __global__ void k_residual(int64_t n, const float *obst, const float *dsyn, float *res, float *rel) {
   for (int64_t i = (int64_t)blockIdx.x * VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB) {
@@ -1393,6 +1426,28 @@ __global__ void k_model_update(int nx, int ny, int nzm1, int joint, float *vs, f
   if (joint) {
     if (gc) gc[ii] = dv[maxvp + ii];
     if (gs) gs[ii] = dv[2 * maxvp + ii];
+  }
+}
+// the same update on the per-period maps (dazim_phase_map_update): dm = c | a1 | a2 blocks of kmax maps of ncell cells, pv
+// [kmax][ny][nx] fp64 (the eikonal solver's maps) updated on the inner vertices in fp32 like vs above; the boundary ring is kept
+__global__ void k_map_update(int nx, int ny, int kmax, int azim, double *pv, float *dm, float minc, float maxc, float *a1, float *a2) {
+  const int nvx = nx - 2, nvz = ny - 2, nmap = nvx * nvz * kmax;
+  const int ii = blockIdx.x * VB + threadIdx.x;
+  if (ii >= nmap) return;
+  const int k = ii / (nvx * nvz), r = ii - k * nvx * nvz, j = r / nvx, i = r - j * nvx;
+  float p = dm[ii];
+  if (p >= 0.500f) p = 0.500f;
+  if (p <= -0.500f) p = -0.500f;
+  if (fabsf(p) < 1e-5f) p = 0.0f;
+  dm[ii] = p;
+  const size_t iv = ((size_t)k * ny + (j + 1)) * nx + (i + 1);
+  float v = (float)pv[iv] + p;
+  if (v < minc) v = minc;
+  if (v > maxc) v = maxc;
+  pv[iv] = (double)v;
+  if (azim) {
+    if (a1) a1[ii] = dm[nmap + ii];
+    if (a2) a2[ii] = dm[2 * nmap + ii];
   }
 }
 // per (block, depth) min, max and sum |.| of the update (the log lines of inv/Main_Jt.f90:621-666): one workgroup each
@@ -2145,6 +2200,9 @@ int dazim_lsmr(dazim_ctx *ctx, const dazim_csr *A, const float *b_u, float damp,
                            normr_o, normAr_o, normx_o, nullptr, 0, nullptr);
 }
 
+static int append_stencil_rows(dazim_ctx *ctx, dazim_csr *A, bool lap2d, int nvx, int nvz, int nzm1, int64_t maxvp, int64_t row_lo,
+                               int64_t nrow, int nblock, const float *w_host, float *dw, long *cnt, long *off);
+
 // ---- N4 ------------------------------------------------------------------------------------------------------------------------
 // = TikhonovRegularization / TikhRegul_joint (inv/TikhRegul.f90:2-104, :107-209): nblock*maxvp rows appended to the resident
 // matrix, generated on the device (block b regularises columns b*maxvp+1.., weight w[b])
@@ -2170,9 +2228,28 @@ int dazim_csr_append_tikhonov_rows(dazim_ctx *ctx, dazim_csr *A, int nx, int ny,
   if ((rc = dz_scratch(ctx, "tikh.w", 64 * 4, &p))) return rc;
   float *dw = (float *)p;
   if (nblock > 64) return dz_fail(ctx, DAZIM_E_BAD_ARG, "too many regularisation blocks");
+  return append_stencil_rows(ctx, A, false, nvx, nvz, nzm1, maxvp, row_lo, nrow, nblock, w_host, dw, cnt, off);
+}
+
+// the generated regularisation rows [row_lo, row_lo + nrow) appended to A: in place when A has room for them, else into new arrays.
+// lap2d: the 2-D maps' 5-point rows (k_lap2d_*, maxvp = ncell, row_lo 0), else the 3-D 7-point rows (k_tikh_*)
+static int append_stencil_rows(dazim_ctx *ctx, dazim_csr *A, bool lap2d, int nvx, int nvz, int nzm1, int64_t maxvp, int64_t row_lo,
+                               int64_t nrow, int nblock, const float *w_host, float *dw, long *cnt, long *off) {
+  int rc;
+  void *p;
   DZ_HIP(hipMemcpyAsync(dw, w_host, (size_t)nblock * 4, hipMemcpyHostToDevice, ctx->stream));
   const unsigned nb = (unsigned)((nrow + 1 + VB - 1) / VB);
-  hipLaunchKernelGGL(k_tikh_count, dim3(nb), dim3(VB), 0, ctx->stream, row_lo, nrow, (int)maxvp, nvx, nvz, nzm1, cnt);
+  if (lap2d)
+    hipLaunchKernelGGL(k_lap2d_count, dim3(nb), dim3(VB), 0, ctx->stream, nrow, (int)maxvp, nvx, nvz, cnt);
+  else
+    hipLaunchKernelGGL(k_tikh_count, dim3(nb), dim3(VB), 0, ctx->stream, row_lo, nrow, (int)maxvp, nvx, nvz, nzm1, cnt);
+  auto fill = [&](int64_t *rowptr, int *col, float *val) {
+    if (lap2d)
+      hipLaunchKernelGGL(k_lap2d_fill, dim3(nb), dim3(VB), 0, ctx->stream, nrow, (int)maxvp, nvx, nvz, off, A->nnz, dw, rowptr, col, val);
+    else
+      hipLaunchKernelGGL(k_tikh_fill, dim3(nb), dim3(VB), 0, ctx->stream, row_lo, nrow, (int)maxvp, nvx, nvz, nzm1, off, A->nnz, dw,
+                         rowptr, col, val);
+  };
   size_t tb = 0;
   DZ_HIP(rocprim::exclusive_scan(nullptr, tb, cnt, off, 0l, (size_t)(nrow + 1), rocprim::plus<long>(), ctx->stream));
   if ((rc = dz_scratch(ctx, "tikh.scan", tb + 256, &p))) return rc;
@@ -2184,8 +2261,7 @@ int dazim_csr_append_tikhonov_rows(dazim_ctx *ctx, dazim_csr *A, int nx, int ny,
   if (nz2 > 0xfffffff0ll) return dz_fail(ctx, DAZIM_E_NNZ_OVERFLOW, "too many stored entries");
   if (A->cap_m >= m2 && A->cap_nnz >= nz2) {   // dazim_rays_build_G left room for these rows: generate them behind the ray rows
     const int64_t nnz1 = A->nnz;
-    hipLaunchKernelGGL(k_tikh_fill, dim3(nb), dim3(VB), 0, ctx->stream, row_lo, nrow, (int)maxvp, nvx, nvz, nzm1, off, A->nnz, dw,
-                       A->rowptr + A->m, A->col, A->val);
+    fill(A->rowptr + A->m, A->col, A->val);
     DZ_HIP(hipGetLastError());
     A->m = m2;
     A->nnz = nz2;
@@ -2203,8 +2279,7 @@ int dazim_csr_append_tikhonov_rows(dazim_ctx *ctx, dazim_csr *A, int nx, int ny,
   DZ_HIP(hipMemcpyAsync(rowptr, A->rowptr, (size_t)A->m * 8, hipMemcpyDeviceToDevice, ctx->stream));
   DZ_HIP(hipMemcpyAsync(col, A->col, (size_t)A->nnz * 4, hipMemcpyDeviceToDevice, ctx->stream));
   DZ_HIP(hipMemcpyAsync(val, A->val, (size_t)A->nnz * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_tikh_fill, dim3(nb), dim3(VB), 0, ctx->stream, row_lo, nrow, (int)maxvp, nvx, nvz, nzm1, off, A->nnz, dw,
-                     rowptr + A->m, col, val);
+  fill(rowptr + A->m, col, val);
   DZ_HIP(hipGetLastError());
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   dz_big_put(ctx, A->rowptr);
@@ -2217,6 +2292,24 @@ int dazim_csr_append_tikhonov_rows(dazim_ctx *ctx, dazim_csr *A, int nx, int ny,
   if ((rc = invalidate_transpose(A))) return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+// 2-D regularisation of the per-period maps (the map analogue of dazim_csr_append_tikhonov): nmap * (nx-2)(ny-2) rows, map b
+// regularising columns b*ncell .. with weight w[b] (host array): 2w on the edge cells, the 5-point Laplacian 4w, -w x 4 inside.
+int dazim_csr_append_laplacian2d(dazim_ctx *ctx, dazim_csr *A, int nx, int ny, int nmap, const float *w_host) {
+  if (!ctx || !A || !w_host || nmap < 1 || nx < 3 || ny < 3) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_csr_append_laplacian2d");
+  const int nvx = nx - 2, nvz = ny - 2;
+  const int64_t ncell = (int64_t)nvx * nvz, nrow = ncell * nmap;
+  if (nrow > A->n || nrow > 0x7ffffff0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "regularisation maps do not fit the %lld columns", (long long)A->n);
+  DZ_HIP(hipSetDevice(ctx->device));
+  int rc;
+  void *p;
+  if ((rc = dz_scratch(ctx, "tikh.cnt", (size_t)(nrow + 1) * 8, &p))) return rc;
+  long *cnt = (long *)p;
+  if ((rc = dz_scratch(ctx, "tikh.off", (size_t)(nrow + 1) * 8, &p))) return rc;
+  long *off = (long *)p;
+  if ((rc = dz_scratch(ctx, "lap2d.w", (size_t)nmap * 4, &p))) return rc;
+  return append_stencil_rows(ctx, A, true, nvx, nvz, 1, ncell, 0, nrow, nmap, w_host, (float *)p, cnt, off);
 }
 
 // = residuals + CalDdatSigma + data weights + weighted right-hand side + row scaling of G (inv/Main_Jt.f90:432-469,
@@ -2321,6 +2414,36 @@ int dazim_model_update(dazim_ctx *ctx, int nx, int ny, int nz, int joint, float 
     DZ_HIP(hipMemcpyAsync(stats, p, (size_t)nblock * nzm1 * 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
   if ((rc = vs.finish()) || (rc = dv.finish()) || (rc = gc.finish()) || (rc = gs.finish())) return rc;
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// the clamped update of the per-period maps (dazim_model_update on the map layout): dm [kmax*ncell, or 3*kmax*ncell when azim]
+// in/out (c block clamped to +-0.5 and zeroed below 1e-5), pv [kmax][ny][nx] fp64 in/out (inner vertices += dc in fp32, clamped to
+// [minc, maxc]; the boundary ring kept), a1, a2 [kmax][ny-2][nx-2] out (azim; nullable).  stats (host, nullable): [nblock][kmax][3]
+// = min, max, sum |.| of the update per block and period.
+int dazim_phase_map_update(dazim_ctx *ctx, int nx, int ny, int kmax, int azim, double *pv_u, float *dm_u, float minc, float maxc,
+                           float *a1_u, float *a2_u, float *stats) {
+  if (!ctx || !pv_u || !dm_u || nx < 3 || ny < 3 || kmax < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_phase_map_update");
+  DZ_HIP(hipSetDevice(ctx->device));
+  const int ncell = (nx - 2) * (ny - 2), nmap = ncell * kmax, nblock = azim ? 3 : 1;
+  DzBuf<double> pv;
+  DzBuf<float> dm, a1, a2;
+  int rc;
+  if ((rc = pv.init(ctx, pv_u, (size_t)nx * ny * kmax, true, true)) || (rc = dm.init(ctx, dm_u, (size_t)nmap * nblock, true, true)) ||
+      (rc = a1.init(ctx, a1_u, azim ? nmap : 0, false, true)) || (rc = a2.init(ctx, a2_u, azim ? nmap : 0, false, true)))
+    return rc;
+  hipLaunchKernelGGL(k_map_update, dim3((nmap + VB - 1) / VB), dim3(VB), 0, ctx->stream, nx, ny, kmax, azim ? 1 : 0, pv.dev, dm.dev,
+                     minc, maxc, azim ? a1.dev : nullptr, azim ? a2.dev : nullptr);
+  DZ_HIP(hipGetLastError());
+  if (stats) {
+    void *p;
+    if ((rc = dz_scratch(ctx, "mu.stats", (size_t)nblock * kmax * 3 * 4, &p))) return rc;
+    hipLaunchKernelGGL(k_update_stats, dim3(nblock * kmax), dim3(VB), 0, ctx->stream, ncell, dm.dev, (float *)p);
+    DZ_HIP(hipGetLastError());
+    DZ_HIP(hipMemcpyAsync(stats, p, (size_t)nblock * kmax * 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if ((rc = pv.finish()) || (rc = dm.finish()) || (rc = a1.finish()) || (rc = a2.finish())) return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }

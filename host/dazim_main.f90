@@ -71,24 +71,7 @@ program DAzimSurfTomo_amd
   if (.not. ex) stop 'unable to open the inputfile'
 
   ! ---- para.in, inv/Main_Jt.f90:158-214 -------------------------------------------------------------
-  open (10, file=inputfile, status='old', action='read')
-  read (10, '(a30)') dummy
-  read (10, '(a30)') dummy
-  read (10, '(a30)') dummy
-  read (10, *) datafile
-  read (10, *) nx, ny, nz
-  read (10, *) goxd, gozd
-  read (10, *) dvxd, dvzd
-  read (10, *) minthk
-  read (10, *) Minvel, Maxvel
-  read (10, *) nsrc
-  read (10, *) spfra
-  read (10, *) maxiter
-  read (10, *) iso_mod
-  read (10, '(a30)') dummy
-  read (10, *) weightVs
-  read (10, *) weightGcs
-  read (10, *) damp
+  include 'read_para.inc'
   write (*, *) 'input Rayleigh wave phase velocity data file:'
   write (*, '(a)') datafile
   write (*, *) 'model origin:latitude,longitue'
@@ -106,14 +89,9 @@ program DAzimSurfTomo_amd
   write (*, *) 'damping'
   write (*, '(f8.1)') damp
   if (nz <= 1) stop 'error nz value.'
-  read (10, '(a30)') dummy
-  read (10, *) kmaxRc
   write (*, *) 'number of period'
   write (*, '(i6)') kmaxRc
   if (kmaxRc <= 0) stop 'Can only deal with Rayleigh wave phase velocity data!'
-  allocate (tRc(kmaxRc))
-  read (10, *) (tRc(i), i=1, kmaxRc)
-  close (10)
   write (logfile, '(a,a)') trim(inputfile), '_inv.log'
   open (66, file=logfile)
   write (66, *)
@@ -133,65 +111,7 @@ program DAzimSurfTomo_amd
   kmax = kmaxRc
 
   ! ---- traveltime data file, inv/Main_Jt.f90:240-318 -------------------------------------------------
-  inquire (file=datafile, exist=ex)
-  if (.not. ex) then
-    write (66, '(a)') 'unable to open the datafile'
-    close (66)
-    stop 'unable to open the datafile'
-  end if
-  write (*, *) 'begin load data file.....'
-  allocate (scxf(nsrc, kmax), sczf(nsrc, kmax), rcxf(nrc, nsrc, kmax), rczf(nrc, nsrc, kmax))
-  allocate (periods(nsrc, kmax), nrc1(nsrc, kmax), nsrc1(kmax))
-  scxf = 0; sczf = 0; rcxf = 0; rczf = 0; periods = 0; nrc1 = 0; nsrc1 = 0
-  ! two passes: count the data lines, then fill (the reference sizes obst by nrc*nsrc*kmax instead)
-  open (87, file=datafile, status='old')
-  dall = 0
-  do
-    read (87, '(a)', iostat=err) line
-    if (err /= 0) exit
-    if (line(1:1) /= '#') dall = dall + 1
-  end do
-  rewind (87)
-  allocate (obst(dall), dist(dall))
-  dall = 0; istep = 0; istep1 = 0; knum = 0; knumo = 12345
-  do
-    read (87, '(a)', iostat=err) line
-    if (err /= 0) exit
-    if (line(1:1) == '#') then
-      read (line, *) str1, sta1_lat, sta1_lon, period, wavetp, veltp
-      if (wavetp == 2 .and. veltp == 0) knum = period
-      if (wavetp == 2 .and. veltp == 1) stop 'can not deal with Rayleigh wave group data'
-      if (wavetp == 1 .and. veltp == 0) stop 'can not deal with Love wave phase data'
-      if (wavetp == 1 .and. veltp == 1) stop 'can not deal with Love wave group data'
-      if (knum < 1 .or. knum > kmax) stop 'period index in the data file exceeds kmaxRc'
-      if (knum /= knumo) istep = 0
-      istep = istep + 1
-      if (istep > nsrc) stop 'more sources per period than para.in allows: increase max(sources, receivers)'
-      istep1 = 0
-      sta1_lat = (90.0 - sta1_lat)*pi/180.0
-      sta1_lon = sta1_lon*pi/180.0
-      scxf(istep, knum) = sta1_lat
-      sczf(istep, knum) = sta1_lon
-      periods(istep, knum) = period
-      nsrc1(knum) = istep
-      knumo = knum
-    else
-      read (line, *) sta2_lat, sta2_lon, velvalue
-      istep1 = istep1 + 1
-      if (istep1 > nrc) stop 'more receivers per source than para.in allows: increase max(sources, receivers)'
-      dall = dall + 1
-      sta2_lat = (90.0 - sta2_lat)*pi/180.0
-      sta2_lon = sta2_lon*pi/180.0
-      rcxf(istep1, istep, knum) = sta2_lat
-      rczf(istep1, istep, knum) = sta2_lon
-      call great_circle(sta1_lat, sta1_lon, sta2_lat, sta2_lon, dist1)
-      dist(dall) = dist1
-      obst(dall) = dist1/velvalue
-      nrc1(istep, knum) = istep1
-    end if
-  end do
-  close (87)
-  write (*, '(a,i7)') ' Number of all measurements', dall
+  include 'read_data.inc'
 
   maxvp = (nx - 2)*(ny - 2)*(nz - 1)
   maxnar = int(spfra*real(dall)*real(nx)*real(ny)*real(nz)*3.0, 8)     ! sparsity fraction, inv/Main_Jt.f90:324
@@ -203,15 +123,7 @@ program DAzimSurfTomo_amd
   gcf = 0; gsf = 0; Lsen_Gsc = 0
 
   ! ---- initial model, inv/Main_Jt.f90:346-356 -----------------------------------------------------------
-  open (11, file='MOD', status='old')
-  vsf = 0
-  read (11, *) (depz(i), i=1, nz)
-  do k = 1, nz
-    do j = 1, ny
-      read (11, *) (vsf(i, j, k), i=1, nx)
-    end do
-  end do
-  close (11)
+  include 'read_mod.inc'
   write (*, *) ' grid points in depth direction:(km)'
   write (*, '(50f7.2)') depz
 
@@ -539,18 +451,7 @@ contains
     tk0 = tk1
   end subroutine
 
-  ! great-circle distance on a 6371 km sphere from colatitude/longitude in radians (haversine, fp32); inv/delsph.f90:1
-  subroutine great_circle(colat1, lon1, colat2, lon2, del)
-    real, intent(in) :: colat1, lon1, colat2, lon2
-    real, intent(out) :: del
-    real :: dlat, dlon, lat1, lat2, a
-    dlat = colat2 - colat1
-    dlon = lon2 - lon1
-    lat1 = pi/2 - colat1
-    lat2 = pi/2 - colat2
-    a = sin(dlat/2)*sin(dlat/2) + sin(dlon/2)*sin(dlon/2)*cos(lat1)*cos(lat2)
-    del = 6371.0*(2*atan2(sqrt(a), sqrt(1 - a)))
-  end subroutine
+  include 'great_circle.inc'
 
   ! scaled 2-norm like the reference's dnrm2 (inv/lsmrblas.f90:247)
   real function nrm2(nn, x)

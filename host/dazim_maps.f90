@@ -1,0 +1,205 @@
+! dazim_maps.f90 -- SurfPhaseMaps_amd: per-period Rayleigh phase-velocity maps and 2-psi anisotropy maps inverted from the data of
+! the 3-D inversion program, period by period in one system, on one MI355X.
+!
+!   SurfPhaseMaps_amd para.in [weight_c [weight_a]]
+!
+! Inputs: the unchanged para.in, traveltime data file and MOD of DAzimSurfTomo_amd (the same readers: read_para.inc,
+! read_data.inc, read_mod.inc).  Starting maps: MOD's dispersion curves (dazim_dispersion_kernels without kernels), the 3-D
+! program's own first-iteration pvRc.  Each of para.in's iterations: eikonal fields on the current maps, map rows
+! (dazim_rays_build_G_maps: dt = fdm.dc + fdmc.a1 + fdms.a2, one column block per period), CalDdatSigma weights
+! (dazim_weight_data), 2-D regularisation (dazim_csr_append_laplacian2d: weight_c on the c maps, weight_a on the a1 / a2 maps;
+! defaults para.in's smoothing for dVsv and for Gc,s), one LSMR over all periods with para.in's damping and the 3-D program's
+! LSMR controls, and the clamped update (dazim_phase_map_update).  iso-mode T inverts c only, F c, a1 and a2 (a1, a2 solved for
+! whole in every iteration, as Gc, Gs in the joint mode).
+! Velocity clamp: [0.85*minvel, maxvel] of para.in -- para.in bounds shear velocities, and a Rayleigh phase velocity lies a few
+! per cent below the shear velocity of the layers it samples, so the lower bound is widened by 15 %.
+!
+! Outputs (names distinct from the 3-D program's, so that both can run in one directory):
+!   period_phaseV_map.dat    lon lat period c                           (format of period_phaseVMOD.dat)
+!   period_Azm_tomo_map.inv  the nine columns of period_Azm_tomo.inv from c, a1, a2 (iso-mode F only)
+!   period_map_coverage.dat  lon lat period DWS [bias]: DWS = sum |fdm| over the rays (dazim_csr_col_abs_sums); in iso-mode F
+!                            the 2-psi azimuthal bias sqrt((sum fdmc)^2 + (sum fdms)^2) / DWS in [0, 1] (dazim_aprod mode 2,
+!                            y = 1), 0 = even azimuthal coverage; both on the unweighted rows of the last iteration's maps
+!   <para>_map.log + stdout  one line per iteration: data, mean / std / RMS of the residual before and after, LSMR istop / itn
+program SurfPhaseMaps_amd
+  use iso_c_binding
+  use dazim_mod
+  implicit none
+  real, parameter :: pi = 3.1415926535898
+  character(len=100) :: inputfile, logfile, arg
+  character(len=80) :: datafile
+  character(len=200) :: line
+  character(len=40) :: dummy
+  character :: str1
+  logical :: ex, iso_mod
+  integer :: nx, ny, nz, nsrc, nrc, maxiter, kmaxRc, kmax, err
+  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp, weight_c, weight_a
+  real*8, allocatable :: tRc(:)
+  real, allocatable :: depz(:), vsf(:, :, :)
+  real, allocatable :: scxf(:, :), sczf(:, :), rcxf(:, :, :), rczf(:, :, :)
+  integer, allocatable :: periods(:, :), nrc1(:, :), nsrc1(:)
+  real, allocatable :: obst(:), dist(:)
+  integer :: dall, i, j, k, istep, istep1, knum, knumo, period, wavetp, veltp
+  real :: sta1_lat, sta1_lon, sta2_lat, sta2_lon, velvalue, dist1
+  ! the map inversion
+  real*8, allocatable, target :: pv(:, :)
+  real, allocatable :: dsyn(:), Tdata(:), datweight(:), cbst(:), dm(:), a1(:), a2(:), w(:), ustats(:, :, :), y(:), after(:)
+  real, allocatable :: dws(:), sfc(:), ones(:)
+  integer :: ncell, nblk, nm, iter, nar, itnlim, localSize, t1, j1, i1, q
+  integer(c_int) :: nfail, istop, itn
+  integer(c_int64_t) :: m64, n64, z64
+  real :: minc, maxc, atol, btol, conlim, anorm, acond, rnorm, arnorm, xnorm, wstats(8), amean, astd, arms
+  real :: c2, s2, amp, ang, rel, isoC, bias
+  real*8 :: pi8 = real(3.1415926535898, 8)
+  type(c_ptr) :: G
+
+  write (*, *)
+  write (*, *) '                       SurfPhaseMaps'
+  write (*, *)
+  if (command_argument_count() < 1) stop 'usage: SurfPhaseMaps_amd para.in [weight_c [weight_a]]'
+  call get_command_argument(1, inputfile)
+  inquire (file=inputfile, exist=ex)
+  if (.not. ex) stop 'unable to open the inputfile'
+  include 'read_para.inc'
+  if (nz <= 1) stop 'error nz value.'
+  if (kmaxRc <= 0) stop 'Can only deal with Rayleigh wave phase velocity data!'
+  weight_c = weightVs; weight_a = weightGcs
+  if (command_argument_count() >= 2) then
+    call get_command_argument(2, arg)
+    read (arg, *) weight_c
+  end if
+  if (command_argument_count() >= 3) then
+    call get_command_argument(3, arg)
+    read (arg, *) weight_a
+  end if
+  write (logfile, '(a,a)') trim(inputfile), '_map.log'
+  open (66, file=logfile)
+  write (66, *)
+  write (66, *) '                  SurfPhaseMaps'
+  write (66, *)
+  nrc = nsrc
+  kmax = kmaxRc
+  minc = 0.85*Minvel; maxc = Maxvel
+  ncell = (nx - 2)*(ny - 2)
+  nblk = merge(1, 3, iso_mod)
+  nm = ncell*kmax*nblk
+  do q = 6, 66, 60
+    write (q, '(a,a)') ' data file: ', trim(datafile)
+    write (q, '(a,3i5,a,i3,a,l2)') ' grid nx ny:', nx, ny, kmax, ' periods; iterations', maxiter, '; iso-mode', iso_mod
+    write (q, '(a,50f6.1)') ' periods (s):', (tRc(i), i=1, kmax)
+    write (q, '(a,2f8.3,a,f8.3,a,2f8.3)') ' smoothing c, a:', weight_c, weight_a, '  damping', damp, '  c range (km/s)', minc, maxc
+  end do
+
+  include 'read_data.inc'
+  allocate (depz(nz), vsf(nx, ny, nz))
+  vsf = 0
+  include 'read_mod.inc'
+
+  ! ---- starting maps: MOD's dispersion curves (= the 3-D program's first-iteration pvRc) ----------------------------------------
+  call dazim_init(0)
+  allocate (pv(nx*ny, kmax))
+  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_null_ptr, c_null_ptr, &
+                                            c_null_ptr, nfail), 'starting maps')
+  if (nfail > 0) write (6, *) 'WARNING:improper initial value in disper - no zero found', nfail
+  allocate (dsyn(dall), Tdata(dall), datweight(dall), cbst(dall + nm), dm(nm), a1(ncell*kmax), a2(ncell*kmax), w(kmax*nblk))
+  allocate (ustats(3, kmax, 3), y(dall + nm), after(dall), dws(nm), sfc(nm), ones(dall))
+  a1 = 0; a2 = 0; ones = 1; dws = 0; sfc = 0
+  w(1:kmax) = weight_c
+  if (.not. iso_mod) w(kmax + 1:3*kmax) = weight_a
+  if (iso_mod) then
+    atol = 1e-3; btol = 1e-3; conlim = 1200; itnlim = 1000; localSize = nm/4
+  else
+    atol = 1e-5; btol = 1e-4; conlim = 200; itnlim = 500; localSize = 10
+  end if
+  do q = 6, 66, 60
+    write (q, '(a)') '  iter   ndata   mean_in    std_in    rms_in  mean_out   std_out   rms_out  istop    itn'
+  end do
+
+  do iter = 1, maxiter
+    call dazim_assemble_G_maps(.not. iso_mod, nx, ny, goxd, gozd, dvxd, dvzd, kmax, pv, periods, scxf, sczf, rcxf, rczf, nrc1, &
+                               nsrc1, kmax, nsrc, nrc, dsyn, G, nar)
+    ! coverage on the unweighted rows (kept from the last iteration)
+    call dazim_check(dazim_csr_col_abs_sums(dazim_handle, G, dws), 'DWS')
+    if (.not. iso_mod) then
+      sfc = 0
+      call dazim_check(dazim_aprod(dazim_handle, 2, G, sfc, ones), 'coverage sums')
+    end if
+    cbst = 0
+    call dazim_check(dazim_weight_data(dazim_handle, G, int(dall, c_int64_t), obst, dsyn, Tdata, datweight, cbst, wstats), &
+                     'data weights')
+    call dazim_check(dazim_csr_append_laplacian2d(dazim_handle, G, nx, ny, kmax*nblk, w), '2-D regularisation')
+    call dazim_check(dazim_csr_dims(G, m64, n64, z64), 'dims')
+    dm = 0
+    call dazim_check(dazim_lsmr(dazim_handle, G, cbst, damp, atol, btol, conlim, itnlim, localSize, dm, istop, itn, anorm, acond, &
+                                rnorm, arnorm, xnorm), 'LSMR')
+    call dazim_check(dazim_phase_map_update(dazim_handle, nx, ny, kmax, merge(0_c_int, 1_c_int, iso_mod), pv, dm, minc, maxc, &
+                                            a1, a2, ustats), 'map update')
+    ! residual after: the data rows (weighted by datweight) times the applied update, unweighted again
+    y = 0
+    call dazim_check(dazim_aprod(dazim_handle, 1, G, dm, y), 'aprod')
+    do i = 1, dall
+      after(i) = Tdata(i) - y(i)/datweight(i)
+    end do
+    amean = sum(after)/dall
+    astd = sqrt(sum((after - amean)**2)/dall)
+    arms = sqrt(sum(after**2)/dall)
+    do q = 6, 66, 60
+      write (q, '(i6,i8,6f10.4,i7,i7)') iter, dall, wstats(1), wstats(2), wstats(4), amean, astd, arms, istop, itn
+    end do
+    call dazim_check(dazim_csr_free(dazim_handle, G), 'free G')
+  end do
+
+  ! ---- output files ------------------------------------------------------------------------------------------------------------
+  open (77, file='period_phaseV_map.dat')
+  do t1 = 1, kmax
+    do j1 = 1, ny - 2
+      do i1 = 1, nx - 2
+        write (77, '(5f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), pv(j1*nx + i1 + 1, t1)
+      end do
+    end do
+  end do
+  close (77)
+  if (.not. iso_mod) then                     ! the arithmetic of write_period_azimuthal (dazim_main.f90)
+    open (42, file='period_Azm_tomo_map.inv', status='replace', action='write')
+    do t1 = 1, kmax
+      do j1 = 1, ny - 2
+        do i1 = 1, nx - 2
+          q = (t1 - 1)*ncell + (j1 - 1)*(nx - 2) + i1
+          c2 = a1(q); s2 = a2(q)
+          amp = sqrt(c2**2 + s2**2)
+          isoC = real(pv(j1*nx + i1 + 1, t1))
+          rel = amp/isoC
+          ang = atan2(s2, c2)/pi8*180
+          if (ang < 0.0) ang = ang + 360
+          ang = 0.5*ang
+          write (42, '(10f10.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), isoC, ang, rel, amp, c2, s2
+        end do
+      end do
+    end do
+    close (42)
+  end if
+  open (43, file='period_map_coverage.dat')
+  do t1 = 1, kmax
+    do j1 = 1, ny - 2
+      do i1 = 1, nx - 2
+        q = (t1 - 1)*ncell + (j1 - 1)*(nx - 2) + i1
+        if (iso_mod) then
+          write (43, '(3f10.4,es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), dws(q)
+        else
+          bias = 0.0
+          if (dws(q) > 0.0) bias = min(1.0, sqrt(sfc(kmax*ncell + q)**2 + sfc(2*kmax*ncell + q)**2)/dws(q))   ! (min: rounding only)
+          write (43, '(3f10.4,es14.5,f10.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), dws(q), bias
+        end if
+      end do
+    end do
+  end do
+  close (43)
+  write (*, *) '  Program finishes successfully'
+  write (66, *) '  Program finishes successfully'
+  close (66)
+  call dazim_finalize()
+
+contains
+
+  include 'great_circle.inc'
+end program

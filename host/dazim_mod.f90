@@ -31,6 +31,9 @@ module dazim_mod
             dazim_dispersion_kernels_sharded, dazim_ti_kernels_sharded, dazim_allmax_int, dazim_allsum_int8, &
             dazim_csr_append_tikhonov_rows, dazim_weight_data_sharded, dazim_ranks_init, dazim_nranks, dazim_rank, &
             dazim_shard_fields, dazim_shard_rows, dazim_allsum
+  ! the per-period map inversion (host/dazim_maps.f90)
+  public :: dazim_dispersion_kernels, dazim_rays_build_G_maps, dazim_csr_append_laplacian2d, dazim_phase_map_update, &
+            dazim_assemble_G_maps
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -172,6 +175,34 @@ module dazim_mod
       real(c_double) :: svs(*), svp(*), srho(*)
       type(c_ptr) :: G
       integer(c_int64_t) :: nnz
+    end function
+    integer(c_int) function dazim_rays_build_G_maps(ctx, nx, ny, goxd, gozd, dvxd, dvzd, kmax, azim, nfield, scx, scz, &
+        period_idx, veln, ttn, ttnr, nstsr, boxes, nray, field_of_ray, rcx, rcz, tpred, G, nnz, nboundary) &
+        bind(C, name="dazim_rays_build_G_maps")
+      import
+      type(c_ptr), value :: ctx, veln, ttn, ttnr, nstsr, boxes
+      integer(c_int), value :: nx, ny, kmax, azim, nfield
+      integer(c_int64_t), value :: nray
+      real(c_float), value :: goxd, gozd, dvxd, dvzd
+      real(c_float) :: scx(*), scz(*), rcx(*), rcz(*), tpred(*)
+      integer(c_int) :: period_idx(*), field_of_ray(*), nboundary
+      type(c_ptr) :: G
+      integer(c_int64_t) :: nnz
+    end function
+    integer(c_int) function dazim_csr_append_laplacian2d(ctx, A, nx, ny, nmap, w) bind(C, name="dazim_csr_append_laplacian2d")
+      import
+      type(c_ptr), value :: ctx, A
+      integer(c_int), value :: nx, ny, nmap
+      real(c_float) :: w(*)
+    end function
+    integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
+        bind(C, name="dazim_phase_map_update")
+      import
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, kmax, azim
+      real(c_float), value :: minc, maxc
+      real(c_double) :: pv(*)
+      real(c_float) :: dm(*), a1(*), a2(*), stats(*)
     end function
     integer(c_int) function dazim_memcpy_h2d(ctx, dst, src, bytes) bind(C, name="dazim_memcpy_h2d")
       import; type(c_ptr), value :: ctx, dst, src; integer(c_size_t), value :: bytes
@@ -815,6 +846,81 @@ contains
     dazim_dev_seconds(3) = dazim_dev_seconds(3) + t_ti
     dazim_dev_seconds(4) = dazim_dev_seconds(4) + max(dazim_last_kernel_seconds(dazim_handle, 'fmm'//c_null_char), 0.0_c_double)
     dazim_dev_seconds(5) = dazim_dev_seconds(5) + max(dazim_last_kernel_seconds(dazim_handle, 'rays'//c_null_char), 0.0_c_double)
+  end subroutine
+
+  ! The map rows of one iteration of the per-period map inversion (host/dazim_maps.f90): eikonal fields on the maps pv(nx*ny, kmaxRc)
+  ! and dazim_rays_build_G_maps over the same (period, source, receiver) order as dazim_assemble_G, lists and maps device-resident
+  ! so that the ray call runs beside the eikonal launch's tail (fmm.async).  dsurf(1:nray) = predicted times, G = the rows.
+  subroutine dazim_assemble_G_maps(azim, nx, ny, goxdf, gozdf, dvxdf, dvzdf, kmaxRc, pv, periods, scxf, sczf, rcxf, rczf, nrc1, &
+                                   nsrcsurf1, kmax, nsrcsurf, nrcf, dsurf, G, nar)
+    logical :: azim
+    integer :: nx, ny, kmaxRc, kmax, nsrcsurf, nrcf, nar
+    real :: dsurf(*), goxdf, gozdf, dvxdf, dvzdf
+    real*8 :: pv(nx*ny, kmaxRc)
+    integer :: periods(nsrcsurf, kmax), nrc1(nsrcsurf, kmax), nsrcsurf1(kmax)
+    real :: scxf(nsrcsurf, kmax), sczf(nsrcsurf, kmax), rcxf(nrcf, nsrcsurf, kmax), rczf(nrcf, nsrcsurf, kmax)
+    type(c_ptr) :: G
+    real, allocatable, target :: scx(:), scz(:), rcx(:), rcz(:), dsurf_h(:)
+    integer, allocatable, target :: per(:), fray(:)
+    real*8, allocatable, target :: pv_h(:, :)
+    type(c_ptr) :: d_veln, d_ttnr, d_nstsr, d_box, p_pv, p_scx, p_scz, p_per, p_fray, p_rcx, p_rcz, p_dsurf
+    real(c_double), pointer :: dpv(:)
+    real(c_float), pointer :: dscx(:), dscz(:), drcx(:), drcz(:), ddsurf(:)
+    integer(c_int), pointer :: dper(:), dfray(:)
+    integer :: nfield, nray, k, s, r, f, nnx, nnz
+    integer(c_int) :: nb
+    integer(c_int64_t) :: nnz64
+    integer(c_size_t) :: nn
+    call dazim_init(0)
+    nfield = sum(nsrcsurf1(1:kmax)); nray = 0
+    do k = 1, kmax
+      nray = nray + sum(nrc1(1:nsrcsurf1(k), k))
+    end do
+    allocate (scx(nfield), scz(nfield), per(nfield), fray(max(nray, 1)), rcx(max(nray, 1)), rcz(max(nray, 1)))
+    f = 0; nray = 0
+    do k = 1, kmax
+      do s = 1, nsrcsurf1(k)
+        f = f + 1
+        scx(f) = scxf(s, k); scz(f) = sczf(s, k); per(f) = periods(s, k)
+        do r = 1, nrc1(s, k)
+          nray = nray + 1
+          fray(nray) = f - 1; rcx(nray) = rcxf(r, s, k); rcz(nray) = rczf(r, s, k)
+        end do
+      end do
+    end do
+    nnx = (nx - 3)*5 + 1; nnz = (ny - 3)*5 + 1
+    nn = int(nnx, c_size_t)*nnz
+    call field_buffer(1, nn*kmaxRc*4, d_veln)
+    call field_buffer(3, int(129*129, c_size_t)*nfield*4, d_ttnr)
+    call field_buffer(4, int(129*129, c_size_t)*nfield*4, d_nstsr)
+    call field_buffer(5, int(48, c_size_t)*nfield, d_box)
+    allocate (pv_h(nx*ny, kmaxRc), dsurf_h(max(nray, 1)))
+    pv_h = pv
+    call upload(10, c_loc(pv_h), int(nx, c_size_t)*ny*kmaxRc*8, p_pv)
+    call upload(11, c_loc(scx), int(nfield, c_size_t)*4, p_scx)
+    call upload(12, c_loc(scz), int(nfield, c_size_t)*4, p_scz)
+    call upload(13, c_loc(per), int(nfield, c_size_t)*4, p_per)
+    call upload(15, c_loc(fray), int(max(nray, 1), c_size_t)*4, p_fray)
+    call upload(16, c_loc(rcx), int(max(nray, 1), c_size_t)*4, p_rcx)
+    call upload(17, c_loc(rcz), int(max(nray, 1), c_size_t)*4, p_rcz)
+    call field_buffer(18, int(max(nray, 1), c_size_t)*4, p_dsurf)
+    call c_f_pointer(p_pv, dpv, [nx*ny*kmaxRc]); call c_f_pointer(p_scx, dscx, [nfield]); call c_f_pointer(p_scz, dscz, [nfield])
+    call c_f_pointer(p_per, dper, [nfield]); call c_f_pointer(p_fray, dfray, [max(nray, 1)])
+    call c_f_pointer(p_rcx, drcx, [max(nray, 1)]); call c_f_pointer(p_rcz, drcz, [max(nray, 1)])
+    call c_f_pointer(p_dsurf, ddsurf, [max(nray, 1)])
+    call check(dazim_set_option(dazim_handle, 'fmm.async'//c_null_char, 1_c_int), 'option')
+    call check(dazim_fmm_batch(dazim_handle, nx, ny, goxdf, gozdf, dvxdf, dvzdf, kmaxRc, dpv, nfield, dscx, dscz, dper, &
+                               d_veln, c_null_ptr, d_ttnr, d_nstsr, d_box, c_null_ptr), 'maps/travel')
+    call check(dazim_rays_build_G_maps(dazim_handle, nx, ny, goxdf, gozdf, dvxdf, dvzdf, kmaxRc, merge(1_c_int, 0_c_int, azim), &
+                                       nfield, dscx, dscz, dper, d_veln, c_null_ptr, d_ttnr, d_nstsr, d_box, int(nray, c_int64_t), &
+                                       dfray, drcx, drcz, ddsurf, G, nnz64, nb), 'maps/rpaths')
+    call check(dazim_set_option(dazim_handle, 'fmm.async'//c_null_char, 0_c_int), 'option')
+    if (nray > 0) then
+      call check(dazim_memcpy_d2h(dazim_handle, c_loc(dsurf_h), p_dsurf, int(nray, c_size_t)*4), 'maps/dsurf')
+      dsurf(1:nray) = dsurf_h(1:nray)
+    end if
+    nar = int(nnz64)
+    if (nb >= 1) write (6, *) nb, ' ray path along the boundary, dangerous!!'
   end subroutine
 
   ! device buffer q holding a copy of `bytes` bytes of host memory

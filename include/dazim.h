@@ -234,6 +234,34 @@ int dazim_rays_build_G_joint(dazim_ctx *ctx, int nx, int ny, int nz, float goxd,
                              const double *sen_vp, const double *sen_rho, const float *Lsen_Gsc,
                              float *tpred, dazim_csr **G, int64_t *nnz, int *n_boundary);
 
+/* ---- per-period phase-velocity and 2-psi anisotropy maps (the map inversion) --------------------------
+ * The reference inverts Rayleigh phase times for the 3-D model only; the maps are the same rows BEFORE the multiplication by the
+ * depth kernels (inv/CalSurfG.f90:1339-1364, inv/CalSurfGAniso_Joint.f90:728-738): dt = fdm.dc + fdmc.a1 + fdms.a2 per ray, where
+ * a1 = sum_k Lsen.Gc and a2 = sum_k Lsen.Gs are the a1_cos / a2_sin columns of period_Azm_tomo.inv.
+ * dazim_rays_build_G_maps: the receiver loop of CalSurfG / CalSurfGAnisoJoint (srtimes, rpaths / rpathsAzim) with the Frechet
+ *   values themselves as row entries -- fdm, and fdmc, fdms when azim -- under the same double ftol rule (option rays.keep_small
+ *   as there), in one column block per period: column blk*kmax*ncell + (period_idx-1)*ncell + (jj-1)*nvx + kk-1 (0-based, ncell =
+ *   (nx-2)(ny-2), blk 0 c, 1 a1, 2 a2), n = kmax*ncell (x3 when azim).  Bit-identical to dazim_rays_build_G / _joint with unit depth
+ *   kernels (sen_vs = 1, sen_vp = sen_rho = 0, Lsen_Gsc = 1) and nz = 2, the period folded into the column.  No model, no depth
+ *   kernels; other arguments as dazim_rays_build_G (ttn = NULL and option fmm.async as there).  Option rays.dense_twin is refused
+ *   (DAZIM_E_BAD_ARG).  Stat "rays.map" = 1 after such a call.
+ * dazim_csr_append_laplacian2d: the 2-D analogue of dazim_csr_append_tikhonov (inv/TikhRegul.f90:2-104): nmap*ncell rows, map b
+ *   regularising columns b*ncell .. with weight w[b] (host): 2w on a cell at an edge of the map, the 5-point Laplacian 4w, -w x 4
+ *   inside; rows in map, j, i order; appended in place when the matrix has reserved room (csr.reserve_*, dazim_csr_threshold).
+ * dazim_phase_map_update: dazim_model_update (inv/Main_Jt.f90:582-620) on the map layout: dm [kmax*ncell, x3 when azim] in/out
+ *   (c block clamped to +-0.5, zeroed below 1e-5); pv [kmax][ny][nx] fp64 in/out (the dazim_fmm_batch maps): inner vertex
+ *   jj*nx+kk of each period += dc in fp32, clamped to [minc, maxc], the boundary ring kept; a1, a2 [kmax][ny-2][nx-2] out (azim,
+ *   nullable) = the a1 / a2 blocks (absolute values, as Gc / Gs of the joint update).  stats (host, nullable): [nblock][kmax][3] =
+ *   min, max, sum |.| of the update per block and period.                                                                   */
+int dazim_rays_build_G_maps(dazim_ctx *ctx, int nx, int ny, float goxd, float gozd, float dvxd, float dvzd, int kmax, int azim,
+                            int nfield, const float *scx, const float *scz, const int *period_idx, const float *veln,
+                            const float *ttn, const float *ttnr, const int *nstsr, const dazim_refbox *boxes, int64_t nray,
+                            const int *field_of_ray, const float *rcx, const float *rcz, float *tpred, dazim_csr **G,
+                            int64_t *nnz, int *n_boundary);
+int dazim_csr_append_laplacian2d(dazim_ctx *ctx, dazim_csr *A, int nx, int ny, int nmap, const float *w);
+int dazim_phase_map_update(dazim_ctx *ctx, int nx, int ny, int kmax, int azim, double *pv, float *dm, float minc, float maxc,
+                           float *a1, float *a2, float *stats);
+
 /* ---- N4: what surrounds the solve in the outer iteration, on the device ------------------------------
  * = TikhonovRegularization / TikhRegul_joint (inv/TikhRegul.f90:2-104, :107-209): appends nblock * maxvp rows, maxvp =
  *   (nx-2)(ny-2)(nz-1); block b regularises columns b*maxvp+1 .. (b+1)*maxvp with weight w[b] (host array): a cell on a face
