@@ -344,6 +344,48 @@ class Context:
                                                     C.c_float(maxc), _ptr(a1), _ptr(a2), _ptr(st)))
         return a1, a2, st
 
+    def vs_kernels(self, vel, sen, skern=None):
+        """dc/dVs table of the 3-D rows (dazim_vs_kernels): vel[nz][ny][nx] and sen = (sen_vs, sen_vp, sen_rho) from depthkernel ->
+        skern[nz][kmax][nx*ny] fp64, the table dazim_rays_build_G multiplies.  numpy in -> numpy out; torch-cuda in -> filled in place."""
+        nz, ny, nx = vel.shape
+        kmax = sen[0].shape[1]
+        if skern is None:
+            if _is_torch(vel):
+                import torch
+                skern = torch.empty((nz, kmax, nx * ny), dtype=torch.float64, device=vel.device)
+            else:
+                skern = np.zeros((nz, kmax, nx * ny), np.float64)
+        if not _is_torch(vel):
+            vel = np.ascontiguousarray(vel, np.float32)
+            sen = [np.ascontiguousarray(s, np.float64) for s in sen]
+        self._check(self.lib.dazim_vs_kernels(self._h, nx, ny, nz, kmax, _ptr(vel, np.float32), _ptr(sen[0], np.float64),
+                                              _ptr(sen[1], np.float64), _ptr(sen[2], np.float64), _ptr(skern, np.float64)))
+        return skern
+
+    def column_lsq(self, nx, ny, nlay, kern, rhs, wdat=None, smooth=0.0, damp=0.0, x=None):
+        """one regularised least-squares problem per inner cell (dazim_column_lsq): kern[>=nlay][kmax][nx*ny] (fp64 skern or fp32
+        Lsen_Gsc), rhs[nrhs][kmax][ny-2][nx-2], wdat[kmax][ny-2][nx-2] or None (all ones).
+        Returns (x[nrhs][nlay][ny-2][nx-2] fp32, n_empty, stats[nrhs][kmax][2] = RMS of r and of r - K x)."""
+        kmax = kern.shape[1]
+        nrhs = rhs.shape[0]
+        fp32 = str(kern.dtype).endswith("float32")
+        if x is None:
+            if _is_torch(rhs):
+                import torch
+                x = torch.empty((nrhs, nlay, ny - 2, nx - 2), dtype=torch.float32, device=rhs.device)
+            else:
+                x = np.zeros((nrhs, nlay, ny - 2, nx - 2), np.float32)
+        if not _is_torch(rhs):
+            kern = np.ascontiguousarray(kern)
+            rhs = np.ascontiguousarray(rhs, np.float32)
+            wdat = None if wdat is None else np.ascontiguousarray(wdat, np.float32)
+        ne = C.c_int(0)
+        st = np.zeros((nrhs, kmax, 2), np.float32)
+        self._check(self.lib.dazim_column_lsq(self._h, nx, ny, int(nlay), kmax, int(fp32), _ptr(kern, np.float32 if fp32 else np.float64),
+                                              nrhs, _ptr(rhs, np.float32), _ptr(wdat, np.float32), C.c_float(smooth), C.c_float(damp),
+                                              _ptr(x, np.float32), C.byref(ne), _ptr(st)))
+        return x, ne.value, st
+
     def ray_paths(self):
         """ray geometries of the last rays_build_G call made with option rays.keep_paths = 1: a list of [nrp][2] arrays
         (colatitude, longitude in rad; receiver first, source last) -- the reference's raypath_refmdl_<T>s.dat content"""

@@ -132,6 +132,18 @@ __host__ __device__ constexpr int dz_tile_shift(int nz) { int l = 0; while ((1 <
 __host__ __device__ __forceinline__ constexpr int dz_tile_x(int x0, int tsh) { return ((x0 >> 2) << tsh) + ((x0 & 3) << 2); }
 __host__ __device__ __forceinline__ constexpr int dz_tile_z(int z0) { return ((z0 & ~3) << 2) | (z0 & 3); }
 
+// The factor of a dVs row entry that does not depend on the ray (inv/CalSurfG.f90:1339-1364): dc/dVs of a model cell for one period,
+// the Brocher derivatives coe_a, coe_rho of the cell's velocity v and its three depth kernels, (svp*coe_a + srho*coe_rho + svs) in
+// the reference's order and precision.  k_row_kernels (rays.hip, the table the 3-D rows multiply) and dazim_vs_kernels (column.hip)
+// both call it, so the two tables are the same bits.
+__device__ __forceinline__ double dz_row_kernel(float v, double svs, double svp, double srho) {
+  const float coe_a = (2.0947f - 0.8206f * 2 * v + 0.2683f * 3 * (v * v) - 0.0251f * 4 * (v * v * v));
+  const float vpft = 0.9409f + 2.0947f * v - 0.8206f * (v * v) + 0.2683f * (v * v * v) - 0.0251f * (v * v * v * v);
+  const float coe_rho = coe_a * (1.6612f - 0.4721f * 2 * vpft + 0.0671f * 3 * (vpft * vpft) -
+                                 0.0043f * 4 * (vpft * vpft * vpft) + 0.000106f * 5 * (vpft * vpft * vpft * vpft));
+  return svp * (double)coe_a + srho * (double)coe_rho + svs;
+}
+
 // named scratch buffer of at least `bytes` bytes
 int dz_scratch(dazim_ctx *ctx, const char *name, size_t bytes, void **out);
 // named PINNED host buffer of at least `bytes` bytes (option ctx.pinned = 0: plain malloc'ed memory, the behaviour before round 6)

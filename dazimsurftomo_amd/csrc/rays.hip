@@ -203,19 +203,14 @@ __device__ __forceinline__ float bilin_cell(const dazim_geom &g, const float *ve
 }
 
 // The factor of a dVs row entry that does not depend on the ray (inv/CalSurfG.f90:1339-1364): the Brocher derivatives of the cell's
-// velocity and the three depth kernels, (svp*coe_a + srho*coe_rho + svs) in the reference's order and precision -- once per model
-// cell, layer and period instead of once per ray that crosses the cell (both passes of rays_kernel; the emit pass is little else).
+// velocity and the three depth kernels, (svp*coe_a + srho*coe_rho + svs) in the reference's order and precision (dz_row_kernel,
+// dazim_internal.h, which dazim_vs_kernels shares) -- once per model cell, layer and period instead of once per ray that crosses the cell (both passes of rays_kernel; the emit pass is little else).
 __global__ void k_row_kernels(long n, int kmax, long ncol, const float *__restrict__ vels, const double *__restrict__ svs,
                               const double *__restrict__ svp, const double *__restrict__ srho, double *__restrict__ out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // (layer, period, column)
   if (i >= n) return;
   const long k = i / (kmax * ncol), c = i % ncol;
-  const float v = vels[k * ncol + c];
-  const float coe_a = (2.0947f - 0.8206f * 2 * v + 0.2683f * 3 * (v * v) - 0.0251f * 4 * (v * v * v));
-  const float vpft = 0.9409f + 2.0947f * v - 0.8206f * (v * v) + 0.2683f * (v * v * v) - 0.0251f * (v * v * v * v);
-  const float coe_rho = coe_a * (1.6612f - 0.4721f * 2 * vpft + 0.0671f * 3 * (vpft * vpft) -
-                                 0.0043f * 4 * (vpft * vpft * vpft) + 0.000106f * 5 * (vpft * vpft * vpft * vpft));
-  out[i] = svp[i] * (double)coe_a + srho[i] * (double)coe_rho + svs[i];
+  out[i] = dz_row_kernel(vels[k * ncol + c], svs[i], svp[i], srho[i]);
 }
 
 // sort key of a ray for the order in which rays are dealt to the wavefronts: field in the high bits, quantised source-receiver

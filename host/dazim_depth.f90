@@ -1,0 +1,333 @@
+! dazim_depth.f90 -- SurfDepthFromMaps_amd: the second step of the classical two-step method.  It turns the per-period maps of
+! SurfPhaseMaps_amd into a depth model, cell by cell, on one MI355X: Vs(z) from each cell's phase-velocity dispersion curve and, in
+! iso-mode F, Gc/L(z) and Gs/L(z) from its 2-psi curves (DESIGN.md section 13).
+!
+!   SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c]]]
+!
+! Inputs: the unchanged para.in and MOD of DAzimSurfTomo_amd (read_para.inc, read_mod.inc; the data file is not opened), the maps
+! period_phaseV_map.dat (and period_Azm_tomo_map.inv in iso-mode F) and, if present, period_map_coverage.dat.  Weights: 1/sigma_c
+! (default 0.01 km/s) where the map's DWS > 0, 0 elsewhere (everywhere 1/sigma_c without a coverage file).  smooth_vs / smooth_gcs
+! default to para.in's two smoothing weights; the damping is para.in's.
+! Vs: para.in's maxiter linearised iterations from MOD, each dazim_dispersion_kernels -> dazim_vs_kernels -> r = c_map - pvRc on the
+! inner cells (w = 0 where pvRc = 0) -> dazim_column_lsq (nlay = nz-1) -> dazim_model_update (para.in's minvel, maxvel).
+! Gc, Gs (iso-mode F): on the final Vs, dazim_ti_kernels, then one dazim_column_lsq on Lsen_Gsc with the two right-hand sides a1, a2:
+! the 2-psi terms are linear in Gc, Gs, so they are solved for whole.
+!
+! Outputs (names distinct from the other programs' so that all three can share a directory; formats of DAzimSurfTomo_amd's files):
+!   DSurfTomo_2step.inv        as DSurfTomo.inv                MOD_2step     as MOD_Ref (a MOD for DAzimSurfTomo_amd)
+!   period_phaseV_2step.dat    c of the final model, as period_phaseV_map.dat
+!   Gc_Gs_model_2step.inv, period_Azm_tomo_2step.inv   (iso-mode F) as Gc_Gs_model.inv, period_Azm_tomo.inv
+!   <para>_2step.log + stdout  one line per iteration: cells used, RMS c misfit before and predicted after the solve, max |dVs|
+program SurfDepthFromMaps_amd
+  use iso_c_binding
+  use dazim_mod
+  implicit none
+  real, parameter :: pi = 3.1415926535898
+  character(len=100) :: inputfile, logfile, arg
+  character(len=80) :: datafile
+  character(len=300) :: line
+  character(len=40) :: dummy
+  logical :: ex, iso_mod, have_cov
+  integer :: nx, ny, nz, nsrc, maxiter, kmaxRc, kmax
+  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp, smooth_vs, smooth_gcs, sigma_c
+  real*8, allocatable :: tRc(:)
+  real, allocatable :: depz(:), vsf(:, :, :)
+  real*8, allocatable, target :: pv(:, :), svs(:, :, :), svp(:, :, :), srho(:, :, :), skern(:, :, :)
+  real, allocatable, target :: lsen(:, :, :)
+  real, allocatable :: cmap(:, :, :), amap(:, :, :, :), cov(:, :, :), wcov(:, :, :), w(:, :, :), r(:, :, :, :), x(:, :, :, :)
+  real, allocatable :: gcf(:, :, :), gsf(:, :, :), ustats(:, :), stats(:, :, :)
+  real :: dummy1(1), vals(9), rms0, rms1, maxdv
+  real*8 :: s0, s1, cnt
+  integer :: i, j, k, t, iter, nlay, ncell, nused, col, q
+  integer(c_int) :: nfail, nempty
+
+  write (*, *)
+  write (*, *) '                       SurfDepthFromMaps'
+  write (*, *)
+  if (command_argument_count() < 1) error stop 'usage: SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c]]]'
+  call get_command_argument(1, inputfile)
+  inquire (file=inputfile, exist=ex)
+  if (.not. ex) error stop 'unable to open the inputfile'
+  include 'read_para.inc'
+  if (nz <= 1) error stop 'error nz value.'
+  if (kmaxRc <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
+  smooth_vs = weightVs; smooth_gcs = weightGcs; sigma_c = 0.01
+  if (command_argument_count() >= 2) then
+    call get_command_argument(2, arg)
+    read (arg, *) smooth_vs
+  end if
+  if (command_argument_count() >= 3) then
+    call get_command_argument(3, arg)
+    read (arg, *) smooth_gcs
+  end if
+  if (command_argument_count() >= 4) then
+    call get_command_argument(4, arg)
+    read (arg, *) sigma_c
+  end if
+  if (sigma_c <= 0) error stop 'sigma_c must be positive'
+  kmax = kmaxRc
+  nlay = nz - 1
+  ncell = (nx - 2)*(ny - 2)
+  if (nlay > 63) error stop 'SurfDepthFromMaps_amd inverts at most 63 layers (nz <= 64)'
+  if (kmax > 60) error stop 'SurfDepthFromMaps_amd takes at most 60 periods'
+  write (logfile, '(a,a)') trim(inputfile), '_2step.log'
+  open (66, file=logfile)
+  write (66, *)
+  write (66, *) '                  SurfDepthFromMaps'
+  write (66, *)
+  do q = 6, 66, 60
+    write (q, '(a,3i5,a,i3,a,i3,a,l2)') ' grid nx ny nz:', nx, ny, nz, ';', kmax, ' periods; iterations', maxiter, '; iso-mode', iso_mod
+    write (q, '(a,50f6.1)') ' periods (s):', (tRc(i), i=1, kmax)
+    write (q, '(a,2f8.3,a,f8.3,a,f8.4,a,2f8.3)') ' smoothing Vs, Gc/Gs:', smooth_vs, smooth_gcs, '  damping', damp, &
+      '  sigma_c (km/s)', sigma_c, '  Vs range', Minvel, Maxvel
+  end do
+
+  allocate (depz(nz), vsf(nx, ny, nz))
+  vsf = 0
+  include 'read_mod.inc'
+
+  ! ---- the maps ------------------------------------------------------------------------------------------------------------------
+  allocate (cmap(nx - 2, ny - 2, kmax), cov(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
+  call read_map('period_phaseV_map.dat', 4, 4, cmap, .true.)
+  inquire (file='period_map_coverage.dat', exist=have_cov)
+  if (have_cov) then
+    call read_map('period_map_coverage.dat', 4, 4, cov, .true.)
+    wcov = merge(1.0/sigma_c, 0.0, cov > 0.0)
+    do q = 6, 66, 60
+      write (q, '(a,i8,a,i8)') ' period_map_coverage.dat: weight 1/sigma_c on the (cell, period) pairs with DWS > 0:', &
+        count(cov > 0.0), ' of', kmax*ncell
+    end do
+  else
+    wcov = 1.0/sigma_c
+    do q = 6, 66, 60
+      write (q, '(a)') ' period_map_coverage.dat is absent: weight 1/sigma_c on every cell and period'
+    end do
+  end if
+  if (.not. iso_mod) then
+    allocate (amap(nx - 2, ny - 2, kmax, 2))
+    call read_map('period_Azm_tomo_map.inv', 9, 8, amap(:, :, :, 1), .true.)
+    call read_map('period_Azm_tomo_map.inv', 9, 9, amap(:, :, :, 2), .false.)
+  end if
+
+  ! ---- Vs, para.in's iterations from MOD -----------------------------------------------------------------------------------------
+  call dazim_init(0)
+  allocate (pv(nx*ny, kmax), svs(nx*ny, kmax, nz), svp(nx*ny, kmax, nz), srho(nx*ny, kmax, nz), skern(nx*ny, kmax, nz))
+  allocate (w(nx - 2, ny - 2, kmax), r(nx - 2, ny - 2, kmax, 2), x(nx - 2, ny - 2, nlay, 2), ustats(3, nlay), stats(2, kmax, 2))
+  do q = 6, 66, 60
+    write (q, '(a)') '  iter  cells  rms_c_before  rms_c_after   max|dVs|'
+  end do
+  do iter = 1, maxiter
+    call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_loc(svs), c_loc(svp), &
+                                              c_loc(srho), nfail), 'dispersion and depth kernels')
+    if (nfail > 0) write (6, *) 'WARNING:improper initial value in disper - no zero found', nfail
+    call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kmax, vsf, svs, svp, srho, skern), 'dc/dVs table')
+    call residual()
+    call dazim_check(dazim_column_lsq(dazim_handle, nx, ny, nlay, kmax, 0, c_loc(skern), 1, r, w, smooth_vs, damp, x, nempty, &
+                                      stats), 'column solve (Vs)')
+    s1 = 0
+    do t = 1, kmax
+      s1 = s1 + real(stats(2, t, 1), 8)**2*count(w(:, :, t) > 0.0)
+    end do
+    rms1 = 0
+    if (cnt > 0) rms1 = real(sqrt(s1/cnt))
+    call dazim_check(dazim_model_update(dazim_handle, nx, ny, nz, 0, vsf, x, Minvel, Maxvel, dummy1, dummy1, ustats), 'model update')
+    maxdv = maxval(abs(x(:, :, :, 1)))
+    do q = 6, 66, 60
+      write (q, '(i6,i7,2f14.5,f11.4)') iter, nused, rms0, rms1, maxdv
+    end do
+  end do
+
+  ! ---- the final model's curves; its misfit --------------------------------------------------------------------------------------
+  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_null_ptr, c_null_ptr, &
+                                            c_null_ptr, nfail), 'dispersion curves of the final model')
+  call residual()
+  do q = 6, 66, 60
+    write (q, '(a,i7,a,f12.5)') ' final model: cells', nused, '  rms_c', rms0
+  end do
+
+  ! ---- Gc, Gs on the final Vs (iso-mode F) ---------------------------------------------------------------------------------------
+  if (.not. iso_mod) then
+    allocate (lsen(nx*ny, kmax, nz - 1), gcf(nx - 2, ny - 2, nlay), gsf(nx - 2, ny - 2, nlay))
+    call dazim_check(dazim_ti_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, lsen), 'TI depth kernels')
+    r = amap
+    call dazim_check(dazim_column_lsq(dazim_handle, nx, ny, nlay, kmax, 1, c_loc(lsen), 2, r, w, smooth_gcs, damp, x, nempty, &
+                                      stats), 'column solve (Gc, Gs)')
+    gcf = x(:, :, :, 1); gsf = x(:, :, :, 2)
+    do q = 6, 66, 60
+      write (q, '(a,2f12.6,a,2f12.6)') ' Gc/Gs: rms a1, a2', sqrt(sum(stats(1, :, 1)**2)/kmax), sqrt(sum(stats(1, :, 2)**2)/kmax), &
+        '  rms misfit a1, a2', sqrt(sum(stats(2, :, 1)**2)/kmax), sqrt(sum(stats(2, :, 2)**2)/kmax)
+      write (q, '(a,2f10.5)') ' max |Gc|, |Gs|:', maxval(abs(gcf)), maxval(abs(gsf))
+    end do
+  end if
+
+  ! ---- output files, in the formats of DAzimSurfTomo_amd's (dazim_main.f90) --------------------------------------------------------
+  open (11, file='MOD_2step')
+  do k = 1, nz
+    write (11, '(f7.1)', advance='no') depz(k)
+  end do
+  do k = 1, nz
+    do j = 1, ny
+      do i = 1, nx
+        if (i == 1) then
+          write (11, '(/f8.4)', advance='no') vsf(i, j, k)
+        else
+          write (11, '(f8.4)', advance='no') vsf(i, j, k)
+        end if
+      end do
+    end do
+  end do
+  close (11)
+  open (63, file='DSurfTomo_2step.inv')
+  do k = 1, nz
+    do j = 1, ny
+      do i = 1, nx
+        write (63, '(5f8.4)') gozd + (j - 2)*dvzd, goxd - (i - 2)*dvxd, depz(k), vsf(i, j, k)
+      end do
+    end do
+  end do
+  close (63)
+  open (77, file='period_phaseV_2step.dat')
+  do t = 1, kmax
+    do j = 1, ny - 2
+      do i = 1, nx - 2
+        write (77, '(5f10.4)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, tRc(t), pv(j*nx + i + 1, t)
+      end do
+    end do
+  end do
+  close (77)
+  if (.not. iso_mod) then
+    open (73, file='Gc_Gs_model_2step.inv')
+    call write_azimuthal(73)
+    close (73)
+    open (42, file='period_Azm_tomo_2step.inv', status='replace', action='write')
+    call write_period_azimuthal(42)
+    close (42)
+  end if
+  write (*, *) '  Program finishes successfully'
+  write (66, *) '  Program finishes successfully'
+  close (66)
+  call dazim_finalize()
+
+contains
+
+  ! w = 1/sigma_c where the map has coverage and pvRc is not 0, r = c_map - pvRc on the inner cells; rms0 over the pairs with w > 0,
+  ! cnt of those pairs, nused = cells with at least one
+  subroutine residual()
+    integer :: i1, j1, t1
+    s0 = 0; cnt = 0
+    do t1 = 1, kmax
+      do j1 = 1, ny - 2
+        do i1 = 1, nx - 2
+          col = j1*nx + i1 + 1
+          w(i1, j1, t1) = wcov(i1, j1, t1)
+          if (pv(col, t1) == 0) w(i1, j1, t1) = 0
+          r(i1, j1, t1, 1) = real(cmap(i1, j1, t1) - pv(col, t1))
+          if (w(i1, j1, t1) > 0) then
+            s0 = s0 + real(r(i1, j1, t1, 1), 8)**2
+            cnt = cnt + 1
+          end if
+        end do
+      end do
+    end do
+    rms0 = 0
+    if (cnt > 0) rms0 = real(sqrt(s0/cnt))
+    nused = count(any(w > 0.0, dim=3))
+  end subroutine
+
+  ! column icol of a map file in the order SurfPhaseMaps_amd writes it (period, then latitude row, then longitude); every line's
+  ! longitude, latitude and period must be para.in's inner grid and periods (1e-3)
+  subroutine read_map(fname, ncol, icol, out, announce)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: ncol, icol
+    real, intent(out) :: out(nx - 2, ny - 2, kmax)
+    logical, intent(in) :: announce
+    integer :: i1, j1, t1, ios
+    logical :: there
+    inquire (file=fname, exist=there)
+    if (.not. there) then
+      write (*, '(a,a,a)') ' ERROR: ', fname, ' is missing (SurfPhaseMaps_amd writes it)'
+      error stop 'a map file is missing'
+    end if
+    open (12, file=fname, status='old', action='read')
+    do t1 = 1, kmax
+      do j1 = 1, ny - 2
+        do i1 = 1, nx - 2
+          read (12, '(a)', iostat=ios) line
+          if (ios == 0) read (line, *, iostat=ios) vals(1:ncol)
+          if (ios /= 0) then
+            write (*, '(a,a,a)') ' ERROR: ', fname, ' has fewer lines than para.in''s inner grid times its periods'
+            error stop 'a map file does not match para.in'
+          end if
+          if (abs(vals(3) - tRc(t1)) > 1e-3) then
+            write (*, '(a,a,a,f10.4,a,f10.4)') ' ERROR: ', fname, ': its periods differ from para.in''s: ', vals(3), ' for', tRc(t1)
+            error stop 'a map file does not match para.in'
+          end if
+          if (abs(vals(1) - (gozd + (j1 - 1)*dvzd)) > 1e-3 .or. abs(vals(2) - (goxd - (i1 - 1)*dvxd)) > 1e-3) then
+            write (*, '(a,a,a,2f10.4)') ' ERROR: ', fname, ': its coordinates are not para.in''s inner grid at', vals(1:2)
+            error stop 'a map file does not match para.in'
+          end if
+          out(i1, j1, t1) = vals(icol)
+        end do
+      end do
+    end do
+    read (12, '(a)', iostat=ios) line
+    if (ios == 0 .and. len_trim(line) > 0) then
+      write (*, '(a,a,a)') ' ERROR: ', fname, ' has more lines than para.in''s inner grid times its periods'
+      error stop 'a map file does not match para.in'
+    end if
+    close (12)
+    if (announce) then
+      do q = 6, 66, 60
+        write (q, '(a,a)') ' read ', fname
+      end do
+    end if
+  end subroutine
+
+  ! lon lat depth Vs fast-axis angle, amplitude, Gc/L %, Gs/L %: the arithmetic of write_azimuthal (dazim_main.f90)
+  subroutine write_azimuthal(unit)
+    integer, intent(in) :: unit
+    integer :: k1, j1, i1
+    real :: c2, s2, amp, ang, vsref
+    real*8 :: pi8 = real(3.1415926535898, 8)
+    do k1 = 1, nz - 1
+      do j1 = 1, ny - 2
+        do i1 = 1, nx - 2
+          c2 = gcf(i1, j1, k1); s2 = gsf(i1, j1, k1)
+          amp = 0.5*sqrt(c2**2 + s2**2)
+          ang = atan2(s2, c2)/pi8*180
+          if (ang < 0.0) ang = ang + 360
+          ang = 0.5*ang
+          vsref = (vsf(i1 + 1, j1 + 1, k1) + vsf(i1 + 1, j1 + 1, k1 + 1))/2
+          write (unit, '(8f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1 + 1), vsref, ang, amp, &
+            gcf(i1, j1, k1)*100, gsf(i1, j1, k1)*100
+        end do
+      end do
+    end do
+  end subroutine
+
+  ! period maps of A1 = sum_k Lsen*Gc, A2 = sum_k Lsen*Gs on the final model: the arithmetic of write_period_azimuthal
+  subroutine write_period_azimuthal(unit)
+    integer, intent(in) :: unit
+    integer :: t1, j1, i1, k1
+    real :: c2, s2, amp, ang, rel, isoC
+    real*8 :: pi8 = real(3.1415926535898, 8)
+    do t1 = 1, kmax
+      do j1 = 1, ny - 2
+        do i1 = 1, nx - 2
+          c2 = 0.0; s2 = 0.0
+          do k1 = 1, nz - 1
+            c2 = c2 + lsen(j1*nx + i1 + 1, t1, k1)*gcf(i1, j1, k1)
+            s2 = s2 + lsen(j1*nx + i1 + 1, t1, k1)*gsf(i1, j1, k1)
+          end do
+          amp = sqrt(c2**2 + s2**2)
+          isoC = real(pv(j1*nx + i1 + 1, t1))
+          rel = amp/isoC
+          ang = atan2(s2, c2)/pi8*180
+          if (ang < 0.0) ang = ang + 360
+          ang = 0.5*ang
+          write (unit, '(10f10.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), isoC, ang, rel, amp, c2, s2
+        end do
+      end do
+    end do
+  end subroutine
+end program

@@ -34,6 +34,8 @@ module dazim_mod
   ! the per-period map inversion (host/dazim_maps.f90)
   public :: dazim_dispersion_kernels, dazim_rays_build_G_maps, dazim_csr_append_laplacian2d, dazim_phase_map_update, &
             dazim_assemble_G_maps
+  ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
+  public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -194,6 +196,23 @@ module dazim_mod
       type(c_ptr), value :: ctx, A
       integer(c_int), value :: nx, ny, nmap
       real(c_float) :: w(*)
+    end function
+    integer(c_int) function dazim_vs_kernels(ctx, nx, ny, nz, kmax, vel, svs, svp, srho, skern) bind(C, name="dazim_vs_kernels")
+      import
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, nz, kmax
+      real(c_float) :: vel(*)
+      real(c_double) :: svs(*), svp(*), srho(*), skern(*)
+    end function
+    ! kern: c_loc of skern (real*8, kern_fp32 = 0) or of Lsen_Gsc (real*4, kern_fp32 = 1)
+    integer(c_int) function dazim_column_lsq(ctx, nx, ny, nlay, kmax, kern_fp32, kern, nrhs, rhs, wdat, smooth, damp, x, n_empty, &
+        stats) bind(C, name="dazim_column_lsq")
+      import
+      type(c_ptr), value :: ctx, kern
+      integer(c_int), value :: nx, ny, nlay, kmax, kern_fp32, nrhs
+      real(c_float), value :: smooth, damp
+      real(c_float) :: rhs(*), wdat(*), x(*), stats(*)
+      integer(c_int) :: n_empty
     end function
     integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
         bind(C, name="dazim_phase_map_update")

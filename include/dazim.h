@@ -72,7 +72,7 @@ int dazim_sync(dazim_ctx *ctx);
 unsigned long long dazim_hash64(const void *data, size_t bytes);
 void *dazim_stream(dazim_ctx *ctx); /* the hipStream_t every kernel of this ctx is launched on */
 /* seconds spent in the last call's kernels, measured with HIP events on the ctx stream; name
- * selects the kernel ("fmm", "gridder", "disp", "ti", "rays", "spmv", "spmvt", "lsmr"); <0 if unknown */
+ * selects the kernel ("fmm", "gridder", "disp", "ti", "rays", "spmv", "spmvt", "lsmr", "vs_kernels", "column_lsq"); <0 if unknown */
 double dazim_last_kernel_seconds(const dazim_ctx *ctx, const char *name);
 /* the same table with a status: times of the last call's kernels AND the counts / choices the library reports ("fmm.wg_per_cu",
  * "spmv.kind", "lsmr.nranks", "fmm.field_pops" ...; docs/OPTIONS.md).  0 and *value, or DAZIM_E_BAD_ARG for an unknown name.      */
@@ -261,6 +261,26 @@ int dazim_rays_build_G_maps(dazim_ctx *ctx, int nx, int ny, float goxd, float go
 int dazim_csr_append_laplacian2d(dazim_ctx *ctx, dazim_csr *A, int nx, int ny, int nmap, const float *w);
 int dazim_phase_map_update(dazim_ctx *ctx, int nx, int ny, int kmax, int azim, double *pv, float *dm, float minc, float maxc,
                            float *a1, float *a2, float *stats);
+
+/* ---- from the maps to a depth model, cell by cell (the second step of the two-step method) ------------------
+ * dazim_vs_kernels: skern [nz][kmax][nx*ny] fp64 = sen_vp*coe_a + sen_rho*coe_rho + sen_vs at vel (the Brocher derivatives of the
+ *   cell's velocity, inv/CalSurfG.f90:1339-1364): the table the 3-D rows of dazim_rays_build_G multiply, bit for bit (an iso row
+ *   entry of layer k is (float)(skern[k] * (double)fdm)).  vel [nz][ny][nx], sen_* [nz][kmax][nx*ny] from
+ *   dazim_dispersion_kernels.
+ * dazim_column_lsq: one regularised least-squares problem per inner cell (jj, kk), column jj*nx + kk of the kernel table: for each
+ *   right-hand side r, the x that minimises ||diag(w)(K x - r)||^2 + smooth^2 ||L x||^2 + damp^2 ||x||^2, K the cell's kmax x nlay
+ *   slice of kern, L the depth rule of TikhRegul (inv/TikhRegul.f90:2) on one column (first and last knot the single entry 2, an
+ *   inner knot 2, -1, -1).  fp64 throughout (normal equations, Cholesky), x rounded to fp32.
+ *   kern [>= nlay][kmax][nx*ny]: fp64 when kern_fp32 == 0 (skern), fp32 otherwise (Lsen_Gsc); the first nlay layers are read.
+ *   rhs [nrhs][kmax][ny-2][nx-2]; wdat [kmax][ny-2][nx-2] = 1/sigma per period and cell, 0 = no data, nullable (all ones).
+ *   x out [nrhs][nlay][ny-2][nx-2]: the dv layout of dazim_model_update (nrhs 1: its dVs block; nrhs 2: its Gc and Gs blocks).
+ *   A cell whose weights are all 0 gets x = 0 exactly; n_empty (host, nullable) counts those cells.  stats (host, nullable)
+ *   [nrhs][kmax][2] = RMS over the cells with w != 0 of r and of r - K x.  Refused (DAZIM_E_BAD_ARG): nlay outside 1..63, kmax
+ *   outside 1..60, nrhs not 1 or 2, a negative smooth or damp, smooth == damp == 0.  One launch, one wavefront per cell.     */
+int dazim_vs_kernels(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, const float *vel, const double *sen_vs, const double *sen_vp,
+                     const double *sen_rho, double *skern);
+int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int kern_fp32, const void *kern, int nrhs, const float *rhs,
+                     const float *wdat, float smooth, float damp, float *x, int *n_empty, float *stats);
 
 /* ---- N4: what surrounds the solve in the outer iteration, on the device ------------------------------
  * = TikhonovRegularization / TikhRegul_joint (inv/TikhRegul.f90:2-104, :107-209): appends nblock * maxvp rows, maxvp =

@@ -1,0 +1,74 @@
+"""Times of the second step of the two-step method (profiles/depth_from_maps.md).
+
+    python tools/depth_step.py [--reps R] [--big N]
+
+On bench.py's S-256 model grid (54 x 54 columns, 12 knots, 16 periods) and on an N x N grid of the same model (default 202: 200 x 200
+inner cells), every array on the device, R rounds of: the dispersion call with kernels (kernel seconds "disp"; "disp.copies" too
+where the perturbed copies ran on the auxiliary stream), dazim_vs_kernels ("vs_kernels"), dazim_column_lsq with the fp64 table and
+one right-hand side and with the fp32 Lsen_Gsc table and two ("column_lsq").  Kernel seconds are dazim_last_kernel_seconds (HIP
+events on the context stream).  Prints one JSON line per grid with the medians and the ratio solve / dispersion."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def one_grid(ctx, n, reps):
+    import torch
+    import bench
+    bench.NX = bench.NY = n
+    dev = torch.device("cuda:0")
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    vel = T(bench.s256_model())
+    nz, kmax, nlay = len(bench.DEPZ), len(bench.PERIODS), len(bench.DEPZ) - 1
+    ncell = (n - 2) * (n - 2)
+    rng = np.random.default_rng(1)
+    r1 = T(0.05 * rng.standard_normal((1, kmax, n - 2, n - 2)).astype(np.float32))
+    r2 = T(0.01 * rng.standard_normal((2, kmax, n - 2, n - 2)).astype(np.float32))
+    w = T(np.full((kmax, n - 2, n - 2), 100.0, np.float32))
+    pv, sen, _ = ctx.depthkernel(vel, bench.DEPZ, bench.PERIODS, bench.MINTHK)
+    lsen = ctx.ti_kernels(vel, bench.DEPZ, bench.PERIODS, bench.MINTHK, pv)
+    skern = ctx.vs_kernels(vel, sen)
+    x1 = torch.empty((1, nlay, n - 2, n - 2), dtype=torch.float32, device=dev)
+    x2 = torch.empty((2, nlay, n - 2, n - 2), dtype=torch.float32, device=dev)
+    runs = {"disp_s": [], "disp_copies_s": [], "vs_kernels_s": [], "column_lsq_fp64_nrhs1_s": [], "column_lsq_fp32_nrhs2_s": []}
+    for rep in range(reps + 1):   # (round 0: warm-up -- code objects, scratch buffers)
+        ctx.depthkernel(vel, bench.DEPZ, bench.PERIODS, bench.MINTHK, pv=pv, sen=sen)
+        ctx.sync()
+        t = {"disp_s": ctx.kernel_seconds("disp"), "disp_copies_s": ctx.kernel_seconds("disp.copies")}
+        ctx.vs_kernels(vel, sen, skern=skern)
+        t["vs_kernels_s"] = ctx.kernel_seconds("vs_kernels")
+        ctx.column_lsq(n, n, nlay, skern, r1, w, 2.0, 0.0, x=x1)
+        t["column_lsq_fp64_nrhs1_s"] = ctx.kernel_seconds("column_lsq")
+        ctx.column_lsq(n, n, nlay, lsen, r2, w, 2.0, 0.0, x=x2)
+        t["column_lsq_fp32_nrhs2_s"] = ctx.kernel_seconds("column_lsq")
+        if rep:
+            for k, v in t.items():
+                runs[k].append(v)
+    med = {k: float(np.median(v)) for k, v in runs.items()}
+    disp = med["disp_s"] + max(med["disp_copies_s"], 0.0)
+    assert torch.isfinite(x1).all() and torch.isfinite(x2).all()
+    return {"grid": f"{n}x{n} columns ({ncell} inner cells), {nz} knots, {kmax} periods", "reps": reps, "median": med,
+            "solve_fp64_over_disp": med["column_lsq_fp64_nrhs1_s"] / disp, "solve_fp32_over_disp": med["column_lsq_fp32_nrhs2_s"] / disp,
+            "runs": runs}
+
+
+def main():
+    import dazimsurftomo_amd as dz
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--big", type=int, default=202)
+    a = ap.parse_args()
+    ctx = dz.Context(0)
+    for n in (54, a.big):
+        print(json.dumps(one_grid(ctx, n, a.reps)), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
