@@ -79,6 +79,7 @@ class Context:
     def __init__(self, device=0):
         self.lib = load()
         self._h = C.c_void_p()
+        self.device = int(device)
         rc = self.lib.dazim_create(C.byref(self._h), int(device))
         if rc:
             raise DazimError(rc, "dazim_create failed (no GPU visible?)")
@@ -386,6 +387,21 @@ class Context:
                                               _ptr(x, np.float32), C.byref(ne), _ptr(st)))
         return x, ne.value, st
 
+    def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50):
+        """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
+        cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
+        data."""
+        nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
+        vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
+        vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
+        cobs, wdat = (np.ascontiguousarray(a, np.float32).reshape(kmax, ny - 2, nx - 2) for a in (cobs, wdat))
+        assert nlay * ncell == vmin.size
+        h, ne = C.c_void_p(), C.c_int(0)
+        self._check(self.lib.dazim_mc_create(self._h, nx, ny, nz, kmax, int(nchain), int(nbin), C.c_ulonglong(int(seed)), _ptr(vel0),
+                                             _ptr(vmin), _ptr(vmax), _ptr(cobs), _ptr(wdat), C.c_float(step), int(nadapt),
+                                             C.byref(h), C.byref(ne)))
+        return MonteCarlo(self, h, nx, ny, nz, kmax, nchain, nbin, ne.value)
+
     def ray_paths(self):
         """ray geometries of the last rays_build_G call made with option rays.keep_paths = 1: a list of [nrp][2] arrays
         (colatitude, longitude in rad; receiver first, source last) -- the reference's raypath_refmdl_<T>s.dat content"""
@@ -461,6 +477,89 @@ class Context:
         self._check(rc)
         return x, dict(istop=istop.value, itn=itn.value, normA=sc[0].value, condA=sc[1].value,
                        normr=sc[2].value, normAr=sc[3].value, normx=sc[4].value)
+
+
+class MonteCarlo:
+    """Metropolis chains of Context.mc_create (dazim_mc): every chain resident on the device"""
+
+    def __init__(self, ctx, handle, nx, ny, nz, kmax, nchain, nbin, n_empty):
+        self.ctx, self._h = ctx, handle
+        self.nx, self.ny, self.nz, self.kmax, self.nchain, self.nbin, self.n_empty = nx, ny, nz, kmax, nchain, nbin, n_empty
+        self.nlay, self.ncell = nz - 1, (nx - 2) * (ny - 2)
+        self.ncs = self.ncell - n_empty
+        self.ncol = self.ncs * nchain
+
+    def proposals(self):
+        """the models the next step evaluates: a torch view [nz][ncol] (fp32, on the context's device) of the handle's array, no
+        copy.  The next step overwrites it, and it is invalid once free() has run."""
+        import torch
+        p, n = C.c_void_p(), C.c_int64(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_proposals(self._h, C.byref(p), C.byref(n)))
+        assert n.value == self.ncol
+        if n.value == 0:
+            return torch.zeros((self.nz, 0), dtype=torch.float32, device=torch.device("cuda", self.ctx.device))
+
+        class _Cai:   # (the CUDA array interface: torch wraps the device pointer without a copy)
+            __cuda_array_interface__ = dict(shape=(self.nz, n.value), typestr="<f4", data=(p.value, False), version=2, strides=None)
+        return torch.as_tensor(_Cai(), device=torch.device("cuda", self.ctx.device))
+
+    def step(self, pv, record):
+        """one step on pv[kmax][ncol] (fp64; numpy or torch-cuda), the curves of proposals(); record 0 = burn-in"""
+        shape = tuple(pv.shape)
+        kmax, ncol = (shape[0], shape[1]) if len(shape) == 2 else (self.kmax, -1)
+        if not _is_torch(pv):
+            pv = np.ascontiguousarray(pv, np.float64)
+        self.ctx._check(self.ctx.lib.dazim_mc_step(self.ctx._h, self._h, int(kmax), C.c_int64(int(ncol)), _ptr(pv, np.float64),
+                                                   int(record)))
+
+    def run(self, depz, sublayers, periods, nburn, nsample):
+        """nburn burn-in and nsample recorded steps with the dispersion forward model (dazim_mc_run); returns the proposals without
+        a root"""
+        depz = np.ascontiguousarray(depz, np.float32)
+        periods = np.ascontiguousarray(periods, np.float64)
+        assert len(depz) == self.nz and len(periods) == self.kmax
+        nr = C.c_int64(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_run(self.ctx._h, self._h, _ptr(depz), C.c_float(sublayers), _ptr(periods), int(nburn),
+                                                  int(nsample), C.byref(nr)))
+        return nr.value
+
+    def state(self):
+        """copies of the chain state: dict cur[nz][ncol], chi2[ncol], scale[sampled cells], step, sums[2][nlay][ncol],
+        hist[sampled cells][nlay][nbin], accepted[ncol], best[nlay][sampled cells], best_chi2[sampled cells]"""
+        cur = np.zeros((self.nz, self.ncol), np.float32)
+        chi2 = np.zeros(self.ncol, np.float64)
+        scale = np.zeros(self.ncs, np.float32)
+        sums = np.zeros((2, self.nlay, self.ncol), np.float64)
+        hist = np.zeros((self.ncs, self.nlay, self.nbin), np.uint32)
+        acc = np.zeros(self.ncol, np.int64)
+        best = np.zeros((self.nlay, self.ncs), np.float32)
+        best_chi2 = np.zeros(self.ncs, np.float64)
+        st = C.c_int64(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_state(self.ctx._h, self._h, _ptr(cur), _ptr(chi2), _ptr(scale), C.byref(st), _ptr(sums),
+                                                    _ptr(hist), _ptr(acc), _ptr(best), _ptr(best_chi2)))
+        return dict(cur=cur, chi2=chi2, scale=scale, step=st.value, sums=sums, hist=hist, accepted=acc, best=best, best_chi2=best_chi2)
+
+    def result(self):
+        """posterior statistics: dict mean, std, best, rhat [nlay][ny-2][nx-2], q [3][nlay][ny-2][nx-2], accept, chi2_best
+        [ny-2][nx-2]"""
+        shp = (self.nlay, self.ny - 2, self.nx - 2)
+        r = dict(mean=np.zeros(shp, np.float32), std=np.zeros(shp, np.float32), q=np.zeros((3,) + shp, np.float32),
+                 best=np.zeros(shp, np.float32), rhat=np.zeros(shp, np.float32), accept=np.zeros(shp[1:], np.float32),
+                 chi2_best=np.zeros(shp[1:], np.float32))
+        self.ctx._check(self.ctx.lib.dazim_mc_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in
+                                                                              ("mean", "std", "q", "best", "rhat", "accept", "chi2_best"))))
+        return r
+
+    def free(self):
+        if self._h:
+            self.ctx.lib.dazim_mc_free(self.ctx._h if self.ctx._h else None, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class SparseMatrix:

@@ -1,0 +1,622 @@
+// column_mc.hip -- Monte-Carlo Vs per map cell: random-walk Metropolis chains on the knots of each cell's
+// Vs column, every chain resident on the device, the forward model the unchanged dispersion kernel (dazim_dispersion_kernels,
+// curves only, one column per chain).
+//
+// k_mc_init draws the start models from the prior; k_mc_step runs one wavefront per sampled cell, one lane per chain: chi^2 of the
+// curves of the proposals, accept / reject, record, adapt the step scale, draw the next proposals; k_mc_final turns the records into
+// the posterior statistics.  Random numbers are Philox4x32-10 keyed on the seed and counted by (step, chain, block): the results
+// depend on the seed and the inputs only.  Sums across chains run over the lanes in chain order inside one lane (k_mc_final); the
+// histogram counts are the only atomics, on integers.
+#include "dazim_internal.h"
+
+#include <chrono>
+#include <cmath>
+
+namespace {
+
+constexpr int MC_WAVE = 64, MC_MAXLAY = 63, MC_MAXPER = 60, MC_MAXCHAIN = 64;
+// Reflections of a proposal into its box.  u >= 2^-33 bounds |z| by sqrt(66 ln 2) < 6.77, and s <= 0.5 (dazim_mc_create refuses a
+// larger start, the adaptation keeps it there) bounds the step by 3.39 box widths; each pass takes one width off the excess, so 4
+// passes always suffice.  The cap and the clamp behind it only make the loop's bound visible: they never act on a valid handle.
+constexpr int MC_MAXFOLD = 8;
+constexpr float MC_SMIN = 1e-3f, MC_SMAX = 0.5f;
+
+// Philox4x32-10 (Salmon et al., SC'11): c = counter in, block out; key (k0, k1) = the seed's low and high words
+__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
+  for (int r = 0; r < 10; r++) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
+    const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0, hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+  }
+}
+
+__device__ __forceinline__ void mc_block(unsigned w[4], long long step, unsigned gid, unsigned blk, unsigned long long seed) {
+  w[0] = (unsigned)step;
+  w[1] = gid;
+  w[2] = blk;
+  w[3] = 0u;
+  philox4x32_10(w, (unsigned)seed, (unsigned)(seed >> 32));
+}
+
+__device__ __forceinline__ double mc_uniform(unsigned w) { return ((double)w + 0.5) * 2.3283064365386962890625e-10; }   // (w + 0.5) 2^-32
+
+struct McDev {
+  int nx, ny, nz, nlay, kmax, nchain, nbin, ncell, ncs;
+  long ncol;
+  unsigned long long seed;
+  const int *cell_of;          // [ncs] inner-cell index of each sampled cell
+  const int *cs_of;            // [ncell] sampled index of each inner cell, -1 = no data
+  const float *vel0;           // [nz][ny][nx]
+  const float *vmin, *vmax;    // [nlay][ncell]
+  const float *cobs, *wdat;    // [kmax][ncell]
+  float *cur, *prop;           // [nz][ncol]
+  double *chi2;                // [ncol]
+  float *scale;                // [ncs]
+  int *acc_win;                // [ncs]
+  double *sums;                // [2][nlay][ncol]
+  unsigned *hist;              // [ncs][nlay][nbin]
+  long long *accepted;         // [ncol]
+  float *best;                 // [nlay][ncs]
+  double *best_chi2;           // [ncs]
+  unsigned long long *counters;   // [0] proposals without a root, [1] accepted moves of recorded steps
+};
+
+// the next proposal of chain (cs, ch) from its current state: v' = v + s (vmax - vmin) z in fp64, reflected into the box, fp32
+__device__ void mc_propose(const McDev &M, int cs, int ch, long long step, float s) {
+  const int cell = M.cell_of[cs];
+  const long col = (long)cs * M.nchain + ch;
+  const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
+  for (int q = 0; q * 4 < M.nlay; q++) {
+    unsigned w[4];
+    mc_block(w, step, gid, 1u + (unsigned)q, M.seed);
+    const double r0 = sqrt(-2.0 * log(mc_uniform(w[0]))), t0 = 6.283185307179586 * mc_uniform(w[1]);
+    const double r1 = sqrt(-2.0 * log(mc_uniform(w[2]))), t1 = 6.283185307179586 * mc_uniform(w[3]);
+    const double z[4] = {r0 * cos(t0), r0 * sin(t0), r1 * cos(t1), r1 * sin(t1)};
+    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) {
+      const int k = q * 4 + i;
+      const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
+      const double d = (double)s * (hi - lo);
+      double v = (double)M.cur[k * M.ncol + col] + d * z[i];
+      for (int r = 0; r < MC_MAXFOLD && (v < lo || v > hi); r++) v = v < lo ? 2.0 * lo - v : 2.0 * hi - v;
+      M.prop[k * M.ncol + col] = (float)fmin(fmax(v, lo), hi);
+    }
+  }
+}
+
+// one wavefront per sampled cell, lane = chain: the start models (step 0 of the counter), the fixed last knot, the bookkeeping
+__global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
+  const int cs = blockIdx.x, ch = threadIdx.x;
+  if (ch >= M.nchain) return;
+  const int cell = M.cell_of[cs], nvx = M.nx - 2, j = cell / nvx, i = cell - j * nvx;
+  const long col = (long)cs * M.nchain + ch, c0 = (long)(j + 1) * M.nx + (i + 1), nxy = (long)M.nx * M.ny;
+  const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
+  for (int q = 0; q * 4 < M.nlay; q++) {
+    unsigned w[4];
+    mc_block(w, 0, gid, 1u + (unsigned)q, M.seed);
+    for (int e = 0; e < 4 && q * 4 + e < M.nlay; e++) {
+      const int k = q * 4 + e;
+      const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
+      const float v = (float)(lo + (hi - lo) * mc_uniform(w[e]));
+      M.prop[k * M.ncol + col] = v;
+      M.cur[k * M.ncol + col] = v;
+    }
+  }
+  const float vl = M.vel0[(long)(M.nz - 1) * nxy + c0];
+  M.prop[(long)(M.nz - 1) * M.ncol + col] = vl;
+  M.cur[(long)(M.nz - 1) * M.ncol + col] = vl;
+  M.chi2[col] = INFINITY;
+  M.accepted[col] = 0;
+  for (int k = 0; k < M.nlay; k++) {
+    M.sums[(long)k * M.ncol + col] = 0.0;
+    M.sums[((long)M.nlay + k) * M.ncol + col] = 0.0;
+  }
+  if (ch == 0) {
+    M.scale[cs] = step0;
+    M.acc_win[cs] = 0;
+    M.best_chi2[cs] = INFINITY;
+    for (int k = 0; k < M.nlay; k++) M.best[(long)k * M.ncs + cs] = M.vel0[(long)k * nxy + c0];
+  }
+}
+
+// one step, one wavefront per sampled cell, lane = chain.  pv [kmax][ncol]: the curves of the proposals.
+// first: the proposals are the start models -- they become the state, no decision.  adapt: the end of an adaptation window.
+__global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__restrict__ pv, long long step, int first, int record,
+                                                     int adapt, int nadapt) {
+  __shared__ float s_scale;
+  __shared__ int s_win;
+  const int cs = blockIdx.x, ch = threadIdx.x;
+  const bool act = ch < M.nchain;
+  const int cell = M.cell_of[cs];
+  const long col = (long)cs * M.nchain + ch;
+  const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
+  double chi2p = 0.0;
+  bool acc = false;
+  if (act) {
+    for (int p = 0; p < M.kmax; p++) {
+      const float w = M.wdat[(long)p * M.ncell + cell];
+      if (w == 0.0f) continue;
+      const double c = pv[(long)p * M.ncol + col];
+      if (c == 0.0) {   // no root at a period with data
+        chi2p = INFINITY;
+        break;
+      }
+      const double r = (double)w * ((double)M.cobs[(long)p * M.ncell + cell] - c);
+      chi2p += r * r;
+    }
+    if (first) {
+      acc = true;
+    } else {
+      const double chi2c = M.chi2[col];
+      if (isinf(chi2c)) {
+        acc = !isinf(chi2p);
+      } else {
+        unsigned w[4];
+        mc_block(w, step, gid, 0u, M.seed);
+        acc = log(mc_uniform(w[0])) < -0.5 * (chi2p - chi2c);
+      }
+    }
+    if (acc) {
+      for (int k = 0; k < M.nlay; k++) M.cur[k * M.ncol + col] = M.prop[k * M.ncol + col];
+      M.chi2[col] = chi2p;
+    }
+  }
+  const int nacc = first ? 0 : __popcll(__ballot(act && acc));
+  const int nnoroot = __popcll(__ballot(act && isinf(chi2p)));
+  if (ch == 0) {
+    if (nnoroot) atomicAdd(&M.counters[0], (unsigned long long)nnoroot);
+    float s = M.scale[cs];
+    if (!record) {
+      int win = M.acc_win[cs] + nacc;
+      if (adapt) {
+        const double rate = (double)win / ((double)nadapt * (double)M.nchain);
+        if (rate > 0.40) s = s * 1.25f;
+        else if (rate < 0.20) s = s / 1.25f;
+        s = fminf(fmaxf(s, MC_SMIN), MC_SMAX);
+        M.scale[cs] = s;
+        win = 0;
+      }
+      M.acc_win[cs] = win;
+    } else if (nacc) {
+      atomicAdd(&M.counters[1], (unsigned long long)nacc);
+    }
+    s_scale = s;
+  }
+  if (record) {
+    if (act) {
+      if (!first && acc) M.accepted[col] += 1;
+      for (int k = 0; k < M.nlay; k++) {
+        const double v = (double)M.cur[k * M.ncol + col];
+        M.sums[(long)k * M.ncol + col] += v;
+        M.sums[((long)M.nlay + k) * M.ncol + col] += v * v;
+        const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
+        int b = (int)((v - lo) / (hi - lo) * (double)M.nbin);
+        b = b < 0 ? 0 : (b >= M.nbin ? M.nbin - 1 : b);
+        atomicAdd(&M.hist[((long)cs * M.nlay + k) * M.nbin + b], 1u);
+      }
+    }
+    // the lowest chi^2 of this step, the first chain on ties; it replaces the cell's best only when strictly lower
+    double m = act ? M.chi2[col] : INFINITY;
+    int l = ch;
+    for (int o = 32; o > 0; o >>= 1) {
+      const double m2 = __shfl_xor(m, o);
+      const int l2 = __shfl_xor(l, o);
+      if (m2 < m || (m2 == m && l2 < l)) {
+        m = m2;
+        l = l2;
+      }
+    }
+    if (ch == 0) s_win = m < M.best_chi2[cs] ? l : -1;
+    __syncthreads();
+    const int win = s_win;
+    if (win >= 0) {
+      if (ch < M.nlay) M.best[(long)ch * M.ncs + cs] = M.cur[(long)ch * M.ncol + (long)cs * M.nchain + win];
+      if (ch == 0) M.best_chi2[cs] = m;
+    }
+  }
+  __syncthreads();
+  if (act) mc_propose(M, cs, ch, step, s_scale);
+}
+
+// posterior statistics, one wavefront per inner cell, lane = knot.  nrec: recorded steps; ndec: recorded steps with a decision
+__global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, long long ndec, float *__restrict__ mean,
+                                                      float *__restrict__ stdv, float *__restrict__ q, float *__restrict__ best,
+                                                      float *__restrict__ rhat, float *__restrict__ accept, float *__restrict__ chi2_best) {
+  const int cell = blockIdx.x, k = threadIdx.x;
+  const int cs = M.cs_of[cell], nvx = M.nx - 2, j = cell / nvx, i = cell - j * nvx;
+  const long c0 = (long)(j + 1) * M.nx + (i + 1), nxy = (long)M.nx * M.ny, o = (long)k * M.ncell + cell;
+  if (cs < 0) {   // no data: the start model
+    if (k < M.nlay) {
+      const float v = M.vel0[(long)k * nxy + c0];
+      mean[o] = v;
+      stdv[o] = 0.0f;
+      best[o] = v;
+      rhat[o] = NAN;
+      for (int e = 0; e < 3; e++) q[(long)e * M.nlay * M.ncell + o] = v;
+    }
+    if (k == 0) {
+      accept[cell] = 0.0f;
+      chi2_best[cell] = 0.0f;
+    }
+    return;
+  }
+  if (k < M.nlay) {
+    const double N = (double)nrec, Mc = (double)M.nchain;
+    double s1 = 0.0, s2 = 0.0, sm = 0.0;
+    for (int ch = 0; ch < M.nchain; ch++) {
+      const long col = (long)cs * M.nchain + ch;
+      const double a = M.sums[(long)k * M.ncol + col], b = M.sums[((long)M.nlay + k) * M.ncol + col];
+      s1 += a;
+      s2 += b;
+      sm += a / N;
+    }
+    const double mu = s1 / (N * Mc);
+    mean[o] = (float)mu;
+    stdv[o] = (float)sqrt(fmax(s2 / (N * Mc) - mu * mu, 0.0));
+    // R-hat (BDA3, chains not split): W the mean within-chain variance, B / N the variance of the chain means
+    double W = 0.0, B = 0.0;
+    const double mbar = sm / Mc;
+    for (int ch = 0; ch < M.nchain; ch++) {
+      const long col = (long)cs * M.nchain + ch;
+      const double a = M.sums[(long)k * M.ncol + col], b = M.sums[((long)M.nlay + k) * M.ncol + col];
+      const double mj = a / N;
+      W += (b - N * mj * mj) / (N - 1.0);
+      B += (mj - mbar) * (mj - mbar);
+    }
+    W /= Mc;
+    B *= N / (Mc - 1.0);
+    rhat[o] = (M.nchain > 1 && nrec > 1 && W > 0.0) ? (float)sqrt(((N - 1.0) / N * W + B / N) / W) : NAN;
+    // 2.5 / 50 / 97.5 % from the counts, linear inside a bin
+    const unsigned *h = M.hist + ((long)cs * M.nlay + k) * M.nbin;
+    const double lo = (double)M.vmin[o], hi = (double)M.vmax[o], tot = N * Mc;
+    const double qs[3] = {0.025, 0.5, 0.975};
+    for (int e = 0; e < 3; e++) {
+      const double target = qs[e] * tot;
+      double cum = 0.0, pos = (double)M.nbin;
+      for (int b = 0; b < M.nbin; b++) {
+        const double nb = (double)h[b];
+        if (nb > 0.0 && cum + nb >= target) {
+          pos = (double)b + (target - cum) / nb;
+          break;
+        }
+        cum += nb;
+      }
+      q[(long)e * M.nlay * M.ncell + o] = (float)(lo + pos * (hi - lo) / (double)M.nbin);
+    }
+    best[o] = M.best[(long)k * M.ncs + cs];
+  }
+  if (k == 0) {
+    long long a = 0;
+    for (int ch = 0; ch < M.nchain; ch++) a += M.accepted[(long)cs * M.nchain + ch];
+    accept[cell] = ndec > 0 ? (float)((double)a / ((double)ndec * (double)M.nchain)) : 0.0f;
+    chi2_best[cell] = (float)M.best_chi2[cs];
+  }
+}
+
+// a host copy of a host or device array
+template <class T>
+int mc_to_host(dazim_ctx *ctx, const T *p, size_t n, std::vector<T> &out) {
+  out.resize(n);
+  if (n == 0) return 0;
+  if (dz_is_device_ptr(p)) {
+    DZ_HIP(hipMemcpyAsync(out.data(), p, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    DZ_HIP(hipStreamSynchronize(ctx->stream));
+  } else {
+    memcpy(out.data(), p, n * sizeof(T));
+  }
+  return 0;
+}
+
+}  // namespace
+
+struct dazim_mc {
+  dazim_ctx *ctx = nullptr;
+  McDev d{};
+  int nadapt = 1;
+  int64_t nstep = 0;        // steps done; 0 = the start models are drawn, not evaluated
+  int64_t nburn_dec = 0;    // burn-in steps with a decision (the adaptation clock)
+  int64_t nrec = 0, nrec_dec = 0;
+  int n_empty = 0;
+  double *pv = nullptr;     // [kmax][ncol]: the curves dazim_mc_run computes
+  std::vector<void *> blocks;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+namespace {
+
+template <class T>
+int mc_alloc(dazim_mc *mc, size_t n, T **out) {
+  dazim_ctx *ctx = mc->ctx;
+  void *p = nullptr;
+  DZ_HIP(dz_malloc_retry(ctx, &p, (n ? n : 1) * sizeof(T)));
+  mc->blocks.push_back(p);
+  *out = (T *)p;
+  return 0;
+}
+
+int mc_release(dazim_mc *mc) {
+  for (void *p : mc->blocks) (void)hipFree(p);
+  if (mc->e0) (void)hipEventDestroy(mc->e0);
+  if (mc->e1) (void)hipEventDestroy(mc->e1);
+  delete mc;
+  return 0;
+}
+
+// one step on the curves pv (device) of the current proposals; enqueued on the ctx stream, no host wait
+int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
+  const bool first = mc->nstep == 0;
+  bool adapt = false;
+  if (!record && !first) {
+    mc->nburn_dec++;
+    adapt = mc->nburn_dec % mc->nadapt == 0;
+  }
+  const long long step = mc->nstep + 1;
+  if (mc->d.ncs > 0) {
+    DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
+    hipLaunchKernelGGL(k_mc_step, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), 0, ctx->stream, mc->d, pv, step, (int)first, record,
+                       (int)adapt, mc->nadapt);
+    DZ_HIP(hipGetLastError());
+    DZ_HIP(hipEventRecord(mc->e1, ctx->stream));
+  }
+  mc->nstep = step;
+  if (record) {
+    mc->nrec++;
+    if (!first) mc->nrec_dec++;
+  }
+  return 0;
+}
+
+int mc_check(dazim_ctx *ctx, dazim_mc *mc, const char *what) {
+  if (!ctx || !mc) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: null context or handle", what);
+  if (mc->ctx != ctx) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: the handle belongs to another context", what);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dazim_mc_create(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, int nchain, int nbin, unsigned long long seed, const float *vel0_u,
+                    const float *vmin_u, const float *vmax_u, const float *cobs_u, const float *wdat_u, float step, int nadapt,
+                    dazim_mc **out, int *n_empty) {
+  if (!ctx || !out || !vel0_u || !vmin_u || !vmax_u || !cobs_u || !wdat_u || nx < 3 || ny < 3)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_create");
+  *out = nullptr;
+  const int nlay = nz - 1;
+  if (nlay < 1 || nlay > MC_MAXLAY) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: nlay %d outside 1..%d", nlay, MC_MAXLAY);
+  if (kmax < 1 || kmax > MC_MAXPER) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: kmax %d outside 1..%d", kmax, MC_MAXPER);
+  if (nchain < 1 || nchain > MC_MAXCHAIN)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: nchain %d outside 1..%d", nchain, MC_MAXCHAIN);
+  if (nbin < 2) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: nbin %d < 2", nbin);
+  if (!(step > 0.0f && step <= MC_SMAX)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: step %g outside (0, %g]", step, MC_SMAX);
+  if (nadapt < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: nadapt %d < 1", nadapt);
+  DZ_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = dz_join_aux(ctx))) return rc;
+  const int ncell = (nx - 2) * (ny - 2);
+  std::vector<float> vel0, vmin, vmax, cobs, wdat;
+  if ((rc = mc_to_host(ctx, vel0_u, (size_t)nz * nx * ny, vel0)) || (rc = mc_to_host(ctx, vmin_u, (size_t)nlay * ncell, vmin)) ||
+      (rc = mc_to_host(ctx, vmax_u, (size_t)nlay * ncell, vmax)) || (rc = mc_to_host(ctx, cobs_u, (size_t)kmax * ncell, cobs)) ||
+      (rc = mc_to_host(ctx, wdat_u, (size_t)kmax * ncell, wdat)))
+    return rc;
+  for (size_t e = 0; e < vmin.size(); e++)
+    if (!std::isfinite(vmin[e]) || !std::isfinite(vmax[e]))
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: a non-finite bound at knot %d, cell %d", (int)(e / ncell), (int)(e % ncell));
+    else if (!(vmin[e] < vmax[e]))
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: vmin %g >= vmax %g at knot %d, cell %d", vmin[e], vmax[e],
+                     (int)(e / ncell), (int)(e % ncell));
+  for (size_t e = 0; e < cobs.size(); e++)
+    if (!std::isfinite(cobs[e]) || !std::isfinite(wdat[e]))
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_create: a non-finite cobs or wdat at period %d, cell %d", (int)(e / ncell),
+                     (int)(e % ncell));
+  std::vector<int> cell_of, cs_of(ncell, -1);
+  for (int c = 0; c < ncell; c++) {
+    bool data = false;
+    for (int p = 0; p < kmax; p++) data = data || wdat[(size_t)p * ncell + c] != 0.0f;
+    if (data) {
+      cs_of[c] = (int)cell_of.size();
+      cell_of.push_back(c);
+    }
+  }
+  dazim_mc *mc = new dazim_mc();
+  mc->ctx = ctx;
+  mc->nadapt = nadapt;
+  mc->n_empty = ncell - (int)cell_of.size();
+  McDev &M = mc->d;
+  M.nx = nx;
+  M.ny = ny;
+  M.nz = nz;
+  M.nlay = nlay;
+  M.kmax = kmax;
+  M.nchain = nchain;
+  M.nbin = nbin;
+  M.ncell = ncell;
+  M.ncs = (int)cell_of.size();
+  M.ncol = (long)M.ncs * nchain;
+  M.seed = seed;
+  int *ci, *co;
+  float *v0, *lo, *hi, *co_, *wd;
+  auto fail = [&](int r) { mc_release(mc); return r; };
+  if ((rc = mc_alloc(mc, cell_of.size(), &ci)) || (rc = mc_alloc(mc, (size_t)ncell, &co)) || (rc = mc_alloc(mc, vel0.size(), &v0)) ||
+      (rc = mc_alloc(mc, vmin.size(), &lo)) || (rc = mc_alloc(mc, vmax.size(), &hi)) || (rc = mc_alloc(mc, cobs.size(), &co_)) ||
+      (rc = mc_alloc(mc, wdat.size(), &wd)) || (rc = mc_alloc(mc, (size_t)nz * M.ncol, &M.cur)) ||
+      (rc = mc_alloc(mc, (size_t)nz * M.ncol, &M.prop)) || (rc = mc_alloc(mc, (size_t)M.ncol, &M.chi2)) ||
+      (rc = mc_alloc(mc, (size_t)M.ncs, &M.scale)) || (rc = mc_alloc(mc, (size_t)M.ncs, &M.acc_win)) ||
+      (rc = mc_alloc(mc, (size_t)2 * nlay * M.ncol, &M.sums)) || (rc = mc_alloc(mc, (size_t)M.ncs * nlay * nbin, &M.hist)) ||
+      (rc = mc_alloc(mc, (size_t)M.ncol, &M.accepted)) || (rc = mc_alloc(mc, (size_t)nlay * M.ncs, &M.best)) ||
+      (rc = mc_alloc(mc, (size_t)M.ncs, &M.best_chi2)) || (rc = mc_alloc(mc, (size_t)2, &M.counters)) ||
+      (rc = mc_alloc(mc, (size_t)kmax * M.ncol, &mc->pv)))
+    return fail(rc);
+  M.cell_of = ci;
+  M.cs_of = co;
+  M.vel0 = v0;
+  M.vmin = lo;
+  M.vmax = hi;
+  M.cobs = co_;
+  M.wdat = wd;
+  auto up = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+  };
+  hipError_t e = hipSuccess;
+  if ((e = up(ci, cell_of.data(), cell_of.size() * 4)) != hipSuccess || (e = up(co, cs_of.data(), cs_of.size() * 4)) != hipSuccess ||
+      (e = up(v0, vel0.data(), vel0.size() * 4)) != hipSuccess || (e = up(lo, vmin.data(), vmin.size() * 4)) != hipSuccess ||
+      (e = up(hi, vmax.data(), vmax.size() * 4)) != hipSuccess || (e = up(co_, cobs.data(), cobs.size() * 4)) != hipSuccess ||
+      (e = up(wd, wdat.data(), wdat.size() * 4)) != hipSuccess ||
+      (e = hipMemsetAsync(M.hist, 0, (size_t)M.ncs * nlay * nbin * sizeof(unsigned), ctx->stream)) != hipSuccess ||
+      (e = hipMemsetAsync(M.counters, 0, 16, ctx->stream)) != hipSuccess || (e = hipEventCreate(&mc->e0)) != hipSuccess ||
+      (e = hipEventCreate(&mc->e1)) != hipSuccess) {
+    mc_release(mc);
+    return dz_fail(ctx, -(int)e - 1000, "dazim_mc_create: %s", hipGetErrorString(e));
+  }
+  if (M.ncs > 0) {
+    hipLaunchKernelGGL(k_mc_init, dim3((unsigned)M.ncs), dim3(MC_WAVE), 0, ctx->stream, M, step);
+    if ((e = hipGetLastError()) != hipSuccess) {
+      mc_release(mc);
+      return dz_fail(ctx, -(int)e - 1000, "dazim_mc_create: %s", hipGetErrorString(e));
+    }
+  }
+  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+    mc_release(mc);
+    return dz_fail(ctx, -(int)e - 1000, "dazim_mc_create: %s", hipGetErrorString(e));
+  }
+  *out = mc;
+  if (n_empty) *n_empty = mc->n_empty;
+  return 0;
+}
+
+int dazim_mc_proposals(dazim_mc *mc, float **vel_dev, int64_t *ncol) {
+  if (!mc) return DAZIM_E_BAD_ARG;
+  if (vel_dev) *vel_dev = mc->d.prop;
+  if (ncol) *ncol = mc->d.ncol;
+  return 0;
+}
+
+int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv_u, int record) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_step"))) return rc;
+  if (kmax != mc->d.kmax || ncol != mc->d.ncol)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_step: curves [%d][%lld] for a handle of [%d][%ld]", kmax, (long long)ncol,
+                   mc->d.kmax, mc->d.ncol);
+  if ((!pv_u && ncol > 0) || (record != 0 && record != 1)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_step");
+  DZ_HIP(hipSetDevice(ctx->device));
+  if ((rc = dz_join_aux(ctx))) return rc;
+  DzBuf<double> pv;
+  if ((rc = pv.init(ctx, pv_u, (size_t)kmax * ncol, true, false))) return rc;
+  if ((rc = mc_launch_step(ctx, mc, pv.dev, record))) return rc;
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.0f;
+  if (mc->d.ncs > 0) DZ_HIP(hipEventElapsedTime(&ms, mc->e0, mc->e1));
+  ctx->ksec["mc_step"] = ms * 1e-3;
+  return 0;
+}
+
+int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
+                 int64_t *n_no_root) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_run"))) return rc;
+  if (!depz || !periods || nburn < 0 || nsample < 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_run");
+  if (dz_is_device_ptr(depz) || dz_is_device_ptr(periods))
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_run: depz and periods are host arrays");
+  DZ_HIP(hipSetDevice(ctx->device));
+  if ((rc = dz_join_aux(ctx))) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  unsigned long long c0[2] = {0, 0}, c1[2] = {0, 0};
+  DZ_HIP(hipMemcpy(c0, mc->d.counters, 16, hipMemcpyDeviceToHost));
+  double t_disp = 0.0, t_step = 0.0;
+  int64_t dec0 = mc->nrec_dec;
+  const int nstep = nburn + nsample;
+  for (int s = 0; s < nstep && mc->d.ncs > 0; s++) {
+    int nf = 0;
+    // curves only, one column per chain: nx = ncol, ny = 1 (the call ends with a wait for the stream: the step enqueued before it
+    // has finished when it returns)
+    if ((rc = dazim_dispersion_kernels(ctx, (int)mc->d.ncol, 1, mc->d.nz, mc->d.prop, depz, sublayers, mc->d.kmax, periods, mc->pv,
+                                       nullptr, nullptr, nullptr, &nf)))
+      return rc;
+    t_disp += ctx->ksec["disp"];
+    if (s > 0) {
+      float ms = 0.0f;
+      DZ_HIP(hipEventElapsedTime(&ms, mc->e0, mc->e1));
+      t_step += ms * 1e-3;
+    }
+    if ((rc = mc_launch_step(ctx, mc, mc->pv, s >= nburn ? 1 : 0))) return rc;
+  }
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (nstep > 0 && mc->d.ncs > 0) {
+    float ms = 0.0f;
+    DZ_HIP(hipEventElapsedTime(&ms, mc->e0, mc->e1));
+    t_step += ms * 1e-3;
+  }
+  DZ_HIP(hipMemcpy(c1, mc->d.counters, 16, hipMemcpyDeviceToHost));
+  const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const double dec = (double)(mc->nrec_dec - dec0) * (double)mc->d.ncol;
+  ctx->ksec["mc"] = wall;
+  ctx->ksec["mc.disp"] = t_disp;
+  ctx->ksec["mc.step"] = t_step;
+  ctx->ksec["mc.steps"] = mc->d.ncs > 0 ? nstep : 0;
+  ctx->ksec["mc.accept"] = dec > 0 ? (double)(c1[1] - c0[1]) / dec : 0.0;
+  ctx->ksec["mc.no_root"] = (double)(c1[0] - c0[0]);
+  if (n_no_root) *n_no_root = (int64_t)(c1[0] - c0[0]);
+  return 0;
+}
+
+int dazim_mc_state(dazim_ctx *ctx, dazim_mc *mc, float *cur, double *chi2, float *scale, int64_t *step, double *sums, unsigned *hist,
+                   int64_t *accepted, float *best, double *best_chi2) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_state"))) return rc;
+  DZ_HIP(hipSetDevice(ctx->device));
+  const McDev &M = mc->d;
+  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
+  };
+  DZ_HIP(get(cur, M.cur, (size_t)M.nz * M.ncol * 4));
+  DZ_HIP(get(chi2, M.chi2, (size_t)M.ncol * 8));
+  DZ_HIP(get(scale, M.scale, (size_t)M.ncs * 4));
+  DZ_HIP(get(sums, M.sums, (size_t)2 * M.nlay * M.ncol * 8));
+  DZ_HIP(get(hist, M.hist, (size_t)M.ncs * M.nlay * M.nbin * 4));
+  DZ_HIP(get(accepted, M.accepted, (size_t)M.ncol * 8));
+  DZ_HIP(get(best, M.best, (size_t)M.nlay * M.ncs * 4));
+  DZ_HIP(get(best_chi2, M.best_chi2, (size_t)M.ncs * 8));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (step) *step = mc->nstep;
+  return 0;
+}
+
+int dazim_mc_result(dazim_ctx *ctx, dazim_mc *mc, float *mean_u, float *std_u, float *q_u, float *best_u, float *rhat_u, float *accept_u,
+                    float *chi2_u) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_result"))) return rc;
+  if (!mean_u || !std_u || !q_u || !best_u || !rhat_u || !accept_u || !chi2_u)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_result");
+  if (mc->d.ncs > 0 && mc->nrec < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_result: no recorded step yet");
+  DZ_HIP(hipSetDevice(ctx->device));
+  const McDev &M = mc->d;
+  const size_t nk = (size_t)M.nlay * M.ncell;
+  DzBuf<float> mean, stdv, q, best, rhat, acc, chi2;
+  if ((rc = mean.init(ctx, mean_u, nk, false, true)) || (rc = stdv.init(ctx, std_u, nk, false, true)) ||
+      (rc = q.init(ctx, q_u, 3 * nk, false, true)) || (rc = best.init(ctx, best_u, nk, false, true)) ||
+      (rc = rhat.init(ctx, rhat_u, nk, false, true)) || (rc = acc.init(ctx, accept_u, (size_t)M.ncell, false, true)) ||
+      (rc = chi2.init(ctx, chi2_u, (size_t)M.ncell, false, true)))
+    return rc;
+  hipLaunchKernelGGL(k_mc_final, dim3((unsigned)M.ncell), dim3(MC_WAVE), 0, ctx->stream, M, (long long)mc->nrec, (long long)mc->nrec_dec,
+                     mean.dev, stdv.dev, q.dev, best.dev, rhat.dev, acc.dev, chi2.dev);
+  DZ_HIP(hipGetLastError());
+  if ((rc = mean.finish()) || (rc = stdv.finish()) || (rc = q.finish()) || (rc = best.finish()) || (rc = rhat.finish()) ||
+      (rc = acc.finish()) || (rc = chi2.finish()))
+    return rc;
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int dazim_mc_free(dazim_ctx *ctx, dazim_mc *mc) {
+  if (!mc) return 0;
+  if (ctx) (void)hipStreamSynchronize(ctx->stream);
+  return mc_release(mc);
+}
+
+}  // extern "C"

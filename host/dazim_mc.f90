@@ -1,0 +1,325 @@
+! dazim_mc.f90 -- SurfDepthMC_amd: the Monte-Carlo second step of the two-step method.  It samples each map cell's Vs column with
+! random-walk Metropolis chains on one MI355X and reports the posterior mean, spread and credible interval of every knot (DESIGN.md
+! section 14), where SurfDepthFromMaps_amd returns one linearised model.
+!
+!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed]]]]]
+!
+! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
+! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
+! Prior per cell and knot: uniform on [max(Minvel, MOD - width), min(Maxvel, MOD + width)]; width 0 (default) = [Minvel, Maxvel].
+! nsample recorded steps (default 2000) after as many burn-in steps, nchain chains per cell (default 32), sigma_c 0.01 km/s, seed 1.
+!
+! Outputs (names of their own, so that the three programs can share a directory):
+!   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
+!   Vs_posterior_mc.dat          per inner cell and sampled knot: lon lat depth mean std p2.5 p50 p97.5 best R-hat
+!   period_phaseV_mc.dat         c of the posterior-mean model, as period_phaseV_map.dat
+!   cell_mc.dat                  per inner cell: lon lat acceptance, RMS c misfit of the best and of the mean model
+!   <para>_mc.log + stdout       settings, cells, proposals without a root, acceptance quartiles, R-hat, misfit
+program SurfDepthMC_amd
+  use iso_c_binding
+  use dazim_mod
+  implicit none
+  integer, parameter :: nbin = 200, nadapt = 50
+  real, parameter :: step0 = 0.05
+  character(len=100) :: inputfile, logfile, arg
+  character(len=80) :: datafile
+  character(len=300) :: line
+  character(len=40) :: dummy
+  logical :: ex, iso_mod, have_cov
+  integer :: nx, ny, nz, nsrc, maxiter, kmaxRc, kmax, nsample, nchain, ios
+  integer(c_long_long) :: seed
+  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp, width, sigma_c
+  real*8, allocatable :: tRc(:)
+  real, allocatable :: depz(:), vsf(:, :, :), vmc(:, :, :), vbest(:, :, :)
+  real*8, allocatable :: pvm(:, :), pvb(:, :)
+  real, allocatable :: cmap(:, :, :), cov(:, :, :), wcov(:, :, :), vmin(:, :, :), vmax(:, :, :)
+  real, allocatable :: mean(:, :, :), std(:, :, :), qq(:, :, :, :), best(:, :, :), rhat(:, :, :), acc(:, :), chi2b(:, :)
+  real, allocatable :: sorted(:), rms_b(:, :), rms_m(:, :)
+  logical, allocatable :: sampled(:, :)
+  real :: vals(9), rms_all, t_run, t_disp, t_step
+  real*8 :: s0, cnt
+  integer :: i, j, k, t, nlay, ncell, q, ns, nr
+  integer(c_int) :: nfail, nempty
+  integer(c_int64_t) :: nnoroot
+  type(c_ptr) :: mc
+
+  write (*, *)
+  write (*, *) '                       SurfDepthMC'
+  write (*, *)
+  if (command_argument_count() < 1) error stop 'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed]]]]]'
+  call get_command_argument(1, inputfile)
+  inquire (file=inputfile, exist=ex)
+  if (.not. ex) error stop 'unable to open the inputfile'
+  include 'read_para.inc'
+  if (nz <= 1) error stop 'error nz value.'
+  if (kmaxRc <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
+  nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1
+  ios = 0
+  if (command_argument_count() >= 2) call int_arg(2, nsample)
+  if (command_argument_count() >= 3) call int_arg(3, nchain)
+  if (command_argument_count() >= 4) call real_arg(4, width)
+  if (command_argument_count() >= 5) call real_arg(5, sigma_c)
+  if (command_argument_count() >= 6) then
+    call get_command_argument(6, arg)
+    read (arg, *, iostat=ios) seed
+    if (ios /= 0) call bad_arg(6)
+  end if
+  if (nsample < 1) error stop 'nsample must be at least 1'
+  if (nchain < 1 .or. nchain > 64) error stop 'nchain must be 1..64'
+  if (width < 0) error stop 'width must not be negative'
+  if (sigma_c <= 0) error stop 'sigma_c must be positive'
+  kmax = kmaxRc
+  nlay = nz - 1
+  ncell = (nx - 2)*(ny - 2)
+  if (nlay > 63) error stop 'SurfDepthMC_amd samples at most 63 knots (nz <= 64)'
+  if (kmax > 60) error stop 'SurfDepthMC_amd takes at most 60 periods'
+  if (.not. (Minvel < Maxvel)) error stop 'para.in''s Vs range is empty'
+  write (logfile, '(a,a)') trim(inputfile), '_mc.log'
+  open (66, file=logfile)
+  write (66, *)
+  write (66, *) '                  SurfDepthMC'
+  write (66, *)
+  do q = 6, 66, 60
+    write (q, '(a,3i5,a,i3,a)') ' grid nx ny nz:', nx, ny, nz, ';', kmax, ' periods'
+    write (q, '(a,50f6.1)') ' periods (s):', (tRc(i), i=1, kmax)
+    write (q, '(a,i7,a,i7,a,i3,a,i20)') ' recorded steps', nsample, '  burn-in steps', nsample, '  chains per cell', nchain, &
+      '  seed', seed
+    write (q, '(a,f8.4,a,f8.3,a,i4,a,i4)') ' sigma_c (km/s)', sigma_c, '  initial step scale', step0, '  adaptation every', &
+      nadapt, ' burn-in steps;  histogram bins', nbin
+    if (width > 0) then
+      write (q, '(a,f8.4,a,2f8.3)') ' prior: uniform on MOD +-', width, ' km/s inside para.in''s Vs range', Minvel, Maxvel
+    else
+      write (q, '(a,2f8.3)') ' prior: uniform on para.in''s Vs range', Minvel, Maxvel
+    end if
+  end do
+
+  allocate (depz(nz), vsf(nx, ny, nz))
+  vsf = 0
+  include 'read_mod.inc'
+
+  ! ---- the maps and the weights (SurfDepthFromMaps_amd's) ------------------------------------------------------------------------
+  allocate (cmap(nx - 2, ny - 2, kmax), cov(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
+  call read_map('period_phaseV_map.dat', 4, 4, cmap, .true.)
+  inquire (file='period_map_coverage.dat', exist=have_cov)
+  if (have_cov) then
+    call read_map('period_map_coverage.dat', 4, 4, cov, .true.)
+    wcov = merge(1.0/sigma_c, 0.0, cov > 0.0)
+    do q = 6, 66, 60
+      write (q, '(a,i8,a,i8)') ' period_map_coverage.dat: weight 1/sigma_c on the (cell, period) pairs with DWS > 0:', &
+        count(cov > 0.0), ' of', kmax*ncell
+    end do
+  else
+    wcov = 1.0/sigma_c
+    do q = 6, 66, 60
+      write (q, '(a)') ' period_map_coverage.dat is absent: weight 1/sigma_c on every cell and period'
+    end do
+  end if
+
+  ! ---- the prior box per cell and knot -------------------------------------------------------------------------------------------
+  allocate (vmin(nx - 2, ny - 2, nlay), vmax(nx - 2, ny - 2, nlay))
+  if (width > 0) then
+    vmin = max(Minvel, vsf(2:nx - 1, 2:ny - 1, 1:nlay) - width)
+    vmax = min(Maxvel, vsf(2:nx - 1, 2:ny - 1, 1:nlay) + width)
+  else
+    vmin = Minvel
+    vmax = Maxvel
+  end if
+  if (any(.not. (vmin < vmax))) then
+    write (*, '(a)') ' ERROR: MOD lies outside para.in''s Vs range by more than width: an empty prior box'
+    error stop 'empty prior box'
+  end if
+
+  ! ---- the chains ----------------------------------------------------------------------------------------------------------------
+  call dazim_init(0)
+  call dazim_check(dazim_mc_create(dazim_handle, nx, ny, nz, kmax, nchain, nbin, seed, vsf, vmin, vmax, cmap, wcov, step0, nadapt, &
+                                   mc, nempty), 'Monte-Carlo chains')
+  do q = 6, 66, 60
+    write (q, '(a,i8,a,i8)') ' cells sampled', ncell - nempty, '  cells without data (start model kept)', nempty
+  end do
+  call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
+  t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
+  t_disp = real(dazim_last_kernel_seconds(dazim_handle, 'mc.disp'//c_null_char))
+  t_step = real(dazim_last_kernel_seconds(dazim_handle, 'mc.step'//c_null_char))
+  allocate (mean(nx - 2, ny - 2, nlay), std(nx - 2, ny - 2, nlay), qq(nx - 2, ny - 2, nlay, 3), best(nx - 2, ny - 2, nlay))
+  allocate (rhat(nx - 2, ny - 2, nlay), acc(nx - 2, ny - 2), chi2b(nx - 2, ny - 2))
+  call dazim_check(dazim_mc_result(dazim_handle, mc, mean, std, qq, best, rhat, acc, chi2b), 'posterior statistics')
+  call dazim_check(dazim_mc_free(dazim_handle, mc), 'Monte-Carlo chains')
+
+  ! ---- the curves of the mean and of the best model ------------------------------------------------------------------------------
+  allocate (vmc(nx, ny, nz), vbest(nx, ny, nz), pvm(nx*ny, kmax), pvb(nx*ny, kmax))
+  vmc = vsf; vbest = vsf
+  vmc(2:nx - 1, 2:ny - 1, 1:nlay) = mean
+  vbest(2:nx - 1, 2:ny - 1, 1:nlay) = best
+  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vmc, depz, minthk, kmax, tRc, pvm, c_null_ptr, c_null_ptr, &
+                                            c_null_ptr, nfail), 'dispersion curves of the mean model')
+  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vbest, depz, minthk, kmax, tRc, pvb, c_null_ptr, c_null_ptr, &
+                                            c_null_ptr, nfail), 'dispersion curves of the best model')
+  allocate (rms_b(nx - 2, ny - 2), rms_m(nx - 2, ny - 2), sampled(nx - 2, ny - 2))
+  sampled = any(wcov /= 0.0, dim=3)
+  s0 = 0; cnt = 0
+  do j = 1, ny - 2
+    do i = 1, nx - 2
+      rms_b(i, j) = cell_rms(pvb, i, j)
+      rms_m(i, j) = cell_rms(pvm, i, j)
+      do t = 1, kmax
+        if (wcov(i, j, t) /= 0.0) then
+          s0 = s0 + (real(cmap(i, j, t), 8) - pvm(j*nx + i + 1, t))**2
+          cnt = cnt + 1
+        end if
+      end do
+    end do
+  end do
+  rms_all = 0
+  if (cnt > 0) rms_all = real(sqrt(s0/cnt))
+
+  ! ---- summary -------------------------------------------------------------------------------------------------------------------
+  ns = count(sampled)
+  do q = 6, 66, 60
+    write (q, '(a,i12,a,i12)') ' proposals without a root:', nnoroot, ' of', int(2*nsample, 8)*ns*nchain
+    write (q, '(a,f9.2,a,f9.2,a,f9.3,a)') ' run', t_run, ' s (dispersion calls', t_disp, ' s, step kernels', t_step, ' s)'
+  end do
+  if (ns > 0) then
+    allocate (sorted(ns))
+    sorted = pack(acc, sampled)
+    call sort(sorted)
+    do q = 6, 66, 60
+      write (q, '(a,3f8.3)') ' acceptance over cells, quartiles 25/50/75 %:', sorted(max(1, nint(0.25*ns))), &
+        sorted(max(1, nint(0.5*ns))), sorted(max(1, nint(0.75*ns)))
+    end do
+    deallocate (sorted)
+    nr = count(spread(sampled, 3, nlay) .and. rhat == rhat)
+    allocate (sorted(max(nr, 1)))
+    sorted = 0
+    if (nr > 0) sorted(1:nr) = pack(rhat, spread(sampled, 3, nlay) .and. rhat == rhat)
+    call sort(sorted(1:max(nr, 1)))
+    do q = 6, 66, 60
+      write (q, '(a,2f9.4)') ' R-hat over (cell, knot), median and maximum:', sorted(max(1, (nr + 1)/2)), sorted(max(nr, 1))
+    end do
+  end if
+  do q = 6, 66, 60
+    write (q, '(a,f12.5)') ' posterior-mean model: rms_c', rms_all
+  end do
+
+  ! ---- output files --------------------------------------------------------------------------------------------------------------
+  open (11, file='MOD_mc')
+  do k = 1, nz
+    write (11, '(f7.1)', advance='no') depz(k)
+  end do
+  do k = 1, nz
+    do j = 1, ny
+      do i = 1, nx
+        if (i == 1) then
+          write (11, '(/f8.4)', advance='no') vmc(i, j, k)
+        else
+          write (11, '(f8.4)', advance='no') vmc(i, j, k)
+        end if
+      end do
+    end do
+  end do
+  close (11)
+  open (63, file='DSurfTomo_mc.inv')
+  do k = 1, nz
+    do j = 1, ny
+      do i = 1, nx
+        write (63, '(5f8.4)') gozd + (j - 2)*dvzd, goxd - (i - 2)*dvxd, depz(k), vmc(i, j, k)
+      end do
+    end do
+  end do
+  close (63)
+  open (64, file='Vs_posterior_mc.dat')
+  do k = 1, nlay
+    do j = 1, ny - 2
+      do i = 1, nx - 2
+        write (64, '(3f10.4,7f10.4)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, depz(k), mean(i, j, k), std(i, j, k), &
+          qq(i, j, k, 1), qq(i, j, k, 2), qq(i, j, k, 3), best(i, j, k), rhat(i, j, k)
+      end do
+    end do
+  end do
+  close (64)
+  open (77, file='period_phaseV_mc.dat')
+  do t = 1, kmax
+    do j = 1, ny - 2
+      do i = 1, nx - 2
+        write (77, '(5f10.4)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, tRc(t), pvm(j*nx + i + 1, t)
+      end do
+    end do
+  end do
+  close (77)
+  open (78, file='cell_mc.dat')
+  do j = 1, ny - 2
+    do i = 1, nx - 2
+      write (78, '(3f10.4,2f10.5)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, acc(i, j), rms_b(i, j), rms_m(i, j)
+    end do
+  end do
+  close (78)
+  write (*, *) '  Program finishes successfully'
+  write (66, *) '  Program finishes successfully'
+  close (66)
+  call dazim_finalize()
+
+contains
+
+  include 'read_map.inc'
+
+  subroutine bad_arg(n)
+    integer, intent(in) :: n
+    write (*, '(a,i2,a,a)') ' ERROR: argument', n, ' is not a number: ', trim(arg)
+    error stop 'bad argument'
+  end subroutine
+
+  subroutine int_arg(n, v)
+    integer, intent(in) :: n
+    integer, intent(inout) :: v
+    call get_command_argument(n, arg)
+    read (arg, *, iostat=ios) v
+    if (ios /= 0) call bad_arg(n)
+  end subroutine
+
+  subroutine real_arg(n, v)
+    integer, intent(in) :: n
+    real, intent(inout) :: v
+    call get_command_argument(n, arg)
+    read (arg, *, iostat=ios) v
+    if (ios /= 0) call bad_arg(n)
+  end subroutine
+
+  ! RMS over the periods with a weight of cmap - c at inner cell (i1, j1); 0 for a cell without data
+  real function cell_rms(pv, i1, j1)
+    real*8, intent(in) :: pv(:, :)
+    integer, intent(in) :: i1, j1
+    integer :: t1, n1
+    real*8 :: s
+    s = 0; n1 = 0
+    do t1 = 1, kmax
+      if (wcov(i1, j1, t1) /= 0.0) then
+        s = s + (real(cmap(i1, j1, t1), 8) - pv(j1*nx + i1 + 1, t1))**2
+        n1 = n1 + 1
+      end if
+    end do
+    cell_rms = 0
+    if (n1 > 0) cell_rms = real(sqrt(s/n1))
+  end function
+
+  subroutine sort(a)   ! Shell sort with gaps 3h+1 (up to (nx-2)(ny-2)(nz-1) values)
+    real, intent(inout) :: a(:)
+    integer :: i1, j1, h
+    real :: x
+    h = 1
+    do while (h < size(a)/3)
+      h = 3*h + 1
+    end do
+    do while (h >= 1)
+      do i1 = h + 1, size(a)
+        x = a(i1)
+        j1 = i1 - h
+        do while (j1 >= 1)
+          if (a(j1) <= x) exit
+          a(j1 + h) = a(j1)
+          j1 = j1 - h
+        end do
+        a(j1 + h) = x
+      end do
+      h = h/3
+    end do
+  end subroutine
+end program

@@ -36,6 +36,9 @@ module dazim_mod
             dazim_assemble_G_maps
   ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
   public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq
+  ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
+  public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
+            dazim_last_kernel_seconds
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -213,6 +216,56 @@ module dazim_mod
       real(c_float), value :: smooth, damp
       real(c_float) :: rhs(*), wdat(*), x(*), stats(*)
       integer(c_int) :: n_empty
+    end function
+    ! Monte-Carlo Vs per map cell (include/dazim.h): mc is the opaque handle; arrays in the C layouts given there
+    integer(c_int) function dazim_mc_create(ctx, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step, nadapt, &
+        mc, n_empty) bind(C, name="dazim_mc_create")
+      import
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, nz, kmax, nchain, nbin, nadapt
+      integer(c_long_long), value :: seed
+      real(c_float) :: vel0(*), vmin(*), vmax(*), cobs(*), wdat(*)
+      real(c_float), value :: step
+      type(c_ptr) :: mc
+      integer(c_int) :: n_empty
+    end function
+    integer(c_int) function dazim_mc_proposals(mc, vel_dev, ncol) bind(C, name="dazim_mc_proposals")
+      import
+      type(c_ptr), value :: mc
+      type(c_ptr) :: vel_dev
+      integer(c_int64_t) :: ncol
+    end function
+    integer(c_int) function dazim_mc_step(ctx, mc, kmax, ncol, pv, record) bind(C, name="dazim_mc_step")
+      import
+      type(c_ptr), value :: ctx, mc
+      integer(c_int), value :: kmax, record
+      integer(c_int64_t), value :: ncol
+      real(c_double) :: pv(*)
+    end function
+    integer(c_int) function dazim_mc_run(ctx, mc, depz, sublayers, periods, nburn, nsample, n_no_root) bind(C, name="dazim_mc_run")
+      import
+      type(c_ptr), value :: ctx, mc
+      real(c_float) :: depz(*)
+      real(c_float), value :: sublayers
+      real(c_double) :: periods(*)
+      integer(c_int), value :: nburn, nsample
+      integer(c_int64_t) :: n_no_root
+    end function
+    ! every array argument may be c_null_ptr (c_loc of an array otherwise)
+    integer(c_int) function dazim_mc_state(ctx, mc, cur, chi2, scale, step, sums, hist, accepted, best, best_chi2) &
+        bind(C, name="dazim_mc_state")
+      import
+      type(c_ptr), value :: ctx, mc, cur, chi2, scale, sums, hist, accepted, best, best_chi2
+      integer(c_int64_t) :: step
+    end function
+    integer(c_int) function dazim_mc_result(ctx, mc, mean, std, q, best, rhat, accept, chi2_best) bind(C, name="dazim_mc_result")
+      import
+      type(c_ptr), value :: ctx, mc
+      real(c_float) :: mean(*), std(*), q(*), best(*), rhat(*), accept(*), chi2_best(*)
+    end function
+    integer(c_int) function dazim_mc_free(ctx, mc) bind(C, name="dazim_mc_free")
+      import
+      type(c_ptr), value :: ctx, mc
     end function
     integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
         bind(C, name="dazim_phase_map_update")

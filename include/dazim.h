@@ -282,6 +282,64 @@ int dazim_vs_kernels(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, const flo
 int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int kern_fp32, const void *kern, int nrhs, const float *rhs,
                      const float *wdat, float smooth, float damp, float *x, int *n_empty, float *stats);
 
+/* ---- Monte-Carlo Vs per map cell: posterior mean, spread and credible interval ----------------------------
+ * Random-walk Metropolis chains on the knots 0..nlay-1 (nlay = nz - 1) of each inner cell's Vs column, the last knot held at vel0's
+ * value; the forward model is dazim_dispersion_kernels with sen_* = NULL.  Prior: uniform on [vmin, vmax] per cell and knot.
+ * chi^2 = sum_p (w_p (cobs_p - c_p))^2 in period order in fp64 ((double)w * ((double)cobs - c), periods with w == 0 skipped);
+ * c_p == 0 at a period with w != 0 (no root) gives chi^2 = +inf.  Cells with w == 0 at every period are not sampled (n_empty).
+ * Sampled cells are the others in inner-cell order (cs = 0, 1, ..); chain ch of sampled cell cs is column cs*nchain + ch (ncol =
+ * sampled cells * nchain).  Global chain id gid = cell*nchain + ch, cell = (jj-1)(nx-2) + kk-1 the index among ALL inner cells.
+ * Random numbers, all in fp64: block(step, gid, b) = the four words of Philox4x32-10 with counter (step, gid, b, 0) (32-bit words,
+ *   first word first; step truncated to 32 bits) and key (seed & 0xffffffff, seed >> 32); u(word) = (word + 0.5) * 2^-32.
+ *   Start models (step 0): knot 4q+e = (float)(lo + (hi - lo) * u(word e of block(0, gid, 1+q))), lo/hi = (double)vmin/vmax.
+ *   Normals of step t: from block(t, gid, 1+q) = (w0, w1, w2, w3): r0 = sqrt(-2 log u(w0)), a0 = 6.283185307179586 * u(w1),
+ *   r1, a1 likewise from w2, w3; knots 4q, 4q+1, 4q+2, 4q+3 get r0 cos a0, r0 sin a0, r1 cos a1, r1 sin a1.
+ *   Acceptance uniform of step t: u(word 0 of block(t, gid, 0)).
+ * Step t (t = 1, 2, ..; a dazim_mc_step call, or one step of dazim_mc_run), per chain:
+ *   chi2' from the curves pv [kmax][ncol] of the proposals.  t = 1: the proposals are the start models; they become the state with
+ *   chi2', no decision.  t > 1: current chi2 = +inf -> accept iff chi2' is finite; else accept iff log(u) < -0.5 * (chi2' - chi2).
+ *   An accepted proposal replaces the state's nlay knots and chi2.
+ *   Burn-in (record = 0): the cell's accepted moves are counted over its chains; after every nadapt burn-in steps with a decision,
+ *   rate = count / (nadapt * nchain): > 0.40 -> s = s * 1.25f, < 0.20 -> s = s / 1.25f, then s = min(max(s, 1e-3f), 0.5f) (fp32),
+ *   and the count restarts.  Recorded steps (record = 1) keep s: per chain and knot sums[0][k][col] += v, sums[1][k][col] += v*v
+ *   (fp64, v the state); hist[cs][k][b] += 1, b = (int)(((double)v - lo) / (hi - lo) * nbin) clamped to 0..nbin-1; accepted[col]
+ *   += 1 for an accepted move; the cell's best model is the state of its lowest-chi2 chain when that chi2 is strictly lower than
+ *   the best so far (the first in (step, chain) order on ties).
+ *   Next proposals: v' = (double)v + ((double)s * (hi - lo)) * z_k, reflected (v' < lo -> 2 lo - v', v' > hi -> 2 hi - v') until
+ *   inside, rounded to fp32 once; the last knot stays.  (|z| < 6.77 and s <= 0.5 bound the excess by 3.39 widths: at most 4
+ *   reflections.  The loop stops after 8 and clamps to the box, which never acts.)
+ * dazim_mc_create: vel0 [nz][ny][nx] (the last knot; the result of cells without data), vmin, vmax [nlay][ny-2][nx-2], cobs, wdat
+ *   [kmax][ny-2][nx-2] (the layout of dazim_column_lsq), step = the initial s, nadapt >= 1.  Draws the start models.  Refused
+ *   (DAZIM_E_BAD_ARG): nchain outside 1..64, nlay outside 1..63, kmax outside 1..60, nbin < 2, a non-finite vmin, vmax, cobs or
+ *   wdat, vmin >= vmax anywhere, step outside (0, 0.5] (the range the adaptation keeps), nadapt < 1.
+ * dazim_mc_proposals: the device array [nz][ncol] fp32 the next step evaluates (owned by the handle) and ncol.
+ * dazim_mc_step: one step on the curves pv [kmax][ncol] (host or device) of those proposals, from any forward model; kmax and ncol
+ *   state pv's shape and must be the handle's (DAZIM_E_BAD_ARG otherwise, and for a handle of another context).
+ * dazim_mc_run: nburn burn-in then nsample recorded steps, each one dazim_dispersion_kernels call (nx = ncol, ny = 1, curves only,
+ *   depz [nz] and periods [kmax] host arrays as there) and one step launch; no other host wait.  n_no_root (nullable) = proposals
+ *   of the run with chi2' = +inf.  Stats: "mc" (seconds of the run), "mc.disp" (its dispersion kernels), "mc.step" (its step
+ *   kernels), "mc.steps", "mc.accept" (accepted / decisions of its recorded steps), "mc.no_root".
+ * dazim_mc_state: copies of the chain state (each pointer nullable, host or device): cur [nz][ncol], chi2 [ncol], scale [sampled
+ *   cells], step (steps done), sums [2][nlay][ncol], hist [sampled cells][nlay][nbin], accepted [ncol], best [nlay][sampled cells]
+ *   and best_chi2 [sampled cells] (vel0's knots and +inf before the first recorded step).
+ * dazim_mc_result: over the recorded steps (N of them, M = nchain): mean, std (population, of the N*M states), best, rhat [nlay][ny-2]
+ *   [nx-2]; q [3][nlay][ny-2][nx-2] = 2.5 / 50 / 97.5 % of the counts, linear inside a bin; accept, chi2_best [ny-2][nx-2].  R-hat is
+ *   BDA3's, chains not split: sqrt(((N-1)/N W + B/N) / W), NaN for M = 1 or N = 1.  Cells without data: mean = q = best = vel0's
+ *   knots, std 0, rhat NaN, accept 0, chi2_best 0.  Refused before the first recorded step.                                      */
+typedef struct dazim_mc dazim_mc;
+int dazim_mc_create(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, int nchain, int nbin, unsigned long long seed, const float *vel0,
+                    const float *vmin, const float *vmax, const float *cobs, const float *wdat, float step, int nadapt, dazim_mc **mc,
+                    int *n_empty);
+int dazim_mc_proposals(dazim_mc *mc, float **vel_dev, int64_t *ncol);
+int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);
+int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
+                 int64_t *n_no_root);
+int dazim_mc_state(dazim_ctx *ctx, dazim_mc *mc, float *cur, double *chi2, float *scale, int64_t *step, double *sums, unsigned *hist,
+                   int64_t *accepted, float *best, double *best_chi2);
+int dazim_mc_result(dazim_ctx *ctx, dazim_mc *mc, float *mean, float *std, float *q, float *best, float *rhat, float *accept,
+                    float *chi2_best);
+int dazim_mc_free(dazim_ctx *ctx, dazim_mc *mc);
+
 /* ---- N4: what surrounds the solve in the outer iteration, on the device ------------------------------
  * = TikhonovRegularization / TikhRegul_joint (inv/TikhRegul.f90:2-104, :107-209): appends nblock * maxvp rows, maxvp =
  *   (nx-2)(ny-2)(nz-1); block b regularises columns b*maxvp+1 .. (b+1)*maxvp with weight w[b] (host array): a cell on a face

@@ -1,0 +1,130 @@
+"""Times of the Monte-Carlo step (profiles/depth_mc.md).
+
+    python tools/mc_step.py [--steps S] [--big N]
+    python tools/mc_step.py --program [--dir D]
+
+On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
+N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
+recorded) after a 5-step warm-up run.  Reports ms per step -- the run's wall time ("mc"), its dispersion calls ("mc.disp"), its
+k_mc_step launches ("mc.step") and the rest (host work of the calls) -- and curves per second.  One JSON line per case.
+
+--program: the wall time of host/SurfDepthMC_amd's default run (2 000 burn-in + 2 000 recorded steps, 32 chains) at S-256.  The
+inputs are written to D (default: a temporary directory): para.in with S-256's grid, knots, sublayers and periods, the model as MOD,
+and its exact curves as period_phaseV_map.dat (no coverage file: every cell and period weighted).  One JSON line with the wall time
+and the log's summary lines."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def one_case(ctx, n, nchain, steps):
+    import bench
+    bench.NX = bench.NY = n
+    vel = bench.s256_model().astype(np.float32)
+    depz, periods = np.asarray(bench.DEPZ, np.float32), np.asarray(bench.PERIODS, np.float64)
+    nz, kmax, nlay = len(depz), len(periods), len(depz) - 1
+    pv, _, _ = ctx.depthkernel(vel, depz, periods, bench.MINTHK, kernels=False)
+    cobs = pv.reshape(kmax, n, n)[:, 1:-1, 1:-1].astype(np.float32)
+    inner = vel[:nlay, 1:-1, 1:-1]
+    vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
+    wdat = np.full((kmax, n - 2, n - 2), 100.0, np.float32)
+    mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat)
+    mc.run(depz, bench.MINTHK, periods, 5, 0)                 # warm-up: code objects, scratch buffers
+    nr = mc.run(depz, bench.MINTHK, periods, steps // 2, steps - steps // 2)
+    wall, disp, stp = ctx.stat("mc"), ctx.stat("mc.disp"), ctx.stat("mc.step")
+    r = mc.result()
+    mc.free()
+    ms = lambda s: 1e3 * s / steps
+    return {"grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots ({nlay} sampled), {kmax} periods", "nchain": nchain,
+            "steps": steps, "curves_per_step": mc.ncol, "ms_per_step": ms(wall), "disp_ms_per_step": ms(disp),
+            "mc_step_ms_per_step": ms(stp), "other_ms_per_step": ms(wall - disp - stp), "mc_step_share": stp / wall,
+            "curves_per_s": mc.ncol * steps / wall, "accept": ctx.stat("mc.accept"), "no_root": nr,
+            "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
+
+
+PARA = """cccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccc
+c INPUT PARAMETERS
+cccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccc
+surfphase_forward.dat                c: traveltime data file (not read)
+{n} {n} {nz}                           c: nx ny nz
+30.00 100.00                         c: goxd gozd
+0.25 0.25                            c: dvxd dvzd
+{sub}                                    c: number of sublayers
+2.0 4.8                              c: minimum and maximum Vsv
+10                                   c: max(sources, receivers)
+0.4                                  c: sparsity fraction
+1                                    c: maximum of iteration
+T                                    c: iso-mode
+cccccccc control parameters
+2.0                                  c: smoothing for dVsv
+2.0                                  c: smoothing for Gc,s
+0.0                                  c: damping
+cccccccccc periods
+{kmax}                                   c: kmaxRc
+{periods}
+"""
+
+
+def program_run(ctx, d):
+    import bench
+    n = bench.NX = bench.NY = 54
+    vel = bench.s256_model().astype(np.float32)
+    depz, periods = np.asarray(bench.DEPZ, np.float32), np.asarray(bench.PERIODS, np.float64)
+    nz, kmax = len(depz), len(periods)
+    pv, _, nf = ctx.depthkernel(vel, depz, periods, bench.MINTHK, kernels=False)
+    assert nf == 0
+    pv = pv.reshape(kmax, n, n)
+    ctx.close()                      # (the program opens the GPU itself)
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, "para.in"), "w") as f:
+        f.write(PARA.format(n=n, nz=nz, sub=int(bench.MINTHK), kmax=kmax, periods=" ".join("%g" % t for t in periods)))
+    with open(os.path.join(d, "MOD"), "w") as f:
+        f.write(" ".join("%.1f" % z for z in depz) + "\n")
+        for k in range(nz):
+            for j in range(n):
+                f.write(" ".join("%.4f" % vel[k, j, i] for i in range(n)) + "\n")
+    with open(os.path.join(d, "period_phaseV_map.dat"), "w") as f:
+        for t in range(kmax):
+            for j in range(1, n - 1):
+                for i in range(1, n - 1):
+                    f.write("%10.4f%10.4f%10.4f%10.4f\n" % (100.0 + (j - 1) * 0.25, 30.0 - (i - 1) * 0.25, periods[t], pv[t, j, i]))
+    exe = os.path.join(ROOT, "host", "SurfDepthMC_amd")
+    t0 = time.perf_counter()
+    out = subprocess.run([exe, "para.in"], cwd=d, capture_output=True, text=True, timeout=1500)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    log = open(os.path.join(d, "para.in_mc.log")).read().splitlines()
+    keep = [l.strip() for l in log if any(k in l for k in ("cells sampled", "without a root", "run", "acceptance", "R-hat", "rms_c"))]
+    return {"program": "SurfDepthMC_amd para.in (defaults: 2000 + 2000 steps, 32 chains)",
+            "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots, {kmax} periods", "wall_s": wall, "log": keep}
+
+
+def main():
+    import dazimsurftomo_amd as dz
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--big", type=int, default=202)
+    ap.add_argument("--program", action="store_true")
+    ap.add_argument("--dir", default=None)
+    a = ap.parse_args()
+    ctx = dz.Context(0)
+    if a.program:
+        with tempfile.TemporaryDirectory() as tmp:
+            print(json.dumps(program_run(ctx, a.dir or tmp)), flush=True)
+        return
+    for n, nchain in ((54, 8), (54, 32), (54, 64), (a.big, 8)):
+        print(json.dumps(one_case(ctx, n, nchain, a.steps)), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
