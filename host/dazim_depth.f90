@@ -4,10 +4,10 @@
 !
 !   SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c]]]
 !
-! Inputs: the unchanged para.in and MOD of DAzimSurfTomo_amd (read_para.inc, read_mod.inc; the data file is not opened), the maps
-! period_phaseV_map.dat (and period_Azm_tomo_map.inv in iso-mode F) and, if present, period_map_coverage.dat.  Weights: 1/sigma_c
-! (default 0.01 km/s) where the map's DWS > 0, 0 elsewhere (everywhere 1/sigma_c without a coverage file).  smooth_vs / smooth_gcs
-! default to para.in's two smoothing weights; the damping is para.in's.
+! Inputs: the unchanged para.in and MOD of DAzimSurfTomo_amd (read_para, read_mod of module dazim_io; the data file is not opened),
+! the maps period_phaseV_map.dat (and period_Azm_tomo_map.inv in iso-mode F) and, if present, period_map_coverage.dat.  Weights:
+! 1/sigma_c (default 0.01 km/s) where the map's DWS > 0, 0 elsewhere (everywhere 1/sigma_c without a coverage file).  smooth_vs /
+! smooth_gcs default to para.in's two smoothing weights; the damping is para.in's.
 ! Vs: para.in's maxiter linearised iterations from MOD, each dazim_dispersion_kernels -> dazim_vs_kernels -> r = c_map - pvRc on the
 ! inner cells (w = 0 where pvRc = 0) -> dazim_column_lsq (nlay = nz-1) -> dazim_model_update (para.in's minvel, maxvel).
 ! Gc, Gs (iso-mode F): on the final Vs, dazim_ti_kernels, then one dazim_column_lsq on Lsen_Gsc with the two right-hand sides a1, a2:
@@ -21,24 +21,22 @@
 program SurfDepthFromMaps_amd
   use iso_c_binding
   use dazim_mod
+  use dazim_io
   implicit none
-  real, parameter :: pi = 3.1415926535898
-  character(len=100) :: inputfile, logfile, arg
-  character(len=80) :: datafile
-  character(len=300) :: line
-  character(len=40) :: dummy
-  logical :: ex, iso_mod, have_cov
-  integer :: nx, ny, nz, nsrc, maxiter, kmaxRc, kmax
-  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp, smooth_vs, smooth_gcs, sigma_c
+  character(len=100) :: inputfile, logfile
+  type(para_t) :: p
+  logical :: ex, iso_mod
+  integer :: nx, ny, nz, maxiter, kmax
+  real :: minthk, Minvel, Maxvel, damp, smooth_vs, smooth_gcs, sigma_c
   real*8, allocatable :: tRc(:)
   real, allocatable :: depz(:), vsf(:, :, :)
   real*8, allocatable, target :: pv(:, :), svs(:, :, :), svp(:, :, :), srho(:, :, :), skern(:, :, :)
   real, allocatable, target :: lsen(:, :, :)
-  real, allocatable :: cmap(:, :, :), amap(:, :, :, :), cov(:, :, :), wcov(:, :, :), w(:, :, :), r(:, :, :, :), x(:, :, :, :)
+  real, allocatable :: cmap(:, :, :), amap(:, :, :, :), wcov(:, :, :), w(:, :, :), r(:, :, :, :), x(:, :, :, :)
   real, allocatable :: gcf(:, :, :), gsf(:, :, :), ustats(:, :), stats(:, :, :)
-  real :: dummy1(1), vals(9), rms0, rms1, maxdv
+  real :: dummy1(1), rms0, rms1, maxdv
   real*8 :: s0, s1, cnt
-  integer :: i, j, k, t, iter, nlay, ncell, nused, col, q
+  integer :: i, t, iter, nlay, nused, col, q
   integer(c_int) :: nfail, nempty
 
   write (*, *)
@@ -48,26 +46,17 @@ program SurfDepthFromMaps_amd
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
-  include 'read_para.inc'
+  call read_para(inputfile, p)
+  nx = p%nx; ny = p%ny; nz = p%nz; minthk = p%minthk; Minvel = p%Minvel; Maxvel = p%Maxvel; maxiter = p%maxiter
+  iso_mod = p%iso_mod; damp = p%damp; kmax = p%kmaxRc; tRc = p%tRc
   if (nz <= 1) error stop 'error nz value.'
-  if (kmaxRc <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
-  smooth_vs = weightVs; smooth_gcs = weightGcs; sigma_c = 0.01
-  if (command_argument_count() >= 2) then
-    call get_command_argument(2, arg)
-    read (arg, *) smooth_vs
-  end if
-  if (command_argument_count() >= 3) then
-    call get_command_argument(3, arg)
-    read (arg, *) smooth_gcs
-  end if
-  if (command_argument_count() >= 4) then
-    call get_command_argument(4, arg)
-    read (arg, *) sigma_c
-  end if
+  if (kmax <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
+  smooth_vs = p%weightVs; smooth_gcs = p%weightGcs; sigma_c = 0.01
+  call optional_arg(2, smooth_vs)
+  call optional_arg(3, smooth_gcs)
+  call optional_arg(4, sigma_c)
   if (sigma_c <= 0) error stop 'sigma_c must be positive'
-  kmax = kmaxRc
   nlay = nz - 1
-  ncell = (nx - 2)*(ny - 2)
   if (nlay > 63) error stop 'SurfDepthFromMaps_amd inverts at most 63 layers (nz <= 64)'
   if (kmax > 60) error stop 'SurfDepthFromMaps_amd takes at most 60 periods'
   write (logfile, '(a,a)') trim(inputfile), '_2step.log'
@@ -82,31 +71,16 @@ program SurfDepthFromMaps_amd
       '  sigma_c (km/s)', sigma_c, '  Vs range', Minvel, Maxvel
   end do
 
-  allocate (depz(nz), vsf(nx, ny, nz))
-  vsf = 0
-  include 'read_mod.inc'
+  call read_mod('MOD', p, depz, vsf)
 
   ! ---- the maps ------------------------------------------------------------------------------------------------------------------
-  allocate (cmap(nx - 2, ny - 2, kmax), cov(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
-  call read_map('period_phaseV_map.dat', 4, 4, cmap, .true.)
-  inquire (file='period_map_coverage.dat', exist=have_cov)
-  if (have_cov) then
-    call read_map('period_map_coverage.dat', 4, 4, cov, .true.)
-    wcov = merge(1.0/sigma_c, 0.0, cov > 0.0)
-    do q = 6, 66, 60
-      write (q, '(a,i8,a,i8)') ' period_map_coverage.dat: weight 1/sigma_c on the (cell, period) pairs with DWS > 0:', &
-        count(cov > 0.0), ' of', kmax*ncell
-    end do
-  else
-    wcov = 1.0/sigma_c
-    do q = 6, 66, 60
-      write (q, '(a)') ' period_map_coverage.dat is absent: weight 1/sigma_c on every cell and period'
-    end do
-  end if
+  allocate (cmap(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
+  call read_map('period_phaseV_map.dat', p, 4, 4, cmap, .true.)
+  call coverage_weights(p, sigma_c, wcov)
   if (.not. iso_mod) then
     allocate (amap(nx - 2, ny - 2, kmax, 2))
-    call read_map('period_Azm_tomo_map.inv', 9, 8, amap(:, :, :, 1), .true.)
-    call read_map('period_Azm_tomo_map.inv', 9, 9, amap(:, :, :, 2), .false.)
+    call read_map('period_Azm_tomo_map.inv', p, 9, 8, amap(:, :, :, 1), .true.)
+    call read_map('period_Azm_tomo_map.inv', p, 9, 9, amap(:, :, :, 2), .false.)
   end if
 
   ! ---- Vs, para.in's iterations from MOD -----------------------------------------------------------------------------------------
@@ -161,47 +135,12 @@ program SurfDepthFromMaps_amd
   end if
 
   ! ---- output files, in the formats of DAzimSurfTomo_amd's (dazim_main.f90) --------------------------------------------------------
-  open (11, file='MOD_2step')
-  do k = 1, nz
-    write (11, '(f7.1)', advance='no') depz(k)
-  end do
-  do k = 1, nz
-    do j = 1, ny
-      do i = 1, nx
-        if (i == 1) then
-          write (11, '(/f8.4)', advance='no') vsf(i, j, k)
-        else
-          write (11, '(f8.4)', advance='no') vsf(i, j, k)
-        end if
-      end do
-    end do
-  end do
-  close (11)
-  open (63, file='DSurfTomo_2step.inv')
-  do k = 1, nz
-    do j = 1, ny
-      do i = 1, nx
-        write (63, '(5f8.4)') gozd + (j - 2)*dvzd, goxd - (i - 2)*dvxd, depz(k), vsf(i, j, k)
-      end do
-    end do
-  end do
-  close (63)
-  open (77, file='period_phaseV_2step.dat')
-  do t = 1, kmax
-    do j = 1, ny - 2
-      do i = 1, nx - 2
-        write (77, '(5f10.4)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, tRc(t), pv(j*nx + i + 1, t)
-      end do
-    end do
-  end do
-  close (77)
+  call write_mod('MOD_2step', depz, vsf)
+  call write_vs_model('DSurfTomo_2step.inv', p, depz, vsf)
+  call write_phase_map('period_phaseV_2step.dat', p, inner_cells(nx, ny, kmax, pv))
   if (.not. iso_mod) then
-    open (73, file='Gc_Gs_model_2step.inv')
-    call write_azimuthal(73)
-    close (73)
-    open (42, file='period_Azm_tomo_2step.inv', status='replace', action='write')
-    call write_period_azimuthal(42)
-    close (42)
+    call write_azimuthal('Gc_Gs_model_2step.inv', p, depz, vsf, gcf, gsf)
+    call write_period_azimuthal('period_Azm_tomo_2step.inv', p, lsen, gcf, gsf, inner_cells(nx, ny, kmax, pv))
   end if
   write (*, *) '  Program finishes successfully'
   write (66, *) '  Program finishes successfully'
@@ -232,55 +171,5 @@ contains
     rms0 = 0
     if (cnt > 0) rms0 = real(sqrt(s0/cnt))
     nused = count(any(w > 0.0, dim=3))
-  end subroutine
-
-  include 'read_map.inc'
-
-  ! lon lat depth Vs fast-axis angle, amplitude, Gc/L %, Gs/L %: the arithmetic of write_azimuthal (dazim_main.f90)
-  subroutine write_azimuthal(unit)
-    integer, intent(in) :: unit
-    integer :: k1, j1, i1
-    real :: c2, s2, amp, ang, vsref
-    real*8 :: pi8 = real(3.1415926535898, 8)
-    do k1 = 1, nz - 1
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          c2 = gcf(i1, j1, k1); s2 = gsf(i1, j1, k1)
-          amp = 0.5*sqrt(c2**2 + s2**2)
-          ang = atan2(s2, c2)/pi8*180
-          if (ang < 0.0) ang = ang + 360
-          ang = 0.5*ang
-          vsref = (vsf(i1 + 1, j1 + 1, k1) + vsf(i1 + 1, j1 + 1, k1 + 1))/2
-          write (unit, '(8f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1 + 1), vsref, ang, amp, &
-            gcf(i1, j1, k1)*100, gsf(i1, j1, k1)*100
-        end do
-      end do
-    end do
-  end subroutine
-
-  ! period maps of A1 = sum_k Lsen*Gc, A2 = sum_k Lsen*Gs on the final model: the arithmetic of write_period_azimuthal
-  subroutine write_period_azimuthal(unit)
-    integer, intent(in) :: unit
-    integer :: t1, j1, i1, k1
-    real :: c2, s2, amp, ang, rel, isoC
-    real*8 :: pi8 = real(3.1415926535898, 8)
-    do t1 = 1, kmax
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          c2 = 0.0; s2 = 0.0
-          do k1 = 1, nz - 1
-            c2 = c2 + lsen(j1*nx + i1 + 1, t1, k1)*gcf(i1, j1, k1)
-            s2 = s2 + lsen(j1*nx + i1 + 1, t1, k1)*gsf(i1, j1, k1)
-          end do
-          amp = sqrt(c2**2 + s2**2)
-          isoC = real(pv(j1*nx + i1 + 1, t1))
-          rel = amp/isoC
-          ang = atan2(s2, c2)/pi8*180
-          if (ang < 0.0) ang = ang + 360
-          ang = 0.5*ang
-          write (unit, '(10f10.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), isoC, ang, rel, amp, c2, s2
-        end do
-      end do
-    end do
   end subroutine
 end program

@@ -11,6 +11,7 @@
 program SurfAAForward_amd
   use iso_c_binding
   use dazim_mod
+  use dazim_io, only: para_t, great_circle, fast_axis, write_period_azimuthal
   implicit none
   real, parameter :: pi = 3.1415926535898
   character(len=100) :: inputfile, logfile
@@ -30,6 +31,7 @@ program SurfAAForward_amd
   real :: sta1_lat, sta1_lon, sta2_lat, sta2_lon, velvalue, dist1, sta1_latD, sta1_lonD, Tvalue, velTrue, vsref
   real :: sumObs, sumNoise, sumAdd, sumTnos
   type(c_ptr) :: G
+  type(para_t) :: p                          ! the grid and the periods, for dazim_io's writer
   integer(8) :: c0, c1, c2, crate
 
   call system_clock(c0, crate)
@@ -189,8 +191,8 @@ program SurfAAForward_amd
                            goxd, gozd, dvxd, dvzd, kmaxRc, tRc, periods, depz, minthk, &
                            scxf, sczf, rcxf, rczf, nrc1, nsrc1, kmax, nsrc, nrc, writepath)
   write (*, *) ' Construct True Traveltime using True Sensitivity over!'
-  open (42, file='period_Azm_tomo.real', status='replace', action='write')
-  call write_period_azimuthal(42)
+  p%nx = nx; p%ny = ny; p%nz = nz; p%goxd = goxd; p%gozd = gozd; p%dvxd = dvxd; p%dvzd = dvzd; p%kmaxRc = kmaxRc; p%tRc = tRc
+  call write_period_azimuthal('period_Azm_tomo.real', p, Lsen_Gsc, gcf, gsf, tRcV)
 
   ! ---- noise and the synthetic data file, fwd/MainForward.f90:384-437 ----
   sumObs = 0; sumNoise = 0; sumAdd = 0
@@ -267,19 +269,6 @@ contains
     write (unit, '(a,f13.3)') '  Mean noisy Phase C (%): ', sumTnos/dall*100
   end subroutine
 
-  ! great-circle distance on a 6371 km sphere from colatitude/longitude in radians (haversine, fp32); fwd/delsph.f90
-  subroutine great_circle(colat1, lon1, colat2, lon2, del)
-    real, intent(in) :: colat1, lon1, colat2, lon2
-    real, intent(out) :: del
-    real :: dlat, dlon, lat1, lat2, a
-    dlat = colat2 - colat1
-    dlon = lon2 - lon1
-    lat1 = pi/2 - colat1
-    lat2 = pi/2 - colat2
-    a = sin(dlat/2)*sin(dlat/2) + sin(dlon/2)*sin(dlon/2)*cos(lat1)*cos(lat2)
-    del = 6371.0*(2*atan2(sqrt(a), sqrt(1 - a)))
-  end subroutine
-
   ! one standard normal deviate per call, polar Box-Muller on random_number like fwd/gaussian.f90 (which also
   ! discards the second deviate of each pair)
   real function normal_deviate()
@@ -296,49 +285,18 @@ contains
     normal_deviate = x1*w
   end function
 
-  ! period maps of the 2-psi terms A1 = sum_k Lsen*Gc, A2 = sum_k Lsen*Gs; fwd/FwdAzimuthalAniMap.f90:1
-  subroutine write_period_azimuthal(unit)
-    integer, intent(in) :: unit
-    integer :: t1, j1, i1, k1
-    real :: c2, s2, amp, ang, rel, isoC
-    real*8 :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
-    do t1 = 1, kmaxRc
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          c2 = 0.0; s2 = 0.0
-          do k1 = 1, nz - 1
-            c2 = c2 + Lsen_Gsc(j1*nx + i1 + 1, t1, k1)*gcf(i1, j1, k1)
-            s2 = s2 + Lsen_Gsc(j1*nx + i1 + 1, t1, k1)*gsf(i1, j1, k1)
-          end do
-          amp = sqrt(c2**2 + s2**2)
-          isoC = tRcV((j1 - 1)*(nx - 2) + i1, t1)
-          rel = amp/isoC
-          ang = atan2(s2, c2)/pi8*180
-          if (ang < 0.0) ang = ang + 360
-          ang = 0.5*ang
-          write (unit, '(10f10.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), isoC, ang, rel, amp, c2, s2
-        end do
-      end do
-    end do
-    close (unit)
-  end subroutine
-
   ! Gc_Gs_model.real (writeAzimuthal with the mid-layer Vs) and Vs_model.real, fwd/MainForward.f90:459-481
   subroutine write_models(ugc, uvs)
     integer, intent(in) :: ugc, uvs
     integer :: k1, j1, i1
-    real :: c2, s2, amp, ang, vsmid
-    real*8 :: pi8 = real(3.1415926535898, 8)
+    real :: c2, s2, amp, vsmid
     do k1 = 1, nz - 1
       do j1 = 1, ny - 2
         do i1 = 1, nx - 2
           c2 = gcf(i1, j1, k1); s2 = gsf(i1, j1, k1)
           amp = 0.5*sqrt(c2**2 + s2**2)
-          ang = atan2(s2, c2)/pi8*180
-          if (ang < 0.0) ang = ang + 360
-          ang = 0.5*ang
           vsmid = (vsf(i1 + 1, j1 + 1, k1) + vsf(i1 + 1, j1 + 1, k1 + 1))/2
-          write (ugc, '(8f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1 + 1), vsmid, ang, amp, c2*100, s2*100
+          write (ugc, '(8f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1 + 1), vsmid, fast_axis(c2, s2), amp, c2*100, s2*100
           write (uvs, '(5f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, (depz(k1) + depz(k1 + 1))/2, vsmid
         end do
       end do

@@ -1,0 +1,412 @@
+! dazim_io.f90 -- the readers and writers the host programs share: para.in, the traveltime data file, MOD and the per-period map
+! files in; MOD, DSurfTomo.inv, phase-velocity maps and the two azimuthal files out; optional numeric command-line arguments.
+! Every procedure gets what it needs through its arguments.  The module uses neither dazim_mod nor the HIP library, so it compiles,
+! links and runs on a machine without a GPU (tests/test_host_io_cpu.py).  Output formats and the fp32 / real*8 kind of every printed
+! value are those of the reference program (inv/Main_Jt.f90); compile with -O2 -ffp-contract=off like the programs.
+module dazim_io
+  implicit none
+  private
+  public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
+  public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
+
+  real, parameter :: pi = 3.1415926535898
+  real*8, parameter :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
+
+  type para_t                                ! para.in's values under the reference's names, inv/Main_Jt.f90:158-214
+    character(len=80) :: datafile
+    integer :: nx, ny, nz, nsrc, maxiter, kmaxRc
+    real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp
+    logical :: iso_mod
+    real*8, allocatable :: tRc(:)            ! (size 0 when kmaxRc <= 0)
+  end type
+
+  interface optional_arg
+    module procedure int_arg, int8_arg, real_arg
+  end interface
+
+contains
+
+  subroutine read_para(inputfile, p)
+    character(len=*), intent(in) :: inputfile
+    type(para_t), intent(out) :: p
+    character(len=40) :: dummy
+    integer :: u, i
+    open (newunit=u, file=inputfile, status='old', action='read')
+    read (u, '(a30)') dummy
+    read (u, '(a30)') dummy
+    read (u, '(a30)') dummy
+    read (u, *) p%datafile
+    read (u, *) p%nx, p%ny, p%nz
+    read (u, *) p%goxd, p%gozd
+    read (u, *) p%dvxd, p%dvzd
+    read (u, *) p%minthk
+    read (u, *) p%Minvel, p%Maxvel
+    read (u, *) p%nsrc
+    read (u, *) p%spfra
+    read (u, *) p%maxiter
+    read (u, *) p%iso_mod
+    read (u, '(a30)') dummy
+    read (u, *) p%weightVs
+    read (u, *) p%weightGcs
+    read (u, *) p%damp
+    read (u, '(a30)') dummy
+    read (u, *) p%kmaxRc
+    allocate (p%tRc(max(p%kmaxRc, 0)))
+    if (p%kmaxRc > 0) read (u, *) (p%tRc(i), i=1, p%kmaxRc)
+    close (u)
+  end subroutine
+
+  ! the traveltime data file, inv/Main_Jt.f90:240-318: sources and receivers per period as colatitude / longitude in radians,
+  ! traveltimes obst = distance / velocity.  At most nsrc receivers per source.  Unit 66 is the caller's open log.
+  subroutine read_data(p, scxf, sczf, rcxf, rczf, periods, nrc1, nsrc1, obst, dist, dall)
+    type(para_t), intent(in) :: p
+    real, allocatable, intent(out) :: scxf(:, :), sczf(:, :), rcxf(:, :, :), rczf(:, :, :), obst(:), dist(:)
+    integer, allocatable, intent(out) :: periods(:, :), nrc1(:, :), nsrc1(:)
+    integer, intent(out) :: dall
+    character(len=200) :: line
+    character :: str1
+    logical :: ex
+    integer :: u, err, nsrc, nrc, kmax, istep, istep1, knum, knumo, period, wavetp, veltp
+    real :: sta1_lat, sta1_lon, sta2_lat, sta2_lon, velvalue, dist1
+    nsrc = p%nsrc; nrc = p%nsrc; kmax = p%kmaxRc
+    inquire (file=p%datafile, exist=ex)
+    if (.not. ex) then
+      write (66, '(a)') 'unable to open the datafile'
+      close (66)
+      stop 'unable to open the datafile'
+    end if
+    write (*, *) 'begin load data file.....'
+    allocate (scxf(nsrc, kmax), sczf(nsrc, kmax), rcxf(nrc, nsrc, kmax), rczf(nrc, nsrc, kmax))
+    allocate (periods(nsrc, kmax), nrc1(nsrc, kmax), nsrc1(kmax))
+    scxf = 0; sczf = 0; rcxf = 0; rczf = 0; periods = 0; nrc1 = 0; nsrc1 = 0
+    ! two passes: count the data lines, then fill (the reference sizes obst by nrc*nsrc*kmax instead)
+    open (newunit=u, file=p%datafile, status='old')
+    dall = 0
+    do
+      read (u, '(a)', iostat=err) line
+      if (err /= 0) exit
+      if (line(1:1) /= '#') dall = dall + 1
+    end do
+    rewind (u)
+    allocate (obst(dall), dist(dall))
+    dall = 0; istep = 0; istep1 = 0; knum = 0; knumo = 12345
+    do
+      read (u, '(a)', iostat=err) line
+      if (err /= 0) exit
+      if (line(1:1) == '#') then
+        read (line, *) str1, sta1_lat, sta1_lon, period, wavetp, veltp
+        if (wavetp == 2 .and. veltp == 0) knum = period
+        if (wavetp == 2 .and. veltp == 1) stop 'can not deal with Rayleigh wave group data'
+        if (wavetp == 1 .and. veltp == 0) stop 'can not deal with Love wave phase data'
+        if (wavetp == 1 .and. veltp == 1) stop 'can not deal with Love wave group data'
+        if (knum < 1 .or. knum > kmax) stop 'period index in the data file exceeds kmaxRc'
+        if (knum /= knumo) istep = 0
+        istep = istep + 1
+        if (istep > nsrc) stop 'more sources per period than para.in allows: increase max(sources, receivers)'
+        istep1 = 0
+        sta1_lat = (90.0 - sta1_lat)*pi/180.0
+        sta1_lon = sta1_lon*pi/180.0
+        scxf(istep, knum) = sta1_lat
+        sczf(istep, knum) = sta1_lon
+        periods(istep, knum) = period
+        nsrc1(knum) = istep
+        knumo = knum
+      else
+        read (line, *) sta2_lat, sta2_lon, velvalue
+        istep1 = istep1 + 1
+        if (istep1 > nrc) stop 'more receivers per source than para.in allows: increase max(sources, receivers)'
+        dall = dall + 1
+        sta2_lat = (90.0 - sta2_lat)*pi/180.0
+        sta2_lon = sta2_lon*pi/180.0
+        rcxf(istep1, istep, knum) = sta2_lat
+        rczf(istep1, istep, knum) = sta2_lon
+        call great_circle(sta1_lat, sta1_lon, sta2_lat, sta2_lon, dist1)
+        dist(dall) = dist1
+        obst(dall) = dist1/velvalue
+        nrc1(istep, knum) = istep1
+      end if
+    end do
+    close (u)
+    write (*, '(a,i7)') ' Number of all measurements', dall
+  end subroutine
+
+  ! a model in the MOD format (MOD, MOD_Ref, ...), inv/Main_Jt.f90:346-356
+  subroutine read_mod(fname, p, depz, vsf)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real, allocatable, intent(out) :: depz(:), vsf(:, :, :)
+    integer :: u, i, j, k
+    allocate (depz(p%nz), vsf(p%nx, p%ny, p%nz))
+    open (newunit=u, file=fname, status='old')
+    vsf = 0
+    read (u, *) (depz(i), i=1, p%nz)
+    do k = 1, p%nz
+      do j = 1, p%ny
+        read (u, *) (vsf(i, j, k), i=1, p%nx)
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! column icol of a map file in the order SurfPhaseMaps_amd writes it (period, then latitude row, then longitude); every line's
+  ! longitude, latitude and period must be para.in's inner grid and periods (1e-3).  announce: ' read <file>' to stdout and unit 66.
+  subroutine read_map(fname, p, ncol, icol, out, announce)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    integer, intent(in) :: ncol, icol
+    real, intent(out) :: out(p%nx - 2, p%ny - 2, p%kmaxRc)
+    logical, intent(in) :: announce
+    character(len=300) :: line
+    real :: vals(9)
+    integer :: u, i1, j1, t1, ios, q
+    logical :: there
+    inquire (file=fname, exist=there)
+    if (.not. there) then
+      write (*, '(a,a,a)') ' ERROR: ', fname, ' is missing (SurfPhaseMaps_amd writes it)'
+      error stop 'a map file is missing'
+    end if
+    open (newunit=u, file=fname, status='old', action='read')
+    do t1 = 1, p%kmaxRc
+      do j1 = 1, p%ny - 2
+        do i1 = 1, p%nx - 2
+          read (u, '(a)', iostat=ios) line
+          if (ios == 0) read (line, *, iostat=ios) vals(1:ncol)
+          if (ios /= 0) then
+            write (*, '(a,a,a)') ' ERROR: ', fname, ' has fewer lines than para.in''s inner grid times its periods'
+            error stop 'a map file does not match para.in'
+          end if
+          if (abs(vals(3) - p%tRc(t1)) > 1e-3) then
+            write (*, '(a,a,a,f10.4,a,f10.4)') ' ERROR: ', fname, ': its periods differ from para.in''s: ', vals(3), ' for', p%tRc(t1)
+            error stop 'a map file does not match para.in'
+          end if
+          if (abs(vals(1) - (p%gozd + (j1 - 1)*p%dvzd)) > 1e-3 .or. abs(vals(2) - (p%goxd - (i1 - 1)*p%dvxd)) > 1e-3) then
+            write (*, '(a,a,a,2f10.4)') ' ERROR: ', fname, ': its coordinates are not para.in''s inner grid at', vals(1:2)
+            error stop 'a map file does not match para.in'
+          end if
+          out(i1, j1, t1) = vals(icol)
+        end do
+      end do
+    end do
+    read (u, '(a)', iostat=ios) line
+    if (ios == 0 .and. len_trim(line) > 0) then
+      write (*, '(a,a,a)') ' ERROR: ', fname, ' has more lines than para.in''s inner grid times its periods'
+      error stop 'a map file does not match para.in'
+    end if
+    close (u)
+    if (announce) then
+      do q = 6, 66, 60
+        write (q, '(a,a)') ' read ', fname
+      end do
+    end if
+  end subroutine
+
+  ! the weights of the depth and the Monte-Carlo program: 1/sigma_c on the (cell, period) pairs where period_map_coverage.dat has
+  ! DWS > 0 and 0 elsewhere; 1/sigma_c everywhere without that file.  Says which to stdout and unit 66.
+  subroutine coverage_weights(p, sigma_c, wcov)
+    type(para_t), intent(in) :: p
+    real, intent(in) :: sigma_c
+    real, intent(out) :: wcov(p%nx - 2, p%ny - 2, p%kmaxRc)
+    real, allocatable :: cov(:, :, :)
+    logical :: have_cov
+    integer :: q
+    inquire (file='period_map_coverage.dat', exist=have_cov)
+    if (have_cov) then
+      allocate (cov(p%nx - 2, p%ny - 2, p%kmaxRc))
+      call read_map('period_map_coverage.dat', p, 4, 4, cov, .true.)
+      wcov = merge(1.0/sigma_c, 0.0, cov > 0.0)
+      do q = 6, 66, 60
+        write (q, '(a,i8,a,i8)') ' period_map_coverage.dat: weight 1/sigma_c on the (cell, period) pairs with DWS > 0:', &
+          count(cov > 0.0), ' of', size(cov)
+      end do
+    else
+      wcov = 1.0/sigma_c
+      do q = 6, 66, 60
+        write (q, '(a)') ' period_map_coverage.dat is absent: weight 1/sigma_c on every cell and period'
+      end do
+    end if
+  end subroutine
+
+  ! great-circle distance on a 6371 km sphere from colatitude/longitude in radians (haversine, fp32); inv/delsph.f90:1
+  subroutine great_circle(colat1, lon1, colat2, lon2, del)
+    real, intent(in) :: colat1, lon1, colat2, lon2
+    real, intent(out) :: del
+    real :: dlat, dlon, lat1, lat2, a
+    dlat = colat2 - colat1
+    dlon = lon2 - lon1
+    lat1 = pi/2 - colat1
+    lat2 = pi/2 - colat2
+    a = sin(dlat/2)*sin(dlat/2) + sin(dlon/2)*sin(dlon/2)*cos(lat1)*cos(lat2)
+    del = 6371.0*(2*atan2(sqrt(a), sqrt(1 - a)))
+  end subroutine
+
+  ! the inner cells of full-grid maps pv(nx*ny, kmax), in the order the map files list them
+  function inner_cells(nx, ny, kmax, pv) result(c)
+    integer, intent(in) :: nx, ny, kmax
+    real*8, intent(in) :: pv(nx, ny, kmax)
+    real*8 :: c(nx - 2, ny - 2, kmax)
+    c = pv(2:nx - 1, 2:ny - 1, :)
+  end function
+
+  ! optional numeric command-line argument n: v keeps its value when there are fewer than n arguments; text that is not a
+  ! number ends the program
+  subroutine int_arg(n, v)
+    integer, intent(in) :: n
+    integer, intent(inout) :: v
+    character(len=100) :: arg
+    integer :: ios
+    if (command_argument_count() < n) return
+    call get_command_argument(n, arg)
+    read (arg, *, iostat=ios) v
+    if (ios /= 0) call bad_arg(n, arg)
+  end subroutine
+
+  subroutine int8_arg(n, v)
+    integer, intent(in) :: n
+    integer(8), intent(inout) :: v
+    character(len=100) :: arg
+    integer :: ios
+    if (command_argument_count() < n) return
+    call get_command_argument(n, arg)
+    read (arg, *, iostat=ios) v
+    if (ios /= 0) call bad_arg(n, arg)
+  end subroutine
+
+  subroutine real_arg(n, v)
+    integer, intent(in) :: n
+    real, intent(inout) :: v
+    character(len=100) :: arg
+    integer :: ios
+    if (command_argument_count() < n) return
+    call get_command_argument(n, arg)
+    read (arg, *, iostat=ios) v
+    if (ios /= 0) call bad_arg(n, arg)
+  end subroutine
+
+  subroutine bad_arg(n, arg)
+    integer, intent(in) :: n
+    character(len=*), intent(in) :: arg
+    write (*, '(a,i2,a,a)') ' ERROR: argument', n, ' is not a number: ', trim(arg)
+    error stop 'bad argument'
+  end subroutine
+
+  ! MOD format: the depth line, then the velocities row by row (MOD_Ref: inv/Main_Jt.f90:751-765)
+  subroutine write_mod(fname, depz, vs)
+    character(len=*), intent(in) :: fname
+    real, intent(in) :: depz(:), vs(:, :, :)
+    integer :: u, i, j, k
+    open (newunit=u, file=fname)
+    do k = 1, size(depz)
+      write (u, '(f7.1)', advance='no') depz(k)
+    end do
+    do k = 1, size(vs, 3)
+      do j = 1, size(vs, 2)
+        do i = 1, size(vs, 1)
+          if (i == 1) then
+            write (u, '(/f8.4)', advance='no') vs(i, j, k)
+          else
+            write (u, '(f8.4)', advance='no') vs(i, j, k)
+          end if
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! lon lat depth Vs on the whole grid, outer ring included; writeVsmodel, inv/Main_Jt.f90:838
+  subroutine write_vs_model(fname, p, depz, vs)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real, intent(in) :: depz(:), vs(:, :, :)
+    integer :: u, i, j, k
+    open (newunit=u, file=fname)
+    do k = 1, p%nz
+      do j = 1, p%ny
+        do i = 1, p%nx
+          write (u, '(5f8.4)') p%gozd + (j - 2)*p%dvzd, p%goxd - (i - 2)*p%dvxd, depz(k), vs(i, j, k)
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! lon lat period c for the inner cells; WTPeriodPhaseV, inv/Main_Jt.f90:889
+  subroutine write_phase_map(fname, p, c)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real*8, intent(in) :: c(p%nx - 2, p%ny - 2, p%kmaxRc)
+    integer :: u, t1, j1, i1
+    open (newunit=u, file=fname)
+    do t1 = 1, p%kmaxRc
+      do j1 = 1, p%ny - 2
+        do i1 = 1, p%nx - 2
+          write (u, '(5f10.4)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), c(i1, j1, t1)
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! fast-axis angle in degrees, [0, 180), of the 2-psi terms (c2, s2)
+  real function fast_axis(c2, s2) result(ang)
+    real, intent(in) :: c2, s2
+    ang = atan2(s2, c2)/pi8*180
+    if (ang < 0.0) ang = ang + 360
+    ang = 0.5*ang
+  end function
+
+  ! lon lat depth Vs fast-axis angle, amplitude, Gc/L %, Gs/L %; writeAzimuthal, inv/Main_Jt.f90:859
+  subroutine write_azimuthal(fname, p, depz, vs, gc, gs)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real, intent(in) :: depz(:), vs(:, :, :), gc(:, :, :), gs(:, :, :)
+    integer :: u, k1, j1, i1
+    real :: c2, s2
+    open (newunit=u, file=fname)
+    do k1 = 1, p%nz - 1
+      do j1 = 1, p%ny - 2
+        do i1 = 1, p%nx - 2
+          c2 = gc(i1, j1, k1); s2 = gs(i1, j1, k1)
+          write (u, '(8f10.4)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, depz(k1 + 1), &
+            (vs(i1 + 1, j1 + 1, k1) + vs(i1 + 1, j1 + 1, k1 + 1))/2, fast_axis(c2, s2), 0.5*sqrt(c2**2 + s2**2), c2*100, s2*100
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! one line of a period_Azm_tomo file: lon lat period c, fast-axis angle, amplitude relative to c, amplitude, and the 2-psi terms
+  ! c2, s2 themselves (isoC: c in fp32, as the reference holds it)
+  subroutine write_azm_line(u, lon, lat, period, isoC, c2, s2)
+    integer, intent(in) :: u
+    real, intent(in) :: lon, lat, isoC, c2, s2
+    real*8, intent(in) :: period
+    real :: amp
+    amp = sqrt(c2**2 + s2**2)
+    write (u, '(10f10.5)') lon, lat, period, isoC, fast_axis(c2, s2), amp/isoC, amp, c2, s2
+  end subroutine
+
+  ! period maps of the 2-psi terms A1 = sum_k Lsen*Gc, A2 = sum_k Lsen*Gs; inv/FwdAzimuthalAniMap.f90:1.  lsen on the full grid,
+  ! gc, gs and c on the inner cells.
+  subroutine write_period_azimuthal(fname, p, lsen, gc, gs, c)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real, intent(in) :: lsen(p%nx*p%ny, p%kmaxRc, p%nz - 1), gc(:, :, :), gs(:, :, :)
+    real*8, intent(in) :: c(p%nx - 2, p%ny - 2, p%kmaxRc)
+    integer :: u, t1, j1, i1, k1
+    real :: c2, s2
+    open (newunit=u, file=fname, status='replace', action='write')
+    do t1 = 1, p%kmaxRc
+      do j1 = 1, p%ny - 2
+        do i1 = 1, p%nx - 2
+          c2 = 0.0; s2 = 0.0
+          do k1 = 1, p%nz - 1
+            c2 = c2 + lsen(j1*p%nx + i1 + 1, t1, k1)*gc(i1, j1, k1)
+            s2 = s2 + lsen(j1*p%nx + i1 + 1, t1, k1)*gs(i1, j1, k1)
+          end do
+          call write_azm_line(u, p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), real(c(i1, j1, t1)), c2, s2)
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+end module

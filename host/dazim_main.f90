@@ -15,27 +15,23 @@
 program DAzimSurfTomo_amd
   use iso_c_binding
   use dazim_mod
+  use dazim_io
   implicit none
-  real, parameter :: pi = 3.1415926535898
   character(len=100) :: inputfile, logfile
   character(len=80) :: datafile
-  character(len=200) :: line
-  character(len=40) :: dummy
-  character :: str1
+  type(para_t) :: p
   logical :: ex, iso_mod
   logical, external :: ti_kernels_on_device
-  integer :: nx, ny, nz, nsrc, nrc, maxiter, kmaxRc, kmax, err
+  integer :: nx, ny, nz, nsrc, nrc, maxiter, kmaxRc, kmax
   real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp
-  real*8, allocatable :: tRc(:), tRcV(:, :), pv(:, :)
+  real*8, allocatable :: tRc(:), tRcV(:, :, :), pv(:, :)
   real, allocatable :: depz(:), vsf(:, :, :), gcf(:, :, :), gsf(:, :, :), Lsen_Gsc(:, :, :)
   real, allocatable :: scxf(:, :), sczf(:, :), rcxf(:, :, :), rczf(:, :, :)
   integer, allocatable :: periods(:, :), nrc1(:, :), nsrc1(:)
   real, allocatable :: obst(:), dist(:), dsyn(:), cbst(:), sigmaT(:), datweight(:), Tdata(:), resbst(:), fwdTvs(:), fwdTaa(:)
   real, allocatable :: dv(:), norm(:), yfull(:), xtmp(:), rwreg(:)
   integer, allocatable :: rowreg(:), colreg(:)
-  integer :: dall, maxvp, maxm, iter, i, j, k, ii, jj, tt, nar, nar1, nreg, count3, narVs, m, n, istop, itn, itnlim, localSize
-  integer :: istep, istep1, knum, knumo, period, wavetp, veltp
-  real :: sta1_lat, sta1_lon, sta2_lat, sta2_lon, velvalue, dist1
+  integer :: dall, maxvp, maxm, iter, i, j, k, nar, nar1, nreg, count3, narVs, m, n, istop, itn, itnlim, localSize
   real :: mean, std_devs, meanAbs, meandeltaT, atol, btol, conlim, anorm, acond, rnorm, arnorm, xnorm, pertV
   real :: mindVs, maxdVs, meadVs, minGc, maxGc, meaGc, minGs, maxGs, meaGs, VariVs, VariGc, VariGs
   integer(8) :: maxnar
@@ -71,7 +67,10 @@ program DAzimSurfTomo_amd
   if (.not. ex) stop 'unable to open the inputfile'
 
   ! ---- para.in, inv/Main_Jt.f90:158-214 -------------------------------------------------------------
-  include 'read_para.inc'
+  call read_para(inputfile, p)
+  datafile = p%datafile; nx = p%nx; ny = p%ny; nz = p%nz; goxd = p%goxd; gozd = p%gozd; dvxd = p%dvxd; dvzd = p%dvzd
+  minthk = p%minthk; Minvel = p%Minvel; Maxvel = p%Maxvel; nsrc = p%nsrc; spfra = p%spfra; maxiter = p%maxiter; iso_mod = p%iso_mod
+  weightVs = p%weightVs; weightGcs = p%weightGcs; damp = p%damp; kmaxRc = p%kmaxRc; tRc = p%tRc
   write (*, *) 'input Rayleigh wave phase velocity data file:'
   write (*, '(a)') datafile
   write (*, *) 'model origin:latitude,longitue'
@@ -111,19 +110,19 @@ program DAzimSurfTomo_amd
   kmax = kmaxRc
 
   ! ---- traveltime data file, inv/Main_Jt.f90:240-318 -------------------------------------------------
-  include 'read_data.inc'
+  call read_data(p, scxf, sczf, rcxf, rczf, periods, nrc1, nsrc1, obst, dist, dall)
 
   maxvp = (nx - 2)*(ny - 2)*(nz - 1)
   maxnar = int(spfra*real(dall)*real(nx)*real(ny)*real(nz)*3.0, 8)     ! sparsity fraction, inv/Main_Jt.f90:324
-  allocate (depz(nz), vsf(nx, ny, nz), dv(3*maxvp), norm(maxvp), cbst(dall + 3*maxvp), dsyn(dall))
+  allocate (dv(3*maxvp), norm(maxvp), cbst(dall + 3*maxvp), dsyn(dall))
   allocate (sigmaT(dall), datweight(dall), Tdata(dall), resbst(dall), fwdTvs(dall), fwdTaa(dall))
   allocate (Lsen_Gsc(nx*ny, kmaxRc, nz - 1), gcf(nx - 2, ny - 2, nz - 1), gsf(nx - 2, ny - 2, nz - 1))
-  allocate (tRcV((nx - 2)*(ny - 2), kmaxRc), pv(nx*ny, kmaxRc))
+  allocate (tRcV(nx - 2, ny - 2, kmaxRc), pv(nx*ny, kmaxRc))
   allocate (yfull(dall + 3*maxvp), xtmp(3*maxvp), rwreg(7*3*maxvp), rowreg(7*3*maxvp), colreg(7*3*maxvp))
   gcf = 0; gsf = 0; Lsen_Gsc = 0
 
   ! ---- initial model, inv/Main_Jt.f90:346-356 -----------------------------------------------------------
-  include 'read_mod.inc'
+  call read_mod('MOD', p, depz, vsf)
   write (*, *) ' grid points in depth direction:(km)'
   write (*, '(50f7.2)') depz
 
@@ -201,20 +200,10 @@ program DAzimSurfTomo_amd
     call dazim_allsum(dsyn, dall)
     call dazim_check(dazim_set_option(dazim_handle, 'rays.dense_twin'//c_null_char, 0_c_int), 'option')
     call dazim_check(dazim_csr_take_twin(dazim_handle, G, Gd), 'dense twin')
-    if (.not. iso_mod) then                       ! inv/CalSurfGAniso_Joint.f90:801-811 (the iso branch leaves tRcV = 0)
-      do tt = 1, kmaxRc
-        do jj = 1, ny - 2
-          do ii = 1, nx - 2
-            tRcV((jj - 1)*(nx - 2) + ii, tt) = pv(jj*nx + ii + 1, tt)
-          end do
-        end do
-      end do
-    end if
+    ! inv/CalSurfGAniso_Joint.f90:801-811 (the iso branch leaves tRcV = 0)
+    if (.not. iso_mod) tRcV = inner_cells(nx, ny, kmaxRc, pv)
     call tick(3)                             ! dispersion + eikonal + rays + G on the device
-    if (iter == 1) then
-      open (77, file='period_phaseVMOD.dat')
-      call write_phase_maps(77)
-    end if
+    if (iter == 1) call write_phase_map('period_phaseVMOD.dat', p, tRcV)
     call tick(9)
 
     ! ---- residuals, CalDdatSigma weights, weighted right-hand side and row scaling on the device, inv/Main_Jt.f90:432-470 ----
@@ -391,39 +380,12 @@ program DAzimSurfTomo_amd
   end do
 
   ! ---- final models, inv/Main_Jt.f90:751-790 ---------------------------------------------------------------------------------
-  open (11, file='MOD_Ref')
-  do k = 1, nz
-    write (11, '(f7.1)', advance='no') depz(k)
-  end do
-  do k = 1, nz
-    do j = 1, ny
-      do i = 1, nx
-        if (i == 1) then
-          write (11, '(/f8.4)', advance='no') vsf(i, j, k)
-        else
-          write (11, '(f8.4)', advance='no') vsf(i, j, k)
-        end if
-      end do
-    end do
-  end do
-  close (11)
-  open (63, file='DSurfTomo.inv')
-  do k = 1, nz                                            ! writeVsmodel, inv/Main_Jt.f90:838
-    do j = 1, ny
-      do i = 1, nx
-        write (63, '(5f8.4)') gozd + (j - 2)*dvzd, goxd - (i - 2)*dvxd, depz(k), vsf(i, j, k)
-      end do
-    end do
-  end do
-  close (63)
-  open (73, file='Gc_Gs_model.inv')
-  call write_azimuthal(73)
-  close (73)
-  open (77, file='phaseV_FWD.dat')
-  call write_phase_maps(77)
+  call write_mod('MOD_Ref', depz, vsf)
+  call write_vs_model('DSurfTomo.inv', p, depz, vsf)
+  call write_azimuthal('Gc_Gs_model.inv', p, depz, vsf, gcf, gsf)
+  call write_phase_map('phaseV_FWD.dat', p, tRcV)
   write (*, '(a)') '  Begin forward calculate period azimuthal A1, A2.'
-  open (42, file='period_Azm_tomo.inv', status='replace', action='write')
-  call write_period_azimuthal(42)
+  call write_period_azimuthal('period_Azm_tomo.inv', p, Lsen_Gsc, gcf, gsf, tRcV)
   write (66, *) '  -----------------------------------------------------------'
   write (*, *) '  Program finishes successfully'
   write (66, *) '  Program finishes successfully'
@@ -450,8 +412,6 @@ contains
     tph(i) = tph(i) + real(tk1 - tk0, 8)/real(tkrate, 8)
     tk0 = tk1
   end subroutine
-
-  include 'great_circle.inc'
 
   ! scaled 2-norm like the reference's dnrm2 (inv/lsmrblas.f90:247)
   real function nrm2(nn, x)
@@ -578,68 +538,5 @@ contains
       write (66, '(a,f12.4,a)') '  ABS Mean T(dVs):', mabs, 's'
       write (6, '(a,f12.4,a)') '  ABS Mean T(dVs):', mabs, 's'
     end if
-  end subroutine
-
-  ! lon lat period c for the inner cells; WTPeriodPhaseV, inv/Main_Jt.f90:889 (closes the unit like the reference)
-  subroutine write_phase_maps(unit)
-    integer, intent(in) :: unit
-    integer :: t1, j1, i1
-    do t1 = 1, kmaxRc
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          write (unit, '(5f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), tRcV((j1 - 1)*(nx - 2) + i1, t1)
-        end do
-      end do
-    end do
-    close (unit)
-  end subroutine
-
-  ! lon lat depth Vs fast-axis angle, amplitude, Gc/L %, Gs/L %; writeAzimuthal, inv/Main_Jt.f90:859
-  subroutine write_azimuthal(unit)
-    integer, intent(in) :: unit
-    integer :: k1, j1, i1
-    real :: c2, s2, amp, ang, vsref
-    real*8 :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
-    do k1 = 1, nz - 1
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          c2 = gcf(i1, j1, k1); s2 = gsf(i1, j1, k1)
-          amp = 0.5*sqrt(c2**2 + s2**2)
-          ang = atan2(s2, c2)/pi8*180
-          if (ang < 0.0) ang = ang + 360
-          ang = 0.5*ang
-          vsref = (vsf(i1 + 1, j1 + 1, k1) + vsf(i1 + 1, j1 + 1, k1 + 1))/2
-          write (unit, '(8f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1 + 1), vsref, ang, amp, &
-            gcf(i1, j1, k1)*100, gsf(i1, j1, k1)*100
-        end do
-      end do
-    end do
-  end subroutine
-
-  ! period maps of the 2-psi terms A1 = sum_k Lsen*Gc, A2 = sum_k Lsen*Gs; inv/FwdAzimuthalAniMap.f90:1
-  subroutine write_period_azimuthal(unit)
-    integer, intent(in) :: unit
-    integer :: t1, j1, i1, k1
-    real :: c2, s2, amp, ang, rel, isoC
-    real*8 :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
-    do t1 = 1, kmaxRc
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          c2 = 0.0; s2 = 0.0
-          do k1 = 1, nz - 1
-            c2 = c2 + Lsen_Gsc(j1*nx + i1 + 1, t1, k1)*gcf(i1, j1, k1)
-            s2 = s2 + Lsen_Gsc(j1*nx + i1 + 1, t1, k1)*gsf(i1, j1, k1)
-          end do
-          amp = sqrt(c2**2 + s2**2)
-          isoC = tRcV((j1 - 1)*(nx - 2) + i1, t1)
-          rel = amp/isoC
-          ang = atan2(s2, c2)/pi8*180
-          if (ang < 0.0) ang = ang + 360
-          ang = 0.5*ang
-          write (unit, '(10f10.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), isoC, ang, rel, amp, c2, s2
-        end do
-      end do
-    end do
-    close (unit)
   end subroutine
 end program

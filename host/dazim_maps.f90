@@ -3,8 +3,8 @@
 !
 !   SurfPhaseMaps_amd para.in [weight_c [weight_a]]
 !
-! Inputs: the unchanged para.in, traveltime data file and MOD of DAzimSurfTomo_amd (the same readers: read_para.inc,
-! read_data.inc, read_mod.inc).  Starting maps: MOD's dispersion curves (dazim_dispersion_kernels without kernels), the 3-D
+! Inputs: the unchanged para.in, traveltime data file and MOD of DAzimSurfTomo_amd (the same readers, module dazim_io:
+! read_para, read_data, read_mod).  Starting maps: MOD's dispersion curves (dazim_dispersion_kernels without kernels), the 3-D
 ! program's own first-iteration pvRc.  Each of para.in's iterations: eikonal fields on the current maps, map rows
 ! (dazim_rays_build_G_maps: dt = fdm.dc + fdmc.a1 + fdms.a2, one column block per period), CalDdatSigma weights
 ! (dazim_weight_data), 2-D regularisation (dazim_csr_append_laplacian2d: weight_c on the c maps, weight_a on the a1 / a2 maps;
@@ -24,23 +24,19 @@
 program SurfPhaseMaps_amd
   use iso_c_binding
   use dazim_mod
+  use dazim_io
   implicit none
-  real, parameter :: pi = 3.1415926535898
-  character(len=100) :: inputfile, logfile, arg
-  character(len=80) :: datafile
-  character(len=200) :: line
-  character(len=40) :: dummy
-  character :: str1
+  character(len=100) :: inputfile, logfile
+  type(para_t) :: p
   logical :: ex, iso_mod
-  integer :: nx, ny, nz, nsrc, nrc, maxiter, kmaxRc, kmax, err
-  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp, weight_c, weight_a
+  integer :: nx, ny, nz, nsrc, nrc, maxiter, kmax
+  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, damp, weight_c, weight_a
   real*8, allocatable :: tRc(:)
   real, allocatable :: depz(:), vsf(:, :, :)
   real, allocatable :: scxf(:, :), sczf(:, :), rcxf(:, :, :), rczf(:, :, :)
   integer, allocatable :: periods(:, :), nrc1(:, :), nsrc1(:)
   real, allocatable :: obst(:), dist(:)
-  integer :: dall, i, j, k, istep, istep1, knum, knumo, period, wavetp, veltp
-  real :: sta1_lat, sta1_lon, sta2_lat, sta2_lon, velvalue, dist1
+  integer :: dall, i
   ! the map inversion
   real*8, allocatable, target :: pv(:, :)
   real, allocatable :: dsyn(:), Tdata(:), datweight(:), cbst(:), dm(:), a1(:), a2(:), w(:), ustats(:, :, :), y(:), after(:)
@@ -49,8 +45,7 @@ program SurfPhaseMaps_amd
   integer(c_int) :: nfail, istop, itn
   integer(c_int64_t) :: m64, n64, z64
   real :: minc, maxc, atol, btol, conlim, anorm, acond, rnorm, arnorm, xnorm, wstats(8), amean, astd, arms
-  real :: c2, s2, amp, ang, rel, isoC, bias
-  real*8 :: pi8 = real(3.1415926535898, 8)
+  real :: bias
   type(c_ptr) :: G
 
   write (*, *)
@@ -60,40 +55,34 @@ program SurfPhaseMaps_amd
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) stop 'unable to open the inputfile'
-  include 'read_para.inc'
+  call read_para(inputfile, p)
+  nx = p%nx; ny = p%ny; nz = p%nz; goxd = p%goxd; gozd = p%gozd; dvxd = p%dvxd; dvzd = p%dvzd; minthk = p%minthk
+  Minvel = p%Minvel; Maxvel = p%Maxvel; nsrc = p%nsrc; maxiter = p%maxiter; iso_mod = p%iso_mod; damp = p%damp; kmax = p%kmaxRc
+  tRc = p%tRc
   if (nz <= 1) stop 'error nz value.'
-  if (kmaxRc <= 0) stop 'Can only deal with Rayleigh wave phase velocity data!'
-  weight_c = weightVs; weight_a = weightGcs
-  if (command_argument_count() >= 2) then
-    call get_command_argument(2, arg)
-    read (arg, *) weight_c
-  end if
-  if (command_argument_count() >= 3) then
-    call get_command_argument(3, arg)
-    read (arg, *) weight_a
-  end if
+  if (kmax <= 0) stop 'Can only deal with Rayleigh wave phase velocity data!'
+  weight_c = p%weightVs; weight_a = p%weightGcs
+  call optional_arg(2, weight_c)
+  call optional_arg(3, weight_a)
   write (logfile, '(a,a)') trim(inputfile), '_map.log'
   open (66, file=logfile)
   write (66, *)
   write (66, *) '                  SurfPhaseMaps'
   write (66, *)
   nrc = nsrc
-  kmax = kmaxRc
   minc = 0.85*Minvel; maxc = Maxvel
   ncell = (nx - 2)*(ny - 2)
   nblk = merge(1, 3, iso_mod)
   nm = ncell*kmax*nblk
   do q = 6, 66, 60
-    write (q, '(a,a)') ' data file: ', trim(datafile)
+    write (q, '(a,a)') ' data file: ', trim(p%datafile)
     write (q, '(a,3i5,a,i3,a,l2)') ' grid nx ny:', nx, ny, kmax, ' periods; iterations', maxiter, '; iso-mode', iso_mod
     write (q, '(a,50f6.1)') ' periods (s):', (tRc(i), i=1, kmax)
     write (q, '(a,2f8.3,a,f8.3,a,2f8.3)') ' smoothing c, a:', weight_c, weight_a, '  damping', damp, '  c range (km/s)', minc, maxc
   end do
 
-  include 'read_data.inc'
-  allocate (depz(nz), vsf(nx, ny, nz))
-  vsf = 0
-  include 'read_mod.inc'
+  call read_data(p, scxf, sczf, rcxf, rczf, periods, nrc1, nsrc1, obst, dist, dall)
+  call read_mod('MOD', p, depz, vsf)
 
   ! ---- starting maps: MOD's dispersion curves (= the 3-D program's first-iteration pvRc) ----------------------------------------
   call dazim_init(0)
@@ -150,29 +139,14 @@ program SurfPhaseMaps_amd
   end do
 
   ! ---- output files ------------------------------------------------------------------------------------------------------------
-  open (77, file='period_phaseV_map.dat')
-  do t1 = 1, kmax
-    do j1 = 1, ny - 2
-      do i1 = 1, nx - 2
-        write (77, '(5f10.4)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), pv(j1*nx + i1 + 1, t1)
-      end do
-    end do
-  end do
-  close (77)
-  if (.not. iso_mod) then                     ! the arithmetic of write_period_azimuthal (dazim_main.f90)
+  call write_phase_map('period_phaseV_map.dat', p, inner_cells(nx, ny, kmax, pv))
+  if (.not. iso_mod) then                     ! the lines of write_period_azimuthal from the maps' own a1, a2
     open (42, file='period_Azm_tomo_map.inv', status='replace', action='write')
     do t1 = 1, kmax
       do j1 = 1, ny - 2
         do i1 = 1, nx - 2
           q = (t1 - 1)*ncell + (j1 - 1)*(nx - 2) + i1
-          c2 = a1(q); s2 = a2(q)
-          amp = sqrt(c2**2 + s2**2)
-          isoC = real(pv(j1*nx + i1 + 1, t1))
-          rel = amp/isoC
-          ang = atan2(s2, c2)/pi8*180
-          if (ang < 0.0) ang = ang + 360
-          ang = 0.5*ang
-          write (42, '(10f10.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), isoC, ang, rel, amp, c2, s2
+          call write_azm_line(42, gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), real(pv(j1*nx + i1 + 1, t1)), a1(q), a2(q))
         end do
       end do
     end do
@@ -198,8 +172,4 @@ program SurfPhaseMaps_amd
   write (66, *) '  Program finishes successfully'
   close (66)
   call dazim_finalize()
-
-contains
-
-  include 'great_circle.inc'
 end program

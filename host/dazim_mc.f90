@@ -18,25 +18,24 @@
 program SurfDepthMC_amd
   use iso_c_binding
   use dazim_mod
+  use dazim_io
   implicit none
   integer, parameter :: nbin = 200, nadapt = 50
   real, parameter :: step0 = 0.05
-  character(len=100) :: inputfile, logfile, arg
-  character(len=80) :: datafile
-  character(len=300) :: line
-  character(len=40) :: dummy
-  logical :: ex, iso_mod, have_cov
-  integer :: nx, ny, nz, nsrc, maxiter, kmaxRc, kmax, nsample, nchain, ios
+  character(len=100) :: inputfile, logfile
+  type(para_t) :: p
+  logical :: ex
+  integer :: nx, ny, nz, kmax, nsample, nchain
   integer(c_long_long) :: seed
-  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp, width, sigma_c
+  real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, width, sigma_c
   real*8, allocatable :: tRc(:)
   real, allocatable :: depz(:), vsf(:, :, :), vmc(:, :, :), vbest(:, :, :)
   real*8, allocatable :: pvm(:, :), pvb(:, :)
-  real, allocatable :: cmap(:, :, :), cov(:, :, :), wcov(:, :, :), vmin(:, :, :), vmax(:, :, :)
+  real, allocatable :: cmap(:, :, :), wcov(:, :, :), vmin(:, :, :), vmax(:, :, :)
   real, allocatable :: mean(:, :, :), std(:, :, :), qq(:, :, :, :), best(:, :, :), rhat(:, :, :), acc(:, :), chi2b(:, :)
   real, allocatable :: sorted(:), rms_b(:, :), rms_m(:, :)
   logical, allocatable :: sampled(:, :)
-  real :: vals(9), rms_all, t_run, t_disp, t_step
+  real :: rms_all, t_run, t_disp, t_step
   real*8 :: s0, cnt
   integer :: i, j, k, t, nlay, ncell, q, ns, nr
   integer(c_int) :: nfail, nempty
@@ -50,25 +49,21 @@ program SurfDepthMC_amd
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
-  include 'read_para.inc'
+  call read_para(inputfile, p)
+  nx = p%nx; ny = p%ny; nz = p%nz; goxd = p%goxd; gozd = p%gozd; dvxd = p%dvxd; dvzd = p%dvzd; minthk = p%minthk
+  Minvel = p%Minvel; Maxvel = p%Maxvel; kmax = p%kmaxRc; tRc = p%tRc
   if (nz <= 1) error stop 'error nz value.'
-  if (kmaxRc <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
+  if (kmax <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
   nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1
-  ios = 0
-  if (command_argument_count() >= 2) call int_arg(2, nsample)
-  if (command_argument_count() >= 3) call int_arg(3, nchain)
-  if (command_argument_count() >= 4) call real_arg(4, width)
-  if (command_argument_count() >= 5) call real_arg(5, sigma_c)
-  if (command_argument_count() >= 6) then
-    call get_command_argument(6, arg)
-    read (arg, *, iostat=ios) seed
-    if (ios /= 0) call bad_arg(6)
-  end if
+  call optional_arg(2, nsample)
+  call optional_arg(3, nchain)
+  call optional_arg(4, width)
+  call optional_arg(5, sigma_c)
+  call optional_arg(6, seed)
   if (nsample < 1) error stop 'nsample must be at least 1'
   if (nchain < 1 .or. nchain > 64) error stop 'nchain must be 1..64'
   if (width < 0) error stop 'width must not be negative'
   if (sigma_c <= 0) error stop 'sigma_c must be positive'
-  kmax = kmaxRc
   nlay = nz - 1
   ncell = (nx - 2)*(ny - 2)
   if (nlay > 63) error stop 'SurfDepthMC_amd samples at most 63 knots (nz <= 64)'
@@ -93,27 +88,12 @@ program SurfDepthMC_amd
     end if
   end do
 
-  allocate (depz(nz), vsf(nx, ny, nz))
-  vsf = 0
-  include 'read_mod.inc'
+  call read_mod('MOD', p, depz, vsf)
 
   ! ---- the maps and the weights (SurfDepthFromMaps_amd's) ------------------------------------------------------------------------
-  allocate (cmap(nx - 2, ny - 2, kmax), cov(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
-  call read_map('period_phaseV_map.dat', 4, 4, cmap, .true.)
-  inquire (file='period_map_coverage.dat', exist=have_cov)
-  if (have_cov) then
-    call read_map('period_map_coverage.dat', 4, 4, cov, .true.)
-    wcov = merge(1.0/sigma_c, 0.0, cov > 0.0)
-    do q = 6, 66, 60
-      write (q, '(a,i8,a,i8)') ' period_map_coverage.dat: weight 1/sigma_c on the (cell, period) pairs with DWS > 0:', &
-        count(cov > 0.0), ' of', kmax*ncell
-    end do
-  else
-    wcov = 1.0/sigma_c
-    do q = 6, 66, 60
-      write (q, '(a)') ' period_map_coverage.dat is absent: weight 1/sigma_c on every cell and period'
-    end do
-  end if
+  allocate (cmap(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
+  call read_map('period_phaseV_map.dat', p, 4, 4, cmap, .true.)
+  call coverage_weights(p, sigma_c, wcov)
 
   ! ---- the prior box per cell and knot -------------------------------------------------------------------------------------------
   allocate (vmin(nx - 2, ny - 2, nlay), vmax(nx - 2, ny - 2, nlay))
@@ -201,31 +181,8 @@ program SurfDepthMC_amd
   end do
 
   ! ---- output files --------------------------------------------------------------------------------------------------------------
-  open (11, file='MOD_mc')
-  do k = 1, nz
-    write (11, '(f7.1)', advance='no') depz(k)
-  end do
-  do k = 1, nz
-    do j = 1, ny
-      do i = 1, nx
-        if (i == 1) then
-          write (11, '(/f8.4)', advance='no') vmc(i, j, k)
-        else
-          write (11, '(f8.4)', advance='no') vmc(i, j, k)
-        end if
-      end do
-    end do
-  end do
-  close (11)
-  open (63, file='DSurfTomo_mc.inv')
-  do k = 1, nz
-    do j = 1, ny
-      do i = 1, nx
-        write (63, '(5f8.4)') gozd + (j - 2)*dvzd, goxd - (i - 2)*dvxd, depz(k), vmc(i, j, k)
-      end do
-    end do
-  end do
-  close (63)
+  call write_mod('MOD_mc', depz, vmc)
+  call write_vs_model('DSurfTomo_mc.inv', p, depz, vmc)
   open (64, file='Vs_posterior_mc.dat')
   do k = 1, nlay
     do j = 1, ny - 2
@@ -236,15 +193,7 @@ program SurfDepthMC_amd
     end do
   end do
   close (64)
-  open (77, file='period_phaseV_mc.dat')
-  do t = 1, kmax
-    do j = 1, ny - 2
-      do i = 1, nx - 2
-        write (77, '(5f10.4)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, tRc(t), pvm(j*nx + i + 1, t)
-      end do
-    end do
-  end do
-  close (77)
+  call write_phase_map('period_phaseV_mc.dat', p, inner_cells(nx, ny, kmax, pvm))
   open (78, file='cell_mc.dat')
   do j = 1, ny - 2
     do i = 1, nx - 2
@@ -258,30 +207,6 @@ program SurfDepthMC_amd
   call dazim_finalize()
 
 contains
-
-  include 'read_map.inc'
-
-  subroutine bad_arg(n)
-    integer, intent(in) :: n
-    write (*, '(a,i2,a,a)') ' ERROR: argument', n, ' is not a number: ', trim(arg)
-    error stop 'bad argument'
-  end subroutine
-
-  subroutine int_arg(n, v)
-    integer, intent(in) :: n
-    integer, intent(inout) :: v
-    call get_command_argument(n, arg)
-    read (arg, *, iostat=ios) v
-    if (ios /= 0) call bad_arg(n)
-  end subroutine
-
-  subroutine real_arg(n, v)
-    integer, intent(in) :: n
-    real, intent(inout) :: v
-    call get_command_argument(n, arg)
-    read (arg, *, iostat=ios) v
-    if (ios /= 0) call bad_arg(n)
-  end subroutine
 
   ! RMS over the periods with a weight of cmap - c at inner cell (i1, j1); 0 for a cell without data
   real function cell_rms(pv, i1, j1)

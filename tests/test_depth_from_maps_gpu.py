@@ -166,3 +166,14 @@ def test_bad_inputs_stop_with_a_message(tmp_path):
     rc, text = run_failing(tmp_path / "periods", bad)
     assert rc != 0 and "periods differ from para.in's" in text, text
     assert not (tmp_path / "periods" / "MOD_2step").exists()
+
+
+def test_a_word_for_an_optional_argument_is_refused(tmp_path):
+    """the checked parser of host/dazim_io.f90: a message naming the argument and a non-zero status, before anything is read"""
+    build()
+    files = dict(inputs(maxiter=1, iso="T"), **true_maps())
+    for name, text in files.items():
+        (tmp_path / name).write_text(text)
+    out = subprocess.run([DEPTH, "para.in", "2.0", "2.0", "small"], cwd=tmp_path, timeout=300, capture_output=True, text=True)
+    assert out.returncode != 0 and " ERROR: argument 4 is not a number: small" in out.stdout.splitlines(), out.stdout + out.stderr
+    assert not (tmp_path / "MOD_2step").exists()

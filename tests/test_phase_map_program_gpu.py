@@ -134,3 +134,13 @@ def test_both_programs_in_one_directory_leave_the_3d_files_alone(tmp_path):
         a = (tmp_path / "alone" / n).read_text(errors="replace")
         b = (tmp_path / "both" / n).read_text(errors="replace")
         assert strip(a) == strip(b), n
+
+
+def test_a_word_for_an_optional_argument_is_refused(tmp_path):
+    """the checked parser of host/dazim_io.f90: a message naming the argument and a non-zero status, before the data file is read"""
+    build()
+    for name, text in inputs(maxiter=1).items():
+        (tmp_path / name).write_text(text)
+    out = subprocess.run([MAPS, "para.in", "smooth"], cwd=tmp_path, timeout=300, capture_output=True, text=True)
+    assert out.returncode != 0 and " ERROR: argument 2 is not a number: smooth" in out.stdout.splitlines(), out.stdout + out.stderr
+    assert not (tmp_path / "period_phaseV_map.dat").exists()
