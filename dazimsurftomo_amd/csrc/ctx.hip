@@ -82,16 +82,14 @@ int dz_scratch(dazim_ctx *ctx, const char *name, size_t bytes, void **out) {
 int dz_pinned(dazim_ctx *ctx, const char *name, size_t bytes, void **out) {
   auto &s = ctx->pinned[name];
   if (s.second < bytes) {
-    const bool pin = !(ctx->opts.count("ctx.pinned") && !ctx->opts["ctx.pinned"]);
     if (s.first) {
       DZ_HIP(hipStreamSynchronize(ctx->stream));
-      if (hipHostFree(s.first) != hipSuccess) { (void)hipGetLastError(); free(s.first); }
+      DZ_HIP(hipHostFree(s.first));
     }
     s.first = nullptr;
     s.second = 0;
     const size_t want = bytes + bytes / 4 + 64;
-    if (pin) DZ_HIP(hipHostMalloc(&s.first, want));
-    else if (!(s.first = malloc(want))) return dz_fail(ctx, -3, "out of host memory");
+    DZ_HIP(hipHostMalloc(&s.first, want));
     s.second = want;
   }
   *out = s.first;
@@ -266,7 +264,7 @@ int dazim_create(dazim_ctx **out, int device) {
   if (device < 0 || device >= n) return DAZIM_E_BAD_ARG;
   dazim_ctx *ctx = new dazim_ctx;
   ctx->device = device;
-  // Experiments only (tools/exp_cumask.sh): DAZIM_CU_MASK=<hex words, least significant first, comma separated> restricts the
+  // Experiments only: DAZIM_CU_MASK=<hex words, least significant first, comma separated> restricts the
   // library's stream to a subset of the compute units -- "does a kernel's throughput follow the CUs it may use or the memory
   // system behind them?"
   bool masked = false;
@@ -325,7 +323,7 @@ void dazim_destroy(dazim_ctx *ctx) {
   for (auto &kv : ctx->scratch)
     if (kv.second.first) (void)hipFree(kv.second.first);
   for (auto &kv : ctx->pinned)
-    if (kv.second.first && hipHostFree(kv.second.first) != hipSuccess) { (void)hipGetLastError(); free(kv.second.first); }
+    if (kv.second.first) (void)hipHostFree(kv.second.first);
   (void)hipEventDestroy(ctx->ev0);
   (void)hipEventDestroy(ctx->ev1);
   if (ctx->stream3) {

@@ -146,7 +146,7 @@ __device__ __forceinline__ double dz_row_kernel(float v, double svs, double svp,
 
 // named scratch buffer of at least `bytes` bytes
 int dz_scratch(dazim_ctx *ctx, const char *name, size_t bytes, void **out);
-// named PINNED host buffer of at least `bytes` bytes (option ctx.pinned = 0: plain malloc'ed memory, the behaviour before round 6)
+// named PINNED host buffer of at least `bytes` bytes (measured neutral against pageable memory, profiles/r6_pinned_ab.md)
 int dz_pinned(dazim_ctx *ctx, const char *name, size_t bytes, void **out);
 
 size_t dz_trim_caches(dazim_ctx *ctx);                                // free all idle cached blocks; bytes released

@@ -1037,7 +1037,7 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
   // the G rows) another one on the auxiliary stream, and the call returns when the first is done.  dazim_rays_build_G*, the next
   // dazim_dispersion_kernels, dazim_sync and dazim_free join the auxiliary stream; anybody else who reads sen_* (or overwrites
   // vel) before one of these calls dazim_sync first.  What it buys: the dispersion kernel's last, partly filled round of
-  // workgroups (S-256: 64 of 832) and the eikonal kernel share the chip (tools/exp_overlap.py: 293 against 306 ms), and on
+  // workgroups (S-256: 64 of 832) and the eikonal kernel share the chip (measured: 293 against 306 ms), and on
   // small batches (S-128) the two kernels, neither of which fills it, run side by side.
   bool async = kernels && ctx->opts.count("disp.async") && ctx->opts["disp.async"] && !vel.staged && !svs.staged &&
                !svp.staged && !srho.staged && !(ctx->opts.count("disp.pchunk") && ctx->opts["disp.pchunk"] > 0 && ctx->opts["disp.pchunk"] < kmax);
@@ -1083,8 +1083,6 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
     const void *kf = rden == 1 ? (const void *)disp_kernel<1> : (rden == 2 ? (const void *)disp_kernel<2> : (const void *)disp_kernel<0>);
     int occ = 3;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kf, DT, dyn_lds) != hipSuccess || occ < 1) occ = 1;
-    // option disp.occ: at most that many workgroups per CU (room for a kernel of another stream on the same CUs)
-    if (ctx->opts.count("disp.occ") && ctx->opts["disp.occ"] >= 1 && ctx->opts["disp.occ"] < occ) occ = ctx->opts["disp.occ"];
     long nwg = (long)ctx->num_cu * occ;
     if (nwg > ((long)ntask + DT / TW - 1) / (DT / TW)) nwg = ((long)ntask + DT / TW - 1) / (DT / TW);
     // first-period fast-forward (disp_bracket_kernel); off with option disp.ffwd = 0 and when the periods are handed from task to task

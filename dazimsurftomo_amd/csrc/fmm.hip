@@ -241,11 +241,7 @@ struct Heap {
   static constexpr int TOT = HYB ? (CAP << NH) : CAP;   // slots the fast kernel can hold before the field is handed to the spill kernel
   // interior-root table of march(): 288 bytes of LDS, which cost no kernel form a workgroup per CU (LDS comes in 1 280-byte granules:
   // 12 288 + 288 B still give twelve, 16 384 + 288 nine like 16 384 alone -- profiles/r5_lds_granule.md)
-#ifdef DZ_FMM_NOTAB   // experiment: the coordinate path for every root
-  static constexpr bool TAB = false;
-#else
   static constexpr bool TAB = !SPILL && GPL == 16;
-#endif
   unsigned long long *popcnt;   // nodes accepted by the launch (nullable)
   short *tab;   // [144] the wavefront's table (16-bit: the S-256 form must stay within 12 800 bytes of LDS -- allocation comes in
                 // 1 280-byte granules on this chip, and with 12 864 bytes a CU held eleven workgroups instead of twelve, -6 %)
@@ -625,9 +621,7 @@ struct Heap {
 //     second order: c = -(u*u)*(s*s) with u = 2 ri dnx (tref = 4tj - tj2) or 2 risti dnz (tref = 4tk - tk2), tdiv = 3
 //     first order : c = -(s*s)*(ri*ri)*(dnx*dnx), tref = tj, or -(s*s)*(risti*risti)*(dnz*dnz), tref = tk
 // then the common tail tdsh = (-b + sqrt(max(b*b - 4*a*c, 0))) / (2*a), (tref + tdsh) / tdiv.  Bit-identical fields
-// (tests/test_fmm_gpu.py against the oracle on every grid size; option-free, so the old form is kept below for reference only
-// under DZ_FMM_QUADRANT_BRANCHES).
-#ifndef DZ_FMM_QUADRANT_BRANCHES
+// (tests/test_fmm_gpu.py against the oracle on every grid size).
 // Exact fp32 division and square root without the range handling the compiler wraps around them (round 4).  x / y is compiled as
 // v_div_scale x 2, v_rcp, the Newton / residual steps below, v_div_fmas, v_div_fixup: the two scale instructions and the fixup only
 // act on operands near the ends of the exponent range (|y| or |x / y| below 2^-126 or above 2^126, |x| < 2^-103), zeros, infinities
@@ -712,11 +706,7 @@ __device__ __forceinline__ float quadrant_time(float slown, float risti, float d
   const float t = third ? t3 : tsum;
   return (aj || ak) ? t : INFINITY;
 }
-#endif
 
-#ifdef DZ_FMM_LAZYSTAT
-__device__ unsigned long long g_lazy_stat[4];
-#endif
 #ifdef DZ_FMM_PROF   // experiment-only build: per-phase shader-clock totals of the marching loop
 __device__ unsigned long long g_fmm_prof[8];
 #define PROF_DECL unsigned long long pt_ = __builtin_amdgcn_s_memtime(), pa_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
@@ -736,7 +726,7 @@ __device__ unsigned long long g_fmm_prof[8];
 #endif
 
 // (Round 3 measured cache-policy hints on the node accesses of the marching loop -- non-temporal loads -17 %, stores -32 %,
-// both -51 %, tools/exp_fmm_nt.sh on the 8-byte records of that time: L2 / Infinity Cache residency carries them.)
+// both -51 %, on the 8-byte records of that time, docs/history_r1_r3.md: L2 / Infinity Cache residency carries them.)
 
 // ---- one marching run (travel, inv/CalSurfG.f90:356-456), executed by a 16-lane group --------
 // REFINED: urg=1 early-exit rule on the edges flagged in `ex` (bit0 x=1, bit1 x=nnx, bit2 z=1,
@@ -993,10 +983,6 @@ __device__ __forceinline__ bool march(Heap<CAP, SPILL, NT, HYB, GPL> &H, const f
       if constexpr (GPL == 16) found = imin_xor2(found);
       const lmask dropm = wballot((int)uself == fin_node) & fslotm;
       const bool isdrop = lanes(dropm);
-#ifdef DZ_FMM_LAZYSTAT   // experiment build: how often the first four ancestors do not hold the entry (lanes), and pops
-      if (q == 0 && band) atomicAdd(&g_lazy_stat[found == 64 && !isdrop ? 1 : 0], 1ull);
-      if (q == 0 && band && isdrop) atomicAdd(&g_lazy_stat[2], 1ull);
-#endif
       if (__builtin_expect((bandm & wballot(found == 64) & ~dropm) != 0, 0)) {   // (wave-uniform, rare) the higher ancestors
 #pragma unroll
         for (int t = 1; t < LT; t++) {
@@ -1067,7 +1053,7 @@ __device__ __forceinline__ bool march(Heap<CAP, SPILL, NT, HYB, GPL> &H, const f
       n0 = !room ? 0 : (riseb ? (__builtin_ctz(riseb) / NBL) : 4);
       // One-level rise in place (round 3).  41 % of the wave-pops have a rising entry in some group, and in 92 % of those every
       // such group has exactly ONE riser that stops after one level and whose move touches no slot another neighbour of the pop
-      // reads or writes (measured, DZ_FMM_PROF2): then the sequential addtree/updtree calls still reduce to independent
+      // reads or writes (measured in round 3, docs/history_r1_r3.md): then the sequential addtree/updtree calls still reduce to independent
       // writes -- the riser swaps with its parent, everybody else writes as above -- instead of up to four parallel rounds.
       // Conditions, per group (r = the riser, at slot c_r with parent slot p_r and grandparent slot g_r):
       //   * one riser, and its key is not smaller than the key at g_r (it stops at p_r);
@@ -1122,31 +1108,6 @@ __device__ __forceinline__ bool march(Heap<CAP, SPILL, NT, HYB, GPL> &H, const f
 #ifdef DZ_FMM_PROF
     if (wballot(!fast)) pa_[3] += 1000000;   // "fix" slot doubles as a counter of slow-path iterations (x1e6)
     pa_[7] += 1000000;                        // iterations (x1e6) on top of the loop-top ticks
-#endif
-#ifdef DZ_FMM_PROF2   // experiment: how many slow-path pops have, in every group that needs the rounds, exactly ONE rising entry (any
-    // number of levels) whose path no other neighbour of the pop touches?  (counted x1e6 on the "setup+loads" slot; slow pops on "fix")
-    if (!SPILL && wballot(!fast)) {
-      const bool owner = q == 0;
-      const bool act = stfix != 0, isnew = stfix < 0;
-      const unsigned newb = (unsigned)(wballot(owner && isnew) >> gbase) & 0x1111u;
-      const int ntr0 = H.ntr - __popc(newb & ((1u << (4 * n0)) - 1u));            // (H.ntr was advanced for the neighbours < n0)
-      const int c = isnew ? ntr0 + 1 + __popc(newb & ((1u << gl) - 1u)) : stfix;
-      const int pc = c >> 1;
-      const float pk = H.keys[(act && pc < CAP) ? pc : 0];
-      const bool rise = owner && act && c > 1 && trav < pk;
-      const unsigned rb = (unsigned)(wballot(rise) >> gbase) & 0xffffu;
-      const int rl = rb ? __builtin_ctz(rb) : 0;
-      const int cr = __shfl(c, gbase + rl);
-      const bool one = __popc(rb) == 1;
-      auto anc = [&](int x) { if (x < 1 || x > cr) return false; const int d = __clz(x) - __clz(cr); return (cr >> d) == x; };
-      const bool clash = owner && act && gl != rl && (anc(c) || anc(pc));
-      const unsigned cl = (unsigned)(wballot(clash) >> gbase) & 0xffffu;
-      const bool room = ntr0 + __popc(newb) < Heap<CAP, SPILL, NT, HYB, GPL>::TOT;
-      const bool ok = fast || (room && one && cl == 0 && (!HYB || cr < CAP));
-      if (wballot(!ok) == 0) pa_[0] += 1000000;
-      if (wballot(!fast && !room) != 0) pa_[1] += 1000000;       // pops with a group out of room ("popdown" slot)
-      if (wballot(!fast && room && !one) != 0) pa_[2] += 1000000; // ... with several risers in a group ("loadwait" slot)
-    }
 #endif
     if (!fast) {
       nbs[0] = own_i<GPL, 0>(stfix); nbs[1] = own_i<GPL, 1>(stfix);
@@ -1222,14 +1183,6 @@ constexpr int fmm_waves_per_simd() {
   const int w = (163840 / ((lds + 1279) / 1280 * 1280)) / 4;
   return w < 1 ? 1 : (w > 3 ? 3 : w);   // (never fewer than 168 registers: the loop needs ~150-170)
 }
-#ifdef DZ_FMM_WPE   // experiment: register budget for DZ_FMM_WPE wavefronts per SIMD
-#define FMM_WPE_ATTR __attribute__((amdgpu_waves_per_eu(DZ_FMM_WPE, DZ_FMM_WPE)))
-#else
-#define FMM_WPE_ATTR __attribute__((amdgpu_waves_per_eu(fmm_waves_per_simd<CAP, NT, GPL, Heap<CAP, SPILL, NT, HYB, GPL>::TAB>())))
-#endif
-#ifdef DZ_TS_WAITSTAT   // experiment build: clocks the workgroups spend waiting for the previous stage of their task
-__device__ unsigned long long g_ts_wait[2];
-#endif
 // The kernel reads its arguments through a pointer to the kernarg segment that the compiler cannot see through (round 5).  Taken
 // as a by-value struct, the compiler loads all of FmmArgs into ~60 scalar registers at entry and keeps them alive across the
 // marching loop; with the loop's own lane masks that is more than the 102 a wavefront has, and the spill code reloaded a whole
@@ -1242,40 +1195,24 @@ __device__ __forceinline__ FmmArgP arg_launder(FmmArgP p) {
   asm volatile("v_mov_b32 %0, 0" : "=v"(z));
   return (FmmArgP)((const __attribute__((address_space(4))) char *)p + __builtin_amdgcn_readfirstlane(z));
 }
-#ifdef DZ_FMM_ARGS_BYVALUE   // experiment: the round-4 form
-#define FMM_ARGS_DECL(A_)
-#define FMM_ARGS_FRESH
-#else
-#define FMM_ARGS_DECL(A_) FmmArgP Ap = arg_launder((FmmArgP)__builtin_amdgcn_kernarg_segment_ptr())
 #define FMM_ARGS_FRESH Ap = arg_launder(Ap)
-#endif
 template <int CAP, bool SPILL, class NT, bool HYB, int GPL = 16>
-__global__ __launch_bounds__(64) FMM_WPE_ATTR void fmm_kernel(FmmArgs A_) {
-#ifdef DZ_FMM_ARGS_BYVALUE
-  const FmmArgs &A = A_;
-#else
-  FMM_ARGS_DECL(A_);
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fmm_waves_per_simd<CAP, NT, GPL, Heap<CAP, SPILL, NT, HYB, GPL>::TAB>())))
+void fmm_kernel(FmmArgs A_) {
+  FmmArgP Ap = arg_launder((FmmArgP)__builtin_amdgcn_kernarg_segment_ptr());
 #define A (*Ap)
-#endif
   constexpr int GP = GPL, FPW = 64 / GPL;   // lanes per field, fields per wavefront (these shadow the 16-lane constants above)
   // The four fields of a wavefront walk their heaps in step: the lanes of groups 0 and 1 (one 32-lane half of every LDS access:
   // MI355X_MICROARCH.md, LDS) read the SAME slot of two rows, and rows CAP entries apart start in the same bank -- a two-way
-  // conflict on every access of the sift-down (SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS = 0.94).  -DDZ_FMM_SKEW lays the rows out
-  // 0, 1, 3, 2 with a skew of half the banks in front of rows 1 and 2 (what is left of the 1 280-byte LDS granule: 12 768 of
-  // 12 800 B at S-256, still twelve workgroups per CU): the ratio drops to 0.48 and NOTHING else moves -- SQ_WAIT_ANY 124.1 ->
-  // 125.1 G of 315 G wave cycles, 80.9 k fields/s without against 80.4 k with in four same-box pairs (profiles/
-  // r6_fmm_lds_conflicts.md).  The two extra LDS cycles of a conflicting access hide behind the ~100-cycle round trip they belong
-  // to; the conflicts are not on the pop's critical chain.  Default: the plain layout.
-#ifndef DZ_FMM_SKEW
-  constexpr int KSKEW = 0, NSKEW = 0;
-#else
-  constexpr int KSKEW = FPW == 4 ? 16 : 0, NSKEW = FPW == 4 ? 16 : 0;   // entries (16-bit node ids: 8 banks)
-#endif
-  __shared__ __attribute__((aligned(16))) float s_keys_all[FPW * CAP + 2 * KSKEW];
-  __shared__ __attribute__((aligned(16))) NT s_nodes_all[FPW * CAP + 2 * NSKEW];
+  // conflict on every access of the sift-down (SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS = 0.94).  Skewing rows 1 and 2 by half
+  // the banks was measured: the ratio drops to 0.48 and NOTHING else moves (profiles/r6_fmm_lds_conflicts.md) -- the two extra
+  // LDS cycles of a conflicting access hide behind the ~100-cycle round trip they belong to; the conflicts are not on the pop's
+  // critical chain.  So the rows are laid out plainly (in the order 0, 1, 3, 2).
+  __shared__ __attribute__((aligned(16))) float s_keys_all[FPW * CAP];
+  __shared__ __attribute__((aligned(16))) NT s_nodes_all[FPW * CAP];
   auto row_of = [](int g_) { return FPW == 4 ? (g_ == 0 ? 0 : (g_ == 1 ? 1 : (g_ == 3 ? 2 : 3))) : g_; };   // position of group g_'s row
-  auto key_row = [&](int g_) { const int r = row_of(g_); return s_keys_all + r * CAP + (r >= 1 ? KSKEW : 0) + (r >= 3 ? KSKEW : 0); };
-  auto node_row = [&](int g_) { const int r = row_of(g_); return s_nodes_all + r * CAP + (r >= 1 ? NSKEW : 0) + (r >= 3 ? NSKEW : 0); };
+  auto key_row = [&](int g_) { return s_keys_all + row_of(g_) * CAP; };
+  auto node_row = [&](int g_) { return s_nodes_all + row_of(g_) * CAP; };
   // the queue position is handed to the wavefront through slot 0 of the first field's keys (the dummy slot of the marching
   // loop, idle between fields): the kernel's LDS is exactly the heaps, so five 32 KB workgroups of the hybrid heap fill 160 KB
   __shared__ short s_tab[Heap<CAP, SPILL, NT, HYB, GPL>::TAB ? 144 : 2];
@@ -1365,14 +1302,7 @@ __global__ __launch_bounds__(64) FMM_WPE_ATTR void fmm_kernel(FmmArgs A_) {
           s_stage = stg;
           if (stg > 0) {   // its predecessor (same batch, previous stage) must have handed its state over
             const unsigned *flag = A.ts_flag + found / fpw;
-#ifdef DZ_TS_WAITSTAT
-            const unsigned long long w0_ = __builtin_amdgcn_s_memtime();
-#endif
             while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < stg) __builtin_amdgcn_s_sleep(20);
-#ifdef DZ_TS_WAITSTAT
-            atomicAdd(&g_ts_wait[0], __builtin_amdgcn_s_memtime() - w0_);
-            atomicAdd(&g_ts_wait[1], 1ull);
-#endif
           }
           break;
         }
@@ -1384,11 +1314,7 @@ __global__ __launch_bounds__(64) FMM_WPE_ATTR void fmm_kernel(FmmArgs A_) {
     const unsigned fbase = s_base;
     if (fbase == 0xffffffffu) break;
     const int stage = ts ? (int)s_stage : 0;
-#ifdef DZ_TS_LIGHT_ACQ   // measurement only (not coherent across XCDs): what the L2 invalidate of the acquire costs
-    if (stage > 0) asm volatile("buffer_inv sc0" ::: "memory");
-#else
     if (stage > 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // acquire side for the lanes that did not spin
-#endif
     const int q = (int)fbase + grp;
     // node words of the coarse grid and the heap's HBM level: per resident slot, or per field when stages change hands
     unsigned *rec_c = A.rec_c + (ts ? (size_t)q : slot) * nrec_c;
@@ -1645,11 +1571,7 @@ __global__ __launch_bounds__(64) FMM_WPE_ATTR void fmm_kernel(FmmArgs A_) {
       }
     }
     if (ts) {   // hand the batch to its next stage: everything this task stored, then the flag
-#ifdef DZ_TS_LIGHT_REL   // measurement only (not coherent across XCDs): what the L2 write-back of the release costs
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
       __syncthreads();
       if (lane == 0) __hip_atomic_store(A.ts_flag + fbase / fpw, (unsigned)stage + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1680,9 +1602,9 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
   if (ctx->opts.count("fmm.wg_per_cu") && ctx->opts["fmm.wg_per_cu"] > 0 && ctx->opts["fmm.wg_per_cu"] < per_cu) per_cu = ctx->opts["fmm.wg_per_cu"];
   int nwg = ctx->num_cu * per_cu;
   // Small batches: a launch lasts at least as long as ONE field takes alone, and with fewer wavefronts than SIMDs most of the
-  // chip idles; fewer fields per wavefront then put every field on a SIMD of its own sooner.  Option fmm.fpw forces 1, 2 or 4.
+  // chip idles.  Fewer fields per wavefront put every field on a SIMD of its own sooner but were measured and buy nothing (S-128:
+  // 49.4 / 46.8 / 51.7 ms with four / two / one, docs/history_r1_r3.md): the launch is one field's latency, not idle hardware.
   A.fpw = FPW;
-  if (ctx->opts.count("fmm.fpw") && (ctx->opts["fmm.fpw"] == 1 || ctx->opts["fmm.fpw"] == 2 || ctx->opts["fmm.fpw"] == 4) && ctx->opts["fmm.fpw"] < FPW) A.fpw = ctx->opts["fmm.fpw"];
   ctx->ksec["fmm.lanes_per_field"] = GPL;
   ctx->ksec["fmm.fpw"] = A.fpw;
   // Issue priority (round 4).  A batch that leaves most of the chip empty lasts as long as one field's serial chain, and every cycle
@@ -1690,10 +1612,8 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
   // the auxiliary stream (disp.async) -- lengthens that chain: s_setprio 3 gives them the slot first.  S-128: eikonal launch 52.0 ->
   // 45.0 ms (= alone on the chip), step 64.0 -> 56.9 ms; test4_Yunnan program: assembly 1.015 -> 0.875 s.  A batch that fills the chip
   // gains nothing among its own wavefronts and only starves the copies the ray kernel then waits for (S-256: step 368 -> 380 ms), so
-  // the rule is: at most half of the resident workgroups.  Option fmm.prio = 1 / 2 forces it on / off.
+  // the rule is: at most half of the resident workgroups.
   A.prio = (nfield + A.fpw - 1) / A.fpw <= nwg / 2 ? 1 : 0;
-  if (ctx->opts.count("fmm.prio") && ctx->opts["fmm.prio"] == 1) A.prio = 1;
-  if (ctx->opts.count("fmm.prio") && ctx->opts["fmm.prio"] == 2) A.prio = 0;
   ctx->ksec["fmm.prio"] = A.prio;
   if (nwg > (nfield + A.fpw - 1) / A.fpw) nwg = (nfield + A.fpw - 1) / A.fpw;
   const int nslot = nwg * FPW;
@@ -1701,7 +1621,7 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
   A.ovfcap = HYB ? Heap<CAP, false, NT, HYB, GPL>::TOT - CAP : 0;   // the fast kernel: only the HYB heap has HBM levels
   // Time slicing (see fmm_kernel): on when the batch does not fit the resident slots (more than one round) and the per-field node
   // words fit comfortably; option fmm.ts = 1 / 2 forces it on / off (0: this rule), fmm.ts_stages sets the number of coarse stages.
-  // Few stages are best (not because of the hand-over fences: tools/exp_ts_fences.sh; with many short stages handed out
+  // Few stages are best (not because of the hand-over fences, measured; with many short stages handed out
   // stage-major the fields march in step again and the mixture of phases on a CU is lost): S-256's 16 000
   // fields on the 512-slot hybrid heap take 0.240 / 0.253 / 0.248 / 0.249 / 0.252 s with 2 / 3 / 4 / 8 / 12 coarse stages
   // (0.288 s unsliced on the 768-slot heap, same box), the 768-slot heap 0.292 / 0.264 / 0.262 s with 2 / 4 / 8-12; S-512's
@@ -1721,8 +1641,7 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
   A.ts_pops = (int)((nn + nseg - 1) / nseg);
   // (stages of unequal length -- odd batches longer, even ones shorter, to put the batches out of step -- lose badly: +19 % of
   // the time at +-20 %, +44 % at +-40 %: the stage-major hand-out relies on equal tasks, a workgroup that takes a task whose
-  // predecessor is still running waits; with equal stages that wait is 0.15 % of the workgroups' time at 2 stages, 2 % at 8:
-  // tools/exp_ts_wait.sh)
+  // predecessor is still running waits; with equal stages that wait is 0.15 % of the workgroups' time at 2 stages, 2 % at 8, measured)
   ctx->ksec["fmm.ts_stages"] = ts ? (double)nseg : 0.0;
   // owners of node words / HBM heap levels: fields or resident slots.  + 8: the idle lane groups of the last wavefront of a batch
   // (owner index up to nfield + fields per wavefront - 1, at most 8 fields per wavefront) address their own, unused, state
@@ -1897,24 +1816,6 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
     DZ_HIP(hipStreamSynchronize(ctx->stream));
     ctx->ksec["fmm.field_pops"] = (double)hp;   // nodes accepted by this call (all fields, refined + coarse marches, incl. spill reruns)
   }
-#ifdef DZ_TS_WAITSTAT
-  {
-    unsigned long long h[2];
-    DZ_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ts_wait), sizeof h));
-    fprintf(stderr, "ts wait: %llu clocks (100 MHz) in %llu waits of later-stage tasks; %d workgroups\n", h[0], h[1], nwg);
-    unsigned long long z[2] = {0, 0};
-    DZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_ts_wait), z, sizeof z));
-  }
-#endif
-#ifdef DZ_FMM_LAZYSTAT
-  {
-    unsigned long long h[4];
-    DZ_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_lazy_stat), sizeof h));
-    fprintf(stderr, "lazy look-ups: %llu within three levels, %llu higher (second round), %llu the dropped entry\n", h[0], h[1], h[2]);
-    unsigned long long z[4] = {0};
-    DZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_lazy_stat), z, sizeof z));
-  }
-#endif
 #ifdef DZ_FMM_PROF
   {
     unsigned long long h[8];

@@ -232,10 +232,8 @@ __global__ void k_ray_keys(long nray, const int *__restrict__ field, const float
 
 // lanes per ray: 8 in the count pass, which traces every ray (measured: 16 lanes 94 ms, 8 lanes 73 ms, 4 lanes 84 ms on the S-256
 // batch); 16 in the emit pass, which only walks the saved cell lists (lane-parallel work: 8.2 ms with 16 lanes, 12.5 with 8)
-#ifndef DZ_GP_COUNT
-#define DZ_GP_COUNT 8   // (experiment switch, tools/exp_rays_ab.sh: 4 and 16 lanes per ray are both 17 % slower at S-256)
-#endif
-constexpr int GP_COUNT = DZ_GP_COUNT, GP_EMIT = 16;
+constexpr int GP_COUNT = 8, GP_EMIT = 16;   // (count pass, whole step: 4 and 16 lanes per ray are both 17 % slower at S-256)
+constexpr int RAYS_MINW = 4;   // wavefronts per SIMD the isotropic forms of rays_kernel are compiled for (the azimuthal ones: 2)
 constexpr int RPW_MAX = 64 / GP_COUNT;   // rays per wavefront (most of the two passes: sizes the scratch slots)
 __device__ __forceinline__ void cbar() { asm volatile("" ::: "memory"); }  // compiler-only barrier (same-wave ops are in order)
 
@@ -247,14 +245,10 @@ __device__ __forceinline__ void cbar() { asm volatile("" ::: "memory"); }  // co
 // MAP: the rows of the per-period map inversion (dazim_rays_build_G_maps) -- the Frechet values fdm (, fdmc, fdms) themselves,
 // one column block per period: what the 3-D rows are with unit depth kernels and nz = 2, the period folded into the column.
 template <bool EMIT, bool AZIM, bool TILED, bool MAP>
-#ifndef DZ_RAYS_MINW
-#define DZ_RAYS_MINW 4
-#endif
-__global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayArgs A_) {
+__global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs A_) {
   // (arguments through an opaque pointer to the kernarg segment, like fmm_kernel: taken by value, the ~50 scalar registers of
   // RayArgs stay alive across the stepping loop and the spill code moved 93 of its 1 227 VALU instructions per step through
   // VGPR lanes -- v_readlane / v_writelane --, 17 more through scratch memory)
-#ifndef DZ_RAYS_ARGS_BYVALUE
   using ArgP = const __attribute__((address_space(4))) RayArgs *;
   auto launder = [](ArgP p) {
     int z;
@@ -264,10 +258,6 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
   ArgP Ap = launder((ArgP)__builtin_amdgcn_kernarg_segment_ptr());
 #define A (*Ap)
 #define RAYS_ARGS_FRESH Ap = launder(Ap)
-#else
-  const RayArgs &A = A_;
-#define RAYS_ARGS_FRESH
-#endif
   constexpr int GP = EMIT ? GP_EMIT : GP_COUNT;   // lanes per ray
   constexpr int RPW = 64 / GP;                    // rays per wavefront
   constexpr int LPR = 16 / GP;                    // cells of the 4x4 B-spline block per lane
@@ -562,11 +552,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
         float vel = vel_c, vi = vi_c, wi[LPR];            // this lane's vi(m), wi(l)
 #pragma unroll
         for (int q = 0; q < LPR; q++) wi[q] = wi_c[q];
-#ifdef DZ_RAYS_NOCARRY   // experiment: every step computes its starting point
-        if (true) {
-#else
         if (__builtin_expect(__ballot(!carry) != 0, 0)) {  // (first step, clipped points: rare -- and wave-uniform, so out of line)
-#endif
           drx = (x0 - gox) - (float)(ipxo - 1) * dnx;
           drz = (z0 - goz) - (float)(ipzo - 1) * dnz;
           vel = vel_at(g, veln, ipxo, ipzo, drx, drz, rdnx, rdnz);
@@ -730,11 +716,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : DZ_RAYS_MINW) void rays_kernel(RayAr
     // Frechet values are decoded and loaded ONCE into registers and the layers loop over them, where the general loop below decodes
     // the cell id and reloads its Frechet value for each of the nz - 1 layers.  Same entries in the same order.
     constexpr int RC = 8;   // (128 cells in the emit pass, where a ray of the S-256 batch has ~100; 64 in the count pass: sixteen per lane there cost the tracing loop registers, 38.1 -> 40.1 ms)
-#ifdef DZ_RAYS_NOROWCACHE
-    const bool rowcache = false;
-#else
     const bool rowcache = !lovf && ntot <= RC * GP && (MAP || A.skern != nullptr) && !A.dense;
-#endif
     if (rowcache) {
       int sidx[RC], cbase[RC], fidx[RC];
 #pragma unroll
@@ -889,10 +871,8 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   bool overlap = (bool)ctx->fmm_finish && tiled && ctx->fields.fdone && nray > 0;
   // (a pending gather of sharded dispersion tables would run on the third stream too -- dz_join_aux below --: fine with the file
   // transport, whose collectives are host-staged; an RCCL communicator is kept to ONE stream, the main one, so with RCCL the
-  // eikonal call is completed first.  Option comm.gather_stream3 = 1 lifts that.)
-  if (overlap && ctx->aux_epilogue && ctx->comm && ((DzComm *)ctx->comm)->nccl &&
-      !(ctx->opts.count("comm.gather_stream3") && ctx->opts["comm.gather_stream3"]))
-    overlap = false;
+  // eikonal call is completed first.)
+  if (overlap && ctx->aux_epilogue && ctx->comm && ((DzComm *)ctx->comm)->nccl) overlap = false;
   if (overlap)
     for (const void *q : {(const void *)vels_u, (const void *)scx_u, (const void *)scz_u, (const void *)period_u, (const void *)veln_u,
                           (const void *)ttnr_u, (const void *)nstsr_u, (const void *)boxes_u, (const void *)field_u, (const void *)rcx_u,
@@ -1154,8 +1134,7 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
       return over;
     };
     if (ctx->fields.hprog && ctx->fields.total_tasks > 0) {
-      unsigned slack = ctx->fields.nwg / 4 + 8 * 16;
-      if (ctx->opts.count("rays.start_slack") && ctx->opts["rays.start_slack"] > 0) slack = (unsigned)ctx->opts["rays.start_slack"];   // (tuning)
+      const unsigned slack = ctx->fields.nwg / 4 + 8 * 16;
       const unsigned total = ctx->fields.total_tasks;
       const unsigned want = total > slack ? total - slack : 0;
       for (;;) {
@@ -1188,7 +1167,7 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
       }
       long nwg_pass = nwg;
       A.max_quads = 0;
-      A.sweeps = collected ? 1 : (ctx->opts.count("rays.sweeps") && ctx->opts["rays.sweeps"] > 0 ? ctx->opts["rays.sweeps"] : 3);   // (measured: 1 -> 300-302 ms, 2-4 -> 297.6-299.6, 6 -> 301-302, 12 -> 305.6, 32 -> 319.6: every look costs)
+      A.sweeps = collected ? 1 : 3;   // (measured: 1 -> 300-302 ms, 2-4 -> 297.6-299.6, 6 -> 301-302, 12 -> 305.6, 32 -> 319.6: every look costs)
       if (collected) A.fdone = nullptr;
       DZ_HIP(hipMemsetAsync(A.qcount, 0, 32, ctx->stream));        // the count pass's task counters
       if ((rc = launch(false, A, nwg_pass))) return rc;

@@ -113,9 +113,6 @@ __global__ __launch_bounds__(64 * WPB) void spmv_rows(int64_t nrows, const int64
 // One workgroup of 16 wavefronts per CU, each wavefront a row at a time, two 16-byte loads of
 // values and of indices in flight per lane.
 constexpr int LWPB = 16;
-#ifndef DZ_LDSX_UNROLL4
-#define DZ_LDSX_UNROLL4 1
-#endif
 // four consecutive column indices with one load: int4 (16 bytes) or ushort4 (8 bytes)
 template <class IT> struct Idx4;
 template <> struct Idx4<int> { using type = int4; };
@@ -146,7 +143,6 @@ __global__ __launch_bounds__(64 * LWPB) void spmv_rows_ldsx(int64_t nrows, int64
     for (int64_t i = s + lane; i < s4; i += 64) acc += val[i] * xs[idx[i]];
     const int64_t e4 = s4 + ((e - s4) & ~(int64_t)3);
     int64_t i = s4 + 4 * lane;
-#if DZ_LDSX_UNROLL4
     for (; i + 768 < e4; i += 1024) {   // four groups in flight (16-bit indices leave 24 instead of 32 bytes per lane and group)
       using I4 = typename Idx4<IT>::type;
       float4 v[4];
@@ -164,7 +160,6 @@ __global__ __launch_bounds__(64 * LWPB) void spmv_rows_ldsx(int64_t nrows, int64
         acc += v[g].w * xs[c[g].w];
       }
     }
-#endif
     for (; i + 256 < e4; i += 512) {
       using I4 = typename Idx4<IT>::type;
       const float4 v0 = *reinterpret_cast<const float4 *>(val + i);
@@ -469,7 +464,6 @@ __global__ void k_reorth(int64_t n, float *v, const float *lv_prev, const double
 // The barrier: one counter per solve, never reset, target = (barriers so far) x blocks; release / acquire at agent scope
 // (MI355X_MICROARCH.md, inter-workgroup visibility).  All blocks must be resident at once: the host launches at most as many as the
 // occupancy query allows on the device and takes the chain below otherwise (or on a CU-masked stream).
-// Option lsmr.reorth_chain = 1: the chain; lsmr.reorth_blocks: at most that many workgroups.
 constexpr int RC_BLOCKS = 64, RC_THREADS = 1024, RC_EMAX = 16;
 template <int E>
 __global__ __launch_bounds__(RC_THREADS) void k_reorth_coop(int64_t n, float *__restrict__ v, const float *__restrict__ lv, int lim,
@@ -1147,8 +1141,7 @@ int launch_spmvT(dazim_ctx *ctx, const dazim_csr *A, const float *y, float ymax,
   // matrix is 20 877 ray rows of 2 548 entries and 73 440 regularisation rows of seven, 284 per segment on average, 637 in the ray rows)
   const bool split = !(ctx->opts.count("spmv.split") && !ctx->opts["spmv.split"]) && A->split_row < A->m;
   const int64_t nsplit = split ? A->split_row : A->m;
-  bool shortseg = (split ? A->long_avg : (double)A->nnz / (double)A->m) < 400.0 * A->ncb;   // measured: 16 lanes win at 141 and 296 entries per segment, 64 at 553
-  if (ctx->opts.count("spmv.gl16") && ctx->opts["spmv.gl16"] >= 0) shortseg = ctx->opts["spmv.gl16"] != 0;
+  const bool shortseg = (split ? A->long_avg : (double)A->nnz / (double)A->m) < 400.0 * A->ncb;   // measured: 16 lanes win at 141 and 296 entries per segment, 64 at 553
   ctx->ksec["spmvt.split_row"] = (double)nsplit;
   const dim3 sgrid(nchunk * A->ncb), sblock(64 * SCW);
 #define DZ_SCATTER(GL_, NG_, IT_, COLP_)                                                                                        \
@@ -1198,8 +1191,7 @@ int launch_spmvA(dazim_ctx *ctx, const dazim_csr *A, const float *x, float *out,
   const size_t lds = (size_t)A->cbw * 2 * 4;
   const bool split = !(ctx->opts.count("spmv.split") && !ctx->opts["spmv.split"]) && A->split_row < A->m;
   const int64_t nsplit = split ? A->split_row : A->m;
-  bool shortseg = (split ? A->long_avg : (double)A->nnz / (double)A->m) < 600.0 * npair;    // measured: 16 lanes win at 282 and 519 entries per segment
-  if (ctx->opts.count("spmv.gl16") && ctx->opts["spmv.gl16"] >= 0) shortseg = ctx->opts["spmv.gl16"] != 0;
+  const bool shortseg = (split ? A->long_avg : (double)A->nnz / (double)A->m) < 600.0 * npair;    // measured: 16 lanes win at 282 and 519 entries per segment
   ctx->ksec["spmv.split_row"] = (double)nsplit;
   const dim3 bgrid(nset * npair), bblock(64 * SCW);
 #define DZ_BLOCKED(GL_, NG_, IT_, COLP_)                                                                                        \
@@ -2080,7 +2072,6 @@ int dazim_lsmr_traced(dazim_ctx *ctx, const dazim_csr *A, const float *b_u, floa
       }
       const double *pa = part;
       int npa = gn_t;
-      const bool chain = ctx->opts.count("lsmr.reorth_chain") && ctx->opts["lsmr.reorth_chain"];
       // localVOrtho :733-748 in one launch (k_reorth_coop) when v fits the registers of RC_BLOCKS workgroups
       // as few workgroups as hold v with <= RC_EMAX elements per thread, eight where that is enough: a step's grid barrier is
       // atomics on one word across XCDs (whose L2s do not share it), and its cost grows with the arrivals -- test4_Yunnan's
@@ -2089,11 +2080,10 @@ int dazim_lsmr_traced(dazim_ctx *ctx, const dazim_csr *A, const float *b_u, floa
       if (rcb < 8) rcb = 8;
       if (rcb > (int)((n + RC_THREADS - 1) / RC_THREADS)) rcb = (int)((n + RC_THREADS - 1) / RC_THREADS);
       if (rcb > RC_BLOCKS) rcb = RC_BLOCKS;
-      if (ctx->opts.count("lsmr.reorth_blocks") && ctx->opts["lsmr.reorth_blocks"] > 0 && ctx->opts["lsmr.reorth_blocks"] < rcb) rcb = ctx->opts["lsmr.reorth_blocks"];
       const int64_t per_thread = (n + (int64_t)rcb * RC_THREADS - 1) / ((int64_t)rcb * RC_THREADS);
       // the grid barrier of k_reorth_coop needs every workgroup resident at once: bounded by what the occupancy query allows on this
       // device (coop_max, taken once per solve) -- never on a stream restricted to some CUs (DAZIM_CU_MASK), where that bound does not hold
-      if (localVecs > 0 && lim > 0 && per_thread <= RC_EMAX && !chain && rcb <= coop_max) {
+      if (localVecs > 0 && lim > 0 && per_thread <= RC_EMAX && rcb <= coop_max) {
         unsigned *bar = reinterpret_cast<unsigned *>(part2 + 2 * NPART);
         const unsigned base = reorth_barriers;
         reorth_barriers += (unsigned)lim * (unsigned)rcb;

@@ -279,7 +279,7 @@ def test_fmm_time_sliced_many_hand_overs(ctx):
     heaps, against the unsliced 768-slot kernel: every traveltime identical (compared on the device).  (The slot look-up of
     the lazy back-pointers must not take a stale LDS slot beyond the heap's end for an entry -- after a hand-over such slots hold
     another field's node ids, which can coincide with the neighbour looked for: before the bound on the look-up about one field
-    in 40 000 came out wrong, 7 runs of 18 in tools/stress_ts.sh.)"""
+    in 40 000 came out wrong, 7 runs of 18 of a repeated stage-count sweep.)"""
     import torch
     nx = ny = 54
     kmax, nsrc = 16, 1000

@@ -1,12 +1,14 @@
 #!/bin/bash
 # BASELINE config 5 (S-512, 8 ranks, strong scaling) at a quarter of its source count on ONE GPU: eight ranks over the file transport
 # against one rank on the same field list; tables and predicted times bit for bit, x to the LSMR bar.   bash tools/experiments/config5_rehearsal.sh [sources]
+# (a run that fails or outlasts its time limit ends the script: nothing is started on the GPU after it)
+set -euo pipefail
 src=${1:-2000}
 rm -f /tmp/c5_*.npz
-python bench.py --workload s512 --scaling strong --sources $src --steps 1 --warmup 0 --no-cpu --dump /tmp/c5_one 2>/dev/null | python -c "
+timeout -k 10 900 python bench.py --workload s512 --scaling strong --sources $src --steps 1 --warmup 0 --no-cpu --dump /tmp/c5_one | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('1 rank :', round(d['ms_per_step'],1), 'ms', round(d['value']), 'fields/s', d['config']['workload'][:90])"
-DAZIM_BENCH_REHEARSAL=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29671 bench.py --gpus 8 --workload s512 --scaling strong --sources $src --steps 1 --warmup 0 --no-cpu --dump /tmp/c5_many 2>/dev/null | python -c "
+DAZIM_BENCH_REHEARSAL=1 timeout -k 10 1800 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29671 bench.py --gpus 8 --workload s512 --scaling strong --sources $src --steps 1 --warmup 0 --no-cpu --dump /tmp/c5_many | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('8 ranks:', round(d['ms_per_step'],1), 'ms (one shared GPU)', round(d['value']), 'fields/s', d['lsmr']['driver'], d['lsmr']['collectives_per_iteration'], d['dispersion'][:60], 'overlap', d['rays_beside_eikonal_tail'])"
 python - <<'PY'

@@ -1,6 +1,7 @@
 """Experiment (round 4): would the ray kernel's count pass fit beside the eikonal kernel?  Two contexts, two host threads, S-256
 workload of bench.py: context A marches the batch with fmm.wg_per_cu = WPC (room left on every CU), context B traces the rays of a
-previously computed copy of the fields with rays.wg_per_cu = R, started DELAY ms after the eikonal launch."""
+previously computed copy of the fields with rays.wg_per_cu = R, started DELAY ms after the eikonal launch.
+One process, run under a time limit:   timeout -k 10 600 python tools/experiments/exp_overlap_rays.py"""
 import os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch

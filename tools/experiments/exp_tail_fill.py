@@ -1,6 +1,7 @@
 """Experiment (round 6, after round 4's exp_overlap_rays.py): does the ray kernel fill the TAIL of the eikonal launch?  Two contexts, two host threads, S-256
 workload of bench.py: context A marches the batch with fmm.wg_per_cu = WPC (room left on every CU), context B traces the rays of a
-previously computed copy of the fields with rays.wg_per_cu = R, started DELAY ms after the eikonal launch."""
+previously computed copy of the fields with rays.wg_per_cu = R, started DELAY ms after the eikonal launch.
+One process, run under a time limit:   timeout -k 10 600 python tools/experiments/exp_tail_fill.py"""
 import os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
