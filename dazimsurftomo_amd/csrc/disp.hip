@@ -7,10 +7,13 @@
 // reference's bracket + Neville root search as independent state machines that meet at the only
 // expensive step, the Dunkin compound-matrix secular function (dltar4), which all lanes evaluate
 // in lockstep (uniform trip count = number of layers).  Nothing per-lane is indexed dynamically:
-// the layer stack is rebuilt on the fly from the column's knots (LDS, broadcast reads) with the
-// lane's single perturbed knot patched in, and the Earth-flattening factors, which depend on the
+// the layer stack is rebuilt from the column's knots (LDS, broadcast reads) with the lane's single
+// perturbed knot patched in -- on the fly where the lanes of a wavefront hold different columns, once
+// per task into LDS tables where they hold the perturbed copies of a few columns (TableLayers) --
+// and the Earth-flattening factors, which depend on the
 // layer thicknesses only, come from a host table (same libm log/powf the CPU reference calls).
 // fp64 VALU + transcendental bound; no MFMA, negligible HBM traffic.
+#include <algorithm>
 #include <cmath>
 
 #include "dazim_internal.h"
@@ -65,6 +68,10 @@ struct DispArgs {
   // ... and pvRc by the launch of the columns' own curves (var0 = 0, one variant per column); null: disp_finalize
   double *pv;                 // [kmax][ncol]
   int *nfail;                 // periods without a root (counted where pv is written)
+  // shared layer stacks (disp_kernel<*, false, true>, see TableLayers)
+  int npatch;                 // rows of a lane's patch table: the most layers one knot touches
+  const int *krange;          // [nz + 1][2]: first layer (1-based) and number of layers that knot pi touches; pi = 0: none
+  double *nev;                // [2][NEVN][resident lanes]: the lanes' Neville tables
 };
 
 __device__ __forceinline__ double sgn(double x) { return copysign(1.0, x); }
@@ -162,6 +169,44 @@ __device__ __forceinline__ void layer_model(const Knots &K, const Layer *lay, in
   d = L.d;
 }
 
+// Where the secular function and the start-up take layer m's (a, b, rho, d) from.
+// KnotLayers: rebuilt from the lane's knots at every access (layer_model: ~60 instructions per layer).
+template <int RDEN>
+struct KnotLayers {
+  const Knots &K;
+  const Layer *lay;
+  int nz;
+  bool fast;
+  __device__ __forceinline__ void get(int m, float &a, float &b, float &rho, float &d) const {
+    layer_model<RDEN>(K, lay, m, nz, fast, a, b, rho, d);
+  }
+};
+// TableLayers: the lanes of a wavefront that works on the perturbed copies of a launch are 64 of the 1 + 6 nz variants of a few
+// columns, and a variant differs from its column in ONE knot, which enters only the sublayers of the two intervals next to it --
+// a contiguous range of layers (S-256: 8 of 45).  So layer_model runs once per task, not once per secular evaluation: into a base
+// table per column, (a, b, rho, d) of every layer from the unperturbed knots, and into a patch table per lane, (a, b, rho) of the
+// layers m_lo .. m_lo + cnt - 1 its knot touches, from the lane's own Knots.  Both hold exactly what layer_model returns, so the
+// secular function sees the same bits.  A row of either table starts with (a, b, rho), so an access is a range test, ONE select --
+// of the address: the column's row or the lane's own -- and the reads (rows of 3 words per lane: the lanes' reads of their own rows
+// fall into different banks); d is the column's in any case.  PATCH = false: one unperturbed model (disp_bracket_kernel).
+template <bool PATCH>
+struct TableLayers {
+  const float *lds;     // both tables are addressed from here, in words (the layer's part of an address is wavefront-uniform)
+  int boff;             // layer m of the lane's column: lds[boff + 4 m] (base table: float4 [mmax])
+  int poff;             // layer m of the lane's own rows: lds[poff + 3 TW m] (patch table: [npatch][TW][3], row 0 = layer m_lo)
+  int m_lo;
+  unsigned cnt;
+  __device__ __forceinline__ void get(int m, float &a, float &b, float &rho, float &d) const {
+    const int ib = boff + 4 * m;
+    int i = ib;
+    if (PATCH) i = (unsigned)(m - m_lo) < cnt ? poff + 3 * TW * m : ib;
+    a = lds[i];
+    b = lds[i + 1];
+    rho = lds[i + 2];
+    d = lds[ib + 3];
+  }
+};
+
 // inv/surfdisp96.f:767-865 with var (:868-985), dnka (:1018-1062) and normc (:989-1014) inlined;
 // llw = 1 (no water layer).  normc's log() is dead in the reference and dropped.
 // fp64 divisions are ~30 instructions each on CDNA, so three groups of them are replaced by cheaper forms that
@@ -169,8 +214,8 @@ __device__ __forceinline__ void layer_model(const Knots &K, const Layer *lay, in
 // rounded to fp32): the normalisation of the compound vector multiplies by the reciprocal of its largest entry
 // instead of dividing five times, 1/rho and 1/rho^2 are formed once per layer, and fb/omega uses the reciprocal of
 // omega hoisted out of the layer loop; the remaining divisions of the layer loop use frcp/fdiv above.
-template <int RDEN>
-__device__ double dltar4(const Knots &K, const Layer *lay, int mmax, int nz, bool fast, double wvno, double omga, bool exp3 = false) {
+template <class LS>
+__device__ double dltar4(const LS &S, int mmax, double wvno, double omga, bool exp3 = false) {
 #pragma clang fp contract(fast)   // FMA contraction inside the secular function only (the file is built with -ffp-contract=off)
   double e0, e1, e2, e3, e4;
   double omega = omga;
@@ -178,7 +223,7 @@ __device__ double dltar4(const Knots &K, const Layer *lay, int mmax, int nz, boo
   const double wvno2 = wvno * wvno;
   const double romega = 1.0 / omega;
   float fa, fb, frho, fd;
-  layer_model<RDEN>(K, lay, mmax, nz, fast, fa, fb, frho, fd);
+  S.get(mmax, fa, fb, frho, fd);
   {
     const double xka = omega / (double)fa, xkb = omega / (double)fb;
     double wvnop = wvno + xka, wvnom = fabs(wvno - xka);
@@ -198,7 +243,7 @@ __device__ double dltar4(const Knots &K, const Layer *lay, int mmax, int nz, boo
     e4 = wvno2 - ra * rb;
   }
   for (int m = mmax - 1; m >= 1; m--) {
-    layer_model<RDEN>(K, lay, m, nz, fast, fa, fb, frho, fd);
+    S.get(m, fa, fb, frho, fd);
     const double xka = fdiv(omega, (double)fa), xkb = fdiv(omega, (double)fb);
     const double t = (double)fb * romega;
     const double gammk = 2.0 * t * t;
@@ -332,14 +377,14 @@ __device__ __forceinline__ void brocher(float vs, float &vp, float &rho) {  // i
 enum { P_G1, P_G2, P_N0, P_NA, P_NB, P_GV, P_GW, P_DONE };
 
 // start-up of surfdisp96 (:134-216): extremal velocities of the layer stack and the start value of the first period's search
-template <int RDEN>
-__device__ __forceinline__ void startup(const Knots &K, const Layer *lay, int mmax, int nz, bool fast, float &betmx, float &cc1) {
+template <class LS>
+__device__ __forceinline__ void startup(const LS &S, int mmax, float &betmx, float &cc1) {
   float betmn = 1.e20f, a_mn = 1.0f, b_mn = 1.0f;
   betmx = -1.e20f;
   int jsol = 1;
   for (int m = 1; m <= mmax; m++) {
     float fa, fb, fr, fd;
-    layer_model<RDEN>(K, lay, m, nz, fast, fa, fb, fr, fd);
+    S.get(m, fa, fb, fr, fd);
     if (fb > 0.01f && fb < betmn) {
       betmn = fb;
       a_mn = fa;
@@ -392,6 +437,7 @@ template <int RDEN>
 __global__ __launch_bounds__(64) void disp_bracket_kernel(DispArgs A) {
   __shared__ Layer s_lay[NL];
   __shared__ float s_knot[3 * NZMAX];
+  __shared__ float4 s_base[NL];   // the column's layer stack (TableLayers: one model for the whole wavefront)
   const int lane = threadIdx.x, col = blockIdx.x;
   const int nz = A.nz, mmax = A.mmax;
   for (int i = lane; i < mmax; i += 64) s_lay[i] = A.lay[i];
@@ -422,8 +468,15 @@ __global__ __launch_bounds__(64) void disp_bracket_kernel(DispArgs A) {
       }
     fast = __all(ok);
   }
+  for (int m = lane + 1; m <= mmax; m += 64) {
+    float a, b, r, d;
+    layer_model<RDEN>(K, s_lay, m, nz, fast, a, b, r, d);
+    s_base[m - 1] = make_float4(a, b, r, d);
+  }
+  __syncthreads();
+  const TableLayers<false> S{(const float *)s_base, -4, 0, 0, 0u};
   float betmx, cc1;
-  startup<RDEN>(K, s_lay, mmax, nz, fast, betmx, cc1);
+  startup(S, mmax, betmx, cc1);
   const double dc = fabs((double)0.005f), TWOPI = 2.0 * 3.141592653589793;
   const double omega = TWOPI / A.t[0];
   const double climit = (double)betmx + dc;      // a visited point at or above it ends the reference's search (:470)
@@ -437,7 +490,7 @@ __global__ __launch_bounds__(64) void disp_bracket_kernel(DispArgs A) {
   for (int blk = 0; blk < FF_BLOCKS; blk++) {
     double c = cblk;
     for (int i = 0; i < lane; i++) c = c + dc;   // the reference's c2 = c1 + dc, one step after the other
-    const double del = dltar4<RDEN>(K, s_lay, mmax, nz, fast, omega / c, omega, A.exp3 != 0);
+    const double del = dltar4(S, mmax, omega / c, omega, A.exp3 != 0);
     const unsigned long long neg = __ballot(sgn(del) < 0.0);
     const unsigned long long before = (neg << 1) | (blk > 0 ? prev_last : (neg & 1ull));
     const unsigned long long chg = neg ^ before;                     // bit j: the sign changes between points j-1 and j
@@ -510,12 +563,22 @@ __global__ __launch_bounds__(64) void disp_bracket_kernel(DispArgs A) {
 #ifdef DZ_DISP_STAT
 __device__ unsigned long long g_disp_stat[4];
 #endif
-template <int RDEN, bool TEAMS = false>
+// SHARE (the host decides, option disp.share): the lanes take their layers from TableLayers.  The patch tables want the LDS that the
+// Neville tables hold (45 KB of the 52.5 KB that three workgroups per CU may have each), and those are touched a handful of times
+// between two secular evaluations of ~15 k instructions: they move to HBM, [NEVN][resident lane], coalesced (DispArgs::nev).
+template <int RDEN, bool TEAMS = false, bool SHARE = false>
 __global__ __launch_bounds__(DT, 3) void disp_kernel(DispArgs A) {
+  static_assert(!(TEAMS && SHARE), "a team holds one item: nothing to share");
   __shared__ Layer s_lay[NL];
   __shared__ double s_t[NP];
-  extern __shared__ __attribute__((aligned(16))) float s_knots[];  // [DT / 64][cpb][3][nz]
-  __shared__ double s_x[NEVN][DT], s_y[NEVN][DT];
+  extern __shared__ __attribute__((aligned(16))) float s_knots[];  // [DT / 64][cpb][3][nz]; SHARE: + float4 [DT / 64][cpb][mmax] + [DT / 64][npatch][TW][3]
+  constexpr int NEVL = SHARE ? 1 : DT;
+  __shared__ double s_x[NEVN][NEVL], s_y[NEVN][NEVL];
+  const size_t nev_n = (size_t)gridDim.x * DT;
+  double *const nev_x = SHARE ? A.nev + (size_t)blockIdx.x * DT + threadIdx.x : nullptr, *const nev_y = SHARE ? nev_x + NEVN * nev_n : nullptr;
+  // entry i of this lane's Neville tables x / y, wherever they live: a reference into HBM (SHARE) or into LDS
+  auto NX = [&](int i) -> double & { if constexpr (SHARE) return nev_x[(size_t)i * nev_n]; else return s_x[i][threadIdx.x]; };
+  auto NY = [&](int i) -> double & { if constexpr (SHARE) return nev_y[(size_t)i * nev_n]; else return s_y[i][threadIdx.x]; };
   const int tid = threadIdx.x, lane = tid & 63;
   const int nz = A.nz, kmax = A.kmax, mmax = A.mmax, nvar = A.nvar, nvarp = A.nvarp;
   const long nwork = (long)A.ncol * nvarp;
@@ -600,8 +663,38 @@ __global__ __launch_bounds__(DT, 3) void disp_kernel(DispArgs A) {
     }
     // ---- start-up of surfdisp96 (:134-216): extremal velocities, half-space start value (recomputed per chunk: one pass
     // over the layers, the cost of a fraction of one secular evaluation) ----
+    const KnotLayers<RDEN> SK{K, s_lay, nz, fast};
+    TableLayers<true> ST{s_knots, 0, 0, 0, 0u};
+    if constexpr (SHARE) {   // the task's layer tables: one layer of a column per lane, then every lane the layers its knot touches
+      // this wavefront's tables lie behind the knots of all wavefronts (the other instantiations have no such LDS)
+      float4 *const s_tab = (float4 *)(s_knots + (((DT / TW) * cpb * 3 * nz + 3) & ~3));
+      float4 *const s_base = s_tab + (size_t)(tid >> 6) * cpb * mmax;
+      float *const s_patch = (float *)(s_tab + (size_t)(DT / TW) * cpb * mmax) + (size_t)(tid >> 6) * A.npatch * 3 * TW + 3 * lane;
+      ST.boff = (int)((const float *)(s_base + (size_t)(col - col0) * mmax) - s_knots) - 4;
+      for (int i = lane; i < cpb * mmax; i += TW) {
+        const int c = i / mmax, m = i - c * mmax + 1;
+        if (col0 + c >= A.ncol) continue;
+        const Knots Kc{s_knot + (c * 3 + 0) * nz, s_knot + (c * 3 + 1) * nz, s_knot + (c * 3 + 2) * nz, 0, -1, 0.0f};
+        float a, b, r, d;
+        layer_model<RDEN>(Kc, s_lay, m, nz, fast, a, b, r, d);
+        s_base[i] = make_float4(a, b, r, d);
+      }
+      ST.m_lo = A.krange[2 * K.pi];
+      ST.cnt = (unsigned)A.krange[2 * K.pi + 1];
+      ST.poff = (int)(s_patch - s_knots) - 3 * TW * ST.m_lo;
+      for (unsigned j = 0; j < (unsigned)A.npatch; j++)
+        if (j < ST.cnt) {
+          float a, b, r, d;
+          layer_model<RDEN>(K, s_lay, ST.m_lo + (int)j, nz, fast, a, b, r, d);
+          s_patch[j * (3 * TW) + 0] = a;
+          s_patch[j * (3 * TW) + 1] = b;
+          s_patch[j * (3 * TW) + 2] = r;
+        }
+      __builtin_amdgcn_wave_barrier();
+    }
     float betmx, cc1;
-    startup<RDEN>(K, s_lay, mmax, nz, fast, betmx, cc1);
+    if constexpr (SHARE) startup(ST, mmax, betmx, cc1);
+    else startup(SK, mmax, betmx, cc1);
     const float ddc = 0.005f, sone = 1.5f;
     const double onea = (double)sone, TWOPI = 2.0 * 3.141592653589793;
     const double cc = (double)cc1, dc = fabs((double)ddc), cm = cc;
@@ -636,7 +729,9 @@ __global__ __launch_bounds__(DT, 3) void disp_kernel(DispArgs A) {
       st_iter++;
       if (phase != P_DONE) st_act++;
 #endif
-      const double del = dltar4<RDEN>(K, s_lay, mmax, nz, fast, omega / ceval, omega, A.exp3 != 0);
+      double del;
+      if constexpr (SHARE) del = dltar4(ST, mmax, omega / ceval, omega, A.exp3 != 0);
+      else del = dltar4(SK, mmax, omega / ceval, omega, A.exp3 != 0);
       if (phase == P_DONE) continue;
       bool advance_bracket = false, nev_top = false, nev_body = false, finish = false, fail = false;
       switch (phase) {
@@ -655,7 +750,7 @@ __global__ __launch_bounds__(DT, 3) void disp_kernel(DispArgs A) {
               if (m > lim) m = lim > 0 ? lim : 0;
             }
             if (m >= 2) {
-              s_x[0][tid] = c1;                        // (the Neville table is idle during the bracket search)
+              NX(0) = c1;                        // (the Neville table is idle during the bracket search)
               for (int i = 0; i < m; i++) c1 = c1 + dc;   // the same additions the step-by-step search would have made
               ceval = c1;
               phase = P_GV;
@@ -668,7 +763,7 @@ __global__ __launch_bounds__(DT, 3) void disp_kernel(DispArgs A) {
           if (sgn(del) == sgn(del1))
             del1 = del;
           else {
-            c1 = s_x[0][tid];
+            c1 = NX(0);
             if (var > 0) atomicAdd(&A.ff_stat[3], 1u);
           }
           advance_bracket = true;
@@ -796,29 +891,29 @@ __global__ __launch_bounds__(DT, 3) void disp_kernel(DispArgs A) {
             mm = 1;
           } else {
             if (nev == 2) {
-              s_x[mm][tid] = c3;
-              s_y[mm][tid] = del3;
+              NX(mm) = c3;
+              NY(mm) = del3;
             } else {
-              s_x[0][tid] = c1;
-              s_y[0][tid] = del1;
-              s_x[1][tid] = c2;
-              s_y[1][tid] = del2;
+              NX(0) = c1;
+              NY(0) = del1;
+              NX(1) = c2;
+              NY(1) = del2;
               mm = 1;
             }
             bool bad = false;
-            const double ym = s_y[mm][tid];
+            const double ym = NY(mm);
             for (int kk = 1; kk <= mm; kk++) {
               const int j = mm - kk + 1;
-              const double yj = s_y[j - 1][tid];
+              const double yj = NY(j - 1);
               const double denom = ym - yj;
               if (fabs(denom) < 1.0e-10 * fabs(ym)) {
                 bad = true;
                 break;
               }
-              s_x[j - 1][tid] = (-yj * s_x[j][tid] + ym * s_x[j - 1][tid]) / denom;
+              NX(j - 1) = (-yj * NX(j) + ym * NX(j - 1)) / denom;
             }
             if (!bad) {
-              c3 = s_x[0][tid];
+              c3 = NX(0);
               nev = 2;
               mm = mm + 1;
               if (mm > 10) mm = 10;
@@ -1018,6 +1113,25 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
   A.team = 1;
   A.mmax = mmax;
   A.vel = vel.dev;
+  // shared layer stacks (TableLayers): the contiguous range of layers that knot pi touches -- the sublayers of intervals pi - 1 and
+  // pi, for the last knot those of the last interval and the half-space -- and the longest such range
+  std::vector<int> krange(2 * (nz + 1), 0);
+  A.npatch = 1;
+  for (int pi = 1; pi <= nz; pi++) {
+    int lo = 0, hi = 0;
+    for (int m = 1; m <= mmax; m++)
+      if ((pi > 1 && lay[m - 1].iv == pi - 1) || lay[m - 1].iv == pi || (pi == nz && lay[m - 1].iv == 0)) {
+        if (!lo) lo = m;
+        hi = m;
+      }
+    krange[2 * pi] = lo;
+    krange[2 * pi + 1] = lo ? hi - lo + 1 : 0;
+    if (krange[2 * pi + 1] > A.npatch) A.npatch = krange[2 * pi + 1];
+  }
+  A.nev = nullptr;
+  if ((rc = dz_scratch(ctx, "disp.krange", sizeof(int) * 2 * (NZMAX + 1), &p))) return rc;
+  A.krange = (const int *)p;
+  DZ_HIP(hipMemcpyAsync(p, krange.data(), sizeof(int) * krange.size(), hipMemcpyHostToDevice, ctx->stream));
   if ((rc = dz_scratch(ctx, "disp.lay", sizeof(Layer) * NL, &p))) return rc;
   A.lay = (Layer *)p;
   DZ_HIP(hipMemcpyAsync(p, lay.data(), sizeof(Layer) * mmax, hipMemcpyHostToDevice, ctx->stream));
@@ -1060,6 +1174,25 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
   DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
   DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
   DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
+  // Shared layer stacks for the launch that holds the perturbed copies (all variants, or the copies of disp.async): knots + base
+  // tables + patch tables per wavefront, where that leaves three workgroups per CU (LDS comes in granules of 1 280 bytes, 42 of them
+  // per workgroup) -- models with many sublayers per interval or very many layers keep rebuilding their layers.  Option disp.share = 0
+  // forces that path.
+  const void *kshare = rden == 1 ? (const void *)disp_kernel<1, false, true>
+                                 : (rden == 2 ? (const void *)disp_kernel<2, false, true> : (const void *)disp_kernel<0, false, true>);
+  auto share_lds = [&](int nvarp) {
+    const size_t cpb = (size_t)(TW + nvarp - 1) / nvarp + 1, knots = (((size_t)(DT / TW) * cpb * 3 * nz + 3) & ~(size_t)3) * sizeof(float);
+    return knots + (size_t)(DT / TW) * cpb * mmax * sizeof(float4) + (size_t)(DT / TW) * A.npatch * 3 * TW * sizeof(float);
+  };
+  bool share = kernels && !(ctx->opts.count("disp.share") && !ctx->opts["disp.share"]);
+  if (share) {
+    hipFuncAttributes fa;
+    DZ_HIP(hipFuncGetAttributes(&fa, kshare));
+    const size_t need = std::max(share_lds(nvar), share_lds(nvar - 1));
+    share = fa.sharedSizeBytes + need <= (size_t)42 * 1280;
+    if (share) DZ_HIP(hipFuncSetAttribute(kshare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+  }
+  ctx->ksec["disp.share"] = share ? 1.0 : 0.0;
   if (async && (rc = dz_aux_init(ctx))) return rc;
   {
     const long nwork = (long)ncol * nvar;
@@ -1082,7 +1215,11 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
     A.st_f = (int *)p;
     const void *kf = rden == 1 ? (const void *)disp_kernel<1> : (rden == 2 ? (const void *)disp_kernel<2> : (const void *)disp_kernel<0>);
     int occ = 3;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kf, DT, dyn_lds) != hipSuccess || occ < 1) occ = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, share ? kshare : kf, DT, share ? share_lds(nvar) : dyn_lds) != hipSuccess || occ < 1) occ = 1;
+    if (share) {   // the Neville tables of every lane that can be resident
+      if ((rc = dz_scratch(ctx, "disp.nev", sizeof(double) * 2 * NEVN * (size_t)ctx->num_cu * occ * DT, &p))) return rc;
+      A.nev = (double *)p;
+    }
     long nwg = (long)ctx->num_cu * occ;
     if (nwg > ((long)ntask + DT / TW - 1) / (DT / TW)) nwg = ((long)ntask + DT / TW - 1) / (DT / TW);
     // first-period fast-forward (disp_bracket_kernel); off with option disp.ffwd = 0 and when the periods are handed from task to task
@@ -1126,7 +1263,15 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
       DZ_HIP(hipGetLastError());
     }
     auto launch = [&](const DispArgs &B, long nwgB, size_t lds, hipStream_t st) {
-      if (B.team > 1) {
+      if (share && B.team == 1 && B.nvarp > 1) {
+        lds = share_lds(B.nvarp);
+        if (rden == 1)
+          hipLaunchKernelGGL((disp_kernel<1, false, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
+        else if (rden == 2)
+          hipLaunchKernelGGL((disp_kernel<2, false, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
+        else
+          hipLaunchKernelGGL((disp_kernel<0, false, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
+      } else if (B.team > 1) {
         if (rden == 1)
           hipLaunchKernelGGL((disp_kernel<1, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
         else if (rden == 2)
