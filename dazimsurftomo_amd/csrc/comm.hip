@@ -141,7 +141,7 @@ int dz_allgather(dazim_ctx *ctx, DzComm *c, const void *send_dev, void *recv_dev
 int dz_allreduce(dazim_ctx *ctx, DzComm *c, void *dbuf, size_t count, int dtype, int op) {
   if (count == 0) return 0;
   const size_t esz = dtype == DZ_F32 ? 4 : 8, bytes = count * esz;
-  if (c->dir.empty() && ctx->opts.count("comm.allreduce") && ctx->opts["comm.allreduce"] == 1) {   // RCCL's own all-reduce (its order)
+  if (c->dir.empty() && dz_opt(ctx, "comm.allreduce", 0) == 1) {   // RCCL's own all-reduce (its order)
     const ncclDataType_t t = dtype == DZ_F32 ? ncclFloat : (dtype == DZ_F64 ? ncclDouble : ncclInt64);
     DZ_NCCL(ncclAllReduce(dbuf, dbuf, count, t, op == DZ_SUM ? ncclSum : ncclMax, c->nccl, ctx->stream));
     return 0;
@@ -487,9 +487,9 @@ int dazim_dispersion_kernels_sharded(dazim_ctx *ctx, int nx, int ny, int nz, con
   // that waiting for this rank's copies costs less than the ray kernel beside the eikonal tail brings: an RCCL communicator is
   // kept to the main stream, where a deferred gather would sit behind the whole eikonal launch and keep the ray call from
   // starting beside it (rays.hip).  The same decision on every rank: options and rank count are the ranks' own.
-  const bool gather_now = (c->nccl && c->nranks >= 4 && ctx->opts.count("fmm.async") && ctx->opts["fmm.async"]) ||
-                          (ctx->opts.count("comm.gather_now") && ctx->opts["comm.gather_now"]);   // (test knob: the same path over files)
-  const bool defer = !gather_now && !svs.staged && !svp.staged && !srho.staged && ctx->opts.count("disp.async") && ctx->opts["disp.async"];
+  const bool gather_now = (c->nccl && c->nranks >= 4 && dz_opt(ctx, "fmm.async", 0) != 0) ||
+                          dz_opt(ctx, "comm.gather_now", 0) != 0;   // (test knob: the same path over files)
+  const bool defer = !gather_now && !svs.staged && !svp.staged && !srho.staged && dz_opt(ctx, "disp.async", 0) != 0;
   if (defer) {
     if (!ctx->aux_pending) {   // nothing of this rank on the auxiliary stream: an event that is already complete
       if ((rc = dz_aux_init(ctx))) return rc;

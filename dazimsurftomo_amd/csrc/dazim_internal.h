@@ -83,6 +83,11 @@ struct dazim_ctx {
 };
 
 int dz_fail(dazim_ctx *c, int code, const char *fmt, ...);
+// value of an option, `def` where it was never set (the look-up does not insert it)
+static inline int dz_opt(const dazim_ctx *ctx, const char *name, int def) {
+  const auto it = ctx->opts.find(name);
+  return it == ctx->opts.end() ? def : it->second;
+}
 
 // ---- the communicator of a multi-rank run (comm.hip) ---------------------------------------------------------------------------
 struct DzComm {
@@ -156,6 +161,21 @@ int dz_stage_get(dazim_ctx *ctx, size_t bytes, void **out);   // a device block 
 void dz_stage_put(dazim_ctx *ctx, void *p);                   // give it back (kept for reuse; freed by dazim_destroy)
 int dz_big_get(dazim_ctx *ctx, size_t bytes, void **out);     // a device array for a matrix (see dazim_ctx::big)
 void dz_big_put(dazim_ctx *ctx, void *p);                     // return it (any hipMalloc'ed pointer is accepted; ctx may be null)
+// dz_scratch / dz_big_get for `count` elements of T
+template <class T>
+static inline int dz_scratch(dazim_ctx *ctx, const char *name, size_t count, T **out) {
+  void *p = nullptr;
+  const int rc = dz_scratch(ctx, name, count * sizeof(T), &p);
+  *out = (T *)p;
+  return rc;
+}
+template <class T>
+static inline int dz_big_get(dazim_ctx *ctx, size_t count, T **out) {
+  void *p = nullptr;
+  const int rc = dz_big_get(ctx, count * sizeof(T), &p);
+  *out = (T *)p;
+  return rc;
+}
 
 // take ownership of device CSR arrays whose allocations hold cap_m rows / cap_nnz entries (0 = exactly m / nnz); sparse.hip
 extern "C" int dz_csr_adopt_cap(dazim_ctx *ctx, int64_t m, int64_t n, int64_t nnz, int64_t *rowptr, int *col, float *val,

@@ -1068,7 +1068,7 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
     for (int v : {6, 10, 12, 14, 18, 20, 22, 24, 26, 28, 30, 36}) fastdiv_ok = fastdiv_ok || d == v;
     if (!pow2) rden = (fastdiv_ok && rden != 0) ? 2 : 0;
   }
-  if (ctx->opts.count("disp.rden") && !ctx->opts["disp.rden"]) rden = 0;   // test knob: keep the divisions
+  if (dz_opt(ctx, "disp.rden", 1) == 0) rden = 0;   // test knob: keep the divisions
   const int mmax = (int)lay.size();
   if (mmax > NL) return dz_fail(ctx, DAZIM_E_BAD_ARG, "refined model has %d layers > NL=%d", mmax, NL);
   {
@@ -1138,10 +1138,9 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
   if ((rc = dz_scratch(ctx, "disp.t", sizeof(double) * NP, &p))) return rc;
   A.t = (double *)p;
   DZ_HIP(hipMemcpyAsync(p, periods, sizeof(double) * kmax, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = dz_scratch(ctx, "disp.cg", sizeof(float) * (size_t)ncol * nvar * kmax, &p))) return rc;
-  A.cg = (float *)p;
-  if ((rc = dz_scratch(ctx, "disp.nfail", 16, &p))) return rc;
-  int *d_nfail = (int *)p;
+  if ((rc = dz_scratch(ctx, "disp.cg", (size_t)ncol * nvar * kmax, &A.cg))) return rc;
+  int *d_nfail;
+  if ((rc = dz_scratch(ctx, "disp.nfail", 4, &d_nfail))) return rc;
   DZ_HIP(hipMemsetAsync(d_nfail, 0, 4, ctx->stream));
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   auto knot_lds = [&](int nvarp, int items = TW) { return (size_t)(DT / TW) * ((items + nvarp - 1) / nvarp + 1) * 3 * nz * sizeof(float); };
@@ -1153,8 +1152,8 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
   // vel) before one of these calls dazim_sync first.  What it buys: the dispersion kernel's last, partly filled round of
   // workgroups (S-256: 64 of 832) and the eikonal kernel share the chip (measured: 293 against 306 ms), and on
   // small batches (S-128) the two kernels, neither of which fills it, run side by side.
-  bool async = kernels && ctx->opts.count("disp.async") && ctx->opts["disp.async"] && !vel.staged && !svs.staged &&
-               !svp.staged && !srho.staged && !(ctx->opts.count("disp.pchunk") && ctx->opts["disp.pchunk"] > 0 && ctx->opts["disp.pchunk"] < kmax);
+  bool async = kernels && dz_opt(ctx, "disp.async", 0) != 0 && !vel.staged && !svs.staged &&
+               !svp.staged && !srho.staged && !(dz_opt(ctx, "disp.pchunk", 0) > 0 && dz_opt(ctx, "disp.pchunk", 0) < kmax);
   // the column curves of an asynchronous call in teams (disp_kernel: TEAM grid points of the bracket search at a time) when the
   // extra wavefronts do not add a round of workgroups to the copies beside them: everything fits one round (S-128), or the copies
   // need a second, partly filled round anyway (S-256: 832 + 183 workgroups on 768 slots; the curves are what the eikonal kernel
@@ -1163,8 +1162,8 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
   const double wg_copies = (double)(((long)ncol * (nvar - 1) + DT - 1) / DT), wg_teams = (double)((ncol * TEAM + DT - 1) / DT);
   const double wg_round = (double)((long)ctx->num_cu * 3);
   bool teams = wg_copies + wg_teams <= 0.98 * wg_round || (wg_copies > 1.02 * wg_round && wg_copies + wg_teams <= 1.9 * wg_round);
-  if (ctx->opts.count("disp.team") && ctx->opts["disp.team"] == 1) teams = true;
-  if (ctx->opts.count("disp.team") && ctx->opts["disp.team"] == 2) teams = false;
+  if (dz_opt(ctx, "disp.team", 0) == 1) teams = true;
+  if (dz_opt(ctx, "disp.team", 0) == 2) teams = false;
   const size_t dyn_lds = knot_lds(nvar), dyn_lds_base = teams ? knot_lds(1, TW / TEAM) : knot_lds(1);
   if (dyn_lds_base + 56 * 1024 > 160 * 1024) async = false;   // (very many knots: the 64 columns of a base task would not fit the LDS)
   const size_t dyn_max = async && dyn_lds_base > dyn_lds ? dyn_lds_base : dyn_lds;
@@ -1184,7 +1183,7 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
     const size_t cpb = (size_t)(TW + nvarp - 1) / nvarp + 1, knots = (((size_t)(DT / TW) * cpb * 3 * nz + 3) & ~(size_t)3) * sizeof(float);
     return knots + (size_t)(DT / TW) * cpb * mmax * sizeof(float4) + (size_t)(DT / TW) * A.npatch * 3 * TW * sizeof(float);
   };
-  bool share = kernels && !(ctx->opts.count("disp.share") && !ctx->opts["disp.share"]);
+  bool share = kernels && dz_opt(ctx, "disp.share", 1) != 0;
   if (share) {
     hipFuncAttributes fa;
     DZ_HIP(hipFuncGetAttributes(&fa, kshare));
@@ -1199,26 +1198,21 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
     // task queue: groups of DT items x chunks of pchunk periods (see disp_kernel); persistent workgroups, as many as are resident
     A.ngroup = (int)((nwork + TW - 1) / TW);
     A.pchunk = kmax;
-    if (ctx->opts.count("disp.pchunk") && ctx->opts["disp.pchunk"] > 0) A.pchunk = ctx->opts["disp.pchunk"];
+    if (dz_opt(ctx, "disp.pchunk", 0) > 0) A.pchunk = dz_opt(ctx, "disp.pchunk", 0);
     if (A.pchunk > kmax) A.pchunk = kmax;
     A.nchunk = (kmax + A.pchunk - 1) / A.pchunk;
     const size_t ntask = (size_t)A.ngroup * A.nchunk;
-    if ((rc = dz_scratch(ctx, "disp.ready", ntask * 4 + 64, &p))) return rc;
-    A.ready = (int *)p;
-    A.counter = (unsigned *)((char *)p + ntask * 4 + 16 - (ntask * 4) % 16);
-    DZ_HIP(hipMemsetAsync(p, 0, ntask * 4 + 64, ctx->stream));
-    if ((rc = dz_scratch(ctx, "disp.st_c", (size_t)nwork * 8, &p))) return rc;
-    A.st_c = (double *)p;
-    if ((rc = dz_scratch(ctx, "disp.st_d", (size_t)nwork * 8, &p))) return rc;
-    A.st_d = (double *)p;
-    if ((rc = dz_scratch(ctx, "disp.st_f", (size_t)nwork * 4, &p))) return rc;
-    A.st_f = (int *)p;
+    if ((rc = dz_scratch(ctx, "disp.ready", ntask + 16, &A.ready))) return rc;
+    A.counter = (unsigned *)((char *)A.ready + ntask * 4 + 16 - (ntask * 4) % 16);
+    DZ_HIP(hipMemsetAsync(A.ready, 0, ntask * 4 + 64, ctx->stream));
+    if ((rc = dz_scratch(ctx, "disp.st_c", (size_t)nwork, &A.st_c))) return rc;
+    if ((rc = dz_scratch(ctx, "disp.st_d", (size_t)nwork, &A.st_d))) return rc;
+    if ((rc = dz_scratch(ctx, "disp.st_f", (size_t)nwork, &A.st_f))) return rc;
     const void *kf = rden == 1 ? (const void *)disp_kernel<1> : (rden == 2 ? (const void *)disp_kernel<2> : (const void *)disp_kernel<0>);
     int occ = 3;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, share ? kshare : kf, DT, share ? share_lds(nvar) : dyn_lds) != hipSuccess || occ < 1) occ = 1;
     if (share) {   // the Neville tables of every lane that can be resident
-      if ((rc = dz_scratch(ctx, "disp.nev", sizeof(double) * 2 * NEVN * (size_t)ctx->num_cu * occ * DT, &p))) return rc;
-      A.nev = (double *)p;
+      if ((rc = dz_scratch(ctx, "disp.nev", 2 * NEVN * (size_t)ctx->num_cu * occ * DT, &A.nev))) return rc;
     }
     long nwg = (long)ctx->num_cu * occ;
     if (nwg > ((long)ntask + DT / TW - 1) / (DT / TW)) nwg = ((long)ntask + DT / TW - 1) / (DT / TW);
@@ -1230,20 +1224,16 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
     // 0 = no jump.
     A.ffwd = 0;
     if (A.nchunk == 1) {
-      A.ffwd = 1;
-      if (ctx->opts.count("disp.ffwd")) A.ffwd = ctx->opts["disp.ffwd"] < 0 ? 0 : (ctx->opts["disp.ffwd"] > 2 ? 2 : ctx->opts["disp.ffwd"]);
+      const int ff = dz_opt(ctx, "disp.ffwd", 1);
+      A.ffwd = ff < 0 ? 0 : (ff > 2 ? 2 : ff);
     }
-    A.exp3 = ctx->opts.count("disp.exp3") && ctx->opts["disp.exp3"] ? 1 : 0;
-    if ((rc = dz_scratch(ctx, "disp.ff_stat", 64, &p))) return rc;
-    A.ff_stat = (unsigned *)p;
+    A.exp3 = dz_opt(ctx, "disp.exp3", 0) != 0 ? 1 : 0;
+    if ((rc = dz_scratch(ctx, "disp.ff_stat", 16, &A.ff_stat))) return rc;
     DZ_HIP(hipMemsetAsync(A.ff_stat, 0, 64, ctx->stream));
-    if ((rc = dz_scratch(ctx, "disp.ff_m", (size_t)ncol * 4 + 16, &p))) return rc;
-    A.ff_m = (int *)p;
-    if ((rc = dz_scratch(ctx, "disp.ff_c", (size_t)ncol * 8 + 16, &p))) return rc;
-    A.ff_c = (double *)p;
-    if ((rc = dz_scratch(ctx, "disp.ff_v", (size_t)ncol * 4 + 16, &p))) return rc;
-    A.ff_v = (int *)p;
-    if (async && ctx->opts["disp.async"] == 1) {
+    if ((rc = dz_scratch(ctx, "disp.ff_m", (size_t)ncol + 4, &A.ff_m))) return rc;
+    if ((rc = dz_scratch(ctx, "disp.ff_c", (size_t)ncol + 2, &A.ff_c))) return rc;
+    if ((rc = dz_scratch(ctx, "disp.ff_v", (size_t)ncol + 4, &A.ff_v))) return rc;
+    if (async && dz_opt(ctx, "disp.async", 0) == 1) {
       // 1 = two streams where they pay: what the eikonal kernel can share the chip with is the copies' last, partly filled round
       // (or a launch that never fills it); over many rounds that is a small part of the launch and the two kernels only take
       // each other's LDS (S-512, four rounds: eikonal kernel +0.31 s for 0.25 s of dispersion).  2 = always.
@@ -1310,10 +1300,9 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
       B.nfail = d_nfail;
       B.ngroup = (ncol + TW / B.team - 1) / (TW / B.team);
       ctx->ksec["disp.team"] = B.team;
-      if ((rc = dz_scratch(ctx, "disp.ready_b", (size_t)B.ngroup * 4 + 64, &p))) return rc;
-      B.ready = (int *)p;
-      B.counter = (unsigned *)((char *)p + (size_t)B.ngroup * 4 + 16 - ((size_t)B.ngroup * 4) % 16);
-      DZ_HIP(hipMemsetAsync(p, 0, (size_t)B.ngroup * 4 + 64, ctx->stream));
+      if ((rc = dz_scratch(ctx, "disp.ready_b", (size_t)B.ngroup + 16, &B.ready))) return rc;
+      B.counter = (unsigned *)((char *)B.ready + (size_t)B.ngroup * 4 + 16 - ((size_t)B.ngroup * 4) % 16);
+      DZ_HIP(hipMemsetAsync(B.ready, 0, (size_t)B.ngroup * 4 + 64, ctx->stream));
       DZ_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
       const long nwgB = ((long)B.ngroup + DT / TW - 1) / (DT / TW);
       launch(B, nwgB, dyn_lds_base, ctx->stream);   // (first: its workgroups want a CU's LDS before the copies' have filled them)

@@ -1599,7 +1599,7 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 16) per_cu = 16;
   ctx->ksec["fmm.wg_per_cu"] = (double)per_cu;
-  if (ctx->opts.count("fmm.wg_per_cu") && ctx->opts["fmm.wg_per_cu"] > 0 && ctx->opts["fmm.wg_per_cu"] < per_cu) per_cu = ctx->opts["fmm.wg_per_cu"];
+  if (dz_opt(ctx, "fmm.wg_per_cu", 0) > 0 && dz_opt(ctx, "fmm.wg_per_cu", 0) < per_cu) per_cu = dz_opt(ctx, "fmm.wg_per_cu", 0);
   int nwg = ctx->num_cu * per_cu;
   // Small batches: a launch lasts at least as long as ONE field takes alone, and with fewer wavefronts than SIMDs most of the
   // chip idles.  Fewer fields per wavefront put every field on a SIMD of its own sooner but were measured and buy nothing (S-128:
@@ -1628,14 +1628,14 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
   // 32 000 fields (1024-slot hybrid heap) 4.29 s unsliced, 4.03 / 3.96 / 3.97 s with 2 / 4 / 8.  Defaults: 2 on the 512-slot heaps
   // with 16-bit ids (round 5, the all-LDS one on a 166 x 166 grid, 16 000 fields: 156 k fields/s with 2 stages, 122 k with 4), 8 on the one with two HBM levels (S-512: 2.68 / 2.63 / 2.61 s with 2 / 4 / 8), 4 elsewhere.
   bool ts = nfield > nslot;
-  if (ctx->opts.count("fmm.ts") && ctx->opts["fmm.ts"] == 1) ts = true;
-  if (ctx->opts.count("fmm.ts") && ctx->opts["fmm.ts"] == 2) ts = false;
+  if (dz_opt(ctx, "fmm.ts", 0) == 1) ts = true;
+  if (dz_opt(ctx, "fmm.ts", 0) == 2) ts = false;
   const size_t rec_field_bytes = (size_t)tile_records(A.g.nnx, A.g.nnz) * sizeof(unsigned);
   {
     size_t mfree = 0, mtot = 0;
     if (hipMemGetInfo(&mfree, &mtot) != hipSuccess || (size_t)nfield * rec_field_bytes > mfree / 4) ts = false;
   }
-  int nseg = ctx->opts.count("fmm.ts_stages") && ctx->opts["fmm.ts_stages"] > 0 ? ctx->opts["fmm.ts_stages"] : (CAP <= 512 ? (sizeof(NT) == 2 ? 2 : (HYB ? 8 : 4)) : 4);
+  int nseg = dz_opt(ctx, "fmm.ts_stages", 0) > 0 ? dz_opt(ctx, "fmm.ts_stages", 0) : (CAP <= 512 ? (sizeof(NT) == 2 ? 2 : (HYB ? 8 : 4)) : 4);
   A.ts_nstage = ts ? 1 + nseg : 1;
   // (stage lengths that shrink towards the end -- a shorter tail -- were measured and lose: 0.251-0.265 s against 0.247 s)
   A.ts_pops = (int)((nn + nseg - 1) / nseg);
@@ -1659,24 +1659,17 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
   }
   A.ts_flag = nullptr; A.ts_keys = nullptr; A.ts_nodes = nullptr;
   if (ts) {
-    if ((rc = dz_scratch(ctx, "fmm.ts_flag", ((size_t)nfield / A.fpw + 2) * 4, &p))) return rc;
-    A.ts_flag = (unsigned *)p;
+    if ((rc = dz_scratch(ctx, "fmm.ts_flag", ((size_t)nfield / A.fpw + 2), &A.ts_flag))) return rc;
     DZ_HIP(hipMemsetAsync(A.ts_flag, 0, ((size_t)nfield / A.fpw + 2) * 4, ctx->stream));
-    if ((rc = dz_scratch(ctx, "fmm.ts_keys", (size_t)nfield * CAP * 4, &p))) return rc;
-    A.ts_keys = (float *)p;
-    if ((rc = dz_scratch(ctx, "fmm.ts_nodes", (size_t)nfield * CAP * 4, &p))) return rc;
-    A.ts_nodes = (int *)p;
+    if ((rc = dz_scratch(ctx, "fmm.ts_keys", (size_t)nfield * CAP, &A.ts_keys))) return rc;
+    if ((rc = dz_scratch(ctx, "fmm.ts_nodes", (size_t)nfield * CAP, &A.ts_nodes))) return rc;
   }
-  if ((rc = dz_scratch(ctx, "fmm.rec_r", (size_t)nslot * NREC_R * sizeof(unsigned), &p))) return rc;
-  A.rec_r = (unsigned *)p;
-  if ((rc = dz_scratch(ctx, "fmm.velnr", (size_t)nslot * nr * 4, &p))) return rc;
-  A.velnr = (float *)p;
-  if ((rc = dz_scratch(ctx, "fmm.slownr", (size_t)nslot * NREC_R * sizeof(float2), &p))) return rc;
-  A.slownr = (float2 *)p;
+  if ((rc = dz_scratch(ctx, "fmm.rec_r", (size_t)nslot * NREC_R, &A.rec_r))) return rc;
+  if ((rc = dz_scratch(ctx, "fmm.velnr", (size_t)nslot * nr, &A.velnr))) return rc;
+  if ((rc = dz_scratch(ctx, "fmm.slownr", (size_t)nslot * NREC_R, &A.slownr))) return rc;
   if ((rc = dz_scratch(ctx, "fmm.ovf", nown * A.ovfcap * sizeof(HEnt) + 64, &p))) return rc;
   A.ovf = (HEnt *)p;
-  if ((rc = dz_scratch(ctx, "fmm.counter", 256, &p))) return rc;
-  A.counter = (unsigned *)p;
+  if ((rc = dz_scratch(ctx, "fmm.counter", 64, &A.counter))) return rc;
   A.status = d_status;
   A.flist = nullptr;
   std::vector<int> order(nfield);
@@ -1686,7 +1679,7 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
     if ((rc = dz_pinned(ctx, "fmm.host", (size_t)nfield * 12 + 64, &p))) return rc;
     int *hper = (int *)p;
     float *hx = (float *)p + nfield, *hz = (float *)p + 2 * (size_t)nfield;
-    const bool sorted = !(ctx->opts.count("fmm.sort") && !ctx->opts["fmm.sort"]);
+    const bool sorted = dz_opt(ctx, "fmm.sort", 1) != 0;
     DZ_HIP(hipMemcpyAsync(hper, A.period, (size_t)nfield * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (sorted) {
       DZ_HIP(hipMemcpyAsync(hx, A.scx, (size_t)nfield * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1734,7 +1727,7 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
     DZ_HIP(hipMemcpyAsync(p, po, (size_t)nfield * 4, hipMemcpyHostToDevice, ctx->stream));
     A.flist = (const int *)p;
   }
-  const bool force_spill = ctx->opts.count("fmm.force_spill") && ctx->opts["fmm.force_spill"];
+  const bool force_spill = dz_opt(ctx, "fmm.force_spill", 0) != 0;
   if ((rc = dz_pinned(ctx, "fmm.host_status", (size_t)nfield * 4 + 64, &p))) return rc;
   int *hs_pin = (int *)p;
   if ((rc = dz_async_init(ctx))) return rc;
@@ -1790,8 +1783,7 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
     if (nwg2 > nwg) nwg2 = nwg;
     // the spill kernel keeps every slot >= CAP in HBM: maxbt entries per resident field, allocated only when a field needs it
     A.ovfcap = ovfcap;
-    if ((rc = dz_scratch(ctx, "fmm.ovf_spill", (size_t)nwg2 * 4 * ovfcap * sizeof(HEnt), &p))) return rc;
-    A.ovf = (HEnt *)p;
+    if ((rc = dz_scratch(ctx, "fmm.ovf_spill", (size_t)nwg2 * 4 * ovfcap, &A.ovf))) return rc;
     if (keep_tiled && ts) {   // (the first launch's node words ARE the results: the rerun marches in blocks of its own and copies)
       if ((rc = dz_scratch(ctx, "fmm.rec_spill", (size_t)(nwg2 * 4 + 8) * rec_field_bytes, &p))) return rc;
       A.rec_c = (unsigned *)p;
@@ -1898,26 +1890,22 @@ extern "C" int dazim_fmm_batch(dazim_ctx *ctx, int nx, int ny, float goxd, float
   }
   float *d_rc, *d_rr, *d_veln;
   void *p;
-  if ((rc = dz_scratch(ctx, "fmm.risti_c", rc_tab.size() * 4, &p))) return rc;
-  d_rc = (float *)p;
-  if ((rc = dz_scratch(ctx, "fmm.risti_r", rr_tab.size() * 4, &p))) return rc;
-  d_rr = (float *)p;
+  if ((rc = dz_scratch(ctx, "fmm.risti_c", rc_tab.size(), &d_rc))) return rc;
+  if ((rc = dz_scratch(ctx, "fmm.risti_r", rr_tab.size(), &d_rr))) return rc;
   DZ_HIP(hipMemcpyAsync(d_rc, rc_tab.data(), rc_tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   DZ_HIP(hipMemcpyAsync(d_rr, rr_tab.data(), rr_tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   DZ_HIP(hipStreamSynchronize(ctx->stream));  // the vectors above die at scope exit
   if (veln.dev)
     d_veln = veln.dev;
   else {
-    if ((rc = dz_scratch(ctx, "fmm.veln", nn * kmax * 4, &p))) return rc;
-    d_veln = (float *)p;
+    if ((rc = dz_scratch(ctx, "fmm.veln", nn * kmax, &d_veln))) return rc;
   }
-  if ((rc = dz_scratch(ctx, "fmm.slown", (size_t)tile_records(g.nnx, g.nnz) * kmax * sizeof(float2), &p))) return rc;
-  float2 *d_slown = (float2 *)p;
-  if ((rc = dz_scratch(ctx, "fmm.vflag", 64, &p))) return rc;
-  int *d_vflag = (int *)p;
+  float2 *d_slown;
+  int *d_vflag;
+  if ((rc = dz_scratch(ctx, "fmm.slown", (size_t)tile_records(g.nnx, g.nnz) * kmax, &d_slown)) || (rc = dz_scratch(ctx, "fmm.vflag", 16, &d_vflag))) return rc;
   // the short exact division / square root of the quadrant solve (div_exact): node spacings of 2 .. 4096 km on the coarse grid
   // (0.25 km on the refined one) and, checked by gridder_kernel, velocities of 0.125 .. 16 km/s.  Option fmm.ieee = 1: never.
-  bool fastm = !(ctx->opts.count("fmm.ieee") && ctx->opts["fmm.ieee"]);
+  bool fastm = dz_opt(ctx, "fmm.ieee", 0) == 0;
   {
     const float u1 = fabsf(EARTH * g.dnx);
     if (!(u1 >= FAST_STEP_MIN && u1 <= FAST_STEP_MAX)) fastm = false;
@@ -1960,31 +1948,29 @@ extern "C" int dazim_fmm_batch(dazim_ctx *ctx, int nx, int ny, float goxd, float
     A0.boxes = boxes.dev;
     int *d_status = status.dev;
     if (!d_status) {
-      if ((rc = dz_scratch(ctx, "fmm.status", (size_t)nfield * 4, &p))) return rc;
-      d_status = (int *)p;
+      if ((rc = dz_scratch(ctx, "fmm.status", (size_t)nfield, &d_status))) return rc;
     }
     // Option fmm.async: return once the launch is enqueued (see dazim_ctx::fmm_finish).  Only when nothing of this call waits for
     // the launch on the host: the coarse fields stay inside the library (ttn == NULL) and every array is device-resident.
-    const bool async = ctx->opts.count("fmm.async") && ctx->opts["fmm.async"] && !ttn_u && !pv.staged && !scx.staged && !scz.staged &&
+    const bool async = dz_opt(ctx, "fmm.async", 0) != 0 && !ttn_u && !pv.staged && !scx.staged && !scz.staged &&
                        !period.staged && !veln.staged && !ttnr.staged && !nstsr.staged && !boxes.staged && !status.staged &&
                        ttnr.dev && nstsr.dev && boxes.dev;
     A0.fdone = nullptr;
     if (async) {
-      if ((rc = dz_scratch(ctx, "fmm.fdone", (size_t)nfield * 4 + 16, &p))) return rc;
-      A0.fdone = (int *)p;
+      if ((rc = dz_scratch(ctx, "fmm.fdone", (size_t)nfield + 4, &A0.fdone))) return rc;
     }
     // LDS heap slots per field: the narrow band of an N x M grid peaks near 3*max(N,M) entries (and the
     // 129 x 129 refined grid near 400); the smallest instantiation above that maximises the number of
     // fields in flight per CU.  A field whose band still outgrows it is redone by the spill kernel.
     int cap = 3 * (g.nnx > g.nnz ? g.nnx : g.nnz);
     if (cap < 3 * RM) cap = 3 * RM;
-    if (ctx->opts.count("fmm.cap") && ctx->opts["fmm.cap"] > 0) cap = ctx->opts["fmm.cap"];
+    if (dz_opt(ctx, "fmm.cap", 0) > 0) cap = dz_opt(ctx, "fmm.cap", 0);
     auto hsp = std::make_shared<std::vector<int>>(nfield);
     std::function<int()> fin;
     const bool small = g.nnx <= 256 && g.nnz <= 256;   // node id fits 16 bits
     bool use_hyb512 = cap > 512 && nfield > ctx->num_cu * 8 * FPW;
-    if (ctx->opts.count("fmm.hyb512") && ctx->opts["fmm.hyb512"] == 1) use_hyb512 = true;
-    if (ctx->opts.count("fmm.hyb512") && ctx->opts["fmm.hyb512"] == 2) use_hyb512 = false;
+    if (dz_opt(ctx, "fmm.hyb512", 0) == 1) use_hyb512 = true;
+    if (dz_opt(ctx, "fmm.hyb512", 0) == 2) use_hyb512 = false;
     // (fmm.no_hybrid = 1 or an explicit fmm.cap: the one-level hybrid / all-LDS heaps of the branches below)
     // The small-LDS forms trade latency for wavefronts: a batch that leaves the chip half empty anyway (fewer than 2.5 workgroups
     // per CU) marches faster on the heaps with more levels in LDS -- 1 600 fields: 511 x 511 nodes 0.60 against 0.71 s, 341 x 341
@@ -1992,13 +1978,13 @@ extern "C" int dazim_fmm_batch(dazim_ctx *ctx, int nx, int ny, float goxd, float
     // unless the bands would outgrow those (grids above 768 nodes a side: the all-LDS 2048-slot heap hands them to the spill kernel).
     // fmm.hyb2 = 1 / 2 forces the small-LDS forms on / off.
     bool use_hyb2 = cap > 768 && ((long)nfield > (long)ctx->num_cu * 10 || cap > 2304);
-    if (ctx->opts.count("fmm.hyb2") && ctx->opts["fmm.hyb2"] == 1) use_hyb2 = cap > 768;
-    if (ctx->opts.count("fmm.hyb2") && ctx->opts["fmm.hyb2"] == 2) use_hyb2 = false;
-    if ((ctx->opts.count("fmm.no_hybrid") && ctx->opts["fmm.no_hybrid"]) || (ctx->opts.count("fmm.cap") && ctx->opts["fmm.cap"] > 0)) use_hyb2 = false;
+    if (dz_opt(ctx, "fmm.hyb2", 0) == 1) use_hyb2 = cap > 768;
+    if (dz_opt(ctx, "fmm.hyb2", 0) == 2) use_hyb2 = false;
+    if (dz_opt(ctx, "fmm.no_hybrid", 0) != 0 || dz_opt(ctx, "fmm.cap", 0) > 0) use_hyb2 = false;
     // Eight fields per wavefront (8 lanes per field, two quadrants per lane; round 4, option fmm.gp8): 1 = on the heaps the batch
     // would take anyway (512 LDS slots, all-LDS up to 170-node grids, + one HBM level up to 256), 2 = 255 LDS slots + two HBM
     // levels (1.5 KB of LDS per field).  Grids with 16-bit node ids only.  Measurements: DESIGN.md section 4.
-    const int gp8 = ctx->opts.count("fmm.gp8") ? ctx->opts["fmm.gp8"] : 0;
+    const int gp8 = dz_opt(ctx, "fmm.gp8", 0);
     if (gp8 && small && cap <= 768) {
       if (gp8 == 2) rc = run_fmm<256, unsigned short, true, 8>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
       else if (cap <= 512) rc = run_fmm<512, unsigned short, false, 8>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
@@ -2020,7 +2006,7 @@ extern "C" int dazim_fmm_batch(dazim_ctx *ctx, int nx, int ny, float goxd, float
     else if (cap <= 2048 && use_hyb2) rc = run_fmm<512, int, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
     else if (cap <= 1024) rc = run_fmm<1024, int>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
     // (fmm.hyb2 = 2) grids of 342 .. 682 nodes a side: levels 1-10 in LDS + levels 11 (and, never reached there, 12) in HBM
-    else if (cap <= 2048 && !(ctx->opts.count("fmm.no_hybrid") && ctx->opts["fmm.no_hybrid"])) rc = run_fmm<1024, int, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
+    else if (cap <= 2048 && dz_opt(ctx, "fmm.no_hybrid", 0) == 0) rc = run_fmm<1024, int, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
     // grids above 682 nodes a side: levels 1-10 in LDS, 11 and 12 in HBM (bands up to 4 095 entries = 1 365 nodes a side without
     // the spill kernel, five workgroups per CU instead of the two of the all-LDS 2048-slot heap)
     else if (use_hyb2) rc = run_fmm<1024, int, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);

@@ -832,7 +832,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
 
 }  // namespace
 
-struct dazim_csr;  // sparse.hip
+struct dazim_csr;  // sparse_internal.h
 extern "C" int dazim_csr_adopt(dazim_ctx *ctx, int64_t m, int64_t n, int64_t nnz, int64_t *rowptr, int *col,
                                float *val, dazim_csr **out);
 
@@ -848,7 +848,7 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   // map mode (dazim_rays_build_G_maps): no model, no depth kernels; nz = 2 stands for the one "layer" of a map
   const bool joint = map ? azim : lsen_u != nullptr;
   if (map) nz = 2;
-  if (map && ctx->opts.count("rays.dense_twin") && ctx->opts["rays.dense_twin"])
+  if (map && dz_opt(ctx, "rays.dense_twin", 0) != 0)
     return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G_maps: option rays.dense_twin serves the 3-D program's diagnostics only");
   dazim_geom g;
   if (dazim_geometry(nx, ny, goxd, gozd, dvxd, dvzd, &g)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad grid");
@@ -958,13 +958,13 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
     for (unsigned c = 0; c < 65536u; c++)   // (cell ids are 16-bit: the identity is checked for all of them, once per call)
       if ((unsigned)(((unsigned long long)c * A.nvx_magic) >> 32) != c / d) return dz_fail(ctx, DAZIM_E_BAD_ARG, "internal: reciprocal of nvx");
   }
-  if (!map && !(ctx->opts.count("rays.skern") && !ctx->opts["rays.skern"])) {   // (option rays.skern = 0: every entry from the three kernels)
-    void *pk;
-    if ((rc = dz_scratch(ctx, "rays.skern", nk * sizeof(double), &pk))) return rc;
+  if (!map && dz_opt(ctx, "rays.skern", 1) != 0) {   // (option rays.skern = 0: every entry from the three kernels)
+    double *pk;
+    if ((rc = dz_scratch(ctx, "rays.skern", nk, &pk))) return rc;
     hipLaunchKernelGGL(k_row_kernels, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, (long)nk, kmax, (long)ncol,
-                       vels.dev, svs.dev, svp.dev, srho.dev, (double *)pk);
+                       vels.dev, svs.dev, svp.dev, srho.dev, pk);
     DZ_HIP(hipGetLastError());
-    A.skern = (const double *)pk;
+    A.skern = pk;
   }
   {  // dpl, inv/CalSurfG.f90:1829-1833 (host libm sin, geometry only)
     float dpl = g.dnx * EARTH;
@@ -985,48 +985,38 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   void *p;
   const int64_t m = nray;
   const size_t nr1 = (size_t)(nray > 0 ? nray : 1);
-  if ((rc = dz_scratch(ctx, "rays.status", nr1 * 4, &p))) return rc;
-  A.status = (int *)p;
-  if ((rc = dz_scratch(ctx, "rays.rb", nr1 * 4, &p))) return rc;
-  A.rbflag = (int *)p;
-  if ((rc = dz_scratch(ctx, "rays.count", (size_t)(m + 1) * 8, &p))) return rc;
-  A.count = (long *)p;
+  if ((rc = dz_scratch(ctx, "rays.status", nr1, &A.status))) return rc;
+  if ((rc = dz_scratch(ctx, "rays.rb", nr1, &A.rbflag))) return rc;
+  if ((rc = dz_scratch(ctx, "rays.count", (size_t)(m + 1), &A.count))) return rc;
   // LDS cell lists: 512 entries keep 16 wavefronts (128 rays) on a CU, which is worth 25 % on the S-256 grid where longer lists
   // are rare; large inversion grids (S-512: rays cross > 100 cells) get 1024.  Longer lists fall back to a full-grid sweep.
   A.lcap = g.nvx * g.nvz <= 4096 ? 512 : 1024;
-  if (ctx->opts.count("rays.lcap") && ctx->opts["rays.lcap"] >= 16 && ctx->opts["rays.lcap"] <= 8192)   // tuning / test knob: small
-    A.lcap = ctx->opts["rays.lcap"];                                                                      // values force the fallbacks
+  if (dz_opt(ctx, "rays.lcap", 0) >= 16 && dz_opt(ctx, "rays.lcap", 0) <= 8192) A.lcap = dz_opt(ctx, "rays.lcap", 0);   // tuning / test knob: small values force the fallbacks
   if (A.lcap > g.nvx * g.nvz) A.lcap = g.nvx * g.nvz;
   A.LK = A.lcap;   // cell lists handed from the count pass to the emit pass (longer ones are traced again)
-  A.keep_small = ctx->opts.count("rays.keep_small") && ctx->opts["rays.keep_small"] ? 1 : 0;
+  A.keep_small = dz_opt(ctx, "rays.keep_small", 0) != 0 ? 1 : 0;
   A.pts = nullptr;
   A.npts = nullptr;
   A.pcap = 0;
-  if (ctx->opts.count("rays.keep_paths") && ctx->opts["rays.keep_paths"]) {
+  if (dz_opt(ctx, "rays.keep_paths", 0) != 0) {
     // a ray advances half a cell per step: a few times (nnx + nnz) points even for a path that wanders; longer ones are flagged
     A.pcap = 4 * (g.nnx + g.nnz) + 16;
-    if ((rc = dz_scratch(ctx, "rays.pts", nr1 * (size_t)A.pcap * sizeof(float2), &p))) return rc;
-    A.pts = (float2 *)p;
-    if ((rc = dz_scratch(ctx, "rays.npts", nr1 * 4, &p))) return rc;
-    A.npts = (int *)p;
+    if ((rc = dz_scratch(ctx, "rays.pts", nr1 * (size_t)A.pcap, &A.pts))) return rc;
+    if ((rc = dz_scratch(ctx, "rays.npts", nr1, &A.npts))) return rc;
     DZ_HIP(hipMemsetAsync(A.npts, 0, nr1 * 4, ctx->stream));
   }
   ctx->ksec["rays.path_cap"] = A.pcap;
   ctx->ksec["rays.path_rays"] = A.pts ? (double)nray : 0.0;
-  const bool twin = ctx->opts.count("rays.dense_twin") && ctx->opts["rays.dense_twin"] && !A.keep_small;
+  const bool twin = dz_opt(ctx, "rays.dense_twin", 0) != 0 && !A.keep_small;
   A.dense = twin ? 2 : 0;
   A.countd = nullptr;
   if (twin) {
-    if ((rc = dz_scratch(ctx, "rays.countd", (size_t)(m + 1) * 8, &p))) return rc;
-    A.countd = (long *)p;
+    if ((rc = dz_scratch(ctx, "rays.countd", (size_t)(m + 1), &A.countd))) return rc;
     DZ_HIP(hipMemsetAsync(A.countd, 0, (size_t)(m + 1) * 8, ctx->stream));
   }
-  if ((rc = dz_scratch(ctx, "rays.nlist", nr1 * 4, &p))) return rc;
-  A.nlist = (int *)p;
-  if ((rc = dz_scratch(ctx, "rays.lcell", nr1 * A.LK * 2, &p))) return rc;
-  A.lcell = (unsigned short *)p;
-  if ((rc = dz_scratch(ctx, "rays.lval", nr1 * A.LK * 4 * (joint ? 3 : 1), &p))) return rc;
-  A.lval = (float *)p;
+  if ((rc = dz_scratch(ctx, "rays.nlist", nr1, &A.nlist))) return rc;
+  if ((rc = dz_scratch(ctx, "rays.lcell", nr1 * A.LK, &A.lcell))) return rc;
+  if ((rc = dz_scratch(ctx, "rays.lval", nr1 * A.LK * (joint ? 3 : 1), &A.lval))) return rc;
   int64_t *rowptr = nullptr;
   float *val = nullptr;
   int *col = nullptr;
@@ -1035,9 +1025,9 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   // By default: one regularisation row per model parameter with the 7-point stencil of inv/TikhRegul.f90 (a few MB).
   // (map mode: the 5-point stencil of dazim_csr_append_laplacian2d on every map)
   int64_t res_rows = (int64_t)g.nvx * g.nvz * (map ? kmax : nz - 1) * (joint ? 3 : 1), res_nnz = (map ? 5 : 7) * res_rows;
-  if (ctx->opts.count("csr.reserve_rows") && ctx->opts["csr.reserve_rows"] > res_rows) res_rows = ctx->opts["csr.reserve_rows"];
-  if (ctx->opts.count("csr.reserve_nnz") && ctx->opts["csr.reserve_nnz"] > res_nnz) res_nnz = ctx->opts["csr.reserve_nnz"];
-  { void *pp; if ((rc = dz_big_get(ctx, (size_t)(m + res_rows + 1) * 8, &pp))) return rc; rowptr = (int64_t *)pp; }
+  if (dz_opt(ctx, "csr.reserve_rows", 0) > res_rows) res_rows = dz_opt(ctx, "csr.reserve_rows", 0);
+  if (dz_opt(ctx, "csr.reserve_nnz", 0) > res_nnz) res_nnz = dz_opt(ctx, "csr.reserve_nnz", 0);
+  if ((rc = dz_big_get(ctx, (size_t)(m + res_rows + 1), &rowptr))) return rc;
   struct Arrays {   // the matrix arrays go back to the cache on every early return (until the matrix has adopted them)
     dazim_ctx *c; int64_t *&rp; float *&v; int *&cl; bool keep = false;
     ~Arrays() { if (!keep) { dz_big_put(c, rp); dz_big_put(c, v); dz_big_put(c, cl); } }
@@ -1077,22 +1067,21 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   }
   if (per_cu > 16) per_cu = 16;
   if (per_cu < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "inversion grid too large for the LDS cell lists");
-  if (ctx->opts.count("rays.wg_per_cu") && ctx->opts["rays.wg_per_cu"] > 0 && ctx->opts["rays.wg_per_cu"] < per_cu) per_cu = ctx->opts["rays.wg_per_cu"];
+  if (dz_opt(ctx, "rays.wg_per_cu", 0) > 0 && dz_opt(ctx, "rays.wg_per_cu", 0) < per_cu) per_cu = dz_opt(ctx, "rays.wg_per_cu", 0);
   long nwg = (long)ctx->num_cu * per_cu;
   if (nwg > (nray + RPW_MAX - 1) / RPW_MAX) nwg = (nray + RPW_MAX - 1) / RPW_MAX;
   if (nwg >= 8) nwg -= nwg % 8;   // the XCD-aware ray order wants a multiple of 8
   if (nwg < 1) nwg = 1;
-  if ((rc = dz_scratch(ctx, "rays.fdm", (size_t)nwg * RPW_MAX * (g.nvx + 2) * (g.nvz + 2) * 4 * (joint ? 3 : 1), &p))) return rc;
-  A.fdm_scratch = (float *)p;
+  if ((rc = dz_scratch(ctx, "rays.fdm", (size_t)nwg * RPW_MAX * (g.nvx + 2) * (g.nvz + 2) * (joint ? 3 : 1), &A.fdm_scratch))) return rc;
   A.perm = nullptr;
-  if (nray >= 64 && nray < (1ll << 32) && !(ctx->opts.count("rays.sort") && !ctx->opts["rays.sort"])) {
+  if (nray >= 64 && nray < (1ll << 32) && dz_opt(ctx, "rays.sort", 1) != 0) {
     int fbits = 1;
     while ((1ll << fbits) < nfield) fbits++;
     const int dbits = 32 - fbits > 12 ? 12 : 32 - fbits;
     if (dbits >= 4) {
       unsigned *k0, *k1, *v0, *v1;
-      if ((rc = dz_scratch(ctx, "rays.sortbuf", (size_t)nray * 16 + 64, &p))) return rc;
-      k0 = (unsigned *)p; k1 = k0 + nray; v0 = k1 + nray; v1 = v0 + nray;
+      if ((rc = dz_scratch(ctx, "rays.sortbuf", (size_t)nray * 4 + 16, &k0))) return rc;
+      k1 = k0 + nray; v0 = k1 + nray; v1 = v0 + nray;
       const float ex = (float)g.nnx * g.dnx, ez = (float)g.nnz * g.dnz;
       const float inv_dmax = 1.0f / sqrtf(ex * ex + ez * ez);
       hipLaunchKernelGGL(k_ray_keys, dim3((unsigned)((nray + 255) / 256)), dim3(256), 0, ctx->stream, (long)nray, field.dev, scx.dev,
@@ -1105,15 +1094,13 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
       A.perm = v1;
     }
   }
-  if ((rc = dz_scratch(ctx, "rays.qcount", 128, &p))) return rc;
-  A.qcount = (unsigned *)p;
+  if ((rc = dz_scratch(ctx, "rays.qcount", 32, &A.qcount))) return rc;
   DZ_HIP(hipMemsetAsync(A.qcount, 0, 128, ctx->stream));
   int64_t nnz = 0;
   double overlap_tail_s = 0.0;
   if (overlap) {
     const size_t nq = (size_t)((nray + RPW_MAX - 1) / RPW_MAX) + 8;
-    if ((rc = dz_scratch(ctx, "rays.defer", nq * 4, &p))) return rc;
-    A.defer_mark = (int *)p;
+    if ((rc = dz_scratch(ctx, "rays.defer", nq, &A.defer_mark))) return rc;
     DZ_HIP(hipMemsetAsync(A.defer_mark, 0, nq * 4, ctx->stream));
   }
   DzTimer t(ctx, "rays");
@@ -1205,8 +1192,7 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
     DZ_HIP(hipStreamSynchronize(ctx->stream));
   }
   const int64_t cap_nnz = nnz + res_nnz;   // (options csr.reserve_rows / csr.reserve_nnz: room for rows appended later)
-  { void *pp; if ((rc = dz_big_get(ctx, (size_t)(cap_nnz > 0 ? cap_nnz : 1) * 4, &pp))) return rc; val = (float *)pp; }
-  { void *pp; if ((rc = dz_big_get(ctx, (size_t)(cap_nnz > 0 ? cap_nnz : 1) * 4, &pp))) return rc; col = (int *)pp; }
+  if ((rc = dz_big_get(ctx, (size_t)(cap_nnz > 0 ? cap_nnz : 1), &val)) || (rc = dz_big_get(ctx, (size_t)(cap_nnz > 0 ? cap_nnz : 1), &col))) return rc;
   A.val = val;
   A.col = col;
   if (nray > 0 && (rc = launch(true, A, nwg))) return rc;
@@ -1217,15 +1203,14 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
   Arrays arrays_d{ctx, rowptr_d, val_d, col_d};
   int64_t nnz_d = 0;
   if (twin) {
-    { void *pp; if ((rc = dz_big_get(ctx, (size_t)(m + 1) * 8, &pp))) return rc; rowptr_d = (int64_t *)pp; }
+    if ((rc = dz_big_get(ctx, (size_t)(m + 1), &rowptr_d))) return rc;
     size_t tb = 0;
     DZ_HIP(rocprim::exclusive_scan(nullptr, tb, A.countd, (long *)rowptr_d, 0l, (size_t)(m + 1), rocprim::plus<long>(), ctx->stream));
     if ((rc = dz_scratch(ctx, "rays.scan", tb + 256, &p))) return rc;
     DZ_HIP(rocprim::exclusive_scan(p, tb, A.countd, (long *)rowptr_d, 0l, (size_t)(m + 1), rocprim::plus<long>(), ctx->stream));
     DZ_HIP(hipMemcpyAsync(&nnz_d, rowptr_d + m, 8, hipMemcpyDeviceToHost, ctx->stream));
     DZ_HIP(hipStreamSynchronize(ctx->stream));
-    { void *pp; if ((rc = dz_big_get(ctx, (size_t)(nnz_d > 0 ? nnz_d : 1) * 4, &pp))) return rc; val_d = (float *)pp; }
-    { void *pp; if ((rc = dz_big_get(ctx, (size_t)(nnz_d > 0 ? nnz_d : 1) * 4, &pp))) return rc; col_d = (int *)pp; }
+    if ((rc = dz_big_get(ctx, (size_t)(nnz_d > 0 ? nnz_d : 1), &val_d)) || (rc = dz_big_get(ctx, (size_t)(nnz_d > 0 ? nnz_d : 1), &col_d))) return rc;
     RayArgs D = A;
     D.dense = 1;
     D.rowptr = (const long *)rowptr_d;

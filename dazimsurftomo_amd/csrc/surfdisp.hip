@@ -608,12 +608,9 @@ extern "C" int dazim_surfdisp96(dazim_ctx *ctx, int nmodel, int nlayer_max, cons
       (rc = up("sd.cc", f_cc.data(), (size_t)nmodel * 8, (const void **)&S.cc)) ||
       (rc = up("sd.t", periods, (size_t)kmax * 8, (const void **)&S.t)))
     return rc;
-  if ((rc = dz_scratch(ctx, "sd.c", (size_t)nmodel * kmax * 8, &p))) return rc;
-  S.c = (double *)p;
-  if ((rc = dz_scratch(ctx, "sd.cb", (size_t)nmodel * kmax * 8, &p))) return rc;
-  S.cb = (double *)p;
-  if ((rc = dz_scratch(ctx, "sd.nfail", 16, &p))) return rc;
-  S.nfail = (int *)p;
+  if ((rc = dz_scratch(ctx, "sd.c", (size_t)nmodel * kmax, &S.c))) return rc;
+  if ((rc = dz_scratch(ctx, "sd.cb", (size_t)nmodel * kmax, &S.cb))) return rc;
+  if ((rc = dz_scratch(ctx, "sd.nfail", 4, &S.nfail))) return rc;
   DZ_HIP(hipMemsetAsync(S.nfail, 0, 4, ctx->stream));
   DzBuf<double> out;
   if ((rc = out.init(ctx, cg, (size_t)nmodel * kmax, false, true))) return rc;

@@ -542,9 +542,8 @@ extern "C" int dazim_ti_kernels(dazim_ctx *ctx, int nx, int ny, int nz, const fl
   A.vel = vel.dev; A.pv = pv.dev; A.lsen = lsen.dev;
   // one scratch block for the small tables
   const size_t tab_bytes = (size_t)mmax * (2 * sizeof(int) + 4 * sizeof(float) + 3 * sizeof(double)) + kmax * sizeof(float) + 256;
-  void *p;
-  if ((rc = dz_scratch(ctx, "ti.tables", tab_bytes, &p))) return rc;
-  char *base = (char *)p;
+  char *base;
+  if ((rc = dz_scratch(ctx, "ti.tables", tab_bytes, &base))) return rc;
   auto put = [&](const void *src, size_t bytes) -> void * {
     void *dst = base;
     (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream);
@@ -562,17 +561,14 @@ extern "C" int dazim_ti_kernels(dazim_ctx *ctx, int nx, int ny, int nz, const fl
   A.vtp = (const float *)put(vtp.data(), mmax * 4);
   A.twopi_t = (const float *)put(tper.data(), kmax * 4);
   DZ_HIP(hipGetLastError());
-  if ((rc = dz_scratch(ctx, "ti.model64", (size_t)mmax * ncol * 8 * 4, &p))) return rc;
-  A.zta = (double *)p; A.ztl = A.zta + (size_t)mmax * ncol; A.ztf = A.ztl + (size_t)mmax * ncol; A.zrho = A.ztf + (size_t)mmax * ncol;
-  if ((rc = dz_scratch(ctx, "ti.model32", (size_t)mmax * ncol * 4 * 6, &p))) return rc;
-  A.fTA = (float *)p; A.fTL = A.fTA + (size_t)mmax * ncol; A.fTF = A.fTL + (size_t)mmax * ncol;
+  if ((rc = dz_scratch(ctx, "ti.model64", (size_t)mmax * ncol * 4, &A.zta))) return rc;
+  A.ztl = A.zta + (size_t)mmax * ncol; A.ztf = A.ztl + (size_t)mmax * ncol; A.zrho = A.ztf + (size_t)mmax * ncol;
+  if ((rc = dz_scratch(ctx, "ti.model32", (size_t)mmax * ncol * 6, &A.fTA))) return rc;
+  A.fTL = A.fTA + (size_t)mmax * ncol; A.fTF = A.fTL + (size_t)mmax * ncol;
   A.frho = A.fTF + (size_t)mmax * ncol; A.fvp = A.frho + (size_t)mmax * ncol; A.fvs = A.fvp + (size_t)mmax * ncol;
-  if ((rc = dz_scratch(ctx, "ti.up", (size_t)mmax * 6 * nlane * 8, &p))) return rc;
-  A.upv = (double *)p;
-  if ((rc = dz_scratch(ctx, "ti.prt", (size_t)mmax * 4 * nlane * 8, &p))) return rc;
-  A.prt = (double *)p;
-  if ((rc = dz_scratch(ctx, "ti.bad", 16, &p))) return rc;
-  A.bad = (int *)p;
+  if ((rc = dz_scratch(ctx, "ti.up", (size_t)mmax * 6 * nlane, &A.upv))) return rc;
+  if ((rc = dz_scratch(ctx, "ti.prt", (size_t)mmax * 4 * nlane, &A.prt))) return rc;
+  if ((rc = dz_scratch(ctx, "ti.bad", 4, &A.bad))) return rc;
   DZ_HIP(hipMemsetAsync(A.bad, 0, 4, ctx->stream));
   DZ_HIP(hipStreamSynchronize(ctx->stream));   // host tables go out of scope after the launches are queued; keep it simple
   {

@@ -191,7 +191,7 @@ def lsmr_distributed(ops, b_local, n, damp, atol, btol, conlim, itnlim, localSiz
         itn += 1
         u.mul_(float(-alpha))
         ops.aprod1(v, u)                              # u = A_p v - alpha u   (local rows only)
-        # ONE collective per iteration, as in the library (sparse.hip, k_local_norm_scal): the shard is scaled by its own norm,
+        # ONE collective per iteration, as in the library (lsmr.hip, k_local_norm_scal): the shard is scaled by its own norm,
         # w_p = beta_p A_p^T (u_p / beta_p), and the n values of w travel with beta_p^2 in one all-reduce
         bp2 = (u.double() ** 2).sum().reshape(1)      # local ||u_p||^2, stays on the device
         bp = torch.sqrt(bp2).to(f32)
