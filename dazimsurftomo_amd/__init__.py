@@ -433,15 +433,23 @@ class Context:
         self._check(self.lib.dazim_aprod(self._h, int(mode), A._h, _ptr(x, np.float32), _ptr(y, np.float32)))
 
     # ---- N4: what surrounds the solve in the outer iteration -----------------------------------------
-    def weight_data(self, G, obst, dsyn):
+    def weight_data(self, G, obst, dsyn, row0=None, dall_glob=None):
         """residual, CalDdatSigma weights (inv/CalSigamNorm.f90:2), weighted right-hand side; scales the data rows of G (nullable).
-        numpy in -> (res, datweight, rhs, stats dict)"""
+        numpy in -> (res, datweight, rhs, stats dict)
+        row0, dall_glob: dazim_weight_data_sharded -- obst, dsyn are this rank's data rows [row0, row0 + len(obst)) of dall_glob;
+        with a communicator attached meandeltaT / stddeltaT and the statistics are those of all data (every rank must call)."""
         obst = np.ascontiguousarray(obst, np.float32); dsyn = np.ascontiguousarray(dsyn, np.float32)
         n = len(obst)
         res, wgt, rhs = (np.zeros(n, np.float32) for _ in range(3))
         st = np.zeros(8, np.float32)
-        self._check(self.lib.dazim_weight_data(self._h, G._h if G is not None else None, C.c_int64(n), _ptr(obst), _ptr(dsyn),
-                                               _ptr(res), _ptr(wgt), _ptr(rhs), _ptr(st)))
+        gh = G._h if G is not None else None
+        if row0 is None and dall_glob is None:
+            self._check(self.lib.dazim_weight_data(self._h, gh, C.c_int64(n), _ptr(obst), _ptr(dsyn),
+                                                   _ptr(res), _ptr(wgt), _ptr(rhs), _ptr(st)))
+        else:
+            self._check(self.lib.dazim_weight_data_sharded(self._h, gh, C.c_int64(n), C.c_int64(int(row0 or 0)),
+                                                           C.c_int64(n if dall_glob is None else int(dall_glob)), _ptr(obst),
+                                                           _ptr(dsyn), _ptr(res), _ptr(wgt), _ptr(rhs), _ptr(st)))
         keys = ("mean", "std", "mean_abs", "rms", "meandeltaT", "stddeltaT", "mean_weight", "mean_abs_weighted")
         return res, wgt, rhs, dict(zip(keys, map(float, st)))
 
@@ -588,6 +596,16 @@ class SparseMatrix:
         self.ctx._check(self.ctx.lib.dazim_csr_dims(self._h, C.byref(m0), None, C.byref(z0)))
         self.m, self.nnz = m0.value, z0.value
 
+    def append_tikhonov_rows(self, nx, ny, nz, weights, row_lo, row_hi):
+        """rows [row_lo, row_hi) of the len(weights) * (nx-2)(ny-2)(nz-1) rows of append_tikhonov (dazim_csr_append_tikhonov_rows):
+        the share of one rank of a row-sharded system"""
+        w = np.ascontiguousarray(weights, np.float32)
+        m0, z0 = C.c_int64(0), C.c_int64(0)
+        self.ctx._check(self.ctx.lib.dazim_csr_append_tikhonov_rows(self.ctx._h, self._h, nx, ny, nz, len(w), _ptr(w),
+                                                                    C.c_int64(row_lo), C.c_int64(row_hi)))
+        self.ctx._check(self.ctx.lib.dazim_csr_dims(self._h, C.byref(m0), None, C.byref(z0)))
+        self.m, self.nnz = m0.value, z0.value
+
     def append_laplacian2d(self, nx, ny, weights):
         """2-D regularisation rows of the per-period maps generated on the device (dazim_csr_append_laplacian2d): one block of
         (nx-2)(ny-2) rows per weight, map b regularising columns b*ncell .."""
@@ -616,6 +634,12 @@ class SparseMatrix:
         m0, z0 = C.c_int64(0), C.c_int64(0)
         self.ctx._check(self.ctx.lib.dazim_csr_dims(h, C.byref(m0), None, C.byref(z0)))
         return SparseMatrix(self.ctx, h, m0.value, self.n, z0.value)
+
+    def col_abs_sums(self):
+        """DWS, norm(col) = sum |rw| over the column's entries (inv/Main_Jt.f90:477-481, dazim_csr_col_abs_sums) -> fp32 [n]"""
+        out = np.zeros(self.n, np.float32)
+        self.ctx._check(self.ctx.lib.dazim_csr_col_abs_sums(self.ctx._h, self._h, _ptr(out)))
+        return out
 
     def to_coo(self):
         irow = np.zeros(self.nnz, np.int32); icol = np.zeros(self.nnz, np.int32); rw = np.zeros(self.nnz, np.float32)
