@@ -71,7 +71,7 @@ struct dazim_ctx {
   // is enqueued, and the dazim_rays_build_G* call that follows runs its count pass on a third stream as non-blocking passes over
   // the quads of rays whose fields' completion flags are set -- its workgroups are dispatched as the eikonal launch's persistent
   // workgroups leave: the ray kernel fills the TAIL of the eikonal launch (profiles/r6_tail_fill.md).  fmm_finish = what the
-  // eikonal call still owes (statuses, spill reruns, timers); run by the ray call, by dazim_sync / dazim_free / a copy / the next
+  // eikonal call still owes (FmmBatch::finish of fmm.hip; the closure holds the batch); run by the ray call, by dazim_sync / dazim_free / a copy / the next
   // eikonal or dispersion call, whichever comes first (dz_fmm_finish).
   std::function<int()> fmm_finish;
   unsigned *hprog = nullptr;           // pinned, device-visible: 8 progress words of an asynchronous eikonal launch (dz_async_init)
@@ -131,9 +131,10 @@ int dz_join_aux_if_touched(dazim_ctx *ctx, const void *dev, size_t bytes);   // 
                      hipGetErrorString(e_));                                                   \
   } while (0)
 
-// The eikonal kernel's 4 x 4-tile layout of a grid (fmm.hip: tile_shift / tile_x / tile_z, which these restate for the ray kernel):
-// node (x0, z0), 0-based, is word dz_tile_x(x0, tsh) + dz_tile_z(z0), tsh = dz_tile_shift(nnz)
+// The eikonal kernel's 4 x 4-tile layout of a grid (described in fmm.hip; the ray kernel reads the finished fields through it):
+// node (x0, z0), 0-based, is word dz_tile_x(x0, tsh) + dz_tile_z(z0), tsh = dz_tile_shift(nnz); a field takes dz_tile_records words
 __host__ __device__ constexpr int dz_tile_shift(int nz) { int l = 0; while ((1 << l) < ((nz + 3) >> 2)) l++; return l + 4; }
+__host__ __device__ constexpr int dz_tile_records(int nx, int nz) { return ((nx + 3) >> 2) << dz_tile_shift(nz); }
 __host__ __device__ __forceinline__ constexpr int dz_tile_x(int x0, int tsh) { return ((x0 >> 2) << tsh) + ((x0 & 3) << 2); }
 __host__ __device__ __forceinline__ constexpr int dz_tile_z(int z0) { return ((z0 & ~3) << 2) | (z0 & 3); }
 

@@ -31,7 +31,7 @@ constexpr float EARTH = 6371.0f;
 
 struct __align__(8) HEnt {
   float key;
-  int node;  // index of the node's record in the tiled layout (tile_x + tile_z below; the reference keeps int16 px,pz: inv/CalSurfG.f90:238)
+  int node;  // index of the node's record in the tiled layout (dz_tile_x + dz_tile_z; the reference keeps int16 px,pz: inv/CalSurfG.f90:238)
 };
 
 // Node word (round 3): ONE 32-bit word per node instead of the reference's {time, status} pair.  An alive node holds its time
@@ -79,10 +79,10 @@ struct FmmArgs {
   int ovfcap;
   unsigned *counter;     // [0..7] the XCD ranges' queue positions; [16..17] (as one 64-bit word) nodes accepted by the launch
   const int *flist;  // nullable: indirection used by the spill rerun
-  int prio;          // 1: the wavefronts raise their issue priority (small batches beside the dispersion copies, see run_fmm)
+  int prio;          // 1: the wavefronts raise their issue priority (small batches beside the dispersion copies, see FmmBatch::plan)
   int fastm;         // grid steps within the range in which the short exact division / square root may run (see div_exact)
   const int *vflag;  // [1] set by gridder_kernel when a phase velocity lies outside that range
-  int fpw;           // fields a wavefront takes per batch (1, 2 or FPW = 4 of its 16-lane groups are active): see run_fmm
+  int fpw;           // fields a wavefront takes per batch (1, 2 or FPW = 4 of its 16-lane groups are active): see FmmBatch::plan
   // time slicing (see fmm_kernel): a field is marched in ts_nstage tasks -- stage 0 = refined march + injection, stages 1.. =
   // ts_pops accepted nodes of the coarse march each (the last one: to the end) -- that may run on different workgroups
   int ts_nstage;     // 1: the whole field in one task (rec_c / ovf are per resident slot); > 1: rec_c / ovf / the arrays below per field
@@ -105,25 +105,16 @@ __device__ __forceinline__ void bspl4(float u, float w[4]) {
 }
 
 // Node words live in HBM in 4 x 4 tiles (16 words of 4 bytes, see w_alive: two z-neighbouring tiles per 128-byte line): node
-// (ix0, iz0), 0-based, of a grid
-// with ntz tiles per column of tiles (ceil(nz/4) rounded up to a power of two) is record
+// (ix0, iz0), 0-based, of a grid with ntz tiles per column of tiles (ceil(nz/4) rounded up to a power of two) is record
 // ((ix0>>2)*ntz + (iz0>>2))*16 + (ix0&3)*4 + (iz0&3).  The stencil of a pop reaches +-3 nodes in both directions: in the
 // reference's column-major order that is 7 columns = 7-8 lines, tiled it is 4-6.  The two coordinates contribute separately, so
 // the five addresses of a lane cost three X and three Z parts.  That record index is also the node's name in the heap (16 bits
 // on grids up to 256 x 256, 32 bits otherwise): entries that move need no decoding to find their record, and only the root of a
-// pop is turned back into coordinates (rid_x0 / rid_z0).  tsh = log2 of the record stride between columns of tiles.
-__host__ __device__ constexpr int tile_shift(int nz) { int l = 0; while ((1 << l) < ((nz + 3) >> 2)) l++; return l + 4; }
-__host__ __device__ constexpr int tile_stride(int nz) { return 1 << tile_shift(nz); }
-__host__ __device__ constexpr int tile_records(int nx, int nz) { return ((nx + 3) >> 2) * tile_stride(nz); }
-__host__ __device__ __forceinline__ constexpr int tile_x(int x0, int tsh) { return ((x0 >> 2) << tsh) + ((x0 & 3) << 2); }
-__host__ __device__ __forceinline__ constexpr int tile_z(int z0) { return ((z0 & ~3) << 2) | (z0 & 3); }
+// pop is turned back into coordinates (rid_x0 / rid_z0).  tsh = log2 of the record stride between columns of tiles.  (dz_tile_*: dazim_internal.h)
 __device__ __forceinline__ int rid_x0(int rid, int tsh) { return ((rid >> tsh) << 2) | ((rid >> 2) & 3); }
 __device__ __forceinline__ int rid_z0(int rid, int tsh) { return (((rid & ((1 << tsh) - 1)) >> 4) << 2) | (rid & 3); }
-static_assert(tile_shift(256) == dz_tile_shift(256) && tile_shift(511) == dz_tile_shift(511) && tile_shift(71) == dz_tile_shift(71) &&
-              tile_x(37, 10) == dz_tile_x(37, 10) && tile_x(510, 11) == dz_tile_x(510, 11) && tile_z(37) == dz_tile_z(37) &&
-              tile_z(510) == dz_tile_z(510), "dazim_internal.h restates this layout for the ray kernel");
-constexpr int TSH_R = tile_shift(DAZIM_RMAX);                       // refined grid: 33 tiles per column of tiles, stride 64 tiles
-constexpr int NREC_R = tile_records(DAZIM_RMAX, DAZIM_RMAX);        // 33 792 record slots per refined field
+constexpr int TSH_R = dz_tile_shift(DAZIM_RMAX);                       // refined grid: 33 tiles per column of tiles, stride 64 tiles
+constexpr int NREC_R = dz_tile_records(DAZIM_RMAX, DAZIM_RMAX);        // 33 792 record slots per refined field
 
 // ---- gridder: inv/CalSurfG.f90:1423-1516, one thread per propagation node -------------------
 // FAST_V*: the velocities between which fmm_kernel may use the short exact division / square root (div_exact); veln and velnr are
@@ -162,7 +153,7 @@ __global__ void gridder_kernel(dazim_geom g, int kmax, const double *__restrict_
   }
   if (bad) *vflag = 1;
   veln[tid] = sumi;
-  slown[(size_t)k * tile_records(g.nnx, g.nnz) + tile_x(stx - 1, tile_shift(g.nnz)) + tile_z(stz - 1)] = make_float2(1.0f / sumi, risti_c[stx - 1]);   // 4 x 4 tiles
+  slown[(size_t)k * dz_tile_records(g.nnx, g.nnz) + dz_tile_x(stx - 1, dz_tile_shift(g.nnz)) + dz_tile_z(stz - 1)] = make_float2(1.0f / sumi, risti_c[stx - 1]);   // 4 x 4 tiles
 }
 
 // ---- narrow-band heap (addtree/downtree/updtree, inv/CalSurfG.f90:738-891) -------------------
@@ -219,13 +210,13 @@ template <int GPL, int N> __device__ __forceinline__ int own_i(int v) {
 }
 template <int GPL, int N> __device__ __forceinline__ float own_f(float v) { return __int_as_float(own_i<GPL, N>(__float_as_int(v))); }
 
-// LDS layout is structure-of-arrays: fp32 keys + node ids (the node's record index, see tile_x above): NT = unsigned short when
+// LDS layout is structure-of-arrays: fp32 keys + node ids (the node's record index, see dz_tile_x): NT = unsigned short when
 // both grids of a field have at most 65 536 record slots (sides <= 256, the S-256 case: 6 bytes per entry, a third more fields
 // in flight per CU), NT = int otherwise.
 
 // HYB: the upper levels of the heap (slots < CAP, a power of two) live in LDS and are sifted by the parallel routines exactly as in
 // the all-LDS heap; the NH levels below (slots CAP .. (CAP << NH) - 1) live in the HBM array `ovf` and are reached by one
-// sequential step of the sift-down per level, by the owner lanes' direct writes and by rising entries.  Three uses (run_fmm's
+// sequential step of the sift-down per level, by the owner lanes' direct writes and by rising entries.  Three uses (fmm_pick_form's
 // dispatch): 512 slots + one HBM level with 16-bit ids on 171..256-node grids when the batch is large (S-256: a third wavefront
 // per SIMD), 512 slots + TWO HBM levels with 32-bit ids on 257..682-node grids (S-512: ten workgroups per CU; these grids wait
 // on latencies, and twice the wavefronts are worth one or two more dependent memory accesses per pop), 1024 slots + one level
@@ -236,7 +227,7 @@ struct Heap {
   static constexpr int LV = GPL == 16 ? 4 : 3;            // levels per parallel sift-down step: GPL - 1 parent positions
   static constexpr unsigned GMASK = (1u << GPL) - 1u;
   // HBM levels of the hybrid heap: one with 16-bit node ids, two with 32-bit ids (grids of 257..682 nodes a side: levels 1-9 in
-  // LDS, levels 10 and 11 in HBM; above that levels 1-10 in LDS, 11 and 12 in HBM -- see run_fmm's dispatch)
+  // LDS, levels 10 and 11 in HBM; above that levels 1-10 in LDS, 11 and 12 in HBM -- see fmm_pick_form)
   static constexpr int NH = (HYB && (sizeof(NT) == 4 || CAP <= 256)) ? 2 : 1;
   static constexpr int TOT = HYB ? (CAP << NH) : CAP;   // slots the fast kernel can hold before the field is handed to the spill kernel
   // interior-root table of march(): 288 bytes of LDS, which cost no kernel form a workgroup per CU (LDS comes in 1 280-byte granules:
@@ -626,7 +617,7 @@ struct Heap {
 // v_div_scale x 2, v_rcp, the Newton / residual steps below, v_div_fmas, v_div_fixup: the two scale instructions and the fixup only
 // act on operands near the ends of the exponent range (|y| or |x / y| below 2^-126 or above 2^126, |x| < 2^-103), zeros, infinities
 // and NaNs; in between they pass their operands through and the quotient is the one of the FMA steps, which are repeated here as
-// they stand.  run_fmm only lets this form run when the grid's steps and velocities keep every operand within 2^+-30 of one
+// they stand.  dazim_fmm_batch only lets this form run when the grid's steps and velocities keep every operand within 2^+-30 of one
 // (`fast` false: the compiler's sequences).  Division by three: q = RN(x / 3), then one residual step -- equal to x / 3.0f for every
 // finite float (2^32 cases, tools/check_div3.c).  Square root: v_sqrt_f32 is within one ulp; the two residual tests pick the
 // correctly rounded neighbour (the compiler's own sequence minus its rescaling of arguments below 2^-96 and its class test).
@@ -757,8 +748,8 @@ __device__ __forceinline__ bool march(Heap<CAP, SPILL, NT, HYB, GPL> &H, const f
   const bool tab_ok = TAB && nnx >= 8 && nnz >= 8 && tsh <= 14;   // (16-bit table entries: tile strides up to 2^14 records)
   const unsigned XMASK = ~((1u << tsh) - 1u) | 0xCu, ZMASK = ((1u << tsh) - 1u) & ~0xCu;   // the x and z bits of a record index
   // (both parts are monotone in their coordinate: one unsigned range test each; a grid too small to have an interior never passes)
-  const unsigned xlo = tab_ok ? (unsigned)tile_x(3, tsh) : 0xffffffffu, xspan = tab_ok ? (unsigned)tile_x(nnx - 4, tsh) - xlo : 0u;
-  const unsigned zlo = (unsigned)tile_z(3), zspan = tab_ok ? (unsigned)tile_z(nnz - 4) - zlo : 0u;
+  const unsigned xlo = tab_ok ? (unsigned)dz_tile_x(3, tsh) : 0xffffffffu, xspan = tab_ok ? (unsigned)dz_tile_x(nnx - 4, tsh) - xlo : 0u;
+  const unsigned zlo = (unsigned)dz_tile_z(3), zspan = tab_ok ? (unsigned)dz_tile_z(nnz - 4) - zlo : 0u;
   const short *xt = nullptr, *zt = nullptr;
   if constexpr (TAB) {
     short *tab = H.tab;
@@ -768,13 +759,13 @@ __device__ __forceinline__ bool march(Heap<CAP, SPILL, NT, HYB, GPL> &H, const f
       const int c = l >> 2, m = l & 3, d = (c >> 1) - 1, sg = (c & 1) ? 1 : -1;   // class = (dix or diz, jd or kd), residue
       const int c0 = 4 + m, cn = c0 + d;
       if (e < 24) {
-        tab[l] = (short)(tile_x(cn, tsh) - tile_x(c0, tsh));
-        tab[24 + l] = (short)(tile_x(cn + sg, tsh) - tile_x(cn, tsh));
-        tab[48 + l] = (short)(tile_x(cn + 2 * sg, tsh) - tile_x(cn, tsh));
+        tab[l] = (short)(dz_tile_x(cn, tsh) - dz_tile_x(c0, tsh));
+        tab[24 + l] = (short)(dz_tile_x(cn + sg, tsh) - dz_tile_x(cn, tsh));
+        tab[48 + l] = (short)(dz_tile_x(cn + 2 * sg, tsh) - dz_tile_x(cn, tsh));
       } else {
-        tab[72 + l] = (short)(tile_z(cn) - tile_z(c0));
-        tab[96 + l] = (short)(tile_z(cn + sg) - tile_z(cn));
-        tab[120 + l] = (short)(tile_z(cn + 2 * sg) - tile_z(cn));
+        tab[72 + l] = (short)(dz_tile_z(cn) - dz_tile_z(c0));
+        tab[96 + l] = (short)(dz_tile_z(cn + sg) - dz_tile_z(cn));
+        tab[120 + l] = (short)(dz_tile_z(cn + 2 * sg) - dz_tile_z(cn));
       }
     }
     cbar();
@@ -848,8 +839,8 @@ __device__ __forceinline__ bool march(Heap<CAP, SPILL, NT, HYB, GPL> &H, const f
       const bool vk = nvalid && (unsigned)k0 < unz, vk2 = vk && (unsigned)k20 < unz;
       // tiled record indices: an X part per column (neighbour, +-1, +-2) and a Z part per row; out-of-grid coordinates give
       // garbage that the validity flags replace by the root's own record.  Unsigned indices: no sign extension per address.
-      const int xn = tile_x(nx0, tsh), xj = tile_x(j0, tsh), xj2 = tile_x(j20, tsh);
-      const int zn = tile_z(nz0), zk = tile_z(k0), zk2 = tile_z(k20);
+      const int xn = dz_tile_x(nx0, tsh), xj = dz_tile_x(j0, tsh), xj2 = dz_tile_x(j20, tsh);
+      const int zn = dz_tile_z(nz0), zk = dz_tile_z(k0), zk2 = dz_tile_z(k20);
       uself = nvalid ? (unsigned)(xn + zn) : uroot;
       aj_i = vj ? (unsigned)(xj + zn) : uroot;
       aj2_i = vj2 ? (unsigned)(xj2 + zn) : uroot;
@@ -864,8 +855,8 @@ __device__ __forceinline__ bool march(Heap<CAP, SPILL, NT, HYB, GPL> &H, const f
         const int kp0 = nz0 + 1, kp20 = nz0 + 2;
         vkp = nvalid && (unsigned)kp0 < unz;
         vk2p = vkp && (unsigned)kp20 < unz;
-        akp_i = vkp ? (unsigned)(xn + tile_z(kp0)) : uroot;
-        ak2p_i = vk2p ? (unsigned)(xn + tile_z(kp20)) : uroot;
+        akp_i = vkp ? (unsigned)(xn + dz_tile_z(kp0)) : uroot;
+        ak2p_i = vk2p ? (unsigned)(xn + dz_tile_z(kp20)) : uroot;
       }
     }
     const bool nvalid = lanes(nvalidm), vj = lanes(vjm), vj2 = lanes(vj2m), vk = lanes(vkm), vk2 = lanes(vk2m);
@@ -1222,7 +1213,7 @@ void fmm_kernel(FmmArgs A_) {
   g.nvx = A.g.nvx; g.nvz = A.g.nvz; g.nnx = A.g.nnx; g.nnz = A.g.nnz;
   g.gox = A.g.gox; g.goz = A.g.goz; g.dnx = A.g.dnx; g.dnz = A.g.dnz; g.dvx = A.g.dvx; g.dvz = A.g.dvz;
   const int nnx = g.nnx, nnz = g.nnz, nn = nnx * nnz;
-  const int tsh_c = tile_shift(nnz), nrec_c = tile_records(nnx, nnz);
+  const int tsh_c = dz_tile_shift(nnz), nrec_c = dz_tile_records(nnx, nnz);
   const size_t slot = (size_t)blockIdx.x * FPW + grp;
   unsigned *rec_r = A.rec_r + slot * NREC_R;
   float *velnr = A.velnr + slot * RM * RM;
@@ -1254,8 +1245,8 @@ void fmm_kernel(FmmArgs A_) {
         return;
       }
       for (int cx = 0; cx < nnx; cx++) {   // traveltime-grid write, back in the reference's column-major order
-        const int tx = tile_x(cx, tsh_c);
-        for (int cz = gl; cz < nnz; cz += GP) ttn[(size_t)cx * nnz + cz] = __int_as_float((int)rec[tx + tile_z(cz)]);   // all alive
+        const int tx = dz_tile_x(cx, tsh_c);
+        for (int cz = gl; cz < nnz; cz += GP) ttn[(size_t)cx * nnz + cz] = __int_as_float((int)rec[tx + dz_tile_z(cz)]);   // all alive
       }
     } else {
       unsigned *dst = A.ttn_tiled + (size_t)(A.tslot ? A.tslot[f] : f) * nrec_c;
@@ -1275,7 +1266,7 @@ void fmm_kernel(FmmArgs A_) {
   };
   int fastm = __builtin_amdgcn_readfirstlane(*A.vflag) == 0 ? A.fastm : 0;
   asm volatile("" : "+v"(fastm));   // (kept in a vector register: as a scalar it is spilled and comes back through v_readlane in every pop)
-  if (A.prio) __builtin_amdgcn_s_setprio(3);   // issue priority over another kernel's wavefronts on the same SIMD (see run_fmm)
+  if (A.prio) __builtin_amdgcn_s_setprio(3);   // issue priority over another kernel's wavefronts on the same SIMD (see FmmBatch::plan)
   const int nstage = SPILL ? 1 : A.ts_nstage;
   const bool ts = nstage > 1;
   unsigned &s_stage = *reinterpret_cast<unsigned *>(key_row(1));   // (the dummy slot of the second field, like s_base)
@@ -1416,7 +1407,7 @@ void fmm_kernel(FmmArgs A_) {
             }
             const float vr = sum[0] + sum[1] + sum[2] + sum[3];
             velnr[idx] = vr;
-            const int ti = tile_x(idm2 - 1, TSH_R) + tile_z(idm1 - 1);
+            const int ti = dz_tile_x(idm2 - 1, TSH_R) + dz_tile_z(idm1 - 1);
             slownr[ti] = make_float2(1.0f / vr, risti_rr[idm2 - 1]);
             rec_r[ti] = W_FAR;
           }
@@ -1457,7 +1448,7 @@ void fmm_kernel(FmmArgs A_) {
               const float ds = sqrtf(ax * ax + az * az);
               const float t0 = 2.0f * ds / (vss[i - 1][jj - 1] + vsrc);
               const int ux = rsx - 1 + i, uz = rsz - 1 + jj;
-              const int urid = tile_x(ux - 1, TSH_R) + tile_z(uz - 1);
+              const int urid = dz_tile_x(ux - 1, TSH_R) + dz_tile_z(uz - 1);
               H.add(t0, urid);
             }
         }
@@ -1479,7 +1470,7 @@ void fmm_kernel(FmmArgs A_) {
               int st = -9;
               float tt = 0.0f;
               if (c < nnxr && r < nnzr) {
-                const unsigned w = rec_r[tile_x(c, TSH_R) + tile_z(r)];
+                const unsigned w = rec_r[dz_tile_x(c, TSH_R) + dz_tile_z(r)];
                 if (w_is_alive(w)) { st = 0; tt = __int_as_float((int)w); }
                 else if (w == W_FAR) st = -1;
                 else { st = (int)(w & 0x7fffffffu); tt = H.get(st).key; }
@@ -1494,10 +1485,10 @@ void fmm_kernel(FmmArgs A_) {
         const int bw = bx.vnr - bx.vnl + 1, bh = bx.vnb - bx.vnt + 1, nbox = bw * bh;
         for (int i = gl; i < nbox; i += GP) {
           const int bxi = i / bh, bzi = i - bxi * bh;  // column-major inside the box
-          const unsigned w = rec_r[tile_x(bxi * SGDL, TSH_R) + tile_z(bzi * SGDL)];
+          const unsigned w = rec_r[dz_tile_x(bxi * SGDL, TSH_R) + dz_tile_z(bzi * SGDL)];
           // alive: its time; close (in the refined band when the march stopped): its trial time = the key at its slot, to be put
           // into the coarse heap; far
-          rec_c[tile_x(bx.vnl - 1 + bxi, tsh_c) + tile_z(bx.vnt - 1 + bzi)] =
+          rec_c[dz_tile_x(bx.vnl - 1 + bxi, tsh_c) + dz_tile_z(bx.vnt - 1 + bzi)] =
               (w_is_alive(w) || w == W_FAR) ? w : w_pending(H.get((int)(w & 0x7fffffffu)).key);
         }
         cbar();
@@ -1512,14 +1503,14 @@ void fmm_kernel(FmmArgs A_) {
           if (i < nbox) {
             const int bxi = i / bh, bzi = i - bxi * bh;
             const int cx = bx.vnl + bxi, cz = bx.vnt + bzi;
-            const int tx = tile_x(cx - 1, tsh_c), tz = tile_z(cz - 1);
+            const int tx = dz_tile_x(cx - 1, tsh_c), tz = dz_tile_z(cz - 1);
             p = &rec_c[tx + tz];
             w = *p;
             if (w_is_alive(w)) {
-              if (cz - 1 >= 1 && rec_c[tx + tile_z(cz - 2)] == W_FAR) promote = true;
-              if (cz + 1 <= nnz && rec_c[tx + tile_z(cz)] == W_FAR) promote = true;
-              if (cx - 1 >= 1 && rec_c[tile_x(cx - 2, tsh_c) + tz] == W_FAR) promote = true;
-              if (cx + 1 <= nnx && rec_c[tile_x(cx, tsh_c) + tz] == W_FAR) promote = true;
+              if (cz - 1 >= 1 && rec_c[tx + dz_tile_z(cz - 2)] == W_FAR) promote = true;
+              if (cz + 1 <= nnz && rec_c[tx + dz_tile_z(cz)] == W_FAR) promote = true;
+              if (cx - 1 >= 1 && rec_c[dz_tile_x(cx - 2, tsh_c) + tz] == W_FAR) promote = true;
+              if (cx + 1 <= nnx && rec_c[dz_tile_x(cx, tsh_c) + tz] == W_FAR) promote = true;
             }
           }
           cbar();
@@ -1538,7 +1529,7 @@ void fmm_kernel(FmmArgs A_) {
           if (i < nbox) {
             const int bxi = i / bh, bzi = i - bxi * bh;
             const int cx = bx.vnl + bxi, cz = bx.vnt + bzi;
-            node = tile_x(cx - 1, tsh_c) + tile_z(cz - 1);
+            node = dz_tile_x(cx - 1, tsh_c) + dz_tile_z(cz - 1);
             w = rec_c[node];
           }
           unsigned m = (unsigned)((wballot(w_is_pending(w)) >> (grp * GP)) & ((1ull << GP) - 1ull));
@@ -1580,100 +1571,180 @@ void fmm_kernel(FmmArgs A_) {
 }
 
 
+// ---- the heap forms: one row per fast instantiation of fmm_kernel, everything the host driver needs to know about it ----
+struct FmmForm {
+  int cap, id_bytes, hyb, gpl;   // LDS slots per field, bytes of a node id, 1 = heap levels in HBM below those in LDS, lanes per field
+  int tot;                       // slots the fast kernel holds in all (Heap::TOT) before the field goes to the spill rerun
+  const void *kernel, *spill;    // fmm_kernel<CAP, false, NT, HYB, GPL> and its rerun fmm_kernel<CAP, true, NT, false> (16 lanes per field)
+};
 template <int CAP, class NT, bool HYB = false, int GPL = 16>
-int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_status, std::shared_ptr<std::vector<int>> hsp, bool async,
-            std::function<int()> *finish_out) {
-  constexpr int FPW = 64 / GPL;   // fields per wavefront of the fast kernel (the spill rerun keeps 16 lanes per field)
-  int rc;
-  void *p;
-  // workgroups (one wavefront, FPW fields each): as many as the LDS heaps allow per CU
-  int per_cu = 0;
-  DZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fmm_kernel<CAP, false, NT, HYB, GPL>, 64, 0));
-  {   // the API rounds LDS differently from the allocator, which hands out 1 280-byte granules of the CU's 160 KB: at 12 288, 16 384
-      // and 32 768 bytes it answers one workgroup too many (measured: tools/lds_granule_probe.hip, profiles/r5_lds_granule.md)
-    hipFuncAttributes fa;
-    DZ_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&fmm_kernel<CAP, false, NT, HYB, GPL>)));
-    const int by_lds = (int)(163840 / ((fa.sharedSizeBytes + 1279) / 1280 * 1280));
-    if (per_cu > by_lds) per_cu = by_lds;
+FmmForm fmm_form() {
+  return {CAP, (int)sizeof(NT), HYB, GPL, Heap<CAP, false, NT, HYB, GPL>::TOT, (const void *)fmm_kernel<CAP, false, NT, HYB, GPL>,
+          (const void *)fmm_kernel<CAP, true, NT, false>};
+}
+enum {   // the rows of fmm_pick_form's table, in its order: LDS slots, _S = 16-bit node ids, _H = hybrid, 8 = eight lanes per field
+  F256_SH8, F512_S8, F512_SH8, F64_S, F64, F512_S, F512, F512_SH, F768_S, F768, F512_H, F1024, F1024_H, F1536, F2048 };
+// The heap form of a batch of nfield fields on an nnx x nnz grid (`opt`: the context whose options may force one).
+const FmmForm *fmm_pick_form(int nnx, int nnz, int nfield, int num_cu, const dazim_ctx *opt) {
+  static const FmmForm tab[] = {
+      fmm_form<256, unsigned short, true, 8>(), fmm_form<512, unsigned short, false, 8>(), fmm_form<512, unsigned short, true, 8>(),
+      fmm_form<64, unsigned short>(),        fmm_form<64, int>(),             fmm_form<512, unsigned short>(), fmm_form<512, int>(),
+      fmm_form<512, unsigned short, true>(), fmm_form<768, unsigned short>(), fmm_form<768, int>(),            fmm_form<512, int, true>(),
+      fmm_form<1024, int>(),                 fmm_form<1024, int, true>(),     fmm_form<1536, int>(),           fmm_form<2048, int>()};
+  static_assert(sizeof tab / sizeof tab[0] == F2048 + 1, "one enumerator per row of the table, in the table's order");
+  // LDS heap slots per field: the narrow band of an N x M grid peaks near 3*max(N,M) entries (and the
+  // 129 x 129 refined grid near 400); the smallest instantiation above that maximises the number of
+  // fields in flight per CU.  A field whose band still outgrows it is redone by the spill kernel.
+  int cap = 3 * (nnx > nnz ? nnx : nnz);
+  if (cap < 3 * RM) cap = 3 * RM;
+  if (dz_opt(opt, "fmm.cap", 0) > 0) cap = dz_opt(opt, "fmm.cap", 0);
+  const bool small = nnx <= 256 && nnz <= 256;   // node id fits 16 bits
+  bool use_hyb512 = cap > 512 && nfield > num_cu * 8 * FPW;
+  if (dz_opt(opt, "fmm.hyb512", 0) == 1) use_hyb512 = true;
+  if (dz_opt(opt, "fmm.hyb512", 0) == 2) use_hyb512 = false;
+  // (fmm.no_hybrid = 1 or an explicit fmm.cap: the one-level hybrid / all-LDS heaps of the branches below)
+  // The small-LDS forms trade latency for wavefronts: a batch that leaves the chip half empty anyway (fewer than 2.5 workgroups
+  // per CU) marches faster on the heaps with more levels in LDS -- 1 600 fields: 511 x 511 nodes 0.60 against 0.71 s, 341 x 341
+  // 0.21 against 0.29 s, 701 x 701 0.86 against 1.33 s; 4 800 fields: 1.08 / 0.82 s and 0.40 / 0.33 s the other way round --
+  // unless the bands would outgrow those (grids above 768 nodes a side: the all-LDS 2048-slot heap hands them to the spill kernel).
+  // fmm.hyb2 = 1 / 2 forces the small-LDS forms on / off.
+  bool use_hyb2 = cap > 768 && ((long)nfield > (long)num_cu * 10 || cap > 2304);
+  if (dz_opt(opt, "fmm.hyb2", 0) == 1) use_hyb2 = cap > 768;
+  if (dz_opt(opt, "fmm.hyb2", 0) == 2) use_hyb2 = false;
+  if (dz_opt(opt, "fmm.no_hybrid", 0) != 0 || dz_opt(opt, "fmm.cap", 0) > 0) use_hyb2 = false;
+  // Eight fields per wavefront (8 lanes per field, two quadrants per lane; round 4, option fmm.gp8): 1 = on the heaps the batch
+  // would take anyway (512 LDS slots, all-LDS up to 170-node grids, + one HBM level up to 256), 2 = 255 LDS slots + two HBM
+  // levels (1.5 KB of LDS per field).  Grids with 16-bit node ids only.  Measurements: DESIGN.md section 4.
+  const int gp8 = dz_opt(opt, "fmm.gp8", 0);
+  if (gp8 && small && cap <= 768) return &tab[gp8 == 2 ? F256_SH8 : cap <= 512 ? F512_S8 : F512_SH8];
+  if (cap <= 64) return &tab[small ? F64_S : F64];
+  if (cap <= 512) return &tab[small ? F512_S : F512];
+  // grids of 171 .. 256 nodes a side (S-256) with more fields than the 768-slot heaps hold at once (8 workgroups of 4 per CU):
+  // levels 1-9 in LDS + level 10 in HBM -- 12 workgroups per CU, a third wavefront per SIMD, and time slicing (FmmBatch::plan) keeps
+  // them all busy to the end.  The 13 % of the fields whose band outgrows 511 entries pay for the HBM level (-17 % at equal
+  // occupancy), so batches that fit the 768-slot heaps stay there.  Option fmm.hyb512 = 1 / 2 forces it on / off.
+  if (cap <= 768 && small && use_hyb512) return &tab[F512_SH];
+  if (cap <= 768) return &tab[small ? F768_S : F768];
+  // grids of 257 .. 682 nodes a side (S-512): levels 1-9 in LDS, levels 10 and 11 in HBM -- 16 KB of LDS per workgroup, ten
+  // workgroups per CU instead of five.  These kernels wait on latencies (1.25 wavefronts per SIMD with 1024 LDS slots), so twice
+  // the wavefronts for one or two more dependent memory accesses per pop is a good trade: 341 x 341 nodes 20.2 -> 31.3 k
+  // fields/s against the all-LDS 1024-slot heap, S-512 7 950 -> 11 300 against levels 1-10 in LDS (same box, bit-identical).
+  // (option fmm.hyb2 = 2: the forms below)
+  if (cap <= 2048 && use_hyb2) return &tab[F512_H];
+  if (cap <= 1024) return &tab[F1024];
+  // (fmm.hyb2 = 2) grids of 342 .. 682 nodes a side: levels 1-10 in LDS + levels 11 (and, never reached there, 12) in HBM
+  if (cap <= 2048 && dz_opt(opt, "fmm.no_hybrid", 0) == 0) return &tab[F1024_H];
+  // grids above 682 nodes a side: levels 1-10 in LDS, 11 and 12 in HBM (bands up to 4 095 entries = 1 365 nodes a side without
+  // the spill kernel, five workgroups per CU instead of the two of the all-LDS 2048-slot heap)
+  if (use_hyb2) return &tab[F1024_H];
+  return &tab[cap <= 1536 ? F1536 : F2048];
+}
+
+// ---- one eikonal batch on the host: a member function per stage, called in this order by dazim_fmm_batch.  finish() runs at once,
+// or -- option fmm.async -- when the ray call (or dazim_sync ...) asks for it through ctx->fmm_finish, which holds the object till then ----
+struct FmmBatch {
+  dazim_ctx *ctx = nullptr;
+  FmmArgs A;
+  const FmmForm *form = nullptr;
+  int nfield = 0;          // of the call (A.nfield becomes the rerun's)
+  size_t nn = 0, nr = 0;   // nodes of the coarse and of the refined grid
+  bool async = false;      // asked for by the caller; launch() decides
+  int nwg = 0, nslot = 0, nseg = 0, ovfcap = 0;
+  bool ts = false, keep_tiled = false, force_spill = false;
+  size_t nrec = 0;   // node words of a coarse field
+  unsigned total_tasks = 0;
+  int *hs_pin = nullptr;   // pinned: the statuses as the device wrote them (+ the pop count behind them)
+  std::vector<int> hs;     // ... and on the host, for first_error()
+  int plan() {
+    // workgroups (one wavefront, fields-per-wavefront fields each): as many as the LDS heaps allow per CU
+    int per_cu = 0;
+    DZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, form->kernel, 64, 0));
+    {   // the API rounds LDS differently from the allocator, which hands out 1 280-byte granules of the CU's 160 KB: at 12 288, 16 384
+        // and 32 768 bytes it answers one workgroup too many (measured: tools/lds_granule_probe.hip, profiles/r5_lds_granule.md)
+      hipFuncAttributes fa;
+      DZ_HIP(hipFuncGetAttributes(&fa, form->kernel));
+      const int by_lds = (int)(163840 / ((fa.sharedSizeBytes + 1279) / 1280 * 1280));
+      if (per_cu > by_lds) per_cu = by_lds;
+    }
+    per_cu = std::min(std::max(per_cu, 1), 16);
+    ctx->ksec["fmm.wg_per_cu"] = (double)per_cu;
+    if (dz_opt(ctx, "fmm.wg_per_cu", 0) > 0 && dz_opt(ctx, "fmm.wg_per_cu", 0) < per_cu) per_cu = dz_opt(ctx, "fmm.wg_per_cu", 0);
+    nwg = ctx->num_cu * per_cu;
+    // Small batches: a launch lasts at least as long as ONE field takes alone, and with fewer wavefronts than SIMDs most of the
+    // chip idles.  Fewer fields per wavefront put every field on a SIMD of its own sooner but were measured and buy nothing (S-128:
+    // 49.4 / 46.8 / 51.7 ms with four / two / one, docs/history_r1_r3.md): the launch is one field's latency, not idle hardware.
+    A.fpw = 64 / form->gpl;   // fields per wavefront of the fast kernel (the spill rerun keeps 16 lanes per field)
+    ctx->ksec["fmm.lanes_per_field"] = form->gpl;
+    ctx->ksec["fmm.fpw"] = A.fpw;
+    // Issue priority (round 4).  A batch that leaves most of the chip empty lasts as long as one field's serial chain, and every cycle
+    // one of its wavefronts waits for an issue slot behind another kernel's wavefronts -- the dispersion kernel's perturbed copies on
+    // the auxiliary stream (disp.async) -- lengthens that chain: s_setprio 3 gives them the slot first.  S-128: eikonal launch 52.0 ->
+    // 45.0 ms (= alone on the chip), step 64.0 -> 56.9 ms; test4_Yunnan program: assembly 1.015 -> 0.875 s.  A batch that fills the chip
+    // gains nothing among its own wavefronts and only starves the copies the ray kernel then waits for (S-256: step 368 -> 380 ms), so
+    // the rule is: at most half of the resident workgroups.
+    A.prio = (nfield + A.fpw - 1) / A.fpw <= nwg / 2 ? 1 : 0;
+    ctx->ksec["fmm.prio"] = A.prio;
+    if (nwg > (nfield + A.fpw - 1) / A.fpw) nwg = (nfield + A.fpw - 1) / A.fpw;
+    nslot = nwg * A.fpw;
+    ovfcap = (int)((nn > nr ? nn : nr) / 2 + 64);  // maxbt = nint(snb*nnx*nnz), inv/CalSurfG.f90:1068
+    A.ovfcap = form->hyb ? form->tot - form->cap : 0;   // the fast kernel: only the HYB heap has HBM levels
+    // Time slicing (see fmm_kernel): on when the batch does not fit the resident slots (more than one round) and the per-field node
+    // words fit comfortably; option fmm.ts = 1 / 2 forces it on / off (0: this rule), fmm.ts_stages sets the number of coarse stages.
+    // Few stages are best (not because of the hand-over fences, measured; with many short stages handed out
+    // stage-major the fields march in step again and the mixture of phases on a CU is lost): S-256's 16 000
+    // fields on the 512-slot hybrid heap take 0.240 / 0.253 / 0.248 / 0.249 / 0.252 s with 2 / 3 / 4 / 8 / 12 coarse stages
+    // (0.288 s unsliced on the 768-slot heap, same box), the 768-slot heap 0.292 / 0.264 / 0.262 s with 2 / 4 / 8-12; S-512's
+    // 32 000 fields (1024-slot hybrid heap) 4.29 s unsliced, 4.03 / 3.96 / 3.97 s with 2 / 4 / 8.  Defaults: 2 on the 512-slot heaps
+    // with 16-bit ids (round 5, the all-LDS one on a 166 x 166 grid, 16 000 fields: 156 k fields/s with 2 stages, 122 k with 4), 8 on the one with two HBM levels (S-512: 2.68 / 2.63 / 2.61 s with 2 / 4 / 8), 4 elsewhere.
+    ts = nfield > nslot;
+    if (dz_opt(ctx, "fmm.ts", 0) == 1) ts = true;
+    if (dz_opt(ctx, "fmm.ts", 0) == 2) ts = false;
+    nrec = (size_t)dz_tile_records(A.g.nnx, A.g.nnz);
+    {
+      size_t mfree = 0, mtot = 0;
+      if (hipMemGetInfo(&mfree, &mtot) != hipSuccess || (size_t)nfield * nrec * sizeof(unsigned) > mfree / 4) ts = false;
+    }
+    nseg = dz_opt(ctx, "fmm.ts_stages", 0) > 0 ? dz_opt(ctx, "fmm.ts_stages", 0) : (form->cap <= 512 ? (form->id_bytes == 2 ? 2 : (form->hyb ? 8 : 4)) : 4);
+    A.ts_nstage = ts ? 1 + nseg : 1;
+    // (stage lengths that shrink towards the end -- a shorter tail -- were measured and lose: 0.251-0.265 s against 0.247 s)
+    A.ts_pops = (int)((nn + nseg - 1) / nseg);
+    // (stages of unequal length -- odd batches longer, even ones shorter, to put the batches out of step -- lose badly: +19 % of
+    // the time at +-20 %, +44 % at +-40 %: the stage-major hand-out relies on equal tasks, a workgroup that takes a task whose
+    // predecessor is still running waits; with equal stages that wait is 0.15 % of the workgroups' time at 2 stages, 2 % at 8, measured)
+    ctx->ksec["fmm.ts_stages"] = ts ? (double)nseg : 0.0;
+    return 0;
   }
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 16) per_cu = 16;
-  ctx->ksec["fmm.wg_per_cu"] = (double)per_cu;
-  if (dz_opt(ctx, "fmm.wg_per_cu", 0) > 0 && dz_opt(ctx, "fmm.wg_per_cu", 0) < per_cu) per_cu = dz_opt(ctx, "fmm.wg_per_cu", 0);
-  int nwg = ctx->num_cu * per_cu;
-  // Small batches: a launch lasts at least as long as ONE field takes alone, and with fewer wavefronts than SIMDs most of the
-  // chip idles.  Fewer fields per wavefront put every field on a SIMD of its own sooner but were measured and buy nothing (S-128:
-  // 49.4 / 46.8 / 51.7 ms with four / two / one, docs/history_r1_r3.md): the launch is one field's latency, not idle hardware.
-  A.fpw = FPW;
-  ctx->ksec["fmm.lanes_per_field"] = GPL;
-  ctx->ksec["fmm.fpw"] = A.fpw;
-  // Issue priority (round 4).  A batch that leaves most of the chip empty lasts as long as one field's serial chain, and every cycle
-  // one of its wavefronts waits for an issue slot behind another kernel's wavefronts -- the dispersion kernel's perturbed copies on
-  // the auxiliary stream (disp.async) -- lengthens that chain: s_setprio 3 gives them the slot first.  S-128: eikonal launch 52.0 ->
-  // 45.0 ms (= alone on the chip), step 64.0 -> 56.9 ms; test4_Yunnan program: assembly 1.015 -> 0.875 s.  A batch that fills the chip
-  // gains nothing among its own wavefronts and only starves the copies the ray kernel then waits for (S-256: step 368 -> 380 ms), so
-  // the rule is: at most half of the resident workgroups.
-  A.prio = (nfield + A.fpw - 1) / A.fpw <= nwg / 2 ? 1 : 0;
-  ctx->ksec["fmm.prio"] = A.prio;
-  if (nwg > (nfield + A.fpw - 1) / A.fpw) nwg = (nfield + A.fpw - 1) / A.fpw;
-  const int nslot = nwg * FPW;
-  const int ovfcap = (int)((nn > nr ? nn : nr) / 2 + 64);  // maxbt = nint(snb*nnx*nnz), inv/CalSurfG.f90:1068
-  A.ovfcap = HYB ? Heap<CAP, false, NT, HYB, GPL>::TOT - CAP : 0;   // the fast kernel: only the HYB heap has HBM levels
-  // Time slicing (see fmm_kernel): on when the batch does not fit the resident slots (more than one round) and the per-field node
-  // words fit comfortably; option fmm.ts = 1 / 2 forces it on / off (0: this rule), fmm.ts_stages sets the number of coarse stages.
-  // Few stages are best (not because of the hand-over fences, measured; with many short stages handed out
-  // stage-major the fields march in step again and the mixture of phases on a CU is lost): S-256's 16 000
-  // fields on the 512-slot hybrid heap take 0.240 / 0.253 / 0.248 / 0.249 / 0.252 s with 2 / 3 / 4 / 8 / 12 coarse stages
-  // (0.288 s unsliced on the 768-slot heap, same box), the 768-slot heap 0.292 / 0.264 / 0.262 s with 2 / 4 / 8-12; S-512's
-  // 32 000 fields (1024-slot hybrid heap) 4.29 s unsliced, 4.03 / 3.96 / 3.97 s with 2 / 4 / 8.  Defaults: 2 on the 512-slot heaps
-  // with 16-bit ids (round 5, the all-LDS one on a 166 x 166 grid, 16 000 fields: 156 k fields/s with 2 stages, 122 k with 4), 8 on the one with two HBM levels (S-512: 2.68 / 2.63 / 2.61 s with 2 / 4 / 8), 4 elsewhere.
-  bool ts = nfield > nslot;
-  if (dz_opt(ctx, "fmm.ts", 0) == 1) ts = true;
-  if (dz_opt(ctx, "fmm.ts", 0) == 2) ts = false;
-  const size_t rec_field_bytes = (size_t)tile_records(A.g.nnx, A.g.nnz) * sizeof(unsigned);
-  {
-    size_t mfree = 0, mtot = 0;
-    if (hipMemGetInfo(&mfree, &mtot) != hipSuccess || (size_t)nfield * rec_field_bytes > mfree / 4) ts = false;
+  int scratch() {
+    int rc;
+    // owners of node words / HBM heap levels: fields or resident slots.  + 8: the idle lane groups of the last wavefront of a batch
+    // (owner index up to nfield + fields per wavefront - 1, at most 8 fields per wavefront) address their own, unused, state
+    const size_t nown = (ts ? (size_t)nfield : (size_t)nslot) + 8;
+    if ((rc = dz_scratch(ctx, "fmm.rec_c", nown * nrec, &A.rec_c))) return rc;
+    keep_tiled = A.ttn == nullptr;   // the fields stay inside the library, in tiles (dazim_fmm_batch with ttn == NULL)
+    A.ttn_tiled = nullptr; A.tslot = nullptr;
+    if (keep_tiled && ts) {
+      A.ttn_tiled = A.rec_c;   // every field's node words end where they were marched: nothing is copied (tslot: field_order)
+    } else if (keep_tiled) {
+      if ((rc = dz_scratch(ctx, "fmm.ttn_tiled", (size_t)nfield * nrec, &A.ttn_tiled))) return rc;
+    }
+    A.ts_flag = nullptr; A.ts_keys = nullptr; A.ts_nodes = nullptr;
+    if (ts) {
+      if ((rc = dz_scratch(ctx, "fmm.ts_flag", ((size_t)nfield / A.fpw + 2), &A.ts_flag))) return rc;
+      DZ_HIP(hipMemsetAsync(A.ts_flag, 0, ((size_t)nfield / A.fpw + 2) * 4, ctx->stream));
+      if ((rc = dz_scratch(ctx, "fmm.ts_keys", (size_t)nfield * form->cap, &A.ts_keys))) return rc;
+      if ((rc = dz_scratch(ctx, "fmm.ts_nodes", (size_t)nfield * form->cap, &A.ts_nodes))) return rc;
+    }
+    if ((rc = dz_scratch(ctx, "fmm.rec_r", (size_t)nslot * NREC_R, &A.rec_r))) return rc;
+    if ((rc = dz_scratch(ctx, "fmm.velnr", (size_t)nslot * nr, &A.velnr))) return rc;
+    if ((rc = dz_scratch(ctx, "fmm.slownr", (size_t)nslot * NREC_R, &A.slownr))) return rc;
+    if ((rc = dz_scratch(ctx, "fmm.ovf", nown * A.ovfcap + 8, &A.ovf))) return rc;
+    if ((rc = dz_scratch(ctx, "fmm.counter", 64, &A.counter))) return rc;
+    A.flist = nullptr;
+    return 0;
   }
-  int nseg = dz_opt(ctx, "fmm.ts_stages", 0) > 0 ? dz_opt(ctx, "fmm.ts_stages", 0) : (CAP <= 512 ? (sizeof(NT) == 2 ? 2 : (HYB ? 8 : 4)) : 4);
-  A.ts_nstage = ts ? 1 + nseg : 1;
-  // (stage lengths that shrink towards the end -- a shorter tail -- were measured and lose: 0.251-0.265 s against 0.247 s)
-  A.ts_pops = (int)((nn + nseg - 1) / nseg);
-  // (stages of unequal length -- odd batches longer, even ones shorter, to put the batches out of step -- lose badly: +19 % of
-  // the time at +-20 %, +44 % at +-40 %: the stage-major hand-out relies on equal tasks, a workgroup that takes a task whose
-  // predecessor is still running waits; with equal stages that wait is 0.15 % of the workgroups' time at 2 stages, 2 % at 8, measured)
-  ctx->ksec["fmm.ts_stages"] = ts ? (double)nseg : 0.0;
-  // owners of node words / HBM heap levels: fields or resident slots.  + 8: the idle lane groups of the last wavefront of a batch
-  // (owner index up to nfield + fields per wavefront - 1, at most 8 fields per wavefront) address their own, unused, state
-  const size_t nown = (ts ? (size_t)nfield : (size_t)nslot) + 8;
-  if ((rc = dz_scratch(ctx, "fmm.rec_c", nown * rec_field_bytes, &p))) return rc;
-  A.rec_c = (unsigned *)p;
-  const bool keep_tiled = A.ttn == nullptr;   // the fields stay inside the library, in tiles (dazim_fmm_batch with ttn == NULL)
-  A.ttn_tiled = nullptr;
-  A.tslot = nullptr;
-  if (keep_tiled && ts) {
-    A.ttn_tiled = A.rec_c;   // every field's node words end where they were marched: nothing is copied (tslot below)
-  } else if (keep_tiled) {
-    if ((rc = dz_scratch(ctx, "fmm.ttn_tiled", (size_t)nfield * rec_field_bytes, &p))) return rc;
-    A.ttn_tiled = (unsigned *)p;
-  }
-  A.ts_flag = nullptr; A.ts_keys = nullptr; A.ts_nodes = nullptr;
-  if (ts) {
-    if ((rc = dz_scratch(ctx, "fmm.ts_flag", ((size_t)nfield / A.fpw + 2), &A.ts_flag))) return rc;
-    DZ_HIP(hipMemsetAsync(A.ts_flag, 0, ((size_t)nfield / A.fpw + 2) * 4, ctx->stream));
-    if ((rc = dz_scratch(ctx, "fmm.ts_keys", (size_t)nfield * CAP, &A.ts_keys))) return rc;
-    if ((rc = dz_scratch(ctx, "fmm.ts_nodes", (size_t)nfield * CAP, &A.ts_nodes))) return rc;
-  }
-  if ((rc = dz_scratch(ctx, "fmm.rec_r", (size_t)nslot * NREC_R, &A.rec_r))) return rc;
-  if ((rc = dz_scratch(ctx, "fmm.velnr", (size_t)nslot * nr, &A.velnr))) return rc;
-  if ((rc = dz_scratch(ctx, "fmm.slownr", (size_t)nslot * NREC_R, &A.slownr))) return rc;
-  if ((rc = dz_scratch(ctx, "fmm.ovf", nown * A.ovfcap * sizeof(HEnt) + 64, &p))) return rc;
-  A.ovf = (HEnt *)p;
-  if ((rc = dz_scratch(ctx, "fmm.counter", 64, &A.counter))) return rc;
-  A.status = d_status;
-  A.flist = nullptr;
-  std::vector<int> order(nfield);
-  {   // stable counting sort of the fields by period (the list the XCD ranges are cut from)
+  int field_order() {   // stable counting sort of the fields by period (the list the XCD ranges are cut from)
+    int rc; void *p;
+    std::vector<int> order(nfield);
     // (the host's reads of the step land in pinned memory -- dz_pinned: DMA transfers instead of blit kernels that queue behind
     // whatever holds the chip)
     if ((rc = dz_pinned(ctx, "fmm.host", (size_t)nfield * 12 + 64, &p))) return rc;
@@ -1726,121 +1797,116 @@ int run_fmm(dazim_ctx *ctx, FmmArgs A, int nfield, size_t nn, size_t nr, int *d_
     if ((rc = dz_scratch(ctx, "fmm.order", (size_t)nfield * 4 + 16, &p))) return rc;
     DZ_HIP(hipMemcpyAsync(p, po, (size_t)nfield * 4, hipMemcpyHostToDevice, ctx->stream));
     A.flist = (const int *)p;
+    return 0;
   }
-  const bool force_spill = dz_opt(ctx, "fmm.force_spill", 0) != 0;
-  if ((rc = dz_pinned(ctx, "fmm.host_status", (size_t)nfield * 4 + 64, &p))) return rc;
-  int *hs_pin = (int *)p;
-  if ((rc = dz_async_init(ctx))) return rc;
-  DZ_HIP(hipMemsetAsync(A.counter, 0, 256, ctx->stream));
-  if (A.fdone) DZ_HIP(hipMemsetAsync(A.fdone, 0, (size_t)nfield * 4, ctx->stream));
-  A.hprog = nullptr;
-  unsigned total_tasks = 0;
-  if (A.fdone && ctx->hprog) {
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, ctx->hprog, 0) == hipSuccess && dp) {
-      for (int c = 0; c < 8; c++) ctx->hprog[c] = 0;
-      A.hprog = (unsigned *)dp;
-      const unsigned nq = ((unsigned)nfield + (unsigned)A.fpw - 1) / (unsigned)A.fpw;
-      for (unsigned c = 0; c < 8; c++) total_tasks += ((nq * (c + 1) >> 3) - (nq * c >> 3)) * (unsigned)A.ts_nstage;
-    } else {
-      (void)hipGetLastError();
+  int progress_words() {   // the cleared counters and flags, and the host-mapped words an asynchronous launch reports its progress in
+    int rc; void *p;
+    force_spill = dz_opt(ctx, "fmm.force_spill", 0) != 0;
+    if ((rc = dz_pinned(ctx, "fmm.host_status", (size_t)nfield * 4 + 64, &p))) return rc;
+    hs_pin = (int *)p;
+    hs = std::vector<int>(nfield);
+    if ((rc = dz_async_init(ctx))) return rc;
+    DZ_HIP(hipMemsetAsync(A.counter, 0, 256, ctx->stream));
+    if (A.fdone) DZ_HIP(hipMemsetAsync(A.fdone, 0, (size_t)nfield * 4, ctx->stream));
+    A.hprog = nullptr;
+    if (A.fdone && ctx->hprog) {
+      void *dp = nullptr;
+      if (hipHostGetDevicePointer(&dp, ctx->hprog, 0) == hipSuccess && dp) {
+        for (int c = 0; c < 8; c++) ctx->hprog[c] = 0;
+        A.hprog = (unsigned *)dp;
+        const unsigned nq = ((unsigned)nfield + (unsigned)A.fpw - 1) / (unsigned)A.fpw;
+        for (unsigned c = 0; c < 8; c++) total_tasks += ((nq * (c + 1) >> 3) - (nq * c >> 3)) * (unsigned)A.ts_nstage;
+      } else {
+        (void)hipGetLastError();
+      }
     }
+    return 0;
   }
-  // (what a ray kernel on another stream must see complete before it starts: the gridder's velocity grids, the cleared flags)
-  DZ_HIP(hipEventRecord(ctx->ev_pre, ctx->stream));
-  DZ_HIP(hipEventRecord(ctx->ev_f0, ctx->stream));
-  if (!force_spill) {
-    hipLaunchKernelGGL((fmm_kernel<CAP, false, NT, HYB, GPL>), dim3(nwg), dim3(64), 0, ctx->stream, A);
-    DZ_HIP(hipGetLastError());
-  }
-  DZ_HIP(hipEventRecord(ctx->ev_f1, ctx->stream));
-  // ---- everything after the launch: statuses, spill reruns, timers.  At once, or -- option fmm.async -- when the ray call (or
-  // dazim_sync ...) asks for it, so that the ray kernel's count pass can be enqueued beside the launch ----
-  auto fin = [=]() mutable -> int {
-  int rc;
-  void *p;
-  std::vector<int> &hs = *hsp;
-  std::vector<int> redo;
-  if (!force_spill) {
-    DZ_HIP(hipMemcpyAsync(hs_pin, d_status, (size_t)nfield * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DZ_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(hs.data(), hs_pin, (size_t)nfield * 4);
-    for (int i = 0; i < nfield; i++)
-      if (hs[i] == -2) redo.push_back(i);
-  } else {
-    for (int i = 0; i < nfield; i++) redo.push_back(i);
-  }
-  ctx->ksec["fmm.spilled_fields"] = (double)redo.size();
-  if (!redo.empty()) {  // fields whose narrow band outgrew the LDS heap: same kernel, HBM spill enabled
-    if ((rc = dz_scratch(ctx, "fmm.flist", redo.size() * 4, &p))) return rc;
-    DZ_HIP(hipMemcpyAsync(p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    A.flist = (const int *)p;
-    A.nfield = (int)redo.size();
-    DZ_HIP(hipMemsetAsync(A.counter, 0, 64, ctx->stream));   // (the queue positions; the count of accepted nodes goes on)
-    A.fpw = 4;                                        // (16 lanes per field: the spill kernel's sequential sift-down is written for them)
-    A.ts_nstage = 1;
-    int nwg2 = ((int)redo.size() + 3) / 4;
-    if (nwg2 > nwg) nwg2 = nwg;
-    // the spill kernel keeps every slot >= CAP in HBM: maxbt entries per resident field, allocated only when a field needs it
-    A.ovfcap = ovfcap;
-    if ((rc = dz_scratch(ctx, "fmm.ovf_spill", (size_t)nwg2 * 4 * ovfcap, &A.ovf))) return rc;
-    if (keep_tiled && ts) {   // (the first launch's node words ARE the results: the rerun marches in blocks of its own and copies)
-      if ((rc = dz_scratch(ctx, "fmm.rec_spill", (size_t)(nwg2 * 4 + 8) * rec_field_bytes, &p))) return rc;
-      A.rec_c = (unsigned *)p;
+  int launch() {   // the fast kernel, and what the ray call that follows is told about it
+    // (what a ray kernel on another stream must see complete before it starts: the gridder's velocity grids, the cleared flags)
+    DZ_HIP(hipEventRecord(ctx->ev_pre, ctx->stream));
+    DZ_HIP(hipEventRecord(ctx->ev_f0, ctx->stream));
+    if (!force_spill) {
+      void *params[] = {&A};
+      DZ_HIP(hipLaunchKernel(form->kernel, dim3(nwg), dim3(64), params, 0, ctx->stream));
     }
-    hipLaunchKernelGGL((fmm_kernel<CAP, true, NT, false>), dim3(nwg2), dim3(64), 0, ctx->stream, A);
-    DZ_HIP(hipGetLastError());
     DZ_HIP(hipEventRecord(ctx->ev_f1, ctx->stream));
-    DZ_HIP(hipMemcpyAsync(hs_pin, d_status, (size_t)nfield * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DZ_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(hs.data(), hs_pin, (size_t)nfield * 4);
+    ctx->fields.tiled = keep_tiled ? A.ttn_tiled : nullptr; ctx->fields.tslot = keep_tiled ? A.tslot : nullptr;
+    ctx->fields.nfield = nfield; ctx->fields.nnx = A.g.nnx; ctx->fields.nnz = A.g.nnz;
+    ctx->fields.stride = dz_tile_records(A.g.nnx, A.g.nnz); ctx->fields.tsh = dz_tile_shift(A.g.nnz);
+    // (a batch that fits the resident slots has no tail worth filling -- its workgroups all end together -- and a ray pass beside it
+    // would only wait: such a call completes at once)
+    // ... and with eight coarse stages (the two-level hybrid heaps of the 257..682-node grids: S-512) the tail is a ninth of a field's
+    // march: the ray passes beside it only stretch the launch by what they save afterwards (3.00 s either way) -- not there
+    async = async && ts && A.hprog != nullptr && nseg <= 4;
+    ctx->fields.fdone = async ? A.fdone : nullptr; ctx->fields.nwg = (unsigned)nwg;
+    ctx->fields.hprog = A.hprog ? ctx->hprog : nullptr; ctx->fields.total_tasks = total_tasks;
+    ctx->ksec["fmm.async"] = async ? 1.0 : 0.0;
+    return 0;
   }
-  {
+  int finish() {   // everything after the launch: statuses, spill reruns, timers
+    int rc; void *p;
+    std::vector<int> redo;
+    if (!force_spill) {
+      DZ_HIP(hipMemcpyAsync(hs_pin, A.status, (size_t)nfield * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DZ_HIP(hipStreamSynchronize(ctx->stream));
+      memcpy(hs.data(), hs_pin, (size_t)nfield * 4);
+      for (int i = 0; i < nfield; i++)
+        if (hs[i] == -2) redo.push_back(i);
+    } else {
+      for (int i = 0; i < nfield; i++) redo.push_back(i);
+    }
+    ctx->ksec["fmm.spilled_fields"] = (double)redo.size();
+    if (!redo.empty()) {  // fields whose narrow band outgrew the LDS heap: same kernel, HBM spill enabled
+      if ((rc = dz_scratch(ctx, "fmm.flist", redo.size() * 4, &p))) return rc;
+      DZ_HIP(hipMemcpyAsync(p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+      A.flist = (const int *)p;
+      A.nfield = (int)redo.size();
+      DZ_HIP(hipMemsetAsync(A.counter, 0, 64, ctx->stream));   // (the queue positions; the count of accepted nodes goes on)
+      A.fpw = 4;                                        // (16 lanes per field: the spill kernel's sequential sift-down is written for them)
+      A.ts_nstage = 1;
+      int nwg2 = ((int)redo.size() + 3) / 4;
+      if (nwg2 > nwg) nwg2 = nwg;
+      // the spill kernel keeps every slot >= CAP in HBM: maxbt entries per resident field, allocated only when a field needs it
+      A.ovfcap = ovfcap;
+      if ((rc = dz_scratch(ctx, "fmm.ovf_spill", (size_t)nwg2 * 4 * ovfcap, &A.ovf))) return rc;
+      if (keep_tiled && ts) {   // (the first launch's node words ARE the results: the rerun marches in blocks of its own and copies)
+        if ((rc = dz_scratch(ctx, "fmm.rec_spill", (size_t)(nwg2 * 4 + 8) * nrec, &A.rec_c))) return rc;
+      }
+      void *params[] = {&A};
+      DZ_HIP(hipLaunchKernel(form->spill, dim3(nwg2), dim3(64), params, 0, ctx->stream));
+      DZ_HIP(hipEventRecord(ctx->ev_f1, ctx->stream));
+      DZ_HIP(hipMemcpyAsync(hs_pin, A.status, (size_t)nfield * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DZ_HIP(hipStreamSynchronize(ctx->stream));
+      memcpy(hs.data(), hs_pin, (size_t)nfield * 4);
+    }
     float ms = 0;
     DZ_HIP(hipEventSynchronize(ctx->ev_f1));
     DZ_HIP(hipEventElapsedTime(&ms, ctx->ev_f0, ctx->ev_f1));
     ctx->ksec["fmm"] = ms * 1e-3;
-  }
-  {
     unsigned long long &hp = *(unsigned long long *)(hs_pin + nfield + 2 - (nfield & 1));
     hp = 0;
     DZ_HIP(hipMemcpyAsync(&hp, A.counter + 16, 8, hipMemcpyDeviceToHost, ctx->stream));
     DZ_HIP(hipStreamSynchronize(ctx->stream));
     ctx->ksec["fmm.field_pops"] = (double)hp;   // nodes accepted by this call (all fields, refined + coarse marches, incl. spill reruns)
-  }
 #ifdef DZ_FMM_PROF
-  {
-    unsigned long long h[8];
-    DZ_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fmm_prof), sizeof h));
-    fprintf(stderr, "fmm prof (memtime ticks): setup+loads %llu popdown %llu loadwait %llu fix %llu quadrant %llu siftups-fast %llu siftups-slow %llu - looptop %llu\n",
-            h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-    unsigned long long z[8] = {0};
-    DZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_fmm_prof), z, sizeof z));
-  }
+    {
+      unsigned long long h[8];
+      DZ_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fmm_prof), sizeof h));
+      fprintf(stderr, "fmm prof (memtime ticks): setup+loads %llu popdown %llu loadwait %llu fix %llu quadrant %llu siftups-fast %llu siftups-slow %llu - looptop %llu\n",
+              h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
+      unsigned long long z[8] = {0};
+      DZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_fmm_prof), z, sizeof z));
+    }
 #endif
-  return 0;
-  };
-  ctx->fields.tiled = keep_tiled ? A.ttn_tiled : nullptr;
-  ctx->fields.tslot = keep_tiled ? A.tslot : nullptr;
-  ctx->fields.nfield = nfield;
-  ctx->fields.nnx = A.g.nnx;
-  ctx->fields.nnz = A.g.nnz;
-  ctx->fields.stride = tile_records(A.g.nnx, A.g.nnz);
-  ctx->fields.tsh = tile_shift(A.g.nnz);
-  // (a batch that fits the resident slots has no tail worth filling -- its workgroups all end together -- and a ray pass beside it
-  // would only wait: such a call completes at once)
-  // ... and with eight coarse stages (the two-level hybrid heaps of the 257..682-node grids: S-512) the tail is a ninth of a field's
-  // march: the ray passes beside it only stretch the launch by what they save afterwards (3.00 s either way) -- not there
-  async = async && ts && A.hprog != nullptr && nseg <= 4;
-  ctx->fields.fdone = async ? A.fdone : nullptr;
-  ctx->fields.nwg = (unsigned)nwg;
-  ctx->fields.hprog = A.hprog ? ctx->hprog : nullptr;
-  ctx->fields.total_tasks = total_tasks;
-  ctx->ksec["fmm.async"] = async ? 1.0 : 0.0;
-  if (!async) return fin();
-  *finish_out = fin;
-  return 0;
-}
+    return 0;
+  }
+  int first_error() {   // first failing field, like the reference's STOP
+    for (int i = 0; i < nfield; i++)
+      if (hs[i]) return dz_fail(ctx, hs[i], "field %d: source lies outside bounds of model", i);
+    return 0;
+  }
+};
 
 }  // namespace
 
@@ -1869,16 +1935,12 @@ extern "C" int dazim_fmm_batch(dazim_ctx *ctx, int nx, int ny, float goxd, float
   DzBuf<int> period, nstsr, status;
   DzBuf<dazim_refbox> boxes;
   int rc;
-  if ((rc = pv.init(ctx, pv_u, npv * kmax, true, false))) return rc;
-  if ((rc = scx.init(ctx, scx_u, nfield, true, false))) return rc;
-  if ((rc = scz.init(ctx, scz_u, nfield, true, false))) return rc;
-  if ((rc = period.init(ctx, period_u, nfield, true, false))) return rc;
-  if ((rc = veln.init(ctx, veln_u, nn * kmax, false, true))) return rc;
-  if ((rc = ttn.init(ctx, ttn_u, nn * nfield, false, true))) return rc;
-  if ((rc = ttnr.init(ctx, ttnr_u, nr * nfield, false, true))) return rc;
-  if ((rc = nstsr.init(ctx, nstsr_u, nr * nfield, false, true))) return rc;
-  if ((rc = boxes.init(ctx, boxes_u, nfield, false, true))) return rc;
-  if ((rc = status.init(ctx, status_u, nfield, false, true))) return rc;
+  if ((rc = pv.init(ctx, pv_u, npv * kmax, true, false)) || (rc = scx.init(ctx, scx_u, nfield, true, false)) ||
+      (rc = scz.init(ctx, scz_u, nfield, true, false)) || (rc = period.init(ctx, period_u, nfield, true, false)) ||
+      (rc = veln.init(ctx, veln_u, nn * kmax, false, true)) || (rc = ttn.init(ctx, ttn_u, nn * nfield, false, true)) ||
+      (rc = ttnr.init(ctx, ttnr_u, nr * nfield, false, true)) || (rc = nstsr.init(ctx, nstsr_u, nr * nfield, false, true)) ||
+      (rc = boxes.init(ctx, boxes_u, nfield, false, true)) || (rc = status.init(ctx, status_u, nfield, false, true)))
+    return rc;
 
   // host tables of EARTH*sin(colatitude): same libm sinf the CPU reference calls (fouds2 :585)
   std::vector<float> rc_tab(g.nnx), rr_tab((size_t)g.nnx * RM);
@@ -1888,36 +1950,23 @@ extern "C" int dazim_fmm_batch(dazim_ctx *ctx, int nx, int ny, float goxd, float
     const float goxr = g.gox + g.dnx * (float)(vnl - 1);
     for (int i = 1; i <= RM; i++) rr_tab[(size_t)(vnl - 1) * RM + i - 1] = EARTH * sinf(goxr + (float)(i - 1) * dnxr);
   }
-  float *d_rc, *d_rr, *d_veln;
-  void *p;
+  float *d_rc, *d_rr, *d_veln = veln.dev;
   if ((rc = dz_scratch(ctx, "fmm.risti_c", rc_tab.size(), &d_rc))) return rc;
   if ((rc = dz_scratch(ctx, "fmm.risti_r", rr_tab.size(), &d_rr))) return rc;
   DZ_HIP(hipMemcpyAsync(d_rc, rc_tab.data(), rc_tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   DZ_HIP(hipMemcpyAsync(d_rr, rr_tab.data(), rr_tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   DZ_HIP(hipStreamSynchronize(ctx->stream));  // the vectors above die at scope exit
-  if (veln.dev)
-    d_veln = veln.dev;
-  else {
-    if ((rc = dz_scratch(ctx, "fmm.veln", nn * kmax, &d_veln))) return rc;
-  }
+  if (!d_veln && (rc = dz_scratch(ctx, "fmm.veln", nn * kmax, &d_veln))) return rc;
   float2 *d_slown;
   int *d_vflag;
-  if ((rc = dz_scratch(ctx, "fmm.slown", (size_t)tile_records(g.nnx, g.nnz) * kmax, &d_slown)) || (rc = dz_scratch(ctx, "fmm.vflag", 16, &d_vflag))) return rc;
+  if ((rc = dz_scratch(ctx, "fmm.slown", (size_t)dz_tile_records(g.nnx, g.nnz) * kmax, &d_slown)) || (rc = dz_scratch(ctx, "fmm.vflag", 16, &d_vflag))) return rc;
   // the short exact division / square root of the quadrant solve (div_exact): node spacings of 2 .. 4096 km on the coarse grid
   // (0.25 km on the refined one) and, checked by gridder_kernel, velocities of 0.125 .. 16 km/s.  Option fmm.ieee = 1: never.
   bool fastm = dz_opt(ctx, "fmm.ieee", 0) == 0;
-  {
-    const float u1 = fabsf(EARTH * g.dnx);
-    if (!(u1 >= FAST_STEP_MIN && u1 <= FAST_STEP_MAX)) fastm = false;
-    for (float r : rc_tab) {
-      const float v1 = fabsf(r * g.dnz);
-      if (!(v1 >= FAST_STEP_MIN && v1 <= FAST_STEP_MAX)) fastm = false;
-    }
-    for (float r : rr_tab) {   // (the refined lattice: its steps are an eighth of these)
-      const float v1 = fabsf(r * g.dnz);
-      if (!(v1 >= FAST_STEP_MIN && v1 <= FAST_STEP_MAX)) fastm = false;
-    }
-  }
+  auto step_ok = [](float km) { return fabsf(km) >= FAST_STEP_MIN && fabsf(km) <= FAST_STEP_MAX; };
+  if (!step_ok(EARTH * g.dnx)) fastm = false;
+  for (float r : rc_tab) if (!step_ok(r * g.dnz)) fastm = false;
+  for (float r : rr_tab) if (!step_ok(r * g.dnz)) fastm = false;   // (the refined lattice: its steps are an eighth of these)
   ctx->ksec["fmm.fast_math"] = fastm ? 1.0 : 0.0;
   {
     DzTimer t(ctx, "gridder");
@@ -1928,109 +1977,37 @@ extern "C" int dazim_fmm_batch(dazim_ctx *ctx, int nx, int ny, float goxd, float
     t.stop();
   }
   if (nfield > 0) {
-    FmmArgs A0;
-    A0.g = g;
-    A0.nfield = nfield;
-    A0.kmax = kmax;
-    A0.pv = pv.dev;
-    A0.veln = d_veln;
-    A0.slown = d_slown;
-    A0.scx = scx.dev;
-    A0.scz = scz.dev;
-    A0.period = period.dev;
-    A0.risti_c = d_rc;
-    A0.risti_r = d_rr;
-    A0.fastm = fastm ? 1 : 0;
-    A0.vflag = d_vflag;
-    A0.ttn = ttn.dev;
-    A0.ttnr = ttnr.dev;
-    A0.nstsr = nstsr.dev;
-    A0.boxes = boxes.dev;
-    int *d_status = status.dev;
-    if (!d_status) {
-      if ((rc = dz_scratch(ctx, "fmm.status", (size_t)nfield, &d_status))) return rc;
-    }
+    auto b = std::make_shared<FmmBatch>();
+    FmmArgs &A0 = b->A;
+    A0.g = g; A0.nfield = nfield; A0.kmax = kmax;
+    A0.pv = pv.dev; A0.veln = d_veln; A0.slown = d_slown; A0.risti_c = d_rc; A0.risti_r = d_rr;
+    A0.scx = scx.dev; A0.scz = scz.dev; A0.period = period.dev;
+    A0.fastm = fastm ? 1 : 0; A0.vflag = d_vflag;
+    A0.ttn = ttn.dev; A0.ttnr = ttnr.dev; A0.nstsr = nstsr.dev; A0.boxes = boxes.dev;
+    A0.status = status.dev;
+    if (!A0.status && (rc = dz_scratch(ctx, "fmm.status", (size_t)nfield, &A0.status))) return rc;
     // Option fmm.async: return once the launch is enqueued (see dazim_ctx::fmm_finish).  Only when nothing of this call waits for
     // the launch on the host: the coarse fields stay inside the library (ttn == NULL) and every array is device-resident.
     const bool async = dz_opt(ctx, "fmm.async", 0) != 0 && !ttn_u && !pv.staged && !scx.staged && !scz.staged &&
                        !period.staged && !veln.staged && !ttnr.staged && !nstsr.staged && !boxes.staged && !status.staged &&
                        ttnr.dev && nstsr.dev && boxes.dev;
     A0.fdone = nullptr;
-    if (async) {
-      if ((rc = dz_scratch(ctx, "fmm.fdone", (size_t)nfield + 4, &A0.fdone))) return rc;
-    }
-    // LDS heap slots per field: the narrow band of an N x M grid peaks near 3*max(N,M) entries (and the
-    // 129 x 129 refined grid near 400); the smallest instantiation above that maximises the number of
-    // fields in flight per CU.  A field whose band still outgrows it is redone by the spill kernel.
-    int cap = 3 * (g.nnx > g.nnz ? g.nnx : g.nnz);
-    if (cap < 3 * RM) cap = 3 * RM;
-    if (dz_opt(ctx, "fmm.cap", 0) > 0) cap = dz_opt(ctx, "fmm.cap", 0);
-    auto hsp = std::make_shared<std::vector<int>>(nfield);
-    std::function<int()> fin;
-    const bool small = g.nnx <= 256 && g.nnz <= 256;   // node id fits 16 bits
-    bool use_hyb512 = cap > 512 && nfield > ctx->num_cu * 8 * FPW;
-    if (dz_opt(ctx, "fmm.hyb512", 0) == 1) use_hyb512 = true;
-    if (dz_opt(ctx, "fmm.hyb512", 0) == 2) use_hyb512 = false;
-    // (fmm.no_hybrid = 1 or an explicit fmm.cap: the one-level hybrid / all-LDS heaps of the branches below)
-    // The small-LDS forms trade latency for wavefronts: a batch that leaves the chip half empty anyway (fewer than 2.5 workgroups
-    // per CU) marches faster on the heaps with more levels in LDS -- 1 600 fields: 511 x 511 nodes 0.60 against 0.71 s, 341 x 341
-    // 0.21 against 0.29 s, 701 x 701 0.86 against 1.33 s; 4 800 fields: 1.08 / 0.82 s and 0.40 / 0.33 s the other way round --
-    // unless the bands would outgrow those (grids above 768 nodes a side: the all-LDS 2048-slot heap hands them to the spill kernel).
-    // fmm.hyb2 = 1 / 2 forces the small-LDS forms on / off.
-    bool use_hyb2 = cap > 768 && ((long)nfield > (long)ctx->num_cu * 10 || cap > 2304);
-    if (dz_opt(ctx, "fmm.hyb2", 0) == 1) use_hyb2 = cap > 768;
-    if (dz_opt(ctx, "fmm.hyb2", 0) == 2) use_hyb2 = false;
-    if (dz_opt(ctx, "fmm.no_hybrid", 0) != 0 || dz_opt(ctx, "fmm.cap", 0) > 0) use_hyb2 = false;
-    // Eight fields per wavefront (8 lanes per field, two quadrants per lane; round 4, option fmm.gp8): 1 = on the heaps the batch
-    // would take anyway (512 LDS slots, all-LDS up to 170-node grids, + one HBM level up to 256), 2 = 255 LDS slots + two HBM
-    // levels (1.5 KB of LDS per field).  Grids with 16-bit node ids only.  Measurements: DESIGN.md section 4.
-    const int gp8 = dz_opt(ctx, "fmm.gp8", 0);
-    if (gp8 && small && cap <= 768) {
-      if (gp8 == 2) rc = run_fmm<256, unsigned short, true, 8>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-      else if (cap <= 512) rc = run_fmm<512, unsigned short, false, 8>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-      else rc = run_fmm<512, unsigned short, true, 8>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    } else
-    if (cap <= 64) rc = small ? run_fmm<64, unsigned short>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin) : run_fmm<64, int>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    else if (cap <= 512) rc = small ? run_fmm<512, unsigned short>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin) : run_fmm<512, int>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    // grids of 171 .. 256 nodes a side (S-256) with more fields than the 768-slot heaps hold at once (8 workgroups of 4 per CU):
-    // levels 1-9 in LDS + level 10 in HBM -- 12 workgroups per CU, a third wavefront per SIMD, and time slicing (run_fmm) keeps
-    // them all busy to the end.  The 13 % of the fields whose band outgrows 511 entries pay for the HBM level (-17 % at equal
-    // occupancy), so batches that fit the 768-slot heaps stay there.  Option fmm.hyb512 = 1 / 2 forces it on / off.
-    else if (cap <= 768 && small && use_hyb512) rc = run_fmm<512, unsigned short, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    else if (cap <= 768) rc = small ? run_fmm<768, unsigned short>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin) : run_fmm<768, int>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    // grids of 257 .. 682 nodes a side (S-512): levels 1-9 in LDS, levels 10 and 11 in HBM -- 16 KB of LDS per workgroup, ten
-    // workgroups per CU instead of five.  These kernels wait on latencies (1.25 wavefronts per SIMD with 1024 LDS slots), so twice
-    // the wavefronts for one or two more dependent memory accesses per pop is a good trade: 341 x 341 nodes 20.2 -> 31.3 k
-    // fields/s against the all-LDS 1024-slot heap, S-512 7 950 -> 11 300 against levels 1-10 in LDS (same box, bit-identical).
-    // (option fmm.hyb2 = 2: the forms below)
-    else if (cap <= 2048 && use_hyb2) rc = run_fmm<512, int, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    else if (cap <= 1024) rc = run_fmm<1024, int>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    // (fmm.hyb2 = 2) grids of 342 .. 682 nodes a side: levels 1-10 in LDS + levels 11 (and, never reached there, 12) in HBM
-    else if (cap <= 2048 && dz_opt(ctx, "fmm.no_hybrid", 0) == 0) rc = run_fmm<1024, int, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    // grids above 682 nodes a side: levels 1-10 in LDS, 11 and 12 in HBM (bands up to 4 095 entries = 1 365 nodes a side without
-    // the spill kernel, five workgroups per CU instead of the two of the all-LDS 2048-slot heap)
-    else if (use_hyb2) rc = run_fmm<1024, int, true>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    else if (cap <= 1536) rc = run_fmm<1536, int>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    else rc = run_fmm<2048, int>(ctx, A0, nfield, nn, nr, d_status, hsp, async, &fin);
-    if (rc) return rc;
-    // first failing field, like the reference's STOP
-    auto first_error = [ctx, hsp, nfield]() -> int {
-      const std::vector<int> &hs = *hsp;
-      for (int i = 0; i < nfield; i++)
-        if (hs[i]) return dz_fail(ctx, hs[i], "field %d: source lies outside bounds of model", i);
-      return 0;
-    };
-    if (fin) {   // the launch is on its way: the rest when the ray call (or dazim_sync, dazim_free, the next eikonal call) asks for it
+    if (async && (rc = dz_scratch(ctx, "fmm.fdone", (size_t)nfield + 4, &A0.fdone))) return rc;
+    b->ctx = ctx; b->nfield = nfield; b->nn = nn; b->nr = nr; b->async = async;
+    b->form = fmm_pick_form(g.nnx, g.nnz, nfield, ctx->num_cu, ctx);
+    if ((rc = b->plan()) || (rc = b->scratch()) || (rc = b->field_order()) || (rc = b->progress_words()) || (rc = b->launch())) return rc;
+    if (b->async) {   // the launch is on its way: the rest when the ray call (or dazim_sync, dazim_free, the next eikonal call) asks for it
       ctx->fmm_busy = true;
       busy.keep = true;
-      ctx->fmm_finish = [ctx, fin, first_error]() -> int {
-        const int r = fin();
-        ctx->fmm_busy = false;
-        return r ? r : first_error();
+      ctx->fmm_finish = [b]() -> int {
+        const int r = b->finish();
+        b->ctx->fmm_busy = false;
+        return r ? r : b->first_error();
       };
       return 0;
     }
-    rc = first_error();
+    if ((rc = b->finish())) return rc;
+    rc = b->first_error();
   }
   int rc2;
   if ((rc2 = veln.finish()) || (rc2 = ttn.finish()) || (rc2 = ttnr.finish()) || (rc2 = nstsr.finish()) ||

@@ -830,59 +830,26 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
 #undef A
 #undef RAYS_ARGS_FRESH
 
-}  // namespace
-
-struct dazim_csr;  // sparse_internal.h
-extern "C" int dazim_csr_adopt(dazim_ctx *ctx, int64_t m, int64_t n, int64_t nnz, int64_t *rowptr, int *col,
-                               float *val, dazim_csr **out);
-
-static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, float gozd, float dvxd,
-                                  float dvzd, int kmax, const float *vels_u, int nfield, const float *scx_u,
-                                  const float *scz_u, const int *period_u, const int *kidx_u, const float *veln_u,
-                                  const float *ttn_u, const float *ttnr_u, const int *nstsr_u,
-                                  const dazim_refbox *boxes_u, int64_t nray, const int *field_u, const float *rcx_u,
-                                  const float *rcz_u, const double *svs_u, const double *svp_u, const double *srho_u,
-                                  const float *lsen_u, float *dsurf_u, dazim_csr **G, int64_t *nnz_out, int *n_boundary,
-                                  bool map = false, bool azim = false) {
-  if (!ctx || !G) return DAZIM_E_BAD_ARG;
-  // map mode (dazim_rays_build_G_maps): no model, no depth kernels; nz = 2 stands for the one "layer" of a map
-  const bool joint = map ? azim : lsen_u != nullptr;
-  if (map) nz = 2;
-  if (map && dz_opt(ctx, "rays.dense_twin", 0) != 0)
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G_maps: option rays.dense_twin serves the 3-D program's diagnostics only");
-  dazim_geom g;
-  if (dazim_geometry(nx, ny, goxd, gozd, dvxd, dvzd, &g)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad grid");
-  if (nray < 0 || nfield < 1 || nz < 2 || kmax < 1 || (size_t)g.nvx * g.nvz > 65535u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_rays_build_G");
-  // every array the kernels dereference must be there: dazim_fmm_batch can be called without the refined outputs (ttnr, nstsr,
-  // boxes nullable there), but the ray tracer reads them next to the source (inv/CalSurfG.f90:1941-1952)
-  // ttn == NULL: the coarse fields are the ones the last dazim_fmm_batch call (made with ttn == NULL) kept inside the library
-  const bool tiled = ttn_u == nullptr;
-  if (tiled && (!ctx->fields.tiled || ctx->fields.nfield != nfield || ctx->fields.nnx != g.nnx || ctx->fields.nnz != g.nnz))
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G: ttn is NULL and the last dazim_fmm_batch call did not keep %d fields of this grid inside the library (call it with ttn = NULL)", nfield);
-  if (!scx_u || !scz_u || !period_u || !veln_u || !ttnr_u || !nstsr_u || !boxes_u || !dsurf_u ||
-      (!map && (!vels_u || !svs_u || !svp_u || !srho_u)) || (nray > 0 && (!field_u || !rcx_u || !rcz_u)))
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G: NULL array (the refined fields ttnr, nstsr and boxes of dazim_fmm_batch are required)");
-  DZ_HIP(hipSetDevice(ctx->device));
-  // An asynchronous eikonal call (option fmm.async) is still marching: the count pass goes to the context's third stream, where its
-  // workgroups are dispatched as the eikonal launch's persistent workgroups leave and every quad of rays waits for its fields'
-  // completion flags -- the ray kernel fills the tail of the eikonal launch.  Only if nothing here has to wait on the host for the
-  // main stream (every array device-resident); otherwise the eikonal call is completed first.  (A pending gather of sharded
-  // dispersion tables -- dz_join_aux below -- runs on the third stream too, behind the perturbed copies it follows.)
-  bool overlap = (bool)ctx->fmm_finish && tiled && ctx->fields.fdone && nray > 0;
-  // (a pending gather of sharded dispersion tables would run on the third stream too -- dz_join_aux below --: fine with the file
-  // transport, whose collectives are host-staged; an RCCL communicator is kept to ONE stream, the main one, so with RCCL the
-  // eikonal call is completed first.)
-  if (overlap && ctx->aux_epilogue && ctx->comm && ((DzComm *)ctx->comm)->nccl) overlap = false;
-  if (overlap)
-    for (const void *q : {(const void *)vels_u, (const void *)scx_u, (const void *)scz_u, (const void *)period_u, (const void *)veln_u,
-                          (const void *)ttnr_u, (const void *)nstsr_u, (const void *)boxes_u, (const void *)field_u, (const void *)rcx_u,
-                          (const void *)rcz_u, (const void *)svs_u, (const void *)svp_u, (const void *)srho_u, (const void *)dsurf_u,
-                          (const void *)kidx_u, (const void *)lsen_u})
-      if (q && !dz_is_device_ptr(q)) overlap = false;
-  if (!overlap) {
-    const int rcf = dz_fmm_finish(ctx);
-    if (rcf) return rcf;
-  }
+// One dazim_rays_build_G* call on the host: the entry's arguments by name, what the stages hand each other, and a member function
+// per stage (run() is the order).  Members are destroyed in reverse order, so on every early return the matrix arrays go back to
+// the cache first, then the staged inputs, then the third stream is drained and the context's stream restored.
+struct RayBuild {
+  // ---- the call ----
+  dazim_ctx *ctx;
+  int nx = 0, ny = 0, nz = 0, kmax = 0, nfield = 0;
+  float goxd = 0, gozd = 0, dvxd = 0, dvzd = 0;
+  const float *vels = nullptr, *scx = nullptr, *scz = nullptr, *veln = nullptr, *ttn = nullptr, *ttnr = nullptr, *rcx = nullptr, *rcz = nullptr;
+  const float *lsen = nullptr;   // joint rows (3-D)
+  const int *period = nullptr, *kidx = nullptr, *nstsr = nullptr, *field = nullptr;
+  const dazim_refbox *boxes = nullptr;
+  const double *svs = nullptr, *svp = nullptr, *srho = nullptr;
+  int64_t nray = 0;
+  float *dsurf = nullptr;   // outputs
+  dazim_csr **G = nullptr;
+  int64_t *nnz_out = nullptr;
+  int *n_boundary = nullptr;
+  bool map = false, azim = false;   // map rows (dazim_rays_build_G_maps), with the 2-psi blocks
+  // ---- guards ----
   struct StreamSwap {   // while the count pass is prepared and launched, "the context's stream" is the third stream
     dazim_ctx *c; hipStream_t main; bool on = false;
     void restore() { if (on) { c->stream = main; on = false; } }
@@ -890,230 +857,267 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
       if (on) (void)hipStreamSynchronize(c->stream);   // (an early return: nothing of this call may still run when its buffers go)
       restore();
     }
-  } swap{ctx, ctx->stream};
-  if (overlap) {
-    DZ_HIP(hipStreamWaitEvent(ctx->stream3, ctx->ev_pre, 0));   // the velocity grids and the cleared flags, enqueued before the launch
-    ctx->stream = ctx->stream3;
-    swap.on = true;
-  }
-  {   // the depth kernels may still be in the making on the auxiliary stream (dazim_dispersion_kernels with disp.async)
-    const int rcj = dz_join_aux(ctx);
-    if (rcj) return rcj;
-  }
-  const size_t nn = (size_t)g.nnx * g.nnz, nr = (size_t)RM * RM, ncol = (size_t)nx * ny;
-  DzBuf<float> vels, scx, scz, veln, ttn, ttnr, rcx, rcz, dsurf;
-  DzBuf<int> period, kidx, nstsr, field;
-  DzBuf<dazim_refbox> boxes;
-  DzBuf<double> svs, svp, srho;
-  int rc;
-  if (!map && (rc = vels.init(ctx, vels_u, (size_t)nz * ncol, true, false))) return rc;
-  if ((rc = scx.init(ctx, scx_u, nfield, true, false))) return rc;
-  if ((rc = scz.init(ctx, scz_u, nfield, true, false))) return rc;
-  if ((rc = period.init(ctx, period_u, nfield, true, false))) return rc;
-  if ((rc = kidx.init(ctx, kidx_u ? kidx_u : period_u, nfield, true, false))) return rc;
-  if ((rc = veln.init(ctx, veln_u, nn * kmax, true, false))) return rc;
-  if (!tiled && (rc = ttn.init(ctx, ttn_u, nn * nfield, true, false))) return rc;
-  if ((rc = ttnr.init(ctx, ttnr_u, nr * nfield, true, false))) return rc;
-  if ((rc = nstsr.init(ctx, nstsr_u, nr * nfield, true, false))) return rc;
-  if ((rc = boxes.init(ctx, boxes_u, nfield, true, false))) return rc;
-  if ((rc = field.init(ctx, field_u, nray, true, false))) return rc;
-  if ((rc = rcx.init(ctx, rcx_u, nray, true, false))) return rc;
-  if ((rc = rcz.init(ctx, rcz_u, nray, true, false))) return rc;
-  const size_t nk = (size_t)nz * kmax * ncol;
-  if (!map && ((rc = svs.init(ctx, svs_u, nk, true, false)) || (rc = svp.init(ctx, svp_u, nk, true, false)) ||
-                (rc = srho.init(ctx, srho_u, nk, true, false))))
-    return rc;
-  if ((rc = dsurf.init(ctx, dsurf_u, nray, false, true))) return rc;
-  DzBuf<float> lsen;
-  if (joint && !map && (rc = lsen.init(ctx, lsen_u, (size_t)(nz - 1) * kmax * ncol, true, false))) return rc;
-  // index conventions follow the reference: periods and kernel slots 1-based (periods(srcnum,knumi), knumi), field_of_ray 0-based
-  if ((rc = dz_check_range(ctx, period.dev, nfield, 1, kmax, "period_idx"))) return rc;
-  if ((rc = dz_check_range(ctx, kidx.dev, nfield, 1, kmax, "kernel_idx"))) return rc;
-  if ((rc = dz_check_range(ctx, field.dev, nray, 0, nfield - 1, "field_of_ray"))) return rc;
-
-  RayArgs A;
-  A.g = g;
-  A.nx = nx; A.ny = ny; A.nz = nz; A.kmax = kmax;
-  A.nray = nray;
-  A.field = field.dev; A.rcx = rcx.dev; A.rcz = rcz.dev; A.scx = scx.dev; A.scz = scz.dev;
-  A.period = period.dev; A.kidx = kidx.dev; A.veln = veln.dev; A.ttn = ttn.dev; A.ttnr = ttnr.dev;
-  A.tslot = nullptr; A.tsh = 0; A.fstride = (long)nn;
-  if (tiled) {
-    A.ttn = reinterpret_cast<const float *>(ctx->fields.tiled);   // (the node word of a finished node is its time)
-    A.tslot = ctx->fields.tslot; A.tsh = ctx->fields.tsh; A.fstride = ctx->fields.stride;
-  }
-  ctx->ksec["rays.tiled_fields"] = tiled ? 1.0 : 0.0;
-  ctx->ksec["rays.map"] = map ? 1.0 : 0.0;
-  ctx->ksec["rays.overlap"] = overlap ? 1.0 : 0.0;
-  A.fdone = overlap ? ctx->fields.fdone : nullptr;
-  A.defer_mark = nullptr;
-  A.max_quads = 0;
-  A.sweeps = 1;
-  A.nstsr = nstsr.dev; A.boxes = boxes.dev; A.vels = vels.dev; A.svs = svs.dev; A.svp = svp.dev; A.srho = srho.dev;
-  A.lsen = joint && !map ? lsen.dev : nullptr;
-  A.skern = nullptr;
-  {
-    const unsigned d = (unsigned)g.nvx;
-    A.nvx_magic = (unsigned)((0x100000000ull + d - 1) / d);
-    for (unsigned c = 0; c < 65536u; c++)   // (cell ids are 16-bit: the identity is checked for all of them, once per call)
-      if ((unsigned)(((unsigned long long)c * A.nvx_magic) >> 32) != c / d) return dz_fail(ctx, DAZIM_E_BAD_ARG, "internal: reciprocal of nvx");
-  }
-  if (!map && dz_opt(ctx, "rays.skern", 1) != 0) {   // (option rays.skern = 0: every entry from the three kernels)
-    double *pk;
-    if ((rc = dz_scratch(ctx, "rays.skern", nk, &pk))) return rc;
-    hipLaunchKernelGGL(k_row_kernels, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, (long)nk, kmax, (long)ncol,
-                       vels.dev, svs.dev, svp.dev, srho.dev, pk);
-    DZ_HIP(hipGetLastError());
-    A.skern = pk;
-  }
-  {  // dpl, inv/CalSurfG.f90:1829-1833 (host libm sin, geometry only)
-    float dpl = g.dnx * EARTH;
-    float rd1 = g.dnz * EARTH * sinf(g.gox);
-    if (rd1 < dpl) dpl = rd1;
-    rd1 = g.dnz * EARTH * sinf(g.gox + (float)(g.nnx - 1) * g.dnx);
-    if (rd1 < dpl) dpl = rd1;
-    A.dplh = dpl;
-  }
-  {  // reciprocals of the loop-invariant divisors of the ray kernel (divr): the divisors as fp32 values the kernel would divide by
-    const float dnxr = g.dvx / (float)(GDX * 8), dnzr = g.dvz / (float)(GDZ * 8);   // = dazim_refbox::dnxr/dnzr (sgdl = 8, fmm.hip)
-    const float e2dnx = 2.0f * EARTH * g.dnx, e2dnxr = 2.0f * EARTH * dnxr;
-    A.r_dnx = 1.0 / (double)g.dnx;   A.r_dnz = 1.0 / (double)g.dnz;
-    A.r_dnxr = 1.0 / (double)dnxr;   A.r_dnzr = 1.0 / (double)dnzr;
-    A.r_dvx = 1.0 / (double)g.dvx;   A.r_dvz = 1.0 / (double)g.dvz;
-    A.r_e2dnx = 1.0 / (double)e2dnx; A.r_e2dnxr = 1.0 / (double)e2dnxr;
-  }
-  void *p;
-  const int64_t m = nray;
-  const size_t nr1 = (size_t)(nray > 0 ? nray : 1);
-  if ((rc = dz_scratch(ctx, "rays.status", nr1, &A.status))) return rc;
-  if ((rc = dz_scratch(ctx, "rays.rb", nr1, &A.rbflag))) return rc;
-  if ((rc = dz_scratch(ctx, "rays.count", (size_t)(m + 1), &A.count))) return rc;
-  // LDS cell lists: 512 entries keep 16 wavefronts (128 rays) on a CU, which is worth 25 % on the S-256 grid where longer lists
-  // are rare; large inversion grids (S-512: rays cross > 100 cells) get 1024.  Longer lists fall back to a full-grid sweep.
-  A.lcap = g.nvx * g.nvz <= 4096 ? 512 : 1024;
-  if (dz_opt(ctx, "rays.lcap", 0) >= 16 && dz_opt(ctx, "rays.lcap", 0) <= 8192) A.lcap = dz_opt(ctx, "rays.lcap", 0);   // tuning / test knob: small values force the fallbacks
-  if (A.lcap > g.nvx * g.nvz) A.lcap = g.nvx * g.nvz;
-  A.LK = A.lcap;   // cell lists handed from the count pass to the emit pass (longer ones are traced again)
-  A.keep_small = dz_opt(ctx, "rays.keep_small", 0) != 0 ? 1 : 0;
-  A.pts = nullptr;
-  A.npts = nullptr;
-  A.pcap = 0;
-  if (dz_opt(ctx, "rays.keep_paths", 0) != 0) {
-    // a ray advances half a cell per step: a few times (nnx + nnz) points even for a path that wanders; longer ones are flagged
-    A.pcap = 4 * (g.nnx + g.nnz) + 16;
-    if ((rc = dz_scratch(ctx, "rays.pts", nr1 * (size_t)A.pcap, &A.pts))) return rc;
-    if ((rc = dz_scratch(ctx, "rays.npts", nr1, &A.npts))) return rc;
-    DZ_HIP(hipMemsetAsync(A.npts, 0, nr1 * 4, ctx->stream));
-  }
-  ctx->ksec["rays.path_cap"] = A.pcap;
-  ctx->ksec["rays.path_rays"] = A.pts ? (double)nray : 0.0;
-  const bool twin = dz_opt(ctx, "rays.dense_twin", 0) != 0 && !A.keep_small;
-  A.dense = twin ? 2 : 0;
-  A.countd = nullptr;
-  if (twin) {
-    if ((rc = dz_scratch(ctx, "rays.countd", (size_t)(m + 1), &A.countd))) return rc;
-    DZ_HIP(hipMemsetAsync(A.countd, 0, (size_t)(m + 1) * 8, ctx->stream));
-  }
-  if ((rc = dz_scratch(ctx, "rays.nlist", nr1, &A.nlist))) return rc;
-  if ((rc = dz_scratch(ctx, "rays.lcell", nr1 * A.LK, &A.lcell))) return rc;
-  if ((rc = dz_scratch(ctx, "rays.lval", nr1 * A.LK * (joint ? 3 : 1), &A.lval))) return rc;
-  int64_t *rowptr = nullptr;
-  float *val = nullptr;
-  int *col = nullptr;
-  // the caller may announce rows it is going to append (regularisation): the CSR arrays then get that much slack and
-  // dazim_csr_append_coo writes behind the ray rows instead of reallocating and copying the matrix
-  // By default: one regularisation row per model parameter with the 7-point stencil of inv/TikhRegul.f90 (a few MB).
-  // (map mode: the 5-point stencil of dazim_csr_append_laplacian2d on every map)
-  int64_t res_rows = (int64_t)g.nvx * g.nvz * (map ? kmax : nz - 1) * (joint ? 3 : 1), res_nnz = (map ? 5 : 7) * res_rows;
-  if (dz_opt(ctx, "csr.reserve_rows", 0) > res_rows) res_rows = dz_opt(ctx, "csr.reserve_rows", 0);
-  if (dz_opt(ctx, "csr.reserve_nnz", 0) > res_nnz) res_nnz = dz_opt(ctx, "csr.reserve_nnz", 0);
-  if ((rc = dz_big_get(ctx, (size_t)(m + res_rows + 1), &rowptr))) return rc;
+  } swap;
+  struct {
+    DzBuf<float> vels, scx, scz, veln, ttn, ttnr, rcx, rcz, dsurf, lsen;
+    DzBuf<int> period, kidx, nstsr, field;
+    DzBuf<dazim_refbox> boxes;
+    DzBuf<double> svs, svp, srho;
+  } d;
   struct Arrays {   // the matrix arrays go back to the cache on every early return (until the matrix has adopted them)
-    dazim_ctx *c; int64_t *&rp; float *&v; int *&cl; bool keep = false;
+    dazim_ctx *c; int64_t *rp = nullptr; float *v = nullptr; int *cl = nullptr; int64_t nnz = 0, cap_nnz = 0; bool keep = false;
     ~Arrays() { if (!keep) { dz_big_put(c, rp); dz_big_put(c, v); dz_big_put(c, cl); } }
-  } arrays{ctx, rowptr, val, col};
-  A.dsurf = dsurf.dev;
-  A.rowptr = (const long *)rowptr;
-  A.val = nullptr;
-  A.col = nullptr;
-  const size_t lds = (size_t)A.lcap * 2 * RPW_MAX + 16;   // one cell list per ray of the wavefront
+  } arrays, arrays_d;   // G and its dense twin
+  // ---- between the stages ----
+  dazim_geom g;
+  bool joint = false, tiled = false, overlap = false, twin = false;
+  size_t nn = 0, nr = 0, ncol = 0, nk = 0, nr1 = 0, lds = 0;
+  int64_t res_rows = 0, res_nnz = 0;
+  long nwg = 0;
+  double overlap_tail_s = 0.0;
+  RayArgs A;
+  explicit RayBuild(dazim_ctx *c) : ctx(c), swap{c, c ? c->stream : nullptr}, arrays{c}, arrays_d{c} {}
+  int check() {
+    if (!ctx || !G) return DAZIM_E_BAD_ARG;
+    // map mode (dazim_rays_build_G_maps): no model, no depth kernels; nz = 2 stands for the one "layer" of a map
+    joint = map ? azim : lsen != nullptr;
+    if (map) nz = 2;
+    if (map && dz_opt(ctx, "rays.dense_twin", 0) != 0)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G_maps: option rays.dense_twin serves the 3-D program's diagnostics only");
+    if (dazim_geometry(nx, ny, goxd, gozd, dvxd, dvzd, &g)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad grid");
+    if (nray < 0 || nfield < 1 || nz < 2 || kmax < 1 || (size_t)g.nvx * g.nvz > 65535u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_rays_build_G");
+    // every array the kernels dereference must be there: dazim_fmm_batch can be called without the refined outputs (ttnr, nstsr,
+    // boxes nullable there), but the ray tracer reads them next to the source (inv/CalSurfG.f90:1941-1952)
+    // ttn == NULL: the coarse fields are the ones the last dazim_fmm_batch call (made with ttn == NULL) kept inside the library
+    tiled = ttn == nullptr;
+    if (tiled && (!ctx->fields.tiled || ctx->fields.nfield != nfield || ctx->fields.nnx != g.nnx || ctx->fields.nnz != g.nnz))
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G: ttn is NULL and the last dazim_fmm_batch call did not keep %d fields of this grid inside the library (call it with ttn = NULL)", nfield);
+    if (!scx || !scz || !period || !veln || !ttnr || !nstsr || !boxes || !dsurf ||
+        (!map && (!vels || !svs || !svp || !srho)) || (nray > 0 && (!field || !rcx || !rcz)))
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_rays_build_G: NULL array (the refined fields ttnr, nstsr and boxes of dazim_fmm_batch are required)");
+    DZ_HIP(hipSetDevice(ctx->device));
+    return 0;
+  }
+  int decide_overlap() {
+    // An asynchronous eikonal call (option fmm.async) is still marching: the count pass goes to the context's third stream, where its
+    // workgroups are dispatched as the eikonal launch's persistent workgroups leave and every quad of rays waits for its fields'
+    // completion flags -- the ray kernel fills the tail of the eikonal launch.  Only if nothing here has to wait on the host for the
+    // main stream (every array device-resident); otherwise the eikonal call is completed first.
+    overlap = (bool)ctx->fmm_finish && tiled && ctx->fields.fdone && nray > 0;
+    // (a pending gather of sharded dispersion tables would run on the third stream too -- dz_join_aux below --: fine with the file
+    // transport, whose collectives are host-staged; an RCCL communicator is kept to ONE stream, the main one, so with RCCL the
+    // eikonal call is completed first.)
+    if (overlap && ctx->aux_epilogue && ctx->comm && ((DzComm *)ctx->comm)->nccl) overlap = false;
+    if (overlap)
+      for (const void *q : {(const void *)vels, (const void *)scx, (const void *)scz, (const void *)period, (const void *)veln,
+                            (const void *)ttnr, (const void *)nstsr, (const void *)boxes, (const void *)field, (const void *)rcx,
+                            (const void *)rcz, (const void *)svs, (const void *)svp, (const void *)srho, (const void *)dsurf,
+                            (const void *)kidx, (const void *)lsen})
+        if (q && !dz_is_device_ptr(q)) overlap = false;
+    if (!overlap) { const int rcf = dz_fmm_finish(ctx); if (rcf) return rcf; }
+    if (overlap) {
+      DZ_HIP(hipStreamWaitEvent(ctx->stream3, ctx->ev_pre, 0));   // the velocity grids and the cleared flags, enqueued before the launch
+      ctx->stream = ctx->stream3;
+      swap.on = true;
+    }
+    // the depth kernels may still be in the making on the auxiliary stream (dazim_dispersion_kernels with disp.async)
+    return dz_join_aux(ctx);
+  }
+  int stage_inputs() {
+    nn = (size_t)g.nnx * g.nnz; nr = (size_t)RM * RM; ncol = (size_t)nx * ny;
+    int rc;
+    if (!map && (rc = d.vels.init(ctx, vels, (size_t)nz * ncol, true, false))) return rc;
+    if ((rc = d.scx.init(ctx, scx, nfield, true, false)) || (rc = d.scz.init(ctx, scz, nfield, true, false)) ||
+        (rc = d.period.init(ctx, period, nfield, true, false)) || (rc = d.kidx.init(ctx, kidx ? kidx : period, nfield, true, false)) ||
+        (rc = d.veln.init(ctx, veln, nn * kmax, true, false)) || (!tiled && (rc = d.ttn.init(ctx, ttn, nn * nfield, true, false))) ||
+        (rc = d.ttnr.init(ctx, ttnr, nr * nfield, true, false)) || (rc = d.nstsr.init(ctx, nstsr, nr * nfield, true, false)) ||
+        (rc = d.boxes.init(ctx, boxes, nfield, true, false)) || (rc = d.field.init(ctx, field, nray, true, false)) ||
+        (rc = d.rcx.init(ctx, rcx, nray, true, false)) || (rc = d.rcz.init(ctx, rcz, nray, true, false)))
+      return rc;
+    nk = (size_t)nz * kmax * ncol;
+    if (!map && ((rc = d.svs.init(ctx, svs, nk, true, false)) || (rc = d.svp.init(ctx, svp, nk, true, false)) ||
+                  (rc = d.srho.init(ctx, srho, nk, true, false))))
+      return rc;
+    if ((rc = d.dsurf.init(ctx, dsurf, nray, false, true))) return rc;
+    if (joint && !map && (rc = d.lsen.init(ctx, lsen, (size_t)(nz - 1) * kmax * ncol, true, false))) return rc;
+    // index conventions follow the reference: periods and kernel slots 1-based (periods(srcnum,knumi), knumi), field_of_ray 0-based
+    if ((rc = dz_check_range(ctx, d.period.dev, nfield, 1, kmax, "period_idx"))) return rc;
+    if ((rc = dz_check_range(ctx, d.kidx.dev, nfield, 1, kmax, "kernel_idx"))) return rc;
+    return dz_check_range(ctx, d.field.dev, nray, 0, nfield - 1, "field_of_ray");
+  }
+  int kernel_constants() {
+    int rc;
+    A.g = g;
+    A.nx = nx; A.ny = ny; A.nz = nz; A.kmax = kmax;
+    A.nray = nray;
+    A.field = d.field.dev; A.rcx = d.rcx.dev; A.rcz = d.rcz.dev; A.scx = d.scx.dev; A.scz = d.scz.dev;
+    A.period = d.period.dev; A.kidx = d.kidx.dev; A.veln = d.veln.dev; A.ttn = d.ttn.dev; A.ttnr = d.ttnr.dev;
+    A.tslot = nullptr; A.tsh = 0; A.fstride = (long)nn;
+    if (tiled) {
+      A.ttn = reinterpret_cast<const float *>(ctx->fields.tiled);   // (the node word of a finished node is its time)
+      A.tslot = ctx->fields.tslot; A.tsh = ctx->fields.tsh; A.fstride = ctx->fields.stride;
+    }
+    ctx->ksec["rays.tiled_fields"] = tiled ? 1.0 : 0.0;
+    ctx->ksec["rays.map"] = map ? 1.0 : 0.0;
+    ctx->ksec["rays.overlap"] = overlap ? 1.0 : 0.0;
+    A.fdone = overlap ? ctx->fields.fdone : nullptr;
+    A.defer_mark = nullptr; A.max_quads = 0; A.sweeps = 1;
+    A.nstsr = d.nstsr.dev; A.boxes = d.boxes.dev; A.vels = d.vels.dev; A.svs = d.svs.dev; A.svp = d.svp.dev; A.srho = d.srho.dev;
+    A.lsen = joint && !map ? d.lsen.dev : nullptr;
+    A.skern = nullptr;
+    {
+      const unsigned dv = (unsigned)g.nvx;
+      A.nvx_magic = (unsigned)((0x100000000ull + dv - 1) / dv);
+      for (unsigned c = 0; c < 65536u; c++)   // (cell ids are 16-bit: the identity is checked for all of them, once per call)
+        if ((unsigned)(((unsigned long long)c * A.nvx_magic) >> 32) != c / dv) return dz_fail(ctx, DAZIM_E_BAD_ARG, "internal: reciprocal of nvx");
+    }
+    if (!map && dz_opt(ctx, "rays.skern", 1) != 0) {   // (option rays.skern = 0: every entry from the three kernels)
+      double *pk;
+      if ((rc = dz_scratch(ctx, "rays.skern", nk, &pk))) return rc;
+      hipLaunchKernelGGL(k_row_kernels, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, (long)nk, kmax, (long)ncol,
+                         d.vels.dev, d.svs.dev, d.svp.dev, d.srho.dev, pk);
+      DZ_HIP(hipGetLastError());
+      A.skern = pk;
+    }
+    {  // dpl, inv/CalSurfG.f90:1829-1833 (host libm sin, geometry only)
+      float dpl = g.dnx * EARTH;
+      float rd1 = g.dnz * EARTH * sinf(g.gox);
+      if (rd1 < dpl) dpl = rd1;
+      rd1 = g.dnz * EARTH * sinf(g.gox + (float)(g.nnx - 1) * g.dnx);
+      if (rd1 < dpl) dpl = rd1;
+      A.dplh = dpl;
+    }
+    {  // reciprocals of the loop-invariant divisors of the ray kernel (divr): the divisors as fp32 values the kernel would divide by
+      const float dnxr = g.dvx / (float)(GDX * 8), dnzr = g.dvz / (float)(GDZ * 8);   // = dazim_refbox::dnxr/dnzr (sgdl = 8, fmm.hip)
+      const float e2dnx = 2.0f * EARTH * g.dnx, e2dnxr = 2.0f * EARTH * dnxr;
+      A.r_dnx = 1.0 / (double)g.dnx;   A.r_dnz = 1.0 / (double)g.dnz;
+      A.r_dnxr = 1.0 / (double)dnxr;   A.r_dnzr = 1.0 / (double)dnzr;
+      A.r_dvx = 1.0 / (double)g.dvx;   A.r_dvz = 1.0 / (double)g.dvz;
+      A.r_e2dnx = 1.0 / (double)e2dnx; A.r_e2dnxr = 1.0 / (double)e2dnxr;
+    }
+    return 0;
+  }
+  int scratch() {
+    int rc;
+    nr1 = (size_t)(nray > 0 ? nray : 1);
+    if ((rc = dz_scratch(ctx, "rays.status", nr1, &A.status))) return rc;
+    if ((rc = dz_scratch(ctx, "rays.rb", nr1, &A.rbflag))) return rc;
+    if ((rc = dz_scratch(ctx, "rays.count", (size_t)(nray + 1), &A.count))) return rc;
+    // LDS cell lists: 512 entries keep 16 wavefronts (128 rays) on a CU, which is worth 25 % on the S-256 grid where longer lists
+    // are rare; large inversion grids (S-512: rays cross > 100 cells) get 1024.  Longer lists fall back to a full-grid sweep.
+    A.lcap = g.nvx * g.nvz <= 4096 ? 512 : 1024;
+    if (dz_opt(ctx, "rays.lcap", 0) >= 16 && dz_opt(ctx, "rays.lcap", 0) <= 8192) A.lcap = dz_opt(ctx, "rays.lcap", 0);   // tuning / test knob: small values force the fallbacks
+    if (A.lcap > g.nvx * g.nvz) A.lcap = g.nvx * g.nvz;
+    A.LK = A.lcap;   // cell lists handed from the count pass to the emit pass (longer ones are traced again)
+    A.keep_small = dz_opt(ctx, "rays.keep_small", 0) != 0 ? 1 : 0;
+    A.pts = nullptr; A.npts = nullptr; A.pcap = 0;
+    if (dz_opt(ctx, "rays.keep_paths", 0) != 0) {
+      // a ray advances half a cell per step: a few times (nnx + nnz) points even for a path that wanders; longer ones are flagged
+      A.pcap = 4 * (g.nnx + g.nnz) + 16;
+      if ((rc = dz_scratch(ctx, "rays.pts", nr1 * (size_t)A.pcap, &A.pts))) return rc;
+      if ((rc = dz_scratch(ctx, "rays.npts", nr1, &A.npts))) return rc;
+      DZ_HIP(hipMemsetAsync(A.npts, 0, nr1 * 4, ctx->stream));
+    }
+    ctx->ksec["rays.path_cap"] = A.pcap;
+    ctx->ksec["rays.path_rays"] = A.pts ? (double)nray : 0.0;
+    twin = dz_opt(ctx, "rays.dense_twin", 0) != 0 && !A.keep_small;
+    A.dense = twin ? 2 : 0;
+    A.countd = nullptr;
+    if (twin) {
+      if ((rc = dz_scratch(ctx, "rays.countd", (size_t)(nray + 1), &A.countd))) return rc;
+      DZ_HIP(hipMemsetAsync(A.countd, 0, (size_t)(nray + 1) * 8, ctx->stream));
+    }
+    if ((rc = dz_scratch(ctx, "rays.nlist", nr1, &A.nlist))) return rc;
+    if ((rc = dz_scratch(ctx, "rays.lcell", nr1 * A.LK, &A.lcell))) return rc;
+    if ((rc = dz_scratch(ctx, "rays.lval", nr1 * A.LK * (joint ? 3 : 1), &A.lval))) return rc;
+    // the caller may announce rows it is going to append (regularisation): the CSR arrays then get that much slack and
+    // dazim_csr_append_coo writes behind the ray rows instead of reallocating and copying the matrix
+    // By default: one regularisation row per model parameter with the 7-point stencil of inv/TikhRegul.f90 (a few MB).
+    // (map mode: the 5-point stencil of dazim_csr_append_laplacian2d on every map)
+    res_rows = (int64_t)g.nvx * g.nvz * (map ? kmax : nz - 1) * (joint ? 3 : 1);
+    res_nnz = (map ? 5 : 7) * res_rows;
+    if (dz_opt(ctx, "csr.reserve_rows", 0) > res_rows) res_rows = dz_opt(ctx, "csr.reserve_rows", 0);
+    if (dz_opt(ctx, "csr.reserve_nnz", 0) > res_nnz) res_nnz = dz_opt(ctx, "csr.reserve_nnz", 0);
+    if ((rc = dz_big_get(ctx, (size_t)(nray + res_rows + 1), &arrays.rp))) return rc;
+    A.dsurf = d.dsurf.dev;
+    A.rowptr = (const long *)arrays.rp; A.val = nullptr; A.col = nullptr;
+    return 0;
+  }
   // the kernel of each pass: count / emit x iso / joint x column-major / tiled fields x 3-D / map rows
-  auto kern = [&](bool emit) -> const void * {
-    static const void *const tab[16] = {
-        (const void *)rays_kernel<false, false, false, false>, (const void *)rays_kernel<false, false, false, true>,
-        (const void *)rays_kernel<false, false, true, false>,  (const void *)rays_kernel<false, false, true, true>,
-        (const void *)rays_kernel<false, true, false, false>,  (const void *)rays_kernel<false, true, false, true>,
-        (const void *)rays_kernel<false, true, true, false>,   (const void *)rays_kernel<false, true, true, true>,
-        (const void *)rays_kernel<true, false, false, false>,  (const void *)rays_kernel<true, false, false, true>,
-        (const void *)rays_kernel<true, false, true, false>,   (const void *)rays_kernel<true, false, true, true>,
-        (const void *)rays_kernel<true, true, false, false>,   (const void *)rays_kernel<true, true, false, true>,
-        (const void *)rays_kernel<true, true, true, false>,    (const void *)rays_kernel<true, true, true, true>};
+  template <int I> static const void *kernel_no() { return (const void *)rays_kernel<(I & 8) != 0, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0>; }
+  const void *kern(bool emit) const {
+    static const void *const tab[16] = {kernel_no<0>(),  kernel_no<1>(),  kernel_no<2>(),  kernel_no<3>(), kernel_no<4>(),  kernel_no<5>(),
+                                        kernel_no<6>(),  kernel_no<7>(),  kernel_no<8>(),  kernel_no<9>(), kernel_no<10>(), kernel_no<11>(),
+                                        kernel_no<12>(), kernel_no<13>(), kernel_no<14>(), kernel_no<15>()};
     return tab[(emit ? 8 : 0) + (joint ? 4 : 0) + (tiled ? 2 : 0) + (map ? 1 : 0)];
-  };
-  auto launch = [&](bool emit, const RayArgs &R, long nwg_) -> int {
+  }
+  int launch(bool emit, const RayArgs &R, long nwg_) {
     RayArgs args = R;
     void *params[] = {&args};
     DZ_HIP(hipLaunchKernel(kern(emit), dim3((unsigned)nwg_), dim3(64), params, lds, ctx->stream));
     return 0;
-  };
-  DZ_HIP(hipFuncSetAttribute(kern(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  DZ_HIP(hipFuncSetAttribute(kern(true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int per_cu = (int)(160 * 1024 / (lds + 256));
-  {   // resident workgroups per CU are limited by LDS or by registers (3 wavefronts per SIMD): persistent workgroups beyond
-      // that only queue up behind the resident ones and unbalance the XCD-ordered ray ranges
-    int occ = 0;
-    const void *kf = kern(false);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kf, 64, lds) == hipSuccess && occ > 0 && occ < per_cu) per_cu = occ;
   }
-  if (per_cu > 16) per_cu = 16;
-  if (per_cu < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "inversion grid too large for the LDS cell lists");
-  if (dz_opt(ctx, "rays.wg_per_cu", 0) > 0 && dz_opt(ctx, "rays.wg_per_cu", 0) < per_cu) per_cu = dz_opt(ctx, "rays.wg_per_cu", 0);
-  long nwg = (long)ctx->num_cu * per_cu;
-  if (nwg > (nray + RPW_MAX - 1) / RPW_MAX) nwg = (nray + RPW_MAX - 1) / RPW_MAX;
-  if (nwg >= 8) nwg -= nwg % 8;   // the XCD-aware ray order wants a multiple of 8
-  if (nwg < 1) nwg = 1;
-  if ((rc = dz_scratch(ctx, "rays.fdm", (size_t)nwg * RPW_MAX * (g.nvx + 2) * (g.nvz + 2) * (joint ? 3 : 1), &A.fdm_scratch))) return rc;
-  A.perm = nullptr;
-  if (nray >= 64 && nray < (1ll << 32) && dz_opt(ctx, "rays.sort", 1) != 0) {
-    int fbits = 1;
-    while ((1ll << fbits) < nfield) fbits++;
-    const int dbits = 32 - fbits > 12 ? 12 : 32 - fbits;
-    if (dbits >= 4) {
-      unsigned *k0, *k1, *v0, *v1;
-      if ((rc = dz_scratch(ctx, "rays.sortbuf", (size_t)nray * 4 + 16, &k0))) return rc;
-      k1 = k0 + nray; v0 = k1 + nray; v1 = v0 + nray;
-      const float ex = (float)g.nnx * g.dnx, ez = (float)g.nnz * g.dnz;
-      const float inv_dmax = 1.0f / sqrtf(ex * ex + ez * ez);
-      hipLaunchKernelGGL(k_ray_keys, dim3((unsigned)((nray + 255) / 256)), dim3(256), 0, ctx->stream, (long)nray, field.dev, scx.dev,
-                         scz.dev, rcx.dev, rcz.dev, inv_dmax, dbits, k0, v0, overlap ? A.tslot : (const int *)nullptr);
-      size_t tb = 0;
-      DZ_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0, k1, v0, v1, (size_t)nray, 0, fbits + dbits, ctx->stream));
-      void *tmp;
-      if ((rc = dz_scratch(ctx, "rays.sorttmp", tb + 256, &tmp))) return rc;
-      DZ_HIP(rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, v1, (size_t)nray, 0, fbits + dbits, ctx->stream));
-      A.perm = v1;
+  int launch_shape() {
+    lds = (size_t)A.lcap * 2 * RPW_MAX + 16;   // one cell list per ray of the wavefront
+    DZ_HIP(hipFuncSetAttribute(kern(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DZ_HIP(hipFuncSetAttribute(kern(true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int per_cu = (int)(160 * 1024 / (lds + 256));
+    {   // resident workgroups per CU are limited by LDS or by registers (3 wavefronts per SIMD): persistent workgroups beyond
+        // that only queue up behind the resident ones and unbalance the XCD-ordered ray ranges
+      int occ = 0;
+      const void *kf = kern(false);
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kf, 64, lds) == hipSuccess && occ > 0 && occ < per_cu) per_cu = occ;
     }
+    if (per_cu > 16) per_cu = 16;
+    if (per_cu < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "inversion grid too large for the LDS cell lists");
+    if (dz_opt(ctx, "rays.wg_per_cu", 0) > 0 && dz_opt(ctx, "rays.wg_per_cu", 0) < per_cu) per_cu = dz_opt(ctx, "rays.wg_per_cu", 0);
+    nwg = (long)ctx->num_cu * per_cu;
+    if (nwg > (nray + RPW_MAX - 1) / RPW_MAX) nwg = (nray + RPW_MAX - 1) / RPW_MAX;
+    if (nwg >= 8) nwg -= nwg % 8;   // the XCD-aware ray order wants a multiple of 8
+    if (nwg < 1) nwg = 1;
+    return dz_scratch(ctx, "rays.fdm", (size_t)nwg * RPW_MAX * (g.nvx + 2) * (g.nvz + 2) * (joint ? 3 : 1), &A.fdm_scratch);
   }
-  if ((rc = dz_scratch(ctx, "rays.qcount", 32, &A.qcount))) return rc;
-  DZ_HIP(hipMemsetAsync(A.qcount, 0, 128, ctx->stream));
-  int64_t nnz = 0;
-  double overlap_tail_s = 0.0;
-  if (overlap) {
-    const size_t nq = (size_t)((nray + RPW_MAX - 1) / RPW_MAX) + 8;
-    if ((rc = dz_scratch(ctx, "rays.defer", nq, &A.defer_mark))) return rc;
-    DZ_HIP(hipMemsetAsync(A.defer_mark, 0, nq * 4, ctx->stream));
+  int sort_rays() {   // ... and the task counters of the passes
+    int rc;
+    A.perm = nullptr;
+    if (nray >= 64 && nray < (1ll << 32) && dz_opt(ctx, "rays.sort", 1) != 0) {
+      int fbits = 1;
+      while ((1ll << fbits) < nfield) fbits++;
+      const int dbits = 32 - fbits > 12 ? 12 : 32 - fbits;
+      if (dbits >= 4) {
+        unsigned *k0, *k1, *v0, *v1;
+        if ((rc = dz_scratch(ctx, "rays.sortbuf", (size_t)nray * 4 + 16, &k0))) return rc;
+        k1 = k0 + nray; v0 = k1 + nray; v1 = v0 + nray;
+        const float ex = (float)g.nnx * g.dnx, ez = (float)g.nnz * g.dnz;
+        const float inv_dmax = 1.0f / sqrtf(ex * ex + ez * ez);
+        hipLaunchKernelGGL(k_ray_keys, dim3((unsigned)((nray + 255) / 256)), dim3(256), 0, ctx->stream, (long)nray, d.field.dev, d.scx.dev,
+                           d.scz.dev, d.rcx.dev, d.rcz.dev, inv_dmax, dbits, k0, v0, overlap ? A.tslot : (const int *)nullptr);
+        size_t tb = 0;
+        DZ_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0, k1, v0, v1, (size_t)nray, 0, fbits + dbits, ctx->stream));
+        void *tmp;
+        if ((rc = dz_scratch(ctx, "rays.sorttmp", tb + 256, &tmp))) return rc;
+        DZ_HIP(rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, v1, (size_t)nray, 0, fbits + dbits, ctx->stream));
+        A.perm = v1;
+      }
+    }
+    if ((rc = dz_scratch(ctx, "rays.qcount", 32, &A.qcount))) return rc;
+    DZ_HIP(hipMemsetAsync(A.qcount, 0, 128, ctx->stream));
+    if (overlap) {
+      const size_t nq = (size_t)((nray + RPW_MAX - 1) / RPW_MAX) + 8;
+      if ((rc = dz_scratch(ctx, "rays.defer", nq, &A.defer_mark))) return rc;
+      DZ_HIP(hipMemsetAsync(A.defer_mark, 0, nq * 4, ctx->stream));
+    }
+    return 0;
   }
-  DzTimer t(ctx, "rays");
-  DZ_HIP(hipMemsetAsync(A.count, 0, (size_t)(m + 1) * 8, ctx->stream));
-  if (!overlap) {
-    if (nray > 0 && (rc = launch(false, A, nwg))) return rc;
-  } else {
-    // ---- the count pass beside the eikonal launch's tail: a sequence of NON-BLOCKING passes on the third stream ----
-    // A pass traces every quad of rays whose fields are finished and marks the others; the host launches the next pass a moment
-    // later for the marked ones, and a last one after the eikonal call is complete (spill reruns included).  The first pass goes
-    // out when the eikonal launch's task queue is nearly empty (the kernel reports the tasks it has handed out through
-    // host-mapped words): from then on its workgroups leave and the passes' workgroups take their slots.  No ray workgroup ever
-    // waits for the eikonal kernel, so nothing depends on which launch's wavefronts the hardware keeps resident.
+  int count_pass() { return nray > 0 ? launch(false, A, nwg) : 0; }
+  // ---- the count pass beside the eikonal launch's tail: a sequence of NON-BLOCKING passes on the third stream ----
+  // A pass traces every quad of rays whose fields are finished and marks the others; the host launches the next pass a moment
+  // later for the marked ones, and a last one after the eikonal call is complete (spill reruns included).  The first pass goes
+  // out when the eikonal launch's task queue is nearly empty (the kernel reports the tasks it has handed out through
+  // host-mapped words): from then on its workgroups leave and the passes' workgroups take their slots.  No ray workgroup ever
+  // waits for the eikonal kernel, so nothing depends on which launch's wavefronts the hardware keeps resident.
+  int count_passes_beside_eikonal() {
+    int rc;
     const auto t_poll0 = std::chrono::steady_clock::now();
     auto fmm_over = [&]() {
       const bool over = hipEventQuery(ctx->ev_f1) == hipSuccess;
@@ -1173,93 +1177,94 @@ static int rays_build_impl(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, f
     if (rcf) return rcf;
     ctx->ksec["rays.passes"] = npass;
     ctx->ksec["rays.deferred_quads"] = left_by_first;   // quads the first pass had to leave (fields still marching, or waiting for their rerun)
-    A.fdone = nullptr;
-    A.defer_mark = nullptr;
-    A.max_quads = 0;
-    A.sweeps = 1;
+    A.fdone = nullptr; A.defer_mark = nullptr; A.max_quads = 0; A.sweeps = 1;
     // what the step pays for the rays: from the end of the eikonal launch on (the passes' share beside it is free) = the last
     // pass beside the launch, as far as it outlasted it, + everything below
     float ms_tail = 0;
     if (hipEventElapsedTime(&ms_tail, ctx->ev_f1, ctx->ev_r1) == hipSuccess && ms_tail > 0) overlap_tail_s = ms_tail * 1e-3;
     if (!ev0_set) (void)hipEventRecord(ctx->ev0, ctx->stream);
+    return 0;
   }
-  {  // exclusive scan of the row counts -> rowptr
-    size_t tb = 0;
-    DZ_HIP(rocprim::exclusive_scan(nullptr, tb, A.count, (long *)rowptr, 0l, (size_t)(m + 1), rocprim::plus<long>(), ctx->stream));
+  // exclusive scan of the row counts -> M.rp, the arrays of that many entries (+ slack), the emit pass.  G, and then its dense
+  // twin: a second emit pass over the saved cell lists (no ray is traced again unless its list did not fit)
+  int scan_and_emit(Arrays &M, long *count, int64_t slack, bool dense_twin) {
+    int rc; void *p; size_t tb = 0;
+    DZ_HIP(rocprim::exclusive_scan(nullptr, tb, count, (long *)M.rp, 0l, (size_t)(nray + 1), rocprim::plus<long>(), ctx->stream));
     if ((rc = dz_scratch(ctx, "rays.scan", tb + 256, &p))) return rc;
-    DZ_HIP(rocprim::exclusive_scan(p, tb, A.count, (long *)rowptr, 0l, (size_t)(m + 1), rocprim::plus<long>(), ctx->stream));
-    DZ_HIP(hipMemcpyAsync(&nnz, rowptr + m, 8, hipMemcpyDeviceToHost, ctx->stream));
+    DZ_HIP(rocprim::exclusive_scan(p, tb, count, (long *)M.rp, 0l, (size_t)(nray + 1), rocprim::plus<long>(), ctx->stream));
+    DZ_HIP(hipMemcpyAsync(&M.nnz, M.rp + nray, 8, hipMemcpyDeviceToHost, ctx->stream));
     DZ_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  const int64_t cap_nnz = nnz + res_nnz;   // (options csr.reserve_rows / csr.reserve_nnz: room for rows appended later)
-  if ((rc = dz_big_get(ctx, (size_t)(cap_nnz > 0 ? cap_nnz : 1), &val)) || (rc = dz_big_get(ctx, (size_t)(cap_nnz > 0 ? cap_nnz : 1), &col))) return rc;
-  A.val = val;
-  A.col = col;
-  if (nray > 0 && (rc = launch(true, A, nwg))) return rc;
-  // ---- the dense twin: a second emit pass over the saved cell lists (no ray is traced again unless its list did not fit) ----
-  int64_t *rowptr_d = nullptr;
-  float *val_d = nullptr;
-  int *col_d = nullptr;
-  Arrays arrays_d{ctx, rowptr_d, val_d, col_d};
-  int64_t nnz_d = 0;
-  if (twin) {
-    if ((rc = dz_big_get(ctx, (size_t)(m + 1), &rowptr_d))) return rc;
-    size_t tb = 0;
-    DZ_HIP(rocprim::exclusive_scan(nullptr, tb, A.countd, (long *)rowptr_d, 0l, (size_t)(m + 1), rocprim::plus<long>(), ctx->stream));
-    if ((rc = dz_scratch(ctx, "rays.scan", tb + 256, &p))) return rc;
-    DZ_HIP(rocprim::exclusive_scan(p, tb, A.countd, (long *)rowptr_d, 0l, (size_t)(m + 1), rocprim::plus<long>(), ctx->stream));
-    DZ_HIP(hipMemcpyAsync(&nnz_d, rowptr_d + m, 8, hipMemcpyDeviceToHost, ctx->stream));
-    DZ_HIP(hipStreamSynchronize(ctx->stream));
-    if ((rc = dz_big_get(ctx, (size_t)(nnz_d > 0 ? nnz_d : 1), &val_d)) || (rc = dz_big_get(ctx, (size_t)(nnz_d > 0 ? nnz_d : 1), &col_d))) return rc;
-    RayArgs D = A;
-    D.dense = 1;
-    D.rowptr = (const long *)rowptr_d;
-    D.val = val_d;
-    D.col = col_d;
-    DZ_HIP(hipMemsetAsync(A.qcount + 8, 0, 32, ctx->stream));   // the emit pass's task counters
-    if (nray > 0 && (rc = launch(true, D, nwg))) return rc;
-  }
-  t.stop();
-  if (overlap) {
-    ctx->ksec["rays.after_fmm_count"] = overlap_tail_s;
-    ctx->ksec["rays"] += overlap_tail_s;
-  }
-  // statuses: first failing ray is the reference's STOP
-  std::vector<int> hs(nr1), hb(nr1);
-  unsigned hq[2] = {0, 0};
-  if (nray > 0) DZ_HIP(hipMemcpyAsync(hq, A.qcount + 16, 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (nray > 0) {
-    DZ_HIP(hipMemcpyAsync(hs.data(), A.status, nray * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DZ_HIP(hipMemcpyAsync(hb.data(), A.rbflag, nray * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DZ_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  int nb = 0, err = 0;
-  for (int64_t i = 0; i < nray; i++) {
-    nb += hb[i];
-    if (hs[i] && !err) err = dz_fail(ctx, hs[i], "ray %ld: receiver lies outside model", (long)i);
-  }
-  if (n_boundary) *n_boundary = nb;
-  if (nnz_out) *nnz_out = nnz;
-  ctx->ksec["rays.list_sweeps"] = hq[0];     // rays that took the full-grid sweep instead of the LDS cell list
-  ctx->ksec["rays.list_retraced"] = hq[1];   // rays the emit pass traced a second time
-  ctx->ksec["rays.lcap"] = A.lcap;
-  if ((rc = dsurf.finish())) return rc;
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  if (err) return err;
-  const int64_t n = (int64_t)g.nvx * g.nvz * (map ? kmax : nz - 1) * (joint ? 3 : 1);
-  arrays.keep = true;   // adopted (dz_csr_adopt_cap frees them itself if it fails)
-  if ((rc = dz_csr_adopt_cap(ctx, m, n, nnz, rowptr, col, val, m + res_rows, cap_nnz, G))) return rc;
-  if (twin) {
-    dazim_csr *Gd = nullptr;
-    arrays_d.keep = true;
-    if ((rc = dz_csr_adopt_cap(ctx, m, n, nnz_d, rowptr_d, col_d, val_d, 0, 0, &Gd)) || (rc = dz_csr_set_twin(ctx, *G, Gd))) {
-      dazim_csr_free(ctx, *G);
-      *G = nullptr;
-      return rc;
+    M.cap_nnz = M.nnz + slack;   // (options csr.reserve_rows / csr.reserve_nnz: room for rows appended later)
+    const size_t cap = (size_t)(M.cap_nnz > 0 ? M.cap_nnz : 1);
+    if ((rc = dz_big_get(ctx, cap, &M.v)) || (rc = dz_big_get(ctx, cap, &M.cl))) return rc;
+    RayArgs R = A;
+    R.rowptr = (const long *)M.rp; R.val = M.v; R.col = M.cl;
+    if (dense_twin) {
+      R.dense = 1;
+      DZ_HIP(hipMemsetAsync(A.qcount + 8, 0, 32, ctx->stream));   // the emit pass's task counters
     }
+    return nray > 0 ? launch(true, R, nwg) : 0;
   }
-  return 0;
-}
+  int statuses() {   // first failing ray is the reference's STOP
+    int rc;
+    std::vector<int> hs(nr1), hb(nr1);
+    unsigned hq[2] = {0, 0};
+    if (nray > 0) {
+      DZ_HIP(hipMemcpyAsync(hq, A.qcount + 16, 8, hipMemcpyDeviceToHost, ctx->stream));
+      DZ_HIP(hipMemcpyAsync(hs.data(), A.status, nray * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DZ_HIP(hipMemcpyAsync(hb.data(), A.rbflag, nray * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DZ_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    int nb = 0, err = 0;
+    for (int64_t i = 0; i < nray; i++) {
+      nb += hb[i];
+      if (hs[i] && !err) err = dz_fail(ctx, hs[i], "ray %ld: receiver lies outside model", (long)i);
+    }
+    if (n_boundary) *n_boundary = nb;
+    if (nnz_out) *nnz_out = arrays.nnz;
+    ctx->ksec["rays.list_sweeps"] = hq[0];     // rays that took the full-grid sweep instead of the LDS cell list
+    ctx->ksec["rays.list_retraced"] = hq[1];   // rays the emit pass traced a second time
+    ctx->ksec["rays.lcap"] = A.lcap;
+    if ((rc = d.dsurf.finish())) return rc;
+    DZ_HIP(hipStreamSynchronize(ctx->stream));
+    return err;
+  }
+  int adopt() {
+    int rc;
+    const int64_t n = (int64_t)g.nvx * g.nvz * (map ? kmax : nz - 1) * (joint ? 3 : 1);
+    arrays.keep = true;   // adopted (dz_csr_adopt_cap frees them itself if it fails)
+    if ((rc = dz_csr_adopt_cap(ctx, nray, n, arrays.nnz, arrays.rp, arrays.cl, arrays.v, nray + res_rows, arrays.cap_nnz, G))) return rc;
+    if (twin) {
+      dazim_csr *Gd = nullptr;
+      arrays_d.keep = true;
+      if ((rc = dz_csr_adopt_cap(ctx, nray, n, arrays_d.nnz, arrays_d.rp, arrays_d.cl, arrays_d.v, 0, 0, &Gd)) || (rc = dz_csr_set_twin(ctx, *G, Gd))) {
+        dazim_csr_free(ctx, *G);
+        *G = nullptr;
+        return rc;
+      }
+    }
+    return 0;
+  }
+  int run() {
+    int rc;
+    if ((rc = check()) || (rc = decide_overlap()) || (rc = stage_inputs()) || (rc = kernel_constants()) || (rc = scratch()) ||
+        (rc = launch_shape()) || (rc = sort_rays()))
+      return rc;
+    DzTimer t(ctx, "rays");
+    DZ_HIP(hipMemsetAsync(A.count, 0, (size_t)(nray + 1) * 8, ctx->stream));
+    if ((rc = overlap ? count_passes_beside_eikonal() : count_pass())) return rc;
+    if ((rc = scan_and_emit(arrays, A.count, res_nnz, false))) return rc;
+    if (twin && ((rc = dz_big_get(ctx, (size_t)(nray + 1), &arrays_d.rp)) || (rc = scan_and_emit(arrays_d, A.countd, 0, true)))) return rc;
+    t.stop();
+    if (overlap) {
+      ctx->ksec["rays.after_fmm_count"] = overlap_tail_s;
+      ctx->ksec["rays"] += overlap_tail_s;
+    }
+    return (rc = statuses()) ? rc : adopt();
+  }
+};
+
+}  // namespace
 
 // = the receiver loop of CalSurfG (inv/CalSurfG.f90:1326-1364) for every ray of a batch of fields
 extern "C" int dazim_rays_build_G(dazim_ctx *ctx, int nx, int ny, int nz, float goxd, float gozd, float dvxd,
@@ -1269,8 +1274,14 @@ extern "C" int dazim_rays_build_G(dazim_ctx *ctx, int nx, int ny, int nz, float 
                                   int64_t nray, const int *field, const float *rcx, const float *rcz,
                                   const double *svs, const double *svp, const double *srho, float *dsurf,
                                   dazim_csr **G, int64_t *nnz_out, int *n_boundary) {
-  return rays_build_impl(ctx, nx, ny, nz, goxd, gozd, dvxd, dvzd, kmax, vels, nfield, scx, scz, period, kidx, veln, ttn, ttnr,
-                         nstsr, boxes, nray, field, rcx, rcz, svs, svp, srho, nullptr, dsurf, G, nnz_out, n_boundary);
+  RayBuild b(ctx);
+  b.nx = nx; b.ny = ny; b.nz = nz; b.goxd = goxd; b.gozd = gozd; b.dvxd = dvxd; b.dvzd = dvzd;
+  b.kmax = kmax; b.vels = vels; b.svs = svs; b.svp = svp; b.srho = srho;
+  b.nfield = nfield; b.scx = scx; b.scz = scz; b.period = period; b.kidx = kidx;
+  b.veln = veln; b.ttn = ttn; b.ttnr = ttnr; b.nstsr = nstsr; b.boxes = boxes;
+  b.nray = nray; b.field = field; b.rcx = rcx; b.rcz = rcz;
+  b.dsurf = dsurf; b.G = G; b.nnz_out = nnz_out; b.n_boundary = n_boundary;
+  return b.run();
 }
 // = the receiver loop of CalSurfGAnisoJoint (inv/CalSurfGAniso_Joint.f90:680-752): rpathsAzim and rows
 // with the three column blocks dVs | Gc | Gs; lsen = Lsen_Gsc from depthkernelTI (TI kernels, an input)
@@ -1283,8 +1294,14 @@ extern "C" int dazim_rays_build_G_joint(dazim_ctx *ctx, int nx, int ny, int nz, 
                                         const float *lsen, float *dsurf, dazim_csr **G, int64_t *nnz_out,
                                         int *n_boundary) {
   if (!lsen) return dz_fail(ctx, DAZIM_E_BAD_ARG, "joint mode needs Lsen_Gsc");
-  return rays_build_impl(ctx, nx, ny, nz, goxd, gozd, dvxd, dvzd, kmax, vels, nfield, scx, scz, period, kidx, veln, ttn, ttnr,
-                         nstsr, boxes, nray, field, rcx, rcz, svs, svp, srho, lsen, dsurf, G, nnz_out, n_boundary);
+  RayBuild b(ctx);
+  b.nx = nx; b.ny = ny; b.nz = nz; b.goxd = goxd; b.gozd = gozd; b.dvxd = dvxd; b.dvzd = dvzd;
+  b.kmax = kmax; b.vels = vels; b.svs = svs; b.svp = svp; b.srho = srho; b.lsen = lsen;
+  b.nfield = nfield; b.scx = scx; b.scz = scz; b.period = period; b.kidx = kidx;
+  b.veln = veln; b.ttn = ttn; b.ttnr = ttnr; b.nstsr = nstsr; b.boxes = boxes;
+  b.nray = nray; b.field = field; b.rcx = rcx; b.rcz = rcz;
+  b.dsurf = dsurf; b.G = G; b.nnz_out = nnz_out; b.n_boundary = n_boundary;
+  return b.run();
 }
 
 // Map rows (the per-period phase-velocity / 2-psi map inversion): the same receiver loop with the Frechet values themselves as the
@@ -1296,9 +1313,14 @@ extern "C" int dazim_rays_build_G_maps(dazim_ctx *ctx, int nx, int ny, float gox
                                        const float *veln, const float *ttn, const float *ttnr, const int *nstsr,
                                        const dazim_refbox *boxes, int64_t nray, const int *field, const float *rcx,
                                        const float *rcz, float *dsurf, dazim_csr **G, int64_t *nnz_out, int *n_boundary) {
-  return rays_build_impl(ctx, nx, ny, 2, goxd, gozd, dvxd, dvzd, kmax, nullptr, nfield, scx, scz, period, nullptr, veln, ttn, ttnr,
-                         nstsr, boxes, nray, field, rcx, rcz, nullptr, nullptr, nullptr, nullptr, dsurf, G, nnz_out, n_boundary,
-                         true, azim != 0);
+  RayBuild b(ctx);
+  b.map = true; b.azim = azim != 0;
+  b.nx = nx; b.ny = ny; b.nz = 2; b.goxd = goxd; b.gozd = gozd; b.dvxd = dvxd; b.dvzd = dvzd;
+  b.kmax = kmax; b.nfield = nfield; b.scx = scx; b.scz = scz; b.period = period;
+  b.veln = veln; b.ttn = ttn; b.ttnr = ttnr; b.nstsr = nstsr; b.boxes = boxes;
+  b.nray = nray; b.field = field; b.rcx = rcx; b.rcz = rcz;
+  b.dsurf = dsurf; b.G = G; b.nnz_out = nnz_out; b.n_boundary = n_boundary;
+  return b.run();
 }
 
 // The ray geometries of the last dazim_rays_build_G[_joint] call made with option "rays.keep_paths" = 1: what the reference

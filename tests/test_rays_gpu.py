@@ -503,3 +503,93 @@ def test_asynchronous_eikonal_call_reports_its_error_when_collected(ctx):
     finally:
         ctx.set_option("fmm.async", 0)
         ctx.set_option("fmm.ts", 0)
+
+
+def _resident_case(ctx, joint):
+    """the 17 x 15 case of the tests above with every array device-resident, and a function that runs the eikonal call (fields kept
+    in tiles) and the ray call once with the options as they stand; returns what the ray call gave and the refined outputs"""
+    import torch
+    nx, ny, kmax = 17, 15, 3
+    depz = np.array([0.0, 10.0, 35.0, 60.0], np.float32)
+    t = np.array([8.0, 14.0, 22.0])
+    vel, scxf, sczf, rcxf, rczf, nrc1, nsrc1, periods = build_case(nx, ny, depz, kmax, 9, 6, 3)
+    host = flatten(scxf, sczf, rcxf, rczf, nrc1, nsrc1, periods)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d_vel = T(vel)
+    pv, sen, _ = ctx.depthkernel(d_vel, depz, t, 2.0)
+    lsen = ctx.ti_kernels(d_vel, depz, t, 2.0, pv) if joint else None
+    d = [T(a) for a in host]
+    g = ctx.fmm_batch(nx, ny, 30.0, 100.0, 0.25, 0.25, pv.cpu().numpy(), *host[:3])["geom"]
+    nf = len(host[0])
+
+    def run(rx=None, rz=None):
+        bufs = dict(veln=torch.empty((kmax, g.nnx, g.nnz), dtype=torch.float32, device="cuda"),
+                    ttnr=torch.zeros((nf, 129, 129), dtype=torch.float32, device="cuda"),
+                    nstsr=torch.zeros((nf, 129, 129), dtype=torch.int32, device="cuda"),
+                    boxes=torch.zeros((nf, 12), dtype=torch.int32, device="cuda"),
+                    status=torch.zeros((nf,), dtype=torch.int32, device="cuda"))
+        fields = ctx.fmm_batch(nx, ny, 30.0, 100.0, 0.25, 0.25, pv, d[0], d[1], d[2], keep_fields=True, **bufs)
+        G, tpred, nb = ctx.rays_build_G(nx, ny, 30.0, 100.0, 0.25, 0.25, d_vel, fields, d[0], d[1], d[2], d[3],
+                                        d[4] if rx is None else T(rx), d[5] if rz is None else T(rz), sen, lsen=lsen)
+        return G, tpred.cpu().numpy(), nb, bufs["ttnr"].cpu().numpy(), bufs["nstsr"].cpu().numpy()
+    return host, run
+
+
+@pytest.mark.parametrize("joint", [False, True])
+def test_dense_twin_beside_an_asynchronous_eikonal_launch_equals_the_synchronous_run(ctx, joint):
+    """option rays.dense_twin with the count pass run as non-blocking passes beside the eikonal launch (fmm.async, rays.overlap = 1):
+    the twin's row counts are gathered by those passes and its scan + emit follow G's -- G, the twin, predicted times, boundary
+    count and the refined outputs must be the bits of the synchronous run"""
+    _, run = _resident_case(ctx, joint)
+    res = []
+    try:
+        ctx.set_option("fmm.ts", 1)
+        ctx.set_option("rays.dense_twin", 1)
+        for asyn in (0, 1):
+            ctx.set_option("fmm.async", asyn)
+            G, tpred, nb, ttnr, nstsr = run()
+            assert ctx.stat("rays.overlap") == float(asyn)
+            Gd = G.take_twin()
+            assert Gd is not None and Gd.nnz > G.nnz
+            res.append((G.to_coo(), Gd.to_coo(), tpred, nb, ttnr, nstsr))
+            Gd.free(); G.free()
+    finally:
+        for k in ("fmm.async", "fmm.ts", "rays.dense_twin"):
+            ctx.set_option(k, 0)
+    a, b = res
+    for x, y in zip(a[0] + a[1], b[0] + b[1]):
+        assert np.array_equal(x, y)
+    assert np.array_equal(a[2], b[2]) and a[3] == b[3] and np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5]) and a[2].min() > 0
+
+
+def test_receiver_outside_under_overlap_leaves_a_usable_context(ctx):
+    """a receiver far outside the grid in a ray call whose count pass ran beside an asynchronous eikonal launch: the call returns the
+    reference's STOP condition after it has collected the eikonal call, puts the matrix arrays back and restores the context's
+    stream -- the same context then gives the same bits asynchronously and synchronously"""
+    import dazimsurftomo_amd as dz
+    host, run = _resident_case(ctx, False)
+    rx, rz = host[4].copy(), host[5].copy()
+    ox, oz = synth.radians([45.0], [101.0])
+    rx[7], rz[7] = ox[0], oz[0]
+    res = []
+    try:
+        ctx.set_option("fmm.ts", 1)
+        ctx.set_option("fmm.async", 1)
+        with pytest.raises(dz.DazimError) as e:
+            run(rx, rz)
+        assert e.value.code == dz.DAZIM_E_RECEIVER_OUTSIDE
+        assert ctx.stat("rays.overlap") == 1.0        # the failing call did run its count pass beside the launch
+        ctx.sync()                                   # the eikonal call has been collected: nothing is pending
+        for asyn in (1, 0):
+            ctx.set_option("fmm.async", asyn)
+            G, tpred, nb, _, _ = run()
+            assert ctx.stat("rays.overlap") == float(asyn)
+            res.append((G.to_coo(), tpred))
+            G.free()
+    finally:
+        ctx.set_option("fmm.async", 0)
+        ctx.set_option("fmm.ts", 0)
+    (coo_a, tp_a), (coo_s, tp_s) = res
+    for x, y in zip(coo_a, coo_s):
+        assert np.array_equal(x, y)
+    assert np.array_equal(tp_a, tp_s) and tp_a.min() > 0
