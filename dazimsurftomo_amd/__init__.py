@@ -57,6 +57,11 @@ def to_radians(lat_deg, lon_deg):
         (lon * PI_F32 / np.float32(180.0)).astype(np.float32)
 
 
+# dazim_lsmr_rec (include/dazim.h), and the byte Context.lsmr fills its trace array with before the call
+LSMR_REC = np.dtype([("itn", "<i4")] + [(k, "<f4") for k in ("x1", "normr", "normAr", "test1", "test2", "test3", "rtol", "normA", "condA")])
+LSMR_TRACE_FILL = 0xA5
+
+
 def comm_unique_id():
     """128-byte RCCL id (rank 0 creates it and sends it to the other ranks)"""
     buf = C.create_string_buffer(128)
@@ -467,8 +472,11 @@ class Context:
                                                 C.c_float(maxvel), _ptr(gc), _ptr(gs), _ptr(st)))
         return gc, gs, st
 
-    def lsmr(self, A, b, damp, atol, btol, conlim, itnlim, localSize, x=None):
-        """LSMR (inv/lsmrModule.f90:36) -> x, info dict (istop, itn, normA, condA, normr, normAr, normx)"""
+    def lsmr(self, A, b, damp, atol, btol, conlim, itnlim, localSize, x=None, trace_cap=None):
+        """LSMR (inv/lsmrModule.f90:36) -> x, info dict (istop, itn, normA, condA, normr, normAr, normx).
+        trace_cap: dazim_lsmr_traced with a host array of trace_cap records -> info["trace"] (LSMR_REC, the trace_n records the
+        call reports) and info["trace_tail"]: eight more records behind the array's end, filled (like the whole array before
+        the call) with the byte LSMR_TRACE_FILL, which the call must leave as they are"""
         if x is None:
             if _is_torch(b):
                 import torch
@@ -479,12 +487,23 @@ class Context:
             b = np.ascontiguousarray(b, np.float32)
         istop, itn = C.c_int(0), C.c_int(0)
         sc = [C.c_float(0) for _ in range(5)]
-        rc = self.lib.dazim_lsmr(self._h, A._h, _ptr(b, np.float32), C.c_float(damp), C.c_float(atol), C.c_float(btol),
-                                 C.c_float(conlim), int(itnlim), int(localSize), _ptr(x, np.float32),
-                                 C.byref(istop), C.byref(itn), *[C.byref(s) for s in sc])
-        self._check(rc)
-        return x, dict(istop=istop.value, itn=itn.value, normA=sc[0].value, condA=sc[1].value,
-                       normr=sc[2].value, normAr=sc[3].value, normx=sc[4].value)
+        args = (self._h, A._h, _ptr(b, np.float32), C.c_float(damp), C.c_float(atol), C.c_float(btol),
+                C.c_float(conlim), int(itnlim), int(localSize), _ptr(x, np.float32),
+                C.byref(istop), C.byref(itn), *[C.byref(s) for s in sc])
+        if trace_cap is None:
+            self._check(self.lib.dazim_lsmr(*args))
+        else:
+            cap = int(trace_cap)
+            rec = np.empty(max(cap, 0) + 8, LSMR_REC)
+            rec.view(np.uint8)[:] = LSMR_TRACE_FILL
+            ntr = C.c_int(0)
+            self._check(self.lib.dazim_lsmr_traced(*args, C.c_void_p(rec.ctypes.data), cap, C.byref(ntr)))
+        info = dict(istop=istop.value, itn=itn.value, normA=sc[0].value, condA=sc[1].value,
+                    normr=sc[2].value, normAr=sc[3].value, normx=sc[4].value)
+        if trace_cap is not None:
+            info["trace"] = rec[:ntr.value]
+            info["trace_tail"] = rec[max(cap, 0):]
+        return x, info
 
 
 class MonteCarlo:

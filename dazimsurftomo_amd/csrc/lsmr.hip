@@ -741,6 +741,10 @@ struct LsmrSolve : LsmrArgs {
     ctx->ksec["spmvt"] = n_spmvt ? t_spmvt / n_spmvt : -1.0;
     ctx->ksec["lsmr.normb"] = normb;
     ctx->ksec["lsmr.host_syncs"] = host_syncs;
+    // the form reorthogonalise() took (the same for every iteration of a solve): 0 no window (or no iteration), 1 k_reorth_coop, 2 the chain
+    ctx->ksec["lsmr.reorth_kind"] = localVecs > 0 && n_enq > 0 ? (per_thread <= RC_EMAX && rcb <= coop_max ? 1.0 : 2.0) : 0.0;
+    ctx->ksec["lsmr.reorth_blocks"] = rcb;
+    ctx->ksec["lsmr.reorth_per_thread"] = (double)per_thread;
     // counted, not assumed: collectives issued by the loop / iterations enqueued (the n floats of A_p^T u_p with the double ||u_p||^2)
     ctx->ksec["lsmr.collectives_per_iteration"] = comm && n_enq > 0 ? (double)n_coll / (double)n_enq : 0.0;
     ctx->ksec["lsmr.collective_kind"] = comm ? (rccl_allreduce ? 2.0 : 1.0) : 0.0;   // 1 all-gather + rank-ordered sums, 2 ncclAllReduce
