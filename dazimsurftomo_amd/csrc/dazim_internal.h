@@ -150,6 +150,21 @@ __device__ __forceinline__ double dz_row_kernel(float v, double svs, double svp,
   return svp * (double)coe_a + srho * (double)coe_rho + svs;
 }
 
+// The refined layer table of a column model, refineGrid2LayerMdl (inv/CalSurfG.f90:2339-2365) in its fp32 expressions: the interval
+// between knots i and i + 1 (iv = i, 1-based) becomes nsub sublayers, sublayer j with the weights fm / den = (2j - 1) / (2 nsub) and the
+// thickness thk; the last row is the half-space (iv = 0).  dazim_dispersion_kernels and dazim_ti_kernels build their tables on it.
+struct DzRefinedLayer { int iv; float fm, den, thk; };
+static inline std::vector<DzRefinedLayer> dz_refine_layers(const float *depz, int nz, float minthk0) {
+  std::vector<DzRefinedLayer> lay;
+  for (int i = 1; i <= nz - 1; i++) {
+    const float thk = depz[i] - depz[i - 1], minthk = thk / minthk0;
+    const int nsub = (int)((thk + 1.0e-4f) / minthk) + 1;
+    for (int j = 1; j <= nsub; j++) lay.push_back({i, (float)(2 * j - 1), (float)(2 * nsub), thk / (float)nsub});
+  }
+  lay.push_back({0, 0.0f, 1.0f, 0.0f});
+  return lay;
+}
+
 // named scratch buffer of at least `bytes` bytes
 int dz_scratch(dazim_ctx *ctx, const char *name, size_t bytes, void **out);
 // named PINNED host buffer of at least `bytes` bytes (measured neutral against pageable memory, profiles/r6_pinned_ab.md)

@@ -1021,57 +1021,74 @@ __global__ void disp_finalize(int ncol, int nz, int kmax, int nvar, const float 
   }
 }
 
-}  // namespace
-
-// = depthkernel (inv/CalSurfG.f90:1); kernels==0 -> only pvRc (CalRayleighPhase behaviour,
-// fwd/FwdTraveltimeCPS.f90:4)
-extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, const float *vel_u,
-                                        const float *depz, float minthk0, int kmax, const double *periods,
-                                        double *pv_u, double *svs_u, double *svp_u, double *srho_u, int *n_failed) {
-  if (!ctx || !vel_u || !depz || !periods || !pv_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "null argument");
-  if (nz < 2 || nz > NZMAX || kmax < 1 || kmax > NP || nx < 1 || ny < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad nz/kmax");
-  DZ_HIP(hipSetDevice(ctx->device));
-  const bool kernels = svs_u && svp_u && srho_u;
-  const int ncol = nx * ny, nvar = kernels ? 1 + 6 * nz : 1;
-  // ---- geometry-only layer table: refineGrid2LayerMdl (inv/CalSurfG.f90:2339-2365) + sphere (:510-545) ----
-  std::vector<Layer> lay;
-  for (int i = 1; i <= nz - 1; i++) {
-    const float thk = depz[i] - depz[i - 1];
-    const float minthk = thk / minthk0;
-    const int nsub = (int)((thk + 1.0e-4f) / minthk) + 1;
-    const float newthk = thk / (float)nsub;
-    for (int j = 1; j <= nsub; j++) {
-      Layer L;
-      L.d = newthk;
-      L.iv = i;
-      L.fm = (float)(2 * j - 1);
-      L.den = (float)(2 * nsub);
-      lay.push_back(L);
-    }
-  }
-  {
-    Layer L;
-    L.d = 0.0f;
-    L.iv = 0;
-    L.fm = 0;
-    L.den = 1;
-    lay.push_back(L);
-  }
-  // division-free layer interpolation (see layer_model): 1 = every 2*nsub a power of two, 2 = every 2*nsub a power of two or one
-  // of the divisors the reciprocal + correction form was verified on exhaustively, 0 = divide
-  int rden = 1;
-  for (Layer &L : lay) {
+// ---- the kernel forms: one row per division class (template argument RDEN, see layer_model) with everything the host driver can launch ----
+struct DispForm { const void *plain, *teams, *share, *bracket; };   // disp_kernel<R>, <R, true>, <R, false, true>, disp_bracket_kernel<R>
+enum { RDEN_DIVIDE, RDEN_POW2, RDEN_FASTDIV, RDEN_CLASSES };   // the values of RDEN = the rows of disp_pick_form's table
+// division-free layer interpolation (see layer_model): 1 = every 2*nsub a power of two, 2 = every 2*nsub a power of two or one
+// of the divisors the reciprocal + correction form was verified on exhaustively, 0 = divide
+const DispForm *disp_pick_form(const std::vector<Layer> &lay, const dazim_ctx *opt) {
+  static_assert(RDEN_CLASSES == 3, "a row per value of RDEN: a new class gets its four kernels here");
+  // Written kind by kind and, within a kind, in the order in which this file has always named the kernels: the compiler emits them in
+  // the order of their first use, so the code object stays the same bytes (and every kernel at the address it was measured at).
+  static const DispForm *const tab = [] {
+    static DispForm t[RDEN_CLASSES];
+    t[0].plain = (const void *)disp_kernel<0>, t[1].plain = (const void *)disp_kernel<1>, t[2].plain = (const void *)disp_kernel<2>;
+    t[0].teams = (const void *)disp_kernel<0, true>, t[1].teams = (const void *)disp_kernel<1, true>, t[2].teams = (const void *)disp_kernel<2, true>;
+    t[1].share = (const void *)disp_kernel<1, false, true>, t[2].share = (const void *)disp_kernel<2, false, true>, t[0].share = (const void *)disp_kernel<0, false, true>;
+    t[1].bracket = (const void *)disp_bracket_kernel<1>, t[2].bracket = (const void *)disp_bracket_kernel<2>, t[0].bracket = (const void *)disp_bracket_kernel<0>;
+    return t;
+  }();
+  int rden = RDEN_POW2;
+  for (const Layer &L : lay) {
     const int d = (int)L.den;
-    L.rden = 1.0f / L.den;
     const bool pow2 = (d & (d - 1)) == 0 && d <= (1 << 20);
     bool fastdiv_ok = false;
     for (int v : {6, 10, 12, 14, 18, 20, 22, 24, 26, 28, 30, 36}) fastdiv_ok = fastdiv_ok || d == v;
-    if (!pow2) rden = (fastdiv_ok && rden != 0) ? 2 : 0;
+    if (!pow2) rden = (fastdiv_ok && rden != RDEN_DIVIDE) ? RDEN_FASTDIV : RDEN_DIVIDE;
   }
-  if (dz_opt(ctx, "disp.rden", 1) == 0) rden = 0;   // test knob: keep the divisions
-  const int mmax = (int)lay.size();
-  if (mmax > NL) return dz_fail(ctx, DAZIM_E_BAD_ARG, "refined model has %d layers > NL=%d", mmax, NL);
-  {
+  if (dz_opt(opt, "disp.rden", 1) == 0) rden = RDEN_DIVIDE;   // test knob: keep the divisions
+  return &tab[rden];
+}
+
+// a queue's task counter: behind its `ntask` ready flags, on the next 16-byte boundary
+unsigned *queue_counter(int *ready, size_t ntask) { return (unsigned *)((char *)ready + ntask * 4 + 16 - (ntask * 4) % 16); }
+
+// ---- one dispersion call on the host: a member function per stage, called in this order by dazim_dispersion_kernels.  plan() issues nothing
+// on a stream; tables() behind it allocates the scratch blocks in the order and with the sizes (the Neville tables' from plan()'s occupancy) they always had ----
+struct DispCall {
+  dazim_ctx *ctx = nullptr;
+  int nx = 0, ny = 0, nz = 0, kmax = 0; float minthk0 = 0.0f;   // the entry point's arguments
+  const float *vel_u = nullptr, *depz = nullptr;
+  const double *periods = nullptr;
+  double *pv_u = nullptr, *svs_u = nullptr, *svp_u = nullptr, *srho_u = nullptr;
+  int *n_failed = nullptr;
+  bool kernels = false; size_t nk = 0;   // depth kernels wanted (all three tables given), entries of one table
+  int ncol = 0, nvar = 0, mmax = 0;
+  std::vector<Layer> lay; std::vector<int> krange;   // the refined layers; per knot the first layer it touches and how many (DispArgs::krange)
+  const DispForm *form = nullptr;
+  DzBuf<float> vel;
+  DzBuf<double> pv, svs, svp, srho;
+  DispArgs A{};           // the arguments of a launch of every variant (pv, svs .. and nfail null: disp_finalize writes them)
+  int *d_nfail = nullptr;
+  bool async = false, teams = false, share = false;   // plan()'s decisions
+  size_t dyn_lds = 0, dyn_lds_base = 0;   // ... dynamic LDS of a launch of every variant (or of the copies) and of the curves' launch,
+  int occ = 3; long nwg = 0;              // workgroups per CU and in all
+  size_t knot_lds(int nvarp, int items = TW) const { return (size_t)(DT / TW) * ((items + nvarp - 1) / nvarp + 1) * 3 * nz * sizeof(float); }
+  size_t share_lds(int nvarp) const {
+    const size_t cpb = (size_t)(TW + nvarp - 1) / nvarp + 1, knots = (((size_t)(DT / TW) * cpb * 3 * nz + 3) & ~(size_t)3) * sizeof(float);
+    return knots + (size_t)(DT / TW) * cpb * mmax * sizeof(float4) + (size_t)(DT / TW) * A.npatch * 3 * TW * sizeof(float);
+  }
+  // ---- geometry-only layer table: refineGrid2LayerMdl (inv/CalSurfG.f90:2339-2365) + sphere (:510-545) ----
+  int layers() {
+    kernels = svs_u && svp_u && srho_u;
+    ncol = nx * ny, nvar = kernels ? 1 + 6 * nz : 1, nk = (size_t)nz * kmax * ncol;
+    for (const DzRefinedLayer &R : dz_refine_layers(depz, nz, minthk0)) {
+      Layer L;
+      L.d = R.thk, L.iv = R.iv, L.fm = R.fm, L.den = R.den, L.rden = 1.0f / R.den;
+      lay.push_back(L);
+    }
+    form = disp_pick_form(lay, ctx), mmax = (int)lay.size();
+    if (mmax > NL) return dz_fail(ctx, DAZIM_E_BAD_ARG, "refined model has %d layers > NL=%d", mmax, NL);
     const double ar = 6370.0;
     double dr = 0.0, r0 = ar;
     lay[mmax - 1].d = 1.0f;
@@ -1086,153 +1103,93 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
       r0 = r1;
     }
     lay[mmax - 1].d = 0.0f;
+    // shared layer stacks (TableLayers): the contiguous range of layers that knot pi touches -- the sublayers of intervals pi - 1 and
+    // pi, for the last knot those of the last interval and the half-space -- and the longest such range
+    krange.assign(2 * (nz + 1), 0);
+    A.npatch = 1;
+    for (int pi = 1; pi <= nz; pi++) {
+      int lo = 0, hi = 0;
+      for (int m = 1; m <= mmax; m++)
+        if ((pi > 1 && lay[m - 1].iv == pi - 1) || lay[m - 1].iv == pi || (pi == nz && lay[m - 1].iv == 0)) {
+          if (!lo) lo = m;
+          hi = m;
+        }
+      krange[2 * pi] = lo, krange[2 * pi + 1] = lo ? hi - lo + 1 : 0;
+      if (krange[2 * pi + 1] > A.npatch) A.npatch = krange[2 * pi + 1];
+    }
+    return 0;
   }
-  DzBuf<float> vel;
-  DzBuf<double> pv, svs, svp, srho;
-  int rc;
-  if ((rc = dz_fmm_finish(ctx))) return rc; // (an asynchronous eikonal call nobody has collected)
-  if ((rc = dz_join_aux(ctx))) return rc;   // (an earlier call's perturbed copies may still be running on the auxiliary stream)
-  const size_t nk = (size_t)nz * kmax * ncol;
-  if ((rc = vel.init(ctx, vel_u, (size_t)nz * ncol, true, false))) return rc;
-  if ((rc = pv.init(ctx, pv_u, (size_t)kmax * ncol, false, true))) return rc;
-  if (kernels) {
-    if ((rc = svs.init(ctx, svs_u, nk, false, true))) return rc;
-    if ((rc = svp.init(ctx, svp_u, nk, false, true))) return rc;
-    if ((rc = srho.init(ctx, srho_u, nk, false, true))) return rc;
+  int buffers() {
+    int rc;
+    if ((rc = dz_fmm_finish(ctx))) return rc; // (an asynchronous eikonal call nobody has collected)
+    if ((rc = dz_join_aux(ctx))) return rc;   // (an earlier call's perturbed copies may still be running on the auxiliary stream)
+    if ((rc = vel.init(ctx, vel_u, (size_t)nz * ncol, true, false))) return rc;
+    if ((rc = pv.init(ctx, pv_u, (size_t)kmax * ncol, false, true))) return rc;
+    if (kernels && ((rc = svs.init(ctx, svs_u, nk, false, true)) || (rc = svp.init(ctx, svp_u, nk, false, true)) || (rc = srho.init(ctx, srho_u, nk, false, true))))
+      return rc;
+    return 0;
   }
-  void *p;
-  DispArgs A;
-  A.svs = A.svp = A.srho = A.pv = nullptr;
-  A.nfail = nullptr;
-  A.ncol = ncol;
-  A.nz = nz;
-  A.kmax = kmax;
-  A.nvar = nvar;
-  A.var0 = 0;
-  A.nvarp = nvar;
-  A.team = 1;
-  A.mmax = mmax;
-  A.vel = vel.dev;
-  // shared layer stacks (TableLayers): the contiguous range of layers that knot pi touches -- the sublayers of intervals pi - 1 and
-  // pi, for the last knot those of the last interval and the half-space -- and the longest such range
-  std::vector<int> krange(2 * (nz + 1), 0);
-  A.npatch = 1;
-  for (int pi = 1; pi <= nz; pi++) {
-    int lo = 0, hi = 0;
-    for (int m = 1; m <= mmax; m++)
-      if ((pi > 1 && lay[m - 1].iv == pi - 1) || lay[m - 1].iv == pi || (pi == nz && lay[m - 1].iv == 0)) {
-        if (!lo) lo = m;
-        hi = m;
-      }
-    krange[2 * pi] = lo;
-    krange[2 * pi + 1] = lo ? hi - lo + 1 : 0;
-    if (krange[2 * pi + 1] > A.npatch) A.npatch = krange[2 * pi + 1];
-  }
-  A.nev = nullptr;
-  if ((rc = dz_scratch(ctx, "disp.krange", sizeof(int) * 2 * (NZMAX + 1), &p))) return rc;
-  A.krange = (const int *)p;
-  DZ_HIP(hipMemcpyAsync(p, krange.data(), sizeof(int) * krange.size(), hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = dz_scratch(ctx, "disp.lay", sizeof(Layer) * NL, &p))) return rc;
-  A.lay = (Layer *)p;
-  DZ_HIP(hipMemcpyAsync(p, lay.data(), sizeof(Layer) * mmax, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = dz_scratch(ctx, "disp.t", sizeof(double) * NP, &p))) return rc;
-  A.t = (double *)p;
-  DZ_HIP(hipMemcpyAsync(p, periods, sizeof(double) * kmax, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = dz_scratch(ctx, "disp.cg", (size_t)ncol * nvar * kmax, &A.cg))) return rc;
-  int *d_nfail;
-  if ((rc = dz_scratch(ctx, "disp.nfail", 4, &d_nfail))) return rc;
-  DZ_HIP(hipMemsetAsync(d_nfail, 0, 4, ctx->stream));
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  auto knot_lds = [&](int nvarp, int items = TW) { return (size_t)(DT / TW) * ((items + nvarp - 1) / nvarp + 1) * 3 * nz * sizeof(float); };
-  // Option disp.async (device-resident vel and sen_* -- pvRc may be a host array, it is complete and copied when the call
-  // returns --, depth kernels wanted, one period chunk): the column's own curves -- all the
-  // eikonal solve needs -- are one launch on the context's stream, the 6*nz perturbed copies (72/73 of the work, wanted only by
-  // the G rows) another one on the auxiliary stream, and the call returns when the first is done.  dazim_rays_build_G*, the next
-  // dazim_dispersion_kernels, dazim_sync and dazim_free join the auxiliary stream; anybody else who reads sen_* (or overwrites
-  // vel) before one of these calls dazim_sync first.  What it buys: the dispersion kernel's last, partly filled round of
-  // workgroups (S-256: 64 of 832) and the eikonal kernel share the chip (measured: 293 against 306 ms), and on
-  // small batches (S-128) the two kernels, neither of which fills it, run side by side.
-  bool async = kernels && dz_opt(ctx, "disp.async", 0) != 0 && !vel.staged && !svs.staged &&
-               !svp.staged && !srho.staged && !(dz_opt(ctx, "disp.pchunk", 0) > 0 && dz_opt(ctx, "disp.pchunk", 0) < kmax);
-  // the column curves of an asynchronous call in teams (disp_kernel: TEAM grid points of the bracket search at a time) when the
-  // extra wavefronts do not add a round of workgroups to the copies beside them: everything fits one round (S-128), or the copies
-  // need a second, partly filled round anyway (S-256: 832 + 183 workgroups on 768 slots; the curves are what the eikonal kernel
-  // waits for, 23.5 -> 12 ms, step 370 -> 366 ms).  test4_Yunnan (0.89 of a round, 1.01 with teams: 62 -> 25 ms of column curves,
-  // but the copies beside them 139 -> 163 ms) stays without.  Option disp.team = 1 / 2 forces them on / off.
-  const double wg_copies = (double)(((long)ncol * (nvar - 1) + DT - 1) / DT), wg_teams = (double)((ncol * TEAM + DT - 1) / DT);
-  const double wg_round = (double)((long)ctx->num_cu * 3);
-  bool teams = wg_copies + wg_teams <= 0.98 * wg_round || (wg_copies > 1.02 * wg_round && wg_copies + wg_teams <= 1.9 * wg_round);
-  if (dz_opt(ctx, "disp.team", 0) == 1) teams = true;
-  if (dz_opt(ctx, "disp.team", 0) == 2) teams = false;
-  const size_t dyn_lds = knot_lds(nvar), dyn_lds_base = teams ? knot_lds(1, TW / TEAM) : knot_lds(1);
-  if (dyn_lds_base + 56 * 1024 > 160 * 1024) async = false;   // (very many knots: the 64 columns of a base task would not fit the LDS)
-  const size_t dyn_max = async && dyn_lds_base > dyn_lds ? dyn_lds_base : dyn_lds;
-  DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
-  DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
-  DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
-  DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
-  DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
-  DZ_HIP(hipFuncSetAttribute((const void *)disp_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
-  // Shared layer stacks for the launch that holds the perturbed copies (all variants, or the copies of disp.async): knots + base
-  // tables + patch tables per wavefront, where that leaves three workgroups per CU (LDS comes in granules of 1 280 bytes, 42 of them
-  // per workgroup) -- models with many sublayers per interval or very many layers keep rebuilding their layers.  Option disp.share = 0
-  // forces that path.
-  const void *kshare = rden == 1 ? (const void *)disp_kernel<1, false, true>
-                                 : (rden == 2 ? (const void *)disp_kernel<2, false, true> : (const void *)disp_kernel<0, false, true>);
-  auto share_lds = [&](int nvarp) {
-    const size_t cpb = (size_t)(TW + nvarp - 1) / nvarp + 1, knots = (((size_t)(DT / TW) * cpb * 3 * nz + 3) & ~(size_t)3) * sizeof(float);
-    return knots + (size_t)(DT / TW) * cpb * mmax * sizeof(float4) + (size_t)(DT / TW) * A.npatch * 3 * TW * sizeof(float);
-  };
-  bool share = kernels && dz_opt(ctx, "disp.share", 1) != 0;
-  if (share) {
-    hipFuncAttributes fa;
-    DZ_HIP(hipFuncGetAttributes(&fa, kshare));
-    const size_t need = std::max(share_lds(nvar), share_lds(nvar - 1));
-    share = fa.sharedSizeBytes + need <= (size_t)42 * 1280;
-    if (share) DZ_HIP(hipFuncSetAttribute(kshare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-  }
-  ctx->ksec["disp.share"] = share ? 1.0 : 0.0;
-  if (async && (rc = dz_aux_init(ctx))) return rc;
-  {
-    const long nwork = (long)ncol * nvar;
+  // every decision of the call: one launch or two, the kernels of the row, their LDS, the workgroups, the period chunks, the jump
+  int plan() {
+    A.ncol = ncol, A.nz = nz, A.kmax = kmax, A.nvar = nvar, A.mmax = mmax;
+    A.var0 = 0, A.nvarp = nvar, A.team = 1, A.vel = vel.dev;
+    // Option disp.async (device-resident vel and sen_* -- pvRc may be a host array, it is complete and copied when the call
+    // returns --, depth kernels wanted, one period chunk): the column's own curves -- all the
+    // eikonal solve needs -- are one launch on the context's stream, the 6*nz perturbed copies (72/73 of the work, wanted only by
+    // the G rows) another one on the auxiliary stream, and the call returns when the first is done.  dazim_rays_build_G*, the next
+    // dazim_dispersion_kernels, dazim_sync and dazim_free join the auxiliary stream; anybody else who reads sen_* (or overwrites
+    // vel) before one of these calls dazim_sync first.  What it buys: the dispersion kernel's last, partly filled round of
+    // workgroups (S-256: 64 of 832) and the eikonal kernel share the chip (measured: 293 against 306 ms), and on
+    // small batches (S-128) the two kernels, neither of which fills it, run side by side.
+    async = kernels && dz_opt(ctx, "disp.async", 0) != 0 && !vel.staged && !svs.staged &&
+            !svp.staged && !srho.staged && !(dz_opt(ctx, "disp.pchunk", 0) > 0 && dz_opt(ctx, "disp.pchunk", 0) < kmax);
+    // the column curves of an asynchronous call in teams (disp_kernel: TEAM grid points of the bracket search at a time) when the
+    // extra wavefronts do not add a round of workgroups to the copies beside them: everything fits one round (S-128), or the copies
+    // need a second, partly filled round anyway (S-256: 832 + 183 workgroups on 768 slots; the curves are what the eikonal kernel
+    // waits for, 23.5 -> 12 ms, step 370 -> 366 ms).  test4_Yunnan (0.89 of a round, 1.01 with teams: 62 -> 25 ms of column curves,
+    // but the copies beside them 139 -> 163 ms) stays without.  Option disp.team = 1 / 2 forces them on / off.
+    const double wg_copies = (double)(((long)ncol * (nvar - 1) + DT - 1) / DT), wg_teams = (double)((ncol * TEAM + DT - 1) / DT);
+    const double wg_round = (double)((long)ctx->num_cu * 3);
+    teams = wg_copies + wg_teams <= 0.98 * wg_round || (wg_copies > 1.02 * wg_round && wg_copies + wg_teams <= 1.9 * wg_round);
+    if (dz_opt(ctx, "disp.team", 0) == 1) teams = true;
+    if (dz_opt(ctx, "disp.team", 0) == 2) teams = false;
+    dyn_lds = knot_lds(nvar), dyn_lds_base = teams ? knot_lds(1, TW / TEAM) : knot_lds(1);
+    if (dyn_lds_base + 56 * 1024 > 160 * 1024) async = false;   // (very many knots: the 64 columns of a base task would not fit the LDS)
+    const size_t dyn_max = async && dyn_lds_base > dyn_lds ? dyn_lds_base : dyn_lds;
+    for (const void *k : {form->plain, form->teams}) DZ_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
+    // Shared layer stacks for the launch that holds the perturbed copies (all variants, or the copies of disp.async): knots + base
+    // tables + patch tables per wavefront, where that leaves three workgroups per CU (LDS comes in granules of 1 280 bytes, 42 of them
+    // per workgroup) -- models with many sublayers per interval or very many layers keep rebuilding their layers.  Option disp.share = 0
+    // forces that path.
+    share = kernels && dz_opt(ctx, "disp.share", 1) != 0;
+    if (share) {
+      hipFuncAttributes fa;
+      DZ_HIP(hipFuncGetAttributes(&fa, form->share));
+      const size_t need = std::max(share_lds(nvar), share_lds(nvar - 1));
+      share = fa.sharedSizeBytes + need <= (size_t)42 * 1280;
+      if (share) DZ_HIP(hipFuncSetAttribute(form->share, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+    }
+    ctx->ksec["disp.share"] = share ? 1.0 : 0.0;
+    if (const int rc = async ? dz_aux_init(ctx) : 0) return rc;
     // task queue: groups of DT items x chunks of pchunk periods (see disp_kernel); persistent workgroups, as many as are resident
-    A.ngroup = (int)((nwork + TW - 1) / TW);
+    A.ngroup = (int)(((long)ncol * nvar + TW - 1) / TW);
     A.pchunk = kmax;
     if (dz_opt(ctx, "disp.pchunk", 0) > 0) A.pchunk = dz_opt(ctx, "disp.pchunk", 0);
     if (A.pchunk > kmax) A.pchunk = kmax;
     A.nchunk = (kmax + A.pchunk - 1) / A.pchunk;
-    const size_t ntask = (size_t)A.ngroup * A.nchunk;
-    if ((rc = dz_scratch(ctx, "disp.ready", ntask + 16, &A.ready))) return rc;
-    A.counter = (unsigned *)((char *)A.ready + ntask * 4 + 16 - (ntask * 4) % 16);
-    DZ_HIP(hipMemsetAsync(A.ready, 0, ntask * 4 + 64, ctx->stream));
-    if ((rc = dz_scratch(ctx, "disp.st_c", (size_t)nwork, &A.st_c))) return rc;
-    if ((rc = dz_scratch(ctx, "disp.st_d", (size_t)nwork, &A.st_d))) return rc;
-    if ((rc = dz_scratch(ctx, "disp.st_f", (size_t)nwork, &A.st_f))) return rc;
-    const void *kf = rden == 1 ? (const void *)disp_kernel<1> : (rden == 2 ? (const void *)disp_kernel<2> : (const void *)disp_kernel<0>);
-    int occ = 3;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, share ? kshare : kf, DT, share ? share_lds(nvar) : dyn_lds) != hipSuccess || occ < 1) occ = 1;
-    if (share) {   // the Neville tables of every lane that can be resident
-      if ((rc = dz_scratch(ctx, "disp.nev", 2 * NEVN * (size_t)ctx->num_cu * occ * DT, &A.nev))) return rc;
-    }
-    long nwg = (long)ctx->num_cu * occ;
-    if (nwg > ((long)ntask + DT / TW - 1) / (DT / TW)) nwg = ((long)ntask + DT / TW - 1) / (DT / TW);
+    const long ntask = (long)A.ngroup * A.nchunk;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, share ? form->share : form->plain, DT, share ? share_lds(nvar) : dyn_lds) != hipSuccess || occ < 1) occ = 1;
+    nwg = (long)ctx->num_cu * occ;
+    if (nwg > (ntask + DT / TW - 1) / (DT / TW)) nwg = (ntask + DT / TW - 1) / (DT / TW);
     // first-period fast-forward (disp_bracket_kernel); off with option disp.ffwd = 0 and when the periods are handed from task to task
     // Option disp.ffwd: 1 (default) = the jump for the column's own model only, which is exact -- disp_bracket_kernel evaluated
     // every skipped grid point with the same function; 2 = the 6*nz perturbed copies jump as well, behind the gates described at
     // disp_bracket_kernel (equal to the step-by-step search on every model family tried, tools/stress_disp_ffwd.py, but a
     // statistical statement, not a proof: hence opt-in, with its statistics under dazim_last_kernel_seconds("disp.ffwd_*"));
     // 0 = no jump.
-    A.ffwd = 0;
-    if (A.nchunk == 1) {
-      const int ff = dz_opt(ctx, "disp.ffwd", 1);
-      A.ffwd = ff < 0 ? 0 : (ff > 2 ? 2 : ff);
-    }
+    const int ff = dz_opt(ctx, "disp.ffwd", 1);
+    A.ffwd = A.nchunk > 1 || ff < 0 ? 0 : (ff > 2 ? 2 : ff);
     A.exp3 = dz_opt(ctx, "disp.exp3", 0) != 0 ? 1 : 0;
-    if ((rc = dz_scratch(ctx, "disp.ff_stat", 16, &A.ff_stat))) return rc;
-    DZ_HIP(hipMemsetAsync(A.ff_stat, 0, 64, ctx->stream));
-    if ((rc = dz_scratch(ctx, "disp.ff_m", (size_t)ncol + 4, &A.ff_m))) return rc;
-    if ((rc = dz_scratch(ctx, "disp.ff_c", (size_t)ncol + 2, &A.ff_c))) return rc;
-    if ((rc = dz_scratch(ctx, "disp.ff_v", (size_t)ncol + 4, &A.ff_v))) return rc;
     if (async && dz_opt(ctx, "disp.async", 0) == 1) {
       // 1 = two streams where they pay: what the eikonal kernel can share the chip with is the copies' last, partly filled round
       // (or a launch that never fills it); over many rounds that is a small part of the launch and the two kernels only take
@@ -1241,115 +1198,150 @@ extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, 
       if (rounds > 2.0) async = false;
     }
     ctx->ksec["disp.async"] = async ? 1.0 : 0.0;
+    if (async) ctx->ksec["disp.team"] = teams ? TEAM : 1;
+    return 0;
+  }
+  // the small tables and the queues' scratch, with their uploads and memsets on the context's stream
+  int tables() {
+    int rc;
+    if ((rc = dz_scratch(ctx, "disp.krange", (size_t)2 * (NZMAX + 1), &A.krange))) return rc;
+    DZ_HIP(hipMemcpyAsync((void *)A.krange, krange.data(), sizeof(int) * krange.size(), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = dz_scratch(ctx, "disp.lay", (size_t)NL, &A.lay))) return rc;
+    DZ_HIP(hipMemcpyAsync((void *)A.lay, lay.data(), sizeof(Layer) * mmax, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = dz_scratch(ctx, "disp.t", (size_t)NP, &A.t))) return rc;
+    DZ_HIP(hipMemcpyAsync((void *)A.t, periods, sizeof(double) * kmax, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = dz_scratch(ctx, "disp.cg", (size_t)ncol * nvar * kmax, &A.cg))) return rc;
+    if ((rc = dz_scratch(ctx, "disp.nfail", 4, &d_nfail))) return rc;
+    DZ_HIP(hipMemsetAsync(d_nfail, 0, 4, ctx->stream));
+    DZ_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t nwork = (size_t)ncol * nvar, ntask = (size_t)A.ngroup * A.nchunk;
+    if ((rc = dz_scratch(ctx, "disp.ready", ntask + 16, &A.ready))) return rc;
+    A.counter = queue_counter(A.ready, ntask);
+    DZ_HIP(hipMemsetAsync(A.ready, 0, ntask * 4 + 64, ctx->stream));
+    if ((rc = dz_scratch(ctx, "disp.st_c", nwork, &A.st_c)) || (rc = dz_scratch(ctx, "disp.st_d", nwork, &A.st_d)) || (rc = dz_scratch(ctx, "disp.st_f", nwork, &A.st_f)))
+      return rc;
+    // the Neville tables of every lane that can be resident
+    if (share && (rc = dz_scratch(ctx, "disp.nev", 2 * NEVN * (size_t)ctx->num_cu * occ * DT, &A.nev))) return rc;
+    if ((rc = dz_scratch(ctx, "disp.ff_stat", 16, &A.ff_stat))) return rc;
+    DZ_HIP(hipMemsetAsync(A.ff_stat, 0, 64, ctx->stream));
+    if ((rc = dz_scratch(ctx, "disp.ff_m", (size_t)ncol + 4, &A.ff_m)) || (rc = dz_scratch(ctx, "disp.ff_c", (size_t)ncol + 2, &A.ff_c)) || (rc = dz_scratch(ctx, "disp.ff_v", (size_t)ncol + 4, &A.ff_v)))
+      return rc;
+    return 0;
+  }
+  // The kernel of the row that a launch of disp_kernel with the arguments B takes: shared layer stacks where it holds perturbed copies,
+  // one lane each; the team form where an item has TEAM lanes; else the plain form.
+  const void *kernel_for(const DispArgs &B) const { return share && B.team == 1 && B.nvarp > 1 ? form->share : (B.team > 1 ? form->teams : form->plain); }
+  int launch_kernel(const void *kernel, const DispArgs &B, long nwgB, int threads, size_t lds, hipStream_t st) {
+    void *params[] = {(void *)&B};
+    DZ_HIP(hipLaunchKernel(kernel, dim3((unsigned)nwgB), dim3(threads), params, lds, st));
+    DZ_HIP(hipGetLastError());
+    return 0;
+  }
+  int launch_queue(const DispArgs &B, long nwgB, size_t lds, hipStream_t st) {   // (the shared form has its own LDS layout)
+    return launch_kernel(kernel_for(B), B, nwgB, DT, kernel_for(B) == form->share ? share_lds(B.nvarp) : lds, st);
+  }
+  int launch() {
+    int rc;
     ctx->aux_timed = false;
     DzTimer t(ctx, "disp");
-    if (A.ffwd) {
-      if (rden == 1)
-        hipLaunchKernelGGL(disp_bracket_kernel<1>, dim3((unsigned)ncol), dim3(64), 0, ctx->stream, A);
-      else if (rden == 2)
-        hipLaunchKernelGGL(disp_bracket_kernel<2>, dim3((unsigned)ncol), dim3(64), 0, ctx->stream, A);
-      else
-        hipLaunchKernelGGL(disp_bracket_kernel<0>, dim3((unsigned)ncol), dim3(64), 0, ctx->stream, A);
-      DZ_HIP(hipGetLastError());
-    }
-    auto launch = [&](const DispArgs &B, long nwgB, size_t lds, hipStream_t st) {
-      if (share && B.team == 1 && B.nvarp > 1) {
-        lds = share_lds(B.nvarp);
-        if (rden == 1)
-          hipLaunchKernelGGL((disp_kernel<1, false, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-        else if (rden == 2)
-          hipLaunchKernelGGL((disp_kernel<2, false, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-        else
-          hipLaunchKernelGGL((disp_kernel<0, false, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-      } else if (B.team > 1) {
-        if (rden == 1)
-          hipLaunchKernelGGL((disp_kernel<1, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-        else if (rden == 2)
-          hipLaunchKernelGGL((disp_kernel<2, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-        else
-          hipLaunchKernelGGL((disp_kernel<0, true>), dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-      } else if (rden == 1)
-        hipLaunchKernelGGL(disp_kernel<1>, dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-      else if (rden == 2)
-        hipLaunchKernelGGL(disp_kernel<2>, dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-      else
-        hipLaunchKernelGGL(disp_kernel<0>, dim3((unsigned)nwgB), dim3(DT), lds, st, B);
-    };
-    const long nf = (long)ncol * kmax;
-    if (!async) {
-      launch(A, nwg, dyn_lds, ctx->stream);
-      DZ_HIP(hipGetLastError());
-      hipLaunchKernelGGL(disp_finalize, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nz, kmax, nvar,
-                         vel.dev, A.cg, pv.dev, kernels ? svs.dev : nullptr, kernels ? svp.dev : nullptr,
-                         kernels ? srho.dev : nullptr, d_nfail);
-      DZ_HIP(hipGetLastError());
-    } else {
-      // the copies: auxiliary stream, behind everything enqueued so far (tables, counters, the bracket kernel)
-      DispArgs C = A;
-      C.var0 = 1;
-      C.nvarp = nvar - 1;
-      C.ngroup = (int)(((long)ncol * C.nvarp + TW - 1) / TW);
-      long nwgC = (long)ctx->num_cu * occ, needC = ((long)C.ngroup + DT / TW - 1) / (DT / TW);
-      if (nwgC > needC) nwgC = needC;
-      // the column's own curves: a handful of workgroups on the main stream, their own task counter
-      DispArgs B = A;
-      B.var0 = 0;
-      B.nvarp = 1;
-      B.team = teams ? TEAM : 1;
-      B.pv = pv.dev;              // (written by the launch itself: no kernel behind it that waits for a free SIMD beside the copies)
-      B.nfail = d_nfail;
-      B.ngroup = (ncol + TW / B.team - 1) / (TW / B.team);
-      ctx->ksec["disp.team"] = B.team;
-      if ((rc = dz_scratch(ctx, "disp.ready_b", (size_t)B.ngroup + 16, &B.ready))) return rc;
-      B.counter = (unsigned *)((char *)B.ready + (size_t)B.ngroup * 4 + 16 - ((size_t)B.ngroup * 4) % 16);
-      DZ_HIP(hipMemsetAsync(B.ready, 0, (size_t)B.ngroup * 4 + 64, ctx->stream));
-      DZ_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-      const long nwgB = ((long)B.ngroup + DT / TW - 1) / (DT / TW);
-      launch(B, nwgB, dyn_lds_base, ctx->stream);   // (first: its workgroups want a CU's LDS before the copies' have filled them)
-      DZ_HIP(hipGetLastError());
-      DZ_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-      DZ_HIP(hipEventRecord(ctx->ev_a0, ctx->stream2));
-      // (the copies' launch forms the central differences itself -- DispArgs::svs: a separate kernel behind it would wait for a free
-      // SIMD until the eikonal kernel's persistent workgroups leave, 190 ms at S-256, profiles/r3_bench_kernel_stats.md)
-      C.svs = svs.dev;
-      C.svp = svp.dev;
-      C.srho = srho.dev;
-      launch(C, nwgC, dyn_lds, ctx->stream2);
-      DZ_HIP(hipGetLastError());
-      DZ_HIP(hipEventRecord(ctx->ev_a1, ctx->stream2));
-      ctx->aux_pending = true;
-      ctx->aux_timed = true;
-      ctx->aux_ranges.clear();
-      ctx->aux_ranges.push_back({(const char *)vel.dev, (size_t)nz * ncol * sizeof(float)});
-      for (const double *q : {svs.dev, svp.dev, srho.dev})
-        if (q) ctx->aux_ranges.push_back({(const char *)q, nk * sizeof(double)});
-    }
+    if (A.ffwd && (rc = launch_kernel(form->bracket, A, ncol, 64, 0, ctx->stream))) return rc;
+    if ((rc = async ? launch_two_streams() : launch_one_stream())) return rc;
     t.stop();
+    return 0;
   }
-  if ((rc = dz_pinned(ctx, "disp.host", 64, &p))) return rc;
-  int &nfail = *(int *)p;                 // (pinned: a DMA transfer, not a blit kernel that queues behind the perturbed copies)
-  unsigned *hst = (unsigned *)p + 4;
-  nfail = 0;
-  hst[0] = hst[1] = hst[2] = hst[3] = 0;
-  DZ_HIP(hipMemcpyAsync(&nfail, d_nfail, 4, hipMemcpyDeviceToHost, ctx->stream));
+  int launch_one_stream() {
+    int rc;
+    if ((rc = launch_queue(A, nwg, dyn_lds, ctx->stream))) return rc;
+    hipLaunchKernelGGL(disp_finalize, dim3((unsigned)(((long)ncol * kmax + 255) / 256)), dim3(256), 0, ctx->stream, ncol, nz, kmax, nvar,
+                       vel.dev, A.cg, pv.dev, kernels ? svs.dev : nullptr, kernels ? svp.dev : nullptr,
+                       kernels ? srho.dev : nullptr, d_nfail);
+    DZ_HIP(hipGetLastError());
+    return 0;
+  }
+  // the column's own curves: a handful of workgroups on the main stream, their own task counter (launch_two_streams allocates it)
+  DispArgs curves_args() const {
+    DispArgs B = A;
+    B.var0 = 0, B.nvarp = 1, B.team = teams ? TEAM : 1, B.ngroup = (ncol + TW / B.team - 1) / (TW / B.team);
+    B.pv = pv.dev, B.nfail = d_nfail;   // (written by the launch itself: no kernel behind it that waits for a free SIMD beside the copies)
+    return B;
+  }
+  // the copies: auxiliary stream, behind everything enqueued so far (tables, counters, the bracket kernel)
+  // (the copies' launch forms the central differences itself -- DispArgs::svs: a separate kernel behind it would wait for a free
+  // SIMD until the eikonal kernel's persistent workgroups leave, 190 ms at S-256, profiles/r3_bench_kernel_stats.md)
+  DispArgs copies_args() const {
+    DispArgs C = A;
+    C.var0 = 1, C.nvarp = nvar - 1, C.ngroup = (int)(((long)ncol * C.nvarp + TW - 1) / TW);
+    C.svs = svs.dev, C.svp = svp.dev, C.srho = srho.dev;
+    return C;
+  }
+  int launch_two_streams() {
+    int rc;
+    const DispArgs C = copies_args();
+    const long nwgC = std::min((long)ctx->num_cu * occ, ((long)C.ngroup + DT / TW - 1) / (DT / TW));
+    DispArgs B = curves_args();
+    if ((rc = dz_scratch(ctx, "disp.ready_b", (size_t)B.ngroup + 16, &B.ready))) return rc;
+    B.counter = queue_counter(B.ready, (size_t)B.ngroup);
+    DZ_HIP(hipMemsetAsync(B.ready, 0, (size_t)B.ngroup * 4 + 64, ctx->stream));
+    DZ_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+    const long nwgB = ((long)B.ngroup + DT / TW - 1) / (DT / TW);
+    if ((rc = launch_queue(B, nwgB, dyn_lds_base, ctx->stream))) return rc;   // (first: its workgroups want a CU's LDS before the copies' have filled them)
+    DZ_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+    DZ_HIP(hipEventRecord(ctx->ev_a0, ctx->stream2));
+    if ((rc = launch_queue(C, nwgC, dyn_lds, ctx->stream2))) return rc;
+    DZ_HIP(hipEventRecord(ctx->ev_a1, ctx->stream2));
+    ctx->aux_pending = ctx->aux_timed = true;
+    ctx->aux_ranges.clear();
+    ctx->aux_ranges.push_back({(const char *)vel.dev, (size_t)nz * ncol * sizeof(float)});
+    for (const double *q : {svs.dev, svp.dev, srho.dev})
+      if (q) ctx->aux_ranges.push_back({(const char *)q, nk * sizeof(double)});
+    return 0;
+  }
+  int collect() {
+    int rc;
+    void *p;
+    if ((rc = dz_pinned(ctx, "disp.host", 64, &p))) return rc;
+    int &nfail = *(int *)p;                 // (pinned: a DMA transfer, not a blit kernel that queues behind the perturbed copies)
+    unsigned *hst = (unsigned *)p + 4;
+    nfail = 0, hst[0] = hst[1] = hst[2] = hst[3] = 0;
+    DZ_HIP(hipMemcpyAsync(&nfail, d_nfail, 4, hipMemcpyDeviceToHost, ctx->stream));
 #ifdef DZ_DISP_STAT
-  {
-    unsigned long long h[4];
-    DZ_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_disp_stat), sizeof h));
-    fprintf(stderr, "disp stat: lane-evaluations done %llu, offered by the wavefronts %llu (%.3f used), by the workgroups %llu (%.3f used)\n", h[0], h[1],
-            (double)h[0] / (double)h[1], h[2], (double)h[0] / (double)h[2]);
-    unsigned long long z[4] = {0};
-    DZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_disp_stat), z, sizeof z));
-  }
+    {
+      unsigned long long h[4];
+      DZ_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_disp_stat), sizeof h));
+      fprintf(stderr, "disp stat: lane-evaluations done %llu, offered by the wavefronts %llu (%.3f used), by the workgroups %llu (%.3f used)\n", h[0], h[1],
+              (double)h[0] / (double)h[1], h[2], (double)h[0] / (double)h[2]);
+      unsigned long long z[4] = {0};
+      DZ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_disp_stat), z, sizeof z));
+    }
 #endif
-  if (!ctx->aux_pending) DZ_HIP(hipMemcpyAsync(hst, A.ff_stat, 16, hipMemcpyDeviceToHost, ctx->stream));   // (async: the copies' statistics are not waited for)
-  if ((rc = pv.finish()) || (rc = svs.finish()) || (rc = svp.finish()) || (rc = srho.finish())) return rc;
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  if (n_failed) *n_failed = nfail;
-  ctx->ksec["disp.ffwd_mode"] = A.ffwd;
-  ctx->ksec["disp.ffwd_gated_columns"] = hst[0];      // mode 2: columns whose perturbed copies may not jump (roughness gate)
-  ctx->ksec["disp.ffwd_dip_columns"] = hst[1];        // ... columns whose copies stop in front of a dip of |del|
-  ctx->ksec["disp.ffwd_jumped_copies"] = hst[2];      // ... perturbed copies that jumped
-  ctx->ksec["disp.ffwd_fallback_copies"] = hst[3];    // ... of which the arrival point had the other sign (searched step by step)
-  return 0;
+    if (!ctx->aux_pending) DZ_HIP(hipMemcpyAsync(hst, A.ff_stat, 16, hipMemcpyDeviceToHost, ctx->stream));   // (async: the copies' statistics are not waited for)
+    if ((rc = pv.finish()) || (rc = svs.finish()) || (rc = svp.finish()) || (rc = srho.finish())) return rc;
+    DZ_HIP(hipStreamSynchronize(ctx->stream));
+    if (n_failed) *n_failed = nfail;
+    ctx->ksec["disp.ffwd_mode"] = A.ffwd;
+    ctx->ksec["disp.ffwd_gated_columns"] = hst[0];      // mode 2: columns whose perturbed copies may not jump (roughness gate)
+    ctx->ksec["disp.ffwd_dip_columns"] = hst[1];        // ... columns whose copies stop in front of a dip of |del|
+    ctx->ksec["disp.ffwd_jumped_copies"] = hst[2];      // ... perturbed copies that jumped
+    ctx->ksec["disp.ffwd_fallback_copies"] = hst[3];    // ... of which the arrival point had the other sign (searched step by step)
+    return 0;
+  }
+};
+
+}  // namespace
+
+// = depthkernel (inv/CalSurfG.f90:1); kernels==0 -> only pvRc (CalRayleighPhase behaviour,
+// fwd/FwdTraveltimeCPS.f90:4)
+extern "C" int dazim_dispersion_kernels(dazim_ctx *ctx, int nx, int ny, int nz, const float *vel_u, const float *depz, float minthk0,
+                                        int kmax, const double *periods, double *pv_u, double *svs_u, double *svp_u, double *srho_u,
+                                        int *n_failed) {
+  if (!ctx || !vel_u || !depz || !periods || !pv_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "null argument");
+  if (nz < 2 || nz > NZMAX || kmax < 1 || kmax > NP || nx < 1 || ny < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad nz/kmax");
+  DZ_HIP(hipSetDevice(ctx->device));
+  DispCall c;
+  c.ctx = ctx, c.nx = nx, c.ny = ny, c.nz = nz, c.kmax = kmax;
+  c.vel_u = vel_u, c.depz = depz, c.minthk0 = minthk0, c.periods = periods;
+  c.pv_u = pv_u, c.svs_u = svs_u, c.svp_u = svp_u, c.srho_u = srho_u, c.n_failed = n_failed;
+  int rc;
+  if ((rc = c.layers()) || (rc = c.buffers()) || (rc = c.plan()) || (rc = c.tables()) || (rc = c.launch())) return rc;
+  return c.collect();
 }

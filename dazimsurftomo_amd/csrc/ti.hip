@@ -487,16 +487,9 @@ extern "C" int dazim_ti_kernels(dazim_ctx *ctx, int nx, int ny, int nz, const fl
   // ---- geometry-only tables: refineLayerMdl, sphere_tdisp96 (radius 6371), bldsph (radius 6370) ----
   std::vector<int> knot, jlay;
   std::vector<float> fm, den, thk, vtp, tper(kmax);
-  for (int i = 0; i < nz - 1; i++) {
-    const float t = depz[i + 1] - depz[i];
-    const float minthk = t / minthk0;
-    const int nsub = (int)((t + 1.0e-4f) / minthk) + 1;
-    for (int j = 1; j <= nsub; j++) {
-      knot.push_back(i); jlay.push_back(i); fm.push_back((float)(2 * j - 1)); den.push_back((float)(2 * nsub));
-      thk.push_back(t / (float)nsub);
-    }
+  for (const DzRefinedLayer &L : dz_refine_layers(depz, nz, minthk0)) {   // (0-based knots here; the half-space: knot -1, row nz - 1)
+    knot.push_back(L.iv - 1); jlay.push_back(L.iv ? L.iv - 1 : nz - 1); fm.push_back(L.fm); den.push_back(L.den); thk.push_back(L.thk);
   }
-  knot.push_back(-1); jlay.push_back(nz - 1); fm.push_back(0.f); den.push_back(1.f); thk.push_back(0.f);
   const int mmax = (int)knot.size();
   if (mmax > NLMAX) return dz_fail(ctx, DAZIM_E_BAD_ARG, "refined model has %d layers > NL=%d", mmax, NLMAX);
   std::vector<double> zd(mmax), pw_rho(mmax), pw_el(mmax);

@@ -397,6 +397,81 @@ def test_column_curves_in_teams_are_bit_identical():
             assert np.array_equal(a, b)
 
 
+FASTDIV_DENOMINATORS = (6, 10, 12, 14, 18, 20, 22, 24, 26, 28, 30, 36)   # the divisors the reciprocal + correction form was verified on
+
+
+def _division_class(depz, sublayers, rden_option=1):
+    """the kernel class (template argument RDEN) the driver picks: the 2*nsub of refineGrid2LayerMdl with the driver's fp32
+    expressions; 1 = all powers of two, 2 = powers of two or verified divisors, 0 = divide (or option disp.rden = 0)"""
+    depz = np.asarray(depz, np.float32)
+    thk = depz[1:] - depz[:-1]
+    minthk = thk / np.float32(sublayers)
+    den = 2 * (((thk + np.float32(1.0e-4)) / minthk).astype(np.int64) + 1)
+    assert thk.dtype == np.float32 and minthk.dtype == np.float32
+    if rden_option == 0:
+        return 0, den
+    pow2 = (den & (den - 1)) == 0
+    if pow2.all():
+        return 1, den
+    return (2 if (pow2 | np.isin(den, FASTDIV_DENOMINATORS)).all() else 0), den
+
+
+def test_every_dispersion_kernel_form_gives_the_same_bits():
+    """The driver launches one of four kernels per division class (RDEN 0, 1, 2): the plain form, the team form (the columns' own
+    curves of a two-stream call), the form with shared layer stacks (the perturbed copies) and the first-period bracket kernel.
+    Each class is run (a) plain on every variant, one stream, (b) with the defaults (shared stacks), (c) on two streams with the
+    curves in teams and (d) as (a) without the bracket kernel: pvRc, the three kernel tables and the failure count must be the
+    same bits in all four, class 0 (option disp.rden = 0) must equal class 2 on the same model, and the same model passed as host
+    arrays declines the second stream and equals (a)."""
+    import torch
+    import dazimsurftomo_amd as dz
+    dev = torch.device("cuda:0")
+    depz = np.array([0.0, 5.0, 10.0, 20.0, 35.0, 60.0], np.float32)
+    t = np.array([5.0, 8.0, 12.0, 18.0, 26.0, 36.0])
+    vel = model(5, 4, depz, 21)
+    d_vel = torch.from_numpy(np.ascontiguousarray(vel)).to(dev)
+
+    def call(v, opts, want):
+        c = dz.Context(0)
+        try:
+            for k, o in opts.items():
+                c.set_option(k, o)
+            pv, sen, nf = c.depthkernel(v, depz, t, sublayers)
+            for k, w in want.items():
+                assert c.kernel_seconds(k) == w, (cls, opts, k, c.kernel_seconds(k))
+            c.sync()
+            if isinstance(pv, torch.Tensor):
+                pv, sen = pv.cpu().numpy(), [s.cpu().numpy() for s in sen]
+            return pv, sen, nf
+        finally:
+            c.close()
+
+    def same(x, y, what):
+        assert x[2] == y[2], (what, x[2], y[2])
+        assert np.array_equal(x[0], y[0]), (what, "pvRc", np.abs(x[0] - y[0]).max())
+        for q, (a, b) in enumerate(zip(x[1], y[1])):
+            assert np.array_equal(a, b), (what, "sen", q, np.abs(a - b).max())
+
+    by_class = {}
+    for cls, sublayers, rden, den_want in ((1, 3.0, 1, 8), (2, 2.0, 1, 6), (0, 2.0, 0, 6)):
+        got, den = _division_class(depz, sublayers, rden)
+        assert got == cls and (den == den_want).all(), (cls, got, den)
+        base = {"disp.rden": 0} if rden == 0 else {}
+        plain = dict(base, **{"disp.share": 0})
+        a = call(d_vel, plain, {"disp.share": 0, "disp.async": 0, "disp.ffwd_mode": 1})
+        b = call(d_vel, base, {"disp.share": 1, "disp.async": 0})
+        c2 = call(d_vel, dict(base, **{"disp.async": 2, "disp.team": 1}), {"disp.async": 1, "disp.team": 16, "disp.share": 1})
+        d = call(d_vel, dict(plain, **{"disp.ffwd": 0}), {"disp.share": 0, "disp.async": 0, "disp.ffwd_mode": 0})
+        host = call(vel, dict(base, **{"disp.async": 2}), {"disp.async": 0})   # (staged buffers decline the second stream)
+        assert (a[0] > 0).all() and a[2] == 0 and all(np.abs(s).max() > 0 for s in a[1])   # (a real answer, not equal garbage)
+        same(b, a, (cls, "shared stacks"))
+        same(c2, a, (cls, "two streams, teams"))
+        same(d, a, (cls, "no fast-forward"))
+        same(host, a, (cls, "host arrays"))
+        by_class[cls] = a
+    same(by_class[0], by_class[2], "dividing class against reciprocal + correction")
+
+
 @pytest.mark.gpu
 def test_host_copies_join_the_perturbed_copies_only_when_they_touch_their_arrays():
     """dazim_memcpy_h2d / _d2h after an asynchronous dazim_dispersion_kernels call: a copy into an unrelated device array leaves
