@@ -392,10 +392,10 @@ class Context:
                                               _ptr(x, np.float32), C.byref(ne), _ptr(st)))
         return x, ne.value, st
 
-    def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50):
+    def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
         cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
-        data."""
+        data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal)."""
         nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
         vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
         vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
@@ -405,7 +405,10 @@ class Context:
         self._check(self.lib.dazim_mc_create(self._h, nx, ny, nz, kmax, int(nchain), int(nbin), C.c_ulonglong(int(seed)), _ptr(vel0),
                                              _ptr(vmin), _ptr(vmax), _ptr(cobs), _ptr(wdat), C.c_float(step), int(nadapt),
                                              C.byref(h), C.byref(ne)))
-        return MonteCarlo(self, h, nx, ny, nz, kmax, nchain, nbin, ne.value)
+        mc = MonteCarlo(self, h, nx, ny, nz, kmax, nchain, nbin, ne.value)
+        if proposal != 0:
+            mc.set_proposal(proposal)
+        return mc
 
     def ray_paths(self):
         """ray geometries of the last rays_build_G call made with option rays.keep_paths = 1: a list of [nrp][2] arrays
@@ -529,6 +532,29 @@ class MonteCarlo:
         class _Cai:   # (the CUDA array interface: torch wraps the device pointer without a copy)
             __cuda_array_interface__ = dict(shape=(self.nz, n.value), typestr="<f4", data=(p.value, False), version=2, strides=None)
         return torch.as_tensor(_Cai(), device=torch.device("cuda", self.ctx.device))
+
+    def set_proposal(self, kind):
+        """the proposal kind (dazim_mc_set_proposal): 0 isotropic in box units, 1 shaped by the chains' covariance, learnt during
+        burn-in and frozen afterwards; refused once a step has been done"""
+        self.ctx._check(self.ctx.lib.dazim_mc_set_proposal(self.ctx._h, self._h, int(kind)))
+
+    def cov_state(self):
+        """the proposal kind and, for kind 1, copies of the covariance state (dazim_mc_cov_state): dict kind, cov_n[sampled cells],
+        cov_s1[sampled cells][nlay], cov_s2, chol[sampled cells][nlay (nlay + 1) / 2] (pair (a, c), c <= a, at a (a + 1) / 2 + c),
+        cov_set[sampled cells]; for kind 0 dict kind alone"""
+        kind = C.c_int(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_cov_state(self.ctx._h, self._h, C.byref(kind), None, None, None, None, None))
+        if kind.value != 1:
+            return dict(kind=kind.value)
+        npair = self.nlay * (self.nlay + 1) // 2
+        cov_n = np.zeros(self.ncs, np.int64)
+        s1 = np.zeros((self.ncs, self.nlay), np.float64)
+        s2 = np.zeros((self.ncs, npair), np.float64)
+        chol = np.zeros((self.ncs, npair), np.float64)
+        cov_set = np.zeros(self.ncs, np.int32)
+        self.ctx._check(self.ctx.lib.dazim_mc_cov_state(self.ctx._h, self._h, None, _ptr(cov_n), _ptr(s1), _ptr(s2), _ptr(chol),
+                                                        _ptr(cov_set)))
+        return dict(kind=1, cov_n=cov_n, cov_s1=s1, cov_s2=s2, chol=chol, cov_set=cov_set)
 
     def step(self, pv, record):
         """one step on pv[kmax][ncol] (fp64; numpy or torch-cuda), the curves of proposals(); record 0 = burn-in"""

@@ -18,8 +18,15 @@ constexpr int MC_WAVE = 64, MC_MAXLAY = 63, MC_MAXPER = 60, MC_MAXCHAIN = 64;
 // Reflections of a proposal into its box.  u >= 2^-33 bounds |z| by sqrt(66 ln 2) < 6.77, and s <= 0.5 (dazim_mc_create refuses a
 // larger start, the adaptation keeps it there) bounds the step by 3.39 box widths; each pass takes one width off the excess, so 4
 // passes always suffice.  The cap and the clamp behind it only make the loop's bound visible: they never act on a valid handle.
+// With the covariance proposal (kind 1) the step is s (hi - lo) y_k, y = L z: u in [0, 1] bounds C_kk, the squared norm of row k of L,
+// by 1/4 + 1e-8; each Box-Muller pair has norm r <= 6.77, so |z|_2 <= 6.77 sqrt(ceil(nlay / 2)); s <= 2 / sqrt(nlay).  Together
+// |s y_k| <= 2 * 0.50000001 * 6.77 * sqrt(ceil(nlay / 2) / nlay) < 6.78 box widths (the ratio is 1 at nlay = 1, less above): at most 7
+// passes, still below the cap.
 constexpr int MC_MAXFOLD = 8;
 constexpr float MC_SMIN = 1e-3f, MC_SMAX = 0.5f;
+// kind 1: states per knot a window must hold before it is factored, and the ridge on the diagonal of the covariance
+constexpr int MC_COV_MIN = 8;
+constexpr double MC_COV_RIDGE = 1e-8;
 
 // Philox4x32-10 (Salmon et al., SC'11): c = counter in, block out; key (k0, k1) = the seed's low and high words
 __device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
@@ -66,6 +73,11 @@ struct McDev {
   float *best;                 // [nlay][ncs]
   double *best_chi2;           // [ncs]
   unsigned long long *counters;   // [0] proposals without a root, [1] accepted moves of recorded steps
+  // kind 1 only (null otherwise); npair = nlay (nlay + 1) / 2, pair (a, c), c <= a, at a (a + 1) / 2 + c
+  long long *cov_n;            // [ncs] states in the sums
+  double *cov_s1, *cov_s2;     // [ncs][nlay], [ncs][npair]: sums of u and of u_a u_c, u the state in box units
+  double *chol;                // [ncs][npair]: the lower factor of the last covariance that factored
+  int *cov_set;                // [ncs]: 1 once chol holds a factor
 };
 
 // the next proposal of chain (cs, ch) from its current state: v' = v + s (vmax - vmin) z in fp64, reflected into the box, fp32
@@ -87,6 +99,94 @@ __device__ void mc_propose(const McDev &M, int cs, int ch, long long step, float
       for (int r = 0; r < MC_MAXFOLD && (v < lo || v > hi); r++) v = v < lo ? 2.0 * lo - v : 2.0 * hi - v;
       M.prop[k * M.ncol + col] = (float)fmin(fmax(v, lo), hi);
     }
+  }
+}
+
+__device__ __forceinline__ int mc_pair_row(int e) {   // the row a of packed pair e
+  int a = 0;
+  while ((a + 1) * (a + 2) / 2 <= e) a++;
+  return a;
+}
+
+// kind 1, a burn-in step with a decision: the cell's states us [nlay][nchain] (LDS) join the sums, pair e on lane e mod 64, the
+// chains in chain order inside the lane; the lane of the diagonal pair (a, a) keeps s1[a] too
+__device__ void mc_cov_accumulate(const McDev &M, int cs, int ch, const float *us) {
+  const int n = M.nlay, npair = n * (n + 1) / 2, nc = M.nchain, cell = M.cell_of[cs];
+  double *s1 = M.cov_s1 + (long)cs * n, *s2 = M.cov_s2 + (long)cs * npair;
+  for (int e = ch; e < npair; e += MC_WAVE) {
+    const int a = mc_pair_row(e), c = e - a * (a + 1) / 2;
+    const double loa = (double)M.vmin[(long)a * M.ncell + cell], wa = (double)M.vmax[(long)a * M.ncell + cell] - loa;
+    const double loc = (double)M.vmin[(long)c * M.ncell + cell], wc = (double)M.vmax[(long)c * M.ncell + cell] - loc;
+    double t1 = a == c ? s1[a] : 0.0, t2 = s2[e];
+    for (int j = 0; j < nc; j++) {
+      const double ua = ((double)us[a * nc + j] - loa) / wa, uc = ((double)us[c * nc + j] - loc) / wc;
+      t1 += ua;
+      t2 += ua * uc;
+    }
+    s2[e] = t2;
+    if (a == c) s1[a] = t1;
+  }
+  if (ch == 0) M.cov_n[cs] += nc;
+}
+
+// kind 1, an adaptation point with cn >= MC_COV_MIN nlay states in the sums (visible to every lane): the covariance of the window
+// into L (LDS, packed lower triangle), the sums back to 0, then k_column_lsq's right-looking Cholesky on the packed triangle.
+// Returns whether every pivot was finite and > 0 (the same on every lane); L holds the factor then.
+__device__ bool mc_cov_factor(const McDev &M, int cs, int ch, long long cn, double *L) {
+  const int n = M.nlay, npair = n * (n + 1) / 2;
+  double *s1 = M.cov_s1 + (long)cs * n, *s2 = M.cov_s2 + (long)cs * npair;
+  const double dn = (double)cn;
+  for (int e = ch; e < npair; e += MC_WAVE) {
+    const int a = mc_pair_row(e), c = e - a * (a + 1) / 2;
+    double C = s2[e] / dn - (s1[a] / dn) * (s1[c] / dn);
+    if (a == c) C += MC_COV_RIDGE;
+    L[e] = C;
+  }
+  __syncthreads();
+  for (int e = ch; e < npair; e += MC_WAVE) s2[e] = 0.0;
+  if (ch < n) s1[ch] = 0.0;
+  if (ch == 0) M.cov_n[cs] = 0;
+  for (int c = 0; c < n; c++) {                   // column c
+    const int cc = c * (c + 1) / 2 + c;
+    const double p = L[cc];
+    if (!(isfinite(p) && p > 0.0)) return false;
+    const double d = sqrt(p);
+    if (ch > c && ch < n) L[ch * (ch + 1) / 2 + c] /= d;
+    __syncthreads();
+    if (ch == c) L[cc] = d;
+    const int m = n - c - 1;
+    for (int q = ch; q < m * m; q += MC_WAVE) {
+      const int a = c + 1 + q / m, e = c + 1 + q % m;
+      if (e <= a) L[a * (a + 1) / 2 + e] -= L[a * (a + 1) / 2 + c] * L[e * (e + 1) / 2 + c];
+    }
+    __syncthreads();
+  }
+  return true;
+}
+
+// kind 1, a cell with a factor: v' = v + s (vmax - vmin) y, y = L z with the normals of mc_propose, y_k summed in j order in fp64.
+// zs [nlay][nchain] (LDS) takes the chain's normals; L is read at one address by every lane (a broadcast).
+__device__ void mc_propose_cov(const McDev &M, int cs, int ch, long long step, float s, const double *L, double *zs) {
+  const int cell = M.cell_of[cs], nc = M.nchain;
+  const long col = (long)cs * M.nchain + ch;
+  const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
+  for (int q = 0; q * 4 < M.nlay; q++) {
+    unsigned w[4];
+    mc_block(w, step, gid, 1u + (unsigned)q, M.seed);
+    const double r0 = sqrt(-2.0 * log(mc_uniform(w[0]))), t0 = 6.283185307179586 * mc_uniform(w[1]);
+    const double r1 = sqrt(-2.0 * log(mc_uniform(w[2]))), t1 = 6.283185307179586 * mc_uniform(w[3]);
+    const double z[4] = {r0 * cos(t0), r0 * sin(t0), r1 * cos(t1), r1 * sin(t1)};
+    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) zs[(q * 4 + i) * nc + ch] = z[i];
+  }
+  for (int k = 0; k < M.nlay; k++) {
+    const double *Lk = L + k * (k + 1) / 2;
+    double y = 0.0;
+    for (int j = 0; j <= k; j++) y += Lk[j] * zs[j * nc + ch];
+    const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
+    const double d = (double)s * (hi - lo);
+    double v = (double)M.cur[k * M.ncol + col] + d * y;
+    for (int r = 0; r < MC_MAXFOLD && (v < lo || v > hi); r++) v = v < lo ? 2.0 * lo - v : 2.0 * hi - v;
+    M.prop[k * M.ncol + col] = (float)fmin(fmax(v, lo), hi);
   }
 }
 
@@ -127,6 +227,9 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
 
 // one step, one wavefront per sampled cell, lane = chain.  pv [kmax][ncol]: the curves of the proposals.
 // first: the proposals are the start models -- they become the state, no decision.  adapt: the end of an adaptation window.
+// KIND 1 (covariance proposals) adds, in dynamic LDS, L [npair] fp64 and behind it the normals zs [nlay][nchain] fp64, whose first
+// half holds the staged states [nlay][nchain] fp32 while they are accumulated: 48 384 bytes at nlay = 63, nchain = 64.
+template <int KIND>
 __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__restrict__ pv, long long step, int first, int record,
                                                      int adapt, int nadapt) {
   __shared__ float s_scale;
@@ -178,7 +281,10 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         const double rate = (double)win / ((double)nadapt * (double)M.nchain);
         if (rate > 0.40) s = s * 1.25f;
         else if (rate < 0.20) s = s / 1.25f;
-        s = fminf(fmaxf(s, MC_SMIN), MC_SMAX);
+        float smax = MC_SMAX;
+        if constexpr (KIND == 1)
+          if (M.cov_set[cs]) smax = 2.0f / sqrtf((float)M.nlay);
+        s = fminf(fmaxf(s, MC_SMIN), smax);
         M.scale[cs] = s;
         win = 0;
       }
@@ -220,8 +326,48 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       if (ch == 0) M.best_chi2[cs] = m;
     }
   }
-  __syncthreads();
-  if (act) mc_propose(M, cs, ch, step, s_scale);
+  if constexpr (KIND == 1) {
+    extern __shared__ double mc_lds[];
+    const int npair = M.nlay * (M.nlay + 1) / 2;
+    double *L = mc_lds, *zs = mc_lds + npair;
+    int set = M.cov_set[cs];
+    bool have = false;   // L holds the cell's factor
+    if (!record && !first) {
+      float *us = (float *)zs;
+      if (act)
+        for (int k = 0; k < M.nlay; k++) us[k * M.nchain + ch] = M.cur[k * M.ncol + col];
+      __syncthreads();
+      mc_cov_accumulate(M, cs, ch, us);
+      if (adapt) {
+        __syncthreads();
+        const long long cn = M.cov_n[cs];
+        if (cn >= (long long)MC_COV_MIN * M.nlay && mc_cov_factor(M, cs, ch, cn, L)) {
+          for (int e = ch; e < npair; e += MC_WAVE) M.chol[(long)cs * npair + e] = L[e];
+          have = true;
+          if (!set) {   // the first factor: the scale restarts for the new metric
+            set = 1;
+            if (ch == 0) {
+              M.cov_set[cs] = 1;
+              s_scale = 1.0f / sqrtf((float)M.nlay);
+              M.scale[cs] = s_scale;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (set) {
+      if (!have)
+        for (int e = ch; e < npair; e += MC_WAVE) L[e] = M.chol[(long)cs * npair + e];
+      __syncthreads();
+      if (act) mc_propose_cov(M, cs, ch, step, s_scale, L, zs);
+    } else if (act) {
+      mc_propose(M, cs, ch, step, s_scale);
+    }
+  } else {
+    __syncthreads();
+    if (act) mc_propose(M, cs, ch, step, s_scale);
+  }
 }
 
 // posterior statistics, one wavefront per inner cell, lane = knot.  nrec: recorded steps; ndec: recorded steps with a decision
@@ -319,6 +465,7 @@ struct dazim_mc {
   dazim_ctx *ctx = nullptr;
   McDev d{};
   int nadapt = 1;
+  int kind = 0;             // the proposal: 0 isotropic in box units, 1 shaped by the chains' covariance
   int64_t nstep = 0;        // steps done; 0 = the start models are drawn, not evaluated
   int64_t nburn_dec = 0;    // burn-in steps with a decision (the adaptation clock)
   int64_t nrec = 0, nrec_dec = 0;
@@ -359,8 +506,14 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
   const long long step = mc->nstep + 1;
   if (mc->d.ncs > 0) {
     DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
-    hipLaunchKernelGGL(k_mc_step, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), 0, ctx->stream, mc->d, pv, step, (int)first, record,
-                       (int)adapt, mc->nadapt);
+    if (mc->kind == 1) {
+      const size_t lds = ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double);
+      hipLaunchKernelGGL(k_mc_step<1>, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record,
+                         (int)adapt, mc->nadapt);
+    } else {
+      hipLaunchKernelGGL(k_mc_step<0>, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), 0, ctx->stream, mc->d, pv, step, (int)first, record,
+                         (int)adapt, mc->nadapt);
+    }
     DZ_HIP(hipGetLastError());
     DZ_HIP(hipEventRecord(mc->e1, ctx->stream));
   }
@@ -497,6 +650,54 @@ int dazim_mc_proposals(dazim_mc *mc, float **vel_dev, int64_t *ncol) {
   return 0;
 }
 
+int dazim_mc_set_proposal(dazim_ctx *ctx, dazim_mc *mc, int kind) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_set_proposal"))) return rc;
+  if (kind != 0 && kind != 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_proposal: kind %d is neither 0 nor 1", kind);
+  if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_proposal: the handle has done %lld steps", (long long)mc->nstep);
+  DZ_HIP(hipSetDevice(ctx->device));
+  McDev &M = mc->d;
+  if (kind == 1 && !M.chol) {
+    const size_t n1 = (size_t)M.ncs * M.nlay, n2 = (size_t)M.ncs * (M.nlay * (M.nlay + 1) / 2);
+    if ((rc = mc_alloc(mc, (size_t)M.ncs, &M.cov_n)) || (rc = mc_alloc(mc, n1, &M.cov_s1)) || (rc = mc_alloc(mc, n2, &M.cov_s2)) ||
+        (rc = mc_alloc(mc, (size_t)M.ncs, &M.cov_set)) || (rc = mc_alloc(mc, n2, &M.chol)))
+      return rc;
+    DZ_HIP(hipMemsetAsync(M.cov_n, 0, (size_t)M.ncs * sizeof(long long), ctx->stream));
+    DZ_HIP(hipMemsetAsync(M.cov_s1, 0, n1 * sizeof(double), ctx->stream));
+    DZ_HIP(hipMemsetAsync(M.cov_s2, 0, n2 * sizeof(double), ctx->stream));
+    DZ_HIP(hipMemsetAsync(M.cov_set, 0, (size_t)M.ncs * sizeof(int), ctx->stream));
+    DZ_HIP(hipMemsetAsync(M.chol, 0, n2 * sizeof(double), ctx->stream));
+    DZ_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  mc->kind = kind;
+  return 0;
+}
+
+int dazim_mc_cov_state(dazim_ctx *ctx, dazim_mc *mc, int *kind, int64_t *cov_n, double *cov_s1, double *cov_s2, double *chol,
+                       int *cov_set) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_cov_state"))) return rc;
+  if (kind) *kind = mc->kind;
+  if (mc->kind != 1) {
+    if (cov_n || cov_s1 || cov_s2 || chol || cov_set)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_cov_state: the handle's proposal kind %d keeps no covariance", mc->kind);
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  const McDev &M = mc->d;
+  const size_t n1 = (size_t)M.ncs * M.nlay, n2 = (size_t)M.ncs * (M.nlay * (M.nlay + 1) / 2);
+  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
+  };
+  DZ_HIP(get(cov_n, M.cov_n, (size_t)M.ncs * 8));
+  DZ_HIP(get(cov_s1, M.cov_s1, n1 * 8));
+  DZ_HIP(get(cov_s2, M.cov_s2, n2 * 8));
+  DZ_HIP(get(chol, M.chol, n2 * 8));
+  DZ_HIP(get(cov_set, M.cov_set, (size_t)M.ncs * 4));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv_u, int record) {
   int rc;
   if ((rc = mc_check(ctx, mc, "dazim_mc_step"))) return rc;
@@ -561,6 +762,14 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
   ctx->ksec["mc.steps"] = mc->d.ncs > 0 ? nstep : 0;
   ctx->ksec["mc.accept"] = dec > 0 ? (double)(c1[1] - c0[1]) / dec : 0.0;
   ctx->ksec["mc.no_root"] = (double)(c1[0] - c0[0]);
+  int cov_cells = 0;
+  if (mc->kind == 1 && mc->d.ncs > 0) {
+    std::vector<int> set((size_t)mc->d.ncs);
+    DZ_HIP(hipMemcpy(set.data(), mc->d.cov_set, set.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int v : set) cov_cells += v;
+  }
+  ctx->ksec["mc.proposal"] = mc->kind;
+  ctx->ksec["mc.cov_cells"] = cov_cells;
   if (n_no_root) *n_no_root = (int64_t)(c1[0] - c0[0]);
   return 0;
 }

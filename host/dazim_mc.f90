@@ -2,12 +2,14 @@
 ! random-walk Metropolis chains on one MI355X and reports the posterior mean, spread and credible interval of every knot (DESIGN.md
 ! section 14), where SurfDepthFromMaps_amd returns one linearised model.
 !
-!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed]]]]]
+!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal]]]]]]
 !
 ! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
 ! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
 ! Prior per cell and knot: uniform on [max(Minvel, MOD - width), min(Maxvel, MOD + width)]; width 0 (default) = [Minvel, Maxvel].
 ! nsample recorded steps (default 2000) after as many burn-in steps, nchain chains per cell (default 32), sigma_c 0.01 km/s, seed 1.
+! proposal 0 (default): moves isotropic in box units; 1: moves shaped by the chains' own covariance, learnt per cell during burn-in
+! and frozen afterwards (one more settings line and one more summary line: the cells with an adapted covariance).
 !
 ! Outputs (names of their own, so that the three programs can share a directory):
 !   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
@@ -25,7 +27,7 @@ program SurfDepthMC_amd
   character(len=100) :: inputfile, logfile
   type(para_t) :: p
   logical :: ex
-  integer :: nx, ny, nz, kmax, nsample, nchain
+  integer :: nx, ny, nz, kmax, nsample, nchain, proposal
   integer(c_long_long) :: seed
   real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, width, sigma_c
   real*8, allocatable :: tRc(:)
@@ -37,7 +39,7 @@ program SurfDepthMC_amd
   logical, allocatable :: sampled(:, :)
   real :: rms_all, t_run, t_disp, t_step
   real*8 :: s0, cnt
-  integer :: i, j, k, t, nlay, ncell, q, ns, nr
+  integer :: i, j, k, t, nlay, ncell, q, ns, nr, ncov
   integer(c_int) :: nfail, nempty
   integer(c_int64_t) :: nnoroot
   type(c_ptr) :: mc
@@ -45,7 +47,7 @@ program SurfDepthMC_amd
   write (*, *)
   write (*, *) '                       SurfDepthMC'
   write (*, *)
-  if (command_argument_count() < 1) error stop 'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed]]]]]'
+  if (command_argument_count() < 1) error stop 'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal]]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -54,16 +56,18 @@ program SurfDepthMC_amd
   Minvel = p%Minvel; Maxvel = p%Maxvel; kmax = p%kmaxRc; tRc = p%tRc
   if (nz <= 1) error stop 'error nz value.'
   if (kmax <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
-  nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1
+  nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1; proposal = 0
   call optional_arg(2, nsample)
   call optional_arg(3, nchain)
   call optional_arg(4, width)
   call optional_arg(5, sigma_c)
   call optional_arg(6, seed)
+  call optional_arg(7, proposal)
   if (nsample < 1) error stop 'nsample must be at least 1'
   if (nchain < 1 .or. nchain > 64) error stop 'nchain must be 1..64'
   if (width < 0) error stop 'width must not be negative'
   if (sigma_c <= 0) error stop 'sigma_c must be positive'
+  if (proposal /= 0 .and. proposal /= 1) error stop 'proposal must be 0 or 1'
   nlay = nz - 1
   ncell = (nx - 2)*(ny - 2)
   if (nlay > 63) error stop 'SurfDepthMC_amd samples at most 63 knots (nz <= 64)'
@@ -86,6 +90,7 @@ program SurfDepthMC_amd
     else
       write (q, '(a,2f8.3)') ' prior: uniform on para.in''s Vs range', Minvel, Maxvel
     end if
+    if (proposal == 1) write (q, '(a)') ' proposal 1: shaped by the chains'' covariance, learnt per cell during burn-in'
   end do
 
   call read_mod('MOD', p, depz, vsf)
@@ -116,10 +121,12 @@ program SurfDepthMC_amd
   do q = 6, 66, 60
     write (q, '(a,i8,a,i8)') ' cells sampled', ncell - nempty, '  cells without data (start model kept)', nempty
   end do
+  if (proposal /= 0) call dazim_check(dazim_mc_set_proposal(dazim_handle, mc, proposal), 'Monte-Carlo proposal')
   call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
   t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
   t_disp = real(dazim_last_kernel_seconds(dazim_handle, 'mc.disp'//c_null_char))
   t_step = real(dazim_last_kernel_seconds(dazim_handle, 'mc.step'//c_null_char))
+  ncov = nint(dazim_last_kernel_seconds(dazim_handle, 'mc.cov_cells'//c_null_char))
   allocate (mean(nx - 2, ny - 2, nlay), std(nx - 2, ny - 2, nlay), qq(nx - 2, ny - 2, nlay, 3), best(nx - 2, ny - 2, nlay))
   allocate (rhat(nx - 2, ny - 2, nlay), acc(nx - 2, ny - 2), chi2b(nx - 2, ny - 2))
   call dazim_check(dazim_mc_result(dazim_handle, mc, mean, std, qq, best, rhat, acc, chi2b), 'posterior statistics')
@@ -157,6 +164,7 @@ program SurfDepthMC_amd
   do q = 6, 66, 60
     write (q, '(a,i12,a,i12)') ' proposals without a root:', nnoroot, ' of', int(2*nsample, 8)*ns*nchain
     write (q, '(a,f9.2,a,f9.2,a,f9.3,a)') ' run', t_run, ' s (dispersion calls', t_disp, ' s, step kernels', t_step, ' s)'
+    if (proposal == 1) write (q, '(a,i8,a,i8)') ' cells with an adapted covariance:', ncov, ' of', ns
   end do
   if (ns > 0) then
     allocate (sorted(ns))

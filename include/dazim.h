@@ -308,6 +308,27 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
  *   Next proposals: v' = (double)v + ((double)s * (hi - lo)) * z_k, reflected (v' < lo -> 2 lo - v', v' > hi -> 2 hi - v') until
  *   inside, rounded to fp32 once; the last knot stays.  (|z| < 6.77 and s <= 0.5 bound the excess by 3.39 widths: at most 4
  *   reflections.  The loop stops after 8 and clamps to the box, which never acts.)
+ * Proposal kind 1 (dazim_mc_set_proposal; kind 0 is the step above, unchanged): the proposal takes the shape of the chains' own
+ *   covariance, learnt during burn-in (Haario et al., 2001) and frozen afterwards: the recorded steps are plain Metropolis steps with
+ *   a fixed symmetric proposal.  Per sampled cell, with npair = nlay (nlay + 1) / 2 and pair (a, c), c <= a, at a (a + 1) / 2 + c, the
+ *   handle holds cov_n (int64), cov_s1 [nlay], cov_s2 [npair] (fp64), chol [npair] (fp64, a lower-triangular factor) and cov_set
+ *   (int), all 0 at the start.  The step gains:
+ *   Accumulate: in a burn-in step with a decision (record = 0, t > 1), after the decision, for the chains ch = 0 .. nchain-1 in that
+ *   order, with u_k = ((double)v_k - lo_k) / (hi_k - lo_k) of the chain's state: cov_s1[k] += u_k, cov_s2[(a,c)] += u_a * u_c,
+ *   cov_n += 1.  Recorded steps accumulate nothing.
+ *   Factor: at the end of an adaptation window, after the scale rule, nothing if cov_n < 8 nlay (the sums keep growing: windows
+ *   merge for few chains).  Otherwise m = s1 / n, C(a,c) = s2(a,c) / n - m_a * m_c, the diagonal + 1e-8; a right-looking Cholesky in
+ *   dazim_column_lsq's elimination order (column by column: pivot p = C(c,c), d = sqrt(p), the column below / d, then one update
+ *   C(a,e) -= C(a,c) * C(e,c) per element of the trailing triangle) in fp64, stopped at the first pivot that is not finite and > 0.
+ *   If no pivot stopped it chol takes the factor, and if cov_set was 0 it becomes 1 and the cell's s becomes 1.0f / sqrtf((float)
+ *   nlay); otherwise chol and cov_set stay.  In both cases cov_n, cov_s1 and cov_s2 return to 0.
+ *   Scale range: while cov_set is 1 (as the scale rule finds it, before this window's factor) the clamp of s is [1e-3f, 2.0f /
+ *   sqrtf((float)nlay)] (fp32) instead of [1e-3f, 0.5f]; the thresholds and the factor 1.25f are the same.
+ *   Next proposals, same normals z: where cov_set is 1, y_k = sum_{j=0..k} chol(k,j) * z_j summed in j order in fp64 and v' =
+ *   (double)v + ((double)s * (hi - lo)) * y_k, with the same reflections, one rounding to fp32 and the last knot untouched; where
+ *   cov_set is 0, the formula above.  (u in [0, 1] bounds C_kk, the squared norm of row k of chol, by 1/4 + 1e-8; each Box-Muller
+ *   pair has norm <= 6.77, so |z|_2 <= 6.77 sqrt(ceil(nlay / 2)); s <= 2 / sqrt(nlay): the excess stays below 6.78 widths, at most 7
+ *   reflections, and the clamp still never acts.)
  * dazim_mc_create: vel0 [nz][ny][nx] (the last knot; the result of cells without data), vmin, vmax [nlay][ny-2][nx-2], cobs, wdat
  *   [kmax][ny-2][nx-2] (the layout of dazim_column_lsq), step = the initial s, nadapt >= 1.  Draws the start models.  Refused
  *   (DAZIM_E_BAD_ARG): nchain outside 1..64, nlay outside 1..63, kmax outside 1..60, nbin < 2, a non-finite vmin, vmax, cobs or
@@ -318,7 +339,12 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
  * dazim_mc_run: nburn burn-in then nsample recorded steps, each one dazim_dispersion_kernels call (nx = ncol, ny = 1, curves only,
  *   depz [nz] and periods [kmax] host arrays as there) and one step launch; no other host wait.  n_no_root (nullable) = proposals
  *   of the run with chi2' = +inf.  Stats: "mc" (seconds of the run), "mc.disp" (its dispersion kernels), "mc.step" (its step
- *   kernels), "mc.steps", "mc.accept" (accepted / decisions of its recorded steps), "mc.no_root".
+ *   kernels), "mc.steps", "mc.accept" (accepted / decisions of its recorded steps), "mc.no_root", "mc.proposal" (the kind) and
+ *   "mc.cov_cells" (cells with cov_set = 1 at its end).
+ * dazim_mc_set_proposal: kind 0 (the default) or 1; kind 1 allocates the arrays above.  DAZIM_E_BAD_ARG for another kind, for a
+ *   handle of another context, or once a step has been done.
+ * dazim_mc_cov_state: kind, and for kind 1 copies of cov_n, cov_set [sampled cells], cov_s1 [sampled cells][nlay], cov_s2, chol
+ *   [sampled cells][npair] (each pointer nullable, host or device).  DAZIM_E_BAD_ARG for kind 0 when an array is requested.
  * dazim_mc_state: copies of the chain state (each pointer nullable, host or device): cur [nz][ncol], chi2 [ncol], scale [sampled
  *   cells], step (steps done), sums [2][nlay][ncol], hist [sampled cells][nlay][nbin], accepted [ncol], best [nlay][sampled cells]
  *   and best_chi2 [sampled cells] (vel0's knots and +inf before the first recorded step).
@@ -331,6 +357,9 @@ int dazim_mc_create(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, int nchain
                     const float *vmin, const float *vmax, const float *cobs, const float *wdat, float step, int nadapt, dazim_mc **mc,
                     int *n_empty);
 int dazim_mc_proposals(dazim_mc *mc, float **vel_dev, int64_t *ncol);
+int dazim_mc_set_proposal(dazim_ctx *ctx, dazim_mc *mc, int kind);
+int dazim_mc_cov_state(dazim_ctx *ctx, dazim_mc *mc, int *kind, int64_t *cov_n, double *cov_s1, double *cov_s2, double *chol,
+                       int *cov_set);
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);
 int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
                  int64_t *n_no_root);

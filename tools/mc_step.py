@@ -1,7 +1,7 @@
 """Times of the Monte-Carlo step (profiles/depth_mc.md).
 
-    python tools/mc_step.py [--steps S] [--big N]
-    python tools/mc_step.py --program [--dir D]
+    python tools/mc_step.py [--steps S] [--big N] [--proposal K]
+    python tools/mc_step.py --program [--dir D] [--proposal K]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -11,7 +11,11 @@ k_mc_step launches ("mc.step") and the rest (host work of the calls) -- and curv
 --program: the wall time of host/SurfDepthMC_amd's default run (2 000 burn-in + 2 000 recorded steps, 32 chains) at S-256.  The
 inputs are written to D (default: a temporary directory): para.in with S-256's grid, knots, sublayers and periods, the model as MOD,
 and its exact curves as period_phaseV_map.dat (no coverage file: every cell and period weighted).  One JSON line with the wall time
-and the log's summary lines."""
+and the log's summary lines.
+
+--proposal 1: the covariance-adapted proposal (dazim_mc_set_proposal) instead of the default 0.  The timed run then adapts every 5
+burn-in steps instead of every 50, so that its S/2 burn-in steps hold factorisations and its recorded steps draw from the factor;
+"cov_cells" counts the cells that did."""
 import argparse
 import json
 import os
@@ -26,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one_case(ctx, n, nchain, steps):
+def one_case(ctx, n, nchain, steps, proposal):
     import bench
     bench.NX = bench.NY = n
     vel = bench.s256_model().astype(np.float32)
@@ -37,7 +41,7 @@ def one_case(ctx, n, nchain, steps):
     inner = vel[:nlay, 1:-1, 1:-1]
     vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
     wdat = np.full((kmax, n - 2, n - 2), 100.0, np.float32)
-    mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat)
+    mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat, nadapt=5 if proposal else 50, proposal=proposal)
     mc.run(depz, bench.MINTHK, periods, 5, 0)                 # warm-up: code objects, scratch buffers
     nr = mc.run(depz, bench.MINTHK, periods, steps // 2, steps - steps // 2)
     wall, disp, stp = ctx.stat("mc"), ctx.stat("mc.disp"), ctx.stat("mc.step")
@@ -45,7 +49,7 @@ def one_case(ctx, n, nchain, steps):
     mc.free()
     ms = lambda s: 1e3 * s / steps
     return {"grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots ({nlay} sampled), {kmax} periods", "nchain": nchain,
-            "steps": steps, "curves_per_step": mc.ncol, "ms_per_step": ms(wall), "disp_ms_per_step": ms(disp),
+            "proposal": proposal, "cov_cells": int(ctx.stat("mc.cov_cells")), "steps": steps, "curves_per_step": mc.ncol, "ms_per_step": ms(wall), "disp_ms_per_step": ms(disp),
             "mc_step_ms_per_step": ms(stp), "other_ms_per_step": ms(wall - disp - stp), "mc_step_share": stp / wall,
             "curves_per_s": mc.ncol * steps / wall, "accept": ctx.stat("mc.accept"), "no_root": nr,
             "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
@@ -74,7 +78,7 @@ cccccccccc periods
 """
 
 
-def program_run(ctx, d):
+def program_run(ctx, d, proposal):
     import bench
     n = bench.NX = bench.NY = 54
     vel = bench.s256_model().astype(np.float32)
@@ -99,12 +103,14 @@ def program_run(ctx, d):
                     f.write("%10.4f%10.4f%10.4f%10.4f\n" % (100.0 + (j - 1) * 0.25, 30.0 - (i - 1) * 0.25, periods[t], pv[t, j, i]))
     exe = os.path.join(ROOT, "host", "SurfDepthMC_amd")
     t0 = time.perf_counter()
-    out = subprocess.run([exe, "para.in"], cwd=d, capture_output=True, text=True, timeout=1500)
+    args = ["2000", "32", "0", "0.01", "1", str(proposal)] if proposal else []
+    out = subprocess.run([exe, "para.in"] + args, cwd=d, capture_output=True, text=True, timeout=1500)
     wall = time.perf_counter() - t0
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     log = open(os.path.join(d, "para.in_mc.log")).read().splitlines()
-    keep = [l.strip() for l in log if any(k in l for k in ("cells sampled", "without a root", "run", "acceptance", "R-hat", "rms_c"))]
-    return {"program": "SurfDepthMC_amd para.in (defaults: 2000 + 2000 steps, 32 chains)",
+    keep = [l.strip() for l in log if any(k in l for k in ("cells sampled", "without a root", "run", "acceptance", "R-hat", "rms_c", "proposal",
+                                                                "covariance"))]
+    return {"program": "SurfDepthMC_amd para.in (defaults: 2000 + 2000 steps, 32 chains)", "proposal": proposal,
             "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots, {kmax} periods", "wall_s": wall, "log": keep}
 
 
@@ -115,14 +121,15 @@ def main():
     ap.add_argument("--big", type=int, default=202)
     ap.add_argument("--program", action="store_true")
     ap.add_argument("--dir", default=None)
+    ap.add_argument("--proposal", type=int, default=0, choices=(0, 1))
     a = ap.parse_args()
     ctx = dz.Context(0)
     if a.program:
         with tempfile.TemporaryDirectory() as tmp:
-            print(json.dumps(program_run(ctx, a.dir or tmp)), flush=True)
+            print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal)), flush=True)
         return
     for n, nchain in ((54, 8), (54, 32), (54, 64), (a.big, 8)):
-        print(json.dumps(one_case(ctx, n, nchain, a.steps)), flush=True)
+        print(json.dumps(one_case(ctx, n, nchain, a.steps, a.proposal)), flush=True)
     ctx.close()
 
 
