@@ -22,6 +22,12 @@
 
 namespace {
 
+#ifdef DZ_RAYS_MARK   // experiment-only build: phase markers in the assembly (tools/rays_phase_count.py counts the instructions between them)
+#define RAYS_MARK(i) asm volatile("; MARK " #i ::: "memory")
+#else
+#define RAYS_MARK(i)
+#endif
+
 constexpr int GDX = 5, GDZ = 5;
 constexpr int RM = DAZIM_RMAX;
 constexpr float EARTH = 6371.0f;
@@ -85,6 +91,8 @@ struct RayArgs {
                            // coe_a / coe_rho of the LAST such cell of the ray, which is what the reference's second loop uses
                            // (inv/CalSurfG.f90:1369-1378, inv/CalSurfGAniso_Joint.f90:759-775 do not recompute them)
   long *countd;            // [nray] twin entries per row (count pass out when dense = 2)
+  int plain_step;          // option rays.plain_step (test knob): the stepping loop never carries a value over, always takes the general
+                           // vel_at and always does the refined-box work -- a second route to the same bits
   int keep_small;          // 1: keep every non-zero row entry of the |fdm| >= ftol cells (the forward program's dense GGc/GGs,
                            // fwd/FwdTraveltimeCPS.f90:694-712); 0: the inversion's second |row| > ftol threshold
   const long *rowptr;      // [nray+1] (emit pass in)
@@ -158,15 +166,18 @@ __device__ __forceinline__ void basis(float v, float b[4]) {  // inv/CalSurfG.f9
 
 // x / 6.0f through divr (the reciprocal is a compile-time constant)
 __device__ __forceinline__ float div6(float x) { return divr(x, 1.0 / 6.0); }
-// element i (0..3) of the cubic B-spline basis at v, inv/CalSurfG.f90:2145-2148: only the selected numerator is divided
-// (the kernel is bound by instruction issue; the four divisions of the plain form were a fifth of a step)
+// element i (0..3) of the cubic B-spline basis at v, inv/CalSurfG.f90:2145-2148: only the selected numerator is formed and divided
+// (the kernel is bound by instruction issue; the four divisions of the plain form were a fifth of a step).  i is a constant of the lane at every call site (hoisted, or folded where the compiler knows
+// its range).  Elements 0 and 3 are the cube of w = 1 - v or v; elements 1 and 2 are (p + c * w^2) + d * w^3 with w = v and
+// (p, c, d) = (4, -6, 3) or (1 + 3 v, 3, -3): the reference's sums in the reference's order, x + (-k) * y for its x - k * y (the
+// same number: negation is exact).  tools/check_basis.c compares this with the plain four-numerator form over all fp32 patterns.
 __device__ __forceinline__ float basis1(float v, int i) {
-  const float om = 1.0f - v;
-  const float n0 = om * om * om;
-  const float n1 = 4.0f - 6.0f * (v * v) + 3.0f * (v * v * v);
-  const float n2 = 1.0f + 3.0f * v + 3.0f * (v * v) - 3.0f * (v * v * v);
-  const float n3 = v * v * v;
-  return div6(i == 0 ? n0 : (i == 1 ? n1 : (i == 2 ? n2 : n3)));
+  const float w = i == 0 ? 1.0f - v : v;
+  const float t2 = w * w, t3 = t2 * w;
+  const float p = i == 1 ? 4.0f : 1.0f + 3.0f * v;
+  const float c = i == 1 ? -6.0f : 3.0f, d = i == 1 ? 3.0f : -3.0f;
+  const float n = (p + c * t2) + d * t3;
+  return div6((i == 0 || i == 3) ? t3 : n);
 }
 
 // bilinear velocity inside coarse cell (ipx,ipz), inv/CalSurfG.f90:2129-2137
@@ -181,6 +192,21 @@ __device__ __forceinline__ float vel_at(const dazim_geom &g, const float *veln, 
       produ = produ * (1.0f - fabsf(divr((float)(l - 1) * g.dnx - drx, rdnx)));
       if (ipz - 1 + m <= g.nnz && ipx - 1 + l <= g.nnx && ipz - 1 + m >= 1 && ipx - 1 + l >= 1)
         vel = vel + veln[(size_t)(ipx - 2 + l) * g.nnz + (ipz - 2 + m)] * produ;
+    }
+  return vel;
+}
+// the same for a cell that touches neither the last row nor the last column of the grid (1 <= ipx < nnx, 1 <= ipz < nnz): all four
+// bounds tests of vel_at pass there, so the four terms are added unconditionally, in the same order
+__device__ __forceinline__ float vel_at_interior(const dazim_geom &g, const float *veln, int ipx, int ipz, float drx, float drz,
+                                                 double rdnx, double rdnz) {
+  float vel = 0.0f;
+#pragma unroll
+  for (int l = 1; l <= 2; l++)
+#pragma unroll
+    for (int m = 1; m <= 2; m++) {
+      float produ = (1.0f - fabsf(divr((float)(m - 1) * g.dnz - drz, rdnz)));
+      produ = produ * (1.0f - fabsf(divr((float)(l - 1) * g.dnx - drx, rdnx)));
+      vel = vel + veln[(size_t)(ipx - 2 + l) * g.nnz + (ipz - 2 + m)] * produ;
     }
   return vel;
 }
@@ -450,24 +476,40 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
           const float *t = ttn + (size_t)(ipx - 1) * nnz + (ipz - 1);
           tc00 = t[0]; tc01 = t[1]; tc10 = t[nnz]; tc11 = t[nnz + 1];
         }
+      };
+      auto load_refined_corner_times = [&]() {
         if (ipxr >= 1 && ipxr < nnxr && ipzr >= 1 && ipzr < nnzr) {   // (outside the refined box igref is 0 and these are not used)
           const float *u = ttnr + (size_t)(ipxr - 1) * RM + (ipzr - 1);
           tr00 = u[0]; tr01 = u[1]; tr10 = u[RM]; tr11 = u[RM + 1];
         }
       };
       load_corner_times();
+      load_refined_corner_times();
       // What a step needs at its starting point -- velocity and B-spline weights at (x0, z0) -- is what the step before computed at
       // its end point, bit for bit, whenever that end point was the step's (x1, z1) itself in the same cells: the last sub-segment
       // ends at x0 + 1.0f * (x1 - x0), which is x1 exactly unless the two differ by more than a factor of two (Sterbenz), and the
       // cell indices agree unless the point was clipped to the grid.  Checked per ray after every step; the values are carried
       // over only while every ray of the wavefront may (a sixth of the step's instructions otherwise repeated).
+      // What is carried is the start-point term of the scatter itself, rdc = vi * wi / (vel * vel) per cell of this lane: the end-point
+      // term (rdc1) of one sub-segment is the start-point term (rdc2) of the next, same operands and same operations, within a step
+      // and -- with `carry` -- from the last sub-segment of one step to the first of the next.  vel, vi and wi live inside a sub-segment.
       bool carry = false;
-      float vel_c = 0.0f, vi_c = 0.0f, wi_c[LPR];
+      float rdc[LPR];
 #pragma unroll
-      for (int q = 0; q < LPR; q++) wi_c[q] = 0.0f;
+      for (int q = 0; q < LPR; q++) rdc[q] = 0.0f;
+      // Wave-uniform limits of the two short cuts below, closed until the first step's start-point block (the one rare block every
+      // ray passes) has looked at option rays.plain_step, and left closed by it: `fart` = +inf, no point is far from the refined box;
+      // nnx_in = nnz_in = 0, no cell is interior (which also keeps `carry` off).
+      // Far from the refined box: the box has at most RM nodes per axis, (RM - 1) / 8 = 16 coarse cells (eight refined cells per coarse
+      // one, fmm.hip), and contains its source's cell, so a point more than 16 coarse cells from the source in x or in z is outside it.
+      // One more cell of margin (eight refined cells) covers the roundings of the box origin, of the differences and of the
+      // reciprocal products, which are ~1e-3 of a refined cell; max(dnx, dnz) serves both axes.  A NaN compares false: not far.
+      float fart = __builtin_inff();
+      int nnx_in = 0, nnz_in = 0;
       const long maxrp = (long)nnx * nnz;
       for (long j = 1; j <= maxrp; j++) {
         if (sw == 1) break;
+        RAYS_MARK(0);
         float dtx, dtz;
         if (igref == 1) {
           dtx = tr10 - tr00;
@@ -487,24 +529,36 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
         const float rd1 = sqrtf(dtx * dtx + dtz * dtz);
         float x1 = x0 - dpl * dtx / (EARTH * rd1);
         float z1 = z0 - dpl * dtz / (EARTH * sinx0 * rd1);
+        RAYS_MARK(1);
         const int ipxo = ipx, ipzo = ipz;
-        ipxr = (int)divr(x1 - goxr, rdnxr) + 1;
-        ipzr = (int)divr(z1 - gozr, rdnzr) + 1;
-        igref = in_refined(ipxr, ipzr);
+        const float sdx = scx - x1, sdz = scz - z1;
+        bool srcell = false;   // the point is in the source's cell of the refined grid
+        if (__ballot(!(fabsf(sdx) > fart || fabsf(sdz) > fart)) != 0) {
+          ipxr = (int)divr(x1 - goxr, rdnxr) + 1;
+          ipzr = (int)divr(z1 - gozr, rdnzr) + 1;
+          igref = in_refined(ipxr, ipzr);
+          srcell = igref == 1 && ipxr == isx && ipzr == isz;
+          load_refined_corner_times();
+        } else {   // every ray of the wavefront is far from its refined box: in_refined would be 0 and the refined times unused
+          igref = 0;
+        }
         ipx = (int)divr(x1 - gox, rdnx) + 1;
         ipz = (int)divr(z1 - goz, rdnz) + 1;
+        RAYS_MARK(2);
         float sinx1 = dz_sinf(x1);
-        sred = ((scx - x1) * EARTH) * ((scx - x1) * EARTH);
-        e2 = (scz - z1) * EARTH * sinx1;
+        sred = (sdx * EARTH) * (sdx * EARTH);
+        e2 = sdz * EARTH * sinx1;
         sred = sqrtf(sred + e2 * e2);
         sw = 0;
         if (sred < 2.0f * dpl) sw = 1;
-        if (sw == 0 && igref == 1 && ipxr == isx && ipzr == isz) sw = 1;
+        if (srcell) sw = 1;
+        RAYS_MARK(3);
         bool clipx = false;
         if (ipx < 1) { x1 = gox; ipx = 1; rb = 1; clipx = true; }
         if (ipx >= nnx) { x1 = gox + (float)(nnx - 1) * dnx; ipx = nnx - 1; rb = 1; clipx = true; }
         if (ipz < 1) { z1 = goz; ipz = 1; rb = 1; }
         if (ipz >= nnz) { z1 = goz + (float)(nnz - 1) * dnz; ipz = nnz - 1; rb = 1; }
+        RAYS_MARK(4);
         load_corner_times();
         if (keep_pts) {   // rgx(j+1) after the clipping, then rgx(j+2) = the source if this was the last step (:352-400)
           if (np < A.pcap) rp[np] = make_float2(x1, z1);
@@ -517,6 +571,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
         if (clipx) sinx1 = dz_sinf(x1);   // the next step starts from the clipped point
         float c2psi = 0.0f, s2psi = 0.0f;
         if (AZIM) step_azimuth(x0, z0, x1, z1, c2psi, s2psi);
+        RAYS_MARK(5);
         // ---- Frechet weights, :2077-2229 ----
         const int ivx = (ipx - 1) / GDX + 1, ivz = (ipz - 1) / GDZ + 1;
         const int ivxo = (ipxo - 1) / GDX + 1, ivzo = (ipzo - 1) / GDZ + 1;
@@ -548,27 +603,27 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
         nhp++;  // the closing sub-segment with vrat = 1, chp = 0
         if (nhp == 1) vr0 = 1.0f;
         if (nhp == 2) vr1 = 1.0f;
+        RAYS_MARK(6);
         float drx, drz;
-        float vel = vel_c, vi = vi_c, wi[LPR];            // this lane's vi(m), wi(l)
-#pragma unroll
-        for (int q = 0; q < LPR; q++) wi[q] = wi_c[q];
         if (__builtin_expect(__ballot(!carry) != 0, 0)) {  // (first step, clipped points: rare -- and wave-uniform, so out of line)
           drx = (x0 - gox) - (float)(ipxo - 1) * dnx;
           drz = (z0 - goz) - (float)(ipzo - 1) * dnz;
-          vel = vel_at(g, veln, ipxo, ipzo, drx, drz, rdnx, rdnz);
+          const float vel = vel_at(g, veln, ipxo, ipzo, drx, drz, rdnx, rdnz);
           drx = (x0 - gox) - (float)(ivxo - 1) * dvx;
           drz = (z0 - goz) - (float)(ivzo - 1) * dvz;
-          vi = basis1(divr(drx, rdvx), lm);
+          const float vi = basis1(divr(drx, rdvx), lm);
 #pragma unroll
-          for (int q = 0; q < LPR; q++) wi[q] = basis1(divr(drz, rdvz), l0 + q * LSTEP);
+          for (int q = 0; q < LPR; q++) rdc[q] = vi * basis1(divr(drz, rdvz), l0 + q * LSTEP) / (vel * vel);
+          if (A.plain_step == 0) {   // open the short cuts (see above)
+            fart = (float)((RM - 1) / 8 + 1) * fmaxf(dnx, dnz);
+            nnx_in = nnx;
+            nnz_in = nnz;
+          }
         }
+        RAYS_MARK(7);
         int ivxt = ivxo, ivzt = ivzo;
         bool endsame = false;
         for (int k = 1; k <= nhp; k++) {
-          const float velo = vel, vio = vi;
-          float wio[LPR];
-#pragma unroll
-          for (int q = 0; q < LPR; q++) wio[q] = wi[q];
           if (k > 1) {
             const int cp = (k == 2) ? chp0 : chp1;
             if (cp == 1) ivxt = ivx;
@@ -582,15 +637,21 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
           endsame = rigx == x1 && rigz == z1 && ipxt == ipx && ipzt == ipz && ivxt == ivx && ivzt == ivz;   // (of the last sub-segment)
           drx = (rigx - gox) - (float)(ipxt - 1) * dnx;
           drz = (rigz - goz) - (float)(ipzt - 1) * dnz;
-          vel = vel_at(g, veln, ipxt, ipzt, drx, drz, rdnx, rdnz);
+          const bool inner = ipxt >= 1 && ipxt < nnx_in && ipzt >= 1 && ipzt < nnz_in;
+          endsame = endsame && inner;   // (a start point in an edge cell is formed anew by the general vel_at)
+          float vel;
+          if (__builtin_expect(__ballot(!inner) == 0, 1)) vel = vel_at_interior(g, veln, ipxt, ipzt, drx, drz, rdnx, rdnz);
+          else vel = vel_at(g, veln, ipxt, ipzt, drx, drz, rdnx, rdnz);
           drx = (rigx - gox) - (float)(ivxt - 1) * dvx;
           drz = (rigz - goz) - (float)(ivzt - 1) * dvz;
-          vi = basis1(divr(drx, rdvx), lm);
+          const float vi = basis1(divr(drx, rdvx), lm);
+          float wi[LPR];            // this lane's vi(m), wi(l)
 #pragma unroll
           for (int q = 0; q < LPR; q++) wi[q] = basis1(divr(drz, rdvz), l0 + q * LSTEP);
           const float dinc = (k == 1) ? vrk * dpl : (vrk - vrp) * dpl;
           // block of this sub-segment: cells (ivzt-2+l, ivxt-2+m), l,m = 1..4
           const int nbx = ivxt - 1, nbz = ivzt - 1;
+          RAYS_MARK(8);
           if (nbx != cbx || nbz != cbz) {
             flush();
             cbar();
@@ -603,10 +664,12 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
               if (AZIM) { accc[q] = gfdmc[fi]; accs[q] = gfdms[fi]; }
             }
           }
+          RAYS_MARK(9);
 #pragma unroll
           for (int q = 0; q < LPR; q++) {
             const float rdc1 = vi * wi[q] / (vel * vel);
-            const float rdc2 = vio * wio[q] / (velo * velo);
+            const float rdc2 = rdc[q];
+            rdc[q] = rdc1;
             float r1 = -(rdc1 + rdc2) * dinc / 2.0f;
             acc[q] = r1 + acc[q];
             if (AZIM) {   // inv/rpathsAzim.f90:580-586
@@ -617,14 +680,12 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
             }
           }
         }
+        RAYS_MARK(10);
         carry = endsame;
-        vel_c = vel;
-        vi_c = vi;
-#pragma unroll
-        for (int q = 0; q < LPR; q++) wi_c[q] = wi[q];
         x0 = x1;
         z0 = z1;
         sinx0 = sinx1;
+      RAYS_MARK(11);
       }
       flush();
       if (keep_pts) A.npts[ray] = np <= A.pcap ? np : -1;
@@ -1010,6 +1071,7 @@ struct RayBuild {
     if (A.lcap > g.nvx * g.nvz) A.lcap = g.nvx * g.nvz;
     A.LK = A.lcap;   // cell lists handed from the count pass to the emit pass (longer ones are traced again)
     A.keep_small = dz_opt(ctx, "rays.keep_small", 0) != 0 ? 1 : 0;
+    A.plain_step = dz_opt(ctx, "rays.plain_step", 0) != 0 ? 1 : 0;
     A.pts = nullptr; A.npts = nullptr; A.pcap = 0;
     if (dz_opt(ctx, "rays.keep_paths", 0) != 0) {
       // a ray advances half a cell per step: a few times (nnx + nnz) points even for a path that wanders; longer ones are flagged
