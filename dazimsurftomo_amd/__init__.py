@@ -273,6 +273,14 @@ class Context:
         return out
 
     # ---- K4+K5 -------------------------------------------------------------------------------
+    def _check_rays(self, rc, tpred, nnz, nb):
+        """a ray call that failed on a ray's status (receiver outside) has still filled in the other rays' times, the entry count of
+        their rows and the boundary count: the error carries them as `partial` (there is no matrix)"""
+        if rc:
+            err = DazimError(rc, self.lib.dazim_last_error(self._h).decode())
+            err.partial = {"tpred": tpred, "nnz": nnz.value, "n_boundary": nb.value}
+            raise err
+
     def rays_build_G(self, nx, ny, goxd, gozd, dvxd, dvzd, vels, fields, scx, scz, period_idx, field_of_ray,
                      rcx, rcz, sen, kernel_idx=None, tpred=None, lsen=None):
         """srtimes + rpaths + row assembly (receiver loop of CalSurfG, inv/CalSurfG.f90:1326-1364).
@@ -303,7 +311,7 @@ class Context:
             rc = self.lib.dazim_rays_build_G(*args, *tail)
         else:              # joint rows dVs | Gc | Gs (CalSurfGAnisoJoint), lsen = Lsen_Gsc[nz-1][kmax][nx*ny]
             rc = self.lib.dazim_rays_build_G_joint(*args, _ptr(lsen, np.float32), *tail)
-        self._check(rc)
+        self._check_rays(rc, tpred, nnz, nb)
         n = (nx - 2) * (ny - 2) * (nz - 1) * (1 if lsen is None else 3)
         return SparseMatrix(self, h, nray, n, nnz.value), tpred, nb.value
 
@@ -331,7 +339,7 @@ class Context:
                                               _ptr(fields["veln"]), _ptr(fields["ttn"]), _ptr(fields["ttnr"]), _ptr(fields["nstsr"]),
                                               bptr, C.c_int64(nray), _ptr(field_of_ray), _ptr(rcx), _ptr(rcz), _ptr(tpred),
                                               C.byref(h), C.byref(nnz), C.byref(nb))
-        self._check(rc)
+        self._check_rays(rc, tpred, nnz, nb)
         n = (nx - 2) * (ny - 2) * kmax * (3 if azim else 1)
         return SparseMatrix(self, h, nray, n, nnz.value), tpred, nb.value
 

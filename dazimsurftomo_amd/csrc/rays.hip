@@ -8,7 +8,9 @@
 // is inherently serial and is executed redundantly by the lanes of a group, while the 4x4 B-spline scatter of every
 // sub-segment is spread over them: each lane keeps two cells of the current 4x4 block of the Frechet grid(s) in
 // registers and the block is written back to the ray's grid in HBM scratch only when the ray leaves it.  Touched cells are collected in an
-// LDS cell list.  Rows are emitted straight into CSR in the reference's column order (depth-major, then jj,
+// LDS cell list.  The grid of a ray (its "slot") is stored in the order the list wants it (jj the row, kk contiguous) and is all zeros
+// between rays: a ray remembers the range of B-spline blocks it has been in, looks for its cells in that range only and puts zeros
+// back into it, so the work per ray follows the ray and not the grid.  Rows are emitted straight into CSR in the reference's column order (depth-major, then jj,
 // kk) by a count pass, an exclusive scan and an emit pass that reuses the saved cell lists -- no atomics, so G
 // is reproducible.  fp32 without FMA like the reference.
 #include <cmath>
@@ -73,7 +75,7 @@ struct RayArgs {
   int *nlist;              // [nray]  cells with |fdm| >= ftol saved by the count pass (-1: did not fit, retrace)
   unsigned short *lcell;   // [nray][LK] their (jj,kk) cell ids, ascending
   float *lval;             // [nray][LK] (x3 in joint mode) their fdm (, fdmc, fdms) values
-  float *fdm_scratch;      // [nwg*4][(nvx+2)*(nvz+2)] (x3 in joint mode): one Frechet grid slot per 16-lane group
+  float *fdm_scratch;      // [nwg*8][nvz+2][nvx+2] (x3 in joint mode): one Frechet grid slot per lane group, all zeros between rays
   int LK;
   int lcap;                // LDS cell-list capacity per ray
   const unsigned *perm;    // [nray] order in which the rays are dealt to the lane groups: by field, then by source-receiver
@@ -295,13 +297,20 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
   g.gox = A.g.gox; g.goz = A.g.goz; g.dnx = A.g.dnx; g.dnz = A.g.dnz; g.dvx = A.g.dvx; g.dvz = A.g.dvz;
   const int lane = threadIdx.x, grp = lane / GP, gl = lane & (GP - 1);
   const int lm = gl & 3, l0 = gl >> 2;  // this lane's cells of the 4x4 scatter: (m, l) = (lm, l0 + q*LSTEP), q < LPR
-  const int nnx = g.nnx, nnz = g.nnz, nvx = g.nvx, nvz = g.nvz, ldf = nvz + 2, nf = ldf * (nvx + 2);
+  const int nnx = g.nnx, nnz = g.nnz, nvx = g.nvx, nvz = g.nvz;
+  const int ldf = nvx + 2, nf = ldf * (nvz + 2);   // the slot: cell (jj, kk) at jj * ldf + kk, 0 <= jj <= nvz + 1, 0 <= kk <= nvx + 1
   constexpr int NG = AZIM ? 3 : 1;
   const unsigned nvx_magic = A.nvx_magic;   // (cell ids are decoded in the innermost loops of the row assembly: two instructions instead of the ~20 of an integer division)
   const int LC = A.lcap;   // list capacity (<= 1024 so that 12 wavefronts fit a CU); longer lists fall back to a full-grid sweep
   unsigned short *s_list = s_lists + (size_t)grp * LC;
   float *gfdm = A.fdm_scratch + ((size_t)blockIdx.x * RPW + grp) * nf * NG;
   float *gfdmc = gfdm + nf, *gfdms = gfdm + 2 * nf;
+  // The slot is ALL ZEROS whenever its group takes a ray (the host clears the scratch once per call; every ray clears what it wrote).
+  // s_rng: the B-spline blocks (cbx, cbz) the ray being traced has been in -- min cbx, min cbz, max cbx, max cbz --, kept in LDS so
+  // that the stepping loop holds no register for it; the ray's non-zero cells lie in kk = min cbx .. max cbx + 3, jj likewise.
+  __shared__ int s_rngs[RPW][4];
+  int *s_rng = s_rngs[grp];
+  constexpr int RC = 8;   // cells per lane of the row assembly's register form (see `usual` below)
   const float gox = g.gox, goz = g.goz, dnx = g.dnx, dnz = g.dnz, dvx = g.dvx, dvz = g.dvz;
   const double rdnx = A.r_dnx, rdnz = A.r_dnz, rdnxr = A.r_dnxr, rdnzr = A.r_dnzr, rdvx = A.r_dvx, rdvz = A.r_dvz;
   const unsigned gmask_shift = grp * GP;
@@ -378,8 +387,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
     const int *nstsr = A.nstsr + (size_t)f * RM * RM;
     const dazim_refbox bx = A.boxes[f];
     const int saved = EMIT ? A.nlist[ray] : -1;   // EMIT: reuse the count pass's Frechet cells when they fit
-    if (saved < 0)
-      for (int i = gl; i < nf * NG; i += GP) gfdm[i] = 0.0f;
+    if (saved < 0 && gl < 4) s_rng[gl] = gl < 2 ? 0x7fffffff : -1;   // traced here: no block yet
     cbar();
     int status = 0, rb = 0;
     // ---------------- srtimes, inv/CalSurfG.f90:1644-1711 ----------------
@@ -458,7 +466,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
         if (cbx > -100) {
 #pragma unroll
           for (int q = 0; q < LPR; q++) {
-            const int fi = (cbx + lm) * ldf + (cbz + l0 + q * LSTEP);
+            const int fi = (cbz + l0 + q * LSTEP) * ldf + (cbx + lm);
             gfdm[fi] = acc[q];
             if (AZIM) { gfdmc[fi] = accc[q]; gfdms[fi] = accs[q]; }
           }
@@ -657,9 +665,14 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
             cbar();
             cbx = nbx;
             cbz = nbz;
+            // (LDS atomics without a result: no register, and the lanes of a group all bring the same values)
+            __hip_atomic_fetch_min(s_rng + 0, nbx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_min(s_rng + 1, nbz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_max(s_rng + 2, nbx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_max(s_rng + 3, nbz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
             for (int q = 0; q < LPR; q++) {
-              const int fi = (cbx + lm) * ldf + (cbz + l0 + q * LSTEP);
+              const int fi = (cbz + l0 + q * LSTEP) * ldf + (cbx + lm);
               acc[q] = gfdm[fi];
               if (AZIM) { accc[q] = gfdmc[fi]; accs[q] = gfdms[fi]; }
             }
@@ -698,33 +711,39 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
     }
     // ---------------- G row, inv/CalSurfG.f90:1339-1364 ----------------
     // cells with |fdm| >= ftol in (jj,kk) order -> this group's LDS list
+    // The usual ray (its cell list fits RC cells per lane, the combined kernels are there, no dense twin) takes the register form of
+    // the row assembly below; a saved list of that kind is read where it lies (A.lval) and the slot is not touched.
+    auto usual = [&](int n) { return n <= LC && n <= RC * GP && (MAP || A.skern != nullptr) && !A.dense; };
     int nlist = 0;
     if (saved >= 0) {
       nlist = saved;
       const size_t o = (size_t)ray * A.LK, ov = o * NG;
+      const bool viaslot = !usual(saved);   // (the general loop reads the slot: cleared again at the end of the ray)
       for (int i = gl; i < nlist; i += GP) {
         const int c = A.lcell[o + i];
-        const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
         s_list[i] = (unsigned short)c;
-        gfdm[kk * ldf + jj] = A.lval[ov + i];
-        if (AZIM) {
-          gfdmc[kk * ldf + jj] = A.lval[ov + A.LK + i];
-          gfdms[kk * ldf + jj] = A.lval[ov + 2 * A.LK + i];
+        if (viaslot) {
+          const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
+          gfdm[jj * ldf + kk] = A.lval[ov + i];
+          if (AZIM) {
+            gfdmc[jj * ldf + kk] = A.lval[ov + A.LK + i];
+            gfdms[jj * ldf + kk] = A.lval[ov + 2 * A.LK + i];
+          }
         }
       }
     } else if (!status) {
-      for (int base = 0; base < nvz * nvx; base += GP) {
-        const int c = base + gl;
-        bool keep = false;
-        if (c < nvz * nvx) {
-          const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
-          keep = fabsf(gfdm[kk * ldf + jj]) >= FTOL;
+      // the rows and columns of the blocks the ray has been in, in ascending cell order (everything else is zero, below FTOL);
+      // no block at all: an empty range
+      const int kk0 = max(s_rng[0], 1), kk1 = min(s_rng[2] + 3, nvx), jj0 = max(s_rng[1], 1), jj1 = min(s_rng[3] + 3, nvz);
+      for (int jj = jj0; jj <= jj1; jj++)
+        for (int kb = kk0; kb <= kk1; kb += GP) {
+          const int kk = kb + gl;
+          const bool keep = kk <= kk1 && fabsf(gfdm[jj * ldf + kk]) >= FTOL;
+          const unsigned m = (unsigned)((__ballot(keep) >> gmask_shift) & GMASK);
+          const int pos = nlist + __popc(m & ((1u << gl) - 1u));
+          if (keep && pos < LC) s_list[pos] = (unsigned short)((jj - 1) * nvx + kk - 1);
+          nlist += __popc(m);
         }
-        const unsigned m = (unsigned)((__ballot(keep) >> gmask_shift) & GMASK);
-        const int pos = nlist + __popc(m & ((1u << gl) - 1u));
-        if (keep && pos < LC) s_list[pos] = (unsigned short)c;
-        nlist += __popc(m);
-      }
     }
     cbar();
     if (!EMIT) {   // hand the Frechet cells to the emit pass so that it need not trace the ray again
@@ -734,10 +753,10 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
           const int c = s_list[i];
           const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
           A.lcell[o + i] = (unsigned short)c;
-          A.lval[ov + i] = gfdm[kk * ldf + jj];
+          A.lval[ov + i] = gfdm[jj * ldf + kk];
           if (AZIM) {
-            A.lval[ov + A.LK + i] = gfdmc[kk * ldf + jj];
-            A.lval[ov + 2 * A.LK + i] = gfdms[kk * ldf + jj];
+            A.lval[ov + A.LK + i] = gfdmc[jj * ldf + kk];
+            A.lval[ov + 2 * A.LK + i] = gfdms[jj * ldf + kk];
           }
         }
       if (gl == 0) A.nlist[ray] = (status || nlist <= A.LK) ? (status ? 0 : nlist) : -1;
@@ -765,7 +784,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
           bool k2 = false;
           if (c < nvz * nvx) {
             const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
-            k2 = fabsf(gfdm[kk * ldf + jj]) >= FTOL;
+            k2 = fabsf(gfdm[jj * ldf + kk]) >= FTOL;
           }
           const unsigned m2 = (unsigned)((__ballot(k2) >> gmask_shift) & GMASK);
           if (m2) clast = base + (31 - __clz(m2));
@@ -776,8 +795,8 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
     // The usual ray (its cell list fits RC cells per lane, the combined kernels are there, no dense twin): every cell's indices and
     // Frechet values are decoded and loaded ONCE into registers and the layers loop over them, where the general loop below decodes
     // the cell id and reloads its Frechet value for each of the nz - 1 layers.  Same entries in the same order.
-    constexpr int RC = 8;   // (128 cells in the emit pass, where a ray of the S-256 batch has ~100; 64 in the count pass: sixteen per lane there cost the tracing loop registers, 38.1 -> 40.1 ms)
-    const bool rowcache = !lovf && ntot <= RC * GP && (MAP || A.skern != nullptr) && !A.dense;
+    // (RC = 8: 128 cells in the emit pass, where a ray of the S-256 batch has ~100; 64 in the count pass: sixteen per lane there cost the tracing loop registers, 38.1 -> 40.1 ms)
+    const bool rowcache = usual(nlist);
     if (rowcache) {
       int sidx[RC], cbase[RC], fidx[RC];
 #pragma unroll
@@ -787,13 +806,14 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
         const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
         sidx[i] = jj * (nvx + 2) + kk;
         cbase[i] = (jj - 1) * nvx + kk;
-        fidx[i] = kk * ldf + jj;
+        fidx[i] = jj * ldf + kk;
       }
       for (int blk = 0; blk < NG; blk++) {
         float fdv[RC];
         const float *fsrc = blk == 0 ? gfdm : (blk == 1 ? gfdmc : gfdms);
+        const float *lsrc = A.lval + ((size_t)ray * NG + blk) * A.LK;   // a saved list: the same bits, contiguous
 #pragma unroll
-        for (int i = 0; i < RC; i++) fdv[i] = (i * GP + gl < ntot) ? fsrc[fidx[i]] : 0.0f;
+        for (int i = 0; i < RC; i++) fdv[i] = (i * GP + gl < ntot) ? (saved >= 0 ? lsrc[i * GP + gl] : fsrc[fidx[i]]) : 0.0f;
         for (int k = 1; k <= nlay; k++) {
           const size_t sk = ((size_t)(k - 1) * A.kmax + kslot) * ncol;
           const int nk = blk * bstride + poff + (k - 1) * nvz * nvx;
@@ -831,15 +851,15 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
           int c = 0;
           if (cell) c = lovf ? li : s_list[li];
           const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
-          if (cell && lovf) cell = fabsf(gfdm[kk * ldf + jj]) >= FTOL;
+          if (cell && lovf) cell = fabsf(gfdm[jj * ldf + kk]) >= FTOL;
           if (cell && MAP) {
-            rowv = (blk == 0 ? gfdm : (blk == 1 ? gfdmc : gfdms))[kk * ldf + jj];
+            rowv = (blk == 0 ? gfdm : (blk == 1 ? gfdmc : gfdms))[jj * ldf + kk];
             keep = A.keep_small ? (rowv != 0.0f) : (fabsf(rowv) > FTOL);
             nn = blk * bstride + poff + (jj - 1) * nvx + kk;
           } else if (cell) {
             const size_t si = ((size_t)(k - 1) * A.kmax + kslot) * ncol + (size_t)jj * (nvx + 2) + kk;
             if (blk == 0) {
-              const float fd = gfdm[kk * ldf + jj];
+              const float fd = gfdm[jj * ldf + kk];
               double r;
               if (A.skern) {
                 r = A.skern[si] * (double)fd;           // (the cell's factor from k_row_kernels: same operations, same order)
@@ -863,7 +883,7 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
                 if (EMIT && A.dense == 1) rowv = (float)rd;
               }
             } else {
-              rowv = A.lsen[si] * (blk == 1 ? gfdmc : gfdms)[kk * ldf + jj];
+              rowv = A.lsen[si] * (blk == 1 ? gfdmc : gfdms)[jj * ldf + kk];
               keepd = rowv != 0.0f;
             }
             keep = A.keep_small ? (rowv != 0.0f) : (fabsf(rowv) > FTOL);
@@ -880,6 +900,25 @@ __global__ __launch_bounds__(64, AZIM ? 2 : RAYS_MINW) void rays_kernel(RayArgs 
           cnt += __popc(m);
         }
       }
+    // zeros back into what this ray wrote, so that the slot's next ray finds it clean: the rectangle of its blocks (border rows and
+    // columns included; empty for a ray with a status, which traced nothing), or the cells of a saved list that went through the slot
+    cbar();
+    if (saved < 0) {
+      const int x0 = max(s_rng[0], 0), x1 = min(s_rng[2] + 3, nvx + 1), z0 = max(s_rng[1], 0), z1 = min(s_rng[3] + 3, nvz + 1);
+      for (int z = z0; z <= z1; z++)
+        for (int x = x0 + gl; x <= x1; x += GP) {
+          gfdm[z * ldf + x] = 0.0f;
+          if (AZIM) { gfdmc[z * ldf + x] = 0.0f; gfdms[z * ldf + x] = 0.0f; }
+        }
+    } else if (!rowcache) {
+      for (int i = gl; i < nlist; i += GP) {
+        const int c = s_list[i];
+        const int jj = (int)__umulhi((unsigned)c, nvx_magic) + 1, kk = c - (jj - 1) * nvx + 1;
+        gfdm[jj * ldf + kk] = 0.0f;
+        if (AZIM) { gfdmc[jj * ldf + kk] = 0.0f; gfdms[jj * ldf + kk] = 0.0f; }
+      }
+    }
+    cbar();
     if (!EMIT && gl == 0) {
       A.count[ray] = cnt;
       if (A.dense == 2) A.countd[ray] = cntd;
@@ -1135,9 +1174,18 @@ struct RayBuild {
     if (dz_opt(ctx, "rays.wg_per_cu", 0) > 0 && dz_opt(ctx, "rays.wg_per_cu", 0) < per_cu) per_cu = dz_opt(ctx, "rays.wg_per_cu", 0);
     nwg = (long)ctx->num_cu * per_cu;
     if (nwg > (nray + RPW_MAX - 1) / RPW_MAX) nwg = (nray + RPW_MAX - 1) / RPW_MAX;
+    if (dz_opt(ctx, "rays.nwg", 0) > 0 && dz_opt(ctx, "rays.nwg", 0) < nwg) nwg = dz_opt(ctx, "rays.nwg", 0);   // test knob: few slots serve many rays
     if (nwg >= 8) nwg -= nwg % 8;   // the XCD-aware ray order wants a multiple of 8
     if (nwg < 1) nwg = 1;
-    return dz_scratch(ctx, "rays.fdm", (size_t)nwg * RPW_MAX * (g.nvx + 2) * (g.nvz + 2) * (joint ? 3 : 1), &A.fdm_scratch);
+    // The Frechet slots must be all zeros when the first pass starts; every ray leaves its slot as it found it (rays_kernel).  The
+    // block is cached by name across calls, grids and forms (a slot of this call may straddle slots of the last one, and a new block
+    // holds anything), so it is cleared here, once per call, on the stream the passes run on.
+    const size_t nslot = (size_t)nwg * RPW_MAX * (g.nvx + 2) * (g.nvz + 2) * (joint ? 3 : 1);
+    int rc;
+    if ((rc = dz_scratch(ctx, "rays.fdm", nslot, &A.fdm_scratch))) return rc;
+    DZ_HIP(hipMemsetAsync(A.fdm_scratch, 0, nslot * sizeof(float), ctx->stream));
+    ctx->ksec["rays.nwg"] = (double)nwg;
+    return 0;
   }
   int sort_rays() {   // ... and the task counters of the passes
     int rc;
