@@ -400,10 +400,12 @@ class Context:
                                               _ptr(x, np.float32), C.byref(ne), _ptr(st)))
         return x, ne.value, st
 
-    def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0):
+    def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
+                  ntemp=1, tmax=1.0, nswap=1):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
         cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
-        data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal)."""
+        data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal).  ntemp > 1: parallel
+        tempering with ntemp rungs up to temperature tmax and a swap round every nswap steps (MonteCarlo.set_tempering)."""
         nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
         vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
         vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
@@ -416,6 +418,8 @@ class Context:
         mc = MonteCarlo(self, h, nx, ny, nz, kmax, nchain, nbin, ne.value)
         if proposal != 0:
             mc.set_proposal(proposal)
+        if ntemp != 1:
+            mc.set_tempering(ntemp, tmax, nswap)
         return mc
 
     def ray_paths(self):
@@ -563,6 +567,30 @@ class MonteCarlo:
         self.ctx._check(self.ctx.lib.dazim_mc_cov_state(self.ctx._h, self._h, None, _ptr(cov_n), _ptr(s1), _ptr(s2), _ptr(chol),
                                                         _ptr(cov_set)))
         return dict(kind=1, cov_n=cov_n, cov_s1=s1, cov_s2=s2, chol=chol, cov_set=cov_set)
+
+    def set_tempering(self, ntemp, tmax, nswap=1):
+        """parallel tempering (dazim_mc_set_tempering): chain ch is rung ch % ntemp of replica group ch // ntemp, rung r samples
+        the posterior to the power beta_r = tmax ** (-r / (ntemp - 1)), neighbouring rungs swap states every nswap steps and only the
+        nchain / ntemp rung-0 chains are recorded; ntemp 1 is the default, no tempering.  Refused once a step has been done"""
+        self.ctx._check(self.ctx.lib.dazim_mc_set_tempering(self.ctx._h, self._h, int(ntemp), float(tmax), int(nswap)))
+
+    def temper_state(self):
+        """the ladder and, for ntemp > 1, copies of its state (dazim_mc_temper_state): dict ntemp, tmax, nswap, beta[ntemp],
+        scale[sampled cells][ntemp], swap_try, swap_acc[sampled cells][ntemp - 1]; for ntemp 1 dict ntemp, tmax, nswap alone"""
+        nt, tmax, nswap = C.c_int(0), C.c_float(0), C.c_int(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_temper_state(self.ctx._h, self._h, C.byref(nt), C.byref(tmax), C.byref(nswap), None, None,
+                                                           None, None))
+        out = dict(ntemp=nt.value, tmax=tmax.value, nswap=nswap.value)
+        if nt.value == 1:
+            return out
+        beta = np.zeros(nt.value, np.float64)
+        scale = np.zeros((self.ncs, nt.value), np.float32)
+        swap_try = np.zeros((self.ncs, nt.value - 1), np.int64)
+        swap_acc = np.zeros((self.ncs, nt.value - 1), np.int64)
+        self.ctx._check(self.ctx.lib.dazim_mc_temper_state(self.ctx._h, self._h, None, None, None, _ptr(beta), _ptr(scale),
+                                                           _ptr(swap_try), _ptr(swap_acc)))
+        out.update(beta=beta, scale=scale, swap_try=swap_try, swap_acc=swap_acc)
+        return out
 
     def step(self, pv, record):
         """one step on pv[kmax][ncol] (fp64; numpy or torch-cuda), the curves of proposals(); record 0 = burn-in"""

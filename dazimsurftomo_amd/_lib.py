@@ -91,5 +91,9 @@ def load():
     lib.dazim_last_error.restype = C.c_char_p
     lib.dazim_last_kernel_seconds.restype = C.c_double
     lib.dazim_stream.restype = C.c_void_p
+    lib.dazim_mc_set_tempering.restype = C.c_int
+    lib.dazim_mc_set_tempering.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int]
+    lib.dazim_mc_temper_state.restype = C.c_int
+    lib.dazim_mc_temper_state.argtypes = [C.c_void_p] * 9
     _lib = lib
     return lib

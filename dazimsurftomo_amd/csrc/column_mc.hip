@@ -7,8 +7,13 @@
 // the posterior statistics.  Random numbers are Philox4x32-10 keyed on the seed and counted by (step, chain, block): the results
 // depend on the seed and the inputs only.  Sums across chains run over the lanes in chain order inside one lane (k_mc_final); the
 // histogram counts are the only atomics, on integers.
+//
+// Parallel tempering (dazim_mc_set_tempering): chain ch is rung ch % ntemp of replica group ch / ntemp, rung r samples the posterior
+// to the power beta_r, and neighbouring rungs of a group exchange their states.  A group's rungs are neighbouring lanes of the cell's
+// wavefront, so a swap is a lane shuffle inside k_mc_step<KIND, 1>; only the rung-0 chains are recorded.
 #include "dazim_internal.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 
@@ -78,7 +83,20 @@ struct McDev {
   double *cov_s1, *cov_s2;     // [ncs][nlay], [ncs][npair]: sums of u and of u_a u_c, u the state in box units
   double *chol;                // [ncs][npair]: the lower factor of the last covariance that factored
   int *cov_set;                // [ncs]: 1 once chol holds a factor
+  // tempering only (ntemp = 1 and null otherwise); while it is on, scale [ncs] follows rung 0 of tscale
+  int ntemp, nswap;
+  const double *beta;          // [ntemp]
+  float *tscale;               // [ncs][ntemp]
+  int *tacc_win;               // [ncs][ntemp]
+  long long *swap_try, *swap_acc;   // [ncs][ntemp - 1]
 };
+
+// the lanes of rung r: chains r, r + ntemp, ..
+__device__ __forceinline__ unsigned long long mc_rung_mask(int nchain, int ntemp, int r) {
+  unsigned long long m = 0ull;
+  for (int j = r; j < nchain; j += ntemp) m |= 1ull << j;
+  return m;
+}
 
 // the next proposal of chain (cs, ch) from its current state: v' = v + s (vmax - vmin) z in fp64, reflected into the box, fp32
 __device__ void mc_propose(const McDev &M, int cs, int ch, long long step, float s) {
@@ -109,8 +127,9 @@ __device__ __forceinline__ int mc_pair_row(int e) {   // the row a of packed pai
 }
 
 // kind 1, a burn-in step with a decision: the cell's states us [nlay][nchain] (LDS) join the sums, pair e on lane e mod 64, the
-// chains in chain order inside the lane; the lane of the diagonal pair (a, a) keeps s1[a] too
-__device__ void mc_cov_accumulate(const McDev &M, int cs, int ch, const float *us) {
+// chains in chain order inside the lane; the lane of the diagonal pair (a, a) keeps s1[a] too.  Tempered handles pass stride =
+// ntemp: the rung-0 chains alone
+__device__ void mc_cov_accumulate(const McDev &M, int cs, int ch, const float *us, int stride) {
   const int n = M.nlay, npair = n * (n + 1) / 2, nc = M.nchain, cell = M.cell_of[cs];
   double *s1 = M.cov_s1 + (long)cs * n, *s2 = M.cov_s2 + (long)cs * npair;
   for (int e = ch; e < npair; e += MC_WAVE) {
@@ -118,7 +137,7 @@ __device__ void mc_cov_accumulate(const McDev &M, int cs, int ch, const float *u
     const double loa = (double)M.vmin[(long)a * M.ncell + cell], wa = (double)M.vmax[(long)a * M.ncell + cell] - loa;
     const double loc = (double)M.vmin[(long)c * M.ncell + cell], wc = (double)M.vmax[(long)c * M.ncell + cell] - loc;
     double t1 = a == c ? s1[a] : 0.0, t2 = s2[e];
-    for (int j = 0; j < nc; j++) {
+    for (int j = 0; j < nc; j += stride) {
       const double ua = ((double)us[a * nc + j] - loa) / wa, uc = ((double)us[c * nc + j] - loc) / wc;
       t1 += ua;
       t2 += ua * uc;
@@ -126,7 +145,7 @@ __device__ void mc_cov_accumulate(const McDev &M, int cs, int ch, const float *u
     s2[e] = t2;
     if (a == c) s1[a] = t1;
   }
-  if (ch == 0) M.cov_n[cs] += nc;
+  if (ch == 0) M.cov_n[cs] += nc / stride;
 }
 
 // kind 1, an adaptation point with cn >= MC_COV_MIN nlay states in the sums (visible to every lane): the covariance of the window
@@ -229,17 +248,24 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
 // first: the proposals are the start models -- they become the state, no decision.  adapt: the end of an adaptation window.
 // KIND 1 (covariance proposals) adds, in dynamic LDS, L [npair] fp64 and behind it the normals zs [nlay][nchain] fp64, whose first
 // half holds the staged states [nlay][nchain] fp32 while they are accumulated: 48 384 bytes at nlay = 63, nchain = 64.
-template <int KIND>
+// TEMPER 1 (a ladder of ntemp > 1 rungs): the decision of rung r takes beta_r, the scale and its window are per rung (lane r < ntemp
+// keeps rung r's, counting its chains in the ballot), neighbouring rungs swap states by lane shuffles after the decision, and only
+// the rung-0 lanes record.  Each lane carries its chi^2 in a register from the decision through the swap.
+template <int KIND, int TEMPER>
 __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__restrict__ pv, long long step, int first, int record,
                                                      int adapt, int nadapt) {
   __shared__ float s_scale;
   __shared__ int s_win;
+  __shared__ float s_rscale[TEMPER ? MC_MAXCHAIN : 1];   // TEMPER: the scale of every rung
   const int cs = blockIdx.x, ch = threadIdx.x;
   const bool act = ch < M.nchain;
   const int cell = M.cell_of[cs];
   const long col = (long)cs * M.nchain + ch;
   const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
+  const int nt = TEMPER ? M.ntemp : 1, rung = ch % nt;
   double chi2p = 0.0;
+  double chi2s = INFINITY;   // TEMPER: the chain's chi^2 after the decision, then after the swap
+  unsigned wswap = 0u;       // TEMPER: word 1 of block(step, gid, 0), the swap uniform of a pair's lower chain
   bool acc = false;
   if (act) {
     for (int p = 0; p < M.kmax; p++) {
@@ -257,7 +283,13 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       acc = true;
     } else {
       const double chi2c = M.chi2[col];
-      if (isinf(chi2c)) {
+      if constexpr (TEMPER) {
+        unsigned w[4];
+        mc_block(w, step, gid, 0u, M.seed);
+        wswap = w[1];
+        chi2s = chi2c;
+        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * M.beta[rung] * (chi2p - chi2c);
+      } else if (isinf(chi2c)) {
         acc = !isinf(chi2p);
       } else {
         unsigned w[4];
@@ -268,11 +300,70 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
     if (acc) {
       for (int k = 0; k < M.nlay; k++) M.cur[k * M.ncol + col] = M.prop[k * M.ncol + col];
       M.chi2[col] = chi2p;
+      chi2s = chi2p;
     }
   }
-  const int nacc = first ? 0 : __popcll(__ballot(act && acc));
+  const unsigned long long bacc = first ? 0ull : __ballot(act && acc);
+  const int nacc = __popcll(bacc);
   const int nnoroot = __popcll(__ballot(act && isinf(chi2p)));
-  if (ch == 0) {
+  if constexpr (TEMPER) {
+    // a swap round: pairs (r, r + 1), r of the round's parity, in every group; the pair's lower lane decides, both lanes take the
+    // other's knots (each reads and writes its own column only) and chi^2
+    if (!first && step % M.nswap == 0) {
+      const int par = (int)((step / M.nswap) & 1);
+      const bool lower = act && rung + 1 < nt && (rung & 1) == par;
+      const bool upper = act && rung > 0 && ((rung - 1) & 1) == par;
+      const double cup = __shfl_down(chi2s, 1), cdn = __shfl_up(chi2s, 1);
+      int sw = 0;
+      if (lower) {
+        if (isinf(chi2s)) sw = !isinf(cup);
+        else if (!isinf(cup)) sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) * (chi2s - cup);
+      }
+      const int swu = __shfl_up(sw, 1);
+      const bool swp = lower ? sw != 0 : (upper && swu != 0);
+      const int partner = lower ? ch + 1 : (upper ? ch - 1 : ch);
+      for (int k = 0; k < M.nlay; k++) {
+        const float v = act ? M.cur[k * M.ncol + col] : 0.0f;
+        const float vp = __shfl(v, partner);
+        if (swp) M.cur[k * M.ncol + col] = vp;
+      }
+      if (swp) {
+        chi2s = lower ? cup : cdn;
+        M.chi2[col] = chi2s;
+      }
+      const unsigned long long btry = __ballot(lower), bswp = __ballot(lower && sw != 0);
+      if (ch < nt - 1) {
+        const unsigned long long mask = mc_rung_mask(M.nchain, nt, ch);
+        M.swap_try[(long)cs * (nt - 1) + ch] += __popcll(btry & mask);
+        M.swap_acc[(long)cs * (nt - 1) + ch] += __popcll(bswp & mask);
+      }
+    }
+    if (ch == 0 && nnoroot) atomicAdd(&M.counters[0], (unsigned long long)nnoroot);
+    if (ch < nt) {   // lane r keeps rung r's scale and window
+      const int nar = __popcll(bacc & mc_rung_mask(M.nchain, nt, ch));
+      const long o = (long)cs * nt + ch;
+      float s = M.tscale[o];
+      if (!record) {
+        int win = M.tacc_win[o] + nar;
+        if (adapt) {
+          const double rate = (double)win / ((double)nadapt * (double)(M.nchain / nt));
+          if (rate > 0.40) s = s * 1.25f;
+          else if (rate < 0.20) s = s / 1.25f;
+          float smax = MC_SMAX;
+          if constexpr (KIND == 1)
+            if (M.cov_set[cs]) smax = 2.0f / sqrtf((float)M.nlay);
+          s = fminf(fmaxf(s, MC_SMIN), smax);
+          M.tscale[o] = s;
+          if (ch == 0) M.scale[cs] = s;
+          win = 0;
+        }
+        M.tacc_win[o] = win;
+      } else if (ch == 0 && nar) {
+        atomicAdd(&M.counters[1], (unsigned long long)nar);
+      }
+      s_rscale[ch] = s;
+    }
+  } else if (ch == 0) {
     if (nnoroot) atomicAdd(&M.counters[0], (unsigned long long)nnoroot);
     float s = M.scale[cs];
     if (!record) {
@@ -295,7 +386,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
     s_scale = s;
   }
   if (record) {
-    if (act) {
+    if (act && rung == 0) {
       if (!first && acc) M.accepted[col] += 1;
       for (int k = 0; k < M.nlay; k++) {
         const double v = (double)M.cur[k * M.ncol + col];
@@ -337,7 +428,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       if (act)
         for (int k = 0; k < M.nlay; k++) us[k * M.nchain + ch] = M.cur[k * M.ncol + col];
       __syncthreads();
-      mc_cov_accumulate(M, cs, ch, us);
+      mc_cov_accumulate(M, cs, ch, us, nt);
       if (adapt) {
         __syncthreads();
         const long long cn = M.cov_n[cs];
@@ -346,6 +437,12 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
           have = true;
           if (!set) {   // the first factor: the scale restarts for the new metric
             set = 1;
+            if constexpr (TEMPER) {
+              if (ch < nt) {
+                s_rscale[ch] = 1.0f / sqrtf((float)M.nlay);
+                M.tscale[(long)cs * nt + ch] = s_rscale[ch];
+              }
+            }
             if (ch == 0) {
               M.cov_set[cs] = 1;
               s_scale = 1.0f / sqrtf((float)M.nlay);
@@ -356,21 +453,23 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       }
     }
     __syncthreads();
+    const float s = TEMPER ? s_rscale[rung] : s_scale;
     if (set) {
       if (!have)
         for (int e = ch; e < npair; e += MC_WAVE) L[e] = M.chol[(long)cs * npair + e];
       __syncthreads();
-      if (act) mc_propose_cov(M, cs, ch, step, s_scale, L, zs);
+      if (act) mc_propose_cov(M, cs, ch, step, s, L, zs);
     } else if (act) {
-      mc_propose(M, cs, ch, step, s_scale);
+      mc_propose(M, cs, ch, step, s);
     }
   } else {
     __syncthreads();
-    if (act) mc_propose(M, cs, ch, step, s_scale);
+    if (act) mc_propose(M, cs, ch, step, TEMPER ? s_rscale[rung] : s_scale);
   }
 }
 
-// posterior statistics, one wavefront per inner cell, lane = knot.  nrec: recorded steps; ndec: recorded steps with a decision
+// posterior statistics, one wavefront per inner cell, lane = knot.  nrec: recorded steps; ndec: recorded steps with a decision.
+// The recorded chains are ch = 0, ntemp, 2 ntemp, .. (every chain without tempering), M of them
 __global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, long long ndec, float *__restrict__ mean,
                                                       float *__restrict__ stdv, float *__restrict__ q, float *__restrict__ best,
                                                       float *__restrict__ rhat, float *__restrict__ accept, float *__restrict__ chi2_best) {
@@ -393,9 +492,9 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, l
     return;
   }
   if (k < M.nlay) {
-    const double N = (double)nrec, Mc = (double)M.nchain;
+    const double N = (double)nrec, Mc = (double)(M.nchain / M.ntemp);
     double s1 = 0.0, s2 = 0.0, sm = 0.0;
-    for (int ch = 0; ch < M.nchain; ch++) {
+    for (int ch = 0; ch < M.nchain; ch += M.ntemp) {
       const long col = (long)cs * M.nchain + ch;
       const double a = M.sums[(long)k * M.ncol + col], b = M.sums[((long)M.nlay + k) * M.ncol + col];
       s1 += a;
@@ -408,7 +507,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, l
     // R-hat (BDA3, chains not split): W the mean within-chain variance, B / N the variance of the chain means
     double W = 0.0, B = 0.0;
     const double mbar = sm / Mc;
-    for (int ch = 0; ch < M.nchain; ch++) {
+    for (int ch = 0; ch < M.nchain; ch += M.ntemp) {
       const long col = (long)cs * M.nchain + ch;
       const double a = M.sums[(long)k * M.ncol + col], b = M.sums[((long)M.nlay + k) * M.ncol + col];
       const double mj = a / N;
@@ -417,7 +516,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, l
     }
     W /= Mc;
     B *= N / (Mc - 1.0);
-    rhat[o] = (M.nchain > 1 && nrec > 1 && W > 0.0) ? (float)sqrt(((N - 1.0) / N * W + B / N) / W) : NAN;
+    rhat[o] = (M.nchain / M.ntemp > 1 && nrec > 1 && W > 0.0) ? (float)sqrt(((N - 1.0) / N * W + B / N) / W) : NAN;
     // 2.5 / 50 / 97.5 % from the counts, linear inside a bin
     const unsigned *h = M.hist + ((long)cs * M.nlay + k) * M.nbin;
     const double lo = (double)M.vmin[o], hi = (double)M.vmax[o], tot = N * Mc;
@@ -439,8 +538,8 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, l
   }
   if (k == 0) {
     long long a = 0;
-    for (int ch = 0; ch < M.nchain; ch++) a += M.accepted[(long)cs * M.nchain + ch];
-    accept[cell] = ndec > 0 ? (float)((double)a / ((double)ndec * (double)M.nchain)) : 0.0f;
+    for (int ch = 0; ch < M.nchain; ch += M.ntemp) a += M.accepted[(long)cs * M.nchain + ch];
+    accept[cell] = ndec > 0 ? (float)((double)a / ((double)ndec * (double)(M.nchain / M.ntemp))) : 0.0f;
     chi2_best[cell] = (float)M.best_chi2[cs];
   }
 }
@@ -466,6 +565,9 @@ struct dazim_mc {
   McDev d{};
   int nadapt = 1;
   int kind = 0;             // the proposal: 0 isotropic in box units, 1 shaped by the chains' covariance
+  float step0 = 0.0f;       // the initial step scale
+  float tmax = 1.0f;        // tempering: the top rung's temperature (the ladder itself is in d)
+  std::vector<double> beta{1.0};
   int64_t nstep = 0;        // steps done; 0 = the start models are drawn, not evaluated
   int64_t nburn_dec = 0;    // burn-in steps with a decision (the adaptation clock)
   int64_t nrec = 0, nrec_dec = 0;
@@ -506,14 +608,12 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
   const long long step = mc->nstep + 1;
   if (mc->d.ncs > 0) {
     DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
-    if (mc->kind == 1) {
-      const size_t lds = ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double);
-      hipLaunchKernelGGL(k_mc_step<1>, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record,
-                         (int)adapt, mc->nadapt);
-    } else {
-      hipLaunchKernelGGL(k_mc_step<0>, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), 0, ctx->stream, mc->d, pv, step, (int)first, record,
-                         (int)adapt, mc->nadapt);
-    }
+    const size_t lds =
+        mc->kind == 1 ? ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double) : 0;
+    auto kern = mc->kind == 1 ? (mc->d.ntemp > 1 ? k_mc_step<1, 1> : k_mc_step<1, 0>)
+                              : (mc->d.ntemp > 1 ? k_mc_step<0, 1> : k_mc_step<0, 0>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record, (int)adapt,
+                       mc->nadapt);
     DZ_HIP(hipGetLastError());
     DZ_HIP(hipEventRecord(mc->e1, ctx->stream));
   }
@@ -580,6 +680,7 @@ int dazim_mc_create(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, int nchain
   dazim_mc *mc = new dazim_mc();
   mc->ctx = ctx;
   mc->nadapt = nadapt;
+  mc->step0 = step;
   mc->n_empty = ncell - (int)cell_of.size();
   McDev &M = mc->d;
   M.nx = nx;
@@ -593,6 +694,8 @@ int dazim_mc_create(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, int nchain
   M.ncs = (int)cell_of.size();
   M.ncol = (long)M.ncs * nchain;
   M.seed = seed;
+  M.ntemp = 1;
+  M.nswap = 1;
   int *ci, *co;
   float *v0, *lo, *hi, *co_, *wd;
   auto fail = [&](int r) { mc_release(mc); return r; };
@@ -698,6 +801,70 @@ int dazim_mc_cov_state(dazim_ctx *ctx, dazim_mc *mc, int *kind, int64_t *cov_n, 
   return 0;
 }
 
+int dazim_mc_set_tempering(dazim_ctx *ctx, dazim_mc *mc, int ntemp, float tmax, int nswap) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_set_tempering"))) return rc;
+  McDev &M = mc->d;
+  if (ntemp < 1 || ntemp > M.nchain || M.nchain % ntemp != 0)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_tempering: ntemp %d does not divide the %d chains", ntemp, M.nchain);
+  if (ntemp > 1 && !(std::isfinite(tmax) && tmax > 1.0f))
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_tempering: tmax %g is not a finite temperature above 1", tmax);
+  if (nswap < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_tempering: nswap %d < 1", nswap);
+  if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_tempering: the handle has done %lld steps", (long long)mc->nstep);
+  DZ_HIP(hipSetDevice(ctx->device));
+  std::vector<double> beta((size_t)ntemp, 1.0);
+  for (int r = 1; r < ntemp; r++) beta[r] = std::pow((double)tmax, -(double)r / (double)(ntemp - 1));
+  if (ntemp > 1) {
+    // sized for any ladder of the handle, so that a second call allocates nothing
+    const size_t nr = (size_t)M.ncs * M.nchain;
+    if (!M.tscale) {
+      double *b;
+      if ((rc = mc_alloc(mc, (size_t)M.nchain, &b)) || (rc = mc_alloc(mc, nr, &M.tscale)) || (rc = mc_alloc(mc, nr, &M.tacc_win)) ||
+          (rc = mc_alloc(mc, nr, &M.swap_try)) || (rc = mc_alloc(mc, nr, &M.swap_acc)))
+        return rc;
+      M.beta = b;
+    }
+    const std::vector<float> s0(nr, mc->step0);
+    DZ_HIP(hipMemcpyAsync((void *)M.beta, beta.data(), beta.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    DZ_HIP(hipMemcpyAsync(M.tscale, s0.data(), nr * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    DZ_HIP(hipMemsetAsync(M.tacc_win, 0, nr * sizeof(int), ctx->stream));
+    DZ_HIP(hipMemsetAsync(M.swap_try, 0, nr * sizeof(long long), ctx->stream));
+    DZ_HIP(hipMemsetAsync(M.swap_acc, 0, nr * sizeof(long long), ctx->stream));
+    DZ_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  M.ntemp = ntemp;
+  M.nswap = nswap;
+  mc->tmax = tmax;
+  mc->beta = beta;
+  return 0;
+}
+
+int dazim_mc_temper_state(dazim_ctx *ctx, dazim_mc *mc, int *ntemp, float *tmax, int *nswap, double *beta, float *scale,
+                          int64_t *swap_try, int64_t *swap_acc) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_temper_state"))) return rc;
+  const McDev &M = mc->d;
+  if (ntemp) *ntemp = M.ntemp;
+  if (tmax) *tmax = mc->tmax;
+  if (nswap) *nswap = M.nswap;
+  if (M.ntemp == 1) {
+    if (beta || scale || swap_try || swap_acc)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_temper_state: the handle is not tempered and keeps no ladder");
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
+  };
+  const size_t np = (size_t)M.ncs * (M.ntemp - 1);
+  DZ_HIP(get(beta, M.beta, (size_t)M.ntemp * 8));
+  DZ_HIP(get(scale, M.tscale, (size_t)M.ncs * M.ntemp * 4));
+  DZ_HIP(get(swap_try, M.swap_try, np * 8));
+  DZ_HIP(get(swap_acc, M.swap_acc, np * 8));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv_u, int record) {
   int rc;
   if ((rc = mc_check(ctx, mc, "dazim_mc_step"))) return rc;
@@ -755,7 +922,7 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
   }
   DZ_HIP(hipMemcpy(c1, mc->d.counters, 16, hipMemcpyDeviceToHost));
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  const double dec = (double)(mc->nrec_dec - dec0) * (double)mc->d.ncol;
+  const double dec = (double)(mc->nrec_dec - dec0) * (double)(mc->d.ncol / mc->d.ntemp);   // the recorded (rung-0) chains'
   ctx->ksec["mc"] = wall;
   ctx->ksec["mc.disp"] = t_disp;
   ctx->ksec["mc.step"] = t_step;
@@ -768,6 +935,25 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
     DZ_HIP(hipMemcpy(set.data(), mc->d.cov_set, set.size() * sizeof(int), hipMemcpyDeviceToHost));
     for (int v : set) cov_cells += v;
   }
+  // the swap acceptance of every (cell, rung pair), over all the handle's steps
+  double swap_min = 0.0, swap_med = 0.0;
+  if (mc->d.ntemp > 1 && mc->d.ncs > 0) {
+    const size_t np = (size_t)mc->d.ncs * (mc->d.ntemp - 1);
+    std::vector<long long> tr(np), ac(np);
+    DZ_HIP(hipMemcpy(tr.data(), mc->d.swap_try, np * sizeof(long long), hipMemcpyDeviceToHost));
+    DZ_HIP(hipMemcpy(ac.data(), mc->d.swap_acc, np * sizeof(long long), hipMemcpyDeviceToHost));
+    std::vector<double> rate;
+    for (size_t e = 0; e < np; e++)
+      if (tr[e] > 0) rate.push_back((double)ac[e] / (double)tr[e]);
+    if (!rate.empty()) {
+      std::sort(rate.begin(), rate.end());
+      swap_min = rate.front();
+      swap_med = 0.5 * (rate[(rate.size() - 1) / 2] + rate[rate.size() / 2]);
+    }
+  }
+  ctx->ksec["mc.ntemp"] = mc->d.ntemp;
+  ctx->ksec["mc.swap_min"] = swap_min;
+  ctx->ksec["mc.swap_med"] = swap_med;
   ctx->ksec["mc.proposal"] = mc->kind;
   ctx->ksec["mc.cov_cells"] = cov_cells;
   if (n_no_root) *n_no_root = (int64_t)(c1[0] - c0[0]);

@@ -2,7 +2,7 @@
 ! random-walk Metropolis chains on one MI355X and reports the posterior mean, spread and credible interval of every knot (DESIGN.md
 ! section 14), where SurfDepthFromMaps_amd returns one linearised model.
 !
-!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal]]]]]]
+!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax]]]]]]]]
 !
 ! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
 ! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
@@ -10,6 +10,9 @@
 ! nsample recorded steps (default 2000) after as many burn-in steps, nchain chains per cell (default 32), sigma_c 0.01 km/s, seed 1.
 ! proposal 0 (default): moves isotropic in box units; 1: moves shaped by the chains' own covariance, learnt per cell during burn-in
 ! and frozen afterwards (one more settings line and one more summary line: the cells with an adapted covariance).
+! ntemp 1 (default): no tempering.  ntemp > 1 (a divisor of nchain): parallel tempering, every ntemp chains of a cell form a ladder
+! of temperatures 1 .. tmax (default 16, geometric) whose neighbours swap states after every step; only the nchain / ntemp chains
+! at temperature 1 are recorded (more settings lines, the swap acceptance over cells and rung pairs in the summary).
 !
 ! Outputs (names of their own, so that the three programs can share a directory):
 !   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
@@ -27,7 +30,11 @@ program SurfDepthMC_amd
   character(len=100) :: inputfile, logfile
   type(para_t) :: p
   logical :: ex
-  integer :: nx, ny, nz, kmax, nsample, nchain, proposal
+  integer :: nx, ny, nz, kmax, nsample, nchain, proposal, ntemp, ncold
+  integer, parameter :: nswap = 1
+  real :: tmax
+  real(c_double), allocatable, target :: beta(:)
+  integer(c_int64_t), allocatable, target :: swap_try(:, :), swap_acc(:, :)
   integer(c_long_long) :: seed
   real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, width, sigma_c
   real*8, allocatable :: tRc(:)
@@ -47,7 +54,8 @@ program SurfDepthMC_amd
   write (*, *)
   write (*, *) '                       SurfDepthMC'
   write (*, *)
-  if (command_argument_count() < 1) error stop 'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal]]]]]]'
+  if (command_argument_count() < 1) error stop &
+    'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax]]]]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -56,18 +64,24 @@ program SurfDepthMC_amd
   Minvel = p%Minvel; Maxvel = p%Maxvel; kmax = p%kmaxRc; tRc = p%tRc
   if (nz <= 1) error stop 'error nz value.'
   if (kmax <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
-  nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1; proposal = 0
+  nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1; proposal = 0; ntemp = 1; tmax = 16
   call optional_arg(2, nsample)
   call optional_arg(3, nchain)
   call optional_arg(4, width)
   call optional_arg(5, sigma_c)
   call optional_arg(6, seed)
   call optional_arg(7, proposal)
+  call optional_arg(8, ntemp)
+  call optional_arg(9, tmax)
   if (nsample < 1) error stop 'nsample must be at least 1'
   if (nchain < 1 .or. nchain > 64) error stop 'nchain must be 1..64'
   if (width < 0) error stop 'width must not be negative'
   if (sigma_c <= 0) error stop 'sigma_c must be positive'
   if (proposal /= 0 .and. proposal /= 1) error stop 'proposal must be 0 or 1'
+  if (ntemp < 1 .or. ntemp > nchain) error stop 'ntemp must be 1..nchain and divide nchain'
+  if (mod(nchain, ntemp) /= 0) error stop 'ntemp must be 1..nchain and divide nchain'
+  if (ntemp > 1 .and. .not. (tmax > 1 .and. tmax <= huge(tmax))) error stop 'tmax must be a finite temperature above 1'
+  ncold = nchain/ntemp
   nlay = nz - 1
   ncell = (nx - 2)*(ny - 2)
   if (nlay > 63) error stop 'SurfDepthMC_amd samples at most 63 knots (nz <= 64)'
@@ -91,6 +105,8 @@ program SurfDepthMC_amd
       write (q, '(a,2f8.3)') ' prior: uniform on para.in''s Vs range', Minvel, Maxvel
     end if
     if (proposal == 1) write (q, '(a)') ' proposal 1: shaped by the chains'' covariance, learnt per cell during burn-in'
+    if (ntemp > 1) write (q, '(a,i3,a,f9.3,a,i3,a,i3,a)') ' parallel tempering:', ntemp, ' rungs up to T =', tmax, &
+      ', a swap round every', nswap, ' step(s);', ncold, ' chains per cell at T = 1 are recorded'
   end do
 
   call read_mod('MOD', p, depz, vsf)
@@ -122,6 +138,15 @@ program SurfDepthMC_amd
     write (q, '(a,i8,a,i8)') ' cells sampled', ncell - nempty, '  cells without data (start model kept)', nempty
   end do
   if (proposal /= 0) call dazim_check(dazim_mc_set_proposal(dazim_handle, mc, proposal), 'Monte-Carlo proposal')
+  if (ntemp > 1) then
+    allocate (beta(ntemp), swap_try(ntemp - 1, ncell - nempty), swap_acc(ntemp - 1, ncell - nempty))
+    call dazim_check(dazim_mc_set_tempering(dazim_handle, mc, ntemp, tmax, nswap), 'Monte-Carlo tempering')
+    call dazim_check(dazim_mc_temper_state(dazim_handle, mc, c_null_ptr, c_null_ptr, c_null_ptr, c_loc(beta), c_null_ptr, &
+                                           c_null_ptr, c_null_ptr), 'tempering ladder')
+    do q = 6, 66, 60
+      write (q, '(a,64f8.3)') ' ladder, temperatures 1 / beta:', (1.0d0/beta(i), i=1, ntemp)
+    end do
+  end if
   call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
   t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
   t_disp = real(dazim_last_kernel_seconds(dazim_handle, 'mc.disp'//c_null_char))
@@ -130,6 +155,8 @@ program SurfDepthMC_amd
   allocate (mean(nx - 2, ny - 2, nlay), std(nx - 2, ny - 2, nlay), qq(nx - 2, ny - 2, nlay, 3), best(nx - 2, ny - 2, nlay))
   allocate (rhat(nx - 2, ny - 2, nlay), acc(nx - 2, ny - 2), chi2b(nx - 2, ny - 2))
   call dazim_check(dazim_mc_result(dazim_handle, mc, mean, std, qq, best, rhat, acc, chi2b), 'posterior statistics')
+  if (ntemp > 1) call dazim_check(dazim_mc_temper_state(dazim_handle, mc, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                                                        c_null_ptr, c_loc(swap_try), c_loc(swap_acc)), 'swap counts')
   call dazim_check(dazim_mc_free(dazim_handle, mc), 'Monte-Carlo chains')
 
   ! ---- the curves of the mean and of the best model ------------------------------------------------------------------------------
@@ -166,6 +193,19 @@ program SurfDepthMC_amd
     write (q, '(a,f9.2,a,f9.2,a,f9.3,a)') ' run', t_run, ' s (dispersion calls', t_disp, ' s, step kernels', t_step, ' s)'
     if (proposal == 1) write (q, '(a,i8,a,i8)') ' cells with an adapted covariance:', ncov, ' of', ns
   end do
+  if (ntemp > 1 .and. ns > 0) then
+    nr = count(swap_try > 0)
+    allocate (sorted(max(nr, 1)))
+    sorted = 0
+    if (nr > 0) sorted(1:nr) = pack(real(swap_acc)/real(max(swap_try, 1_c_int64_t)), swap_try > 0)
+    call sort(sorted)
+    do q = 6, 66, 60
+      write (q, '(a,4f8.3)') ' swap acceptance over (cell, rung pair), minimum and quartiles 25/50/75 %:', sorted(1), &
+        sorted(max(1, nint(0.25*nr))), sorted(max(1, nint(0.5*nr))), sorted(max(1, nint(0.75*nr)))
+      write (q, '(a,i3,a,i3,a)') ' the statistics below are of the', ncold, ' chains per cell at T = 1 (of', nchain, ')'
+    end do
+    deallocate (sorted)
+  end if
   if (ns > 0) then
     allocate (sorted(ns))
     sorted = pack(acc, sampled)

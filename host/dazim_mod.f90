@@ -38,7 +38,7 @@ module dazim_mod
   public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
   public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
-            dazim_mc_set_proposal, dazim_mc_cov_state, dazim_last_kernel_seconds
+            dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -276,6 +276,18 @@ module dazim_mod
     integer(c_int) function dazim_mc_cov_state(ctx, mc, kind, cov_n, cov_s1, cov_s2, chol, cov_set) bind(C, name="dazim_mc_cov_state")
       import
       type(c_ptr), value :: ctx, mc, kind, cov_n, cov_s1, cov_s2, chol, cov_set
+    end function
+    integer(c_int) function dazim_mc_set_tempering(ctx, mc, ntemp, tmax, nswap) bind(C, name="dazim_mc_set_tempering")
+      import
+      type(c_ptr), value :: ctx, mc
+      integer(c_int), value :: ntemp, nswap
+      real(c_float), value :: tmax
+    end function
+    ! every argument after mc may be c_null_ptr (c_loc of a variable or an array otherwise)
+    integer(c_int) function dazim_mc_temper_state(ctx, mc, ntemp, tmax, nswap, beta, scale, swap_try, swap_acc) &
+        bind(C, name="dazim_mc_temper_state")
+      import
+      type(c_ptr), value :: ctx, mc, ntemp, tmax, nswap, beta, scale, swap_try, swap_acc
     end function
     integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
         bind(C, name="dazim_phase_map_update")

@@ -329,6 +329,32 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
  *   cov_set is 0, the formula above.  (u in [0, 1] bounds C_kk, the squared norm of row k of chol, by 1/4 + 1e-8; each Box-Muller
  *   pair has norm <= 6.77, so |z|_2 <= 6.77 sqrt(ceil(nlay / 2)); s <= 2 / sqrt(nlay): the excess stays below 6.78 widths, at most 7
  *   reflections, and the clamp still never acts.)
+ * Parallel tempering (dazim_mc_set_tempering; without it, or with ntemp = 1, the step is the one above, unchanged): replica exchange
+ *   (Swendsen and Wang, 1986; Geyer, 1991) for posteriors with separate modes.  ntemp divides nchain; chain ch is rung r = ch % ntemp
+ *   of replica group g = ch / ntemp, so ncold = nchain / ntemp chains (ch = 0, ntemp, 2 ntemp, ..) sit at rung 0.  beta_0 = 1 and
+ *   beta_r = tmax^(-r / (ntemp - 1)) (pow in fp64 on the host, once; the step takes beta from the handle); rung r samples the
+ *   posterior to the power beta_r, rung 0 the posterior itself.  Per sampled cell the handle holds scale and its window count per
+ *   rung [ntemp] (every scale starts at dazim_mc_create's step) and swap_try, swap_acc [ntemp - 1] (int64, 0 at the start).  The
+ *   step changes in this way:
+ *   Decision at rung r: accept iff log(u) < -0.5 * beta_r * (chi2' - chi2) (fp64, evaluated left to right); the uniform, the t = 1
+ *   rule and the rules for chi2 = +inf are the ones above.
+ *   Scale: rung r of a cell counts the accepted burn-in moves of its ncold chains; at the end of a window rate_r = count_r / (nadapt *
+ *   ncold) moves the rung's own scale with the thresholds, the factor 1.25f and the clamps above ([1e-3f, 2.0f / sqrtf((float)nlay)]
+ *   for every rung while the cell's cov_set is 1), and every rung's count restarts.  dazim_mc_state's scale is rung 0's.
+ *   Swap: in a step with a decision (t > 1) and t % nswap == 0, after the decision and before anything is recorded, accumulated or
+ *   proposed; round w = t / nswap pairs the rungs (r, r + 1) with r % 2 == w % 2 and r + 1 < ntemp in every group.  For the pair of
+ *   chain cl (rung r) and cl + 1: u = u(word 1 of block(t, gid(cl), 0)), D = 0.5 * (beta_r - beta_{r+1}) * (chi2_r - chi2_{r+1})
+ *   (fp64, left to right).  Both chi2 finite: swap iff log(u) < D.  chi2_r = +inf and chi2_{r+1} finite: swap.  Otherwise no swap.
+ *   A swap exchanges the two chains' nlay knots and chi2; the last knot stays.  swap_try[r] += 1 per pair of the round, swap_acc[r]
+ *   += 1 per swap, over the groups and over all steps.
+ *   Records: only the rung-0 chains add to sums, hist and accepted (the columns of the other chains stay 0); the best model is the
+ *   lowest chi2 over all chains of the cell after the swap, with the tie rule above.  dazim_mc_result takes the ncold rung-0 chains
+ *   in chain order with M = ncold everywhere (R-hat NaN for ncold = 1; accept = their accepted moves / (decisions * ncold)).
+ *   Kind 1: the sums take the states of the rung-0 chains only, after the swap, in chain order, and cov_n += ncold; the 8 nlay rule,
+ *   the factor and the reset are unchanged.  A cell has one factor, used by every rung with the rung's own scale, and at the first
+ *   factor every rung's scale becomes 1.0f / sqrtf((float)nlay).  The clamps of s being the same, the bounds on the number of
+ *   reflections above hold at every rung.
+ *   Next proposals: the formulas above with s the scale of the chain's rung.
  * dazim_mc_create: vel0 [nz][ny][nx] (the last knot; the result of cells without data), vmin, vmax [nlay][ny-2][nx-2], cobs, wdat
  *   [kmax][ny-2][nx-2] (the layout of dazim_column_lsq), step = the initial s, nadapt >= 1.  Draws the start models.  Refused
  *   (DAZIM_E_BAD_ARG): nchain outside 1..64, nlay outside 1..63, kmax outside 1..60, nbin < 2, a non-finite vmin, vmax, cobs or
@@ -340,11 +366,20 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
  *   depz [nz] and periods [kmax] host arrays as there) and one step launch; no other host wait.  n_no_root (nullable) = proposals
  *   of the run with chi2' = +inf.  Stats: "mc" (seconds of the run), "mc.disp" (its dispersion kernels), "mc.step" (its step
  *   kernels), "mc.steps", "mc.accept" (accepted / decisions of its recorded steps), "mc.no_root", "mc.proposal" (the kind) and
- *   "mc.cov_cells" (cells with cov_set = 1 at its end).
+ *   "mc.cov_cells" (cells with cov_set = 1 at its end); "mc.ntemp", and "mc.swap_min" and "mc.swap_med", the lowest and the median
+ *   of swap_acc / swap_try over the (cell, rung pair)s with a try, from all the handle's steps (0 without tempering), copied once
+ *   after the run's closing wait.  With tempering "mc.accept" counts the decisions of the rung-0 chains only.
  * dazim_mc_set_proposal: kind 0 (the default) or 1; kind 1 allocates the arrays above.  DAZIM_E_BAD_ARG for another kind, for a
  *   handle of another context, or once a step has been done.
  * dazim_mc_cov_state: kind, and for kind 1 copies of cov_n, cov_set [sampled cells], cov_s1 [sampled cells][nlay], cov_s2, chol
  *   [sampled cells][npair] (each pointer nullable, host or device).  DAZIM_E_BAD_ARG for kind 0 when an array is requested.
+ * dazim_mc_set_tempering: ntemp rungs up to temperature tmax, a swap round every nswap steps; ntemp = 1 restores the default (tmax
+ *   is not looked at then).  It may come before or after dazim_mc_set_proposal.  DAZIM_E_BAD_ARG when ntemp is outside 1..nchain or
+ *   does not divide nchain, when ntemp > 1 and tmax is not finite or <= 1, when nswap < 1, for a handle of another context, or once
+ *   a step has been done.
+ * dazim_mc_temper_state: ntemp, tmax, nswap, and for ntemp > 1 copies of beta [ntemp], scale [sampled cells][ntemp], swap_try and
+ *   swap_acc [sampled cells][ntemp - 1] (each pointer nullable, host or device).  DAZIM_E_BAD_ARG for ntemp = 1 when an array is
+ *   requested.
  * dazim_mc_state: copies of the chain state (each pointer nullable, host or device): cur [nz][ncol], chi2 [ncol], scale [sampled
  *   cells], step (steps done), sums [2][nlay][ncol], hist [sampled cells][nlay][nbin], accepted [ncol], best [nlay][sampled cells]
  *   and best_chi2 [sampled cells] (vel0's knots and +inf before the first recorded step).
@@ -360,6 +395,9 @@ int dazim_mc_proposals(dazim_mc *mc, float **vel_dev, int64_t *ncol);
 int dazim_mc_set_proposal(dazim_ctx *ctx, dazim_mc *mc, int kind);
 int dazim_mc_cov_state(dazim_ctx *ctx, dazim_mc *mc, int *kind, int64_t *cov_n, double *cov_s1, double *cov_s2, double *chol,
                        int *cov_set);
+int dazim_mc_set_tempering(dazim_ctx *ctx, dazim_mc *mc, int ntemp, float tmax, int nswap);
+int dazim_mc_temper_state(dazim_ctx *ctx, dazim_mc *mc, int *ntemp, float *tmax, int *nswap, double *beta, float *scale,
+                          int64_t *swap_try, int64_t *swap_acc);
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);
 int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
                  int64_t *n_no_root);

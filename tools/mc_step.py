@@ -1,7 +1,7 @@
 """Times of the Monte-Carlo step (profiles/depth_mc.md).
 
-    python tools/mc_step.py [--steps S] [--big N] [--proposal K]
-    python tools/mc_step.py --program [--dir D] [--proposal K]
+    python tools/mc_step.py [--steps S] [--big N] [--proposal K] [--ntemp R [--tmax T]]
+    python tools/mc_step.py --program [--dir D] [--proposal K] [--ntemp R [--tmax T]]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -15,7 +15,10 @@ and the log's summary lines.
 
 --proposal 1: the covariance-adapted proposal (dazim_mc_set_proposal) instead of the default 0.  The timed run then adapts every 5
 burn-in steps instead of every 50, so that its S/2 burn-in steps hold factorisations and its recorded steps draw from the factor;
-"cov_cells" counts the cells that did."""
+"cov_cells" counts the cells that did.
+
+--ntemp R: parallel tempering with R rungs up to temperature T (dazim_mc_set_tempering; default T 16, a swap round every step)
+instead of the default 1, no tempering; "swap_min" and "swap_med" are the run's swap acceptances over cells and rung pairs."""
 import argparse
 import json
 import os
@@ -30,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one_case(ctx, n, nchain, steps, proposal):
+def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax):
     import bench
     bench.NX = bench.NY = n
     vel = bench.s256_model().astype(np.float32)
@@ -41,7 +44,8 @@ def one_case(ctx, n, nchain, steps, proposal):
     inner = vel[:nlay, 1:-1, 1:-1]
     vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
     wdat = np.full((kmax, n - 2, n - 2), 100.0, np.float32)
-    mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat, nadapt=5 if proposal else 50, proposal=proposal)
+    mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat, nadapt=5 if proposal else 50, proposal=proposal,
+                       ntemp=ntemp, tmax=tmax)
     mc.run(depz, bench.MINTHK, periods, 5, 0)                 # warm-up: code objects, scratch buffers
     nr = mc.run(depz, bench.MINTHK, periods, steps // 2, steps - steps // 2)
     wall, disp, stp = ctx.stat("mc"), ctx.stat("mc.disp"), ctx.stat("mc.step")
@@ -49,7 +53,9 @@ def one_case(ctx, n, nchain, steps, proposal):
     mc.free()
     ms = lambda s: 1e3 * s / steps
     return {"grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots ({nlay} sampled), {kmax} periods", "nchain": nchain,
-            "proposal": proposal, "cov_cells": int(ctx.stat("mc.cov_cells")), "steps": steps, "curves_per_step": mc.ncol, "ms_per_step": ms(wall), "disp_ms_per_step": ms(disp),
+            "proposal": proposal, "ntemp": ntemp, "swap_min": ctx.stat("mc.swap_min"), "swap_med": ctx.stat("mc.swap_med"),
+            "cov_cells": int(ctx.stat("mc.cov_cells")), "steps": steps, "curves_per_step": mc.ncol, "ms_per_step": ms(wall),
+            "disp_ms_per_step": ms(disp),
             "mc_step_ms_per_step": ms(stp), "other_ms_per_step": ms(wall - disp - stp), "mc_step_share": stp / wall,
             "curves_per_s": mc.ncol * steps / wall, "accept": ctx.stat("mc.accept"), "no_root": nr,
             "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
@@ -78,7 +84,7 @@ cccccccccc periods
 """
 
 
-def program_run(ctx, d, proposal):
+def program_run(ctx, d, proposal, ntemp, tmax):
     import bench
     n = bench.NX = bench.NY = 54
     vel = bench.s256_model().astype(np.float32)
@@ -103,14 +109,16 @@ def program_run(ctx, d, proposal):
                     f.write("%10.4f%10.4f%10.4f%10.4f\n" % (100.0 + (j - 1) * 0.25, 30.0 - (i - 1) * 0.25, periods[t], pv[t, j, i]))
     exe = os.path.join(ROOT, "host", "SurfDepthMC_amd")
     t0 = time.perf_counter()
-    args = ["2000", "32", "0", "0.01", "1", str(proposal)] if proposal else []
+    args = ["2000", "32", "0", "0.01", "1", str(proposal)] if proposal or ntemp > 1 else []
+    if ntemp > 1:
+        args += [str(ntemp), "%g" % tmax]
     out = subprocess.run([exe, "para.in"] + args, cwd=d, capture_output=True, text=True, timeout=1500)
     wall = time.perf_counter() - t0
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     log = open(os.path.join(d, "para.in_mc.log")).read().splitlines()
     keep = [l.strip() for l in log if any(k in l for k in ("cells sampled", "without a root", "run", "acceptance", "R-hat", "rms_c", "proposal",
-                                                                "covariance"))]
-    return {"program": "SurfDepthMC_amd para.in (defaults: 2000 + 2000 steps, 32 chains)", "proposal": proposal,
+                                                                "covariance", "tempering", "ladder", "swap", "T = 1"))]
+    return {"program": "SurfDepthMC_amd para.in (defaults: 2000 + 2000 steps, 32 chains)", "proposal": proposal, "ntemp": ntemp,
             "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots, {kmax} periods", "wall_s": wall, "log": keep}
 
 
@@ -122,14 +130,16 @@ def main():
     ap.add_argument("--program", action="store_true")
     ap.add_argument("--dir", default=None)
     ap.add_argument("--proposal", type=int, default=0, choices=(0, 1))
+    ap.add_argument("--ntemp", type=int, default=1)
+    ap.add_argument("--tmax", type=float, default=16.0)
     a = ap.parse_args()
     ctx = dz.Context(0)
     if a.program:
         with tempfile.TemporaryDirectory() as tmp:
-            print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal)), flush=True)
+            print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal, a.ntemp, a.tmax)), flush=True)
         return
     for n, nchain in ((54, 8), (54, 32), (54, 64), (a.big, 8)):
-        print(json.dumps(one_case(ctx, n, nchain, a.steps, a.proposal)), flush=True)
+        print(json.dumps(one_case(ctx, n, nchain, a.steps, a.proposal, a.ntemp, a.tmax)), flush=True)
     ctx.close()
 
 
