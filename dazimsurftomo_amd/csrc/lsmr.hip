@@ -424,6 +424,9 @@ struct LsmrSolve : LsmrArgs {
   const int *g1 = nullptr, *g2 = nullptr;   // &S->stop, &S->stop2: the guards of the two half-steps
   int istop = 0, itn = 0, ntrace = 0;
   float normA = 0, condA = 0, normr = 0, normAr = 0, normx = 0, normb = 0;
+  // max |u| as A^T u's fixed-point scatter form is told it: u is normalised, so 1 -- unless ||b|| is NaN or Inf (b holds one): then
+  // u does too, and that value sends every A^T u of the solve to the gather form, which propagates it
+  float ymax = 1.0f;
   double t_spmv = 0, t_spmvt = 0;
   int n_spmv = 0, n_spmvt = 0;
   long n_enq = 0;       // iterations enqueued
@@ -541,9 +544,9 @@ struct LsmrSolve : LsmrArgs {
   }
   // v(out) = A^T u + sign*beta*v with partials of ||v||^2 in `part` (row-sharded: local product, all-reduce, then the axpby)
   int spmvT(const float *beta_p, float sign, const int *g) {
-    if (!comm) return dz_launch_spmvT(ctx, A, u, 1.0f, v, beta_p, sign, part, &gn_t, g);
+    if (!comm) return dz_launch_spmvT(ctx, A, u, ymax, v, beta_p, sign, part, &gn_t, g);
     DZ_HIP(hipMemsetAsync(wbuf, 0, n * 4, ctx->stream));
-    if (const int r = dz_launch_spmvT(ctx, A, u, 1.0f, wbuf, nullptr, 1.0f, nullptr, nullptr, g)) return r;
+    if (const int r = dz_launch_spmvT(ctx, A, u, ymax, wbuf, nullptr, 1.0f, nullptr, nullptr, g)) return r;
     if (const int rr = dz_allreduce(ctx, comm, wbuf, (size_t)n, DZ_F32, DZ_SUM)) return rr;
     hipLaunchKernelGGL(k_axpby_norm, dim3(bn), dim3(VB), 0, ctx->stream, n, wbuf, v, beta_p, sign, part, g);
     gn_t = bn;
@@ -560,6 +563,7 @@ struct LsmrSolve : LsmrArgs {
     hipLaunchKernelGGL(k_sumsq, dim3(bm), dim3(VB), 0, ctx->stream, m, u, part);
     float alpha = 0.0f, beta = 0.0f;
     if ((rc = norm_to_host(part, bm, &beta, true))) return rc;
+    if (!std::isfinite(beta)) ymax = beta;
     if (beta > 0.0f) {
       hipLaunchKernelGGL(k_scal_inv, dim3(bm), dim3(VB), 0, ctx->stream, m, u, d_scal, 1.0f);
       if ((rc = spmvT(nullptr, 1.0f, nullptr))) return rc;  // v = 1*v(=0) + A^T u
@@ -616,7 +620,7 @@ struct LsmrSolve : LsmrArgs {
     hipLaunchKernelGGL(k_local_norm_scal, dim3(bm), dim3(VB), 0, ctx->stream, m, u, part, gm_t, w_sum, d_bp, S);
     if (tev) DZ_HIP(hipEventRecord(tev[2], ctx->stream));
     DZ_HIP(hipMemsetAsync(wbuf, 0, n * 4, ctx->stream));
-    if ((r = dz_launch_spmvT(ctx, A, u, 1.0f, wbuf, nullptr, 1.0f, nullptr, nullptr, g1))) return r;
+    if ((r = dz_launch_spmvT(ctx, A, u, ymax, wbuf, nullptr, 1.0f, nullptr, nullptr, g1))) return r;
     hipLaunchKernelGGL(k_scale_by, dim3(bn), dim3(VB), 0, ctx->stream, n, wbuf, d_bp, g1);
     if (tev) DZ_HIP(hipEventRecord(tev[3], ctx->stream));
     if (rccl_allreduce) {   // option comm.allreduce: RCCL's own sums (its order), the two buffers in one group

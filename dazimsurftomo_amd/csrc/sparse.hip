@@ -252,31 +252,35 @@ __global__ void k_narrow_cols(int64_t n, const int *__restrict__ col, unsigned s
     }
   }
 }
+// max |x| over the bit patterns of |x| as unsigned integers: they order like the values for finite x, Inf above every finite
+// value and NaN above Inf, so a NaN anywhere in x is the result (fmaxf would drop it) and an Inf is the result unless a NaN is
+__device__ __forceinline__ unsigned abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned umax2(unsigned a, unsigned b) { return a > b ? a : b; }
 __global__ void k_absmax(int64_t n, const float *x, float *part) {
-  float v = 0.0f;
+  unsigned v = 0u;
   const int64_t n4 = ((reinterpret_cast<uintptr_t>(x) & 15) == 0) ? n / 4 : 0;   // 16-byte loads when the array allows
   for (int64_t i = (int64_t)blockIdx.x * VB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * VB) {
     const float4 q = reinterpret_cast<const float4 *>(x)[i];
-    v = fmaxf(fmaxf(v, fmaxf(fabsf(q.x), fabsf(q.y))), fmaxf(fabsf(q.z), fabsf(q.w)));
+    v = umax2(umax2(v, umax2(abs_bits(q.x), abs_bits(q.y))), umax2(abs_bits(q.z), abs_bits(q.w)));
   }
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB) v = fmaxf(v, fabsf(x[i]));
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB) v = umax2(v, abs_bits(x[i]));
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  __shared__ float s[VB / 64];
+  for (int o = 32; o > 0; o >>= 1) v = umax2(v, (unsigned)__shfl_xor((int)v, o));
+  __shared__ unsigned s[VB / 64];
   if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
-    float t = 0.0f;
-    for (int i = 0; i < VB / 64; i++) t = fmaxf(t, s[i]);
-    part[blockIdx.x] = t;
+    unsigned t = 0u;
+    for (int i = 0; i < VB / 64; i++) t = umax2(t, s[i]);
+    part[blockIdx.x] = __uint_as_float(t);
   }
 }
 __global__ void k_absmax_finish(const float *part, int np, float *res) {
-  float v = 0.0f;
-  for (int i = threadIdx.x; i < np; i += 64) v = fmaxf(v, part[i]);
+  unsigned v = 0u;
+  for (int i = threadIdx.x; i < np; i += 64) v = umax2(v, abs_bits(part[i]));
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  if (threadIdx.x == 0) res[0] = v;
+  for (int o = 32; o > 0; o >>= 1) v = umax2(v, (unsigned)__shfl_xor((int)v, o));
+  if (threadIdx.x == 0) res[0] = __uint_as_float(v);
 }
 
 // ---- software-pipelined walk over CSR row segments (A^T*y scatter and column-blocked A*x) ----
@@ -719,8 +723,11 @@ int dz_launch_spmvT(dazim_ctx *ctx, const dazim_csr *A, const float *y, float ym
   const double pm = (double)A->vmax * (double)ymax;
   ctx->ksec["spmvt.kind"] = (dz_use_scatter(ctx, A) && std::isfinite(pm)) ? 1 : 0;
   ctx->ksec["spmvt.idx_bytes"] = (A->col16 && dz_use_scatter(ctx, A) && std::isfinite(pm)) ? 2 : 4;
+  ctx->ksec["spmvt.lanes"] = 0;   // (the scatter form records its 64 or 16 lanes per row segment below)
+  ctx->ksec["spmv.ncb"] = A->ncb;
+  ctx->ksec["spmv.cbw"] = A->cbw;
   // non-finite values (NaN / Inf in G or y) cannot be put on the fixed-point grid: the gather form propagates them like
-  // the reference's plain loop would
+  // the reference's plain loop would (vmax and ymax come from k_absmax, which returns NaN / Inf if the array holds one)
   if (!dz_use_scatter(ctx, A) || !std::isfinite(pm)) {
     if (!A->colptr) {
       int rc0 = dz_build_transpose(ctx, const_cast<dazim_csr *>(A));
@@ -743,6 +750,7 @@ int dz_launch_spmvT(dazim_ctx *ctx, const dazim_csr *A, const float *y, float ym
   rc = dispatch_rows(A, rs.shortseg, [&](auto gl, auto ng, auto *colp) -> int {
     using IT = std::remove_pointer_t<decltype(colp)>;
     const auto kern = spmvT_scatter<decltype(gl)::value, decltype(ng)::value, IT>;
+    ctx->ksec["spmvt.lanes"] = decltype(gl)::value;
     DZ_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, sgrid, sblock, lds, ctx->stream, rs.nsplit, A->m, nchunk, A->ncb, A->cbw, A->n, A->cbptr,
                        (const IT *)colp, A->val, y, scale, part, guard, (sizeof(IT) == 2 && A->col16_mod > 0) ? 1 : 0);
@@ -762,6 +770,9 @@ int dz_launch_spmvA(dazim_ctx *ctx, const dazim_csr *A, const float *x, float *o
   ctx->ksec["spmv.kind"] = use_blocked(ctx, A) ? 2 : (use_ldsx(ctx, A->m, A->n) ? 1 : 0);
   // index bytes streamed per entry (the whole-x LDS kernel needs the column itself, the blocked one takes either form)
   ctx->ksec["spmv.idx_bytes"] = (A->col16 && (use_blocked(ctx, A) || (use_ldsx(ctx, A->m, A->n) && A->col16_mod == 0))) ? 2 : 4;
+  ctx->ksec["spmv.lanes"] = 0;   // (the column-blocked form records its 64 or 16 lanes per row segment below)
+  ctx->ksec["spmv.ncb"] = A->ncb;
+  ctx->ksec["spmv.cbw"] = A->cbw;
   if (!use_blocked(ctx, A)) {
     const int gm = dz_spmv_blocks(ctx, A->m, A->n);
     if (npart) *npart = gm;
@@ -781,6 +792,7 @@ int dz_launch_spmvA(dazim_ctx *ctx, const dazim_csr *A, const float *x, float *o
   rc = dispatch_rows(A, rs.shortseg, [&](auto gl, auto ng, auto *colp) -> int {
     using IT = std::remove_pointer_t<decltype(colp)>;
     const auto kern = spmv_rows_blocked<decltype(gl)::value, decltype(ng)::value, IT>;
+    ctx->ksec["spmv.lanes"] = decltype(gl)::value;
     DZ_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, bgrid, bblock, lds, ctx->stream, rs.nsplit, A->m, nset, npair, A->ncb, A->cbw, A->n, A->cbptr,
                        (const IT *)colp, A->val, x, part, guard, (sizeof(IT) == 2 && A->col16_mod > 0) ? 1 : 0);
