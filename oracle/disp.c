@@ -348,6 +348,19 @@ int orc_surfdisp96(const float *thk, const float *vp, const float *vs, const flo
   return nok;
 }
 
+/* the rmax orc_refine_layers would return (its nsub arithmetic, nothing written); INT_MAX-safe: stops counting past ORC_NL */
+int orc_refined_count(float minthk0, int mmax, const float *dep) {
+  int k = 0;
+  for (int i = 1; i <= mmax - 1 && k <= ORC_NL; i++) {
+    float thk = dep[i] - dep[i - 1];
+    float minthk = thk / minthk0;
+    float q = (thk + 1.0e-4f) / minthk;
+    if (!(q >= 0.0f && q < (float)ORC_NL)) return ORC_NL + 1;   /* NaN, negative or huge: refuse rather than convert */
+    k += (int)q + 1;
+  }
+  return k + 1;
+}
+
 /* inv/CalSurfG.f90:2317-2376 ; returns rmax */
 int orc_refine_layers(float minthk0, int mmax, const float *dep, const float *vp, const float *vs,
                       const float *rho, float *rthk, float *rvp, float *rvs, float *rrho) {
@@ -387,13 +400,15 @@ static void curve(float minthk, int nz, const float *depz, const float *vp, cons
   orc_surfdisp96(rthk, rvp, rvs, rrho, rmax, kmax, t, cg);
 }
 
-/* inv/CalSurfG.f90:1-139 */
+/* inv/CalSurfG.f90:1-139 ; returns the number of (column, period) pairs without a root, or ORC_E_SIZE (< 0: more than ORC_NL knots
+ * or refined layers, more than ORC_NP periods; nothing is written) */
 int orc_depthkernel(int nx, int ny, int nz, const float *vel, int kmax, const double *t,
                     const float *depz, float minthk, double *pv, double *svs, double *svp,
                     double *srho) {
   const float dln = 0.01f;
   size_t ncol = (size_t)nx * ny;
   int nfail = 0;
+  if (nz < 2 || nz > ORC_NL || kmax < 0 || kmax > ORC_NP || orc_refined_count(minthk, nz, depz) > ORC_NL) return ORC_E_SIZE;
   for (int jj = 0; jj < ny; jj++)
     for (int ii = 0; ii < nx; ii++) {
       size_t col = (size_t)jj * nx + ii;

@@ -38,7 +38,8 @@ int orc_surfdisp96_full(const float *thk, const float *vp, const float *vs, cons
 /* inv/CalSurfG.f90:2317 */
 int orc_refine_layers(float minthk0, int mmax, const float *dep, const float *vp, const float *vs,
                       const float *rho, float *rthk, float *rvp, float *rvs, float *rrho);
-/* inv/CalSurfG.f90:1 ; vel[nz][ny][nx]; pv[kmax][nx*ny]; sen_*[nz][kmax][nx*ny] (may be NULL) */
+/* inv/CalSurfG.f90:1 ; vel[nz][ny][nx]; pv[kmax][nx*ny]; sen_*[nz][kmax][nx*ny] (may be NULL); returns the number of
+ * (column, period) pairs without a root, or ORC_E_SIZE (see below) */
 int orc_depthkernel(int nx, int ny, int nz, const float *vel, int kmax, const double *t,
                     const float *depz, float minthk, double *pv, double *svs, double *svp,
                     double *srho);
@@ -48,13 +49,42 @@ void orc_brocher(float vs, float *vp, float *rho);
 
 /* ---- TI eigenfunction kernels (tregn.c) ------------------------------------------------------ */
 /* inv/tregn96.f:52 as depthkernelTI calls it (Rayleigh, mode 1, iflsph=1, dogam, hs=hr=0, solid layers):
- * d,TA,TC,TF,TL,TN,rho fp32[nl]; t,cp fp32[nt]; outputs fp32 [nt][nl].  returns 0 / 3 (fluid layer) */
+ * d,TA,TC,TF,TL,TN,rho fp32[nl]; t,cp fp32[nt]; outputs fp32 [nt][nl].  returns 0 / 3 (fluid layer) / ORC_E_SIZE */
 int orc_tregn96(int nl, const float *d, const float *TA, const float *TC, const float *TF, const float *TL,
                 const float *TN, const float *rho, int nt, const float *t, const float *cp, float *dcdah,
                 float *dcdbv, float *dcdn);
 /* inv/depthkernelTI.f90:2 ; pv[kmax][nx*ny] (nullable), lsen[nz-1][kmax][nx*ny] fp32 (= Lsen_Gsc) */
 int orc_depthkernel_ti(int nx, int ny, int nz, const float *vel, int kmax, const double *t,
                        const float *depz, float minthk, double *pv, float *lsen);
+/* orc_tregn96, orc_depthkernel_ti and orc_depthkernel refuse a model of more than ORC_NL knots or refined layers and more
+ * than ORC_NP periods (the reference would write past its NL / NP arrays): ORC_E_SIZE, nothing written */
+#define ORC_E_SIZE (-4)
+/* number of refined layers (half-space included) orc_refine_layers would write, without writing them (disp.c) */
+int orc_refined_count(float minthk0, int mmax, const float *dep);
+
+/* Branch census of orc_tregn96: how often the guarded exponentials and special cases of tregn96 were taken since the last
+ * reset.  Counting only: no counter is read by the computation.  One visit = one finite layer of one (column, period); the
+ * per-layer branches are counted in the sweep named, so that a layer counts once although `up` and `down` both evaluate it. */
+enum {
+  ORC_TI_LAYERS = 0,  /* finite layers visited (up sweep)                                                  */
+  ORC_TI_FAC0,        /* varsv: Re(nu d) >= 15, exp(-2 nu d) taken as 0; per wave type, P and SV (up sweep) */
+  ORC_TI_DFAC0,       /* dnka: pex + svex > 35, exp(-(pex+svex)) taken as 0 (up sweep)                     */
+  ORC_TI_FFUNC,       /* ffunc: Re(nu d) >= 40; per wave type                                              */
+  ORC_TI_GFUNC,       /* gfunc: Re(nu d) >= 75; per wave type                                              */
+  ORC_TI_H1FUNC,      /* h1func: Re((nua + nub) d) >= 40                                                   */
+  ORC_TI_H2FUNC,      /* h2func: Re(nu d) >= 40; per wave type                                             */
+  ORC_TI_DOWN0,       /* down: |pex - svex| > 40, the smaller of fp / fs taken as 0                        */
+  ORC_TI_EXT80,       /* svfunc: |ext| >= 80, eigenfunctions at that layer top set to 0                    */
+  ORC_TI_FLUSH,       /* chksiz: a non-zero partial below 1e-36 flushed to 0; per output value             */
+  ORC_TI_T1_UP,       /* cnormc: largest compound-vector entry < 1e-40, scale reset to 1                   */
+  ORC_TI_T1_DOWN,     /* rnormc: the same for the Haskell vector of `down`                                 */
+  ORC_TI_IMAG_RSV,    /* |Im(nu_sv)| > |Re(nu_sv)|: oscillatory SV, c above the layer's Vs (up sweep)      */
+  ORC_TI_IMAG_RP,     /* the same for nu_p: c above the layer's Vp (up sweep)                              */
+  ORC_TI_TINY_NU,     /* the |nu| < 1e-5 (varsv) and < 1e-8 (ffunc, h1func, h2func) special cases          */
+  ORC_TI_NCOUNT
+};
+/* copies the ORC_TI_NCOUNT counters to out (may be NULL) and, if reset != 0, zeroes them afterwards */
+void orc_ti_census(long long *out, int reset);
 
 /* ---- eikonal (fmm.c) ----------------------------------------------------------------------- */
 typedef struct {

@@ -15,6 +15,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 RMAX = 129
+NL, NP = 200, 60      # ORC_NL, ORC_NP
+# the counters of orc_ti_census, in the order of the enum in oracle.h
+TI_CENSUS = ("layers", "fac0", "dfac0", "ffunc", "gfunc", "h1func", "h2func", "down0", "ext80", "flush", "t1_up", "t1_down",
+             "imag_rsv", "imag_rp", "tiny_nu")
 
 f32 = np.float32
 f64 = np.float64
@@ -94,7 +98,9 @@ class Oracle:
             ptrs = [pd(x) for x in s]
         else:
             s, ptrs = None, [None] * 3
-        self.lib.orc_depthkernel(nx, ny, nz, pf(vel), kmax, pd(t), pf(depz), C.c_float(minthk), pd(pv), *ptrs)
+        rc = self.lib.orc_depthkernel(nx, ny, nz, pf(vel), kmax, pd(t), pf(depz), C.c_float(minthk), pd(pv), *ptrs)
+        if rc < 0:
+            raise RuntimeError(f"orc_depthkernel rc={rc}: more than {NL} knots or refined layers, or more than {NP} periods")
         return pv, s
 
     # ---- eikonal ----
@@ -107,8 +113,16 @@ class Oracle:
         rc = self.lib.orc_depthkernel_ti(nx, ny, nz, pf(vel), len(t), pd(t), pf(np.ascontiguousarray(depz, f32)),
                                          C.c_float(minthk), pd(pv), pf(lsen))
         if rc:
-            raise RuntimeError(f"orc_depthkernel_ti rc={rc}")
+            raise RuntimeError(f"orc_depthkernel_ti rc={rc}" + (" (fluid layer)" if rc == 3 else f": more than {NL} knots or refined "
+                               f"layers, or more than {NP} periods" if rc < 0 else ""))
         return pv, lsen
+
+    def ti_census(self, reset=True):
+        """branch census of orc_tregn96 since the last reset (oracle.h): {name: count}; reset=True zeroes the counters afterwards"""
+        n = (C.c_longlong * len(TI_CENSUS))()
+        self.lib.orc_ti_census.restype = None
+        self.lib.orc_ti_census(n, 1 if reset else 0)
+        return dict(zip(TI_CENSUS, (int(v) for v in n)))
 
     def geometry(self, nx, ny, goxd, gozd, dvxd, dvzd):
         g = Geom()

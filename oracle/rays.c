@@ -440,7 +440,10 @@ static int calsurfg_impl(int nx, int ny, int nz, const float *vels, float goxd, 
   double *pv = (double *)malloc(sizeof(double) * kmax * ncol);
   double *svs = (double *)malloc(sizeof(double) * nk), *svp = (double *)malloc(sizeof(double) * nk),
          *srho = (double *)malloc(sizeof(double) * nk);
-  orc_depthkernel(nx, ny, nz, vels, kmax, tRc, depz, minthk, pv, svs, svp, srho);
+  if (orc_depthkernel(nx, ny, nz, vels, kmax, tRc, depz, minthk, pv, svs, svp, srho) < 0) {   /* model larger than NL / NP */
+    free(pv); free(svs); free(svp); free(srho);
+    return ORC_E_SIZE;
+  }
   size_t nn = (size_t)g.nnx * g.nnz, nr = (size_t)ORC_RMAX * ORC_RMAX;
   float *veln = (float *)malloc(sizeof(float) * nn), *ttn = (float *)malloc(sizeof(float) * nn);
   float *ttnr = (float *)malloc(sizeof(float) * nr), *velnr = (float *)malloc(sizeof(float) * nr);

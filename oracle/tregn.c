@@ -19,6 +19,14 @@
 
 #include "oracle.h"
 
+/* branch census (oracle.h): written here, read by nobody but orc_ti_census */
+static long long census[ORC_TI_NCOUNT];
+#define COUNT(which) (census[which]++)
+void orc_ti_census(long long *out, int reset) {
+  if (out) memcpy(out, census, sizeof census);
+  if (reset) memset(census, 0, sizeof census);
+}
+
 typedef struct { double re, im; } cx;
 static cx C(double re, double im) { cx z = {re, im}; return z; }
 static cx cadd(cx a, cx b) { return C(a.re + b.re, a.im + b.im); }
@@ -83,8 +91,8 @@ static void layer_eig(double TA, double TC, double TF, double TL, double rho, do
 
 typedef struct { cx cosp, rsinp, sinpr, cosq, rsinq, sinqr; double pex, svex; } trig;
 
-/* inv/tregn96.f:3363 varsv, solid branch: cosh/sinh of nu*d scaled by exp(-Re(nu*d)) */
-static void layer_trig(const eig *g, double dm, trig *t) {
+/* inv/tregn96.f:3363 varsv, solid branch: cosh/sinh of nu*d scaled by exp(-Re(nu*d)); count: this call is the layer's census visit */
+static void layer_trig(const eig *g, double dm, trig *t, int count) {
   const cx p = cscale(g->rp, dm), q = cscale(g->rsv, dm);
   t->pex = p.re;
   t->svex = q.re;
@@ -92,6 +100,11 @@ static void layer_trig(const eig *g, double dm, trig *t) {
     const cx arg = w ? q : p, nu = w ? g->rsv : g->rp;
     const cx epp = C(cos(arg.im) / 2.0, sin(arg.im) / 2.0), epm = C(epp.re, -epp.im);
     const double fac = arg.re < 15.0 ? exp(-2.0 * arg.re) : 0.0;
+    if (count) {
+      if (!(arg.re < 15.0)) COUNT(ORC_TI_FAC0);
+      if (fabs(nu.im) > fabs(nu.re)) COUNT(w ? ORC_TI_IMAG_RSV : ORC_TI_IMAG_RP);
+      if (fabs(arg.re) < 1.0e-5 && cabs_(nu) < 1.0e-5) COUNT(ORC_TI_TINY_NU);
+    }
     const cx co = cadd(epp, cscale(epm, fac)), si = csub(epp, cscale(epm, fac));
     const cx rs = cmul(nu, si);
     const cx sr = (fabs(arg.re) < 1.0e-5 && cabs_(nu) < 1.0e-5) ? C(dm, 0) : cdiv(si, nu);
@@ -118,6 +131,7 @@ static const int PAIR[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
 /* 5x5 reduced compound matrix of a solid layer (= CA of dnka_tregn), scaled by exp(-(pex+svex)) */
 static void layer_compound(const eig *g, const trig *t, cx CA[5][5]) {
   const double ex = t->pex + t->svex, dfac = ex > 35.0 ? 0.0 : exp(-ex);
+  if (ex > 35.0) COUNT(ORC_TI_DFAC0);
   cx U[4][4], W[4][4], CU[6][6], CW[6][6], CH[6][6], T[6][6], R[6][6];
   layer_factors(g, U, W);
   for (int r = 0; r < 6; r++)
@@ -179,26 +193,31 @@ static void layer_E(const eig *g, cx E[4][4], cx EI[4][4]) {
 
 /* inv/tregn96.f:1385-1474 */
 static cx ffunc(cx nu, double dm) {
-  if (cabs_(nu) < 1.0e-8) return C(dm, 0);
+  if (cabs_(nu) < 1.0e-8) { COUNT(ORC_TI_TINY_NU); return C(dm, 0); }
   const cx arg = cscale(nu, dm);
+  if (!(arg.re < 40.0)) COUNT(ORC_TI_FFUNC);
   const cx ex = arg.re < 40.0 ? cexp_(cscale(arg, -2.0)) : C(0, 0);
   return cdiv(csub(C(1, 0), ex), cscale(nu, 2.0));
 }
 static cx gfunc(cx nu, double dm) {
   const cx arg = cscale(nu, dm);
+  if (!(arg.re < 75.0)) COUNT(ORC_TI_GFUNC);
   return arg.re < 75.0 ? cscale(cexp_(cneg(arg)), dm) : C(0, 0);
 }
 static cx h1func(cx na, cx nb, double dm) {
-  if (cabs_(cadd(nb, na)) < 1.0e-8) return C(dm, 0);
+  if (cabs_(cadd(nb, na)) < 1.0e-8) { COUNT(ORC_TI_TINY_NU); return C(dm, 0); }
   const cx arg = cscale(cadd(na, nb), dm);
+  if (!(arg.re < 40.0)) COUNT(ORC_TI_H1FUNC);
   const cx ex = arg.re < 40.0 ? cexp_(cneg(arg)) : C(0, 0);
   return cdiv(csub(C(1, 0), ex), cadd(nb, na));
 }
 static cx h2func(cx na, cx nb, double dm) {
-  if (cabs_(csub(nb, na)) < 1.0e-8) return C(dm, 0);
+  if (cabs_(csub(nb, na)) < 1.0e-8) { COUNT(ORC_TI_TINY_NU); return C(dm, 0); }
   cx arg = cscale(na, dm);
+  if (!(arg.re < 40.0)) COUNT(ORC_TI_H2FUNC);
   const cx exp_ = arg.re < 40.0 ? cexp_(cneg(arg)) : C(0, 0);
   arg = cscale(nb, dm);
+  if (!(arg.re < 40.0)) COUNT(ORC_TI_H2FUNC);
   const cx exq = arg.re < 40.0 ? cexp_(cneg(arg)) : C(0, 0);
   return cdiv(csub(exq, exp_), csub(na, nb));
 }
@@ -207,7 +226,7 @@ static double normalise(double *v, int n) { /* rnormc, inv/tregn96.f:1513 */
   double t1 = 0.0;
   for (int i = 0; i < n; i++)
     if (fabs(v[i]) > t1) t1 = fabs(v[i]);
-  if (t1 < 1.0e-40) t1 = 1.0;
+  if (t1 < 1.0e-40) { COUNT(ORC_TI_T1_DOWN); t1 = 1.0; }
   for (int i = 0; i < n; i++) v[i] /= t1;
   return log(t1);
 }
@@ -215,20 +234,21 @@ static double cnormalise(cx *v, int n) { /* cnormc, :1475 */
   double t1 = 0.0;
   for (int i = 0; i < n; i++)
     if (cabs_(v[i]) > t1) t1 = cabs_(v[i]);
-  if (t1 < 1.0e-40) t1 = 1.0;
+  if (t1 < 1.0e-40) { COUNT(ORC_TI_T1_UP); t1 = 1.0; }
   for (int i = 0; i < n; i++) v[i] = cscale(v[i], 1.0 / t1), v[i] = v[i];
   return log(t1);
 }
 
 /* tregn96 for one layered TI model.  d,TA,TC,TF,TL,TN,rho: fp32 [nl] as depthkernelTI passes them (the last layer is the
- * half-space).  t, cp fp32 [nt].  Outputs fp32 [nt][nl] (= dcdah_out(k,i) etc. after sprayl/chksiz).  Returns 0, or 3 if a
- * fluid layer is present (not restated). */
+ * half-space).  t, cp fp32 [nt].  Outputs fp32 [nt][nl] (= dcdah_out(k,i) etc. after sprayl/chksiz).  Returns 0, 3 if a
+ * fluid layer is present (not restated), or ORC_E_SIZE if nl or nt exceed the reference's NL / NP arrays. */
 int orc_tregn96(int nl, const float *d_in, const float *TA_in, const float *TC_in, const float *TF_in, const float *TL_in,
                 const float *TN_in, const float *rho_in, int nt, const float *t_in, const float *cp_in, float *dcdah_out,
                 float *dcdbv_out, float *dcdn_out) {
   float d[ORC_NL], ta[ORC_NL], tc[ORC_NL], tl[ORC_NL], tn[ORC_NL], tf[ORC_NL], trho[ORC_NL], vtp[ORC_NL];
   double zd[ORC_NL], zta[ORC_NL], ztc[ORC_NL], ztf[ORC_NL], ztl[ORC_NL], ztn[ORC_NL], zrho[ORC_NL];
   const int mmax = nl;
+  if (nl < 1 || nl > ORC_NL || nt < 0 || nt > ORC_NP) return ORC_E_SIZE;
   for (int i = 0; i < mmax; i++) {
     d[i] = d_in[i]; ta[i] = TA_in[i]; tc[i] = TC_in[i]; tf[i] = TF_in[i]; tl[i] = TL_in[i]; tn[i] = TN_in[i];
     trho[i] = rho_in[i];
@@ -298,7 +318,8 @@ int orc_tregn96(int nl, const float *d_in, const float *TA_in, const float *TC_i
       for (int m = mmax - 2; m >= 0; m--) {
         cx CA[5][5];
         layer_eig(zta[m], ztc[m], ztf[m], ztl[m], zrho[m], omega, wvno, &g);
-        layer_trig(&g, zd[m], &tg);
+        layer_trig(&g, zd[m], &tg, 1);
+        COUNT(ORC_TI_LAYERS);
         layer_compound(&g, &tg, CA);
         for (int i = 0; i < 5; i++) {
           cx s = C(0, 0);
@@ -319,7 +340,8 @@ int orc_tregn96(int nl, const float *d_in, const float *TA_in, const float *TC_i
       double exsum = 0.0;
       for (int m = 0; m < mmax - 1; m++) {
         layer_eig(zta[m], ztc[m], ztf[m], ztl[m], zrho[m], omega, wvno, &g);
-        layer_trig(&g, zd[m], &tg);
+        layer_trig(&g, zd[m], &tg, 0);
+        if (fabs(tg.pex - tg.svex) > 40.0) COUNT(ORC_TI_DOWN0);
         double cpex, fp = 1.0, fs = 1.0;
         if (tg.pex > tg.svex) { fs = (tg.pex - tg.svex) > 40.0 ? 0.0 : exp(-(tg.pex - tg.svex)); cpex = tg.pex; }
         else { fp = (tg.svex - tg.pex) > 40.0 ? 0.0 : exp(-(tg.svex - tg.pex)); cpex = tg.svex; }
@@ -367,6 +389,7 @@ int orc_tregn96(int nl, const float *d_in, const float *TA_in, const float *TC_i
           const double fact = exp(ext);
           ur[i] = uu1 * fact / f1213; uz[i] = uu2 * fact / f1213; tz[i] = uu3 * fact / f1213; tr[i] = uu4 * fact / f1213;
         } else {
+          COUNT(ORC_TI_EXT80);
           ur[i] = uz[i] = tz[i] = tr[i] = 0.0;
         }
       }
@@ -458,6 +481,7 @@ int orc_tregn96(int nl, const float *d_in, const float *TA_in, const float *TC_i
       const double tm3 = tm * tm * tm;
       for (int m = 0; m < mmax; m++) {
         const double a = fah[m] * (double)vtp[m] / tm3, b = fbv[m] * (double)vtp[m] / tm3, n = fn[m];
+        census[ORC_TI_FLUSH] += (a != 0.0 && fabs(a) < 1.0e-36) + (b != 0.0 && fabs(b) < 1.0e-36) + (n != 0.0 && fabs(n) < 1.0e-36);
         dcdah_out[(size_t)ip * nl + m] = fabs(a) < 1.0e-36 ? 0.0f : (float)a;
         dcdbv_out[(size_t)ip * nl + m] = fabs(b) < 1.0e-36 ? 0.0f : (float)b;
         dcdn_out[(size_t)ip * nl + m] = fabs(n) < 1.0e-36 ? 0.0f : (float)n;
@@ -468,10 +492,12 @@ int orc_tregn96(int nl, const float *d_in, const float *TA_in, const float *TC_i
 }
 
 /* depthkernelTI, inv/depthkernelTI.f90:2: per column Brocher model -> layers -> surfdisp96 -> tregn96 -> Lsen_Gsc.
- * vel[nz][ny][nx]; pv[kmax][nx*ny] (may be NULL); lsen[nz-1][kmax][nx*ny] fp32 */
+ * vel[nz][ny][nx]; pv[kmax][nx*ny] (may be NULL); lsen[nz-1][kmax][nx*ny] fp32.  Returns 0, 3 (fluid layer) or ORC_E_SIZE (more
+ * than ORC_NL knots or refined layers, more than ORC_NP periods: nothing is written) */
 int orc_depthkernel_ti(int nx, int ny, int nz, const float *vel, int kmax, const double *t, const float *depz, float minthk,
                        double *pv, float *lsen) {
   const size_t ncol = (size_t)nx * ny;
+  if (nz < 2 || nz > ORC_NL || kmax < 0 || kmax > ORC_NP || orc_refined_count(minthk, nz, depz) > ORC_NL) return ORC_E_SIZE;
   static float dah[ORC_NP * ORC_NL], dbv[ORC_NP * ORC_NL], dn[ORC_NP * ORC_NL];
   memset(lsen, 0, sizeof(float) * (size_t)(nz - 1) * kmax * ncol);
   for (int jj = 0; jj < ny; jj++)

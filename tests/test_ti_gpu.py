@@ -4,11 +4,15 @@ authors' test1 fixture (period_Azm_tomo.real columns 7-9).
 
 Tolerance: the kernel works in fp64 like the reference and rounds its outputs to fp32 (chksiz); device exp/log/
 sincos differ from the host libm in the last place, so values agree to a few fp32 ulps of the largest kernel:
-|diff| <= 1e-6 * max|Lsen| (observed ~1e-7)."""
+|diff| <= 1e-6 * max|Lsen| (observed ~1e-7).  The oracle comparisons hold the same bar per (period, column) lane as well
+(tests/ti_cases.py, measure a): Lsen spans decades over the periods, and the array's maximum is a long-period entry.  These
+inputs take none of tregn96's saturation branches (tests/test_ti_cases_cpu.py); tests/test_ti_edges_gpu.py has the ones that do."""
 import os
 
 import numpy as np
 import pytest
+
+from tests.ti_cases import lane_excess
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -56,6 +60,7 @@ def test_ti_kernels_deep_columns_vs_oracle(ctx, orc, minthk):
     assert nf == 0
     lsen = ctx.ti_kernels(vel, g["depz"], t, minthk, pv_o)     # same phase velocities as the oracle run
     assert np.abs(lsen - ls_o).max() <= TOL * np.abs(ls_o).max()
+    assert lane_excess(lsen, ls_o) <= TOL
     lsen2 = ctx.ti_kernels(vel, g["depz"], t, minthk, pv)      # and with the device's own dispersion curve
     assert np.abs(lsen2 - ls_o).max() <= 2e-5 * np.abs(ls_o).max()   # pvRc may differ by an fp32 ulp (test_disp_gpu.py)
 
@@ -80,4 +85,7 @@ def test_ti_kernels_device_resident_and_failed_root(ctx, orc):
     mask = np.ones_like(ls_o, bool)
     mask[:, 2, 5] = False
     assert np.abs(got - ls_o)[mask].max() <= TOL * np.abs(ls_o).max()
+    ls_m = ls_o.copy()
+    ls_m[:, 2, 5] = 0
+    assert lane_excess(got, ls_m) <= TOL
     assert ctx.kernel_seconds("ti") > 0
