@@ -17,12 +17,23 @@ typedef struct {
   double del1st; /* SAVE del1st, inv/surfdisp96.f:409 */
 } model;
 
+/* branch census (oracle.h): written here, read by nobody but orc_disp_census */
+static long long census[ORC_DISP_NCOUNT];
+#define COUNT(which) (census[which]++)
+void orc_disp_census(long long *out, int reset) {
+  if (out) memcpy(out, census, sizeof census);
+  if (reset) memset(census, 0, sizeof census);
+}
+
 /* inv/surfdisp96.f:868-985 + :1018-1062 + :807-843: one secular-function evaluation */
 static double dltar4(const model *M, double wvno, double omga) {
   double e[5], ee[5], ca[5][5];
   int mmax = M->mmax;
   double omega = omga;
-  if (omega < 1.0e-4) omega = 1.0e-4;
+  if (omega < 1.0e-4) {
+    omega = 1.0e-4;
+    COUNT(ORC_DISP_OMEGA_CLAMP);
+  }
   double wvno2 = wvno * wvno;
   double xka = omega / (double)M->a[mmax - 1];
   double xkb = omega / (double)M->b[mmax - 1];
@@ -58,12 +69,15 @@ static double dltar4(const model *M, double wvno, double omga) {
     double p = ra * dpth, q = rb * dpth;
     /* ---- var ---- */
     double w, x, y, z, cosp, cosq, sinp, sinq, fac, pex = 0.0, sex = 0.0;
+    COUNT(ORC_DISP_LAYERS);
     if (wvno < xka) {
+      COUNT(ORC_DISP_P_OSC);
       sinp = sin(p);
       w = sinp / ra;
       x = -ra * sinp;
       cosp = cos(p);
     } else if (wvno == xka) {
+      COUNT(ORC_DISP_P_EQUAL);
       cosp = 1.0;
       w = dpth;
       x = 0.0;
@@ -71,17 +85,20 @@ static double dltar4(const model *M, double wvno, double omga) {
       pex = p;
       fac = 0.0;
       if (p < 16) fac = exp(-2.0 * p);
+      else COUNT(ORC_DISP_P_SAT);
       cosp = (1.0 + fac) * 0.5;
       sinp = (1.0 - fac) * 0.5;
       w = sinp / ra;
       x = ra * sinp;
     }
     if (wvno < xkb) {
+      COUNT(ORC_DISP_S_OSC);
       sinq = sin(q);
       y = sinq / rb;
       z = -rb * sinq;
       cosq = cos(q);
     } else if (wvno == xkb) {
+      COUNT(ORC_DISP_S_EQUAL);
       cosq = 1.0;
       y = dpth;
       z = 0.0;
@@ -89,6 +106,7 @@ static double dltar4(const model *M, double wvno, double omga) {
       sex = q;
       fac = 0.0;
       if (q < 16) fac = exp(-2.0 * q);
+      else COUNT(ORC_DISP_S_SAT);
       cosq = (1.0 + fac) * 0.5;
       sinq = (1.0 - fac) * 0.5;
       y = sinq / rb;
@@ -97,6 +115,7 @@ static double dltar4(const model *M, double wvno, double omga) {
     double exa = pex + sex;
     double a0 = 0.0;
     if (exa < 60.0) a0 = exp(-exa);
+    else COUNT(ORC_DISP_A0_ZERO);
     double cpcq = cosp * cosq, cpy = cosp * y, cpz = cosp * z, cqw = cosq * w, cqx = cosq * x;
     double xy = x * y, xz = x * z, wy = w * y, wz = w * z;
     /* ---- dnka ---- */
@@ -138,7 +157,10 @@ static double dltar4(const model *M, double wvno, double omga) {
     double t1 = 0.0;
     for (int i = 0; i < 5; i++)
       if (fabs(ee[i]) > t1) t1 = fabs(ee[i]);
-    if (t1 < 1.e-40) t1 = 1.0;
+    if (t1 < 1.e-40) {
+      t1 = 1.0;
+      COUNT(ORC_DISP_T1_TINY);
+    }
     for (int i = 0; i < 5; i++) e[i] = ee[i] / t1;
   }
   return e[0];
@@ -156,8 +178,12 @@ static double nevill(const model *M, double t, double c1, double c2, double del1
   int nev = 1, nctrl = 1, m = 1;
   for (;;) {
     nctrl++;
-    if (nctrl >= 100) break;
+    if (nctrl >= 100) {
+      COUNT(ORC_DISP_NEV_NCTRL);
+      break;
+    }
     if (c3 < fmin(c1, c2) || c3 > fmax(c1, c2)) {
+      COUNT(ORC_DISP_NEV_C3_OUT);
       nev = 0;
       c3 = 0.5 * (c1 + c2);
       del3 = dltar4(M, omega / c3, omega);
@@ -175,6 +201,7 @@ static double nevill(const model *M, double t, double c1, double c2, double del1
     double ss1 = fabs(del1), s1 = (double)0.01f * ss1;
     double ss2 = fabs(del2), s2 = (double)0.01f * ss2;
     if (s1 > ss2 || s2 > ss1 || nev == 0) {
+      COUNT(ORC_DISP_NEV_BISECT);
       c3 = 0.5 * (c1 + c2);
       del3 = dltar4(M, omega / c3, omega);
       nev = 1;
@@ -196,6 +223,7 @@ static double nevill(const model *M, double t, double c1, double c2, double del1
         double denom = y[m] - y[j - 1];
         if (fabs(denom) < 1.0e-10 * fabs(y[m])) {
           bad = 1;
+          COUNT(ORC_DISP_NEV_DENOM);
           break;
         }
         x[j - 1] = (-y[j - 1] * x[j] + y[m] * x[j - 1]) / denom;
@@ -205,7 +233,10 @@ static double nevill(const model *M, double t, double c1, double c2, double del1
         del3 = dltar4(M, omega / c3, omega);
         nev = 2;
         m = m + 1;
-        if (m > 10) m = 10;
+        if (m > 10) {
+          m = 10;
+          COUNT(ORC_DISP_NEV_M_CAP);
+        }
       } else {
         c3 = 0.5 * (c1 + c2);
         del3 = dltar4(M, omega / c3, omega);
@@ -226,11 +257,15 @@ static int getsol(model *M, double t1, double *c1io, double clow, double dc, dou
   if (ifirst == 1) M->del1st = del1;
   double plmn = sgn(M->del1st) * sgn(del1);
   int idir = (ifirst == 1) ? 1 : (plmn >= 0.0 ? 1 : -1);
+  long long steps = 0; /* census only: points left behind, so the bracket's lower end is grid point `steps` of a first period */
+  COUNT(ORC_DISP_GETSOL);
+  if (idir < 0) COUNT(ORC_DISP_GETSOL_DOWN);
   for (;;) {
     c2 = (idir > 0) ? c1 + dc : c1 - dc;
     if (c2 <= clow) {
       idir = 1;
       c1 = clow;
+      COUNT(ORC_DISP_GETSOL_TURN);
       continue;
     }
     omega = TWOPI / t1;
@@ -238,12 +273,24 @@ static int getsol(model *M, double t1, double *c1io, double clow, double dc, dou
     if (sgn(del1) != sgn(del2)) break;
     c1 = c2;
     del1 = del2;
-    if (c1 < cm) return -1;
-    if (c1 >= ((double)betmx + dc)) return -1;
+    steps++;
+    if (ifirst == 1 && steps > census[ORC_DISP_FIRST_STEPS_MAX]) census[ORC_DISP_FIRST_STEPS_MAX] = steps;
+    if (c1 < cm) {
+      COUNT(ORC_DISP_EXIT_BELOW_CM);
+      return -1;
+    }
+    if (c1 >= ((double)betmx + dc)) {
+      COUNT(ORC_DISP_EXIT_WINDOW);
+      return -1;
+    }
   }
+  if (ifirst == 1 && steps > 512) COUNT(ORC_DISP_FIRST_OVER_512);
   c1 = nevill(M, t1, c1, c2, del1, del2);
   *c1io = c1;
-  if (c1 > (double)betmx) return -1;
+  if (c1 > (double)betmx) {
+    COUNT(ORC_DISP_EXIT_ROOT_ABOVE);
+    return -1;
+  }
   return 1;
 }
 

@@ -44,6 +44,39 @@ int orc_depthkernel(int nx, int ny, int nz, const float *vel, int kmax, const do
                     const float *depz, float minthk, double *pv, double *svs, double *svp,
                     double *srho);
 
+/* Branch census of orc_surfdisp96 / orc_depthkernel (disp.c): how often the guards of the secular function and the turns of the
+ * root search of surfdisp96 were taken since the last reset.  Counting only: no counter is read by the computation.  The
+ * per-layer counters count one finite layer of one secular-function evaluation (dltar4); the others count what their line says. */
+enum {
+  ORC_DISP_LAYERS = 0,      /* finite layers visited by dltar4                                                       */
+  ORC_DISP_P_OSC,           /* var: wvno < xka, oscillatory P part (c above the layer's Vp)                         */
+  ORC_DISP_P_EQUAL,         /* var: wvno == xka                                                                      */
+  ORC_DISP_P_SAT,           /* var: p >= 16, exp(-2p) taken as 0                                                     */
+  ORC_DISP_S_OSC,           /* var: wvno < xkb, oscillatory S part                                                   */
+  ORC_DISP_S_EQUAL,         /* var: wvno == xkb                                                                      */
+  ORC_DISP_S_SAT,           /* var: q >= 16, exp(-2q) taken as 0                                                     */
+  ORC_DISP_A0_ZERO,         /* var: pex + sex >= 60, exp(-(pex+sex)) taken as 0                                      */
+  ORC_DISP_T1_TINY,         /* normc: largest compound-vector entry < 1e-40, scale reset to 1                        */
+  ORC_DISP_OMEGA_CLAMP,     /* dltar4: omega < 1e-4 raised to 1e-4; per evaluation                                   */
+  ORC_DISP_NEV_C3_OUT,      /* nevill: the interpolated c3 left [c1, c2] and was replaced by the midpoint            */
+  ORC_DISP_NEV_BISECT,      /* nevill: restart by bisection (|del| ratio above 100, or nev = 0)                      */
+  ORC_DISP_NEV_DENOM,       /* nevill: |y(m) - y(j)| < 1e-10 |y(m)|, interpolation abandoned                         */
+  ORC_DISP_NEV_M_CAP,       /* nevill: m > 10 capped at 10                                                           */
+  ORC_DISP_NEV_NCTRL,       /* nevill: 100 passes without convergence                                                */
+  ORC_DISP_GETSOL,          /* getsol calls (one per period searched)                                                */
+  ORC_DISP_GETSOL_DOWN,     /* getsol: the search starts downwards (idir = -1, reversed dispersion)                  */
+  ORC_DISP_GETSOL_TURN,     /* getsol: c2 <= clow, turned round at the lower bound                                   */
+  ORC_DISP_EXIT_BELOW_CM,   /* getsol: iret = -1 through c1 < cm                                                     */
+  ORC_DISP_EXIT_WINDOW,     /* getsol: iret = -1 through c1 >= betmx + dc                                            */
+  ORC_DISP_EXIT_ROOT_ABOVE, /* getsol: iret = -1 through a refined root above betmx                                  */
+  ORC_DISP_FIRST_OVER_512,  /* first-period searches whose bracket's lower end lies beyond grid point 512            */
+  ORC_DISP_FIRST_STEPS_MAX, /* NOT a count: the largest number of dc steps a first-period search walked (the grid    */
+                            /* point of its bracket's lower end, or of the point at which it gave up)                */
+  ORC_DISP_NCOUNT
+};
+/* copies the ORC_DISP_NCOUNT values to out (may be NULL) and, if reset != 0, zeroes them afterwards */
+void orc_disp_census(long long *out, int reset);
+
 /* inv/CalSurfG.f90:49-53 (Brocher Vp(Vs), rho(Vp), fp32) */
 void orc_brocher(float vs, float *vp, float *rho);
 

@@ -20,6 +20,11 @@ NL, NP = 200, 60      # ORC_NL, ORC_NP
 TI_CENSUS = ("layers", "fac0", "dfac0", "ffunc", "gfunc", "h1func", "h2func", "down0", "ext80", "flush", "t1_up", "t1_down",
              "imag_rsv", "imag_rp", "tiny_nu")
 
+# the values of orc_disp_census, in the order of the enum in oracle.h (the last one is a maximum, not a count)
+DISP_CENSUS = ("layers", "p_osc", "p_equal", "p_sat", "s_osc", "s_equal", "s_sat", "a0_zero", "t1_tiny", "omega_clamp",
+               "nev_c3_out", "nev_bisect", "nev_denom", "nev_m_cap", "nev_nctrl", "getsol", "getsol_down", "getsol_turn",
+               "exit_below_cm", "exit_window", "exit_root_above", "first_over_512", "first_steps_max")
+
 f32 = np.float32
 f64 = np.float64
 i32 = np.int32
@@ -102,6 +107,14 @@ class Oracle:
         if rc < 0:
             raise RuntimeError(f"orc_depthkernel rc={rc}: more than {NL} knots or refined layers, or more than {NP} periods")
         return pv, s
+
+    def disp_census(self, reset=True):
+        """branch census of orc_surfdisp96 / orc_depthkernel since the last reset (oracle.h): {name: value}; reset=True zeroes the
+        counters afterwards"""
+        n = (C.c_longlong * len(DISP_CENSUS))()
+        self.lib.orc_disp_census.restype = None
+        self.lib.orc_disp_census(n, 1 if reset else 0)
+        return dict(zip(DISP_CENSUS, (int(v) for v in n)))
 
     # ---- eikonal ----
     def depthkernel_ti(self, vel, depz, t, minthk):

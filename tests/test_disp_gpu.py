@@ -93,16 +93,24 @@ def test_phase_only_and_low_velocity_zone(ctx, orc):
     within("LVZ pvRc max |d| km/s", np.abs(pv - pvo).max(), PV_ABS)
 
 
+def no_root_column():
+    """vel[10][1][2] on ROUGH_DEPZ: a fast lid over slow channels, whose search leaves the window (c1 >= betmx + dc,
+    inv/surfdisp96.f:470) from the fifth of the periods ROUGH_T on, beside an ordinary gradient"""
+    vel = np.zeros((len(ROUGH_DEPZ), 1, 2), np.float32)
+    vel[:, 0, 0] = [4.54608, 2.8430116, 3.6760201, 3.927757, 4.495318, 3.0541914, 3.4480517, 2.64218, 3.828745, 4.2]
+    vel[:, 0, 1] = 3.0 + 0.02 * ROUGH_DEPZ
+    return vel
+
+
 def test_root_failure_is_reported(ctx, orc):
-    """a column whose half-space is slower than the layers above has no fundamental-mode root in the
-    search window: the reference returns cg=0 for the remaining periods (inv/surfdisp96.f:342-348)"""
-    depz = np.array([0.0, 10.0, 20.0, 40.0], np.float32)
-    vel = np.zeros((4, 1, 2), np.float32)
-    vel[:, 0, 0] = [3.0, 3.5, 3.9, 4.3]
-    vel[:, 0, 1] = [4.6, 4.4, 3.0, 2.6]
-    t = np.array([5.0, 10.0, 20.0, 40.0, 60.0])
-    pv, _, nf = ctx.depthkernel(vel, depz, t, 2.0, kernels=False)
-    pvo, _ = orc.depthkernel(vel, depz, t, 2.0, kernels=False)
+    """a column whose search leaves the window before the sign changes has no fundamental-mode root there: the reference returns
+    cg=0 for the remaining periods (inv/surfdisp96.f:342-348).  The oracle loses the last four of the eight periods of column 0
+    (the column this test used before, a half-space slower than the layers above it, lost none: 0 == 0)"""
+    vel = no_root_column()
+    pv, _, nf = ctx.depthkernel(vel, ROUGH_DEPZ, ROUGH_T, 3.0, kernels=False)
+    pvo, _ = orc.depthkernel(vel, ROUGH_DEPZ, ROUGH_T, 3.0, kernels=False)
+    assert int((pvo == 0).sum()) == 4 and (pvo[4:, 0] == 0).all() and (pvo[:, 1] > 0).all()
+    assert nf > 0
     assert np.array_equal(pv == 0, pvo == 0)
     assert nf == int((pvo == 0).sum())
     within("root-failure columns pvRc max |d| km/s", np.abs(pv - pvo).max(), PV_ABS)
