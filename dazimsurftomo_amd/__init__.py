@@ -401,11 +401,12 @@ class Context:
         return x, ne.value, st
 
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
-                  ntemp=1, tmax=1.0, nswap=1):
+                  ntemp=1, tmax=1.0, nswap=1, aniso=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
         cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
         data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal).  ntemp > 1: parallel
-        tempering with ntemp rungs up to temperature tmax and a swap round every nswap steps (MonteCarlo.set_tempering)."""
+        tempering with ntemp rungs up to temperature tmax and a swap round every nswap steps (MonteCarlo.set_tempering).  aniso: a
+        dict of MonteCarlo.set_aniso's arguments (nthin, amap, wa, smooth, damp) switches the Gc/Gs posteriors on."""
         nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
         vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
         vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
@@ -420,6 +421,8 @@ class Context:
             mc.set_proposal(proposal)
         if ntemp != 1:
             mc.set_tempering(ntemp, tmax, nswap)
+        if aniso is not None:
+            mc.set_aniso(**aniso)
         return mc
 
     def ray_paths(self):
@@ -591,6 +594,55 @@ class MonteCarlo:
                                                            _ptr(swap_try), _ptr(swap_acc)))
         out.update(beta=beta, scale=scale, swap_try=swap_try, swap_acc=swap_acc)
         return out
+
+    def set_aniso(self, nthin, amap=None, wa=None, smooth=0.0, damp=0.0):
+        """Gc/Gs posteriors from the Vs chains (dazim_mc_set_aniso): amap[2][kmax][ny-2][nx-2] = the a1 then a2 maps, wa[kmax][ny-2]
+        [nx-2] = 1/sigma_a (0 = no data), smooth and damp those of column_lsq; run() then takes one sample per nthin recorded
+        steps.  nthin 0 switches it off again.  Refused once a step has been done"""
+        if nthin != 0 and not _is_torch(amap):
+            amap = np.ascontiguousarray(amap, np.float32).reshape(2, self.kmax, self.ny - 2, self.nx - 2)
+            wa = np.ascontiguousarray(wa, np.float32).reshape(self.kmax, self.ny - 2, self.nx - 2)
+        self.ctx._check(self.ctx.lib.dazim_mc_set_aniso(self.ctx._h, self._h, int(nthin), _ptr(amap, np.float32), _ptr(wa, np.float32),
+                                                        float(smooth), float(damp)))
+
+    def _ncolc(self):
+        nt = C.c_int(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_temper_state(self.ctx._h, self._h, C.byref(nt), None, None, None, None, None, None))
+        return self.ncs * (self.nchain // nt.value)
+
+    def aniso_step(self, lsen):
+        """one Gc/Gs sample (dazim_mc_aniso_step) from lsen[nlay][kmax][ncolc] (fp32; numpy or torch-cuda), the Lsen_Gsc of the
+        rung-0 chains' current states in cold-column order (sampled cell, then replica group)"""
+        shape = tuple(lsen.shape)
+        kmax, ncolc = (shape[1], shape[2]) if len(shape) == 3 and shape[0] == self.nlay else (self.kmax, -1)
+        if not _is_torch(lsen):
+            lsen = np.ascontiguousarray(lsen, np.float32)
+        self.ctx._check(self.ctx.lib.dazim_mc_aniso_step(self.ctx._h, self._h, int(kmax), C.c_int64(int(ncolc)), _ptr(lsen, np.float32)))
+
+    def aniso_state(self):
+        """copies of the Gc/Gs sums (dazim_mc_aniso_state): dict nthin, asum[5][nlay][ncolc] (sums of xc, xs, xc^2, xs^2, xc xs),
+        avar[nlay][ncolc], acnt[ncolc], skipped; dict nthin alone while it is off"""
+        nthin = C.c_int(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_aniso_state(self.ctx._h, self._h, C.byref(nthin), None, None, None, None))
+        if nthin.value < 1:
+            return dict(nthin=nthin.value)
+        ncolc = self._ncolc()
+        asum = np.zeros((5, self.nlay, ncolc), np.float64)
+        avar = np.zeros((self.nlay, ncolc), np.float64)
+        acnt = np.zeros(ncolc, np.int64)
+        sk = C.c_int64(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_aniso_state(self.ctx._h, self._h, None, _ptr(asum), _ptr(avar), _ptr(acnt), C.byref(sk)))
+        return dict(nthin=nthin.value, asum=asum, avar=avar, acnt=acnt, skipped=sk.value)
+
+    def aniso_result(self):
+        """Gc/Gs posterior statistics (dazim_mc_aniso_result): dict mean, std, std_between [2][nlay][ny-2][nx-2] (Gc then Gs),
+        cov_cs [nlay][ny-2][nx-2], nsamp [ny-2][nx-2]; std_between is the part of std that the Vs uncertainty contributes"""
+        shp = (self.nlay, self.ny - 2, self.nx - 2)
+        r = dict(mean=np.zeros((2,) + shp, np.float32), std=np.zeros((2,) + shp, np.float32),
+                 std_between=np.zeros((2,) + shp, np.float32), cov_cs=np.zeros(shp, np.float32), nsamp=np.zeros(shp[1:], np.int64))
+        self.ctx._check(self.ctx.lib.dazim_mc_aniso_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in
+                                                                                    ("mean", "std", "std_between", "cov_cs", "nsamp"))))
+        return r
 
     def step(self, pv, record):
         """one step on pv[kmax][ncol] (fp64; numpy or torch-cuda), the curves of proposals(); record 0 = burn-in"""

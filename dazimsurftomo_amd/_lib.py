@@ -95,5 +95,7 @@ def load():
     lib.dazim_mc_set_tempering.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int]
     lib.dazim_mc_temper_state.restype = C.c_int
     lib.dazim_mc_temper_state.argtypes = [C.c_void_p] * 9
+    lib.dazim_mc_set_aniso.restype = C.c_int
+    lib.dazim_mc_set_aniso.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float]
     _lib = lib
     return lib

@@ -21,22 +21,10 @@ __global__ void k_vs_kernels(long n, int kmax, long ncol, const float *__restric
   out[i] = dz_row_kernel(vels[k * ncol + c], svs[i], svp[i], srho[i]);
 }
 
-// entry (a, b) of L^T L for L the depth rule of TikhRegul (inv/TikhRegul.f90:2) restricted to one column of n knots: the first
-// and the last row hold the single entry 2, an inner row i holds 2 at i and -1 at i - 1 and i + 1
-__device__ double ltl(int n, int a, int b) {
-  auto L = [n](int i, int c) -> double {
-    if (i == 0 || i == n - 1) return c == i ? 2.0 : 0.0;
-    return c == i ? 2.0 : ((c == i - 1 || c == i + 1) ? -1.0 : 0.0);
-  };
-  double s = 0.0;
-  const int lo = max(max(a, b) - 1, 0), hi = min(min(a, b) + 1, n - 1);
-  for (int i = lo; i <= hi; i++) s += L(i, a) * L(i, b);
-  return s;
-}
-
 // One wavefront per inner cell (j, i) of the map, column (j+1)*nx + i+1 of the kernel table:
 //   min ||diag(w)(K x - r)||^2 + s2 ||L x||^2 + d2 ||x||^2  for each of the nrhs right-hand sides r,
-// by the normal equations (K^T W^2 K + s2 L^T L + d2 I) x = K^T W^2 r and their Cholesky factor.
+// by the normal equations (K^T W^2 K + s2 L^T L + d2 I) x = K^T W^2 r and their Cholesky factor: dz_column_solve of
+// dazim_internal.h, which k_mc_aniso of column_mc.hip calls too.
 // LDS: A [n][n] (the normal matrix, then its factor in the lower triangle), K [kmax][n], w^2 [kmax], w^2 r [nrhs][kmax],
 // b [nrhs][n] (right-hand sides, then solutions): at most 64 440 bytes for n = 63, kmax = 60, nrhs = 2.
 template <typename KT>
@@ -80,53 +68,7 @@ __global__ __launch_bounds__(CL_WAVE) void k_column_lsq(int nx, int ny, int n, i
     K[p * n + l] = (double)kern[(long)q * ncol + col];
   }
   __syncthreads();
-  for (int q = t; q < n * n; q += CL_WAVE) {      // lower triangle of the normal matrix
-    const int a = q / n, c = q - a * n;
-    if (c > a) continue;
-    double s = 0.0;
-    for (int p = 0; p < kmax; p++)
-      if (w2[p] != 0.0) s += w2[p] * K[p * n + a] * K[p * n + c];
-    s += s2 * ltl(n, a, c);
-    if (a == c) s += d2;
-    A[q] = s;
-  }
-  for (int q = t; q < nrhs * n; q += CL_WAVE) {
-    const int r = q / n, a = q - r * n;
-    double s = 0.0;
-    for (int p = 0; p < kmax; p++)
-      if (w2[p] != 0.0) s += wr[r * kmax + p] * K[p * n + a];
-    b[q] = s;
-  }
-  __syncthreads();
-  for (int c = 0; c < n; c++) {                   // right-looking Cholesky, column c
-    const double d = sqrt(A[c * n + c]);
-    if (t > c && t < n) A[t * n + c] /= d;
-    __syncthreads();
-    if (t == c) A[c * n + c] = d;
-    const int m = n - c - 1;
-    for (int q = t; q < m * m; q += CL_WAVE) {
-      const int a = c + 1 + q / m, e = c + 1 + q % m;
-      if (e <= a) A[a * n + e] -= A[a * n + c] * A[e * n + c];
-    }
-    __syncthreads();
-  }
-  for (int r = 0; r < nrhs; r++) {
-    double *br = b + r * n;
-    for (int c = 0; c < n; c++) {                 // L y = b
-      const double y = br[c] / A[c * n + c];
-      __syncthreads();
-      if (t > c && t < n) br[t] -= A[t * n + c] * y;
-      if (t == c) br[c] = y;
-      __syncthreads();
-    }
-    for (int c = n - 1; c >= 0; c--) {            // L^T x = y
-      const double y = br[c] / A[c * n + c];
-      __syncthreads();
-      if (t < c) br[t] -= A[c * n + t] * y;
-      if (t == c) br[c] = y;
-      __syncthreads();
-    }
-  }
+  dz_column_solve(t, n, kmax, nrhs, A, K, w2, wr, b, s2, d2);
   for (int q = t; q < nrhs * n; q += CL_WAVE) x[(long)q * ncell + cell] = (float)b[q];
   if (part && t < kmax)                           // r^2 and (r - K x)^2 of this cell, 0 where w = 0
     for (int r = 0; r < nrhs; r++) {

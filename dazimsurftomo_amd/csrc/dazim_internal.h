@@ -150,6 +150,82 @@ __device__ __forceinline__ double dz_row_kernel(float v, double svs, double svp,
   return svp * (double)coe_a + srho * (double)coe_rho + svs;
 }
 
+// entry (a, b) of L^T L for L the depth rule of TikhRegul (inv/TikhRegul.f90:2) restricted to one column of n knots: the first
+// and the last row hold the single entry 2, an inner row i holds 2 at i and -1 at i - 1 and i + 1
+__device__ __forceinline__ double dz_ltl(int n, int a, int b) {
+  auto L = [n](int i, int c) -> double {
+    if (i == 0 || i == n - 1) return c == i ? 2.0 : 0.0;
+    return c == i ? 2.0 : ((c == i - 1 || c == i + 1) ? -1.0 : 0.0);
+  };
+  double s = 0.0;
+  const int lo = max(max(a, b) - 1, 0), hi = min(min(a, b) + 1, n - 1);
+  for (int i = lo; i <= hi; i++) s += L(i, a) * L(i, b);
+  return s;
+}
+
+// The regularised column problem of dazim_column_lsq for one wavefront (lane t of 64) on its LDS arrays:
+// from K [kmax][n], w^2 [kmax] and w^2 r [nrhs][kmax] the normal matrix A = K^T W^2 K + s2 L^T L + d2 I (lower triangle of
+// A [n][n]) and b_r = K^T W^2 r_r, the right-looking Cholesky A = R R^T (R replaces the lower triangle; the strict upper triangle
+// of A is never touched) and the two substitutions per right-hand side, which leave the solutions in b [nrhs][n].  fp64, every
+// sum in a fixed order.  The caller has filled K, w2 and wr and passed a barrier.  Returns whether every pivot was finite and
+// > 0 (the same on every lane); the arithmetic does not depend on it.  k_column_lsq (column.hip) and k_mc_aniso (column_mc.hip)
+// both call it, so a cell's Gc/Gs from the depth program and the conditional mean of the Monte-Carlo program are the same bits.
+__device__ __forceinline__ bool dz_column_solve(int t, int n, int kmax, int nrhs, double *A, const double *K, const double *w2,
+                                                const double *wr, double *b, double s2, double d2) {
+  constexpr int W = 64;
+  for (int q = t; q < n * n; q += W) {            // lower triangle of the normal matrix
+    const int a = q / n, c = q - a * n;
+    if (c > a) continue;
+    double s = 0.0;
+    for (int p = 0; p < kmax; p++)
+      if (w2[p] != 0.0) s += w2[p] * K[p * n + a] * K[p * n + c];
+    s += s2 * dz_ltl(n, a, c);
+    if (a == c) s += d2;
+    A[q] = s;
+  }
+  for (int q = t; q < nrhs * n; q += W) {
+    const int r = q / n, a = q - r * n;
+    double s = 0.0;
+    for (int p = 0; p < kmax; p++)
+      if (w2[p] != 0.0) s += wr[r * kmax + p] * K[p * n + a];
+    b[q] = s;
+  }
+  __syncthreads();
+  bool ok = true;
+  for (int c = 0; c < n; c++) {                   // right-looking Cholesky, column c
+    const double p = A[c * n + c];
+    ok = ok && isfinite(p) && p > 0.0;
+    const double d = sqrt(p);
+    if (t > c && t < n) A[t * n + c] /= d;
+    __syncthreads();
+    if (t == c) A[c * n + c] = d;
+    const int m = n - c - 1;
+    for (int q = t; q < m * m; q += W) {
+      const int a = c + 1 + q / m, e = c + 1 + q % m;
+      if (e <= a) A[a * n + e] -= A[a * n + c] * A[e * n + c];
+    }
+    __syncthreads();
+  }
+  for (int r = 0; r < nrhs; r++) {
+    double *br = b + r * n;
+    for (int c = 0; c < n; c++) {                 // L y = b
+      const double y = br[c] / A[c * n + c];
+      __syncthreads();
+      if (t > c && t < n) br[t] -= A[t * n + c] * y;
+      if (t == c) br[c] = y;
+      __syncthreads();
+    }
+    for (int c = n - 1; c >= 0; c--) {            // L^T x = y
+      const double y = br[c] / A[c * n + c];
+      __syncthreads();
+      if (t < c) br[t] -= A[c * n + t] * y;
+      if (t == c) br[c] = y;
+      __syncthreads();
+    }
+  }
+  return ok;
+}
+
 // The refined layer table of a column model, refineGrid2LayerMdl (inv/CalSurfG.f90:2339-2365) in its fp32 expressions: the interval
 // between knots i and i + 1 (iv = i, 1-based) becomes nsub sublayers, sublayer j with the weights fm / den = (2j - 1) / (2 nsub) and the
 // thickness thk; the last row is the half-space (iv = 0).  dazim_dispersion_kernels and dazim_ti_kernels build their tables on it.

@@ -2,7 +2,7 @@
 ! random-walk Metropolis chains on one MI355X and reports the posterior mean, spread and credible interval of every knot (DESIGN.md
 ! section 14), where SurfDepthFromMaps_amd returns one linearised model.
 !
-!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax]]]]]]]]
+!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a]]]]]]]]]]]
 !
 ! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
 ! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
@@ -13,6 +13,15 @@
 ! ntemp 1 (default): no tempering.  ntemp > 1 (a divisor of nchain): parallel tempering, every ntemp chains of a cell form a ladder
 ! of temperatures 1 .. tmax (default 16, geometric) whose neighbours swap states after every step; only the nchain / ntemp chains
 ! at temperature 1 are recorded (more settings lines, the swap acceptance over cells and rung pairs in the summary).
+! aniso_thin 0 (default): Vs only, every file and byte as before.  aniso_thin > 0 (iso-mode F): the Gc/L, Gs/L posterior of every
+! cell and knot from the chains themselves -- conditional on a Vs column the Gc/Gs posterior is the Gaussian of SurfDepthFromMaps_amd's
+! column solve, and after every aniso_thin recorded steps its mean and covariance at the chains' current states join running sums
+! (dazim_mc_set_aniso).  It reads period_Azm_tomo_map.inv (columns 8, 9) as SurfDepthFromMaps_amd does; weights 1/sigma_a (default
+! sigma_c) where DWS > 0; smooth_gcs defaults to para.in's Gc/Gs smoothing weight, the damping is para.in's.  Two more files:
+!   Gc_Gs_posterior_mc.dat       per inner cell and sampled knot: lon lat depth, Gc mean std, Gs mean std, the std_between of Gc and
+!                                of Gs (the part of each std that comes from not knowing Vs), amplitude and its std, fast axis (degrees)
+!                                and its std (write_azimuthal's arithmetic, the stds by the delta method), samples
+!   Gc_Gs_model_mc.inv           the means on the posterior-mean Vs, as Gc_Gs_model.inv
 !
 ! Outputs (names of their own, so that the three programs can share a directory):
 !   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
@@ -30,7 +39,11 @@ program SurfDepthMC_amd
   character(len=100) :: inputfile, logfile
   type(para_t) :: p
   logical :: ex
-  integer :: nx, ny, nz, kmax, nsample, nchain, proposal, ntemp, ncold
+  integer :: nx, ny, nz, kmax, nsample, nchain, proposal, ntemp, ncold, aniso_thin
+  real :: smooth_gcs, sigma_a, t_aniso, gc, gs, g2, vcc, vss, vcs, amp, samp, sang
+  real, allocatable :: amap(:, :, :, :), wa(:, :, :), gmean(:, :, :, :), gstd(:, :, :, :), gstdb(:, :, :, :), gcov(:, :, :)
+  integer(c_int64_t), allocatable :: nsamp(:, :)
+  integer :: npass, nskip
   integer, parameter :: nswap = 1
   real :: tmax
   real(c_double), allocatable, target :: beta(:)
@@ -55,7 +68,7 @@ program SurfDepthMC_amd
   write (*, *) '                       SurfDepthMC'
   write (*, *)
   if (command_argument_count() < 1) error stop &
-    'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax]]]]]]]]'
+    'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a]]]]]]]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -73,6 +86,11 @@ program SurfDepthMC_amd
   call optional_arg(7, proposal)
   call optional_arg(8, ntemp)
   call optional_arg(9, tmax)
+  aniso_thin = 0; smooth_gcs = p%weightGcs
+  call optional_arg(10, aniso_thin)
+  call optional_arg(11, smooth_gcs)
+  sigma_a = sigma_c
+  call optional_arg(12, sigma_a)
   if (nsample < 1) error stop 'nsample must be at least 1'
   if (nchain < 1 .or. nchain > 64) error stop 'nchain must be 1..64'
   if (width < 0) error stop 'width must not be negative'
@@ -81,6 +99,14 @@ program SurfDepthMC_amd
   if (ntemp < 1 .or. ntemp > nchain) error stop 'ntemp must be 1..nchain and divide nchain'
   if (mod(nchain, ntemp) /= 0) error stop 'ntemp must be 1..nchain and divide nchain'
   if (ntemp > 1 .and. .not. (tmax > 1 .and. tmax <= huge(tmax))) error stop 'tmax must be a finite temperature above 1'
+  if (aniso_thin < 0) error stop 'aniso_thin must not be negative'
+  if (aniso_thin > 0 .and. p%iso_mod) then
+    write (*, '(a)') ' ERROR: aniso_thin > 0 needs the 2-psi maps of iso-mode F; para.in has iso-mode T'
+    error stop 'aniso_thin > 0 with iso-mode T'
+  end if
+  if (aniso_thin > 0 .and. sigma_a <= 0) error stop 'sigma_a must be positive'
+  if (aniso_thin > 0 .and. (smooth_gcs < 0 .or. (smooth_gcs == 0 .and. p%damp == 0))) error stop &
+    'smooth_gcs must not be negative, nor 0 together with para.in''s damping'
   ncold = nchain/ntemp
   nlay = nz - 1
   ncell = (nx - 2)*(ny - 2)
@@ -107,6 +133,8 @@ program SurfDepthMC_amd
     if (proposal == 1) write (q, '(a)') ' proposal 1: shaped by the chains'' covariance, learnt per cell during burn-in'
     if (ntemp > 1) write (q, '(a,i3,a,f9.3,a,i3,a,i3,a)') ' parallel tempering:', ntemp, ' rungs up to T =', tmax, &
       ', a swap round every', nswap, ' step(s);', ncold, ' chains per cell at T = 1 are recorded'
+    if (aniso_thin > 0) write (q, '(a,i6,a,f8.3,a,f8.3,a,f8.4)') ' Gc/Gs posteriors: one sample of every recorded chain per', &
+      aniso_thin, ' recorded steps;  smoothing', smooth_gcs, '  damping', p%damp, '  sigma_a (km/s)', sigma_a
   end do
 
   call read_mod('MOD', p, depz, vsf)
@@ -115,6 +143,12 @@ program SurfDepthMC_amd
   allocate (cmap(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
   call read_map('period_phaseV_map.dat', p, 4, 4, cmap, .true.)
   call coverage_weights(p, sigma_c, wcov)
+  if (aniso_thin > 0) then
+    allocate (amap(nx - 2, ny - 2, kmax, 2), wa(nx - 2, ny - 2, kmax))
+    call read_map('period_Azm_tomo_map.inv', p, 9, 8, amap(:, :, :, 1), .true.)
+    call read_map('period_Azm_tomo_map.inv', p, 9, 9, amap(:, :, :, 2), .false.)
+    wa = merge(1.0/sigma_a, 0.0, wcov /= 0.0)
+  end if
 
   ! ---- the prior box per cell and knot -------------------------------------------------------------------------------------------
   allocate (vmin(nx - 2, ny - 2, nlay), vmax(nx - 2, ny - 2, nlay))
@@ -147,6 +181,8 @@ program SurfDepthMC_amd
       write (q, '(a,64f8.3)') ' ladder, temperatures 1 / beta:', (1.0d0/beta(i), i=1, ntemp)
     end do
   end if
+  if (aniso_thin > 0) call dazim_check(dazim_mc_set_aniso(dazim_handle, mc, aniso_thin, amap, wa, smooth_gcs, p%damp), &
+                                       'Gc/Gs posteriors')
   call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
   t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
   t_disp = real(dazim_last_kernel_seconds(dazim_handle, 'mc.disp'//c_null_char))
@@ -157,6 +193,18 @@ program SurfDepthMC_amd
   call dazim_check(dazim_mc_result(dazim_handle, mc, mean, std, qq, best, rhat, acc, chi2b), 'posterior statistics')
   if (ntemp > 1) call dazim_check(dazim_mc_temper_state(dazim_handle, mc, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
                                                         c_null_ptr, c_loc(swap_try), c_loc(swap_acc)), 'swap counts')
+  if (aniso_thin > 0) then
+    t_aniso = real(dazim_last_kernel_seconds(dazim_handle, 'mc.aniso'//c_null_char))
+    npass = nint(dazim_last_kernel_seconds(dazim_handle, 'mc.aniso_passes'//c_null_char))
+    nskip = nint(dazim_last_kernel_seconds(dazim_handle, 'mc.aniso_skipped'//c_null_char))
+    allocate (gmean(nx - 2, ny - 2, nlay, 2), gstd(nx - 2, ny - 2, nlay, 2), gstdb(nx - 2, ny - 2, nlay, 2))
+    allocate (gcov(nx - 2, ny - 2, nlay), nsamp(nx - 2, ny - 2))
+    if (npass > 0) then
+      call dazim_check(dazim_mc_aniso_result(dazim_handle, mc, gmean, gstd, gstdb, gcov, nsamp), 'Gc/Gs posterior statistics')
+    else   ! fewer recorded steps than aniso_thin: no sample
+      gmean = 0; gstd = 0; gstdb = 0; gcov = 0; nsamp = 0
+    end if
+  end if
   call dazim_check(dazim_mc_free(dazim_handle, mc), 'Monte-Carlo chains')
 
   ! ---- the curves of the mean and of the best model ------------------------------------------------------------------------------
@@ -193,6 +241,19 @@ program SurfDepthMC_amd
     write (q, '(a,f9.2,a,f9.2,a,f9.3,a)') ' run', t_run, ' s (dispersion calls', t_disp, ' s, step kernels', t_step, ' s)'
     if (proposal == 1) write (q, '(a,i8,a,i8)') ' cells with an adapted covariance:', ncov, ' of', ns
   end do
+  if (aniso_thin > 0) then
+    nr = count(spread(spread(nsamp > 0, 3, nlay), 4, 2) .and. gstd > 0)
+    allocate (sorted(max(nr, 1)))
+    sorted = 0
+    if (nr > 0) sorted(1:nr) = pack(gstdb/max(gstd, tiny(1.0)), spread(spread(nsamp > 0, 3, nlay), 4, 2) .and. gstd > 0)
+    call sort(sorted)
+    do q = 6, 66, 60
+      write (q, '(a,i7,a,i9,a,f9.2,a)') ' Gc/Gs passes', npass, '  skipped states', nskip, '  in', t_aniso, ' s'
+      write (q, '(a,f8.4)') ' Gc/Gs: median over (cell, knot) of std_between / std, the share of the Vs uncertainty:', &
+        sorted(max(1, (nr + 1)/2))
+    end do
+    deallocate (sorted)
+  end if
   if (ntemp > 1 .and. ns > 0) then
     nr = count(swap_try > 0)
     allocate (sorted(max(nr, 1)))
@@ -242,6 +303,30 @@ program SurfDepthMC_amd
   end do
   close (64)
   call write_phase_map('period_phaseV_mc.dat', p, inner_cells(nx, ny, kmax, pvm))
+  if (aniso_thin > 0) then
+    call write_azimuthal('Gc_Gs_model_mc.inv', p, depz, vmc, gmean(:, :, :, 1), gmean(:, :, :, 2))
+    open (64, file='Gc_Gs_posterior_mc.dat')
+    do k = 1, nlay
+      do j = 1, ny - 2
+        do i = 1, nx - 2
+          ! amplitude and fast axis as write_azimuthal forms them; their stds by the delta method from the Gc/Gs covariance
+          gc = gmean(i, j, k, 1); gs = gmean(i, j, k, 2)
+          vcc = gstd(i, j, k, 1)**2; vss = gstd(i, j, k, 2)**2; vcs = gcov(i, j, k)
+          g2 = gc**2 + gs**2
+          amp = 0.5*sqrt(g2)
+          samp = 0; sang = 0
+          if (g2 > 0) then
+            samp = 0.5*sqrt(max((gc**2*vcc + 2*gc*gs*vcs + gs**2*vss)/g2, 0.0))
+            sang = sqrt(max(0.25*(gs**2*vcc - 2*gc*gs*vcs + gc**2*vss)/g2**2, 0.0))/3.1415926535898*180
+          end if
+          write (64, '(3f10.4,6f12.6,f12.6,f12.6,2f10.3,i9)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, depz(k), gc, &
+            gstd(i, j, k, 1), gs, gstd(i, j, k, 2), gstdb(i, j, k, 1), gstdb(i, j, k, 2), amp, samp, fast_axis(gc, gs), sang, &
+            nsamp(i, j)
+        end do
+      end do
+    end do
+    close (64)
+  end if
   open (78, file='cell_mc.dat')
   do j = 1, ny - 2
     do i = 1, nx - 2

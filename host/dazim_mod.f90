@@ -38,7 +38,8 @@ module dazim_mod
   public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
   public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
-            dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds
+            dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds, &
+            dazim_mc_set_aniso, dazim_mc_aniso_step, dazim_mc_aniso_state, dazim_mc_aniso_result
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -288,6 +289,33 @@ module dazim_mod
         bind(C, name="dazim_mc_temper_state")
       import
       type(c_ptr), value :: ctx, mc, ntemp, tmax, nswap, beta, scale, swap_try, swap_acc
+    end function
+    ! Gc/Gs posteriors from the chains: amap(nx-2, ny-2, kmax, 2), wa(nx-2, ny-2, kmax); results (nx-2, ny-2, nlay, 2), cov_cs
+    ! (nx-2, ny-2, nlay), nsamp(nx-2, ny-2)
+    integer(c_int) function dazim_mc_set_aniso(ctx, mc, nthin, amap, wa, smooth, damp) bind(C, name="dazim_mc_set_aniso")
+      import
+      type(c_ptr), value :: ctx, mc
+      integer(c_int), value :: nthin
+      real(c_float) :: amap(*), wa(*)
+      real(c_float), value :: smooth, damp
+    end function
+    integer(c_int) function dazim_mc_aniso_step(ctx, mc, kmax, ncolc, lsen) bind(C, name="dazim_mc_aniso_step")
+      import
+      type(c_ptr), value :: ctx, mc, lsen
+      integer(c_int), value :: kmax
+      integer(c_int64_t), value :: ncolc
+    end function
+    ! every argument after mc may be c_null_ptr (c_loc of a variable or an array otherwise)
+    integer(c_int) function dazim_mc_aniso_state(ctx, mc, nthin, asum, avar, acnt, skipped) bind(C, name="dazim_mc_aniso_state")
+      import
+      type(c_ptr), value :: ctx, mc, nthin, asum, avar, acnt, skipped
+    end function
+    integer(c_int) function dazim_mc_aniso_result(ctx, mc, mean, std, std_between, cov_cs, nsamp) &
+        bind(C, name="dazim_mc_aniso_result")
+      import
+      type(c_ptr), value :: ctx, mc
+      real(c_float) :: mean(*), std(*), std_between(*), cov_cs(*)
+      integer(c_int64_t) :: nsamp(*)
     end function
     integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
         bind(C, name="dazim_phase_map_update")

@@ -355,6 +355,51 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
  *   factor every rung's scale becomes 1.0f / sqrtf((float)nlay).  The clamps of s being the same, the bounds on the number of
  *   reflections above hold at every rung.
  *   Next proposals: the formulas above with s the scale of the chain's rung.
+ * Gc/Gs posteriors (dazim_mc_set_aniso; without it, or with nthin = 0, every launch and every result is the one above, unchanged):
+ *   the 2-psi terms a1, a2 of a cell are linear in Gc/L, Gs/L, so conditional on one Vs column their posterior
+ *   under Gaussian data errors and dazim_column_lsq's quadratic regulariser is Gaussian with mean x^(Vs) = dazim_column_lsq's solution
+ *   and covariance C(Vs) = the inverse of its normal matrix.  Averaging both over thinned states of the rung-0 chains gives the
+ *   marginal: mean = E[x^], Var = E[diag C] + Var[x^]; the second term is the share of the Vs uncertainty.  Nothing is sampled.
+ *   Notation: ncold = nchain / ntemp, ncolc = sampled cells * ncold; rung-0 chain g of sampled cell cs is cold column cs*ncold + g,
+ *   chain ch = g*ntemp, column cs*nchain + ch of the handle.
+ *   dazim_mc_set_aniso: amap [2][kmax][ny-2][nx-2] = a1 then a2 (the rhs layout of dazim_column_lsq with nrhs = 2), wa [kmax][ny-2]
+ *   [nx-2] = 1/sigma_a per period and cell, 0 = no data (host or device); smooth, damp as in dazim_column_lsq.  nthin >= 1 switches
+ *   the sums on, nthin = 0 restores the default (the arrays are not looked at then).  It may come before or after
+ *   dazim_mc_set_proposal and dazim_mc_set_tempering; ntemp is the handle's when the first sample is taken.  The handle then holds,
+ *   all 0: asum [5][nlay][ncolc] fp64 (sums of xc, xs, xc^2, xs^2, xc*xs), avar [nlay][ncolc] fp64 (sum of diag C), acnt [ncolc] int64
+ *   and the count skipped (int64; kept per cold column and added up when it is asked for).  DAZIM_E_BAD_ARG for nthin < 0, a
+ *   non-finite amap or wa, a negative smooth or damp, smooth == damp == 0, a handle of another context, or once a step has been done.
+ *   dazim_mc_aniso_step: one sample from the chains' current states.  lsen [nlay][kmax][ncolc] fp32 (host or device) = Lsen_Gsc of
+ *   the cold columns' states, what dazim_ti_kernels writes for nx = ncolc, ny = 1; from any source, as dazim_mc_step's curves.  A
+ *   cold column whose chain has chi2 = +inf is skipped: skipped += 1, nothing else.  For every other cold column, K its kmax x nlay
+ *   slice of lsen, w, r1, r2 its cell's wa and amap, s2 = (double)smooth^2, d2 = (double)damp^2, all in fp64:
+ *     w2_p = (double)w_p * (double)w_p, wr_rp = w2_p * (double)r_rp (0 where w_p == 0);
+ *     A(a,c) = sum_p w2_p * K(p,a) * K(p,c) (p order, left to right, periods with w2_p == 0 left out), + s2 * (L^T L)(a,c), + d2 when
+ *     a == c; b_r(a) = sum_p wr_rp * K(p,a) likewise: dazim_column_lsq's sums in its order (one device function serves both).
+ *     Its right-looking Cholesky A = R R^T (column c: d = sqrt(A(c,c)), the column below / d, then A(a,e) -= A(a,c) * A(e,c) on the
+ *     trailing triangle) and its two substitutions give xc, xs, kept in fp64.
+ *     Column k of R^-1: y_k = 1 / R(k,k), y_i = -(sum_{j=k..i-1} R(i,j) * y_j) / R(i,i) for i > k, the sum in j order;
+ *     (A^-1)(k,k) = sum_{i>=k} y_i^2 in i order.
+ *     asum[0..4][k][col] += xc_k, xs_k, xc_k^2, xs_k^2, xc_k * xs_k; avar[k][col] += (A^-1)(k,k); acnt[col] += 1.
+ *   A row of K that is all 0 (dazim_ti_kernels writes one where the state's curve has no root) adds nothing to A or b.  A pivot that
+ *   is not finite and > 0 cannot occur with smooth > 0 or damp > 0 and finite inputs; if one does the column is skipped and counted,
+ *   nothing is added.  DAZIM_E_BAD_ARG before the handle's first step, when Gc/Gs is not switched on, for a kmax or ncolc that is
+ *   not the handle's, for a handle of another context.
+ *   dazim_mc_aniso_state: nthin, and copies (each nullable, host or device; skipped host) of asum, avar, acnt and skipped.
+ *   DAZIM_E_BAD_ARG when Gc/Gs is off and an array is requested.
+ *   dazim_mc_aniso_result, per sampled cell, every sum over its cold columns in column order inside one lane, fp64: n = sum acnt,
+ *   S_e = sum asum[e], Sv = sum avar; m_c = S_0 / n, m_s = S_1 / n, between_c = max(S_2 / n - m_c^2, 0), between_s likewise from S_3,
+ *   within = Sv / n.  mean [2][nlay][ny-2][nx-2] = m_c then m_s, std = sqrt(within + between), std_between = sqrt(between) (both
+ *   [2][nlay][ny-2][nx-2]), cov_cs [nlay][ny-2][nx-2] = S_4 / n - m_c * m_s, nsamp [ny-2][nx-2] (int64) = n; each rounded to fp32
+ *   once.  Cells without Vs data: all 0.  A sampled cell with n = 0: mean 0, std, std_between and cov_cs NaN.  Refused before the
+ *   first sample.
+ *   dazim_mc_run with Gc/Gs on: after every recorded step whose count over the handle's life is a multiple of nthin, one pass: the
+ *   rung-0 states into a compact [nz][ncolc] table, dazim_dispersion_kernels on it (nx = ncolc, ny = 1, curves only, a curve buffer
+ *   of its own), dazim_ti_kernels on the same columns, then the sample above.  Where the TI scratch of all cold columns would pass
+ *   2 GiB the pass goes through the columns in blocks of whole cells (option "mc.aniso_block_cells" > 0 sets the cells per block);
+ *   every column's arithmetic is its own, so the results do not depend on the blocks.  The pass reads the chains and writes only
+ *   its own arrays: the Vs chain, its records and its random numbers are bit for bit what they are without it.  Stats: "mc.aniso"
+ *   (seconds of the run's passes), "mc.aniso_passes", "mc.aniso_skipped" (0 when Gc/Gs is off).
  * dazim_mc_create: vel0 [nz][ny][nx] (the last knot; the result of cells without data), vmin, vmax [nlay][ny-2][nx-2], cobs, wdat
  *   [kmax][ny-2][nx-2] (the layout of dazim_column_lsq), step = the initial s, nadapt >= 1.  Draws the start models.  Refused
  *   (DAZIM_E_BAD_ARG): nchain outside 1..64, nlay outside 1..63, kmax outside 1..60, nbin < 2, a non-finite vmin, vmax, cobs or
@@ -398,6 +443,10 @@ int dazim_mc_cov_state(dazim_ctx *ctx, dazim_mc *mc, int *kind, int64_t *cov_n, 
 int dazim_mc_set_tempering(dazim_ctx *ctx, dazim_mc *mc, int ntemp, float tmax, int nswap);
 int dazim_mc_temper_state(dazim_ctx *ctx, dazim_mc *mc, int *ntemp, float *tmax, int *nswap, double *beta, float *scale,
                           int64_t *swap_try, int64_t *swap_acc);
+int dazim_mc_set_aniso(dazim_ctx *ctx, dazim_mc *mc, int nthin, const float *amap, const float *wa, float smooth, float damp);
+int dazim_mc_aniso_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncolc, const float *lsen);
+int dazim_mc_aniso_state(dazim_ctx *ctx, dazim_mc *mc, int *nthin, double *asum, double *avar, int64_t *acnt, int64_t *skipped);
+int dazim_mc_aniso_result(dazim_ctx *ctx, dazim_mc *mc, float *mean, float *std, float *std_between, float *cov_cs, int64_t *nsamp);
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);
 int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
                  int64_t *n_no_root);

@@ -2,6 +2,7 @@
 
     python tools/mc_step.py [--steps S] [--big N] [--proposal K] [--ntemp R [--tmax T]]
     python tools/mc_step.py --program [--dir D] [--proposal K] [--ntemp R [--tmax T]]
+    python tools/mc_step.py --aniso N [--steps S] [--big N]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -18,7 +19,12 @@ burn-in steps instead of every 50, so that its S/2 burn-in steps hold factorisat
 "cov_cells" counts the cells that did.
 
 --ntemp R: parallel tempering with R rungs up to temperature T (dazim_mc_set_tempering; default T 16, a swap round every step)
-instead of the default 1, no tempering; "swap_min" and "swap_med" are the run's swap acceptances over cells and rung pairs."""
+instead of the default 1, no tempering; "swap_min" and "swap_med" are the run's swap acceptances over cells and rung pairs.
+
+--aniso N: the Gc/Gs pass (dazim_mc_set_aniso, one pass per N recorded steps: gather, dispersion, TI kernels, column solves) at S-256
+with 32 chains and on the big grid with 8: after a warm-up run that holds one pass, three runs of S recorded steps each; reports
+the median over the runs of the ms of one pass ("mc.aniso" / "mc.aniso_passes") beside the ms of one step without its share of the
+passes (profiles/depth_mc_aniso.md)."""
 import argparse
 import json
 import os
@@ -59,6 +65,38 @@ def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax):
             "mc_step_ms_per_step": ms(stp), "other_ms_per_step": ms(wall - disp - stp), "mc_step_share": stp / wall,
             "curves_per_s": mc.ncol * steps / wall, "accept": ctx.stat("mc.accept"), "no_root": nr,
             "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
+
+
+def aniso_case(ctx, n, nchain, steps, nthin):
+    import bench
+    bench.NX = bench.NY = n
+    vel = bench.s256_model().astype(np.float32)
+    depz, periods = np.asarray(bench.DEPZ, np.float32), np.asarray(bench.PERIODS, np.float64)
+    nz, kmax, nlay = len(depz), len(periods), len(depz) - 1
+    pv, _, _ = ctx.depthkernel(vel, depz, periods, bench.MINTHK, kernels=False)
+    lsen = ctx.ti_kernels(vel, depz, periods, bench.MINTHK, pv).reshape(nlay, kmax, n, n)[:, :, 1:-1, 1:-1].astype(np.float64)
+    g = np.stack([0.02 * np.cos(0.4 * np.arange(nlay)), 0.015 * np.sin(0.3 * np.arange(nlay))])
+    amap = np.einsum("lpji,rl->rpji", lsen, g).astype(np.float32)
+    cobs = pv.reshape(kmax, n, n)[:, 1:-1, 1:-1].astype(np.float32)
+    inner = vel[:nlay, 1:-1, 1:-1]
+    vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
+    wdat = np.full((kmax, n - 2, n - 2), 100.0, np.float32)
+    mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat,
+                       aniso=dict(nthin=nthin, amap=amap, wa=wdat, smooth=2.0, damp=0.0))
+    mc.run(depz, bench.MINTHK, periods, 5, nthin)            # warm-up with one pass: code objects, scratch buffers
+    pass_ms, step_ms = [], []
+    for _ in range(3):
+        mc.run(depz, bench.MINTHK, periods, 0, steps)
+        wall, an, npass = ctx.stat("mc"), ctx.stat("mc.aniso"), ctx.stat("mc.aniso_passes")
+        pass_ms.append(1e3 * an / max(npass, 1))
+        step_ms.append(1e3 * (wall - an) / steps)
+    r = mc.aniso_result()
+    mc.free()
+    return {"grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots ({nlay} sampled), {kmax} periods", "nchain": nchain,
+            "aniso_thin": nthin, "steps_per_run": steps, "passes_per_run": int(npass), "cold_columns": mc.ncol,
+            "aniso_ms_per_pass": pass_ms, "aniso_ms_per_pass_median": float(np.median(pass_ms)),
+            "ms_per_step_without_passes": step_ms, "ms_per_step_median": float(np.median(step_ms)),
+            "skipped": int(ctx.stat("mc.aniso_skipped")), "median_std_between_over_std": float(np.nanmedian(r["std_between"] / r["std"]))}
 
 
 PARA = """cccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccc
@@ -132,8 +170,14 @@ def main():
     ap.add_argument("--proposal", type=int, default=0, choices=(0, 1))
     ap.add_argument("--ntemp", type=int, default=1)
     ap.add_argument("--tmax", type=float, default=16.0)
+    ap.add_argument("--aniso", type=int, default=0)
     a = ap.parse_args()
     ctx = dz.Context(0)
+    if a.aniso > 0:
+        for n, nchain in ((54, 32), (a.big, 8)):
+            print(json.dumps(aniso_case(ctx, n, nchain, a.steps, a.aniso)), flush=True)
+        ctx.close()
+        return
     if a.program:
         with tempfile.TemporaryDirectory() as tmp:
             print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal, a.ntemp, a.tmax)), flush=True)
