@@ -401,12 +401,13 @@ class Context:
         return x, ne.value, st
 
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
-                  ntemp=1, tmax=1.0, nswap=1, aniso=None):
+                  ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
         cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
         data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal).  ntemp > 1: parallel
         tempering with ntemp rungs up to temperature tmax and a swap round every nswap steps (MonteCarlo.set_tempering).  aniso: a
-        dict of MonteCarlo.set_aniso's arguments (nthin, amap, wa, smooth, damp) switches the Gc/Gs posteriors on."""
+        dict of MonteCarlo.set_aniso's arguments (nthin, amap, wa, smooth, damp) switches the Gc/Gs posteriors on.  noise: (a0, b0)
+        makes the data-noise scale of every cell an unknown with the prior lambda^2 ~ InverseGamma(a0, b0) (MonteCarlo.set_noise)."""
         nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
         vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
         vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
@@ -423,6 +424,8 @@ class Context:
             mc.set_tempering(ntemp, tmax, nswap)
         if aniso is not None:
             mc.set_aniso(**aniso)
+        if noise is not None:
+            mc.set_noise(*noise)
         return mc
 
     def ray_paths(self):
@@ -642,6 +645,34 @@ class MonteCarlo:
                  std_between=np.zeros((2,) + shp, np.float32), cov_cs=np.zeros(shp, np.float32), nsamp=np.zeros(shp[1:], np.int64))
         self.ctx._check(self.ctx.lib.dazim_mc_aniso_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in
                                                                                     ("mean", "std", "std_between", "cov_cs", "nsamp"))))
+        return r
+
+    def set_noise(self, a0, b0=1.0):
+        """hierarchical data noise (dazim_mc_set_noise): the data std of a cell becomes lambda / w with lambda^2 ~ InverseGamma(a0,
+        b0) a priori; lambda is integrated out of the chains' target and its posterior comes back from noise_result().  a0 0 is the
+        default, the fixed noise level.  Refused once a step has been done"""
+        self.ctx._check(self.ctx.lib.dazim_mc_set_noise(self.ctx._h, self._h, float(a0), float(b0)))
+
+    def noise_state(self):
+        """the prior and, while the mode is on, copies of the noise record (dazim_mc_noise_state): dict a0, b0, nsum[2][ncol] (sums
+        of sqrt(B) and B over the recorded states), ncnt[ncol]; dict a0 = 0, b0 = 0 alone while it is off"""
+        a0, b0 = C.c_float(0), C.c_float(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_noise_state(self.ctx._h, self._h, C.byref(a0), C.byref(b0), None, None))
+        out = dict(a0=a0.value, b0=b0.value)
+        if a0.value == 0:
+            return out
+        nsum = np.zeros((2, self.ncol), np.float64)
+        ncnt = np.zeros(self.ncol, np.int64)
+        self.ctx._check(self.ctx.lib.dazim_mc_noise_state(self.ctx._h, self._h, None, None, _ptr(nsum), _ptr(ncnt)))
+        out.update(nsum=nsum, ncnt=ncnt)
+        return out
+
+    def noise_result(self):
+        """the posterior of the noise scale per inner cell (dazim_mc_noise_result): dict lam_mean, lam_std [ny-2][nx-2] (fp32; the
+        data std of the cell is lam * sigma) and ndata [ny-2][nx-2] (int32), the cell's periods with data"""
+        shp = (self.ny - 2, self.nx - 2)
+        r = dict(lam_mean=np.zeros(shp, np.float32), lam_std=np.zeros(shp, np.float32), ndata=np.zeros(shp, np.int32))
+        self.ctx._check(self.ctx.lib.dazim_mc_noise_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in ("lam_mean", "lam_std", "ndata"))))
         return r
 
     def step(self, pv, record):

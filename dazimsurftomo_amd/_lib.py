@@ -97,5 +97,11 @@ def load():
     lib.dazim_mc_temper_state.argtypes = [C.c_void_p] * 9
     lib.dazim_mc_set_aniso.restype = C.c_int
     lib.dazim_mc_set_aniso.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float]
+    lib.dazim_mc_set_noise.restype = C.c_int
+    lib.dazim_mc_set_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float]
+    lib.dazim_mc_noise_state.restype = C.c_int
+    lib.dazim_mc_noise_state.argtypes = [C.c_void_p] * 6
+    lib.dazim_mc_noise_result.restype = C.c_int
+    lib.dazim_mc_noise_result.argtypes = [C.c_void_p] * 5
     _lib = lib
     return lib

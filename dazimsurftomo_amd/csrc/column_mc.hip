@@ -17,6 +17,11 @@
 // (Rao-Blackwellisation).  k_mc_gather copies the rung-0 states into a compact table, k_mc_aniso solves one wavefront per such
 // column with dz_column_solve and adds to the column's own sums, k_mc_aniso_final reduces them per cell.  The pass only reads the
 // chains.
+//
+// Hierarchical data noise (dazim_mc_set_noise): the data std of a cell is lambda / w_p with lambda^2 ~ InverseGamma(a0, b0), and
+// lambda is integrated out in closed form: k_mc_step<KIND, TEMPER, 1> takes every decision on the energy X = 2 a log(b0 + chi^2 / 2)
+// in place of chi^2 (mc_energy), each recorded rung-0 lane adds sqrt(B) and B = b0 + chi^2 / 2 of its state to its own column, and
+// k_mc_noise_final turns those sums into the posterior mean and std of lambda per cell (Rao-Blackwellisation again).
 #include "dazim_internal.h"
 
 #include <algorithm>
@@ -95,7 +100,19 @@ struct McDev {
   float *tscale;               // [ncs][ntemp]
   int *tacc_win;               // [ncs][ntemp]
   long long *swap_try, *swap_acc;   // [ncs][ntemp - 1]
+  // hierarchical noise only (null otherwise): lambda^2 ~ InverseGamma(na0, nb0) a priori
+  float na0, nb0;
+  double *nsum;                // [2][ncol]: sums of sqrt(B) and of B over the recorded states, B = nb0 + chi^2 / 2
+  long long *ncnt;             // [ncol]: states in them
+  const double *ngam;          // [MC_MAXPER + 1]: exp(lgamma(a - 0.5) - lgamma(a)) at a = na0 + nd / 2, made on the host
 };
+
+// the energy a decision is taken on: chi^2 itself, or with the noise scale integrated out X = 2 a log(B(chi^2)), +inf at +inf
+template <int NOISE>
+__device__ __forceinline__ double mc_energy(const McDev &M, double a, double chi2) {
+  if constexpr (NOISE) return 2.0 * a * log((double)M.nb0 + 0.5 * chi2);
+  else return chi2;
+}
 
 // the lanes of rung r: chains r, r + ntemp, ..
 __device__ __forceinline__ unsigned long long mc_rung_mask(int nchain, int ntemp, int r) {
@@ -257,7 +274,9 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
 // TEMPER 1 (a ladder of ntemp > 1 rungs): the decision of rung r takes beta_r, the scale and its window are per rung (lane r < ntemp
 // keeps rung r's, counting its chains in the ballot), neighbouring rungs swap states by lane shuffles after the decision, and only
 // the rung-0 lanes record.  Each lane carries its chi^2 in a register from the decision through the swap.
-template <int KIND, int TEMPER>
+// NOISE 1 (dazim_mc_set_noise): the lane counts the cell's nd in its weight loop, the decision and the swap compare mc_energy of the
+// two chi^2, and a recorded lane adds sqrt(B) and B of its state to its own column of nsum.  The handle keeps raw chi^2 throughout.
+template <int KIND, int TEMPER, int NOISE>
 __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__restrict__ pv, long long step, int first, int record,
                                                      int adapt, int nadapt) {
   __shared__ float s_scale;
@@ -270,6 +289,8 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
   const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
   const int nt = TEMPER ? M.ntemp : 1, rung = ch % nt;
   double chi2p = 0.0;
+  int nd = 0;                // NOISE: the cell's periods with data, and a = a0 + nd / 2
+  double na = 0.0;
   double chi2s = INFINITY;   // TEMPER: the chain's chi^2 after the decision, then after the swap
   unsigned wswap = 0u;       // TEMPER: word 1 of block(step, gid, 0), the swap uniform of a pair's lower chain
   bool acc = false;
@@ -277,30 +298,34 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
     for (int p = 0; p < M.kmax; p++) {
       const float w = M.wdat[(long)p * M.ncell + cell];
       if (w == 0.0f) continue;
+      nd++;
       const double c = pv[(long)p * M.ncol + col];
       if (c == 0.0) {   // no root at a period with data
         chi2p = INFINITY;
-        break;
+        if constexpr (NOISE) continue;   // (nd needs the rest of the loop; +inf stays)
+        else break;
       }
       const double r = (double)w * ((double)M.cobs[(long)p * M.ncell + cell] - c);
       chi2p += r * r;
     }
+    if constexpr (NOISE) na = (double)M.na0 + 0.5 * nd;
     if (first) {
       acc = true;
     } else {
       const double chi2c = M.chi2[col];
+      const double xp = mc_energy<NOISE>(M, na, chi2p), xc = mc_energy<NOISE>(M, na, chi2c);
       if constexpr (TEMPER) {
         unsigned w[4];
         mc_block(w, step, gid, 0u, M.seed);
         wswap = w[1];
         chi2s = chi2c;
-        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * M.beta[rung] * (chi2p - chi2c);
+        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * M.beta[rung] * (xp - xc);
       } else if (isinf(chi2c)) {
         acc = !isinf(chi2p);
       } else {
         unsigned w[4];
         mc_block(w, step, gid, 0u, M.seed);
-        acc = log(mc_uniform(w[0])) < -0.5 * (chi2p - chi2c);
+        acc = log(mc_uniform(w[0])) < -0.5 * (xp - xc);
       }
     }
     if (acc) {
@@ -323,7 +348,9 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       int sw = 0;
       if (lower) {
         if (isinf(chi2s)) sw = !isinf(cup);
-        else if (!isinf(cup)) sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) * (chi2s - cup);
+        else if (!isinf(cup))
+          sw = log(mc_uniform(wswap)) <
+               0.5 * (M.beta[rung] - M.beta[rung + 1]) * (mc_energy<NOISE>(M, na, chi2s) - mc_energy<NOISE>(M, na, cup));
       }
       const int swu = __shfl_up(sw, 1);
       const bool swp = lower ? sw != 0 : (upper && swu != 0);
@@ -402,6 +429,15 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         int b = (int)((v - lo) / (hi - lo) * (double)M.nbin);
         b = b < 0 ? 0 : (b >= M.nbin ? M.nbin - 1 : b);
         atomicAdd(&M.hist[((long)cs * M.nlay + k) * M.nbin + b], 1u);
+      }
+      if constexpr (NOISE) {
+        const double c2 = M.chi2[col];   // the lane's own store, after the decision and the swap
+        if (!isinf(c2)) {
+          const double B = (double)M.nb0 + 0.5 * c2;
+          M.nsum[col] += sqrt(B);
+          M.nsum[M.ncol + col] += B;
+          M.ncnt[col] += 1;
+        }
       }
     }
     // the lowest chi^2 of this step, the first chain on ties; it replaces the cell's best only when strictly lower
@@ -548,6 +584,40 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, l
     accept[cell] = ndec > 0 ? (float)((double)a / ((double)ndec * (double)(M.nchain / M.ntemp))) : 0.0f;
     chi2_best[cell] = (float)M.best_chi2[cs];
   }
+}
+
+// the noise scale's posterior (dazim_mc_noise_result), one lane per inner cell: conditional on a state lambda^2 ~ IG(a, B), so
+// E[lambda] = g(a) E[sqrt(B)] and E[lambda^2] = E[B] / (a - 1); the cell's cold columns in column order inside the lane
+__global__ __launch_bounds__(MC_WAVE) void k_mc_noise_final(McDev M, float *__restrict__ lam_mean, float *__restrict__ lam_std,
+                                                            int *__restrict__ ndata) {
+  const int cell = blockIdx.x * MC_WAVE + threadIdx.x;
+  if (cell >= M.ncell) return;
+  const int cs = M.cs_of[cell];
+  int nd = 0;
+  for (int p = 0; p < M.kmax; p++) nd += M.wdat[(long)p * M.ncell + cell] != 0.0f;
+  ndata[cell] = nd;
+  if (cs < 0) {
+    lam_mean[cell] = 0.0f;
+    lam_std[cell] = 0.0f;
+    return;
+  }
+  long long n = 0;
+  double s0 = 0.0, s1 = 0.0;
+  for (int ch = 0; ch < M.nchain; ch += M.ntemp) {
+    const long col = (long)cs * M.nchain + ch;
+    n += M.ncnt[col];
+    s0 += M.nsum[col];
+    s1 += M.nsum[M.ncol + col];
+  }
+  if (n == 0) {
+    lam_mean[cell] = NAN;
+    lam_std[cell] = NAN;
+    return;
+  }
+  const double a = (double)M.na0 + 0.5 * nd, dn = (double)n;
+  const double lm = M.ngam[nd] * s0 / dn;
+  lam_mean[cell] = (float)lm;
+  lam_std[cell] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
 }
 
 // Gc/Gs (dazim_mc_set_aniso).  Cold column cs * ncold + g is chain g * ntemp of sampled cell cs.
@@ -709,6 +779,7 @@ struct dazim_mc {
   int nthin = 0;            // Gc/Gs: 0 = off, else one pass per nthin recorded steps of dazim_mc_run
   McAniso an{};             // ... its maps and sums (sized for ntemp = 1, so that any ladder fits)
   int64_t naniso = 0;       // ... samples taken
+  int noise = 0;            // hierarchical noise: 0 = off (d.na0, d.nb0 hold the prior while it is on)
   std::vector<void *> blocks;
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
@@ -746,8 +817,11 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
     DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
     const size_t lds =
         mc->kind == 1 ? ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double) : 0;
-    auto kern = mc->kind == 1 ? (mc->d.ntemp > 1 ? k_mc_step<1, 1> : k_mc_step<1, 0>)
-                              : (mc->d.ntemp > 1 ? k_mc_step<0, 1> : k_mc_step<0, 0>);
+    auto kern = mc->kind == 1 ? (mc->d.ntemp > 1 ? k_mc_step<1, 1, 0> : k_mc_step<1, 0, 0>)
+                              : (mc->d.ntemp > 1 ? k_mc_step<0, 1, 0> : k_mc_step<0, 0, 0>);
+    if (mc->noise)
+      kern = mc->kind == 1 ? (mc->d.ntemp > 1 ? k_mc_step<1, 1, 1> : k_mc_step<1, 0, 1>)
+                           : (mc->d.ntemp > 1 ? k_mc_step<0, 1, 1> : k_mc_step<0, 0, 1>);
     hipLaunchKernelGGL(kern, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record, (int)adapt,
                        mc->nadapt);
     DZ_HIP(hipGetLastError());
@@ -1185,6 +1259,84 @@ int dazim_mc_aniso_result(dazim_ctx *ctx, dazim_mc *mc, float *mean_u, float *st
   return 0;
 }
 
+int dazim_mc_set_noise(dazim_ctx *ctx, dazim_mc *mc, float a0, float b0) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_set_noise"))) return rc;
+  if (!(std::isfinite(a0) && a0 >= 0.0f)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise: a0 %g is not finite and >= 0", a0);
+  if (a0 > 0.0f && !(std::isfinite(b0) && b0 > 0.0f))
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise: b0 %g is not finite and > 0", b0);
+  if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise: the handle has done %lld steps", (long long)mc->nstep);
+  McDev &M = mc->d;
+  if (a0 == 0.0f) {
+    mc->noise = 0;
+    M.na0 = M.nb0 = 0.0f;
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  const size_t nc = (size_t)M.ncol;
+  if (!M.nsum) {
+    double *g;
+    if ((rc = mc_alloc(mc, 2 * nc, &M.nsum)) || (rc = mc_alloc(mc, nc, &M.ncnt)) || (rc = mc_alloc(mc, (size_t)MC_MAXPER + 1, &g)))
+      return rc;
+    M.ngam = g;
+  }
+  // g(a) = Gamma(a - 1/2) / Gamma(a) at a = a0 + nd / 2 for every nd a cell can have: one table, so that host and device agree
+  double gam[MC_MAXPER + 1];
+  for (int nd = 0; nd <= MC_MAXPER; nd++) {
+    const double a = (double)a0 + 0.5 * nd;
+    gam[nd] = std::exp(std::lgamma(a - 0.5) - std::lgamma(a));
+  }
+  DZ_HIP(hipMemcpyAsync((void *)M.ngam, gam, sizeof(gam), hipMemcpyHostToDevice, ctx->stream));
+  DZ_HIP(hipMemsetAsync(M.nsum, 0, (2 * nc ? 2 * nc : 1) * sizeof(double), ctx->stream));
+  DZ_HIP(hipMemsetAsync(M.ncnt, 0, (nc ? nc : 1) * sizeof(long long), ctx->stream));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  M.na0 = a0;
+  M.nb0 = b0;
+  mc->noise = 1;
+  return 0;
+}
+
+int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, double *nsum, int64_t *ncnt) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_noise_state"))) return rc;
+  const McDev &M = mc->d;
+  if (a0) *a0 = M.na0;
+  if (b0) *b0 = M.nb0;
+  if (!mc->noise) {
+    if (nsum || ncnt) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_state: dazim_mc_set_noise has not switched the noise scale on");
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
+  };
+  DZ_HIP(get(nsum, M.nsum, (size_t)2 * M.ncol * 8));
+  DZ_HIP(get(ncnt, M.ncnt, (size_t)M.ncol * 8));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int dazim_mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u, float *lam_std_u, int *ndata_u) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_noise_result"))) return rc;
+  if (!lam_mean_u || !lam_std_u || !ndata_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_noise_result");
+  if (!mc->noise) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_result: dazim_mc_set_noise has not switched the noise scale on");
+  if (mc->d.ncs > 0 && mc->nrec < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_result: no recorded step yet");
+  DZ_HIP(hipSetDevice(ctx->device));
+  const McDev &M = mc->d;
+  DzBuf<float> lm, ls;
+  DzBuf<int> nd;
+  if ((rc = lm.init(ctx, lam_mean_u, (size_t)M.ncell, false, true)) || (rc = ls.init(ctx, lam_std_u, (size_t)M.ncell, false, true)) ||
+      (rc = nd.init(ctx, ndata_u, (size_t)M.ncell, false, true)))
+    return rc;
+  hipLaunchKernelGGL(k_mc_noise_final, dim3((unsigned)((M.ncell + MC_WAVE - 1) / MC_WAVE)), dim3(MC_WAVE), 0, ctx->stream, M, lm.dev,
+                     ls.dev, nd.dev);
+  DZ_HIP(hipGetLastError());
+  if ((rc = lm.finish()) || (rc = ls.finish()) || (rc = nd.finish())) return rc;
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv_u, int record) {
   int rc;
   if ((rc = mc_check(ctx, mc, "dazim_mc_step"))) return rc;
@@ -1293,6 +1445,7 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
   ctx->ksec["mc.swap_min"] = swap_min;
   ctx->ksec["mc.swap_med"] = swap_med;
   ctx->ksec["mc.proposal"] = mc->kind;
+  ctx->ksec["mc.noise"] = mc->noise;
   ctx->ksec["mc.cov_cells"] = cov_cells;
   if (n_no_root) *n_no_root = (int64_t)(c1[0] - c0[0]);
   return 0;

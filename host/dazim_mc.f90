@@ -2,7 +2,8 @@
 ! random-walk Metropolis chains on one MI355X and reports the posterior mean, spread and credible interval of every knot (DESIGN.md
 ! section 14), where SurfDepthFromMaps_amd returns one linearised model.
 !
-!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a]]]]]]]]]]]
+!   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a
+!                            [noise_a0 [noise_b0]]]]]]]]]]]]]
 !
 ! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
 ! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
@@ -22,6 +23,11 @@
 !                                of Gs (the part of each std that comes from not knowing Vs), amplitude and its std, fast axis (degrees)
 !                                and its std (write_azimuthal's arithmetic, the stds by the delta method), samples
 !   Gc_Gs_model_mc.inv           the means on the posterior-mean Vs, as Gc_Gs_model.inv
+! noise_a0 0 (default): the data std is sigma_c everywhere, every file and log line as before.  noise_a0 > 0: the data std of a cell
+! becomes lambda * sigma_c with lambda unknown, lambda^2 ~ InverseGamma(noise_a0, noise_b0) a priori (noise_b0 defaults to 1);
+! lambda is integrated out of the chains' target, so the Vs spreads carry the uncertainty of the noise level, and its posterior per
+! cell comes back from the chains (dazim_mc_set_noise).  One more settings line, one more summary line, one more file:
+!   noise_posterior_mc.dat       per inner cell: lon lat, mean and std of lambda, sigma_c * mean (the data std in km/s), periods
 !
 ! Outputs (names of their own, so that the three programs can share a directory):
 !   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
@@ -44,6 +50,9 @@ program SurfDepthMC_amd
   real, allocatable :: amap(:, :, :, :), wa(:, :, :), gmean(:, :, :, :), gstd(:, :, :, :), gstdb(:, :, :, :), gcov(:, :, :)
   integer(c_int64_t), allocatable :: nsamp(:, :)
   integer :: npass, nskip
+  real :: noise_a0, noise_b0
+  real, allocatable :: lam_mean(:, :), lam_std(:, :)
+  integer(c_int), allocatable :: ndata(:, :)
   integer, parameter :: nswap = 1
   real :: tmax
   real(c_double), allocatable, target :: beta(:)
@@ -68,7 +77,8 @@ program SurfDepthMC_amd
   write (*, *) '                       SurfDepthMC'
   write (*, *)
   if (command_argument_count() < 1) error stop &
-    'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a]]]]]]]]]]]'
+    'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a '// &
+    '[noise_a0 [noise_b0]]]]]]]]]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -91,6 +101,9 @@ program SurfDepthMC_amd
   call optional_arg(11, smooth_gcs)
   sigma_a = sigma_c
   call optional_arg(12, sigma_a)
+  noise_a0 = 0; noise_b0 = 1
+  call optional_arg(13, noise_a0)
+  call optional_arg(14, noise_b0)
   if (nsample < 1) error stop 'nsample must be at least 1'
   if (nchain < 1 .or. nchain > 64) error stop 'nchain must be 1..64'
   if (width < 0) error stop 'width must not be negative'
@@ -107,6 +120,8 @@ program SurfDepthMC_amd
   if (aniso_thin > 0 .and. sigma_a <= 0) error stop 'sigma_a must be positive'
   if (aniso_thin > 0 .and. (smooth_gcs < 0 .or. (smooth_gcs == 0 .and. p%damp == 0))) error stop &
     'smooth_gcs must not be negative, nor 0 together with para.in''s damping'
+  if (.not. (noise_a0 >= 0 .and. noise_a0 <= huge(noise_a0))) error stop 'noise_a0 must not be negative'
+  if (noise_a0 > 0 .and. .not. (noise_b0 > 0 .and. noise_b0 <= huge(noise_b0))) error stop 'noise_b0 must be positive'
   ncold = nchain/ntemp
   nlay = nz - 1
   ncell = (nx - 2)*(ny - 2)
@@ -135,6 +150,8 @@ program SurfDepthMC_amd
       ', a swap round every', nswap, ' step(s);', ncold, ' chains per cell at T = 1 are recorded'
     if (aniso_thin > 0) write (q, '(a,i6,a,f8.3,a,f8.3,a,f8.4)') ' Gc/Gs posteriors: one sample of every recorded chain per', &
       aniso_thin, ' recorded steps;  smoothing', smooth_gcs, '  damping', p%damp, '  sigma_a (km/s)', sigma_a
+    if (noise_a0 > 0) write (q, '(a,f9.4,a,f9.4,a)') ' hierarchical noise: data std lambda * sigma_c per cell, lambda^2 ~ InverseGamma(', &
+      noise_a0, ',', noise_b0, '), integrated out of the chains'' target'
   end do
 
   call read_mod('MOD', p, depz, vsf)
@@ -183,6 +200,7 @@ program SurfDepthMC_amd
   end if
   if (aniso_thin > 0) call dazim_check(dazim_mc_set_aniso(dazim_handle, mc, aniso_thin, amap, wa, smooth_gcs, p%damp), &
                                        'Gc/Gs posteriors')
+  if (noise_a0 > 0) call dazim_check(dazim_mc_set_noise(dazim_handle, mc, noise_a0, noise_b0), 'hierarchical noise')
   call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
   t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
   t_disp = real(dazim_last_kernel_seconds(dazim_handle, 'mc.disp'//c_null_char))
@@ -204,6 +222,10 @@ program SurfDepthMC_amd
     else   ! fewer recorded steps than aniso_thin: no sample
       gmean = 0; gstd = 0; gstdb = 0; gcov = 0; nsamp = 0
     end if
+  end if
+  if (noise_a0 > 0) then
+    allocate (lam_mean(nx - 2, ny - 2), lam_std(nx - 2, ny - 2), ndata(nx - 2, ny - 2))
+    call dazim_check(dazim_mc_noise_result(dazim_handle, mc, lam_mean, lam_std, ndata), 'noise-scale posterior')
   end if
   call dazim_check(dazim_mc_free(dazim_handle, mc), 'Monte-Carlo chains')
 
@@ -285,6 +307,19 @@ program SurfDepthMC_amd
       write (q, '(a,2f9.4)') ' R-hat over (cell, knot), median and maximum:', sorted(max(1, (nr + 1)/2)), sorted(max(nr, 1))
     end do
   end if
+  if (noise_a0 > 0) then
+    nr = count(sampled .and. lam_mean == lam_mean)
+    if (allocated(sorted)) deallocate (sorted)
+    allocate (sorted(max(nr, 1)))
+    sorted = 0
+    if (nr > 0) sorted(1:nr) = pack(lam_mean, sampled .and. lam_mean == lam_mean)
+    call sort(sorted)
+    do q = 6, 66, 60
+      write (q, '(a,5f9.3)') ' noise scale over cells (mean of lambda), minimum, quartiles 25/50/75 % and maximum:', sorted(1), &
+        sorted(max(1, nint(0.25*nr))), sorted(max(1, nint(0.5*nr))), sorted(max(1, nint(0.75*nr))), sorted(max(nr, 1))
+    end do
+    deallocate (sorted)
+  end if
   do q = 6, 66, 60
     write (q, '(a,f12.5)') ' posterior-mean model: rms_c', rms_all
   end do
@@ -323,6 +358,16 @@ program SurfDepthMC_amd
             gstd(i, j, k, 1), gs, gstd(i, j, k, 2), gstdb(i, j, k, 1), gstdb(i, j, k, 2), amp, samp, fast_axis(gc, gs), sang, &
             nsamp(i, j)
         end do
+      end do
+    end do
+    close (64)
+  end if
+  if (noise_a0 > 0) then
+    open (64, file='noise_posterior_mc.dat')
+    do j = 1, ny - 2
+      do i = 1, nx - 2
+        write (64, '(2f10.4,3f12.6,i6)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, lam_mean(i, j), lam_std(i, j), &
+          sigma_c*lam_mean(i, j), ndata(i, j)
       end do
     end do
     close (64)

@@ -39,7 +39,8 @@ module dazim_mod
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
   public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
             dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds, &
-            dazim_mc_set_aniso, dazim_mc_aniso_step, dazim_mc_aniso_state, dazim_mc_aniso_result
+            dazim_mc_set_aniso, dazim_mc_aniso_step, dazim_mc_aniso_state, dazim_mc_aniso_result, dazim_mc_set_noise, &
+            dazim_mc_noise_state, dazim_mc_noise_result
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -316,6 +317,23 @@ module dazim_mod
       type(c_ptr), value :: ctx, mc
       real(c_float) :: mean(*), std(*), std_between(*), cov_cs(*)
       integer(c_int64_t) :: nsamp(*)
+    end function
+    ! the data-noise scale as an unknown per cell: lambda^2 ~ InverseGamma(a0, b0), a0 = 0 switches it off; results (nx-2, ny-2)
+    integer(c_int) function dazim_mc_set_noise(ctx, mc, a0, b0) bind(C, name="dazim_mc_set_noise")
+      import
+      type(c_ptr), value :: ctx, mc
+      real(c_float), value :: a0, b0
+    end function
+    ! every argument after mc may be c_null_ptr (c_loc of a variable or an array otherwise)
+    integer(c_int) function dazim_mc_noise_state(ctx, mc, a0, b0, nsum, ncnt) bind(C, name="dazim_mc_noise_state")
+      import
+      type(c_ptr), value :: ctx, mc, a0, b0, nsum, ncnt
+    end function
+    integer(c_int) function dazim_mc_noise_result(ctx, mc, lam_mean, lam_std, ndata) bind(C, name="dazim_mc_noise_result")
+      import
+      type(c_ptr), value :: ctx, mc
+      real(c_float) :: lam_mean(*), lam_std(*)
+      integer(c_int) :: ndata(*)
     end function
     integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
         bind(C, name="dazim_phase_map_update")

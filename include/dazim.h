@@ -400,6 +400,37 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
  *   every column's arithmetic is its own, so the results do not depend on the blocks.  The pass reads the chains and writes only
  *   its own arrays: the Vs chain, its records and its random numbers are bit for bit what they are without it.  Stats: "mc.aniso"
  *   (seconds of the run's passes), "mc.aniso_passes", "mc.aniso_skipped" (0 when Gc/Gs is off).
+ * Hierarchical data noise (dazim_mc_set_noise; without it, or with a0 = 0, every launch and every result is the one above,
+ *   unchanged): the noise level becomes an unknown of the posterior (Bodin et al., 2012) and is integrated out in closed form, so no
+ *   random number and no tuning knob is added.
+ *   Noise model: the data std of period p in a cell is lambda / w_p, lambda one unknown factor per cell and chain, with the prior
+ *   lambda^2 ~ InverseGamma(a0, b0).  Per sampled cell nd = the number of periods with w != 0 (the same for all of its chains),
+ *   a = (double)a0 + 0.5 * nd, B(chi2) = (double)b0 + 0.5 * chi2.  Integrating lambda out of lambda^-nd exp(-chi2 / (2 lambda^2))
+ *   p(lambda^2) leaves a marginal posterior of the knots proportional to B(chi2)^-a inside the box (a Student-t in the residuals).
+ *   Energy: X(chi2) = 2.0 * a * log(B(chi2)) in fp64, X(+inf) = +inf.
+ *   Step: the one above with X in place of chi2 wherever a decision is taken, nothing else: accept iff log(u) < -0.5 * (X' - X),
+ *   tempered log(u) < -0.5 * beta_r * (X' - X), swap D = 0.5 * (beta_r - beta_{r+1}) * (X_r - X_{r+1}), each evaluated left to right
+ *   as the formulas above are written; the rules for +inf are the ones above.  The uniforms, the normals and the proposals,
+ *   reflection and scale adaptation, the covariance sums and factor, the records of Vs, the histogram and the best model (lowest raw
+ *   chi2; X is monotone in it) stay what they are, and the handle still stores raw chi2 in chi2, best_chi2 and chi2_best.
+ *   Noise record: at a recorded step, after the decision and any swap, a chain at rung 0 whose chi2 is finite adds, with B at its
+ *   state, nsum[0][col] += sqrt(B), nsum[1][col] += B (fp64) and ncnt[col] += 1 (int64); a chain at +inf adds nothing.  nsum
+ *   [2][ncol] and ncnt [ncol] are 0 at the start, and the columns of the other rungs stay 0.
+ *   Result (dazim_mc_noise_result): conditional on a state lambda^2 ~ IG(a, B), so E[lambda] = g E[sqrt(B)] with g = Gamma(a - 1/2)
+ *   / Gamma(a) and E[lambda^2] = E[B] / (a - 1).  One lane per inner cell, the sums over its cold columns in column order in fp64:
+ *   n = sum ncnt, S0 = sum nsum[0], S1 = sum nsum[1]; g = exp(lgamma(a - 0.5) - lgamma(a)) from a table over nd = 0..60 that the
+ *   host makes once when the mode is set; lam_mean = g * S0 / n, lam_std = sqrt(max(S1 / (n * (a - 1)) - lam_mean^2, 0)), NaN where
+ *   a <= 1; both NaN for n = 0; cells without data get 0; each rounded to fp32 once.  ndata [ny-2][nx-2] (int32) = nd.
+ *   The Gc/Gs sums of dazim_mc_set_aniso are unchanged by the mode: they keep 1/sigma_a and do not see lambda.  Both modes may be
+ *   on together.  Stat "mc.noise" of dazim_mc_run is 0 or 1.
+ *   dazim_mc_set_noise: a0 > 0 switches the mode on with the prior (a0, b0); a0 == 0 restores the default (b0 is not looked at
+ *   then).  It may come before or after dazim_mc_set_proposal, dazim_mc_set_tempering and dazim_mc_set_aniso.  DAZIM_E_BAD_ARG for
+ *   a non-finite or negative a0, for a0 > 0 with b0 not finite or <= 0, for a handle of another context, or once a step has been
+ *   done.
+ *   dazim_mc_noise_state: a0, b0 (0, 0 while the mode is off) and copies of nsum and ncnt (each pointer nullable, the arrays host or
+ *   device).  DAZIM_E_BAD_ARG when the mode is off and an array is requested.
+ *   dazim_mc_noise_result: lam_mean, lam_std [ny-2][nx-2] fp32 and ndata [ny-2][nx-2] int32 (host or device).  Refused with the
+ *   mode off or before the first recorded step.
  * dazim_mc_create: vel0 [nz][ny][nx] (the last knot; the result of cells without data), vmin, vmax [nlay][ny-2][nx-2], cobs, wdat
  *   [kmax][ny-2][nx-2] (the layout of dazim_column_lsq), step = the initial s, nadapt >= 1.  Draws the start models.  Refused
  *   (DAZIM_E_BAD_ARG): nchain outside 1..64, nlay outside 1..63, kmax outside 1..60, nbin < 2, a non-finite vmin, vmax, cobs or
@@ -447,6 +478,9 @@ int dazim_mc_set_aniso(dazim_ctx *ctx, dazim_mc *mc, int nthin, const float *ama
 int dazim_mc_aniso_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncolc, const float *lsen);
 int dazim_mc_aniso_state(dazim_ctx *ctx, dazim_mc *mc, int *nthin, double *asum, double *avar, int64_t *acnt, int64_t *skipped);
 int dazim_mc_aniso_result(dazim_ctx *ctx, dazim_mc *mc, float *mean, float *std, float *std_between, float *cov_cs, int64_t *nsamp);
+int dazim_mc_set_noise(dazim_ctx *ctx, dazim_mc *mc, float a0, float b0);
+int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, double *nsum, int64_t *ncnt);
+int dazim_mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean, float *lam_std, int *ndata);
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);
 int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
                  int64_t *n_no_root);

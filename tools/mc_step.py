@@ -3,6 +3,8 @@
     python tools/mc_step.py [--steps S] [--big N] [--proposal K] [--ntemp R [--tmax T]]
     python tools/mc_step.py --program [--dir D] [--proposal K] [--ntemp R [--tmax T]]
     python tools/mc_step.py --aniso N [--steps S] [--big N]
+    python tools/mc_step.py --noise A0 B0 [--steps S] [--proposal K] [--ntemp R [--tmax T]]
+    python tools/mc_step.py --program --noise A0 B0 [--dir D] [--proposal K] [--ntemp R [--tmax T]]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -24,7 +26,12 @@ instead of the default 1, no tempering; "swap_min" and "swap_med" are the run's 
 --aniso N: the Gc/Gs pass (dazim_mc_set_aniso, one pass per N recorded steps: gather, dispersion, TI kernels, column solves) at S-256
 with 32 chains and on the big grid with 8: after a warm-up run that holds one pass, three runs of S recorded steps each; reports
 the median over the runs of the ms of one pass ("mc.aniso" / "mc.aniso_passes") beside the ms of one step without its share of the
-passes (profiles/depth_mc_aniso.md)."""
+passes (profiles/depth_mc_aniso.md).
+
+--noise A0 B0: the hierarchical noise scale (dazim_mc_set_noise, lambda^2 ~ InverseGamma(A0, B0)) at S-256 with 32 chains: five
+pairs of runs of S steps, the mode off then on, alternating, each on a fresh handle after its own warm-up run; reports the ms per
+step of the k_mc_step launches of every run and the medians of the five (profiles/depth_mc_noise.md).  With --program: the default
+run with arguments 13 and 14, the log's noise lines among those kept."""
 import argparse
 import json
 import os
@@ -39,7 +46,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax):
+def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None):
     import bench
     bench.NX = bench.NY = n
     vel = bench.s256_model().astype(np.float32)
@@ -51,20 +58,37 @@ def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax):
     vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
     wdat = np.full((kmax, n - 2, n - 2), 100.0, np.float32)
     mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat, nadapt=5 if proposal else 50, proposal=proposal,
-                       ntemp=ntemp, tmax=tmax)
+                       ntemp=ntemp, tmax=tmax, noise=noise)
     mc.run(depz, bench.MINTHK, periods, 5, 0)                 # warm-up: code objects, scratch buffers
     nr = mc.run(depz, bench.MINTHK, periods, steps // 2, steps - steps // 2)
     wall, disp, stp = ctx.stat("mc"), ctx.stat("mc.disp"), ctx.stat("mc.step")
     r = mc.result()
+    lam = mc.noise_result()["lam_mean"] if noise else None
     mc.free()
     ms = lambda s: 1e3 * s / steps
     return {"grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots ({nlay} sampled), {kmax} periods", "nchain": nchain,
+            "noise": list(noise) if noise else None, "median_lam_mean": float(np.median(lam)) if noise else None,
             "proposal": proposal, "ntemp": ntemp, "swap_min": ctx.stat("mc.swap_min"), "swap_med": ctx.stat("mc.swap_med"),
             "cov_cells": int(ctx.stat("mc.cov_cells")), "steps": steps, "curves_per_step": mc.ncol, "ms_per_step": ms(wall),
             "disp_ms_per_step": ms(disp),
             "mc_step_ms_per_step": ms(stp), "other_ms_per_step": ms(wall - disp - stp), "mc_step_share": stp / wall,
             "curves_per_s": mc.ncol * steps / wall, "accept": ctx.stat("mc.accept"), "no_root": nr,
             "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
+
+
+def noise_cases(ctx, steps, proposal, ntemp, tmax, noise, pairs=5):
+    runs = {"off": [], "on": []}
+    for _ in range(pairs):
+        for name, arg in (("off", None), ("on", tuple(noise))):
+            runs[name].append(one_case(ctx, 54, 32, steps, proposal, ntemp, tmax, arg))
+    out = dict(runs["on"][-1])
+    for name in runs:
+        for key in ("mc_step_ms_per_step", "ms_per_step", "disp_ms_per_step"):
+            v = [r[key] for r in runs[name]]
+            out[f"{key}_{name}"] = v
+            out[f"{key}_{name}_median"] = float(np.median(v))
+    out["median_std_km_s_off"] = runs["off"][-1]["median_std_km_s"]
+    return out
 
 
 def aniso_case(ctx, n, nchain, steps, nthin):
@@ -122,7 +146,7 @@ cccccccccc periods
 """
 
 
-def program_run(ctx, d, proposal, ntemp, tmax):
+def program_run(ctx, d, proposal, ntemp, tmax, noise=None):
     import bench
     n = bench.NX = bench.NY = 54
     vel = bench.s256_model().astype(np.float32)
@@ -147,17 +171,20 @@ def program_run(ctx, d, proposal, ntemp, tmax):
                     f.write("%10.4f%10.4f%10.4f%10.4f\n" % (100.0 + (j - 1) * 0.25, 30.0 - (i - 1) * 0.25, periods[t], pv[t, j, i]))
     exe = os.path.join(ROOT, "host", "SurfDepthMC_amd")
     t0 = time.perf_counter()
-    args = ["2000", "32", "0", "0.01", "1", str(proposal)] if proposal or ntemp > 1 else []
-    if ntemp > 1:
+    args = ["2000", "32", "0", "0.01", "1", str(proposal)] if proposal or ntemp > 1 or noise else []
+    if ntemp > 1 or noise:
         args += [str(ntemp), "%g" % tmax]
+    if noise:                        # aniso_thin, smooth_gcs, sigma_a at their defaults, then noise_a0, noise_b0
+        args += ["0", "2.0", "0.01", "%g" % noise[0], "%g" % noise[1]]
     out = subprocess.run([exe, "para.in"] + args, cwd=d, capture_output=True, text=True, timeout=1500)
     wall = time.perf_counter() - t0
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     log = open(os.path.join(d, "para.in_mc.log")).read().splitlines()
     keep = [l.strip() for l in log if any(k in l for k in ("cells sampled", "without a root", "run", "acceptance", "R-hat", "rms_c", "proposal",
-                                                                "covariance", "tempering", "ladder", "swap", "T = 1"))]
+                                                                "covariance", "tempering", "ladder", "swap", "T = 1", "noise"))]
     return {"program": "SurfDepthMC_amd para.in (defaults: 2000 + 2000 steps, 32 chains)", "proposal": proposal, "ntemp": ntemp,
-            "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots, {kmax} periods", "wall_s": wall, "log": keep}
+            "noise": list(noise) if noise else None, "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots, {kmax} periods",
+            "wall_s": wall, "log": keep}
 
 
 def main():
@@ -171,6 +198,7 @@ def main():
     ap.add_argument("--ntemp", type=int, default=1)
     ap.add_argument("--tmax", type=float, default=16.0)
     ap.add_argument("--aniso", type=int, default=0)
+    ap.add_argument("--noise", type=float, nargs=2, default=None, metavar=("A0", "B0"))
     a = ap.parse_args()
     ctx = dz.Context(0)
     if a.aniso > 0:
@@ -180,7 +208,11 @@ def main():
         return
     if a.program:
         with tempfile.TemporaryDirectory() as tmp:
-            print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal, a.ntemp, a.tmax)), flush=True)
+            print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal, a.ntemp, a.tmax, a.noise)), flush=True)
+        return
+    if a.noise:
+        print(json.dumps(noise_cases(ctx, a.steps, a.proposal, a.ntemp, a.tmax, a.noise)), flush=True)
+        ctx.close()
         return
     for n, nchain in ((54, 8), (54, 32), (54, 64), (a.big, 8)):
         print(json.dumps(one_case(ctx, n, nchain, a.steps, a.proposal, a.ntemp, a.tmax)), flush=True)
