@@ -400,6 +400,35 @@ class Context:
                                               _ptr(x, np.float32), C.byref(ne), _ptr(st)))
         return x, ne.value, st
 
+    def column_resolution(self, nx, ny, nlay, kern, wdat=None, smooth=0.0, damp=0.0, depz=None, rows=False):
+        """posterior std and resolution of column_lsq's problem per inner cell and knot (dazim_column_resolution): kern, wdat, smooth,
+        damp as in column_lsq, depz[nlay] the knots' depths (for `width`), rows=True for the full averaging kernels.  numpy in -> numpy
+        out, torch-cuda kern -> torch-cuda arrays.  Returns a dict: std_post, std_noise, rdiag, rsum, width (None without depz), each
+        [nlay][ny-2][nx-2]; rows [nlay][nlay][ny-2][nx-2] (None unless asked); trace [ny-2][nx-2]; n_empty, n_failed."""
+        kmax = kern.shape[1]
+        fp32 = str(kern.dtype).endswith("float32")
+        if _is_torch(kern):
+            import torch
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=kern.device)
+        else:
+            new = lambda *shape: np.zeros(shape, np.float32)
+            kern = np.ascontiguousarray(kern)
+            wdat = None if wdat is None else np.ascontiguousarray(wdat, np.float32)
+        if depz is not None and not _is_torch(depz):
+            depz = np.ascontiguousarray(depz, np.float32)
+            assert depz.size == nlay
+        out = {k: new(nlay, ny - 2, nx - 2) for k in ("std_post", "std_noise", "rdiag", "rsum")}
+        out["width"] = None if depz is None else new(nlay, ny - 2, nx - 2)
+        out["rows"] = new(nlay, nlay, ny - 2, nx - 2) if rows else None
+        out["trace"] = new(ny - 2, nx - 2)
+        ne, nf = C.c_int(0), C.c_int(0)
+        self._check(self.lib.dazim_column_resolution(self._h, nx, ny, int(nlay), kmax, int(fp32), _ptr(kern, np.float32 if fp32 else np.float64),
+                                                     _ptr(wdat, np.float32), C.c_float(smooth), C.c_float(damp), _ptr(depz, np.float32),
+                                                     *[_ptr(out[k], np.float32) for k in ("std_post", "std_noise", "rdiag", "rsum", "width",
+                                                                                          "rows", "trace")], C.byref(ne), C.byref(nf)))
+        out["n_empty"], out["n_failed"] = ne.value, nf.value
+        return out
+
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
                   ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],

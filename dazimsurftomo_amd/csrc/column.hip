@@ -5,6 +5,7 @@
 // per cell builds its normal matrix (at most 63 x 63) in LDS, factors it by Cholesky and solves, all in fp64.  The launch is bound
 // by latency (a few MB of kernel table in all), so it stays this plain.  Every sum runs in a fixed order: the same inputs give the
 // same bits, whether they come from the host or the device.
+// dazim_column_resolution: posterior covariance and resolution matrix of that problem from the same factor, in the same launch shape.
 #include "dazim_internal.h"
 
 #include <cmath>
@@ -115,6 +116,122 @@ __global__ __launch_bounds__(CL_STATS_TB) void k_column_stats(int ncell, int kma
   }
 }
 
+// Posterior covariance and resolution of k_column_lsq's problem, one 64-lane workgroup per inner cell, lane = knot a.  With
+// A = K^T W^2 K + P, P = s2 L^T L + d2 I, and A = R R^T from dz_column_solve (nrhs = 0: it builds and factors A and touches neither
+// wr nor b): M = R^-1 by dz_column_inverse_factor (column k in row k of A's strict upper triangle, then 1 / R_kk on the diagonal),
+// C = A^-1 = M^T M, Rm = I - C P.  Lane a forms row a of C, C_ac = sum_{i >= max(a, c)} M_ia M_ic in ascending i (C_aa is
+// dz_column_inverse_factor's sum), keeps it in its own row of Cm and walks it once: Rm_ac from the five entries C_ae, |e - c| <= 2,
+// that the pentadiagonal P reaches, and with it the row sum, the spread about z_a and, where asked, the row itself; (Rm C)_aa comes
+// from the same row as sum_p w_p^2 (sum_c C_ac K_pc)^2.  Barriers stand where a lane reads another lane's row of A.
+// LDS: A [n][n], K [kmax][n] (at the end the lanes' Rm_aa for the trace go there), w^2 [kmax], Cm [n][ldc] with
+// ldc = n | 1: a lane's walk along its own row of Cm is free of bank conflicts for every n.  94 224 bytes at n = 63, kmax = 60.
+// cnt[0] counts the cells without data (every output 0), cnt[1] those whose factorisation met a pivot that is not finite and
+// > 0 (every output NaN).
+template <typename KT>
+__global__ __launch_bounds__(CL_WAVE) void k_column_res(int nx, int ny, int n, int kmax, int ldc, const KT *__restrict__ kern,
+                                                        const float *__restrict__ wdat, double s2, double d2,
+                                                        const float *__restrict__ depz, float *__restrict__ std_post,
+                                                        float *__restrict__ std_noise, float *__restrict__ rdiag,
+                                                        float *__restrict__ rsum, float *__restrict__ width,
+                                                        float *__restrict__ rows, float *__restrict__ trace, int *__restrict__ cnt) {
+  extern __shared__ double sm[];
+  double *A = sm;
+  double *K = A + n * n;
+  double *w2 = K + kmax * n;
+  double *Cm = w2 + kmax;
+  const int t = threadIdx.x;
+  const int nvx = nx - 2, ncell = nvx * (ny - 2);
+  const int cell = blockIdx.x;
+  const int j = cell / nvx, i = cell - j * nvx;
+  const long ncol = (long)nx * ny, col = (long)(j + 1) * nx + (i + 1);
+  const long o = (long)t * ncell + cell;
+
+  auto fill = [&](float v) {                      // every output of this cell = v
+    if (t < n) {
+      std_post[o] = std_noise[o] = rdiag[o] = rsum[o] = v;
+      if (width) width[o] = v;
+    }
+    if (rows)
+      for (int q = t; q < n * n; q += CL_WAVE) rows[(long)q * ncell + cell] = v;
+    if (trace && t == 0) trace[cell] = v;
+  };
+  bool data = false;
+  if (t < kmax) {
+    const float w = wdat ? wdat[(long)t * ncell + cell] : 1.0f;
+    data = w != 0.0f;
+    w2[t] = (double)w * (double)w;
+  }
+  if (!__any(data)) {
+    fill(0.0f);
+    if (t == 0) atomicAdd(cnt, 1);
+    return;
+  }
+  for (int q = t; q < n * kmax; q += CL_WAVE) {   // q = l*kmax + p, the table's own order
+    const int l = q / kmax, p = q - l * kmax;
+    K[p * n + l] = (double)kern[(long)q * ncol + col];
+  }
+  __syncthreads();
+  if (!dz_column_solve(t, n, kmax, 0, A, K, w2, nullptr, nullptr, s2, d2)) {
+    fill(nanf(""));
+    if (t == 0) atomicAdd(cnt + 1, 1);
+    return;
+  }
+  double caa = 0.0;
+  if (t < n) caa = dz_column_inverse_factor(t, n, A);
+  __syncthreads();                                // (the other lanes divided by R_tt until here)
+  if (t < n) A[t * n + t] = 1.0 / A[t * n + t];
+  __syncthreads();
+  double rd = 0.0;
+  if (t < n) {
+    const int a = t;
+    double *Ca = Cm + a * ldc;
+    for (int c = 0; c < n; c++) {
+      double s = 0.0;
+      for (int q = max(a, c); q < n; q++) s += A[a * n + q] * A[c * n + q];
+      Ca[c] = c == a ? caa : s;
+    }
+    const double za = depz ? (double)depz[a] : 0.0;
+    // (Rm C)_aa = (C K^T W^2 K C)_aa as the sum of squares sum_p w_p^2 (sum_c C_ac K_pc)^2: the difference C_aa - (C P C)_aa would lose
+    // what is small against C_aa (a well determined direction under a weak regulariser)
+    double nv = 0.0;
+    for (int p = 0; p < kmax; p++)
+      if (w2[p] != 0.0) {
+        double u = 0.0;
+        for (int c = 0; c < n; c++) u += Ca[c] * K[p * n + c];
+        nv += w2[p] * (u * u);
+      }
+    double rs = 0.0, num = 0.0, den = 0.0;
+    for (int c = 0; c < n; c++) {
+      double s = 0.0;
+      for (int e = max(c - 2, 0); e <= min(c + 2, n - 1); e++) s += Ca[e] * (s2 * dz_ltl(n, e, c) + (e == c ? d2 : 0.0));
+      const double rm = (a == c ? 1.0 : 0.0) - s;
+      if (rows) rows[((long)a * n + c) * ncell + cell] = (float)rm;
+      rs += rm;
+      if (depz) {
+        const double dzc = (double)depz[c] - za;
+        num += rm * rm * (dzc * dzc);
+        den += rm * rm;
+      }
+      if (c == a) rd = rm;
+    }
+    std_post[o] = (float)sqrt(caa);
+    std_noise[o] = (float)sqrt(nv);
+    rdiag[o] = (float)rd;
+    rsum[o] = (float)rs;
+    if (width) width[o] = den > 0.0 ? (float)sqrt(num / den) : 0.0f;
+  }
+  if (trace) {
+    __syncthreads();                              // (the lanes read K until here)
+    if (t < n) K[t] = rd;
+    __syncthreads();
+    if (t == 0) {
+      double s = 0.0;
+      for (int a = 0; a < n; a++) s += K[a];
+      trace[cell] = (float)s;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -195,6 +312,60 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
   if ((rc = x.finish())) return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   if (n_empty) *n_empty = ne;
+  return 0;
+}
+
+int dazim_column_resolution(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int kern_fp32, const void *kern_u, const float *wdat_u,
+                            float smooth, float damp, const float *depz_u, float *std_post_u, float *std_noise_u, float *rdiag_u,
+                            float *rsum_u, float *width_u, float *rows_u, float *trace_u, int *n_empty, int *n_failed) {
+  if (!ctx || nx < 3 || ny < 3 || !kern_u || !std_post_u || !std_noise_u || !rdiag_u || !rsum_u)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_column_resolution");
+  if (nlay < 1 || nlay > CL_MAXLAY) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_column_resolution: nlay %d outside 1..%d", nlay, CL_MAXLAY);
+  if (kmax < 1 || kmax > CL_MAXPER) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_column_resolution: kmax %d outside 1..%d", kmax, CL_MAXPER);
+  if (!(smooth >= 0.0f) || !(damp >= 0.0f)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_column_resolution: negative smoothing or damping");
+  if (smooth == 0.0f && damp == 0.0f) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_column_resolution: smoothing and damping both 0");
+  if (!width_u != !depz_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_column_resolution: width and depz go together (both or neither)");
+  DZ_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = dz_join_aux(ctx))) return rc;
+  const int ncell = (nx - 2) * (ny - 2), ldc = nlay | 1;
+  const size_t nk = (size_t)nlay * kmax * nx * ny, no = (size_t)nlay * ncell;
+  DzBuf<double> kd;
+  DzBuf<float> kf, wdat, depz, sp, sn, rd, rs, wd, rw, tr;
+  if ((rc = kern_fp32 ? kf.init(ctx, (const float *)kern_u, nk, true, false) : kd.init(ctx, (const double *)kern_u, nk, true, false)) ||
+      (rc = wdat.init(ctx, wdat_u, wdat_u ? (size_t)kmax * ncell : 0, true, false)) ||
+      (rc = depz.init(ctx, depz_u, depz_u ? (size_t)nlay : 0, true, false)) || (rc = sp.init(ctx, std_post_u, no, false, true)) ||
+      (rc = sn.init(ctx, std_noise_u, no, false, true)) || (rc = rd.init(ctx, rdiag_u, no, false, true)) ||
+      (rc = rs.init(ctx, rsum_u, no, false, true)) || (rc = wd.init(ctx, width_u, width_u ? no : 0, false, true)) ||
+      (rc = rw.init(ctx, rows_u, rows_u ? no * nlay : 0, false, true)) || (rc = tr.init(ctx, trace_u, trace_u ? (size_t)ncell : 0, false, true)))
+    return rc;
+  void *pc;
+  if ((rc = dz_scratch(ctx, "col.res_cnt", 2 * sizeof(int), &pc))) return rc;
+  DZ_HIP(hipMemsetAsync(pc, 0, 2 * sizeof(int), ctx->stream));
+  // A, K, w^2 and the rows of C: more than the 64 KiB a kernel gets unasked from n = 48 or so; a gfx950 workgroup may take 160 KiB
+  const size_t lds = ((size_t)nlay * nlay + (size_t)kmax * nlay + kmax + (size_t)nlay * ldc) * sizeof(double);
+  const void *kfn = kern_fp32 ? (const void *)k_column_res<float> : (const void *)k_column_res<double>;
+  DZ_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (a refusal ends the call: no launch)
+  const double s2 = (double)smooth * (double)smooth, d2 = (double)damp * (double)damp;
+  {
+    DzTimer t(ctx, "column_resolution");
+    if (kern_fp32)
+      hipLaunchKernelGGL(k_column_res<float>, dim3((unsigned)ncell), dim3(CL_WAVE), lds, ctx->stream, nx, ny, nlay, kmax, ldc, kf.dev,
+                         wdat.dev, s2, d2, depz.dev, sp.dev, sn.dev, rd.dev, rs.dev, wd.dev, rw.dev, tr.dev, (int *)pc);
+    else
+      hipLaunchKernelGGL(k_column_res<double>, dim3((unsigned)ncell), dim3(CL_WAVE), lds, ctx->stream, nx, ny, nlay, kmax, ldc, kd.dev,
+                         wdat.dev, s2, d2, depz.dev, sp.dev, sn.dev, rd.dev, rs.dev, wd.dev, rw.dev, tr.dev, (int *)pc);
+    DZ_HIP(hipGetLastError());
+    t.stop();
+  }
+  int cnt[2] = {0, 0};
+  DZ_HIP(hipMemcpyAsync(cnt, pc, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = sp.finish()) || (rc = sn.finish()) || (rc = rd.finish()) || (rc = rs.finish()) || (rc = wd.finish()) || (rc = rw.finish()) ||
+      (rc = tr.finish()))
+    return rc;
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (n_empty) *n_empty = cnt[0];
+  if (n_failed) *n_failed = cnt[1];
   return 0;
 }
 

@@ -643,7 +643,7 @@ __global__ void k_mc_gather(McDev M, long c0, long nb, float *__restrict__ out) 
 
 // One sample of the Gc/Gs sums, one wavefront per cold column c0 + blockIdx.x; lsen [nlay][kmax][nb] holds that column at index
 // blockIdx.x.  LDS as k_column_lsq with nrhs = 2.  After dz_column_solve lane k forms column k of R^-1 by itself, in the unused
-// strict upper triangle of A (row k), and with it (A^-1)_kk.
+// strict upper triangle of A (row k), and with it (A^-1)_kk: dz_column_inverse_factor, which k_column_res of column.hip calls too.
 __global__ __launch_bounds__(MC_WAVE) void k_mc_aniso(McDev M, McAniso S, const float *__restrict__ lsen, long c0, long nb) {
   extern __shared__ double mc_lds[];
   const int n = M.nlay, kmax = M.kmax, t = threadIdx.x;
@@ -678,15 +678,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_aniso(McDev M, McAniso S, const 
   }
   if (t < n) {
     const int k = t;
-    const double yk = 1.0 / A[k * n + k];
-    double dg = yk * yk;
-    for (int i = k + 1; i < n; i++) {
-      double s = A[i * n + k] * yk;
-      for (int j = k + 1; j < i; j++) s += A[i * n + j] * A[k * n + j];
-      const double yi = -s / A[i * n + i];
-      A[k * n + i] = yi;
-      dg += yi * yi;
-    }
+    const double dg = dz_column_inverse_factor(k, n, A);
     const double xc = b[k], xs = b[n + k];
     const long o = (long)k * ncolc + cc, pl = (long)n * ncolc;
     S.asum[o] += xc;

@@ -226,6 +226,24 @@ __device__ __forceinline__ bool dz_column_solve(int t, int n, int kmax, int nrhs
   return ok;
 }
 
+// Column k of the inverse factor M = R^-1 of dz_column_solve's A = R R^T, formed by lane k alone by forward substitution on e_k:
+// y_k = 1 / R_kk, y_i = -(sum_{j=k..i-1} R_ij y_j) / R_ii.  y_i for i > k goes to A[k*n + i], the strict upper triangle of A that the
+// factorisation never touches (row k belongs to lane k, so the lanes need no barrier among themselves); the diagonal keeps R_kk.
+// Returns (A^-1)_kk = sum_{i=k..n-1} y_i^2 in ascending i.  k_mc_aniso (column_mc.hip) and k_column_res (column.hip) both call it,
+// so the Monte-Carlo pass's conditional variance and the depth program's posterior variance are the same bits.
+__device__ __forceinline__ double dz_column_inverse_factor(int k, int n, double *A) {
+  const double yk = 1.0 / A[k * n + k];
+  double dg = yk * yk;
+  for (int i = k + 1; i < n; i++) {
+    double s = A[i * n + k] * yk;
+    for (int j = k + 1; j < i; j++) s += A[i * n + j] * A[k * n + j];
+    const double yi = -s / A[i * n + i];
+    A[k * n + i] = yi;
+    dg += yi * yi;
+  }
+  return dg;
+}
+
 // The refined layer table of a column model, refineGrid2LayerMdl (inv/CalSurfG.f90:2339-2365) in its fp32 expressions: the interval
 // between knots i and i + 1 (iv = i, 1-based) becomes nsub sublayers, sublayer j with the weights fm / den = (2j - 1) / (2 nsub) and the
 // thickness thk; the last row is the half-space (iv = 0).  dazim_dispersion_kernels and dazim_ti_kernels build their tables on it.

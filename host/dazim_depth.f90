@@ -2,7 +2,7 @@
 ! SurfPhaseMaps_amd into a depth model, cell by cell, on one MI355X: Vs(z) from each cell's phase-velocity dispersion curve and, in
 ! iso-mode F, Gc/L(z) and Gs/L(z) from its 2-psi curves (DESIGN.md section 13).
 !
-!   SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c]]]
+!   SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c [resolution]]]]
 !
 ! Inputs: the unchanged para.in and MOD of DAzimSurfTomo_amd (read_para, read_mod of module dazim_io; the data file is not opened),
 ! the maps period_phaseV_map.dat (and period_Azm_tomo_map.inv in iso-mode F) and, if present, period_map_coverage.dat.  Weights:
@@ -12,12 +12,21 @@
 ! inner cells (w = 0 where pvRc = 0) -> dazim_column_lsq (nlay = nz-1) -> dazim_model_update (para.in's minvel, maxvel).
 ! Gc, Gs (iso-mode F): on the final Vs, dazim_ti_kernels, then one dazim_column_lsq on Lsen_Gsc with the two right-hand sides a1, a2:
 ! the 2-psi terms are linear in Gc, Gs, so they are solved for whole.
+! resolution = 1 (default 0: nothing below is computed or written): how well the answer is known, per inner cell and inverted knot,
+! from dazim_column_resolution on the final model: one more dazim_dispersion_kernels with kernels, dazim_vs_kernels, then the
+! posterior std (the regulariser read as a Gaussian prior), the std that the data errors 1/w alone leave, the diagonal and the row
+! sum of the resolution matrix and the depth spread of its row, with the Vs solve's weights, smoothing and damping; in iso-mode F
+! the same on Lsen_Gsc with smooth_gcs (Gc and Gs share K, so they share the numbers).  These are the statistics of the last
+! linearised step: the regulariser acts on the update, not on the model.
 !
 ! Outputs (names distinct from the other programs' so that all three can share a directory; formats of DAzimSurfTomo_amd's files):
 !   DSurfTomo_2step.inv        as DSurfTomo.inv                MOD_2step     as MOD_Ref (a MOD for DAzimSurfTomo_amd)
 !   period_phaseV_2step.dat    c of the final model, as period_phaseV_map.dat
 !   Gc_Gs_model_2step.inv, period_Azm_tomo_2step.inv   (iso-mode F) as Gc_Gs_model.inv, period_Azm_tomo.inv
 !   <para>_2step.log + stdout  one line per iteration: cells used, RMS c misfit before and predicted after the solve, max |dVs|
+!   Vs_resolution_2step.dat    (resolution = 1) lon lat depth Vs std_post std_noise rdiag rsum width, one line per inner cell and
+!                              inverted knot in DSurfTomo_2step.inv's order
+!   Gc_Gs_resolution_2step.dat (resolution = 1, iso-mode F) the same without the Vs column
 program SurfDepthFromMaps_amd
   use iso_c_binding
   use dazim_mod
@@ -33,7 +42,10 @@ program SurfDepthFromMaps_amd
   real*8, allocatable, target :: pv(:, :), svs(:, :, :), svp(:, :, :), srho(:, :, :), skern(:, :, :)
   real, allocatable, target :: lsen(:, :, :)
   real, allocatable :: cmap(:, :, :), amap(:, :, :, :), wcov(:, :, :), w(:, :, :), r(:, :, :, :), x(:, :, :, :)
-  real, allocatable :: gcf(:, :, :), gsf(:, :, :), ustats(:, :), stats(:, :, :)
+  real, allocatable :: gcf(:, :, :), gsf(:, :, :), ustats(:, :), stats(:, :, :), res(:, :, :, :), rtrace(:, :)
+  real*8, allocatable :: pvk(:, :)
+  integer :: ires
+  integer(c_int) :: nbad
   real :: dummy1(1), rms0, rms1, maxdv
   real*8 :: s0, s1, cnt
   integer :: i, t, iter, nlay, nused, col, q
@@ -42,7 +54,7 @@ program SurfDepthFromMaps_amd
   write (*, *)
   write (*, *) '                       SurfDepthFromMaps'
   write (*, *)
-  if (command_argument_count() < 1) error stop 'usage: SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c]]]'
+  if (command_argument_count() < 1) error stop 'usage: SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c [resolution]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -56,6 +68,12 @@ program SurfDepthFromMaps_amd
   call optional_arg(3, smooth_gcs)
   call optional_arg(4, sigma_c)
   if (sigma_c <= 0) error stop 'sigma_c must be positive'
+  ires = 0
+  call optional_arg(5, ires)
+  if (ires /= 0 .and. ires /= 1) then
+    write (*, '(a,i0)') ' ERROR: resolution must be 0 or 1, not ', ires
+    error stop 'bad argument'
+  end if
   nlay = nz - 1
   if (nlay > 63) error stop 'SurfDepthFromMaps_amd inverts at most 63 layers (nz <= 64)'
   if (kmax > 60) error stop 'SurfDepthFromMaps_amd takes at most 60 periods'
@@ -119,6 +137,22 @@ program SurfDepthFromMaps_amd
     write (q, '(a,i7,a,f12.5)') ' final model: cells', nused, '  rms_c', rms0
   end do
 
+  ! ---- how well that Vs is known (resolution = 1): kernels at the final model, the last solve's weights and regularisers ----------
+  if (ires == 1) then
+    allocate (res(nx - 2, ny - 2, nlay, 5), rtrace(nx - 2, ny - 2), pvk(nx*ny, kmax))
+    call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pvk, c_loc(svs), c_loc(svp), &
+                                              c_loc(srho), nfail), 'depth kernels of the final model')
+    call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kmax, vsf, svs, svp, srho, skern), 'dc/dVs table of the final model')
+    call dazim_check(dazim_column_resolution(dazim_handle, nx, ny, nlay, kmax, 0, c_loc(skern), w, smooth_vs, damp, depz, &
+                                             res(:, :, :, 1), res(:, :, :, 2), res(:, :, :, 3), res(:, :, :, 4), res(:, :, :, 5), &
+                                             c_null_ptr, rtrace, nempty, nbad), 'column resolution (Vs)')
+    call write_resolution('Vs_resolution_2step.dat', p, depz, res, vsf)
+    do q = 6, 66, 60
+      write (q, '(a)') ' resolution: posterior std and resolution matrix of the last linearised step (the regulariser acts on the update)'
+    end do
+    call resolution_log('Vs   ')
+  end if
+
   ! ---- Gc, Gs on the final Vs (iso-mode F) ---------------------------------------------------------------------------------------
   if (.not. iso_mod) then
     allocate (lsen(nx*ny, kmax, nz - 1), gcf(nx - 2, ny - 2, nlay), gsf(nx - 2, ny - 2, nlay))
@@ -132,6 +166,13 @@ program SurfDepthFromMaps_amd
         '  rms misfit a1, a2', sqrt(sum(stats(2, :, 1)**2)/kmax), sqrt(sum(stats(2, :, 2)**2)/kmax)
       write (q, '(a,2f10.5)') ' max |Gc|, |Gs|:', maxval(abs(gcf)), maxval(abs(gsf))
     end do
+    if (ires == 1) then
+      call dazim_check(dazim_column_resolution(dazim_handle, nx, ny, nlay, kmax, 1, c_loc(lsen), w, smooth_gcs, damp, depz, &
+                                               res(:, :, :, 1), res(:, :, :, 2), res(:, :, :, 3), res(:, :, :, 4), res(:, :, :, 5), &
+                                               c_null_ptr, rtrace, nempty, nbad), 'column resolution (Gc, Gs)')
+      call write_resolution('Gc_Gs_resolution_2step.dat', p, depz, res)
+      call resolution_log('Gc/Gs')
+    end if
   end if
 
   ! ---- output files, in the formats of DAzimSurfTomo_amd's (dazim_main.f90) --------------------------------------------------------
@@ -148,6 +189,37 @@ program SurfDepthFromMaps_amd
   call dazim_finalize()
 
 contains
+
+  ! one log line of a dazim_column_resolution call: the cells it used, and the median and the minimum over them of trace(R) / nlay,
+  ! the share of the cell's knots that the data resolve
+  subroutine resolution_log(what)
+    character(len=*), intent(in) :: what
+    real, allocatable :: s(:)
+    real :: v
+    integer :: m, gap, i1, j1
+    s = pack(rtrace, any(w /= 0.0, dim=3))/nlay
+    m = size(s)
+    gap = m/2
+    do while (gap > 0)                              ! Shell sort
+      do i1 = gap + 1, m
+        v = s(i1); j1 = i1
+        do while (j1 > gap)
+          if (s(j1 - gap) <= v) exit
+          s(j1) = s(j1 - gap); j1 = j1 - gap
+        end do
+        s(j1) = v
+      end do
+      gap = gap/2
+    end do
+    do q = 6, 66, 60
+      if (m > 0) then
+        write (q, '(a,a,a,i7,a,i5,a,2f9.5)') ' resolution ', what, ': cells', m, '  not factored', nbad, &
+          '  trace(R)/nlay median, min', s((m + 1)/2), s(1)
+      else
+        write (q, '(a,a,a,i7)') ' resolution ', what, ': cells', m
+      end if
+    end do
+  end subroutine
 
   ! w = 1/sigma_c where the map has coverage and pvRc is not 0, r = c_map - pvRc on the inner cells; rms0 over the pairs with w > 0,
   ! cnt of those pairs, nused = cells with at least one

@@ -8,6 +8,7 @@ module dazim_io
   private
   public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
   public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
+  public :: write_resolution
 
   real, parameter :: pi = 3.1415926535898
   real*8, parameter :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
@@ -340,6 +341,27 @@ contains
       do j1 = 1, p%ny - 2
         do i1 = 1, p%nx - 2
           write (u, '(5f10.4)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), c(i1, j1, t1)
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! dazim_column_resolution's numbers, one line per inner cell and inverted knot in write_vs_model's order (knot, then row, then
+  ! column): lon lat depth of the knot, Vs there (only with vs), std_post std_noise rdiag rsum width = res(:, :, :, 1:5)
+  subroutine write_resolution(fname, p, depz, res, vs)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real, intent(in) :: depz(:), res(:, :, :, :)
+    real, intent(in), optional :: vs(:, :, :)
+    integer :: u, k1, j1, i1
+    open (newunit=u, file=fname, status='replace', action='write')
+    do k1 = 1, size(res, 3)
+      do j1 = 1, p%ny - 2
+        do i1 = 1, p%nx - 2
+          write (u, '(3f10.4)', advance='no') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, depz(k1)
+          if (present(vs)) write (u, '(f8.4)', advance='no') vs(i1 + 1, j1 + 1, k1)
+          write (u, '(2f10.5,2f10.4,f10.2)') res(i1, j1, k1, 1:5)
         end do
       end do
     end do

@@ -35,7 +35,7 @@ module dazim_mod
   public :: dazim_dispersion_kernels, dazim_rays_build_G_maps, dazim_csr_append_laplacian2d, dazim_phase_map_update, &
             dazim_assemble_G_maps
   ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
-  public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq
+  public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq, dazim_column_resolution
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
   public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
             dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds, &
@@ -218,6 +218,16 @@ module dazim_mod
       real(c_float), value :: smooth, damp
       real(c_float) :: rhs(*), wdat(*), x(*), stats(*)
       integer(c_int) :: n_empty
+    end function
+    ! rows: c_loc of an [nx-2][ny-2][nlay][nlay] array, or c_null_ptr
+    integer(c_int) function dazim_column_resolution(ctx, nx, ny, nlay, kmax, kern_fp32, kern, wdat, smooth, damp, depz, std_post, &
+        std_noise, rdiag, rsum, width, rows, trace, n_empty, n_failed) bind(C, name="dazim_column_resolution")
+      import
+      type(c_ptr), value :: ctx, kern, rows
+      integer(c_int), value :: nx, ny, nlay, kmax, kern_fp32
+      real(c_float), value :: smooth, damp
+      real(c_float) :: wdat(*), depz(*), std_post(*), std_noise(*), rdiag(*), rsum(*), width(*), trace(*)
+      integer(c_int) :: n_empty, n_failed
     end function
     ! Monte-Carlo Vs per map cell (include/dazim.h): mc is the opaque handle; arrays in the C layouts given there
     integer(c_int) function dazim_mc_create(ctx, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step, nadapt, &

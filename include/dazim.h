@@ -282,6 +282,29 @@ int dazim_vs_kernels(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, const flo
 int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int kern_fp32, const void *kern, int nrhs, const float *rhs,
                      const float *wdat, float smooth, float damp, float *x, int *n_empty, float *stats);
 
+/* dazim_column_resolution: how well dazim_column_lsq's answer is known, per inner cell and knot, from the same Cholesky factor.
+ *   kern, kern_fp32, wdat, smooth, damp, nlay, kmax as in dazim_column_lsq.  Per cell, with W = diag(w), L the depth rule:
+ *     P = smooth^2 L^T L + damp^2 I      A = K^T W^2 K + P = R R^T      M = R^-1      C = A^-1 = M^T M
+ *     Rm = C K^T W^2 K = I - C P         (the resolution matrix: x_est = Rm x_true for noise-free data r = K x_true)
+ *   std_post [nlay][ny-2][nx-2]  = sqrt(C_aa): the posterior std when the regulariser is read as a Gaussian prior of precision P
+ *                                  and the data errors have std 1/w (the reading of dazim_mc_aniso_result's conditional std)
+ *   std_noise                    = sqrt((Rm C)_aa) = sqrt((C K^T W^2 K C)_aa): data errors of std 1/w carried through the
+ *                                  estimator alone, <= std_post; summed as sum_p w_p^2 (sum_c C_ac K_pc)^2
+ *   rdiag                        = Rm_aa         rsum = sum_c Rm_ac
+ *   width                        = sqrt(sum_c Rm_ac^2 (z_c - z_a)^2 / sum_c Rm_ac^2), z = depz [nlay] (host or device); 0 if the
+ *                                  denominator is 0.  width and depz are both given or both NULL.
+ *   rows [nlay][nlay][ny-2][nx-2] (nullable): rows[a][c] = Rm_ac, row a the averaging kernel of knot a
+ *   trace [ny-2][nx-2] (nullable) = sum_a Rm_aa, the number of model parameters the cell's data resolve
+ *   C_ac = sum_{i >= max(a, c)} M_ia M_ic in ascending i; C_aa is the (A^-1)(a,a) that dazim_mc_aniso_step adds to avar, bit for
+ *   bit.  Rm_ac takes the five C_ae, |e - c| <= 2, in ascending e.  fp64 throughout, every sum in a fixed order, each value rounded
+ *   to fp32 once; host and device arguments give the same bits.  A cell whose weights are all 0 gets 0 in every output and is
+ *   counted in n_empty; a cell whose factorisation meets a pivot that is not finite and > 0 (non-finite kernels) gets NaN in every
+ *   output and is counted in n_failed (both host, nullable).  Refused (DAZIM_E_BAD_ARG): what dazim_column_lsq refuses, a missing
+ *   std_post, std_noise, rdiag or rsum, and width without depz or depz without width.  One launch, one wavefront per cell.   */
+int dazim_column_resolution(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int kern_fp32, const void *kern, const float *wdat,
+                            float smooth, float damp, const float *depz, float *std_post, float *std_noise, float *rdiag, float *rsum,
+                            float *width, float *rows, float *trace, int *n_empty, int *n_failed);
+
 /* ---- Monte-Carlo Vs per map cell: posterior mean, spread and credible interval ----------------------------
  * Random-walk Metropolis chains on the knots 0..nlay-1 (nlay = nz - 1) of each inner cell's Vs column, the last knot held at vel0's
  * value; the forward model is dazim_dispersion_kernels with sen_* = NULL.  Prior: uniform on [vmin, vmax] per cell and knot.

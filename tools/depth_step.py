@@ -5,8 +5,12 @@
 On bench.py's S-256 model grid (54 x 54 columns, 12 knots, 16 periods) and on an N x N grid of the same model (default 202: 200 x 200
 inner cells), every array on the device, R rounds of: the dispersion call with kernels (kernel seconds "disp"; "disp.copies" too
 where the perturbed copies ran on the auxiliary stream), dazim_vs_kernels ("vs_kernels"), dazim_column_lsq with the fp64 table and
-one right-hand side and with the fp32 Lsen_Gsc table and two ("column_lsq").  Kernel seconds are dazim_last_kernel_seconds (HIP
-events on the context stream).  Prints one JSON line per grid with the medians and the ratio solve / dispersion."""
+one right-hand side and with the fp32 Lsen_Gsc table and two ("column_lsq"), and dazim_column_resolution beside each solve, on the
+same table with the same weights and regularisers, without and with the rows ("column_resolution").  Kernel seconds are
+dazim_last_kernel_seconds (HIP events on the context stream).  Prints one JSON line per grid with the medians and the ratio solve /
+dispersion, then one line for the solve and the resolution call at nlay 31, 32, 33 and 63 on random tables (16 periods, the big
+grid): an even nlay is where the lanes' reads along the rows of the [nlay][nlay] matrix meet in the same LDS banks
+(profiles/depth_resolution.md)."""
 import argparse
 import json
 import os
@@ -36,7 +40,9 @@ def one_grid(ctx, n, reps):
     skern = ctx.vs_kernels(vel, sen)
     x1 = torch.empty((1, nlay, n - 2, n - 2), dtype=torch.float32, device=dev)
     x2 = torch.empty((2, nlay, n - 2, n - 2), dtype=torch.float32, device=dev)
-    runs = {"disp_s": [], "disp_copies_s": [], "vs_kernels_s": [], "column_lsq_fp64_nrhs1_s": [], "column_lsq_fp32_nrhs2_s": []}
+    depz = T(np.asarray(bench.DEPZ, np.float32)[:nlay])
+    runs = {"disp_s": [], "disp_copies_s": [], "vs_kernels_s": [], "column_lsq_fp64_nrhs1_s": [], "column_lsq_fp32_nrhs2_s": [],
+            "column_resolution_fp64_s": [], "column_resolution_fp64_rows_s": [], "column_resolution_fp32_s": []}
     for rep in range(reps + 1):   # (round 0: warm-up -- code objects, scratch buffers)
         ctx.depthkernel(vel, bench.DEPZ, bench.PERIODS, bench.MINTHK, pv=pv, sen=sen)
         ctx.sync()
@@ -47,15 +53,49 @@ def one_grid(ctx, n, reps):
         t["column_lsq_fp64_nrhs1_s"] = ctx.kernel_seconds("column_lsq")
         ctx.column_lsq(n, n, nlay, lsen, r2, w, 2.0, 0.0, x=x2)
         t["column_lsq_fp32_nrhs2_s"] = ctx.kernel_seconds("column_lsq")
+        res = ctx.column_resolution(n, n, nlay, skern, w, 2.0, 0.0, depz=depz)
+        t["column_resolution_fp64_s"] = ctx.kernel_seconds("column_resolution")
+        ctx.column_resolution(n, n, nlay, skern, w, 2.0, 0.0, depz=depz, rows=True)
+        t["column_resolution_fp64_rows_s"] = ctx.kernel_seconds("column_resolution")
+        ctx.column_resolution(n, n, nlay, lsen, w, 2.0, 0.0, depz=depz)
+        t["column_resolution_fp32_s"] = ctx.kernel_seconds("column_resolution")
         if rep:
             for k, v in t.items():
                 runs[k].append(v)
     med = {k: float(np.median(v)) for k, v in runs.items()}
     disp = med["disp_s"] + max(med["disp_copies_s"], 0.0)
-    assert torch.isfinite(x1).all() and torch.isfinite(x2).all()
+    assert torch.isfinite(x1).all() and torch.isfinite(x2).all() and torch.isfinite(res["std_post"]).all() and res["n_failed"] == 0
     return {"grid": f"{n}x{n} columns ({ncell} inner cells), {nz} knots, {kmax} periods", "reps": reps, "median": med,
             "solve_fp64_over_disp": med["column_lsq_fp64_nrhs1_s"] / disp, "solve_fp32_over_disp": med["column_lsq_fp32_nrhs2_s"] / disp,
             "runs": runs}
+
+
+def nlay_sweep(ctx, n, reps, kmax=16):
+    """the solve and the resolution call at nlay 31, 32, 33 and 63, random fp64 tables: medians of `reps` rounds after a warm-up"""
+    import torch
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(2)
+    out = {}
+    for nlay in (31, 32, 33, 63):
+        kern = torch.from_numpy(rng.standard_normal((nlay, kmax, n * n))).to(dev)
+        r = torch.from_numpy(rng.standard_normal((1, kmax, n - 2, n - 2)).astype(np.float32)).to(dev)
+        depz = torch.arange(nlay, dtype=torch.float32, device=dev)
+        x = torch.empty((1, nlay, n - 2, n - 2), dtype=torch.float32, device=dev)
+        runs = {"column_lsq_s": [], "column_resolution_s": [], "column_resolution_rows_s": []}
+        for i in range(reps + 1):
+            ctx.column_lsq(n, n, nlay, kern, r, None, 0.7, 0.3, x=x)
+            t = {"column_lsq_s": ctx.kernel_seconds("column_lsq")}
+            ctx.column_resolution(n, n, nlay, kern, None, 0.7, 0.3, depz=depz)
+            t["column_resolution_s"] = ctx.kernel_seconds("column_resolution")
+            if nlay < 63:                              # (the rows of 40 000 cells at nlay 63 are 635 MB: left out)
+                ctx.column_resolution(n, n, nlay, kern, None, 0.7, 0.3, depz=depz, rows=True)
+                t["column_resolution_rows_s"] = ctx.kernel_seconds("column_resolution")
+            if i:
+                for k, v in t.items():
+                    runs[k].append(v)
+        out[f"nlay{nlay}"] = {k: float(np.median(v)) for k, v in runs.items() if v}
+        del kern, r, x
+    return {"sweep": f"{n}x{n} columns, {kmax} periods, random fp64 tables, smooth 0.7, damp 0.3", "reps": reps, "median": out}
 
 
 def main():
@@ -67,6 +107,7 @@ def main():
     ctx = dz.Context(0)
     for n in (54, a.big):
         print(json.dumps(one_grid(ctx, n, a.reps)), flush=True)
+    print(json.dumps(nlay_sweep(ctx, a.big, a.reps)), flush=True)
     ctx.close()
 
 
