@@ -12,100 +12,20 @@
 // to the power beta_r, and neighbouring rungs of a group exchange their states.  A group's rungs are neighbouring lanes of the cell's
 // wavefront, so a swap is a lane shuffle inside k_mc_step<KIND, 1>; only the rung-0 chains are recorded.
 //
-// Gc/Gs posteriors (dazim_mc_set_aniso): conditional on a Vs column the Gc/Gs posterior is the Gaussian of dazim_column_lsq's normal
-// equations, so the chains' thinned rung-0 states give its marginal by averaging the conditional mean and covariance
-// (Rao-Blackwellisation).  k_mc_gather copies the rung-0 states into a compact table, k_mc_aniso solves one wavefront per such
-// column with dz_column_solve and adds to the column's own sums, k_mc_aniso_final reduces them per cell.  The pass only reads the
-// chains.
+// Gc/Gs posteriors (dazim_mc_set_aniso) are column_mc_aniso.hip's: a pass that only reads the chains, and that dazim_mc_run reaches
+// through mc_internal.h, which also holds the handle, its device view McDev, the constants and the random numbers.
 //
 // Hierarchical data noise (dazim_mc_set_noise): the data std of a cell is lambda / w_p with lambda^2 ~ InverseGamma(a0, b0), and
 // lambda is integrated out in closed form: k_mc_step<KIND, TEMPER, 1> takes every decision on the energy X = 2 a log(b0 + chi^2 / 2)
 // in place of chi^2 (mc_energy), each recorded rung-0 lane adds sqrt(B) and B = b0 + chi^2 / 2 of its state to its own column, and
 // k_mc_noise_final turns those sums into the posterior mean and std of lambda per cell (Rao-Blackwellisation again).
-#include "dazim_internal.h"
+#include "mc_internal.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 
 namespace {
-
-constexpr int MC_WAVE = 64, MC_MAXLAY = 63, MC_MAXPER = 60, MC_MAXCHAIN = 64;
-// Reflections of a proposal into its box.  u >= 2^-33 bounds |z| by sqrt(66 ln 2) < 6.77, and s <= 0.5 (dazim_mc_create refuses a
-// larger start, the adaptation keeps it there) bounds the step by 3.39 box widths; each pass takes one width off the excess, so 4
-// passes always suffice.  The cap and the clamp behind it only make the loop's bound visible: they never act on a valid handle.
-// With the covariance proposal (kind 1) the step is s (hi - lo) y_k, y = L z: u in [0, 1] bounds C_kk, the squared norm of row k of L,
-// by 1/4 + 1e-8; each Box-Muller pair has norm r <= 6.77, so |z|_2 <= 6.77 sqrt(ceil(nlay / 2)); s <= 2 / sqrt(nlay).  Together
-// |s y_k| <= 2 * 0.50000001 * 6.77 * sqrt(ceil(nlay / 2) / nlay) < 6.78 box widths (the ratio is 1 at nlay = 1, less above): at most 7
-// passes, still below the cap.
-constexpr int MC_MAXFOLD = 8;
-constexpr float MC_SMIN = 1e-3f, MC_SMAX = 0.5f;
-// kind 1: states per knot a window must hold before it is factored, and the ridge on the diagonal of the covariance
-constexpr int MC_COV_MIN = 8;
-constexpr double MC_COV_RIDGE = 1e-8;
-
-// Philox4x32-10 (Salmon et al., SC'11): c = counter in, block out; key (k0, k1) = the seed's low and high words
-__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
-  for (int r = 0; r < 10; r++) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
-    const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0, hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
-    c[0] = hi1 ^ c[1] ^ k0;
-    c[1] = lo1;
-    c[2] = hi0 ^ c[3] ^ k1;
-    c[3] = lo0;
-  }
-}
-
-__device__ __forceinline__ void mc_block(unsigned w[4], long long step, unsigned gid, unsigned blk, unsigned long long seed) {
-  w[0] = (unsigned)step;
-  w[1] = gid;
-  w[2] = blk;
-  w[3] = 0u;
-  philox4x32_10(w, (unsigned)seed, (unsigned)(seed >> 32));
-}
-
-__device__ __forceinline__ double mc_uniform(unsigned w) { return ((double)w + 0.5) * 2.3283064365386962890625e-10; }   // (w + 0.5) 2^-32
-
-struct McDev {
-  int nx, ny, nz, nlay, kmax, nchain, nbin, ncell, ncs;
-  long ncol;
-  unsigned long long seed;
-  const int *cell_of;          // [ncs] inner-cell index of each sampled cell
-  const int *cs_of;            // [ncell] sampled index of each inner cell, -1 = no data
-  const float *vel0;           // [nz][ny][nx]
-  const float *vmin, *vmax;    // [nlay][ncell]
-  const float *cobs, *wdat;    // [kmax][ncell]
-  float *cur, *prop;           // [nz][ncol]
-  double *chi2;                // [ncol]
-  float *scale;                // [ncs]
-  int *acc_win;                // [ncs]
-  double *sums;                // [2][nlay][ncol]
-  unsigned *hist;              // [ncs][nlay][nbin]
-  long long *accepted;         // [ncol]
-  float *best;                 // [nlay][ncs]
-  double *best_chi2;           // [ncs]
-  unsigned long long *counters;   // [0] proposals without a root, [1] accepted moves of recorded steps
-  // kind 1 only (null otherwise); npair = nlay (nlay + 1) / 2, pair (a, c), c <= a, at a (a + 1) / 2 + c
-  long long *cov_n;            // [ncs] states in the sums
-  double *cov_s1, *cov_s2;     // [ncs][nlay], [ncs][npair]: sums of u and of u_a u_c, u the state in box units
-  double *chol;                // [ncs][npair]: the lower factor of the last covariance that factored
-  int *cov_set;                // [ncs]: 1 once chol holds a factor
-  // tempering only (ntemp = 1 and null otherwise); while it is on, scale [ncs] follows rung 0 of tscale
-  int ntemp, nswap;
-  const double *beta;          // [ntemp]
-  float *tscale;               // [ncs][ntemp]
-  int *tacc_win;               // [ncs][ntemp]
-  long long *swap_try, *swap_acc;   // [ncs][ntemp - 1]
-  // hierarchical noise only (null otherwise): lambda^2 ~ InverseGamma(na0, nb0) a priori
-  float na0, nb0;
-  double *nsum;                // [2][ncol]: sums of sqrt(B) and of B over the recorded states, B = nb0 + chi^2 / 2
-  long long *ncnt;             // [ncol]: states in them
-  const double *ngam;          // [MC_MAXPER + 1]: exp(lgamma(a - 0.5) - lgamma(a)) at a = na0 + nd / 2, made on the host
-};
 
 // the energy a decision is taken on: chi^2 itself, or with the noise scale integrated out X = 2 a log(B(chi^2)), +inf at +inf
 template <int NOISE>
@@ -121,32 +41,59 @@ __device__ __forceinline__ unsigned long long mc_rung_mask(int nchain, int ntemp
   return m;
 }
 
-// the next proposal of chain (cs, ch) from its current state: v' = v + s (vmax - vmin) z in fp64, reflected into the box, fp32
+// the box of knot k of inner cell `cell`
+struct McBox { double lo, hi; };
+__device__ __forceinline__ McBox mc_box(const McDev &M, int cell, int k) {
+  const long o = (long)k * M.ncell + cell;
+  return {(double)M.vmin[o], (double)M.vmax[o]};
+}
+
+// the four standard normals of Philox block 1 + q of chain gid at `step`, knots 4 q .. 4 q + 3 (Box-Muller, two pairs; block 0
+// decides and swaps)
+struct McNormals { double z[4]; };
+__device__ __forceinline__ McNormals mc_normals(const McDev &M, long long step, unsigned gid, int q) {
+  unsigned w[4];
+  mc_block(w, step, gid, 1u + (unsigned)q, M.seed);
+  const double r0 = sqrt(-2.0 * log(mc_uniform(w[0]))), t0 = 6.283185307179586 * mc_uniform(w[1]);
+  const double r1 = sqrt(-2.0 * log(mc_uniform(w[2]))), t1 = 6.283185307179586 * mc_uniform(w[3]);
+  return {{r0 * cos(t0), r0 * sin(t0), r1 * cos(t1), r1 * sin(t1)}};
+}
+
+// knot k of the next proposal of column col: v' = v + s (vmax - vmin) y in fp64, reflected into the box, fp32
+__device__ __forceinline__ void mc_store_proposal(const McDev &M, int cell, long col, int k, float s, double y) {
+  const McBox b = mc_box(M, cell, k);
+  const double d = (double)s * (b.hi - b.lo);
+  double v = (double)M.cur[k * M.ncol + col] + d * y;
+  for (int r = 0; r < MC_MAXFOLD && (v < b.lo || v > b.hi); r++) v = v < b.lo ? 2.0 * b.lo - v : 2.0 * b.hi - v;
+  M.prop[k * M.ncol + col] = (float)fmin(fmax(v, b.lo), b.hi);
+}
+
+// the next proposal of chain (cs, ch) from its current state, isotropic in box units: y = z
 __device__ void mc_propose(const McDev &M, int cs, int ch, long long step, float s) {
   const int cell = M.cell_of[cs];
   const long col = (long)cs * M.nchain + ch;
   const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
   for (int q = 0; q * 4 < M.nlay; q++) {
-    unsigned w[4];
-    mc_block(w, step, gid, 1u + (unsigned)q, M.seed);
-    const double r0 = sqrt(-2.0 * log(mc_uniform(w[0]))), t0 = 6.283185307179586 * mc_uniform(w[1]);
-    const double r1 = sqrt(-2.0 * log(mc_uniform(w[2]))), t1 = 6.283185307179586 * mc_uniform(w[3]);
-    const double z[4] = {r0 * cos(t0), r0 * sin(t0), r1 * cos(t1), r1 * sin(t1)};
-    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) {
-      const int k = q * 4 + i;
-      const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
-      const double d = (double)s * (hi - lo);
-      double v = (double)M.cur[k * M.ncol + col] + d * z[i];
-      for (int r = 0; r < MC_MAXFOLD && (v < lo || v > hi); r++) v = v < lo ? 2.0 * lo - v : 2.0 * hi - v;
-      M.prop[k * M.ncol + col] = (float)fmin(fmax(v, lo), hi);
-    }
+    const McNormals n = mc_normals(M, step, gid, q);
+    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) mc_store_proposal(M, cell, col, q * 4 + i, s, n.z[i]);
   }
 }
 
-__device__ __forceinline__ int mc_pair_row(int e) {   // the row a of packed pair e
-  int a = 0;
+// the step scale at the end of an adaptation window: win accepted moves of ndec decisions (nadapt steps of the chains that share the
+// scale); a cell with a factor (kind 1) may go up to 2 / sqrt(nlay)
+__device__ __forceinline__ float mc_adapt_scale(float s, int win, double ndec, bool factor, int nlay) {
+  const double rate = (double)win / ndec;
+  if (rate > 0.40) s = s * 1.25f;
+  else if (rate < 0.20) s = s / 1.25f;
+  const float smax = factor ? 2.0f / sqrtf((float)nlay) : MC_SMAX;
+  return fminf(fmaxf(s, MC_SMIN), smax);
+}
+
+// packed pair e = a (a + 1) / 2 + c, c <= a
+__device__ __forceinline__ void mc_pair(int e, int &a, int &c) {
+  a = 0;
   while ((a + 1) * (a + 2) / 2 <= e) a++;
-  return a;
+  c = e - a * (a + 1) / 2;
 }
 
 // kind 1, a burn-in step with a decision: the cell's states us [nlay][nchain] (LDS) join the sums, pair e on lane e mod 64, the
@@ -156,12 +103,13 @@ __device__ void mc_cov_accumulate(const McDev &M, int cs, int ch, const float *u
   const int n = M.nlay, npair = n * (n + 1) / 2, nc = M.nchain, cell = M.cell_of[cs];
   double *s1 = M.cov_s1 + (long)cs * n, *s2 = M.cov_s2 + (long)cs * npair;
   for (int e = ch; e < npair; e += MC_WAVE) {
-    const int a = mc_pair_row(e), c = e - a * (a + 1) / 2;
-    const double loa = (double)M.vmin[(long)a * M.ncell + cell], wa = (double)M.vmax[(long)a * M.ncell + cell] - loa;
-    const double loc = (double)M.vmin[(long)c * M.ncell + cell], wc = (double)M.vmax[(long)c * M.ncell + cell] - loc;
+    int a, c;
+    mc_pair(e, a, c);
+    const McBox ba = mc_box(M, cell, a), bc = mc_box(M, cell, c);
+    const double wa = ba.hi - ba.lo, wc = bc.hi - bc.lo;
     double t1 = a == c ? s1[a] : 0.0, t2 = s2[e];
     for (int j = 0; j < nc; j += stride) {
-      const double ua = ((double)us[a * nc + j] - loa) / wa, uc = ((double)us[c * nc + j] - loc) / wc;
+      const double ua = ((double)us[a * nc + j] - ba.lo) / wa, uc = ((double)us[c * nc + j] - bc.lo) / wc;
       t1 += ua;
       t2 += ua * uc;
     }
@@ -179,7 +127,8 @@ __device__ bool mc_cov_factor(const McDev &M, int cs, int ch, long long cn, doub
   double *s1 = M.cov_s1 + (long)cs * n, *s2 = M.cov_s2 + (long)cs * npair;
   const double dn = (double)cn;
   for (int e = ch; e < npair; e += MC_WAVE) {
-    const int a = mc_pair_row(e), c = e - a * (a + 1) / 2;
+    int a, c;
+    mc_pair(e, a, c);
     double C = s2[e] / dn - (s1[a] / dn) * (s1[c] / dn);
     if (a == c) C += MC_COV_RIDGE;
     L[e] = C;
@@ -213,22 +162,14 @@ __device__ void mc_propose_cov(const McDev &M, int cs, int ch, long long step, f
   const long col = (long)cs * M.nchain + ch;
   const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
   for (int q = 0; q * 4 < M.nlay; q++) {
-    unsigned w[4];
-    mc_block(w, step, gid, 1u + (unsigned)q, M.seed);
-    const double r0 = sqrt(-2.0 * log(mc_uniform(w[0]))), t0 = 6.283185307179586 * mc_uniform(w[1]);
-    const double r1 = sqrt(-2.0 * log(mc_uniform(w[2]))), t1 = 6.283185307179586 * mc_uniform(w[3]);
-    const double z[4] = {r0 * cos(t0), r0 * sin(t0), r1 * cos(t1), r1 * sin(t1)};
-    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) zs[(q * 4 + i) * nc + ch] = z[i];
+    const McNormals n = mc_normals(M, step, gid, q);
+    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) zs[(q * 4 + i) * nc + ch] = n.z[i];
   }
   for (int k = 0; k < M.nlay; k++) {
     const double *Lk = L + k * (k + 1) / 2;
     double y = 0.0;
     for (int j = 0; j <= k; j++) y += Lk[j] * zs[j * nc + ch];
-    const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
-    const double d = (double)s * (hi - lo);
-    double v = (double)M.cur[k * M.ncol + col] + d * y;
-    for (int r = 0; r < MC_MAXFOLD && (v < lo || v > hi); r++) v = v < lo ? 2.0 * lo - v : 2.0 * hi - v;
-    M.prop[k * M.ncol + col] = (float)fmin(fmax(v, lo), hi);
+    mc_store_proposal(M, cell, col, k, s, y);
   }
 }
 
@@ -244,8 +185,8 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
     mc_block(w, 0, gid, 1u + (unsigned)q, M.seed);
     for (int e = 0; e < 4 && q * 4 + e < M.nlay; e++) {
       const int k = q * 4 + e;
-      const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
-      const float v = (float)(lo + (hi - lo) * mc_uniform(w[e]));
+      const McBox b = mc_box(M, cell, k);
+      const float v = (float)(b.lo + (b.hi - b.lo) * mc_uniform(w[e]));
       M.prop[k * M.ncol + col] = v;
       M.cur[k * M.ncol + col] = v;
     }
@@ -312,21 +253,17 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
     if (first) {
       acc = true;
     } else {
+      // a chain without a curve takes the first proposal that has one; else Metropolis on the energies at the rung's beta (1 without
+      // a ladder, which leaves the product's bits alone).  Where the first rule decides only a ladder draws block 0, for its word 1
       const double chi2c = M.chi2[col];
       const double xp = mc_energy<NOISE>(M, na, chi2p), xc = mc_energy<NOISE>(M, na, chi2c);
-      if constexpr (TEMPER) {
-        unsigned w[4];
-        mc_block(w, step, gid, 0u, M.seed);
-        wswap = w[1];
-        chi2s = chi2c;
-        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * M.beta[rung] * (xp - xc);
-      } else if (isinf(chi2c)) {
-        acc = !isinf(chi2p);
-      } else {
-        unsigned w[4];
-        mc_block(w, step, gid, 0u, M.seed);
-        acc = log(mc_uniform(w[0])) < -0.5 * (xp - xc);
-      }
+      double beta = 1.0;
+      if constexpr (TEMPER) beta = M.beta[rung];
+      unsigned w[4] = {0u, 0u, 0u, 0u};
+      if (TEMPER || !isinf(chi2c)) mc_block(w, step, gid, 0u, M.seed);
+      wswap = w[1];
+      chi2s = chi2c;
+      acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * beta * (xp - xc);
     }
     if (acc) {
       for (int k = 0; k < M.nlay; k++) M.cur[k * M.ncol + col] = M.prop[k * M.ncol + col];
@@ -371,52 +308,27 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         M.swap_acc[(long)cs * (nt - 1) + ch] += __popcll(bswp & mask);
       }
     }
-    if (ch == 0 && nnoroot) atomicAdd(&M.counters[0], (unsigned long long)nnoroot);
-    if (ch < nt) {   // lane r keeps rung r's scale and window
-      const int nar = __popcll(bacc & mc_rung_mask(M.nchain, nt, ch));
-      const long o = (long)cs * nt + ch;
-      float s = M.tscale[o];
-      if (!record) {
-        int win = M.tacc_win[o] + nar;
-        if (adapt) {
-          const double rate = (double)win / ((double)nadapt * (double)(M.nchain / nt));
-          if (rate > 0.40) s = s * 1.25f;
-          else if (rate < 0.20) s = s / 1.25f;
-          float smax = MC_SMAX;
-          if constexpr (KIND == 1)
-            if (M.cov_set[cs]) smax = 2.0f / sqrtf((float)M.nlay);
-          s = fminf(fmaxf(s, MC_SMIN), smax);
-          M.tscale[o] = s;
-          if (ch == 0) M.scale[cs] = s;
-          win = 0;
-        }
-        M.tacc_win[o] = win;
-      } else if (ch == 0 && nar) {
-        atomicAdd(&M.counters[1], (unsigned long long)nar);
-      }
-      s_rscale[ch] = s;
-    }
-  } else if (ch == 0) {
-    if (nnoroot) atomicAdd(&M.counters[0], (unsigned long long)nnoroot);
-    float s = M.scale[cs];
+  }
+  if (ch == 0 && nnoroot) atomicAdd(&M.counters[0], (unsigned long long)nnoroot);
+  if (ch < nt) {   // lane r keeps rung r's scale and window: the ladder's, or without one lane 0 the cell's own
+    const int nar = TEMPER ? __popcll(bacc & mc_rung_mask(M.nchain, nt, ch)) : nacc;
+    const long o = (long)cs * nt + ch;
+    float *sc = TEMPER ? M.tscale + o : M.scale + o;
+    int *wn = TEMPER ? M.tacc_win + o : M.acc_win + o;
+    float s = *sc;
     if (!record) {
-      int win = M.acc_win[cs] + nacc;
+      int win = *wn + nar;
       if (adapt) {
-        const double rate = (double)win / ((double)nadapt * (double)M.nchain);
-        if (rate > 0.40) s = s * 1.25f;
-        else if (rate < 0.20) s = s / 1.25f;
-        float smax = MC_SMAX;
-        if constexpr (KIND == 1)
-          if (M.cov_set[cs]) smax = 2.0f / sqrtf((float)M.nlay);
-        s = fminf(fmaxf(s, MC_SMIN), smax);
-        M.scale[cs] = s;
+        s = mc_adapt_scale(s, win, (double)nadapt * (double)(M.nchain / nt), KIND == 1 && M.cov_set[cs], M.nlay);
+        *sc = s;
+        if (TEMPER && ch == 0) M.scale[cs] = s;
         win = 0;
       }
-      M.acc_win[cs] = win;
-    } else if (nacc) {
-      atomicAdd(&M.counters[1], (unsigned long long)nacc);
+      *wn = win;
+    } else if (ch == 0 && nar) {
+      atomicAdd(&M.counters[1], (unsigned long long)nar);
     }
-    s_scale = s;
+    (TEMPER ? s_rscale[ch] : s_scale) = s;
   }
   if (record) {
     if (act && rung == 0) {
@@ -425,8 +337,8 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         const double v = (double)M.cur[k * M.ncol + col];
         M.sums[(long)k * M.ncol + col] += v;
         M.sums[((long)M.nlay + k) * M.ncol + col] += v * v;
-        const double lo = (double)M.vmin[(long)k * M.ncell + cell], hi = (double)M.vmax[(long)k * M.ncell + cell];
-        int b = (int)((v - lo) / (hi - lo) * (double)M.nbin);
+        const McBox bx = mc_box(M, cell, k);
+        int b = (int)((v - bx.lo) / (bx.hi - bx.lo) * (double)M.nbin);
         b = b < 0 ? 0 : (b >= M.nbin ? M.nbin - 1 : b);
         atomicAdd(&M.hist[((long)cs * M.nlay + k) * M.nbin + b], 1u);
       }
@@ -620,181 +532,10 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_noise_final(McDev M, float *__re
   lam_std[cell] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
 }
 
-// Gc/Gs (dazim_mc_set_aniso).  Cold column cs * ncold + g is chain g * ntemp of sampled cell cs.
-struct McAniso {
-  const float *amap;           // [2][kmax][ncell]
-  const float *wa;             // [kmax][ncell]
-  double s2, d2;
-  double *asum;                // [5][nlay][ncolc]
-  double *avar;                // [nlay][ncolc]
-  long long *acnt;             // [ncolc]
-  long long *askip;            // [ncolc]: samples of the column that were skipped
-};
-
-// cold columns c0 .. c0 + nb - 1 of the current states into out [nz][nb]
-__global__ void k_mc_gather(McDev M, long c0, long nb, float *__restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)M.nz * nb) return;
-  const long k = i / nb, cc = c0 + (i - k * nb);
-  const int ncold = M.nchain / M.ntemp;
-  const long cs = cc / ncold, g = cc - cs * ncold;
-  out[i] = M.cur[k * M.ncol + cs * M.nchain + g * M.ntemp];
-}
-
-// One sample of the Gc/Gs sums, one wavefront per cold column c0 + blockIdx.x; lsen [nlay][kmax][nb] holds that column at index
-// blockIdx.x.  LDS as k_column_lsq with nrhs = 2.  After dz_column_solve lane k forms column k of R^-1 by itself, in the unused
-// strict upper triangle of A (row k), and with it (A^-1)_kk: dz_column_inverse_factor, which k_column_res of column.hip calls too.
-__global__ __launch_bounds__(MC_WAVE) void k_mc_aniso(McDev M, McAniso S, const float *__restrict__ lsen, long c0, long nb) {
-  extern __shared__ double mc_lds[];
-  const int n = M.nlay, kmax = M.kmax, t = threadIdx.x;
-  double *A = mc_lds;
-  double *K = A + n * n;
-  double *w2 = K + kmax * n;
-  double *wr = w2 + kmax;
-  double *b = wr + 2 * kmax;
-  const int ncold = M.nchain / M.ntemp;
-  const long lc = blockIdx.x, cc = c0 + lc, ncolc = (long)M.ncs * ncold;
-  const long cs = cc / ncold, g = cc - cs * ncold;
-  const int cell = M.cell_of[cs];
-  if (isinf(M.chi2[cs * M.nchain + g * M.ntemp])) {   // the chain has no curve yet: no sample
-    if (t == 0) S.askip[cc] += 1;
-    return;
-  }
-  if (t < kmax) {
-    const float w = S.wa[(long)t * M.ncell + cell];
-    const double ww = (double)w * (double)w;
-    w2[t] = ww;
-    for (int r = 0; r < 2; r++) wr[r * kmax + t] = w != 0.0f ? ww * (double)S.amap[((long)r * kmax + t) * M.ncell + cell] : 0.0;
-  }
-  for (int q = t; q < n * kmax; q += MC_WAVE) {   // q = l*kmax + p, the table's own order
-    const int l = q / kmax, p = q - l * kmax;
-    K[p * n + l] = (double)lsen[(long)q * nb + lc];
-  }
-  __syncthreads();
-  const bool ok = dz_column_solve(t, n, kmax, 2, A, K, w2, wr, b, S.s2, S.d2);
-  if (!ok) {
-    if (t == 0) S.askip[cc] += 1;
-    return;
-  }
-  if (t < n) {
-    const int k = t;
-    const double dg = dz_column_inverse_factor(k, n, A);
-    const double xc = b[k], xs = b[n + k];
-    const long o = (long)k * ncolc + cc, pl = (long)n * ncolc;
-    S.asum[o] += xc;
-    S.asum[pl + o] += xs;
-    S.asum[2 * pl + o] += xc * xc;
-    S.asum[3 * pl + o] += xs * xs;
-    S.asum[4 * pl + o] += xc * xs;
-    S.avar[o] += dg;
-  }
-  if (t == 0) S.acnt[cc] += 1;
-}
-
-// the Gc/Gs statistics, one wavefront per inner cell, lane = knot; the cold columns of the cell in column order inside the lane
-__global__ __launch_bounds__(MC_WAVE) void k_mc_aniso_final(McDev M, McAniso S, float *__restrict__ mean, float *__restrict__ stdv,
-                                                            float *__restrict__ stdb, float *__restrict__ cov,
-                                                            long long *__restrict__ nsamp) {
-  const int cell = blockIdx.x, k = threadIdx.x;
-  const int cs = M.cs_of[cell];
-  const long o = (long)k * M.ncell + cell, nk = (long)M.nlay * M.ncell;
-  if (cs < 0) {
-    if (k < M.nlay) {
-      mean[o] = mean[nk + o] = 0.0f;
-      stdv[o] = stdv[nk + o] = 0.0f;
-      stdb[o] = stdb[nk + o] = 0.0f;
-      cov[o] = 0.0f;
-    }
-    if (k == 0) nsamp[cell] = 0;
-    return;
-  }
-  const int ncold = M.nchain / M.ntemp;
-  const long ncolc = (long)M.ncs * ncold, pl = (long)M.nlay * ncolc;
-  long long cnt = 0;
-  for (int g = 0; g < ncold; g++) cnt += S.acnt[(long)cs * ncold + g];
-  if (k == 0) nsamp[cell] = cnt;
-  if (k >= M.nlay) return;
-  if (cnt == 0) {
-    mean[o] = mean[nk + o] = 0.0f;
-    stdv[o] = stdv[nk + o] = NAN;
-    stdb[o] = stdb[nk + o] = NAN;
-    cov[o] = NAN;
-    return;
-  }
-  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, sv = 0.0;
-  for (int g = 0; g < ncold; g++) {
-    const long c = (long)k * ncolc + (long)cs * ncold + g;
-    for (int e = 0; e < 5; e++) s[e] += S.asum[e * pl + c];
-    sv += S.avar[c];
-  }
-  const double dn = (double)cnt, within = sv / dn;
-  const double mc = s[0] / dn, ms = s[1] / dn;
-  const double bc = fmax(s[2] / dn - mc * mc, 0.0), bs = fmax(s[3] / dn - ms * ms, 0.0);
-  mean[o] = (float)mc;
-  mean[nk + o] = (float)ms;
-  stdv[o] = (float)sqrt(within + bc);
-  stdv[nk + o] = (float)sqrt(within + bs);
-  stdb[o] = (float)sqrt(bc);
-  stdb[nk + o] = (float)sqrt(bs);
-  cov[o] = (float)(s[4] / dn - mc * ms);
-}
-
-// a host copy of a host or device array
-template <class T>
-int mc_to_host(dazim_ctx *ctx, const T *p, size_t n, std::vector<T> &out) {
-  out.resize(n);
-  if (n == 0) return 0;
-  if (dz_is_device_ptr(p)) {
-    DZ_HIP(hipMemcpyAsync(out.data(), p, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    DZ_HIP(hipStreamSynchronize(ctx->stream));
-  } else {
-    memcpy(out.data(), p, n * sizeof(T));
-  }
-  return 0;
-}
-
-}  // namespace
-
-struct dazim_mc {
-  dazim_ctx *ctx = nullptr;
-  McDev d{};
-  int nadapt = 1;
-  int kind = 0;             // the proposal: 0 isotropic in box units, 1 shaped by the chains' covariance
-  float step0 = 0.0f;       // the initial step scale
-  float tmax = 1.0f;        // tempering: the top rung's temperature (the ladder itself is in d)
-  std::vector<double> beta{1.0};
-  int64_t nstep = 0;        // steps done; 0 = the start models are drawn, not evaluated
-  int64_t nburn_dec = 0;    // burn-in steps with a decision (the adaptation clock)
-  int64_t nrec = 0, nrec_dec = 0;
-  int n_empty = 0;
-  double *pv = nullptr;     // [kmax][ncol]: the curves dazim_mc_run computes
-  int nthin = 0;            // Gc/Gs: 0 = off, else one pass per nthin recorded steps of dazim_mc_run
-  McAniso an{};             // ... its maps and sums (sized for ntemp = 1, so that any ladder fits)
-  int64_t naniso = 0;       // ... samples taken
-  int noise = 0;            // hierarchical noise: 0 = off (d.na0, d.nb0 hold the prior while it is on)
-  std::vector<void *> blocks;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-
-namespace {
-
-template <class T>
-int mc_alloc(dazim_mc *mc, size_t n, T **out) {
-  dazim_ctx *ctx = mc->ctx;
-  void *p = nullptr;
-  DZ_HIP(dz_malloc_retry(ctx, &p, (n ? n : 1) * sizeof(T)));
-  mc->blocks.push_back(p);
-  *out = (T *)p;
-  return 0;
-}
-
-int mc_release(dazim_mc *mc) {
-  for (void *p : mc->blocks) (void)hipFree(p);
-  if (mc->e0) (void)hipEventDestroy(mc->e0);
-  if (mc->e1) (void)hipEventDestroy(mc->e1);
-  delete mc;
-  return 0;
-}
+// the step kernel of a handle: [noise][kind][tempered]
+using McStepKernel = void (*)(McDev, const double *, long long, int, int, int, int);
+constexpr McStepKernel MC_STEP[2][2][2] = {{{k_mc_step<0, 0, 0>, k_mc_step<0, 1, 0>}, {k_mc_step<1, 0, 0>, k_mc_step<1, 1, 0>}},
+                                           {{k_mc_step<0, 0, 1>, k_mc_step<0, 1, 1>}, {k_mc_step<1, 0, 1>, k_mc_step<1, 1, 1>}}};
 
 // one step on the curves pv (device) of the current proposals; enqueued on the ctx stream, no host wait
 int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
@@ -809,11 +550,7 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
     DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
     const size_t lds =
         mc->kind == 1 ? ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double) : 0;
-    auto kern = mc->kind == 1 ? (mc->d.ntemp > 1 ? k_mc_step<1, 1, 0> : k_mc_step<1, 0, 0>)
-                              : (mc->d.ntemp > 1 ? k_mc_step<0, 1, 0> : k_mc_step<0, 0, 0>);
-    if (mc->noise)
-      kern = mc->kind == 1 ? (mc->d.ntemp > 1 ? k_mc_step<1, 1, 1> : k_mc_step<1, 0, 1>)
-                           : (mc->d.ntemp > 1 ? k_mc_step<0, 1, 1> : k_mc_step<0, 0, 1>);
+    const McStepKernel kern = MC_STEP[mc->noise][mc->kind][mc->d.ntemp > 1];
     hipLaunchKernelGGL(kern, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record, (int)adapt,
                        mc->nadapt);
     DZ_HIP(hipGetLastError());
@@ -825,77 +562,6 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
     if (!first) mc->nrec_dec++;
   }
   return 0;
-}
-
-int mc_check(dazim_ctx *ctx, dazim_mc *mc, const char *what) {
-  if (!ctx || !mc) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: null context or handle", what);
-  if (mc->ctx != ctx) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: the handle belongs to another context", what);
-  return 0;
-}
-
-
-long mc_ncolc(const dazim_mc *mc) { return (long)mc->d.ncs * (mc->d.nchain / mc->d.ntemp); }
-
-// one Gc/Gs sample of the cold columns c0 .. c0 + nb - 1 from lsen [nlay][kmax][nb] (device); enqueued, no host wait
-int mc_launch_aniso(dazim_ctx *ctx, dazim_mc *mc, const float *lsen, long c0, long nb) {
-  const McDev &M = mc->d;
-  if (nb <= 0) return 0;
-  const size_t lds = ((size_t)M.nlay * M.nlay + (size_t)M.kmax * M.nlay + 3 * (size_t)M.kmax + 2 * (size_t)M.nlay) * sizeof(double);
-  hipLaunchKernelGGL(k_mc_aniso, dim3((unsigned)nb), dim3(MC_WAVE), lds, ctx->stream, M, mc->an, lsen, c0, nb);
-  DZ_HIP(hipGetLastError());
-  return 0;
-}
-
-// the bytes dazim_ti_kernels keeps per column in its two large scratch arrays (ti.up, ti.prt of ti.hip)
-size_t mc_ti_bytes_per_column(const dazim_mc *mc, const float *depz, float sublayers) {
-  return dz_refine_layers(depz, mc->d.nz, sublayers).size() * 10 * sizeof(double) * (size_t)mc->d.kmax;
-}
-
-// one pass of dazim_mc_run: the rung-0 states -> their curves -> their Lsen_Gsc -> one sample, in blocks of whole cells
-int mc_aniso_pass(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods) {
-  const McDev &M = mc->d;
-  const int ncold = M.nchain / M.ntemp;
-  // cells per block: option mc.aniso_block_cells, else what keeps the TI scratch below 2 GiB
-  long bc = dz_opt(ctx, "mc.aniso_block_cells", 0);
-  if (bc <= 0) bc = (long)(((size_t)2 << 30) / (mc_ti_bytes_per_column(mc, depz, sublayers) * (size_t)ncold));
-  bc = std::min(std::max(bc, 1L), (long)M.ncs);
-  const size_t nbmax = (size_t)bc * ncold;
-  float *cold, *lsen;
-  double *pvc;
-  int rc;
-  if ((rc = dz_scratch(ctx, "mc.aniso.cold", (size_t)M.nz * nbmax, &cold)) ||
-      (rc = dz_scratch(ctx, "mc.aniso.pv", (size_t)M.kmax * nbmax, &pvc)) ||
-      (rc = dz_scratch(ctx, "mc.aniso.lsen", (size_t)M.nlay * M.kmax * nbmax, &lsen)))
-    return rc;
-  for (long cs0 = 0; cs0 < M.ncs; cs0 += bc) {
-    const long nb = std::min(bc, (long)M.ncs - cs0) * ncold, c0 = cs0 * ncold;
-    const long ng = (long)M.nz * nb;
-    hipLaunchKernelGGL(k_mc_gather, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, ctx->stream, M, c0, nb, cold);
-    DZ_HIP(hipGetLastError());
-    int nf = 0;
-    if ((rc = dazim_dispersion_kernels(ctx, (int)nb, 1, M.nz, cold, depz, sublayers, M.kmax, periods, pvc, nullptr, nullptr, nullptr,
-                                       &nf)) ||
-        (rc = dazim_ti_kernels(ctx, (int)nb, 1, M.nz, cold, depz, sublayers, M.kmax, periods, pvc, lsen)) ||
-        (rc = mc_launch_aniso(ctx, mc, lsen, c0, nb)))
-      return rc;
-    DZ_HIP(hipStreamSynchronize(ctx->stream));   // the next block overwrites the scratch tables
-  }
-  mc->naniso++;
-  return 0;
-}
-
-int64_t mc_aniso_skipped(dazim_ctx *ctx, dazim_mc *mc, int *rc) {
-  std::vector<long long> sk((size_t)mc_ncolc(mc));
-  *rc = 0;
-  if (sk.empty()) return 0;
-  const hipError_t e = hipMemcpy(sk.data(), mc->an.askip, sk.size() * sizeof(long long), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    *rc = dz_fail(ctx, -(int)e - 1000, "dazim_mc aniso: %s", hipGetErrorString(e));
-    return 0;
-  }
-  int64_t n = 0;
-  for (long long v : sk) n += v;
-  return n;
 }
 }  // namespace
 
@@ -964,7 +630,7 @@ int dazim_mc_create(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, int nchain
   M.nswap = 1;
   int *ci, *co;
   float *v0, *lo, *hi, *co_, *wd;
-  auto fail = [&](int r) { mc_release(mc); return r; };
+  const auto fail = [&](int r) { mc_release(mc); return r; };
   if ((rc = mc_alloc(mc, cell_of.size(), &ci)) || (rc = mc_alloc(mc, (size_t)ncell, &co)) || (rc = mc_alloc(mc, vel0.size(), &v0)) ||
       (rc = mc_alloc(mc, vmin.size(), &lo)) || (rc = mc_alloc(mc, vmax.size(), &hi)) || (rc = mc_alloc(mc, cobs.size(), &co_)) ||
       (rc = mc_alloc(mc, wdat.size(), &wd)) || (rc = mc_alloc(mc, (size_t)nz * M.ncol, &M.cur)) ||
@@ -985,28 +651,24 @@ int dazim_mc_create(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, int nchain
   auto up = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
   };
-  hipError_t e = hipSuccess;
-  if ((e = up(ci, cell_of.data(), cell_of.size() * 4)) != hipSuccess || (e = up(co, cs_of.data(), cs_of.size() * 4)) != hipSuccess ||
-      (e = up(v0, vel0.data(), vel0.size() * 4)) != hipSuccess || (e = up(lo, vmin.data(), vmin.size() * 4)) != hipSuccess ||
-      (e = up(hi, vmax.data(), vmax.size() * 4)) != hipSuccess || (e = up(co_, cobs.data(), cobs.size() * 4)) != hipSuccess ||
-      (e = up(wd, wdat.data(), wdat.size() * 4)) != hipSuccess ||
-      (e = hipMemsetAsync(M.hist, 0, (size_t)M.ncs * nlay * nbin * sizeof(unsigned), ctx->stream)) != hipSuccess ||
-      (e = hipMemsetAsync(M.counters, 0, 16, ctx->stream)) != hipSuccess || (e = hipEventCreate(&mc->e0)) != hipSuccess ||
-      (e = hipEventCreate(&mc->e1)) != hipSuccess) {
-    mc_release(mc);
-    return dz_fail(ctx, -(int)e - 1000, "dazim_mc_create: %s", hipGetErrorString(e));
-  }
-  if (M.ncs > 0) {
-    hipLaunchKernelGGL(k_mc_init, dim3((unsigned)M.ncs), dim3(MC_WAVE), 0, ctx->stream, M, step);
-    if ((e = hipGetLastError()) != hipSuccess) {
-      mc_release(mc);
-      return dz_fail(ctx, -(int)e - 1000, "dazim_mc_create: %s", hipGetErrorString(e));
+  const auto start = [&]() -> hipError_t {   // the tables, the events, the start models
+    hipError_t e;
+    if ((e = up(ci, cell_of.data(), cell_of.size() * 4)) != hipSuccess || (e = up(co, cs_of.data(), cs_of.size() * 4)) != hipSuccess ||
+        (e = up(v0, vel0.data(), vel0.size() * 4)) != hipSuccess || (e = up(lo, vmin.data(), vmin.size() * 4)) != hipSuccess ||
+        (e = up(hi, vmax.data(), vmax.size() * 4)) != hipSuccess || (e = up(co_, cobs.data(), cobs.size() * 4)) != hipSuccess ||
+        (e = up(wd, wdat.data(), wdat.size() * 4)) != hipSuccess ||
+        (e = hipMemsetAsync(M.hist, 0, (size_t)M.ncs * nlay * nbin * sizeof(unsigned), ctx->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(M.counters, 0, 16, ctx->stream)) != hipSuccess || (e = hipEventCreate(&mc->e0)) != hipSuccess ||
+        (e = hipEventCreate(&mc->e1)) != hipSuccess)
+      return e;
+    if (M.ncs > 0) {
+      hipLaunchKernelGGL(k_mc_init, dim3((unsigned)M.ncs), dim3(MC_WAVE), 0, ctx->stream, M, step);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-  }
-  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-    mc_release(mc);
-    return dz_fail(ctx, -(int)e - 1000, "dazim_mc_create: %s", hipGetErrorString(e));
-  }
+    return hipStreamSynchronize(ctx->stream);
+  };
+  const hipError_t e = start();
+  if (e != hipSuccess) return fail(dz_fail(ctx, -(int)e - 1000, "dazim_mc_create: %s", hipGetErrorString(e)));
   *out = mc;
   if (n_empty) *n_empty = mc->n_empty;
   return 0;
@@ -1055,14 +717,11 @@ int dazim_mc_cov_state(dazim_ctx *ctx, dazim_mc *mc, int *kind, int64_t *cov_n, 
   DZ_HIP(hipSetDevice(ctx->device));
   const McDev &M = mc->d;
   const size_t n1 = (size_t)M.ncs * M.nlay, n2 = (size_t)M.ncs * (M.nlay * (M.nlay + 1) / 2);
-  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
-  };
-  DZ_HIP(get(cov_n, M.cov_n, (size_t)M.ncs * 8));
-  DZ_HIP(get(cov_s1, M.cov_s1, n1 * 8));
-  DZ_HIP(get(cov_s2, M.cov_s2, n2 * 8));
-  DZ_HIP(get(chol, M.chol, n2 * 8));
-  DZ_HIP(get(cov_set, M.cov_set, (size_t)M.ncs * 4));
+  DZ_HIP(mc_get(ctx, cov_n, M.cov_n, (size_t)M.ncs * 8));
+  DZ_HIP(mc_get(ctx, cov_s1, M.cov_s1, n1 * 8));
+  DZ_HIP(mc_get(ctx, cov_s2, M.cov_s2, n2 * 8));
+  DZ_HIP(mc_get(ctx, chol, M.chol, n2 * 8));
+  DZ_HIP(mc_get(ctx, cov_set, M.cov_set, (size_t)M.ncs * 4));
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -1119,134 +778,11 @@ int dazim_mc_temper_state(dazim_ctx *ctx, dazim_mc *mc, int *ntemp, float *tmax,
     return 0;
   }
   DZ_HIP(hipSetDevice(ctx->device));
-  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
-  };
   const size_t np = (size_t)M.ncs * (M.ntemp - 1);
-  DZ_HIP(get(beta, M.beta, (size_t)M.ntemp * 8));
-  DZ_HIP(get(scale, M.tscale, (size_t)M.ncs * M.ntemp * 4));
-  DZ_HIP(get(swap_try, M.swap_try, np * 8));
-  DZ_HIP(get(swap_acc, M.swap_acc, np * 8));
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  return 0;
-}
-
-int dazim_mc_set_aniso(dazim_ctx *ctx, dazim_mc *mc, int nthin, const float *amap_u, const float *wa_u, float smooth, float damp) {
-  int rc;
-  if ((rc = mc_check(ctx, mc, "dazim_mc_set_aniso"))) return rc;
-  if (nthin < 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: nthin %d < 0", nthin);
-  if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: the handle has done %lld steps", (long long)mc->nstep);
-  if (nthin == 0) {
-    mc->nthin = 0;
-    return 0;
-  }
-  if (!amap_u || !wa_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_set_aniso");
-  if (!(smooth >= 0.0f) || !(damp >= 0.0f)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: negative smoothing or damping");
-  if (smooth == 0.0f && damp == 0.0f) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: smoothing and damping both 0");
-  DZ_HIP(hipSetDevice(ctx->device));
-  McDev &M = mc->d;
-  const size_t nw = (size_t)M.kmax * M.ncell;
-  std::vector<float> amap, wa;
-  if ((rc = mc_to_host(ctx, amap_u, 2 * nw, amap)) || (rc = mc_to_host(ctx, wa_u, nw, wa))) return rc;
-  for (size_t e = 0; e < amap.size(); e++)
-    if (!std::isfinite(amap[e]))
-      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: a non-finite amap at period %d, cell %d", (int)(e / M.ncell % M.kmax),
-                     (int)(e % M.ncell));
-  for (size_t e = 0; e < wa.size(); e++)
-    if (!std::isfinite(wa[e]))
-      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: a non-finite wa at period %d, cell %d", (int)(e / M.ncell),
-                     (int)(e % M.ncell));
-  McAniso &S = mc->an;
-  const size_t nc = (size_t)M.ncol, nl = (size_t)M.nlay;
-  if (!S.asum) {
-    float *am, *w;
-    if ((rc = mc_alloc(mc, 2 * nw, &am)) || (rc = mc_alloc(mc, nw, &w)) || (rc = mc_alloc(mc, 5 * nl * nc, &S.asum)) ||
-        (rc = mc_alloc(mc, nl * nc, &S.avar)) || (rc = mc_alloc(mc, nc, &S.acnt)) || (rc = mc_alloc(mc, nc, &S.askip)))
-      return rc;
-    S.amap = am;
-    S.wa = w;
-  }
-  DZ_HIP(hipMemcpyAsync((void *)S.amap, amap.data(), 2 * nw * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  DZ_HIP(hipMemcpyAsync((void *)S.wa, wa.data(), nw * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  DZ_HIP(hipMemsetAsync(S.asum, 0, (5 * nl * nc ? 5 * nl * nc : 1) * sizeof(double), ctx->stream));
-  DZ_HIP(hipMemsetAsync(S.avar, 0, (nl * nc ? nl * nc : 1) * sizeof(double), ctx->stream));
-  DZ_HIP(hipMemsetAsync(S.acnt, 0, (nc ? nc : 1) * sizeof(long long), ctx->stream));
-  DZ_HIP(hipMemsetAsync(S.askip, 0, (nc ? nc : 1) * sizeof(long long), ctx->stream));
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  S.s2 = (double)smooth * (double)smooth;
-  S.d2 = (double)damp * (double)damp;
-  mc->nthin = nthin;
-  mc->naniso = 0;
-  return 0;
-}
-
-int dazim_mc_aniso_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncolc, const float *lsen_u) {
-  int rc;
-  if ((rc = mc_check(ctx, mc, "dazim_mc_aniso_step"))) return rc;
-  if (mc->nthin < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_aniso_step: dazim_mc_set_aniso has not switched Gc/Gs on");
-  if (mc->nstep < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_aniso_step: the handle has not done a step yet");
-  if (kmax != mc->d.kmax || ncolc != mc_ncolc(mc))
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_aniso_step: kernels [%d][%lld] for a handle of [%d][%ld]", kmax, (long long)ncolc,
-                   mc->d.kmax, mc_ncolc(mc));
-  if (!lsen_u && ncolc > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_aniso_step");
-  DZ_HIP(hipSetDevice(ctx->device));
-  if ((rc = dz_join_aux(ctx))) return rc;
-  DzBuf<float> lsen;
-  if ((rc = lsen.init(ctx, lsen_u, (size_t)mc->d.nlay * kmax * ncolc, true, false))) return rc;
-  {
-    DzTimer t(ctx, "mc_aniso");
-    if ((rc = mc_launch_aniso(ctx, mc, lsen.dev, 0, (long)ncolc))) return rc;
-    t.stop();
-  }
-  mc->naniso++;
-  return 0;
-}
-
-int dazim_mc_aniso_state(dazim_ctx *ctx, dazim_mc *mc, int *nthin, double *asum, double *avar, int64_t *acnt, int64_t *skipped) {
-  int rc;
-  if ((rc = mc_check(ctx, mc, "dazim_mc_aniso_state"))) return rc;
-  if (nthin) *nthin = mc->nthin;
-  if (mc->nthin < 1) {
-    if (asum || avar || acnt || skipped)
-      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_aniso_state: dazim_mc_set_aniso has not switched Gc/Gs on");
-    return 0;
-  }
-  DZ_HIP(hipSetDevice(ctx->device));
-  const McAniso &S = mc->an;
-  const size_t nc = (size_t)mc_ncolc(mc), nl = (size_t)mc->d.nlay;
-  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
-  };
-  DZ_HIP(get(asum, S.asum, 5 * nl * nc * 8));
-  DZ_HIP(get(avar, S.avar, nl * nc * 8));
-  DZ_HIP(get(acnt, S.acnt, nc * 8));
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  if (skipped) {
-    *skipped = mc_aniso_skipped(ctx, mc, &rc);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-int dazim_mc_aniso_result(dazim_ctx *ctx, dazim_mc *mc, float *mean_u, float *std_u, float *stdb_u, float *cov_u, int64_t *nsamp_u) {
-  int rc;
-  if ((rc = mc_check(ctx, mc, "dazim_mc_aniso_result"))) return rc;
-  if (!mean_u || !std_u || !stdb_u || !cov_u || !nsamp_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_aniso_result");
-  if (mc->nthin < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_aniso_result: dazim_mc_set_aniso has not switched Gc/Gs on");
-  if (mc->naniso < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_aniso_result: no Gc/Gs sample yet");
-  DZ_HIP(hipSetDevice(ctx->device));
-  const McDev &M = mc->d;
-  const size_t nk = (size_t)M.nlay * M.ncell;
-  DzBuf<float> mean, stdv, stdb, cov;
-  DzBuf<long long> ns;
-  if ((rc = mean.init(ctx, mean_u, 2 * nk, false, true)) || (rc = stdv.init(ctx, std_u, 2 * nk, false, true)) ||
-      (rc = stdb.init(ctx, stdb_u, 2 * nk, false, true)) || (rc = cov.init(ctx, cov_u, nk, false, true)) ||
-      (rc = ns.init(ctx, (const long long *)nsamp_u, (size_t)M.ncell, false, true)))
-    return rc;
-  hipLaunchKernelGGL(k_mc_aniso_final, dim3((unsigned)M.ncell), dim3(MC_WAVE), 0, ctx->stream, M, mc->an, mean.dev, stdv.dev, stdb.dev,
-                     cov.dev, ns.dev);
-  DZ_HIP(hipGetLastError());
-  if ((rc = mean.finish()) || (rc = stdv.finish()) || (rc = stdb.finish()) || (rc = cov.finish()) || (rc = ns.finish())) return rc;
+  DZ_HIP(mc_get(ctx, beta, M.beta, (size_t)M.ntemp * 8));
+  DZ_HIP(mc_get(ctx, scale, M.tscale, (size_t)M.ncs * M.ntemp * 4));
+  DZ_HIP(mc_get(ctx, swap_try, M.swap_try, np * 8));
+  DZ_HIP(mc_get(ctx, swap_acc, M.swap_acc, np * 8));
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -1299,11 +835,8 @@ int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, dou
     return 0;
   }
   DZ_HIP(hipSetDevice(ctx->device));
-  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
-  };
-  DZ_HIP(get(nsum, M.nsum, (size_t)2 * M.ncol * 8));
-  DZ_HIP(get(ncnt, M.ncnt, (size_t)M.ncol * 8));
+  DZ_HIP(mc_get(ctx, nsum, M.nsum, (size_t)2 * M.ncol * 8));
+  DZ_HIP(mc_get(ctx, ncnt, M.ncnt, (size_t)M.ncol * 8));
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -1449,17 +982,14 @@ int dazim_mc_state(dazim_ctx *ctx, dazim_mc *mc, float *cur, double *chi2, float
   if ((rc = mc_check(ctx, mc, "dazim_mc_state"))) return rc;
   DZ_HIP(hipSetDevice(ctx->device));
   const McDev &M = mc->d;
-  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream) : hipSuccess;
-  };
-  DZ_HIP(get(cur, M.cur, (size_t)M.nz * M.ncol * 4));
-  DZ_HIP(get(chi2, M.chi2, (size_t)M.ncol * 8));
-  DZ_HIP(get(scale, M.scale, (size_t)M.ncs * 4));
-  DZ_HIP(get(sums, M.sums, (size_t)2 * M.nlay * M.ncol * 8));
-  DZ_HIP(get(hist, M.hist, (size_t)M.ncs * M.nlay * M.nbin * 4));
-  DZ_HIP(get(accepted, M.accepted, (size_t)M.ncol * 8));
-  DZ_HIP(get(best, M.best, (size_t)M.nlay * M.ncs * 4));
-  DZ_HIP(get(best_chi2, M.best_chi2, (size_t)M.ncs * 8));
+  DZ_HIP(mc_get(ctx, cur, M.cur, (size_t)M.nz * M.ncol * 4));
+  DZ_HIP(mc_get(ctx, chi2, M.chi2, (size_t)M.ncol * 8));
+  DZ_HIP(mc_get(ctx, scale, M.scale, (size_t)M.ncs * 4));
+  DZ_HIP(mc_get(ctx, sums, M.sums, (size_t)2 * M.nlay * M.ncol * 8));
+  DZ_HIP(mc_get(ctx, hist, M.hist, (size_t)M.ncs * M.nlay * M.nbin * 4));
+  DZ_HIP(mc_get(ctx, accepted, M.accepted, (size_t)M.ncol * 8));
+  DZ_HIP(mc_get(ctx, best, M.best, (size_t)M.nlay * M.ncs * 4));
+  DZ_HIP(mc_get(ctx, best_chi2, M.best_chi2, (size_t)M.ncs * 8));
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   if (step) *step = mc->nstep;
   return 0;

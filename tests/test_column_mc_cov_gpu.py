@@ -1,13 +1,14 @@
 """-m gpu: the covariance-adapted proposal of the Monte-Carlo sampler (dazim_mc_set_proposal kind 1).
 
-The step against its NumPy restatement (tests/mc_cov_ref.py) at three shapes, the sampler on a strongly correlated linear-Gaussian
-posterior against the isotropic proposal, the dispersion forward model in both kinds, reproducibility, the unchanged default and the
-refused calls."""
+The step against its NumPy restatement (tests/mc_ref.py, driven by tests/mc_step_check.py) at three shapes, the sampler on a
+strongly correlated linear-Gaussian posterior against the isotropic proposal, the dispersion forward model in both kinds,
+reproducibility, the unchanged default and the refused calls."""
 import numpy as np
 import pytest
 
 import dazimsurftomo_amd as dz
-from tests import mc_cov_ref, mc_ref
+from tests import mc_ref
+from tests.mc_step_check import drive
 from tests.test_column_mc_gpu import create, disp_setup, per_column
 
 pytestmark = pytest.mark.gpu
@@ -46,55 +47,21 @@ def test_one_step_against_numpy(ctx, nz, nchain, nadapt, nburn, nrec):
     lo, hi = per_column(vmin.astype(np.float64), mc), per_column(vmax.astype(np.float64), mc)
     cb, wd = per_column(cobs, mc), per_column(wdat, mc)
     cov0 = mc.cov_state()
-    ref0 = mc_cov_ref.empty_cov(ncell, nlay)
+    ref0 = mc_ref.empty_cov(ncell, nlay)
     for k in ref0:
         assert np.array_equal(cov0[k], ref0[k]), k
     root = np.sqrt(np.float32(nlay))
-    acc_win = np.zeros(ncell, np.int64)
-    nbd = 0
-    before = after = nfact = 0
-    first_factor_at = None
-    conds = []
-    for t in range(1, nburn + nrec + 1):
-        st, cov = mc.state(), mc.cov_state()
-        prop = mc.proposals().cpu().numpy()
-        record = t > nburn
-        adapt = False
-        if not record and t > 1:
-            nbd += 1
-            adapt = nbd % nadapt == 0
+
+    def forward(t):
         pv = (cb.astype(np.float64) + rng.normal(0, 0.012, cb.shape)).astype(np.float32).astype(np.float64)
         pv[rng.random(pv.shape) < (0.02 if t == 1 else 0.01)] = 0.0
-        exp, ecov, acc, acc_win, factored = mc_cov_ref.step(st, cov, prop, pv, t, record, adapt, nadapt, acc_win, mc._cells, nchain,
-                                                            lo, hi, cb, wd, nbin, seed)
-        if t > 1:
-            before += int((cov["cov_set"] == 0).sum())
-            after += int((cov["cov_set"] == 1).sum())
-        mc.step(pv, int(record))
-        got, gcov = mc.state(), mc.cov_state()
-        gprop = mc.proposals().cpu().numpy()
-        for k in ("cur", "chi2", "scale", "sums", "hist", "accepted", "best", "best_chi2"):
-            assert np.array_equal(got[k], exp[k]), (t, k)
-        for k in ("cov_n", "cov_s1", "cov_s2", "cov_set"):
-            assert np.array_equal(gcov[k], ecov[k]), (t, k)
-        for cs, Cm in factored.items():
-            conds.append(np.linalg.cond(Cm))
-            assert conds[-1] <= 1e6, (t, cs, conds[-1])      # from the restatement alone: the bound below rests on it
-            nfact += 1
-            if first_factor_at is None:
-                first_factor_at = nbd
-            if cov["cov_set"][cs] == 0:                      # the switch: the scale restarts, whatever the rule made of it
-                assert gcov["cov_set"][cs] == 1 and got["scale"][cs] == np.float32(1.0) / root
-        # the factor: fp64 epsilon times the condition number (<= 1e6), with a margin of ten
-        Lref = ecov["chol"]
-        assert np.abs(gcov["chol"] - Lref).max() <= 1e-9 * np.abs(Lref).max(), t
-        nxt = mc_cov_ref.proposals(got["cur"], got["scale"], gcov["chol"], gcov["cov_set"], prop, t, mc._cells, nchain, lo, hi, seed)
-        ulp = np.abs(gprop.view(np.int32).astype(np.int64) - nxt.view(np.int32).astype(np.int64))
-        assert ulp.max() <= 1, (t, ulp.max())
-        assert (gprop[:nlay] >= lo).all() and (gprop[:nlay] <= hi).all()
-    print(f"\n[measured] nlay {nlay}, {nchain} chains: {nfact} factors, cond(C) max {max(conds):.3g}; first factor after "
+        return pv
+
+    run = drive(mc, forward, nburn, nrec, nadapt, lo, hi, cb, wd, nbin, seed)
+    got, gcov, nfact, first_factor_at = run["got"], run["gcov"], run["nfact"], run["first_factor_at"]
+    print(f"\n[measured] nlay {nlay}, {nchain} chains: {nfact} factors, cond(C) max {max(run['conds']):.3g}; first factor after "
           f"{first_factor_at} burn-in decisions; scale {got['scale'].min():.4f}..{got['scale'].max():.4f}")
-    assert before > 0 and after > 0                          # decisions from isotropic and from covariance proposals
+    assert run["before"] > 0 and run["after"] > 0            # decisions from isotropic and from covariance proposals
     assert (gcov["cov_set"] == 1).all() and nfact >= ncell
     assert first_factor_at == (nadapt if nchain * nadapt >= 8 * nlay else nadapt * -(-8 * nlay // (nchain * nadapt)))
     assert (got["scale"] <= np.float32(2.0) / root).all()

@@ -1,12 +1,14 @@
 """-m gpu: Monte-Carlo Vs per map cell (dazim_mc_*).
 
-The step against its NumPy restatement (tests/mc_ref.py) bit for bit, the sampler on a linear-Gaussian problem with a known posterior
-and on the prior alone, reproducibility, recovery with the dispersion forward model, cells without data and the refused arguments."""
+The step against its NumPy restatement (tests/mc_ref.py, driven by tests/mc_step_check.py) bit for bit, the sampler on a
+linear-Gaussian problem with a known posterior and on the prior alone, reproducibility, recovery with the dispersion forward model,
+cells without data and the refused arguments."""
 import numpy as np
 import pytest
 
 import dazimsurftomo_amd as dz
 from tests import mc_ref
+from tests.mc_step_check import check_final, drive
 
 pytestmark = pytest.mark.gpu
 
@@ -58,50 +60,20 @@ def test_one_step_against_numpy(ctx):
     prop = mc.proposals().cpu().numpy()
     assert np.array_equal(prop[:nlay], mc_ref.start_models(gid.astype(np.uint32), lo, hi, seed))
     assert np.array_equal(prop[nlay], per_column(vel0[nlay:, 1:-1, 1:-1], mc)[0])
-    acc_win = np.zeros(ncell, np.int64)
-    nbd = 0
-    ninf0 = ndec = 0
-    for t in range(1, 21):
-        st = mc.state()
-        assert st["step"] == t - 1
-        prop = mc.proposals().cpu().numpy()
-        record = t > 10
-        adapt = False
-        if not record and t > 1:
-            nbd += 1
-            adapt = nbd % nadapt == 0
+
+    def forward(t):
         pv = (cb.astype(np.float64) + rng.normal(0, 0.012, cb.shape)).astype(np.float32).astype(np.float64)
         pv[rng.random(pv.shape) < (0.02 if t == 1 else 0.01)] = 0.0
-        exp, acc, nxt, acc_win = mc_ref.step(st, prop, pv, t, record, adapt, nadapt, acc_win, mc._cells, nchain, lo, hi, cb, wd, nbin,
-                                             seed)
-        mc.step(pv, int(record))
-        got = mc.state()
-        gprop = mc.proposals().cpu().numpy()
-        moved = (got["cur"][:nlay] == prop[:nlay]).all(axis=0) & ((got["cur"][:nlay] != st["cur"][:nlay]).any(axis=0) | (t == 1))
-        assert np.array_equal(moved, acc), t
-        for k in ("cur", "chi2", "scale", "sums", "hist", "accepted", "best", "best_chi2"):
-            assert np.array_equal(got[k], exp[k]), (t, k)
-        ulp = np.abs(gprop.view(np.int32).astype(np.int64) - nxt.view(np.int32).astype(np.int64))
-        assert ulp.max() <= 1, (t, ulp.max())
-        assert (gprop[:nlay] >= lo).all() and (gprop[:nlay] <= hi).all()
-        if t == 1:
-            ninf0 = int(np.isinf(got["chi2"]).sum())
-        else:
-            ndec += int(acc.sum())
-    assert ninf0 > 0 and ndec > 0                # both no-root rules and real decisions were exercised
+        return pv
+
+    run = drive(mc, forward, 10, 10, nadapt, lo, hi, cb, wd, nbin, seed, moved=True)
+    got = run["got"]
+    assert run["ninf0"] > 0 and run["ndec"] > 0  # both no-root rules and real decisions were exercised
     assert (got["scale"] != np.float32(0.05)).any()
     assert np.isfinite(got["best_chi2"]).all()
     # the posterior statistics of the 10 recorded steps against k_mc_final restated from the final state
-    r = mc.result()
-    e = mc_ref.final(got, vmin.reshape(nlay, ncell), vmax.reshape(nlay, ncell), vel0[:nlay, 1:-1, 1:-1].reshape(nlay, ncell),
-                     mc._cells, ncell, nchain, 10, 10, nbin)
-    for k in ("mean", "q", "best", "accept", "chi2_best"):
-        assert np.array_equal(r[k].reshape(e[k].shape), e[k]), k
-    for k in ("std", "rhat"):   # (sqrt in fp64, then fp32: equal, or one fp32 ulp apart)
-        a, b = r[k].reshape(e[k].shape), e[k]
-        fin = np.isfinite(b)
-        assert np.array_equal(np.isfinite(a), fin) and fin.mean() > 0.9, k
-        assert np.abs(a[fin].view(np.int32).astype(np.int64) - b[fin].view(np.int32).astype(np.int64)).max() <= 1, k
+    _, finite = check_final(mc, got, vmin, vmax, vel0, 1, 10, nbin)
+    assert finite > 0.9
     mc.free()
 
 

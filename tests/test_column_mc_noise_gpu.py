@@ -1,13 +1,15 @@
 """-m gpu: the hierarchical data-noise scale of the Monte-Carlo sampler (dazim_mc_set_noise).
 
-The step with the energy X = 2 a log(b0 + chi2 / 2) against its NumPy restatement (tests/mc_noise_ref.py) in both proposal kinds,
-tempered and not, with the noise record and the result; the unchanged default and reproducibility; a linear problem whose posterior
-is a multivariate t; the dispersion forward model with data noisier than assumed; and the refused calls."""
+The step with the energy X = 2 a log(b0 + chi2 / 2) against its NumPy restatement (tests/mc_ref.py, driven by
+tests/mc_step_check.py) in both proposal kinds, tempered and not, with the noise record and the result; the unchanged default and
+reproducibility; a linear problem whose posterior is a multivariate t; the dispersion forward model with data noisier than assumed;
+and the refused calls."""
 import numpy as np
 import pytest
 
 import dazimsurftomo_amd as dz
-from tests import mc_noise_ref, mc_pt_ref
+from tests import mc_ref
+from tests.mc_step_check import check_final, drive, ulps
 from tests.test_column_mc_gpu import create, disp_setup, per_column
 from tests.test_column_mc_temper_gpu import host_forward, step_problem
 from tests.test_mc_noise_ref_cpu import NBIN, NBURN, NCHAIN, NSAMPLE, SEED, check_linear
@@ -36,10 +38,6 @@ SHAPES = {
 }
 
 
-def ulps(a, b):
-    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
-
-
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_noise_step_against_numpy(ctx, shape):
     """every step restated from the library's own state, ladder, proposals, cov_state and noise_state: decisions, cur, chi2, sums,
@@ -48,7 +46,7 @@ def test_noise_step_against_numpy(ctx, shape):
     (nz, nchain, ntemp, nswap, kind), nburn = SHAPES[shape]
     rng, nx, ny, kmax, vel0, vmin, vmax, cobs, wdat = step_problem(nz)
     nbin, seed, tmax = 20, 0x1234_5678_9ABC, 16.0
-    nlay, ncell, ncs = nz - 1, 16, 15
+    ncell, ncs = 16, 15
     mc = create(ctx, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, 0.05, NADAPT)
     if shape == "odd1":                         # the setters in either order
         mc.set_noise(A0, B0)
@@ -64,50 +62,9 @@ def test_noise_step_against_numpy(ctx, shape):
     assert ns["nsum"].shape == (2, mc.ncol) and ns["ncnt"].shape == (mc.ncol,)
     lo, hi = per_column(vmin.astype(np.float64), mc), per_column(vmax.astype(np.float64), mc)
     cb, wd = per_column(cobs, mc), per_column(wdat, mc)
-    acc_win = np.zeros((ncs, ntemp), np.int64)
-    seen = dict.fromkeys(mc_noise_ref.BRANCHES, 0)
-    nbd = ndec = 0
-    for t in range(1, nburn + NREC + 1):
-        st, ns = mc.state(), mc.noise_state()
-        tp = mc_noise_ref.ladder_state(st, mc.temper_state())
-        cov = mc.cov_state() if kind == 1 else None
-        prop = mc.proposals().cpu().numpy()
-        record = t > nburn
-        adapt = False
-        if not record and t > 1:
-            nbd += 1
-            adapt = nbd % NADAPT == 0
-        pv = host_forward(rng, cb, t, nswap)
-        exp, etp, ecov, ens, acc, acc_win, factored, br = mc_noise_ref.step(st, tp, cov, ns, prop, pv, t, record, adapt, NADAPT, acc_win,
-                                                                           mc._cells, nchain, lo, hi, cb, wd, nbin, seed)
-        for k in br:
-            seen[k] += br[k]
-        mc.step(pv, int(record))
-        got, gns = mc.state(), mc.noise_state()
-        gtp = mc_noise_ref.ladder_state(got, mc.temper_state())
-        gprop = mc.proposals().cpu().numpy()
-        if ntemp == 1:                          # without swaps a moved state is an accepted proposal: the decisions themselves
-            moved = (got["cur"][:nlay] == prop[:nlay]).all(axis=0) & ((got["cur"][:nlay] != st["cur"][:nlay]).any(axis=0) | (t == 1))
-            assert np.array_equal(moved, acc), t
-        for k in ("cur", "chi2", "scale", "sums", "hist", "accepted", "best", "best_chi2"):
-            assert np.array_equal(got[k], exp[k]), (t, k)
-        for k in ("scale", "swap_try", "swap_acc"):
-            assert np.array_equal(gtp[k], etp[k]), (t, k)
-        for k in ("nsum", "ncnt"):
-            assert np.array_equal(gns[k], ens[k]), (t, k)
-        gcov = None
-        if kind == 1:
-            gcov = mc.cov_state()
-            for k in ("cov_n", "cov_s1", "cov_s2", "cov_set"):
-                assert np.array_equal(gcov[k], ecov[k]), (t, k)
-            for cs, Cm in factored.items():
-                assert np.linalg.cond(Cm) <= 1e6, (t, cs)
-            assert np.abs(gcov["chol"] - ecov["chol"]).max() <= 1e-9 * max(np.abs(ecov["chol"]).max(), 1e-300), t
-        nxt = mc_pt_ref.proposals(got["cur"], gtp["scale"], gcov, prop, t, mc._cells, nchain, lo, hi, seed)
-        assert ulps(gprop, nxt).max() <= 1, t
-        assert (gprop[:nlay] >= lo).all() and (gprop[:nlay] <= hi).all()
-        if t > 1:
-            ndec += int(acc.sum())
+    # (without swaps a moved state is an accepted proposal: the decisions themselves)
+    run = drive(mc, lambda t: host_forward(rng, cb, t, nswap), nburn, NREC, NADAPT, lo, hi, cb, wd, nbin, seed, moved=ntemp == 1)
+    got, gtp, gcov, gns, seen, ndec = run["got"], run["gtp"], run["gcov"], run["gns"], run["seen"], run["ndec"]
     hot = (np.arange(mc.ncol) % nchain) % ntemp != 0
     assert not gns["nsum"][:, hot].any() and not gns["ncnt"][hot].any()              # the columns of the hot chains stay 0
     assert 0 < gns["ncnt"].sum() <= NREC * ncs * (nchain // ntemp) and gns["ncnt"].max() == NREC
@@ -119,7 +76,7 @@ def test_noise_step_against_numpy(ctx, shape):
         assert (gcov["cov_set"] == 1).all()
     # the result against its restatement
     r = mc.noise_result()
-    e = mc_noise_ref.result(gns, wdat.reshape(kmax, ncell), mc._cells, ncell, nchain, ntemp)
+    e = mc_ref.result(gns, wdat.reshape(kmax, ncell), mc._cells, ncell, nchain, ntemp)
     assert np.array_equal(r["ndata"].ravel(), e["ndata"])
     one, none = 0, 6                            # step_problem's cell with one weighted period, and its cell without data
     assert e["ndata"][one] == 1 and e["ndata"][none] == 0
@@ -131,11 +88,7 @@ def test_noise_step_against_numpy(ctx, shape):
         assert np.array_equal(np.isfinite(a), fin) and fin.sum() >= 14, k
         assert ulps(a[fin], b[fin]).max() <= 1, k
     # the Vs statistics are those of the recorded states, as without the mode
-    rv = mc.result()
-    ev = mc_pt_ref.final(got, vmin.reshape(nlay, ncell), vmax.reshape(nlay, ncell), vel0[:nlay, 1:-1, 1:-1].reshape(nlay, ncell),
-                         mc._cells, ncell, nchain, ntemp, NREC, NREC, nbin)
-    for k in ("mean", "q", "best", "accept", "chi2_best"):
-        assert np.array_equal(rv[k].reshape(ev[k].shape), ev[k]), k
+    check_final(mc, got, vmin, vmax, vel0, ntemp, NREC, nbin, roots=False)
     print(f"\n[measured] {shape}: swap cases {seen}; recorded noise states {gns['ncnt'].sum()}; lam_mean "
           f"{np.nanmin(r['lam_mean'][r['ndata'] > 0]):.3f}..{np.nanmax(r['lam_mean']):.3f}")
     mc.free()
@@ -183,10 +136,10 @@ def test_default_unchanged_and_reproducible(ctx):
 
 def test_linear_student_t_posterior(ctx):
     """c = K v (fp64, host): 16 cells, 12 periods, 4 knots, 32 chains, w = 1 / 0.02 against data noise 0.06, a0 = 2, b0 = 1, 2000
-    burn-in and 8000 recorded steps against the multivariate t (tests/mc_noise_ref.linear_problem) under the bars of
+    burn-in and 8000 recorded steps against the multivariate t (tests/mc_ref.linear_problem) under the bars of
     test_linear_gaussian_posterior; lam_mean and lam_std, second-moment estimates from the same states, within 10 % too.  The same
     run with the mode off is printed beside it: its std is the too-small fixed-sigma one."""
-    pb = mc_noise_ref.linear_problem()
+    pb = mc_ref.linear_problem()
     ncell, kmax, nlay, K = pb["ncell"], pb["kmax"], pb["nlay"], pb["K"]
     nx = ny = 6
     nz = nlay + 1

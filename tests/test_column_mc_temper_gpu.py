@@ -1,12 +1,14 @@
 """-m gpu: parallel tempering of the Monte-Carlo sampler (dazim_mc_set_tempering).
 
-The tempered step against its NumPy restatement (tests/mc_pt_ref.py) in both proposal kinds at five shapes, a bimodal posterior that
-the untempered chains cannot cross, the unchanged default and reproducibility, the dispersion forward model, and the refused calls."""
+The tempered step against its NumPy restatement (tests/mc_ref.py, driven by tests/mc_step_check.py) in both proposal kinds at five
+shapes, a bimodal posterior that the untempered chains cannot cross, the unchanged default and reproducibility, the dispersion
+forward model, and the refused calls."""
 import numpy as np
 import pytest
 
 import dazimsurftomo_amd as dz
-from tests import mc_pt_ref, mc_ref
+from tests import mc_ref
+from tests.mc_step_check import check_final, drive
 from tests.test_column_mc_gpu import create, disp_setup, per_column
 
 pytestmark = pytest.mark.gpu
@@ -67,7 +69,7 @@ def test_tempered_step_against_numpy(ctx, shape, kind):
     nburn = nburns[kind]
     rng, nx, ny, kmax, vel0, vmin, vmax, cobs, wdat = step_problem(nz)
     nbin, seed, tmax = 20, 0x1234_5678_9ABC, 16.0
-    nlay, ncell, ncs, ncold = nz - 1, 16, 15, nchain // ntemp
+    nlay, ncs, ncold = nz - 1, 15, nchain // ntemp
     mc = create(ctx, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, 0.05, NADAPT)
     if kind == 1:                               # the two setters in either order
         mc.set_proposal(1)
@@ -78,55 +80,13 @@ def test_tempered_step_against_numpy(ctx, shape, kind):
     assert mc.n_empty == 1 and mc.ncs == ncs and mc.ncol == ncs * nchain
     tp = mc.temper_state()
     assert (tp["ntemp"], tp["tmax"], tp["nswap"]) == (ntemp, tmax, nswap)
-    assert np.abs(tp["beta"] / mc_pt_ref.ladder(ntemp, tmax) - 1).max() <= 1e-14 and tp["beta"][0] == 1.0
+    assert np.abs(tp["beta"] / mc_ref.ladder(ntemp, tmax) - 1).max() <= 1e-14 and tp["beta"][0] == 1.0
     assert (tp["scale"] == np.float32(0.05)).all() and not tp["swap_try"].any() and not tp["swap_acc"].any()
     lo, hi = per_column(vmin.astype(np.float64), mc), per_column(vmax.astype(np.float64), mc)
     cb, wd = per_column(cobs, mc), per_column(wdat, mc)
-    root = np.sqrt(np.float32(nlay))
-    acc_win = np.zeros((ncs, ntemp), np.int64)
-    seen = dict.fromkeys(mc_pt_ref.BRANCHES, 0)
-    nbd = nfact = nswapped = 0
-    conds = [1.0]
-    for t in range(1, nburn + NREC + 1):
-        st, tp = mc.state(), mc.temper_state()
-        cov = mc.cov_state() if kind == 1 else None
-        prop = mc.proposals().cpu().numpy()
-        record = t > nburn
-        adapt = False
-        if not record and t > 1:
-            nbd += 1
-            adapt = nbd % NADAPT == 0
-        pv = host_forward(rng, cb, t, nswap)
-        exp, etp, ecov, acc, acc_win, factored, br = mc_pt_ref.step(st, tp, cov, prop, pv, t, record, adapt, NADAPT, acc_win, mc._cells,
-                                                                    nchain, lo, hi, cb, wd, nbin, seed)
-        for k in br:
-            seen[k] += br[k]
-        mc.step(pv, int(record))
-        got, gtp = mc.state(), mc.temper_state()
-        gprop = mc.proposals().cpu().numpy()
-        for k in ("cur", "chi2", "scale", "sums", "hist", "accepted", "best", "best_chi2"):
-            assert np.array_equal(got[k], exp[k]), (t, k)
-        for k in ("scale", "swap_try", "swap_acc"):
-            assert np.array_equal(gtp[k], etp[k]), (t, k)
-        assert np.array_equal(got["scale"], gtp["scale"][:, 0]), t
-        gcov = None
-        if kind == 1:
-            gcov = mc.cov_state()
-            for k in ("cov_n", "cov_s1", "cov_s2", "cov_set"):
-                assert np.array_equal(gcov[k], ecov[k]), (t, k)
-            for cs, Cm in factored.items():
-                conds.append(np.linalg.cond(Cm))
-                assert conds[-1] <= 1e6, (t, cs, conds[-1])      # from the restatement alone: the bound below rests on it
-                nfact += 1
-                if cov["cov_set"][cs] == 0:                      # the first factor: every rung's scale restarts
-                    assert gcov["cov_set"][cs] == 1 and (gtp["scale"][cs] == np.float32(1.0) / root).all()
-            # the factor: fp64 epsilon times the condition number (<= 1e6), with a margin of ten
-            assert np.abs(gcov["chol"] - ecov["chol"]).max() <= 1e-9 * max(np.abs(ecov["chol"]).max(), 1e-300), t
-        nxt = mc_pt_ref.proposals(got["cur"], gtp["scale"], gcov, prop, t, mc._cells, nchain, lo, hi, seed)
-        ulp = np.abs(gprop.view(np.int32).astype(np.int64) - nxt.view(np.int32).astype(np.int64))
-        assert ulp.max() <= 1, (t, ulp.max())
-        assert (gprop[:nlay] >= lo).all() and (gprop[:nlay] <= hi).all()
-        nswapped = int(gtp["swap_acc"].sum())
+    run = drive(mc, lambda t: host_forward(rng, cb, t, nswap), nburn, NREC, NADAPT, lo, hi, cb, wd, nbin, seed)
+    got, gtp, gcov, seen, nfact = run["got"], run["gtp"], run["gcov"], run["seen"], run["nfact"]
+    nswapped = int(gtp["swap_acc"].sum())
     hot = (np.arange(mc.ncol) % nchain) % ntemp != 0
     assert not got["sums"][:, :, hot].any() and not got["accepted"][hot].any()       # the columns of the hot chains stay 0
     assert got["hist"].sum() == NREC * nlay * ncs * ncold
@@ -138,19 +98,9 @@ def test_tempered_step_against_numpy(ctx, shape, kind):
     if kind == 1:
         assert (gcov["cov_set"] == 1).all() and nfact >= ncs
     print(f"\n[measured] {shape}, kind {kind}: swap cases {seen}; swaps {nswapped} of {gtp['swap_try'].sum()}; scale "
-          f"{gtp['scale'].min():.4f}..{gtp['scale'].max():.4f}; {nfact} factors, cond(C) max {max(conds):.3g}")
+          f"{gtp['scale'].min():.4f}..{gtp['scale'].max():.4f}; {nfact} factors, cond(C) max {max(run['conds'] + [1.0]):.3g}")
     # the posterior statistics of the recorded steps against k_mc_final restated over the rung-0 chains
-    r = mc.result()
-    e = mc_pt_ref.final(got, vmin.reshape(nlay, ncell), vmax.reshape(nlay, ncell), vel0[:nlay, 1:-1, 1:-1].reshape(nlay, ncell),
-                        mc._cells, ncell, nchain, ntemp, NREC, NREC, nbin)
-    for k in ("mean", "q", "best", "accept", "chi2_best"):
-        assert np.array_equal(r[k].reshape(e[k].shape), e[k]), k
-    for k in ("std", "rhat"):   # (sqrt in fp64, then fp32: equal, or one fp32 ulp apart)
-        a, b = r[k].reshape(e[k].shape), e[k]
-        fin = np.isfinite(b)
-        assert np.array_equal(np.isfinite(a), fin), k
-        if fin.any():
-            assert np.abs(a[fin].view(np.int32).astype(np.int64) - b[fin].view(np.int32).astype(np.int64)).max() <= 1, k
+    r, _ = check_final(mc, got, vmin, vmax, vel0, ntemp, NREC, nbin)
     if ncold == 1:
         assert np.isnan(r["rhat"]).all()
     mc.free()

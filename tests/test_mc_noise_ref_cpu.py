@@ -1,9 +1,9 @@
-"""CPU: the restatement of the hierarchical-noise sampler (tests/mc_noise_ref.py) alone on the linear problem whose posterior is a
+"""CPU: the restatement of the hierarchical-noise sampler (tests/mc_ref.py) alone on the linear problem whose posterior is a
 multivariate t, against that posterior under the bars of tests/test_column_mc_noise_gpu.py's linear test: the bars are reachable by
 the arithmetic before the device is involved."""
 import numpy as np
 
-from tests import mc_noise_ref, mc_pt_ref
+from tests import mc_ref
 
 NBURN, NSAMPLE, NCHAIN, NBIN, SEED = 2000, 8000, 32, 64, 77
 
@@ -27,15 +27,15 @@ def check_linear(pb, mean, std, rhat, lam_mean, lam_std, tag):
 
 
 def test_linear_student_t_posterior_restated():
-    pb = mc_noise_ref.linear_problem()
+    pb = mc_ref.linear_problem()
     ncell, kmax, nlay, K = pb["ncell"], pb["kmax"], pb["nlay"], pb["K"]
     assert (pb["sd"] / pb["sd_fixed"]).min() > 1.0           # the fixed-sigma std is too small in every cell of this problem
     cells = np.arange(ncell)
     wdat = np.full((kmax, ncell), pb["w"], np.float32)
-    st, tp, ns = mc_noise_ref.sample(lambda prop: K @ prop[:nlay].astype(np.float64), NBURN, NSAMPLE, 50, cells, NCHAIN, pb["vmin"].T,
+    st, tp, ns = mc_ref.sample(lambda prop: K @ prop[:nlay].astype(np.float64), NBURN, NSAMPLE, 50, cells, NCHAIN, pb["vmin"].T,
                                      pb["vmax"].T, np.full(ncell, 3.5, np.float32), pb["cobs"].T, wdat, NBIN, SEED, pb["a0"], pb["b0"])
-    r = mc_pt_ref.final(st, pb["vmin"].T.copy(), pb["vmax"].T.copy(), np.full((nlay, ncell), 3.5, np.float32), cells, ncell, NCHAIN, 1,
+    r = mc_ref.final(st, pb["vmin"].T.copy(), pb["vmax"].T.copy(), np.full((nlay, ncell), 3.5, np.float32), cells, ncell, NCHAIN, 1,
                         NSAMPLE, NSAMPLE, NBIN)
-    nr = mc_noise_ref.result(ns, wdat, cells, ncell, NCHAIN, 1)
+    nr = mc_ref.result(ns, wdat, cells, ncell, NCHAIN, 1)
     assert (nr["ndata"] == kmax).all() and (ns["ncnt"] == NSAMPLE).all()
     check_linear(pb, r["mean"].T, r["std"].T, r["rhat"], nr["lam_mean"], nr["lam_std"], "restatement, mode on")
