@@ -430,13 +430,14 @@ class Context:
         return out
 
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
-                  ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None):
+                  ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None, prior=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
         cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
         data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal).  ntemp > 1: parallel
         tempering with ntemp rungs up to temperature tmax and a swap round every nswap steps (MonteCarlo.set_tempering).  aniso: a
         dict of MonteCarlo.set_aniso's arguments (nthin, amap, wa, smooth, damp) switches the Gc/Gs posteriors on.  noise: (a0, b0)
-        makes the data-noise scale of every cell an unknown with the prior lambda^2 ~ InverseGamma(a0, b0) (MonteCarlo.set_noise)."""
+        makes the data-noise scale of every cell an unknown with the prior lambda^2 ~ InverseGamma(a0, b0) (MonteCarlo.set_noise).
+        prior: (smooth, damp) or (smooth, damp, vref) adds the Gaussian smoothness prior to the box (MonteCarlo.set_prior)."""
         nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
         vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
         vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
@@ -455,6 +456,8 @@ class Context:
             mc.set_aniso(**aniso)
         if noise is not None:
             mc.set_noise(*noise)
+        if prior is not None:
+            mc.set_prior(*prior)
         return mc
 
     def ray_paths(self):
@@ -703,6 +706,28 @@ class MonteCarlo:
         r = dict(lam_mean=np.zeros(shp, np.float32), lam_std=np.zeros(shp, np.float32), ndata=np.zeros(shp, np.int32))
         self.ctx._check(self.ctx.lib.dazim_mc_noise_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in ("lam_mean", "lam_std", "ndata"))))
         return r
+
+    def set_prior(self, smooth, damp, vref=None):
+        """Gaussian smoothness prior (dazim_mc_set_prior): column_lsq's regulariser as a prior of precision smooth^2 L^T L +
+        damp^2 I about vref[nz-1][ny-2][nx-2] (None: vel0's knots), truncated by the box; every decision is then taken on the energy
+        plus Q = d^T P d.  smooth = damp = 0 is the default, the box alone.  Refused once a step has been done"""
+        if vref is not None and not _is_torch(vref):
+            vref = np.ascontiguousarray(vref, np.float32).reshape(self.nlay, self.ny - 2, self.nx - 2)
+        self.ctx._check(self.ctx.lib.dazim_mc_set_prior(self.ctx._h, self._h, float(smooth), float(damp), _ptr(vref, np.float32)))
+
+    def prior_state(self):
+        """the prior and, while it is on, copies of its centre and energies (dazim_mc_prior_state): dict smooth, damp,
+        vref[nz-1][ny-2][nx-2], q[ncol] (the Q of the chains' current states); dict smooth = 0, damp = 0 alone while it is off"""
+        s, d = C.c_float(0), C.c_float(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_prior_state(self.ctx._h, self._h, C.byref(s), C.byref(d), None, None))
+        out = dict(smooth=s.value, damp=d.value)
+        if s.value == 0 and d.value == 0:
+            return out
+        vref = np.zeros((self.nlay, self.ny - 2, self.nx - 2), np.float32)
+        q = np.zeros(self.ncol, np.float64)
+        self.ctx._check(self.ctx.lib.dazim_mc_prior_state(self.ctx._h, self._h, None, None, _ptr(vref), _ptr(q)))
+        out.update(vref=vref, q=q)
+        return out
 
     def step(self, pv, record):
         """one step on pv[kmax][ncol] (fp64; numpy or torch-cuda), the curves of proposals(); record 0 = burn-in"""

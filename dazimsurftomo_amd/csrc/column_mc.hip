@@ -19,6 +19,11 @@
 // lambda is integrated out in closed form: k_mc_step<KIND, TEMPER, 1> takes every decision on the energy X = 2 a log(b0 + chi^2 / 2)
 // in place of chi^2 (mc_energy), each recorded rung-0 lane adds sqrt(B) and B = b0 + chi^2 / 2 of its state to its own column, and
 // k_mc_noise_final turns those sums into the posterior mean and std of lambda per cell (Rao-Blackwellisation again).
+//
+// Gaussian smoothness prior (dazim_mc_set_prior): dazim_column_lsq's regulariser read as a prior, exp(-Q / 2) with Q = d^T (smooth^2
+// L^T L + damp^2 I) d, d the state's knots minus a reference, inside the box.  k_mc_step<KIND, TEMPER, NOISE, 1> takes every decision
+// on E + Q in place of E (mc_prior_q; a rung samples (likelihood x Gaussian prior)^beta) and keeps the Q of every chain's state
+// in pq [ncol].  The best model stays the one of lowest raw chi^2: the best-fitting model, not the maximum a posteriori.
 #include "mc_internal.h"
 
 #include <algorithm>
@@ -32,6 +37,23 @@ template <int NOISE>
 __device__ __forceinline__ double mc_energy(const McDev &M, double a, double chi2) {
   if constexpr (NOISE) return 2.0 * a * log((double)M.nb0 + 0.5 * chi2);
   else return chi2;
+}
+
+// the prior energy Q = ps2 |L d|^2 + pd2 |d|^2 of column col of v [nz][ncol] (cur or prop), d = v - pref over the nlay sampled knots;
+// row a of L is 2 d_a at both ends and (2 d_a - d_{a-1}) - d_{a+1} between them (dz_ltl's L).  fp64, both sums in knot order
+__device__ __forceinline__ double mc_prior_q(const McDev &M, const float *__restrict__ v, long col, int cell) {
+  const int n = M.nlay;
+  double q1 = 0.0, q2 = 0.0, dm = 0.0;
+  double d = (double)v[col] - (double)M.pref[cell];
+  for (int a = 0; a < n; a++) {
+    const double dp = a + 1 < n ? (double)v[(a + 1) * M.ncol + col] - (double)M.pref[(long)(a + 1) * M.ncell + cell] : 0.0;
+    const double t = (a == 0 || a == n - 1) ? 2.0 * d : (2.0 * d - dm) - dp;
+    q1 += t * t;
+    q2 += d * d;
+    dm = d;
+    d = dp;
+  }
+  return M.ps2 * q1 + M.pd2 * q2;
 }
 
 // the lanes of rung r: chains r, r + ntemp, ..
@@ -217,7 +239,9 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
 // the rung-0 lanes record.  Each lane carries its chi^2 in a register from the decision through the swap.
 // NOISE 1 (dazim_mc_set_noise): the lane counts the cell's nd in its weight loop, the decision and the swap compare mc_energy of the
 // two chi^2, and a recorded lane adds sqrt(B) and B of its state to its own column of nsum.  The handle keeps raw chi^2 throughout.
-template <int KIND, int TEMPER, int NOISE>
+// PRIOR 1 (dazim_mc_set_prior): the lane walks its column of prop for Q', the decision and the swap compare energy + Q (the rules
+// for +inf still test chi^2 alone), Q travels beside chi^2 through the swap's shuffles, and pq keeps the Q of the lane's state.
+template <int KIND, int TEMPER, int NOISE, int PRIOR>
 __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__restrict__ pv, long long step, int first, int record,
                                                      int adapt, int nadapt) {
   __shared__ float s_scale;
@@ -234,6 +258,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
   double na = 0.0;
   double chi2s = INFINITY;   // TEMPER: the chain's chi^2 after the decision, then after the swap
   unsigned wswap = 0u;       // TEMPER: word 1 of block(step, gid, 0), the swap uniform of a pair's lower chain
+  double qp = 0.0, qs = 0.0;   // PRIOR: Q of the proposal; Q of the chain's state after the decision, then after the swap
   bool acc = false;
   if (act) {
     for (int p = 0; p < M.kmax; p++) {
@@ -250,6 +275,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       chi2p += r * r;
     }
     if constexpr (NOISE) na = (double)M.na0 + 0.5 * nd;
+    if constexpr (PRIOR) qp = mc_prior_q(M, M.prop, col, cell);
     if (first) {
       acc = true;
     } else {
@@ -263,12 +289,21 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       if (TEMPER || !isinf(chi2c)) mc_block(w, step, gid, 0u, M.seed);
       wswap = w[1];
       chi2s = chi2c;
-      acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * beta * (xp - xc);
+      if constexpr (PRIOR) {
+        qs = M.pq[col];
+        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * beta * ((xp + qp) - (xc + qs));
+      } else {
+        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * beta * (xp - xc);
+      }
     }
     if (acc) {
       for (int k = 0; k < M.nlay; k++) M.cur[k * M.ncol + col] = M.prop[k * M.ncol + col];
       M.chi2[col] = chi2p;
       chi2s = chi2p;
+      if constexpr (PRIOR) {
+        M.pq[col] = qp;
+        qs = qp;
+      }
     }
   }
   const unsigned long long bacc = first ? 0ull : __ballot(act && acc);
@@ -282,12 +317,22 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       const bool lower = act && rung + 1 < nt && (rung & 1) == par;
       const bool upper = act && rung > 0 && ((rung - 1) & 1) == par;
       const double cup = __shfl_down(chi2s, 1), cdn = __shfl_up(chi2s, 1);
+      double qup = 0.0, qdn = 0.0;
+      if constexpr (PRIOR) {
+        qup = __shfl_down(qs, 1);
+        qdn = __shfl_up(qs, 1);
+      }
       int sw = 0;
       if (lower) {
         if (isinf(chi2s)) sw = !isinf(cup);
-        else if (!isinf(cup))
-          sw = log(mc_uniform(wswap)) <
-               0.5 * (M.beta[rung] - M.beta[rung + 1]) * (mc_energy<NOISE>(M, na, chi2s) - mc_energy<NOISE>(M, na, cup));
+        else if (!isinf(cup)) {
+          if constexpr (PRIOR)
+            sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) *
+                                              ((mc_energy<NOISE>(M, na, chi2s) + qs) - (mc_energy<NOISE>(M, na, cup) + qup));
+          else
+            sw = log(mc_uniform(wswap)) <
+                 0.5 * (M.beta[rung] - M.beta[rung + 1]) * (mc_energy<NOISE>(M, na, chi2s) - mc_energy<NOISE>(M, na, cup));
+        }
       }
       const int swu = __shfl_up(sw, 1);
       const bool swp = lower ? sw != 0 : (upper && swu != 0);
@@ -300,6 +345,10 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       if (swp) {
         chi2s = lower ? cup : cdn;
         M.chi2[col] = chi2s;
+        if constexpr (PRIOR) {
+          qs = lower ? qup : qdn;
+          M.pq[col] = qs;
+        }
       }
       const unsigned long long btry = __ballot(lower), bswp = __ballot(lower && sw != 0);
       if (ch < nt - 1) {
@@ -532,10 +581,21 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_noise_final(McDev M, float *__re
   lam_std[cell] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
 }
 
-// the step kernel of a handle: [noise][kind][tempered]
+// the step kernel of a handle: [prior][noise][kind][tempered]
 using McStepKernel = void (*)(McDev, const double *, long long, int, int, int, int);
-constexpr McStepKernel MC_STEP[2][2][2] = {{{k_mc_step<0, 0, 0>, k_mc_step<0, 1, 0>}, {k_mc_step<1, 0, 0>, k_mc_step<1, 1, 0>}},
-                                           {{k_mc_step<0, 0, 1>, k_mc_step<0, 1, 1>}, {k_mc_step<1, 0, 1>, k_mc_step<1, 1, 1>}}};
+#define MC_STEP_SET(P)                                                                            \
+  {{{k_mc_step<0, 0, 0, P>, k_mc_step<0, 1, 0, P>}, {k_mc_step<1, 0, 0, P>, k_mc_step<1, 1, 0, P>}}, \
+   {{k_mc_step<0, 0, 1, P>, k_mc_step<0, 1, 1, P>}, {k_mc_step<1, 0, 1, P>, k_mc_step<1, 1, 1, P>}}}
+constexpr McStepKernel MC_STEP[2][2][2][2] = {MC_STEP_SET(0), MC_STEP_SET(1)};
+#undef MC_STEP_SET
+
+// the Q of every chain's state into pq (dazim_mc_set_prior; the step keeps it from there on), lane = chain
+__global__ __launch_bounds__(MC_WAVE) void k_mc_prior_q(McDev M) {
+  const int cs = blockIdx.x, ch = threadIdx.x;
+  if (ch >= M.nchain) return;
+  const long col = (long)cs * M.nchain + ch;
+  M.pq[col] = mc_prior_q(M, M.cur, col, M.cell_of[cs]);
+}
 
 // one step on the curves pv (device) of the current proposals; enqueued on the ctx stream, no host wait
 int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
@@ -550,7 +610,7 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
     DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
     const size_t lds =
         mc->kind == 1 ? ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double) : 0;
-    const McStepKernel kern = MC_STEP[mc->noise][mc->kind][mc->d.ntemp > 1];
+    const McStepKernel kern = MC_STEP[mc->prior][mc->noise][mc->kind][mc->d.ntemp > 1];
     hipLaunchKernelGGL(kern, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record, (int)adapt,
                        mc->nadapt);
     DZ_HIP(hipGetLastError());
@@ -862,6 +922,73 @@ int dazim_mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u, float
   return 0;
 }
 
+int dazim_mc_set_prior(dazim_ctx *ctx, dazim_mc *mc, float smooth, float damp, const float *vref_u) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_set_prior"))) return rc;
+  if (!(std::isfinite(smooth) && smooth >= 0.0f) || !(std::isfinite(damp) && damp >= 0.0f))
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_prior: smooth %g or damp %g is not finite and >= 0", smooth, damp);
+  if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_prior: the handle has done %lld steps", (long long)mc->nstep);
+  McDev &M = mc->d;
+  if (smooth == 0.0f && damp == 0.0f) {
+    mc->prior = 0;
+    mc->psmooth = mc->pdamp = 0.0f;
+    M.ps2 = M.pd2 = 0.0;
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  const size_t nk = (size_t)M.nlay * M.ncell;
+  std::vector<float> vref;
+  if (vref_u) {
+    if ((rc = mc_to_host(ctx, vref_u, nk, vref))) return rc;
+    for (size_t e = 0; e < nk; e++)
+      if (!std::isfinite(vref[e]))
+        return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_prior: a non-finite vref at knot %d, cell %d", (int)(e / M.ncell),
+                       (int)(e % M.ncell));
+  } else {   // vel0's knots at the inner cells
+    std::vector<float> vel0;
+    if ((rc = mc_to_host(ctx, M.vel0, (size_t)M.nz * M.nx * M.ny, vel0))) return rc;
+    vref.resize(nk);
+    const int nvx = M.nx - 2;
+    for (int k = 0; k < M.nlay; k++)
+      for (int c = 0; c < M.ncell; c++)
+        vref[(size_t)k * M.ncell + c] = vel0[((size_t)k * M.ny + (c / nvx + 1)) * M.nx + (c % nvx + 1)];
+  }
+  if (!M.pq) {
+    float *r;
+    if ((rc = mc_alloc(mc, nk, &r)) || (rc = mc_alloc(mc, (size_t)M.ncol, &M.pq))) return rc;
+    M.pref = r;
+  }
+  M.ps2 = (double)smooth * (double)smooth;
+  M.pd2 = (double)damp * (double)damp;
+  DZ_HIP(hipMemcpyAsync((void *)M.pref, vref.data(), nk * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (M.ncs > 0) {   // the start models are the states until the first step
+    hipLaunchKernelGGL(k_mc_prior_q, dim3((unsigned)M.ncs), dim3(MC_WAVE), 0, ctx->stream, M);
+    DZ_HIP(hipGetLastError());
+  }
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  mc->psmooth = smooth;
+  mc->pdamp = damp;
+  mc->prior = 1;
+  return 0;
+}
+
+int dazim_mc_prior_state(dazim_ctx *ctx, dazim_mc *mc, float *smooth, float *damp, float *vref, double *q) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_prior_state"))) return rc;
+  const McDev &M = mc->d;
+  if (smooth) *smooth = mc->psmooth;
+  if (damp) *damp = mc->pdamp;
+  if (!mc->prior) {
+    if (vref || q) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_prior_state: dazim_mc_set_prior has not switched the prior on");
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  DZ_HIP(mc_get(ctx, vref, M.pref, (size_t)M.nlay * M.ncell * 4));
+  DZ_HIP(mc_get(ctx, q, M.pq, (size_t)M.ncol * 8));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv_u, int record) {
   int rc;
   if ((rc = mc_check(ctx, mc, "dazim_mc_step"))) return rc;
@@ -971,6 +1098,7 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
   ctx->ksec["mc.swap_med"] = swap_med;
   ctx->ksec["mc.proposal"] = mc->kind;
   ctx->ksec["mc.noise"] = mc->noise;
+  ctx->ksec["mc.prior"] = mc->prior;
   ctx->ksec["mc.cov_cells"] = cov_cells;
   if (n_no_root) *n_no_root = (int64_t)(c1[0] - c0[0]);
   return 0;

@@ -78,6 +78,10 @@ struct McDev {
   double *nsum;                // [2][ncol]: sums of sqrt(B) and of B over the recorded states, B = nb0 + chi^2 / 2
   long long *ncnt;             // [ncol]: states in them
   const double *ngam;          // [MC_MAXPER + 1]: exp(lgamma(a - 0.5) - lgamma(a)) at a = na0 + nd / 2, made on the host
+  // Gaussian smoothness prior only (null and 0 otherwise): precision ps2 L^T L + pd2 I about pref, truncated by the box
+  double ps2, pd2;             // (double)smooth^2, (double)damp^2
+  const float *pref;           // [nlay][ncell]: the prior's centre
+  double *pq;                  // [ncol]: the prior energy Q of every chain's state
 };
 
 // Gc/Gs (dazim_mc_set_aniso).  Cold column cs * ncold + g is chain g * ntemp of sampled cell cs.
@@ -108,6 +112,8 @@ struct dazim_mc {
   McAniso an{};             // ... its maps and sums (sized for ntemp = 1, so that any ladder fits)
   int64_t naniso = 0;       // ... samples taken
   int noise = 0;            // hierarchical noise: 0 = off (d.na0, d.nb0 hold the prior while it is on)
+  int prior = 0;            // Gaussian smoothness prior: 0 = off (d.ps2, d.pd2, d.pref hold it while it is on)
+  float psmooth = 0.0f, pdamp = 0.0f;
   std::vector<void *> blocks;
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };

@@ -3,7 +3,7 @@
 ! section 14), where SurfDepthFromMaps_amd returns one linearised model.
 !
 !   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a
-!                            [noise_a0 [noise_b0]]]]]]]]]]]]]
+!                            [noise_a0 [noise_b0 [smooth_vs [damp_vs]]]]]]]]]]]]]]]
 !
 ! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
 ! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
@@ -28,6 +28,14 @@
 ! lambda is integrated out of the chains' target, so the Vs spreads carry the uncertainty of the noise level, and its posterior per
 ! cell comes back from the chains (dazim_mc_set_noise).  One more settings line, one more summary line, one more file:
 !   noise_posterior_mc.dat       per inner cell: lon lat, mean and std of lambda, sigma_c * mean (the data std in km/s), periods
+! smooth_vs 0 and damp_vs 0 (default): the uniform box is the whole prior, every file and log byte as before.  Otherwise the box
+! truncates a Gaussian prior about MOD of precision smooth_vs^2 L^T L + damp_vs^2 I, SurfDepthFromMaps_amd's regulariser read as the
+! prior its resolution output reads it as (dazim_mc_set_prior): Vs varies smoothly with depth about MOD, and the directions the
+! periods do not resolve become proper.  One more settings line, one more summary line and, with noise_a0 0, one more file:
+!   Vs_prior_check_mc.dat        per inner cell and sampled knot: lon lat depth, the chains' std, the linearised std_post of
+!                                dazim_column_resolution at the posterior-mean model (its kernels, the run's weights, smooth_vs,
+!                                damp_vs: SurfDepthFromMaps_amd's resolution block) and their ratio (0 where std_post is 0)
+! With noise_a0 > 0 sigma_c is not the data std, the linearised std has nothing to stand on, and the file is not written.
 !
 ! Outputs (names of their own, so that the three programs can share a directory):
 !   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
@@ -51,6 +59,12 @@ program SurfDepthMC_amd
   integer(c_int64_t), allocatable :: nsamp(:, :)
   integer :: npass, nskip
   real :: noise_a0, noise_b0
+  real :: smooth_vs, damp_vs
+  logical :: prior_on
+  real*8, allocatable, target :: svs(:, :, :), svp(:, :, :), srho(:, :, :), skern(:, :, :)
+  real*8, allocatable :: pvk(:, :)
+  real, allocatable :: res(:, :, :, :), rtrace(:, :), ratio(:, :, :)
+  integer(c_int) :: nempty_res, nbad
   real, allocatable :: lam_mean(:, :), lam_std(:, :)
   integer(c_int), allocatable :: ndata(:, :)
   integer, parameter :: nswap = 1
@@ -78,7 +92,7 @@ program SurfDepthMC_amd
   write (*, *)
   if (command_argument_count() < 1) error stop &
     'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a '// &
-    '[noise_a0 [noise_b0]]]]]]]]]]]]]'
+    '[noise_a0 [noise_b0 [smooth_vs [damp_vs]]]]]]]]]]]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -104,6 +118,9 @@ program SurfDepthMC_amd
   noise_a0 = 0; noise_b0 = 1
   call optional_arg(13, noise_a0)
   call optional_arg(14, noise_b0)
+  smooth_vs = 0; damp_vs = 0
+  call optional_arg(15, smooth_vs)
+  call optional_arg(16, damp_vs)
   if (nsample < 1) error stop 'nsample must be at least 1'
   if (nchain < 1 .or. nchain > 64) error stop 'nchain must be 1..64'
   if (width < 0) error stop 'width must not be negative'
@@ -122,6 +139,9 @@ program SurfDepthMC_amd
     'smooth_gcs must not be negative, nor 0 together with para.in''s damping'
   if (.not. (noise_a0 >= 0 .and. noise_a0 <= huge(noise_a0))) error stop 'noise_a0 must not be negative'
   if (noise_a0 > 0 .and. .not. (noise_b0 > 0 .and. noise_b0 <= huge(noise_b0))) error stop 'noise_b0 must be positive'
+  if (.not. (smooth_vs >= 0 .and. smooth_vs <= huge(smooth_vs))) error stop 'smooth_vs must be finite and not negative'
+  if (.not. (damp_vs >= 0 .and. damp_vs <= huge(damp_vs))) error stop 'damp_vs must be finite and not negative'
+  prior_on = smooth_vs > 0 .or. damp_vs > 0
   ncold = nchain/ntemp
   nlay = nz - 1
   ncell = (nx - 2)*(ny - 2)
@@ -152,6 +172,8 @@ program SurfDepthMC_amd
       aniso_thin, ' recorded steps;  smoothing', smooth_gcs, '  damping', p%damp, '  sigma_a (km/s)', sigma_a
     if (noise_a0 > 0) write (q, '(a,f9.4,a,f9.4,a)') ' hierarchical noise: data std lambda * sigma_c per cell, lambda^2 ~ InverseGamma(', &
       noise_a0, ',', noise_b0, '), integrated out of the chains'' target'
+    if (prior_on) write (q, '(a,f8.3,a,f8.3,a)') ' Gaussian prior about MOD inside the box: smoothing', smooth_vs, '  damping', &
+      damp_vs, ' (precision smooth^2 L^T L + damp^2 I)'
   end do
 
   call read_mod('MOD', p, depz, vsf)
@@ -201,6 +223,7 @@ program SurfDepthMC_amd
   if (aniso_thin > 0) call dazim_check(dazim_mc_set_aniso(dazim_handle, mc, aniso_thin, amap, wa, smooth_gcs, p%damp), &
                                        'Gc/Gs posteriors')
   if (noise_a0 > 0) call dazim_check(dazim_mc_set_noise(dazim_handle, mc, noise_a0, noise_b0), 'hierarchical noise')
+  if (prior_on) call dazim_check(dazim_mc_set_prior(dazim_handle, mc, smooth_vs, damp_vs, c_null_ptr), 'Gaussian prior')
   call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
   t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
   t_disp = real(dazim_last_kernel_seconds(dazim_handle, 'mc.disp'//c_null_char))
@@ -240,6 +263,19 @@ program SurfDepthMC_amd
                                             c_null_ptr, nfail), 'dispersion curves of the best model')
   allocate (rms_b(nx - 2, ny - 2), rms_m(nx - 2, ny - 2), sampled(nx - 2, ny - 2))
   sampled = any(wcov /= 0.0, dim=3)
+  ! ---- the chains' std against the linearised std_post at the posterior-mean model (SurfDepthFromMaps_amd's resolution block) ------
+  if (prior_on .and. .not. noise_a0 > 0) then
+    allocate (svs(nx*ny, kmax, nz), svp(nx*ny, kmax, nz), srho(nx*ny, kmax, nz), skern(nx*ny, kmax, nz), pvk(nx*ny, kmax))
+    allocate (res(nx - 2, ny - 2, nlay, 5), rtrace(nx - 2, ny - 2), ratio(nx - 2, ny - 2, nlay))
+    call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vmc, depz, minthk, kmax, tRc, pvk, c_loc(svs), c_loc(svp), &
+                                              c_loc(srho), nfail), 'depth kernels of the mean model')
+    call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kmax, vmc, svs, svp, srho, skern), 'dc/dVs table of the mean model')
+    call dazim_check(dazim_column_resolution(dazim_handle, nx, ny, nlay, kmax, 0, c_loc(skern), wcov, smooth_vs, damp_vs, depz, &
+                                             res(:, :, :, 1), res(:, :, :, 2), res(:, :, :, 3), res(:, :, :, 4), res(:, :, :, 5), &
+                                             c_null_ptr, rtrace, nempty_res, nbad), 'column resolution at the mean model')
+    ratio = 0
+    where (res(:, :, :, 1) > 0) ratio = std/res(:, :, :, 1)
+  end if
   s0 = 0; cnt = 0
   do j = 1, ny - 2
     do i = 1, nx - 2
@@ -320,6 +356,23 @@ program SurfDepthMC_amd
     end do
     deallocate (sorted)
   end if
+  if (prior_on .and. noise_a0 > 0) then
+    do q = 6, 66, 60
+      write (q, '(a)') ' Gaussian prior: Vs_prior_check_mc.dat is not written, with the noise scale unknown sigma_c is not the data std'
+    end do
+  else if (prior_on) then
+    nr = count(spread(sampled, 3, nlay) .and. ratio > 0)
+    if (allocated(sorted)) deallocate (sorted)
+    allocate (sorted(max(nr, 1)))
+    sorted = 0
+    if (nr > 0) sorted(1:nr) = pack(ratio, spread(sampled, 3, nlay) .and. ratio > 0)
+    call sort(sorted)
+    do q = 6, 66, 60
+      write (q, '(a,3f9.4)') ' Gaussian prior: chains'' std / linearised std_post over (cell, knot), quartiles 25/50/75 %:', &
+        sorted(max(1, nint(0.25*nr))), sorted(max(1, (nr + 1)/2)), sorted(max(1, nint(0.75*nr)))
+    end do
+    deallocate (sorted)
+  end if
   do q = 6, 66, 60
     write (q, '(a,f12.5)') ' posterior-mean model: rms_c', rms_all
   end do
@@ -368,6 +421,18 @@ program SurfDepthMC_amd
       do i = 1, nx - 2
         write (64, '(2f10.4,3f12.6,i6)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, lam_mean(i, j), lam_std(i, j), &
           sigma_c*lam_mean(i, j), ndata(i, j)
+      end do
+    end do
+    close (64)
+  end if
+  if (prior_on .and. .not. noise_a0 > 0) then
+    open (64, file='Vs_prior_check_mc.dat')
+    do k = 1, nlay
+      do j = 1, ny - 2
+        do i = 1, nx - 2
+          write (64, '(3f10.4,2f12.6,f12.5)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, depz(k), std(i, j, k), res(i, j, k, 1), &
+            ratio(i, j, k)
+        end do
       end do
     end do
     close (64)

@@ -40,7 +40,7 @@ module dazim_mod
   public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
             dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds, &
             dazim_mc_set_aniso, dazim_mc_aniso_step, dazim_mc_aniso_state, dazim_mc_aniso_result, dazim_mc_set_noise, &
-            dazim_mc_noise_state, dazim_mc_noise_result
+            dazim_mc_noise_state, dazim_mc_noise_result, dazim_mc_set_prior, dazim_mc_prior_state
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -338,6 +338,17 @@ module dazim_mod
     integer(c_int) function dazim_mc_noise_state(ctx, mc, a0, b0, nsum, ncnt) bind(C, name="dazim_mc_noise_state")
       import
       type(c_ptr), value :: ctx, mc, a0, b0, nsum, ncnt
+    end function
+    ! vref: c_loc of [nlay][ny-2][nx-2] real*4, or c_null_ptr for vel0's knots
+    integer(c_int) function dazim_mc_set_prior(ctx, mc, smooth, damp, vref) bind(C, name="dazim_mc_set_prior")
+      import
+      type(c_ptr), value :: ctx, mc, vref
+      real(c_float), value :: smooth, damp
+    end function
+    ! every argument after mc may be c_null_ptr (c_loc of a variable or an array otherwise)
+    integer(c_int) function dazim_mc_prior_state(ctx, mc, smooth, damp, vref, q) bind(C, name="dazim_mc_prior_state")
+      import
+      type(c_ptr), value :: ctx, mc, smooth, damp, vref, q
     end function
     integer(c_int) function dazim_mc_noise_result(ctx, mc, lam_mean, lam_std, ndata) bind(C, name="dazim_mc_noise_result")
       import

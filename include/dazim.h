@@ -454,6 +454,28 @@ int dazim_column_resolution(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, 
  *   device).  DAZIM_E_BAD_ARG when the mode is off and an array is requested.
  *   dazim_mc_noise_result: lam_mean, lam_std [ny-2][nx-2] fp32 and ndata [ny-2][nx-2] int32 (host or device).  Refused with the
  *   mode off or before the first recorded step.
+ * Gaussian smoothness prior (dazim_mc_set_prior; without it, or with smooth = damp = 0, every launch and every result is the one
+ *   above, unchanged): dazim_column_lsq's regulariser read as the prior that dazim_column_resolution reads it as, a Gaussian of
+ *   precision P = smooth^2 L^T L + damp^2 I about a reference column vref, so that the chains' spread means what std_post means and
+ *   the directions the data do not determine become proper.  The uniform box stays: it truncates the Gaussian, and the start models
+ *   are still the box draws.
+ *   Prior energy of a column's fp32 knots v_0..v_{nlay-1} (the fixed last knot takes no part), all in fp64 without contraction:
+ *   s2 = (double)smooth * (double)smooth, d2 likewise; d_k = (double)v_k - (double)vref_k; t_a = 2.0 * d_a for a == 0 or a == nlay-1,
+ *   else t_a = (2.0 * d_a - d_{a-1}) - d_{a+1} (the L of dazim_column_lsq); q1 = sum_a t_a * t_a and q2 = sum_a d_a * d_a, both in
+ *   ascending a from 0.0; Q = s2 * q1 + d2 * q2.  exp(-Q / 2) is the Gaussian of precision P.
+ *   Step: the one above with E + Q in place of E wherever a decision is taken, E = chi2 or, in noise mode, X(chi2); lambda is not
+ *   applied to the prior.  Accept iff log(u) < -0.5 * beta_r * ((E' + Q') - (E + Q)), Q' of the proposal and Q of the state; swap
+ *   D = 0.5 * (beta_r - beta_{r+1}) * ((E_r + Q_r) - (E_{r+1} + Q_{r+1})) with the Q of the states after the decision, and a swap
+ *   exchanges them with the knots: rung r samples (likelihood x Gaussian prior)^beta_r.  The rules for +inf still test chi2 alone.
+ *   The uniforms, the normals, the proposals and their reflection, the scale and covariance adaptation, the records, the histogram,
+ *   the noise record and the Gc/Gs pass do not change, and the handle still stores raw chi2.  The best model stays the state of
+ *   lowest raw chi2: the best-fitting model, not the maximum a posteriori.  Stat "mc.prior" of dazim_mc_run is 0 or 1.
+ *   dazim_mc_set_prior: smooth, damp as in dazim_column_lsq; vref [nlay][ny-2][nx-2] (host or device), NULL = vel0's knots.  smooth
+ *   == 0 and damp == 0 restore the default (vref is not looked at then).  It may come before or after the other dazim_mc_set_*
+ *   calls.  DAZIM_E_BAD_ARG for a negative or non-finite smooth or damp, a non-finite vref, a handle of another context, or once a
+ *   step has been done.
+ *   dazim_mc_prior_state: smooth, damp (0, 0 while the prior is off) and copies of vref and of q [ncol], the Q of the chains' current
+ *   states (each pointer nullable, the arrays host or device).  DAZIM_E_BAD_ARG when the prior is off and an array is requested.
  * dazim_mc_create: vel0 [nz][ny][nx] (the last knot; the result of cells without data), vmin, vmax [nlay][ny-2][nx-2], cobs, wdat
  *   [kmax][ny-2][nx-2] (the layout of dazim_column_lsq), step = the initial s, nadapt >= 1.  Draws the start models.  Refused
  *   (DAZIM_E_BAD_ARG): nchain outside 1..64, nlay outside 1..63, kmax outside 1..60, nbin < 2, a non-finite vmin, vmax, cobs or
@@ -504,6 +526,8 @@ int dazim_mc_aniso_result(dazim_ctx *ctx, dazim_mc *mc, float *mean, float *std,
 int dazim_mc_set_noise(dazim_ctx *ctx, dazim_mc *mc, float a0, float b0);
 int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, double *nsum, int64_t *ncnt);
 int dazim_mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean, float *lam_std, int *ndata);
+int dazim_mc_set_prior(dazim_ctx *ctx, dazim_mc *mc, float smooth, float damp, const float *vref);
+int dazim_mc_prior_state(dazim_ctx *ctx, dazim_mc *mc, float *smooth, float *damp, float *vref, double *q);
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);
 int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
                  int64_t *n_no_root);

@@ -5,6 +5,8 @@
     python tools/mc_step.py --aniso N [--steps S] [--big N]
     python tools/mc_step.py --noise A0 B0 [--steps S] [--proposal K] [--ntemp R [--tmax T]]
     python tools/mc_step.py --program --noise A0 B0 [--dir D] [--proposal K] [--ntemp R [--tmax T]]
+    python tools/mc_step.py --prior S D [--steps S] [--proposal K] [--ntemp R [--tmax T]] [--noise A0 B0]
+    python tools/mc_step.py --program --prior S D [--dir D] [--proposal K] [--ntemp R [--tmax T]] [--noise A0 B0]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -31,7 +33,11 @@ passes (profiles/depth_mc_aniso.md).
 --noise A0 B0: the hierarchical noise scale (dazim_mc_set_noise, lambda^2 ~ InverseGamma(A0, B0)) at S-256 with 32 chains: five
 pairs of runs of S steps, the mode off then on, alternating, each on a fresh handle after its own warm-up run; reports the ms per
 step of the k_mc_step launches of every run and the medians of the five (profiles/depth_mc_noise.md).  With --program: the default
-run with arguments 13 and 14, the log's noise lines among those kept."""
+run with arguments 13 and 14, the log's noise lines among those kept.
+
+--prior S D: the Gaussian smoothness prior (dazim_mc_set_prior, smooth S and damp D about the start model) at S-256 with 32 chains:
+five pairs of runs, the prior off then on, alternating, as for --noise (with --noise the mode is on in both runs of a pair;
+profiles/depth_mc_prior.md).  With --program: the default run with arguments 15 and 16, the log's prior lines among those kept."""
 import argparse
 import json
 import os
@@ -46,7 +52,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None):
+def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None, prior=None):
     import bench
     bench.NX = bench.NY = n
     vel = bench.s256_model().astype(np.float32)
@@ -58,7 +64,7 @@ def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None):
     vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
     wdat = np.full((kmax, n - 2, n - 2), 100.0, np.float32)
     mc = ctx.mc_create(n, n, nz, kmax, nchain, 100, 1, vel, vmin, vmax, cobs, wdat, nadapt=5 if proposal else 50, proposal=proposal,
-                       ntemp=ntemp, tmax=tmax, noise=noise)
+                       ntemp=ntemp, tmax=tmax, noise=noise, prior=prior)
     mc.run(depz, bench.MINTHK, periods, 5, 0)                 # warm-up: code objects, scratch buffers
     nr = mc.run(depz, bench.MINTHK, periods, steps // 2, steps - steps // 2)
     wall, disp, stp = ctx.stat("mc"), ctx.stat("mc.disp"), ctx.stat("mc.step")
@@ -68,6 +74,7 @@ def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None):
     ms = lambda s: 1e3 * s / steps
     return {"grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots ({nlay} sampled), {kmax} periods", "nchain": nchain,
             "noise": list(noise) if noise else None, "median_lam_mean": float(np.median(lam)) if noise else None,
+            "prior": list(prior) if prior else None,
             "proposal": proposal, "ntemp": ntemp, "swap_min": ctx.stat("mc.swap_min"), "swap_med": ctx.stat("mc.swap_med"),
             "cov_cells": int(ctx.stat("mc.cov_cells")), "steps": steps, "curves_per_step": mc.ncol, "ms_per_step": ms(wall),
             "disp_ms_per_step": ms(disp),
@@ -76,11 +83,16 @@ def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None):
             "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
 
 
-def noise_cases(ctx, steps, proposal, ntemp, tmax, noise, pairs=5):
+def noise_cases(ctx, steps, proposal, ntemp, tmax, noise, pairs=5, prior=None):
+    """pairs of runs off / on of the noise mode or, with `prior`, of the prior (the noise mode then as given in both)"""
     runs = {"off": [], "on": []}
     for _ in range(pairs):
-        for name, arg in (("off", None), ("on", tuple(noise))):
-            runs[name].append(one_case(ctx, 54, 32, steps, proposal, ntemp, tmax, arg))
+        for name in ("off", "on"):
+            if prior:
+                runs[name].append(one_case(ctx, 54, 32, steps, proposal, ntemp, tmax, tuple(noise) if noise else None,
+                                           tuple(prior) if name == "on" else None))
+            else:
+                runs[name].append(one_case(ctx, 54, 32, steps, proposal, ntemp, tmax, tuple(noise) if name == "on" else None))
     out = dict(runs["on"][-1])
     for name in runs:
         for key in ("mc_step_ms_per_step", "ms_per_step", "disp_ms_per_step"):
@@ -146,7 +158,7 @@ cccccccccc periods
 """
 
 
-def program_run(ctx, d, proposal, ntemp, tmax, noise=None):
+def program_run(ctx, d, proposal, ntemp, tmax, noise=None, prior=None):
     import bench
     n = bench.NX = bench.NY = 54
     vel = bench.s256_model().astype(np.float32)
@@ -171,19 +183,23 @@ def program_run(ctx, d, proposal, ntemp, tmax, noise=None):
                     f.write("%10.4f%10.4f%10.4f%10.4f\n" % (100.0 + (j - 1) * 0.25, 30.0 - (i - 1) * 0.25, periods[t], pv[t, j, i]))
     exe = os.path.join(ROOT, "host", "SurfDepthMC_amd")
     t0 = time.perf_counter()
-    args = ["2000", "32", "0", "0.01", "1", str(proposal)] if proposal or ntemp > 1 or noise else []
-    if ntemp > 1 or noise:
+    args = ["2000", "32", "0", "0.01", "1", str(proposal)] if proposal or ntemp > 1 or noise or prior else []
+    if ntemp > 1 or noise or prior:
         args += [str(ntemp), "%g" % tmax]
-    if noise:                        # aniso_thin, smooth_gcs, sigma_a at their defaults, then noise_a0, noise_b0
-        args += ["0", "2.0", "0.01", "%g" % noise[0], "%g" % noise[1]]
+    if noise or prior:               # aniso_thin, smooth_gcs, sigma_a at their defaults, then noise_a0, noise_b0
+        args += ["0", "2.0", "0.01"] + (["%g" % noise[0], "%g" % noise[1]] if noise else ["0", "1"])
+    if prior:                        # smooth_vs, damp_vs
+        args += ["%g" % prior[0], "%g" % prior[1]]
     out = subprocess.run([exe, "para.in"] + args, cwd=d, capture_output=True, text=True, timeout=1500)
     wall = time.perf_counter() - t0
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     log = open(os.path.join(d, "para.in_mc.log")).read().splitlines()
     keep = [l.strip() for l in log if any(k in l for k in ("cells sampled", "without a root", "run", "acceptance", "R-hat", "rms_c", "proposal",
-                                                                "covariance", "tempering", "ladder", "swap", "T = 1", "noise"))]
+                                                                "covariance", "tempering", "ladder", "swap", "T = 1", "noise",
+                                                                "Gaussian prior"))]
     return {"program": "SurfDepthMC_amd para.in (defaults: 2000 + 2000 steps, 32 chains)", "proposal": proposal, "ntemp": ntemp,
-            "noise": list(noise) if noise else None, "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots, {kmax} periods",
+            "noise": list(noise) if noise else None, "prior": list(prior) if prior else None, "args": args,
+            "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots, {kmax} periods",
             "wall_s": wall, "log": keep}
 
 
@@ -199,6 +215,7 @@ def main():
     ap.add_argument("--tmax", type=float, default=16.0)
     ap.add_argument("--aniso", type=int, default=0)
     ap.add_argument("--noise", type=float, nargs=2, default=None, metavar=("A0", "B0"))
+    ap.add_argument("--prior", type=float, nargs=2, default=None, metavar=("S", "D"))
     a = ap.parse_args()
     ctx = dz.Context(0)
     if a.aniso > 0:
@@ -208,7 +225,11 @@ def main():
         return
     if a.program:
         with tempfile.TemporaryDirectory() as tmp:
-            print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal, a.ntemp, a.tmax, a.noise)), flush=True)
+            print(json.dumps(program_run(ctx, a.dir or tmp, a.proposal, a.ntemp, a.tmax, a.noise, a.prior)), flush=True)
+        return
+    if a.prior:
+        print(json.dumps(noise_cases(ctx, a.steps, a.proposal, a.ntemp, a.tmax, a.noise, prior=a.prior)), flush=True)
+        ctx.close()
         return
     if a.noise:
         print(json.dumps(noise_cases(ctx, a.steps, a.proposal, a.ntemp, a.tmax, a.noise)), flush=True)
