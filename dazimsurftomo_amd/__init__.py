@@ -429,6 +429,34 @@ class Context:
         out["n_empty"], out["n_failed"] = ne.value, nf.value
         return out
 
+    def map_posterior(self, A, m_data, nx, ny, kmax, azim, damp, sel=None, width=True):
+        """posterior std and resolution of the per-period maps (dazim_map_posterior) from the matrix lsmr is given: A a SparseMatrix
+        whose first m_data rows are the weighted data rows, damp lsmr's damping, sel local indices blk*ncell + cell whose rows of
+        Rm are wanted (numpy, or torch-cuda for torch-cuda outputs).  Returns a dict: std_post, std_noise, rdiag, rsum, width (None
+        when off), leak (None unless azim), each [nblk][kmax][ny-2][nx-2]; trace [nblk][kmax]; rows [kmax][nsel][n_g] (None without
+        sel); n_failed."""
+        nblk = 3 if azim else 1
+        ng = nblk * (nx - 2) * (ny - 2)
+        if sel is not None and _is_torch(sel):
+            import torch
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=sel.device)
+        else:
+            new = lambda *shape: np.zeros(shape, np.float32)
+            sel = None if sel is None else np.ascontiguousarray(sel, np.int32)
+        nsel = 0 if sel is None else int(sel.shape[0])
+        out = {k: new(nblk, kmax, ny - 2, nx - 2) for k in ("std_post", "std_noise", "rdiag", "rsum")}
+        out["width"] = new(nblk, kmax, ny - 2, nx - 2) if width else None
+        out["leak"] = new(nblk, kmax, ny - 2, nx - 2) if azim else None
+        out["rows"] = new(kmax, nsel, ng) if nsel else None
+        out["trace"] = new(nblk, kmax)
+        nf = C.c_int(0)
+        f32 = lambda k: _ptr(out[k], np.float32)
+        self._check(self.lib.dazim_map_posterior(self._h, A._h, C.c_int64(int(m_data)), nx, ny, int(kmax), int(bool(azim)), C.c_float(damp),
+                                                 f32("std_post"), f32("std_noise"), f32("rdiag"), f32("rsum"), f32("width"), f32("leak"),
+                                                 nsel, _ptr(sel, np.int32), f32("rows"), f32("trace"), C.byref(nf)))
+        out["n_failed"] = nf.value
+        return out
+
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
                   ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None, prior=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],

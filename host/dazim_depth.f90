@@ -2,7 +2,7 @@
 ! SurfPhaseMaps_amd into a depth model, cell by cell, on one MI355X: Vs(z) from each cell's phase-velocity dispersion curve and, in
 ! iso-mode F, Gc/L(z) and Gs/L(z) from its 2-psi curves (DESIGN.md section 13).
 !
-!   SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c [resolution]]]]
+!   SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c [resolution [map_sigma]]]]]
 !
 ! Inputs: the unchanged para.in and MOD of DAzimSurfTomo_amd (read_para, read_mod of module dazim_io; the data file is not opened),
 ! the maps period_phaseV_map.dat (and period_Azm_tomo_map.inv in iso-mode F) and, if present, period_map_coverage.dat.  Weights:
@@ -12,6 +12,9 @@
 ! inner cells (w = 0 where pvRc = 0) -> dazim_column_lsq (nlay = nz-1) -> dazim_model_update (para.in's minvel, maxvel).
 ! Gc, Gs (iso-mode F): on the final Vs, dazim_ti_kernels, then one dazim_column_lsq on Lsen_Gsc with the two right-hand sides a1, a2:
 ! the 2-psi terms are linear in Gc, Gs, so they are solved for whole.
+! map_sigma = 1 (default 0): the Vs weights become 1/max(sigma_c, std_post) per cell and period where DWS > 0, std_post the posterior
+! std of c in period_map_uncertainty.dat (SurfPhaseMaps_amd with uncertainty = 1; the run stops without that file); sigma_c is then a
+! floor, and a std that is not finite means no data.
 ! resolution = 1 (default 0: nothing below is computed or written): how well the answer is known, per inner cell and inverted knot,
 ! from dazim_column_resolution on the final model: one more dazim_dispersion_kernels with kernels, dazim_vs_kernels, then the
 ! posterior std (the regulariser read as a Gaussian prior), the std that the data errors 1/w alone leave, the diagonal and the row
@@ -44,7 +47,7 @@ program SurfDepthFromMaps_amd
   real, allocatable :: cmap(:, :, :), amap(:, :, :, :), wcov(:, :, :), w(:, :, :), r(:, :, :, :), x(:, :, :, :)
   real, allocatable :: gcf(:, :, :), gsf(:, :, :), ustats(:, :), stats(:, :, :), res(:, :, :, :), rtrace(:, :)
   real*8, allocatable :: pvk(:, :)
-  integer :: ires
+  integer :: ires, isig
   integer(c_int) :: nbad
   real :: dummy1(1), rms0, rms1, maxdv
   real*8 :: s0, s1, cnt
@@ -54,7 +57,7 @@ program SurfDepthFromMaps_amd
   write (*, *)
   write (*, *) '                       SurfDepthFromMaps'
   write (*, *)
-  if (command_argument_count() < 1) error stop 'usage: SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c [resolution]]]]'
+  if (command_argument_count() < 1) error stop 'usage: SurfDepthFromMaps_amd para.in [smooth_vs [smooth_gcs [sigma_c [resolution [map_sigma]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -72,6 +75,12 @@ program SurfDepthFromMaps_amd
   call optional_arg(5, ires)
   if (ires /= 0 .and. ires /= 1) then
     write (*, '(a,i0)') ' ERROR: resolution must be 0 or 1, not ', ires
+    error stop 'bad argument'
+  end if
+  isig = 0
+  call optional_arg(6, isig)
+  if (isig /= 0 .and. isig /= 1) then
+    write (*, '(a,i0)') ' ERROR: map_sigma must be 0 or 1, not ', isig
     error stop 'bad argument'
   end if
   nlay = nz - 1
@@ -95,6 +104,7 @@ program SurfDepthFromMaps_amd
   allocate (cmap(nx - 2, ny - 2, kmax), wcov(nx - 2, ny - 2, kmax))
   call read_map('period_phaseV_map.dat', p, 4, 4, cmap, .true.)
   call coverage_weights(p, sigma_c, wcov)
+  if (isig == 1) call uncertainty_weights(p, sigma_c, wcov)
   if (.not. iso_mod) then
     allocate (amap(nx - 2, ny - 2, kmax, 2))
     call read_map('period_Azm_tomo_map.inv', p, 9, 8, amap(:, :, :, 1), .true.)

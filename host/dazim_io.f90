@@ -8,7 +8,7 @@ module dazim_io
   private
   public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
   public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
-  public :: write_resolution
+  public :: write_resolution, uncertainty_weights
 
   real, parameter :: pi = 3.1415926535898
   real*8, parameter :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
@@ -225,6 +225,31 @@ contains
         write (q, '(a)') ' period_map_coverage.dat is absent: weight 1/sigma_c on every cell and period'
       end do
     end if
+  end subroutine
+
+  ! map_sigma = 1 of the depth program: on the pairs coverage_weights gave a weight, 1/max(sigma_c, std_post) with the posterior std
+  ! of c from period_map_uncertainty.dat (its fourth column; SurfPhaseMaps_amd with uncertainty = 1), sigma_c the floor; a std that is
+  ! not finite (a period that could not be factored) means no data, weight 0.  Stops when the file is missing, as read_map does.
+  subroutine uncertainty_weights(p, sigma_c, wcov)
+    type(para_t), intent(in) :: p
+    real, intent(in) :: sigma_c
+    real, intent(inout) :: wcov(p%nx - 2, p%ny - 2, p%kmaxRc)
+    real, allocatable :: sd(:, :, :)
+    logical, allocatable :: finite(:, :, :)
+    integer :: q
+    allocate (sd(p%nx - 2, p%ny - 2, p%kmaxRc), finite(p%nx - 2, p%ny - 2, p%kmaxRc))
+    call read_map('period_map_uncertainty.dat', p, 4, 4, sd, .true.)
+    finite = sd == sd .and. abs(sd) <= huge(sd)
+    do q = 6, 66, 60
+      write (q, '(a,i8,a,i8,a,i8)') ' period_map_uncertainty.dat: weight 1/max(sigma_c, std_post) on', count(wcov > 0.0 .and. finite), &
+        ' (cell, period) pairs;', count(wcov > 0.0 .and. finite .and. sd <= sigma_c), ' at the floor sigma_c;', &
+        count(wcov > 0.0 .and. .not. finite), ' without a finite std_post (no data)'
+    end do
+    where (wcov > 0.0 .and. finite)
+      wcov = 1.0/max(sigma_c, sd)
+    elsewhere (wcov > 0.0)
+      wcov = 0.0
+    end where
   end subroutine
 
   ! great-circle distance on a 6371 km sphere from colatitude/longitude in radians (haversine, fp32); inv/delsph.f90:1

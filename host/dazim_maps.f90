@@ -1,7 +1,7 @@
 ! dazim_maps.f90 -- SurfPhaseMaps_amd: per-period Rayleigh phase-velocity maps and 2-psi anisotropy maps inverted from the data of
 ! the 3-D inversion program, period by period in one system, on one MI355X.
 !
-!   SurfPhaseMaps_amd para.in [weight_c [weight_a]]
+!   SurfPhaseMaps_amd para.in [weight_c [weight_a [uncertainty]]]
 !
 ! Inputs: the unchanged para.in, traveltime data file and MOD of DAzimSurfTomo_amd (the same readers, module dazim_io:
 ! read_para, read_data, read_mod).  Starting maps: MOD's dispersion curves (dazim_dispersion_kernels without kernels), the 3-D
@@ -21,6 +21,14 @@
 !                            the 2-psi azimuthal bias sqrt((sum fdmc)^2 + (sum fdms)^2) / DWS in [0, 1] (dazim_aprod mode 2,
 !                            y = 1), 0 = even azimuthal coverage; both on the unweighted rows of the last iteration's maps
 !   <para>_map.log + stdout  one line per iteration: data, mean / std / RMS of the residual before and after, LSMR istop / itn
+! uncertainty = 1 (default 0: nothing below is computed or written): how well the maps are known, from dazim_map_posterior on the last
+! iteration's [W G; L] (the matrix that iteration's LSMR was given) with para.in's damping: the regulariser read as a Gaussian prior,
+! the data errors as CalDdatSigma's sigma.  These are the statistics of the last linearised step.
+!   period_map_uncertainty.dat  lon lat period, then std_post std_noise rdiag rsum width of c; in iso-mode F also std_post rdiag of a1,
+!                            std_post rdiag of a2, and leak of c (the share of c's averaging kernel that lies in a1, a2); one line
+!                            per inner vertex and period in period_phaseV_map.dat's order
+!   log: per period trace(Rm) / ncell per block, the median std_post of c and (iso-mode F) the median leak of c; the periods that
+!                            could not be factored
 program SurfPhaseMaps_amd
   use iso_c_binding
   use dazim_mod
@@ -47,11 +55,15 @@ program SurfPhaseMaps_amd
   real :: minc, maxc, atol, btol, conlim, anorm, acond, rnorm, arnorm, xnorm, wstats(8), amean, astd, arms
   real :: bias
   type(c_ptr) :: G
+  ! uncertainty = 1
+  integer :: iunc
+  integer(c_int) :: nbad
+  real, allocatable, target :: upost(:, :), utrace(:, :)
 
   write (*, *)
   write (*, *) '                       SurfPhaseMaps'
   write (*, *)
-  if (command_argument_count() < 1) stop 'usage: SurfPhaseMaps_amd para.in [weight_c [weight_a]]'
+  if (command_argument_count() < 1) stop 'usage: SurfPhaseMaps_amd para.in [weight_c [weight_a [uncertainty]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) stop 'unable to open the inputfile'
@@ -64,6 +76,13 @@ program SurfPhaseMaps_amd
   weight_c = p%weightVs; weight_a = p%weightGcs
   call optional_arg(2, weight_c)
   call optional_arg(3, weight_a)
+  iunc = 0
+  call optional_arg(4, iunc)
+  if (iunc /= 0 .and. iunc /= 1) then
+    write (*, '(a,i0)') ' ERROR: uncertainty must be 0 or 1, not ', iunc
+    error stop 'bad argument'
+  end if
+  if (iunc == 1 .and. maxiter < 1) error stop 'uncertainty = 1 needs at least one iteration'
   write (logfile, '(a,a)') trim(inputfile), '_map.log'
   open (66, file=logfile)
   write (66, *)
@@ -121,6 +140,14 @@ program SurfPhaseMaps_amd
     dm = 0
     call dazim_check(dazim_lsmr(dazim_handle, G, cbst, damp, atol, btol, conlim, itnlim, localSize, dm, istop, itn, anorm, acond, &
                                 rnorm, arnorm, xnorm), 'LSMR')
+    if (iunc == 1 .and. iter == maxiter) then     ! on this iteration's [W G; L], before the update and before G is freed
+      allocate (upost(nm, 6), utrace(kmax, nblk))
+      upost = 0
+      call dazim_check(dazim_map_posterior(dazim_handle, G, int(dall, c_int64_t), nx, ny, kmax, merge(0_c_int, 1_c_int, iso_mod), &
+                                           damp, upost(:, 1), upost(:, 2), upost(:, 3), upost(:, 4), c_loc(upost(:, 5)), &
+                                           merge(c_null_ptr, c_loc(upost(:, 6)), iso_mod), 0_c_int, c_null_ptr, c_null_ptr, &
+                                           c_loc(utrace), nbad), 'map posterior')
+    end if
     call dazim_check(dazim_phase_map_update(dazim_handle, nx, ny, kmax, merge(0_c_int, 1_c_int, iso_mod), pv, dm, minc, maxc, &
                                             a1, a2, ustats), 'map update')
     ! residual after: the data rows (weighted by datweight) times the applied update, unweighted again
@@ -168,8 +195,66 @@ program SurfPhaseMaps_amd
     end do
   end do
   close (43)
+  if (iunc == 1) then
+    open (44, file='period_map_uncertainty.dat', status='replace', action='write')
+    do t1 = 1, kmax
+      do j1 = 1, ny - 2
+        do i1 = 1, nx - 2
+          q = (t1 - 1)*ncell + (j1 - 1)*(nx - 2) + i1
+          if (iso_mod) then
+            write (44, '(3f10.4,5es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), upost(q, 1:5)
+          else
+            write (44, '(3f10.4,10es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), upost(q, 1:5), &
+              upost(kmax*ncell + q, 1), upost(kmax*ncell + q, 3), upost(2*kmax*ncell + q, 1), upost(2*kmax*ncell + q, 3), upost(q, 6)
+          end if
+        end do
+      end do
+    end do
+    close (44)
+    do q = 6, 66, 60
+      write (q, '(a)') ' uncertainty: posterior std and resolution of the last linearised step (dazim_map_posterior)'
+      do t1 = 1, kmax
+        if (utrace(t1, 1) /= utrace(t1, 1)) then
+          write (q, '(a,f8.2,a)') ' uncertainty period', tRc(t1), ': not factored'
+        else if (iso_mod) then
+          write (q, '(a,f8.2,a,f9.5,a,es12.4)') ' uncertainty period', tRc(t1), ': trace(Rm)/ncell c', utrace(t1, 1)/ncell, &
+            '  median std_post c', median(upost((t1 - 1)*ncell + 1:t1*ncell, 1))
+        else
+          write (q, '(a,f8.2,a,3f9.5,a,es12.4,a,f8.4)') ' uncertainty period', tRc(t1), ': trace(Rm)/ncell c a1 a2', utrace(t1, :)/ncell, &
+            '  median std_post c', median(upost((t1 - 1)*ncell + 1:t1*ncell, 1)), '  median leak c', &
+            median(upost((t1 - 1)*ncell + 1:t1*ncell, 6))
+        end if
+      end do
+      if (nbad > 0) write (q, '(a,i4)') ' uncertainty: periods not factored', nbad
+    end do
+  end if
   write (*, *) '  Program finishes successfully'
   write (66, *) '  Program finishes successfully'
   close (66)
   call dazim_finalize()
+
+contains
+
+  ! the median of v (the lower of the two middle values for an even count), by a Shell sort of a copy
+  real function median(v)
+    real, intent(in) :: v(:)
+    real, allocatable :: s(:)
+    real :: x
+    integer :: m, gap, i2, j2
+    s = v
+    m = size(s)
+    gap = m/2
+    do while (gap > 0)
+      do i2 = gap + 1, m
+        x = s(i2); j2 = i2
+        do while (j2 > gap)
+          if (s(j2 - gap) <= x) exit
+          s(j2) = s(j2 - gap); j2 = j2 - gap
+        end do
+        s(j2) = x
+      end do
+      gap = gap/2
+    end do
+    median = s((m + 1)/2)
+  end function
 end program

@@ -262,6 +262,43 @@ int dazim_csr_append_laplacian2d(dazim_ctx *ctx, dazim_csr *A, int nx, int ny, i
 int dazim_phase_map_update(dazim_ctx *ctx, int nx, int ny, int kmax, int azim, double *pv, float *dm, float minc, float maxc,
                            float *a1, float *a2, float *stats);
 
+/* dazim_map_posterior: how well the maps are known, per period, block (c, a1, a2) and inner cell, from the matrix dazim_lsmr is given.
+ *   A: the first m_data rows are the weighted data rows (unit variance after dazim_weight_data), the rows after them regularisation
+ *   rows of any sparse form; columns in the map layout blk*kmax*ncell + p*ncell + cell, n = nblk*kmax*ncell (nblk = 3 with azim, else
+ *   1); inside a row the columns ascend strictly (the canonical form of every dazim_csr without repeated triplets).  damp as given to
+ *   dazim_lsmr.  A row touches one period only, so the normal matrix is block diagonal; per period p, with the local index
+ *   a = blk*ncell + cell, n_g = nblk*ncell:
+ *     D = sum_{data rows} r^T r       P = sum_{regularisation rows} l^T l + damp^2 I       A_g = D + P = R R^T       M = R^-1
+ *     C = A_g^-1 = M^T M              Rm = C D = I - C P        (the resolution matrix of the regularised solve)
+ *   std_post, std_noise, rdiag, rsum, width, leak: [nblk][kmax][ny-2][nx-2] fp32, the layout of dm (host or device):
+ *     std_post  = sqrt(C_aa)           the posterior std, the regulariser read as a Gaussian prior of precision P
+ *     std_noise = sqrt((Rm C)_aa)      unit data errors carried through the estimator alone, <= std_post
+ *     rdiag     = Rm_aa                rsum = sum_c Rm_ac
+ *     width     (nullable) = sqrt(sum_c Rm_ac^2 ((i_c - i_a)^2 + (j_c - j_a)^2) / sum_c Rm_ac^2) over the unknown's own block, in cells
+ *               (cell = j*(nx-2) + i); 0 if the denominator is 0
+ *     leak      (nullable; NULL when azim = 0) = sum_{c in the other two blocks} Rm_ac^2 / sum_{all c} Rm_ac^2: the share of the
+ *               unknown's averaging kernel that lies in other kinds of unknown (the c <-> 2-psi trade-off); 0 if the denominator is 0
+ *   trace [nblk][kmax] (nullable) = sum_a Rm_aa per block and period.
+ *   rows [kmax][nsel][n_g] (nullable) = row sel[s] of Rm for every period (point-spread functions); sel [nsel] local indices.
+ *   Arithmetic, fp64 throughout, every sum in a fixed order, no floating-point atomics, each value rounded to fp32 once:
+ *     A_g(a,c) = sum over the period's rows in ascending row order of r_a r_c, then damp^2 on the diagonal;
+ *     blocked right-looking Cholesky in place (panel width stat "map_post.nb"): an element's subtractions in ascending column order;
+ *     M by block columns from the last: M21 = -(M22 R21) M11, the inner sums in ascending index;
+ *     C_ac = sum_{i >= max(a, c)} M_ia M_ic in ascending i (the order of dazim_column_resolution);
+ *     Rm_a. = e_a, then for every regularisation row l in ascending order t = sum_e C_ae l_e (ascending e), Rm_ac -= t l_c, then
+ *     Rm_ac -= damp^2 C_ac; (Rm C)_aa = sum_c Rm_ac C_ac; a sum along a row: 256 strided partial sums, combined in a fixed tree.
+ *   Option map_post.mfma: 1 (the default) forms the Cholesky trailing update and C with v_mfma_f64_16x16x4_f64, 0 with plain tiles.
+ *   Host and device arguments give the same bits, and so do two calls.  A period whose factorisation meets a pivot that is not
+ *   finite and > 0 (no regulariser and a cell without rays, non-finite entries) gets NaN in every output and is counted in n_failed
+ *   (host, nullable); the other periods are unaffected.  Refused (DAZIM_E_BAD_ARG, nothing written): m_data outside 0..m, n not
+ *   nblk*kmax*ncell, a missing std_post, std_noise, rdiag or rsum, leak with azim = 0, sel entries outside 0..n_g-1, rows without
+ *   sel, a negative or non-finite damp, a row whose columns lie in two periods or do not ascend strictly (found on the device), n_g
+ *   beyond what the row pass holds in LDS (about 16 000).  Workspace: two n_g x n_g fp64 matrices from the context's scratch, taken
+ *   before the first launch.  Stats: "map_posterior" and its parts "map_post.gram", ".factor", ".inverse", ".c", ".rows" (seconds). */
+int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int nx, int ny, int kmax, int azim, float damp,
+                        float *std_post, float *std_noise, float *rdiag, float *rsum, float *width, float *leak, int nsel,
+                        const int *sel, float *rows, float *trace, int *n_failed);
+
 /* ---- from the maps to a depth model, cell by cell (the second step of the two-step method) ------------------
  * dazim_vs_kernels: skern [nz][kmax][nx*ny] fp64 = sen_vp*coe_a + sen_rho*coe_rho + sen_vs at vel (the Brocher derivatives of the
  *   cell's velocity, inv/CalSurfG.f90:1339-1364): the table the 3-D rows of dazim_rays_build_G multiply, bit for bit (an iso row
