@@ -457,6 +457,41 @@ class Context:
         out["n_failed"] = nf.value
         return out
 
+    def model_posterior(self, A, m_data, nx, ny, nz, joint, damp, depz=None, sel=None, width=True):
+        """posterior std and resolution of the direct 3-D inversion (dazim_model_posterior) from the matrix lsmr is given in an outer
+        iteration: A a SparseMatrix whose first m_data rows are the weighted data rows, damp lsmr's damping, depz[nz-1] the knots'
+        depths (for width_z), sel indices blk*maxvp + k*ncell + cell whose rows of Rm are wanted (numpy, or torch-cuda for torch-cuda
+        outputs).  Returns a dict: std_post, std_noise, rdiag, rsum, width_h (None when off), width_z (None when off or without
+        depz), leak (None unless joint), each [nblk][nz-1][ny-2][nx-2]; trace [nblk][nz-1]; rows [nsel][n] (None without sel);
+        n_failed."""
+        nblk = 3 if joint else 1
+        n = nblk * (nx - 2) * (ny - 2) * (nz - 1)
+        if sel is not None and _is_torch(sel):
+            import torch
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=sel.device)
+        else:
+            new = lambda *shape: np.zeros(shape, np.float32)
+            sel = None if sel is None else np.ascontiguousarray(sel, np.int32)
+        if depz is not None and not _is_torch(depz):
+            depz = np.ascontiguousarray(depz, np.float32)
+            assert depz.size == nz - 1
+        nsel = 0 if sel is None else int(sel.shape[0])
+        shape = (nblk, nz - 1, ny - 2, nx - 2)
+        out = {k: new(*shape) for k in ("std_post", "std_noise", "rdiag", "rsum")}
+        out["width_h"] = new(*shape) if width else None
+        out["width_z"] = new(*shape) if width and depz is not None else None
+        out["leak"] = new(*shape) if joint else None
+        out["rows"] = new(nsel, n) if nsel else None
+        out["trace"] = new(nblk, nz - 1)
+        nf = C.c_int(0)
+        f32 = lambda k: _ptr(out[k], np.float32)
+        self._check(self.lib.dazim_model_posterior(self._h, A._h, C.c_int64(int(m_data)), nx, ny, nz, int(bool(joint)), C.c_float(damp),
+                                                   _ptr(depz, np.float32) if out["width_z"] is not None else None, f32("std_post"),
+                                                   f32("std_noise"), f32("rdiag"), f32("rsum"), f32("width_h"), f32("width_z"),
+                                                   f32("leak"), nsel, _ptr(sel, np.int32), f32("rows"), f32("trace"), C.byref(nf)))
+        out["n_failed"] = nf.value
+        return out
+
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
                   ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None, prior=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],

@@ -1,0 +1,296 @@
+// model_post.hip -- dazim_model_posterior: posterior std and resolution of the direct 3-D inversion from the
+// matrix LSMR is given in an outer iteration, [W G; L], and the damping.  One dense block of n = nblk (nx-2)(ny-2)(nz-1) unknowns:
+//   gram     A_n = sum_rows r^T r + damp^2 I, one wavefront per unknown a, driven from the transpose: only the rows that hold a
+//   factor, inverse, c   dz_mp_dense (map_post_dense.hip), the kernels of dazim_map_posterior
+//   rows     Rm = I - C P entry by entry as a gather over the regularisation entries of column c in the transpose; no row of Rm is
+//            stored (but those asked for), LDS holds the partial sums only
+// fp64, every sum in a fixed order, no floating-point atomics; the dependencies between the steps are launch order on the context's
+// stream.  The two n x n matrices are allocated for the call and released before it returns.
+#include <algorithm>
+#include <cmath>
+
+#include "map_post_internal.h"
+
+namespace {
+
+constexpr int MO_WPC = 8;   // row-pass workgroups per CU; each keeps its own vector t (one fp64 per regularisation row) in memory
+constexpr int MO_UN = 4;    // row entries per lane in flight in the Gram pass
+
+// bad = 1 when a row's columns do not ascend strictly or leave 0..n-1
+__global__ __launch_bounds__(MP_TB) void k_mo_check(int64_t m, int n, const int64_t *rowptr, const int *col, int *bad) {
+  const int64_t r = (int64_t)blockIdx.x * MP_TB + threadIdx.x;
+  if (r >= m) return;
+  int prev = -1;
+  bool b = false;
+  for (int64_t q = rowptr[r]; q < rowptr[r + 1]; q++) {
+    const int c = col[q];
+    b = b || c <= prev || c >= n;
+    prev = c;
+  }
+  if (b) atomicOr(bad, 1);
+}
+
+// regstart[c]: the first entry of column c in the transpose that belongs to a regularisation row (row >= m_data); a column's rows ascend
+__global__ __launch_bounds__(MP_TB) void k_mo_regstart(int n, int64_t m_data, const int64_t *colptr, const int *row, int64_t *regstart) {
+  const int c = blockIdx.x * MP_TB + threadIdx.x;
+  if (c >= n) return;
+  int64_t lo = colptr[c], hi = colptr[c + 1];
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if ((int64_t)row[mid] < m_data) lo = mid + 1;
+    else hi = mid;
+  }
+  regstart[c] = lo;
+}
+
+// row a of A_n (the lower triangle is what the factorisation reads): over the entries (r, v_a) of column a in the transpose, rows
+// ascending, A_n(a, c) += v_a r_c for the entries of row r with c <= a; then damp^2 on the diagonal.  One wavefront per unknown.  The
+// columns of a row are distinct, so MO_UN x 64 of its entries are in flight at a time; the barrier between two rows orders the
+// read-modify-writes of an element that two rows share (it may sit in different lanes).
+__global__ __launch_bounds__(64) void k_mo_gram(int n, const int64_t *colptr, const int *row, const float *tval, const int64_t *rowptr,
+                                                const int *col, const float *val, double d2, double *A) {
+  const int a = blockIdx.x, t = threadIdx.x;
+  double *Aa = A + (size_t)a * n;
+  for (int c = t; c < n; c += 64) Aa[c] = 0.0;
+  __syncthreads();
+  const int64_t pe = colptr[a + 1];
+  for (int64_t p = colptr[a]; p < pe; p++) {
+    const int r = row[p];
+    const double v = (double)tval[p];
+    const int64_t b = rowptr[r], e = rowptr[r + 1];
+    for (int64_t q0 = b; q0 < e; q0 += 64 * MO_UN) {
+      if (col[q0] > a) break;                       // (ascending: nothing at or behind q0 is <= a)
+      int cc[MO_UN];
+      double pr[MO_UN], old[MO_UN];
+#pragma unroll
+      for (int u = 0; u < MO_UN; u++) {
+        const int64_t q = q0 + u * 64 + t;
+        cc[u] = q < e ? col[q] : n;
+        if (cc[u] > a) cc[u] = -1;
+        pr[u] = cc[u] >= 0 ? v * (double)val[q] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < MO_UN; u++) old[u] = cc[u] >= 0 ? Aa[cc[u]] : 0.0;
+#pragma unroll
+      for (int u = 0; u < MO_UN; u++)
+        if (cc[u] >= 0) Aa[cc[u]] = old[u] + pr[u];
+    }
+    __syncthreads();
+  }
+  if (t == 0) Aa[a] += d2;
+}
+
+struct MoOut {
+  float *std_post, *std_noise, *rdiag, *rsum, *width_h, *width_z, *leak, *rows;
+};
+
+// Workgroup g takes the unknowns a = g, g + gridDim.x, ...  For one a: t_l = sum_e C_ae l_e for every regularisation row l (one
+// thread per row, ascending e; row a of C is contiguous) into the workgroup's vector tb in memory, then thread t forms
+// Rm_ac = delta_ac - sum_l t_l l_c - damp^2 C_ac for c = t, t + MP_TB, ... over column c's regularisation entries in the transpose
+// (ascending rows) and adds it to its partial sums; nothing is scattered.
+__global__ __launch_bounds__(MP_TB) void k_mo_rows(int n, int ncell, int nvx, int maxvp, int64_t m_data, int64_t mreg, const int64_t *rowptr,
+                                                   const int *col, const float *val, const int64_t *colptr, const int64_t *regstart,
+                                                   const int *row, const float *tval, double d2, const double *Cm, const int *flag,
+                                                   const float *depz, MoOut out, int nsel, const int *sel, double *tbuf, double *rd64) {
+  __shared__ double red[MP_TB / 64];
+  __shared__ double rdg;
+  const int t = threadIdx.x;
+  double *tb = tbuf + (size_t)blockIdx.x * (size_t)(mreg > 0 ? mreg : 1);
+  const bool failed = *flag != 0;
+  for (int a = blockIdx.x; a < n; a += gridDim.x) {
+    int nmatch = 0;
+    if (out.rows)
+      for (int s = 0; s < nsel; s++) nmatch += sel[s] == a;
+    if (failed) {
+      const float v = nanf("");
+      if (t == 0) {
+        out.std_post[a] = out.std_noise[a] = out.rdiag[a] = out.rsum[a] = v;
+        if (out.width_h) out.width_h[a] = v;
+        if (out.width_z) out.width_z[a] = v;
+        if (out.leak) out.leak[a] = v;
+        rd64[a] = (double)v;
+      }
+      if (nmatch)
+        for (int s = 0; s < nsel; s++)
+          if (sel[s] == a)
+            for (int c = t; c < n; c += MP_TB) out.rows[(size_t)s * n + c] = v;
+      continue;
+    }
+    const double *Ca = Cm + (size_t)a * n;
+    for (int64_t l = t; l < mreg; l += MP_TB) {
+      double s = 0.0;
+      for (int64_t q = rowptr[m_data + l]; q < rowptr[m_data + l + 1]; q++) s += Ca[col[q]] * (double)val[q];
+      tb[l] = s;
+    }
+    __syncthreads();
+    const int blk = a / maxvp, ka = (a % maxvp) / ncell, cella = a % ncell, ia = cella % nvx, ja = cella / nvx;
+    const double za = depz ? (double)depz[ka] : 0.0;
+    double rs = 0.0, nv = 0.0, own = 0.0, oth = 0.0, numh = 0.0, numz = 0.0;
+    for (int c = t; c < n; c += MP_TB) {
+      double r = c == a ? 1.0 : 0.0;
+      const int64_t qe = colptr[c + 1];
+      for (int64_t q = regstart[c]; q < qe; q++) r -= tb[(int64_t)row[q] - m_data] * (double)tval[q];
+      const double cac = Ca[c];
+      r -= d2 * cac;
+      rs += r;
+      nv += r * cac;
+      if (c / maxvp == blk) {
+        const int kc = (c % maxvp) / ncell, cc = c % ncell;
+        const double di = (double)(cc % nvx - ia), dj = (double)(cc / nvx - ja);
+        own += r * r;
+        numh += r * r * (di * di + dj * dj);
+        if (depz) {
+          const double dz = (double)depz[kc] - za;
+          numz += r * r * (dz * dz);
+        }
+      } else {
+        oth += r * r;
+      }
+      if (c == a) rdg = r;
+      if (nmatch)
+        for (int s = 0; s < nsel; s++)
+          if (sel[s] == a) out.rows[(size_t)s * n + c] = (float)r;
+    }
+    rs = mp_block_sum(rs, red);
+    nv = mp_block_sum(nv, red);
+    own = mp_block_sum(own, red);
+    oth = mp_block_sum(oth, red);
+    numh = mp_block_sum(numh, red);
+    numz = mp_block_sum(numz, red);
+    if (t == 0) {
+      out.std_post[a] = (float)sqrt(Ca[a]);
+      out.std_noise[a] = (float)sqrt(fmax(nv, 0.0));
+      out.rdiag[a] = (float)rdg;
+      out.rsum[a] = (float)rs;
+      if (out.width_h) out.width_h[a] = own > 0.0 ? (float)sqrt(numh / own) : 0.0f;
+      if (out.width_z) out.width_z[a] = own > 0.0 ? (float)sqrt(numz / own) : 0.0f;
+      if (out.leak) out.leak[a] = own + oth > 0.0 ? (float)(oth / (own + oth)) : 0.0f;
+      rd64[a] = rdg;
+    }
+    __syncthreads();   // (tb and rdg belong to the next unknown from here on)
+  }
+}
+
+// trace[blk][k] = sum of Rm_aa over the cells of block blk and knot k (workgroup blk * nlay + k)
+__global__ __launch_bounds__(MP_TB) void k_mo_trace(int ncell, const double *rd64, float *trace) {
+  __shared__ double red[MP_TB / 64];
+  double s = 0.0;
+  for (int c = threadIdx.x; c < ncell; c += MP_TB) s += rd64[(size_t)blockIdx.x * ncell + c];
+  s = mp_block_sum(s, red);
+  if (threadIdx.x == 0) trace[blockIdx.x] = (float)s;
+}
+
+struct MoBig {   // the call's own allocations: released on every way out
+  void *p[3] = {nullptr, nullptr, nullptr};
+  ~MoBig() {
+    for (void *q : p)
+      if (q) (void)hipFree(q);
+  }
+};
+
+}  // namespace
+
+extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int nx, int ny, int nz, int joint, float damp,
+                                     const float *depz_u, float *std_post_u, float *std_noise_u, float *rdiag_u, float *rsum_u,
+                                     float *width_h_u, float *width_z_u, float *leak_u, int nsel, const int *sel_u, float *rows_u,
+                                     float *trace_u, int *n_failed) {
+  if (!ctx || !A || nx < 3 || ny < 3 || nz < 2 || !std_post_u || !std_noise_u || !rdiag_u || !rsum_u)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_model_posterior");
+  if (m_data < 0 || m_data > A->m)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: m_data %lld outside 0..%lld", (long long)m_data, (long long)A->m);
+  const int nblk = joint ? 3 : 1, nlay = nz - 1;
+  const int64_t ncell64 = (int64_t)(nx - 2) * (ny - 2), n64 = nblk * ncell64 * nlay;
+  if (A->n != n64 || n64 > (int64_t)1 << 30)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: n %lld is not nblk * (nx-2)(ny-2)(nz-1) = %lld", (long long)A->n, (long long)n64);
+  if (!joint && leak_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: leak without joint");
+  if ((width_z_u != nullptr) != (depz_u != nullptr)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: width_z and depz go together");
+  if (!(damp >= 0.0f) || !std::isfinite(damp)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: damp negative or not finite");
+  if (nsel < 0 || (nsel > 0 && !sel_u)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: nsel without sel");
+  if (rows_u && nsel < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: rows without sel");
+  DZ_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = dz_fmm_finish(ctx)) || (rc = dz_join_aux(ctx))) return rc;
+  const int ncell = (int)ncell64, n = (int)n64, maxvp = ncell * nlay, nvx = nx - 2;
+  const int64_t m = A->m, mreg = m - m_data;
+  // ---- the workspace: refused before the first launch when the card cannot hold it ----
+  const int ngrid = (int)std::min<int64_t>(n, (int64_t)MO_WPC * ctx->num_cu);
+  const size_t bA = (size_t)n * n * 8, bC = (size_t)n * (n > MP_NB ? n : MP_NB) * 8, bT = (size_t)ngrid * (size_t)(mreg > 0 ? mreg : 1) * 8;
+  const size_t bTr = A->colptr ? 0 : (size_t)(n + 1) * 8 + (size_t)(A->nnz > 0 ? A->nnz : 1) * 12 * 3;   // (the transpose and its sort)
+  const size_t need = bA + bC + bT + bTr + ((size_t)64 << 20);
+  size_t fre = 0, tot = 0;
+  DZ_HIP(hipMemGetInfo(&fre, &tot));
+  if (need > fre) {
+    (void)dz_trim_caches(ctx);
+    DZ_HIP(hipMemGetInfo(&fre, &tot));
+  }
+  if (need > fre)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: %lld unknowns need %.1f GiB of device memory, %.1f GiB are free", (long long)n64,
+                   (double)need / 1073741824.0, (double)fre / 1073741824.0);
+  if (!A->colptr && (rc = dz_build_transpose(ctx, const_cast<dazim_csr *>(A)))) return rc;
+  MoBig big;
+  DZ_HIP(dz_malloc_retry(ctx, &big.p[0], bA));
+  DZ_HIP(dz_malloc_retry(ctx, &big.p[1], bC));
+  DZ_HIP(dz_malloc_retry(ctx, &big.p[2], bT));
+  double *Ad = (double *)big.p[0], *Cd = (double *)big.p[1], *tbuf = (double *)big.p[2], *rd64;
+  int64_t *regstart;
+  int *flags;
+  if ((rc = dz_scratch(ctx, "mopost.rd", (size_t)n, &rd64)) || (rc = dz_scratch(ctx, "mopost.reg", (size_t)n, &regstart)) ||
+      (rc = dz_scratch(ctx, "mopost.flags", (size_t)2, &flags)))
+    return rc;
+  DzBuf<float> sp, sn, rd, rs, wh, wz, lk, rw, tr, dz;
+  DzBuf<int> sel;
+  const size_t no = (size_t)n;
+  if ((rc = sel.init(ctx, sel_u, (size_t)nsel, true, false)) || (rc = dz.init(ctx, depz_u, depz_u ? (size_t)nlay : 0, true, false)) ||
+      (rc = sp.init(ctx, std_post_u, no, false, true)) || (rc = sn.init(ctx, std_noise_u, no, false, true)) ||
+      (rc = rd.init(ctx, rdiag_u, no, false, true)) || (rc = rs.init(ctx, rsum_u, no, false, true)) ||
+      (rc = wh.init(ctx, width_h_u, width_h_u ? no : 0, false, true)) || (rc = wz.init(ctx, width_z_u, width_z_u ? no : 0, false, true)) ||
+      (rc = lk.init(ctx, leak_u, leak_u ? no : 0, false, true)) || (rc = rw.init(ctx, rows_u, rows_u ? (size_t)nsel * n : 0, false, true)) ||
+      (rc = tr.init(ctx, trace_u, trace_u ? (size_t)nblk * nlay : 0, false, true)))
+    return rc;
+  if (nsel > 0 && (rc = dz_check_range(ctx, sel.dev, nsel, 0, n - 1, "dazim_model_posterior: sel"))) return rc;
+  int hflag[2] = {0, 0};
+  DZ_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), ctx->stream));
+  if (m > 0) hipLaunchKernelGGL(k_mo_check, dim3((unsigned)((m + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, m, n, A->rowptr, A->col, flags + 1);
+  DZ_HIP(hipGetLastError());
+  DZ_HIP(hipMemcpyAsync(hflag, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (hflag[1]) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: a row's columns do not ascend strictly inside 0..n-1");
+  const bool mfma = dz_opt(ctx, "map_post.mfma", 1) != 0;
+  const double d2 = (double)damp * (double)damp;
+  const MoOut out = {sp.dev, sn.dev, rd.dev, rs.dev, wh.dev, wz.dev, lk.dev, rw.dev};
+  double sec[5] = {0, 0, 0, 0, 0};
+  {
+    DzTimer t(ctx, "model_post.lap");
+    hipLaunchKernelGGL(k_mo_regstart, dim3((unsigned)((n + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, n, m_data, A->colptr, A->row, regstart);
+    hipLaunchKernelGGL(k_mo_gram, dim3((unsigned)n), dim3(64), 0, ctx->stream, n, A->colptr, A->row, A->tval, A->rowptr, A->col, A->val, d2, Ad);
+    DZ_HIP(hipGetLastError());
+    t.stop();
+    sec[0] = ctx->ksec["model_post.lap"];
+  }
+  if ((rc = dz_mp_dense(ctx, n, Ad, Cd, flags, mfma, "model_post.lap", sec + 1))) return rc;
+  {
+    DzTimer t(ctx, "model_post.lap");
+    hipLaunchKernelGGL(k_mo_rows, dim3((unsigned)ngrid), dim3(MP_TB), 0, ctx->stream, n, ncell, nvx, maxvp, m_data, mreg, A->rowptr, A->col, A->val,
+                       A->colptr, regstart, A->row, A->tval, d2, Cd, flags, dz.dev, out, nsel, sel.dev, tbuf, rd64);
+    if (tr.dev) hipLaunchKernelGGL(k_mo_trace, dim3((unsigned)(nblk * nlay)), dim3(MP_TB), 0, ctx->stream, ncell, rd64, tr.dev);
+    DZ_HIP(hipGetLastError());
+    t.stop();
+    sec[4] = ctx->ksec["model_post.lap"];
+  }
+  DZ_HIP(hipMemcpyAsync(hflag, flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = sp.finish()) || (rc = sn.finish()) || (rc = rd.finish()) || (rc = rs.finish()) || (rc = wh.finish()) || (rc = wz.finish()) ||
+      (rc = lk.finish()) || (rc = rw.finish()) || (rc = tr.finish()))
+    return rc;
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (n_failed) *n_failed = hflag[0] != 0;
+  ctx->ksec.erase("model_post.lap");
+  static const char *names[5] = {"model_post.gram", "model_post.factor", "model_post.inverse", "model_post.c", "model_post.rows"};
+  double total = 0.0;
+  for (int i = 0; i < 5; i++) {
+    ctx->ksec[names[i]] = sec[i];
+    total += sec[i];
+  }
+  ctx->ksec["model_posterior"] = total;
+  ctx->ksec["model_post.n"] = (double)n;
+  return 0;
+}

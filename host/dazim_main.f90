@@ -12,6 +12,18 @@
 !            (dazim_aprod on the resident un-thresholded rows).  G never leaves HBM; only O(m) + O(n) vectors cross PCIe.
 !   host   : parsing, the O(n) copy of the regularisation stencil for the ||Lm|| diagnostics, formatted output.
 ! Joint (iso-mode F) inversions take the TI depth kernels Lsen_Gsc from ti_hip.f90 (the device kernels of ti.hip).
+!
+! `DAzimSurfTomo_amd para.in [uncertainty]`, uncertainty = 1 (default 0: nothing below is computed or written, and the program makes the
+! calls and writes the bytes it does without the argument): how well the model is known, from dazim_model_posterior on the last outer
+! iteration's [W G; L] (the matrix that iteration's LSMR was given, m_data = dall) with para.in's damping: the Tikhonov rows read as a
+! Gaussian prior, the data errors as CalDdatSigma's sigma.  This is the exact regularised solution of the last linearised step; LSMR
+! stopped at itnlim is an approximation to that solution, so the file describes what the step aims at, not LSMR's iterate.  One rank
+! only: with DAZIM_NGPU > 1 the matrix is row-sharded and the program stops before the first iteration.
+!   model_uncertainty.dat  lon lat depth, then std_post std_noise rdiag rsum width_h width_z of Vs (width_h in cells, width_z in km); in
+!                          iso-mode F also std_post rdiag of Gc, std_post rdiag of Gs, and leak of Vs (the share of Vs's averaging
+!                          kernel that lies in Gc, Gs); one line per inner cell and inverted knot in Vs_resolution_2step.dat's order
+!   log + stdout: per knot trace(Rm) / ncell per block, the median std_post of Vs and (iso-mode F) the median leak of Vs; "not factored"
+!                          when the normal matrix has no Cholesky factor
 program DAzimSurfTomo_amd
   use iso_c_binding
   use dazim_mod
@@ -49,6 +61,11 @@ program DAzimSurfTomo_amd
   integer :: nfield_all, f0, f1, fidx, d0, dloc, sl, treg0, treg1, nregblk
   real(8) :: tph(9) = 0                      ! wall seconds per phase, printed when DAZIM_TIMING is set (tools/run_test4_program.sh)
   character(len=8) :: timing_env
+  ! uncertainty = 1
+  integer :: iunc, ngpu_env, nblk_u, ncell_u, q_u
+  integer(c_int) :: nbad
+  character(len=32) :: ngpu_val
+  real, allocatable, target :: upost(:, :), utrace(:, :), udepz(:)
 
   call system_clock(c0, crate)
   call system_clock(tk0, tkrate)
@@ -65,6 +82,17 @@ program DAzimSurfTomo_amd
   end if
   inquire (file=inputfile, exist=ex)
   if (.not. ex) stop 'unable to open the inputfile'
+  iunc = 0
+  if (command_argument_count() >= 2) call optional_arg(2, iunc)
+  if (iunc == 1) then                         ! (before any rank is started)
+    ngpu_env = 1
+    call get_environment_variable('DAZIM_NGPU', ngpu_val)
+    if (len_trim(ngpu_val) > 0) read (ngpu_val, *) ngpu_env
+    if (ngpu_env > 1) then
+      write (*, '(a)') ' ERROR: uncertainty = 1 needs the whole matrix on one GPU; with DAZIM_NGPU > 1 its rows are sharded over the ranks'
+      error stop 'uncertainty = 1 with more than one rank'
+    end if
+  end if
 
   ! ---- para.in, inv/Main_Jt.f90:158-214 -------------------------------------------------------------
   call read_para(inputfile, p)
@@ -374,6 +402,16 @@ program DAzimSurfTomo_amd
     end if
     write (66, '(a)') ' '
     write (6, '(a)') '  '
+    if (iunc == 1 .and. iter == maxiter) then   ! on this iteration's [W G; L], before it is freed
+      nblk_u = merge(1, 3, iso_mod)
+      allocate (upost(nblk_u*maxvp, 7), utrace(nz - 1, nblk_u), udepz(nz - 1))
+      upost = 0; utrace = 0
+      udepz = depz(1:nz - 1)
+      call dazim_check(dazim_model_posterior(dazim_handle, G, int(dall, c_int64_t), nx, ny, nz, merge(0_c_int, 1_c_int, iso_mod), damp, &
+                                             c_loc(udepz), upost(:, 1), upost(:, 2), upost(:, 3), upost(:, 4), c_loc(upost(:, 5)), &
+                                             c_loc(upost(:, 6)), merge(c_null_ptr, c_loc(upost(:, 7)), iso_mod), 0_c_int, c_null_ptr, &
+                                             c_null_ptr, c_loc(utrace), nbad), 'model posterior')
+    end if
     call dazim_check(dazim_csr_free(dazim_handle, G), 'free G')
     call dazim_check(dazim_csr_free(dazim_handle, Gd), 'free Gd')
     call tick(9)                             ! output files of the iteration
@@ -386,6 +424,7 @@ program DAzimSurfTomo_amd
   call write_phase_map('phaseV_FWD.dat', p, tRcV)
   write (*, '(a)') '  Begin forward calculate period azimuthal A1, A2.'
   call write_period_azimuthal('period_Azm_tomo.inv', p, Lsen_Gsc, gcf, gsf, tRcV)
+  if (iunc == 1 .and. allocated(upost)) call write_uncertainty()
   write (66, *) '  -----------------------------------------------------------'
   write (*, *) '  Program finishes successfully'
   write (66, *) '  Program finishes successfully'
@@ -412,6 +451,66 @@ contains
     tph(i) = tph(i) + real(tk1 - tk0, 8)/real(tkrate, 8)
     tk0 = tk1
   end subroutine
+
+  ! model_uncertainty.dat and the log's lines from dazim_model_posterior's arrays (upost: std_post, std_noise, rdiag, rsum, width_h,
+  ! width_z, leak per unknown blk*maxvp + (k-1)*ncell + (j-1)*(nx-2) + i; utrace per knot and block)
+  subroutine write_uncertainty()
+    integer :: k1, j1, i1, u
+    ncell_u = (nx - 2)*(ny - 2)
+    open (44, file='model_uncertainty.dat', status='replace', action='write')
+    do k1 = 1, nz - 1
+      do j1 = 1, ny - 2
+        do i1 = 1, nx - 2
+          q_u = (k1 - 1)*ncell_u + (j1 - 1)*(nx - 2) + i1
+          if (iso_mod) then
+            write (44, '(3f10.4,6es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1), upost(q_u, 1:6)
+          else
+            write (44, '(3f10.4,11es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1), upost(q_u, 1:6), &
+              upost(maxvp + q_u, 1), upost(maxvp + q_u, 3), upost(2*maxvp + q_u, 1), upost(2*maxvp + q_u, 3), upost(q_u, 7)
+          end if
+        end do
+      end do
+    end do
+    close (44)
+    do u = 6, 66, 60
+      write (u, '(a)') ' uncertainty: posterior std and resolution of the last linearised step (dazim_model_posterior)'
+      do k1 = 1, nz - 1
+        if (nbad > 0) then
+          write (u, '(a,f8.2,a)') ' uncertainty depth', depz(k1), ': not factored'
+        else if (iso_mod) then
+          write (u, '(a,f8.2,a,f9.5,a,es12.4)') ' uncertainty depth', depz(k1), ': trace(Rm)/ncell Vs', utrace(k1, 1)/ncell_u, &
+            '  median std_post Vs', median(upost((k1 - 1)*ncell_u + 1:k1*ncell_u, 1))
+        else
+          write (u, '(a,f8.2,a,3f9.5,a,es12.4,a,f8.4)') ' uncertainty depth', depz(k1), ': trace(Rm)/ncell Vs Gc Gs', &
+            utrace(k1, :)/ncell_u, '  median std_post Vs', median(upost((k1 - 1)*ncell_u + 1:k1*ncell_u, 1)), '  median leak Vs', &
+            median(upost((k1 - 1)*ncell_u + 1:k1*ncell_u, 7))
+        end if
+      end do
+    end do
+  end subroutine
+
+  ! the median of v (the lower of the two middle values for an even count), by a Shell sort of a copy
+  real function median(v)
+    real, intent(in) :: v(:)
+    real, allocatable :: s(:)
+    real :: x
+    integer :: mm, gap, i2, j2
+    s = v
+    mm = size(s)
+    gap = mm/2
+    do while (gap > 0)
+      do i2 = gap + 1, mm
+        x = s(i2); j2 = i2
+        do while (j2 > gap)
+          if (s(j2 - gap) <= x) exit
+          s(j2) = s(j2 - gap); j2 = j2 - gap
+        end do
+        s(j2) = x
+      end do
+      gap = gap/2
+    end do
+    median = s((mm + 1)/2)
+  end function
 
   ! scaled 2-norm like the reference's dnrm2 (inv/lsmrblas.f90:247)
   real function nrm2(nn, x)

@@ -33,7 +33,7 @@ module dazim_mod
             dazim_shard_fields, dazim_shard_rows, dazim_allsum
   ! the per-period map inversion (host/dazim_maps.f90)
   public :: dazim_dispersion_kernels, dazim_rays_build_G_maps, dazim_csr_append_laplacian2d, dazim_phase_map_update, &
-            dazim_assemble_G_maps, dazim_map_posterior
+            dazim_assemble_G_maps, dazim_map_posterior, dazim_model_posterior
   ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
   public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq, dazim_column_resolution
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
@@ -372,6 +372,17 @@ module dazim_mod
       type(c_ptr), value :: ctx, A, width, leak, sel, rows, trace
       integer(c_int64_t), value :: m_data
       integer(c_int), value :: nx, ny, kmax, azim, nsel
+      real(c_float), value :: damp
+      real(c_float) :: std_post(*), std_noise(*), rdiag(*), rsum(*)
+      integer(c_int) :: n_failed
+    end function
+    ! depz, width_h, width_z, leak, sel, rows, trace: c_loc of an array in the C layout of include/dazim.h, or c_null_ptr
+    integer(c_int) function dazim_model_posterior(ctx, A, m_data, nx, ny, nz, joint, damp, depz, std_post, std_noise, rdiag, rsum, &
+        width_h, width_z, leak, nsel, sel, rows, trace, n_failed) bind(C, name="dazim_model_posterior")
+      import
+      type(c_ptr), value :: ctx, A, depz, width_h, width_z, leak, sel, rows, trace
+      integer(c_int64_t), value :: m_data
+      integer(c_int), value :: nx, ny, nz, joint, nsel
       real(c_float), value :: damp
       real(c_float) :: std_post(*), std_noise(*), rdiag(*), rsum(*)
       integer(c_int) :: n_failed

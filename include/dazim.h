@@ -299,6 +299,42 @@ int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int 
                         float *std_post, float *std_noise, float *rdiag, float *rsum, float *width, float *leak, int nsel,
                         const int *sel, float *rows, float *trace, int *n_failed);
 
+/* dazim_model_posterior: how well the model of the direct 3-D inversion is known, per block (dVs, Gc, Gs), knot and inner cell, from the
+ * matrix dazim_lsmr is given in an outer iteration.  The exact regularised solution of that linearised step is
+ * what it describes; LSMR stopped at itnlim approximates that solution.
+ *   A: the first m_data rows are the weighted data rows (unit variance after dazim_weight_data), the rows after them regularisation
+ *   rows of any sparse form (dazim_csr_append_tikhonov's or others); columns in the 3-D layout of dazim_rays_build_G[_joint],
+ *   a = blk*maxvp + k*ncell + cell, ncell = (nx-2)(ny-2), maxvp = ncell*(nz-1), n = nblk*maxvp (nblk = 3 with joint, else 1); inside
+ *   a row the columns ascend strictly.  damp as given to dazim_lsmr.  One dense block:
+ *     D = sum_{data rows} r^T r       P = sum_{regularisation rows} l^T l + damp^2 I       A_n = D + P = R R^T       M = R^-1
+ *     C = A_n^-1 = M^T M              Rm = C D = I - C P
+ *   std_post, std_noise, rdiag, rsum, width_h, width_z, leak: [nblk][nz-1][ny-2][nx-2] fp32, the layout of dv in dazim_model_update
+ *   (host or device):
+ *     std_post, std_noise, rdiag, rsum   as dazim_map_posterior defines them
+ *     width_h   (nullable) = sqrt(sum_c Rm_ac^2 ((i_c - i_a)^2 + (j_c - j_a)^2) / sum_c Rm_ac^2) over the unknown's own block, all
+ *               knots of it, in cells; 0 if the denominator is 0
+ *     width_z   (nullable; given together with depz [nz-1], the knots' depths, or both NULL) = sqrt(sum_c Rm_ac^2 (z_c - z_a)^2 /
+ *               sum_c Rm_ac^2) over the same entries, in depz's unit; 0 if the denominator is 0
+ *     leak      (nullable; NULL unless joint) = the share of sum_c Rm_ac^2 that lies in the other two blocks; 0 if the sum is 0
+ *   trace [nblk][nz-1] (nullable) = sum of Rm_aa per block and knot.
+ *   rows [nsel][n] (nullable) = row sel[s] of Rm, the point-spread function of unknown sel[s] (what a spike test would show).
+ *   Arithmetic, fp64 throughout, every sum in a fixed order, no floating-point atomics, each value rounded to fp32 once:
+ *     A_n(a,c) = sum over the rows in ascending row order of r_a r_c (products of the fp32 values in fp64), then damp^2 on the diagonal;
+ *     factor, inverse and C are dazim_map_posterior's, by the same kernels (option map_post.mfma selects their tile form);
+ *     Rm_ac = delta_ac - sum over the regularisation rows l with l_c != 0 in ascending row order of t_l l_c, then - damp^2 C_ac, with
+ *     t_l = sum_e C_ae l_e in ascending e; (Rm C)_aa = sum_c Rm_ac C_ac; a sum along a row: 256 strided partial sums, combined in a
+ *     fixed tree.  Host and device arguments give the same bits, and so do two calls.
+ *   If the factorisation meets a pivot that is not finite and > 0, every output is NaN and n_failed (host, nullable) is 1, else 0.
+ *   Refused (DAZIM_E_BAD_ARG, nothing written): m_data outside 0..m, n not nblk*maxvp, nx or ny < 3, nz < 2, a missing std_post,
+ *   std_noise, rdiag or rsum, leak without joint, width_z without depz or the reverse, sel entries outside 0..n-1, rows without sel, a
+ *   negative or non-finite damp, a row whose columns do not ascend strictly (found on the device), and a workspace that the card's free
+ *   memory cannot hold (the message names the GiB needed): two n x n fp64 matrices, allocated for the call and released before it
+ *   returns, and one fp64 per regularisation row for each of the row pass's workgroups.  The matrix's transpose is built if absent.
+ *   Stats: "model_posterior" and its parts "model_post.gram", ".factor", ".inverse", ".c", ".rows" (seconds), "model_post.n". */
+int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int nx, int ny, int nz, int joint, float damp,
+                          const float *depz, float *std_post, float *std_noise, float *rdiag, float *rsum, float *width_h,
+                          float *width_z, float *leak, int nsel, const int *sel, float *rows, float *trace, int *n_failed);
+
 /* ---- from the maps to a depth model, cell by cell (the second step of the two-step method) ------------------
  * dazim_vs_kernels: skern [nz][kmax][nx*ny] fp64 = sen_vp*coe_a + sen_rho*coe_rho + sen_vs at vel (the Brocher derivatives of the
  *   cell's velocity, inv/CalSurfG.f90:1339-1364): the table the 3-D rows of dazim_rays_build_G multiply, bit for bit (an iso row
