@@ -78,6 +78,17 @@ def geometry(nx, ny, goxd, gozd, dvxd, dvzd):
     return g
 
 
+def tradeoff_pick(chi2, reg2sum, gcv=None, logev=None):
+    """the three picks of a trade-off sweep (dazim_tradeoff_pick, host only): dict(corner, gcv, evidence), -1 where there is none"""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
+    chi2, reg2sum, gcv, logev = f(chi2), f(reg2sum), f(gcv), f(logev)
+    ic, ig, ie = C.c_int(-2), C.c_int(-2), C.c_int(-2)
+    rc = load().dazim_tradeoff_pick(int(chi2.shape[0]), _ptr(chi2), _ptr(reg2sum), _ptr(gcv), _ptr(logev), C.byref(ic), C.byref(ig), C.byref(ie))
+    if rc:
+        raise DazimError(rc, "bad arguments to dazim_tradeoff_pick")
+    return dict(corner=ic.value, gcv=ig.value, evidence=ie.value)
+
+
 class Context:
     """One GPU context (`dazim_ctx`).  Raises if no GPU / no library: there is no CPU path."""
 
@@ -490,6 +501,37 @@ class Context:
                                                    f32("std_noise"), f32("rdiag"), f32("rsum"), f32("width_h"), f32("width_z"),
                                                    f32("leak"), nsel, _ptr(sel, np.int32), f32("rows"), f32("trace"), C.byref(nf)))
         out["n_failed"] = nf.value
+        return out
+
+    def model_tradeoff(self, A, m_data, b, nx, ny, nz, joint, scale, damp, dof=True, evidence=True, x=False):
+        """the linearised step of the direct 3-D inversion solved exactly at K regularisation strengths (dazim_model_tradeoff, DESIGN.md
+        section 16): A, m_data as in model_posterior, b[m_data] the weighted right-hand side lsmr is given (numpy or torch-cuda),
+        scale [K][nblk] (or [K]: the same factor on every block) the factors on the stored regularisation rows, damp [K] (or one
+        value).  Returns a dict of numpy fp64 arrays: chi2, xnorm2, logdet_a [K]; reg2 [K][nblk]; dof [K][nblk] and gcv [K] (None
+        unless dof); logdet_p and logev [K] (None unless evidence); x [K][nblk][nz-1][ny-2][nx-2] fp32 (None unless asked); n_failed
+        [K] int32; pick = dict(corner, gcv, evidence), the indices dazim_tradeoff_pick names (-1: none)."""
+        nblk = 3 if joint else 1
+        scale = np.asarray(scale, np.float32)
+        if scale.ndim == 1:
+            scale = np.repeat(scale[:, None], nblk, axis=1)
+        scale = np.ascontiguousarray(scale.reshape(-1, nblk))
+        K = scale.shape[0]
+        damp = np.ascontiguousarray(np.broadcast_to(np.asarray(damp, np.float32), (K,)))
+        if not _is_torch(b):
+            b = np.ascontiguousarray(b, np.float32)
+        assert b.shape[0] == m_data
+        new = lambda *shape: np.zeros(shape, np.float64)
+        out = dict(chi2=new(K), reg2=new(K, nblk), xnorm2=new(K), logdet_a=new(K), logdet_p=new(K) if evidence else None,
+                   dof=new(K, nblk) if dof else None, gcv=new(K) if dof else None, logev=new(K) if evidence else None,
+                   x=np.zeros((K, nblk, nz - 1, ny - 2, nx - 2), np.float32) if x else None)
+        nf = np.zeros(K, np.int32)
+        f64 = lambda k: _ptr(out[k], np.float64)
+        self._check(self.lib.dazim_model_tradeoff(self._h, A._h, C.c_int64(int(m_data)), _ptr(b, np.float32), nx, ny, nz, int(bool(joint)), K,
+                                                  _ptr(scale, np.float32), _ptr(damp, np.float32), int(bool(dof)), int(bool(evidence)),
+                                                  f64("chi2"), f64("reg2"), f64("xnorm2"), f64("logdet_a"), f64("logdet_p"), f64("dof"),
+                                                  f64("gcv"), f64("logev"), _ptr(out["x"], np.float32), _ptr(nf, np.int32)))
+        out["n_failed"] = nf
+        out["pick"] = tradeoff_pick(out["chi2"], out["reg2"].sum(axis=1), out["gcv"], out["logev"])
         return out
 
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,

@@ -1,5 +1,6 @@
 // map_post_dense.hip -- the dense fp64 part that dazim_map_posterior (per period) and dazim_model_posterior (once) share, dz_mp_dense
-// of map_post_internal.h: on one block of ng unknowns
+// of map_post_internal.h, and its two halves dz_mp_factor and dz_mp_inverse_c, which dazim_model_tradeoff calls per sweep point: on one
+// block of ng unknowns
 //   factor   blocked right-looking Cholesky in place, panel width MP_NB: diagonal block, panel solve, trailing update
 //   inverse  M = R^-1 in place, block column by block column from the last: diagonal block, M22 * R21 into the second matrix, -(.) * M11
 //   c        C = M^T M into the second matrix, both triangles
@@ -236,26 +237,29 @@ __global__ __launch_bounds__(MP_TB) void k_mp_ctc(int ng, const double *M, doubl
 
 }  // namespace
 
-int dz_mp_dense(dazim_ctx *ctx, int ng, double *Ad, double *Cd, int *flag, bool mfma, const char *lapname, double *sec) {
+int dz_mp_factor(dazim_ctx *ctx, int ng, double *Ad, int *flag, bool mfma, const char *lapname, double *sec) {
+  DzTimer t(ctx, lapname);
+  for (int k0 = 0; k0 < ng; k0 += MP_NB) {
+    const int nb = std::min(MP_NB, ng - k0), rest = ng - k0 - nb;
+    hipLaunchKernelGGL(k_mp_potrf, dim3(1), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad, flag);
+    if (rest > 0) {
+      const unsigned nt = (unsigned)((rest + MP_TS - 1) / MP_TS);
+      hipLaunchKernelGGL(k_mp_trsm, dim3((unsigned)((rest + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad);
+      if (mfma) hipLaunchKernelGGL(k_mp_syrk<MpMfma>, dim3(nt, nt), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad);
+      else hipLaunchKernelGGL(k_mp_syrk<MpPlain>, dim3(nt, nt), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad);
+    }
+  }
+  DZ_HIP(hipGetLastError());
+  t.stop();
+  sec[0] += ctx->ksec[lapname];
+  return 0;
+}
+
+int dz_mp_inverse_c(dazim_ctx *ctx, int ng, double *Ad, double *Cd, bool mfma, const char *lapname, double *sec) {
   auto lap = [&](int which, DzTimer &t) {
     t.stop();
     sec[which] += ctx->ksec[lapname];
   };
-  {
-    DzTimer t(ctx, lapname);
-    for (int k0 = 0; k0 < ng; k0 += MP_NB) {
-      const int nb = std::min(MP_NB, ng - k0), rest = ng - k0 - nb;
-      hipLaunchKernelGGL(k_mp_potrf, dim3(1), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad, flag);
-      if (rest > 0) {
-        const unsigned nt = (unsigned)((rest + MP_TS - 1) / MP_TS);
-        hipLaunchKernelGGL(k_mp_trsm, dim3((unsigned)((rest + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad);
-        if (mfma) hipLaunchKernelGGL(k_mp_syrk<MpMfma>, dim3(nt, nt), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad);
-        else hipLaunchKernelGGL(k_mp_syrk<MpPlain>, dim3(nt, nt), dim3(MP_TB), 0, ctx->stream, ng, k0, nb, Ad);
-      }
-    }
-    DZ_HIP(hipGetLastError());
-    lap(0, t);
-  }
   {
     DzTimer t(ctx, lapname);
     for (int jb = ((ng - 1) / MP_NB) * MP_NB; jb >= 0; jb -= MP_NB) {
@@ -278,4 +282,9 @@ int dz_mp_dense(dazim_ctx *ctx, int ng, double *Ad, double *Cd, int *flag, bool 
     lap(2, t);
   }
   return 0;
+}
+
+int dz_mp_dense(dazim_ctx *ctx, int ng, double *Ad, double *Cd, int *flag, bool mfma, const char *lapname, double *sec) {
+  const int rc = dz_mp_factor(ctx, ng, Ad, flag, mfma, lapname, sec);
+  return rc ? rc : dz_mp_inverse_c(ctx, ng, Ad, Cd, mfma, lapname, sec);
 }

@@ -1,5 +1,6 @@
-// map_post_internal.h -- what map_post.hip (dazim_map_posterior, one dense block per period) and model_post.hip
-// (dazim_model_posterior, one dense block for the whole 3-D model) share: the sizes of the dense kernels, their two tile forms, the
+// map_post_internal.h -- what map_post.hip (dazim_map_posterior, one dense block per period), model_post.hip
+// (dazim_model_posterior, one dense block for the whole 3-D model) and model_tradeoff.hip (dazim_model_tradeoff, that block at every
+// point of a sweep over the regularisation weights) share: the sizes of the dense kernels, their two tile forms, the
 // fixed-order sum of a workgroup, and the host driver of the dense part (map_post_dense.hip), which both entries call -- so a block
 // of the maps and the block of the model go through the same kernels in the same order, bit for bit.
 #pragma once
@@ -76,7 +77,51 @@ __device__ __forceinline__ double mp_block_sum(double v, double *red) {
   return s;
 }
 
+constexpr int MO_UN = 4;    // row entries per lane in flight in mo_accum_row
+
+// One wavefront (lane t) adds to row a of a normal matrix, Aa[c] for c <= a, the entries [p0, p1) of column a in the transpose, rows
+// ascending: Aa[c] += v_a r_c (SCALED: f * (v_a r_c)) for the entries of row r with c <= a.  The columns of a row are distinct, so
+// MO_UN x 64 of its entries are in flight at a time; the barrier between two rows orders the read-modify-writes of an element that two
+// rows share (it may sit in different lanes).  dazim_model_posterior's Gram pass takes the whole column; dazim_model_tradeoff the data
+// rows once and the regularisation rows per sweep point -- the same numbers added in the same order.
+template <bool SCALED>
+__device__ __forceinline__ void mo_accum_row(int a, int t, int n, int64_t p0, int64_t p1, const int *row, const float *tval,
+                                             const int64_t *rowptr, const int *col, const float *val, double f, double *Aa) {
+  for (int64_t p = p0; p < p1; p++) {
+    const int r = row[p];
+    const double v = (double)tval[p];
+    const int64_t b = rowptr[r], e = rowptr[r + 1];
+    for (int64_t q0 = b; q0 < e; q0 += 64 * MO_UN) {
+      if (col[q0] > a) break;                       // (ascending: nothing at or behind q0 is <= a)
+      int cc[MO_UN];
+      double pr[MO_UN], old[MO_UN];
+#pragma unroll
+      for (int u = 0; u < MO_UN; u++) {
+        const int64_t q = q0 + u * 64 + t;
+        cc[u] = q < e ? col[q] : n;
+        if (cc[u] > a) cc[u] = -1;
+        pr[u] = cc[u] >= 0 ? v * (double)val[q] : 0.0;
+        if (SCALED) pr[u] = f * pr[u];
+      }
+#pragma unroll
+      for (int u = 0; u < MO_UN; u++) old[u] = cc[u] >= 0 ? Aa[cc[u]] : 0.0;
+#pragma unroll
+      for (int u = 0; u < MO_UN; u++)
+        if (cc[u] >= 0) Aa[cc[u]] = old[u] + pr[u];
+    }
+    __syncthreads();
+  }
+}
+
 #pragma GCC visibility push(hidden)
+// dz_mp_dense's two halves: the factorisation alone (seconds ADDED to sec[0]), and inverse and C (sec[1], sec[2]).  dz_mp_dense is
+// the first followed by the second: the same launches in the same order.
+int dz_mp_factor(dazim_ctx *ctx, int ng, double *Ad, int *flag, bool mfma, const char *lap, double *sec);
+int dz_mp_inverse_c(dazim_ctx *ctx, int ng, double *Ad, double *Cd, bool mfma, const char *lap, double *sec);
+// model_post.hip: *bad (device) |= 1 when a row's columns do not ascend strictly inside 0..n-1; regstart[c] = the first entry of column c
+// in the transpose that belongs to a row >= m_data.  Both enqueue on the context's stream.
+int dz_mo_check_rows(dazim_ctx *ctx, const dazim_csr *A, int n, int *bad);
+int dz_mo_regstart(dazim_ctx *ctx, const dazim_csr *A, int n, int64_t m_data, int64_t *regstart);
 // The dense part on one block of ng unknowns, enqueued on the context's stream: Ad [ng][ng] holds the lower triangle of the normal
 // matrix and ends as M = R^-1 (lower triangle), Cd [ng][max(ng, MP_NB)] is scratch for the inverse and ends as C = M^T M, both
 // triangles; *flag (device) is set to 1 at a pivot that is not finite and > 0.  mfma: the tile form of the trailing update and of C.

@@ -14,7 +14,6 @@
 namespace {
 
 constexpr int MO_WPC = 8;   // row-pass workgroups per CU; each keeps its own vector t (one fp64 per regularisation row) in memory
-constexpr int MO_UN = 4;    // row entries per lane in flight in the Gram pass
 
 // bad = 1 when a row's columns do not ascend strictly or leave 0..n-1
 __global__ __launch_bounds__(MP_TB) void k_mo_check(int64_t m, int n, const int64_t *rowptr, const int *col, int *bad) {
@@ -44,39 +43,15 @@ __global__ __launch_bounds__(MP_TB) void k_mo_regstart(int n, int64_t m_data, co
 }
 
 // row a of A_n (the lower triangle is what the factorisation reads): over the entries (r, v_a) of column a in the transpose, rows
-// ascending, A_n(a, c) += v_a r_c for the entries of row r with c <= a; then damp^2 on the diagonal.  One wavefront per unknown.  The
-// columns of a row are distinct, so MO_UN x 64 of its entries are in flight at a time; the barrier between two rows orders the
-// read-modify-writes of an element that two rows share (it may sit in different lanes).
+// ascending, A_n(a, c) += v_a r_c for the entries of row r with c <= a (mo_accum_row); then damp^2 on the diagonal.  One wavefront
+// per unknown.
 __global__ __launch_bounds__(64) void k_mo_gram(int n, const int64_t *colptr, const int *row, const float *tval, const int64_t *rowptr,
                                                 const int *col, const float *val, double d2, double *A) {
   const int a = blockIdx.x, t = threadIdx.x;
   double *Aa = A + (size_t)a * n;
   for (int c = t; c < n; c += 64) Aa[c] = 0.0;
   __syncthreads();
-  const int64_t pe = colptr[a + 1];
-  for (int64_t p = colptr[a]; p < pe; p++) {
-    const int r = row[p];
-    const double v = (double)tval[p];
-    const int64_t b = rowptr[r], e = rowptr[r + 1];
-    for (int64_t q0 = b; q0 < e; q0 += 64 * MO_UN) {
-      if (col[q0] > a) break;                       // (ascending: nothing at or behind q0 is <= a)
-      int cc[MO_UN];
-      double pr[MO_UN], old[MO_UN];
-#pragma unroll
-      for (int u = 0; u < MO_UN; u++) {
-        const int64_t q = q0 + u * 64 + t;
-        cc[u] = q < e ? col[q] : n;
-        if (cc[u] > a) cc[u] = -1;
-        pr[u] = cc[u] >= 0 ? v * (double)val[q] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < MO_UN; u++) old[u] = cc[u] >= 0 ? Aa[cc[u]] : 0.0;
-#pragma unroll
-      for (int u = 0; u < MO_UN; u++)
-        if (cc[u] >= 0) Aa[cc[u]] = old[u] + pr[u];
-    }
-    __syncthreads();
-  }
+  mo_accum_row<false>(a, t, n, colptr[a], colptr[a + 1], row, tval, rowptr, col, val, 1.0, Aa);
   if (t == 0) Aa[a] += d2;
 }
 
@@ -189,6 +164,19 @@ struct MoBig {   // the call's own allocations: released on every way out
 };
 
 }  // namespace
+
+// what dazim_model_tradeoff (model_tradeoff.hip) asks of the same matrix before its own kernels: the row check and regstart
+int dz_mo_check_rows(dazim_ctx *ctx, const dazim_csr *A, int n, int *bad) {
+  if (A->m > 0)
+    hipLaunchKernelGGL(k_mo_check, dim3((unsigned)((A->m + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, A->m, n, A->rowptr, A->col, bad);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+int dz_mo_regstart(dazim_ctx *ctx, const dazim_csr *A, int n, int64_t m_data, int64_t *regstart) {
+  hipLaunchKernelGGL(k_mo_regstart, dim3((unsigned)((n + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, n, m_data, A->colptr, A->row, regstart);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
 
 extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int nx, int ny, int nz, int joint, float damp,
                                      const float *depz_u, float *std_post_u, float *std_noise_u, float *rdiag_u, float *rsum_u,

@@ -8,7 +8,7 @@ module dazim_io
   private
   public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
   public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
-  public :: write_resolution, uncertainty_weights
+  public :: write_resolution, uncertainty_weights, tradeoff_factor, write_tradeoff
 
   real, parameter :: pi = 3.1415926535898
   real*8, parameter :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
@@ -272,6 +272,41 @@ contains
     real*8 :: c(nx - 2, ny - 2, kmax)
     c = pv(2:nx - 1, 2:ny - 1, :)
   end function
+
+  ! point k of npoint (1-based) of the trade-off sweep: the factor 10^(-1 + 2 (k-1)/(npoint-1)) on the regularisation weights
+  real function tradeoff_factor(k, npoint)
+    integer, intent(in) :: k, npoint
+    tradeoff_factor = 10.0**(-1.0 + 2.0*real(k - 1)/real(npoint - 1))
+  end function
+
+  ! one sweep of dazim_model_tradeoff into tradeoff.dat (unit u, open) and the program's log (unit ulog) and stdout.  A line per
+  ! point: sweep id, factor, the effective weights scale*weight per block and the damping, chi2, reg2 per block, xnorm2, dof per
+  ! block, gcv, logev.  Then three lines name the points (1-based, in the file's order; `none` for -1) that dazim_tradeoff_pick chose:
+  ! corner, igcv, iev are its 0-based indices.
+  subroutine write_tradeoff(u, ulog, sweep, label, npoint, nblk, weights, scale, damp, chi2, reg2, xnorm2, dof, gcv, logev, corner, igcv, iev)
+    integer, intent(in) :: u, ulog, sweep, npoint, nblk, corner, igcv, iev
+    character(len=*), intent(in) :: label
+    real, intent(in) :: weights(nblk), scale(nblk, npoint), damp(npoint)
+    real*8, intent(in) :: chi2(npoint), reg2(nblk, npoint), xnorm2(npoint), dof(nblk, npoint), gcv(npoint), logev(npoint)
+    integer :: k, q, which, idx(3), outs(2)
+    character(len=16), parameter :: what(3) = [character(len=16) :: 'L-curve corner', 'GCV minimum', 'evidence maximum']
+    do k = 1, npoint
+      write (u, '(i3,30es16.7e3)') sweep, tradeoff_factor(k, npoint), scale(:, k)*weights, damp(k), chi2(k), reg2(:, k), xnorm2(k), &
+        dof(:, k), gcv(k), logev(k)
+    end do
+    idx = [corner, igcv, iev]
+    outs = [6, ulog]
+    do q = 1, 2
+      do which = 1, 3
+        if (idx(which) < 0) then
+          write (outs(q), '(a,i2,4a)') ' tradeoff sweep', sweep, ' (', label, '): ', trim(what(which))//' none'
+        else
+          write (outs(q), '(a,i2,4a,i4,a,es12.4)') ' tradeoff sweep', sweep, ' (', label, '): ', trim(what(which))//' at point', idx(which) + 1, &
+            ', factor', tradeoff_factor(idx(which) + 1, npoint)
+        end if
+      end do
+    end do
+  end subroutine
 
   ! optional numeric command-line argument n: v keeps its value when there are fewer than n arguments; text that is not a
   ! number ends the program

@@ -24,6 +24,14 @@
 !                          kernel that lies in Gc, Gs); one line per inner cell and inverted knot in Vs_resolution_2step.dat's order
 !   log + stdout: per knot trace(Rm) / ncell per block, the median std_post of Vs and (iso-mode F) the median leak of Vs; "not factored"
 !                          when the normal matrix has no Cholesky factor
+!
+! `DAzimSurfTomo_amd para.in [uncertainty [tradeoff]]`, tradeoff = K >= 3 (default 0: as without the argument): on the same matrix and
+! that iteration's right-hand side, dazim_model_tradeoff at the K factors 10^(-1 + 2k/(K-1)), k = 0 .. K-1, on weightVs and weightGcs
+! together (sweep 1) and, in iso-mode F, on weightGcs alone with weightVs as given (sweep 2), with para.in's damping: the linearised
+! step solved exactly at each factor.  The model the program inverts with is not changed.  One rank only, as uncertainty = 1.
+!   tradeoff.dat           per point: sweep, factor, the effective weights per block and the damping, chi2, |L x|^2 per block (the rows
+!                          at para.in's weights), |x|^2, the resolved parameters tr(Rm) per block, GCV, log evidence
+!   log + stdout: per sweep the L-curve corner, the GCV minimum and the evidence maximum (dazim_tradeoff_pick)
 program DAzimSurfTomo_amd
   use iso_c_binding
   use dazim_mod
@@ -66,6 +74,7 @@ program DAzimSurfTomo_amd
   integer(c_int) :: nbad
   character(len=32) :: ngpu_val
   real, allocatable, target :: upost(:, :), utrace(:, :), udepz(:)
+  integer :: itrade                          ! tradeoff = K
 
   call system_clock(c0, crate)
   call system_clock(tk0, tkrate)
@@ -84,13 +93,22 @@ program DAzimSurfTomo_amd
   if (.not. ex) stop 'unable to open the inputfile'
   iunc = 0
   if (command_argument_count() >= 2) call optional_arg(2, iunc)
-  if (iunc == 1) then                         ! (before any rank is started)
+  itrade = 0
+  if (command_argument_count() >= 3) call optional_arg(3, itrade)
+  if (itrade /= 0 .and. itrade < 3) then
+    write (*, '(a,i6)') ' ERROR: tradeoff is 0 or the number of sweep points, at least 3; it is', itrade
+    error stop 'bad tradeoff argument'
+  end if
+  if (iunc == 1 .or. itrade > 0) then         ! (before any rank is started)
     ngpu_env = 1
     call get_environment_variable('DAZIM_NGPU', ngpu_val)
     if (len_trim(ngpu_val) > 0) read (ngpu_val, *) ngpu_env
-    if (ngpu_env > 1) then
+    if (ngpu_env > 1 .and. iunc == 1) then
       write (*, '(a)') ' ERROR: uncertainty = 1 needs the whole matrix on one GPU; with DAZIM_NGPU > 1 its rows are sharded over the ranks'
       error stop 'uncertainty = 1 with more than one rank'
+    else if (ngpu_env > 1) then
+      write (*, '(a)') ' ERROR: tradeoff > 0 needs the whole matrix on one GPU; with DAZIM_NGPU > 1 its rows are sharded over the ranks'
+      error stop 'tradeoff > 0 with more than one rank'
     end if
   end if
 
@@ -412,6 +430,7 @@ program DAzimSurfTomo_amd
                                              c_loc(upost(:, 6)), merge(c_null_ptr, c_loc(upost(:, 7)), iso_mod), 0_c_int, c_null_ptr, &
                                              c_null_ptr, c_loc(utrace), nbad), 'model posterior')
     end if
+    if (itrade > 0 .and. iter == maxiter) call tradeoff_sweeps()
     call dazim_check(dazim_csr_free(dazim_handle, G), 'free G')
     call dazim_check(dazim_csr_free(dazim_handle, Gd), 'free Gd')
     call tick(9)                             ! output files of the iteration
@@ -450,6 +469,45 @@ contains
     call system_clock(tk1)
     tph(i) = tph(i) + real(tk1 - tk0, 8)/real(tkrate, 8)
     tk0 = tk1
+  end subroutine
+
+  ! tradeoff.dat and the log's lines: dazim_model_tradeoff on this iteration's [W G; L] and weighted right-hand side cbst (the
+  ! regularisation rows of G hold para.in's weights, so the sweep's scale is the factor itself), before the matrix is freed.  The
+  ! sweeps are the points of ONE call, sweep after sweep, so the Gram matrix of the data rows is formed once for both.
+  subroutine tradeoff_sweeps()
+    integer :: nb, nsw, npt, s, k1, p0, p1
+    integer(c_int) :: corner, igcv, iev
+    real, allocatable :: tscale(:, :), tdamp(:), tw(:)
+    real(c_double), allocatable :: tchi2(:), treg2(:, :), txn(:), tlda(:), tldp(:), tdof(:, :), tgcv(:), tlev(:), tsum(:)
+    integer(c_int), allocatable :: tbad(:)
+    nb = merge(1, 3, iso_mod)
+    nsw = merge(1, 2, iso_mod)
+    npt = nsw*itrade
+    allocate (tscale(nb, npt), tdamp(npt), tw(nb), tchi2(npt), treg2(nb, npt), txn(npt), tlda(npt), tldp(npt), tdof(nb, npt), tgcv(npt), &
+              tlev(npt), tsum(npt), tbad(npt))
+    tw(1) = weightVs
+    if (nb == 3) tw(2:3) = weightGcs
+    tdamp = damp
+    do s = 1, nsw
+      do k1 = 1, itrade
+        tscale(:, (s - 1)*itrade + k1) = tradeoff_factor(k1, itrade)
+        if (s == 2) tscale(1, itrade + k1) = 1.0
+      end do
+    end do
+    call dazim_check(dazim_model_tradeoff(dazim_handle, G, int(dall, c_int64_t), cbst, nx, ny, nz, merge(0_c_int, 1_c_int, iso_mod), &
+                                          int(npt, c_int), tscale, tdamp, 1_c_int, 1_c_int, tchi2, treg2, txn, tlda, tldp, tdof, tgcv, &
+                                          tlev, c_null_ptr, tbad), 'model tradeoff')
+    tsum = sum(treg2, dim=1)
+    open (45, file='tradeoff.dat', status='replace', action='write')
+    do s = 1, nsw
+      p0 = (s - 1)*itrade + 1; p1 = s*itrade
+      call dazim_check(dazim_tradeoff_pick(int(itrade, c_int), tchi2(p0:p1), tsum(p0:p1), tgcv(p0:p1), tlev(p0:p1), corner, igcv, iev), &
+                       'tradeoff pick')
+      call write_tradeoff(45, 66, s, trim(merge('all blocks', 'Gc and Gs ', s == 1)), itrade, nb, tw, tscale(:, p0:p1), tdamp(p0:p1), &
+                          tchi2(p0:p1), treg2(:, p0:p1), txn(p0:p1), tdof(:, p0:p1), tgcv(p0:p1), tlev(p0:p1), int(corner), int(igcv), &
+                          int(iev))
+    end do
+    close (45)
   end subroutine
 
   ! model_uncertainty.dat and the log's lines from dazim_model_posterior's arrays (upost: std_post, std_noise, rdiag, rsum, width_h,

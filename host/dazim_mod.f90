@@ -33,7 +33,7 @@ module dazim_mod
             dazim_shard_fields, dazim_shard_rows, dazim_allsum
   ! the per-period map inversion (host/dazim_maps.f90)
   public :: dazim_dispersion_kernels, dazim_rays_build_G_maps, dazim_csr_append_laplacian2d, dazim_phase_map_update, &
-            dazim_assemble_G_maps, dazim_map_posterior, dazim_model_posterior
+            dazim_assemble_G_maps, dazim_map_posterior, dazim_model_posterior, dazim_model_tradeoff, dazim_tradeoff_pick
   ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
   public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq, dazim_column_resolution
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
@@ -386,6 +386,24 @@ module dazim_mod
       real(c_float), value :: damp
       real(c_float) :: std_post(*), std_noise(*), rdiag(*), rsum(*)
       integer(c_int) :: n_failed
+    end function
+    ! scale [nblk, npoint] (the C layout [npoint][nblk]), reg2 and dof likewise; x: c_loc of [n, npoint] or c_null_ptr
+    integer(c_int) function dazim_model_tradeoff(ctx, A, m_data, b, nx, ny, nz, joint, npoint, scale, damp, want_dof, want_evidence, chi2, &
+        reg2, xnorm2, logdet_a, logdet_p, dof, gcv, logev, x, n_failed) bind(C, name="dazim_model_tradeoff")
+      import
+      type(c_ptr), value :: ctx, A, x
+      integer(c_int64_t), value :: m_data
+      integer(c_int), value :: nx, ny, nz, joint, npoint, want_dof, want_evidence
+      real(c_float) :: b(*), scale(*), damp(*)
+      real(c_double) :: chi2(*), reg2(*), xnorm2(*), logdet_a(*), logdet_p(*), dof(*), gcv(*), logev(*)
+      integer(c_int) :: n_failed(*)
+    end function
+    ! corner, igcv, iev: 0-based indices, -1 for none
+    integer(c_int) function dazim_tradeoff_pick(npoint, chi2, reg2sum, gcv, logev, corner, igcv, iev) bind(C, name="dazim_tradeoff_pick")
+      import
+      integer(c_int), value :: npoint
+      real(c_double) :: chi2(*), reg2sum(*), gcv(*), logev(*)
+      integer(c_int) :: corner, igcv, iev
     end function
     integer(c_int) function dazim_memcpy_h2d(ctx, dst, src, bytes) bind(C, name="dazim_memcpy_h2d")
       import; type(c_ptr), value :: ctx, dst, src; integer(c_size_t), value :: bytes

@@ -335,6 +335,46 @@ int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, in
                           const float *depz, float *std_post, float *std_noise, float *rdiag, float *rsum, float *width_h,
                           float *width_z, float *leak, int nsel, const int *sel, float *rows, float *trace, int *n_failed);
 
+/* dazim_model_tradeoff: the linearised step of the direct 3-D inversion solved exactly at K regularisation strengths, with what an
+ * L-curve, generalised cross-validation and the Bayesian evidence need at each.  A, m_data, nx, ny, nz, joint,
+ * the column layout and nblk are dazim_model_posterior's; b [m_data] (host or device) is the weighted right-hand side of the data rows,
+ * as dazim_lsmr is given it; the regularisation rows have right-hand side 0.  Every regularisation row lies in one block.
+ *   scale [K][nblk], damp [K] (host): point k multiplies the stored regularisation rows of block b by scale[k][b] and damps with damp[k]:
+ *     D = sum_{data rows} r^T r     R_b = sum_{regularisation rows of block b} l^T l     g = sum_{data rows} r^T b_r
+ *     P_k = sum_b scale[k][b]^2 R_b + damp[k]^2 I        A_k = D + P_k = R R^T        x_k = A_k^-1 g (forward and back substitution)
+ *   Outputs (host or device; [K] unless noted):
+ *     chi2      |G x_k - b|^2 over the data rows          reg2 [K][nblk]  |L_b x_k|^2, the rows as stored (unscaled)
+ *     xnorm2    |x_k|^2                                    logdet_a        2 sum_i log R_ii
+ *     logdet_p  (nullable; want_evidence) the same from a second factorisation, of P_k alone; NaN when P_k has a pivot that is not
+ *               finite and > 0, which does not count as a failure of the point
+ *     dof [K][nblk] (nullable; want_dof)  sum_{a in block b} sum_c C_ac D_ac, C = A_k^-1: block b's share of tr(Rm)
+ *     gcv       (nullable; want_dof)      m_data chi2 / (m_data - sum_b dof[b])^2
+ *     logev     (nullable; want_evidence) -(chi2 + J)/2 + logdet_p/2 - logdet_a/2 - m_data log(2 pi)/2, J = sum_b scale[k][b]^2 reg2[b]
+ *               + damp[k]^2 xnorm2: the log marginal likelihood of b under unit-variance data errors and the prior N(0, P_k^-1)
+ *     x [K][n] fp32 (nullable)            x_k, rounded once
+ *   A point whose A_k meets a pivot that is not finite and > 0 has NaN in every output and n_failed[k] (host, [K], nullable) = 1, else
+ *   0; the other points are not affected.
+ *   Arithmetic: fp64, every sum in a fixed order set by the problem alone, no floating-point atomics.  D is formed once per call; at
+ *   scale 1 the matrix factored is dazim_model_posterior's, the same numbers added in the same order; the factorisation, and with
+ *   want_dof the inverse and C, are its kernels (option map_post.mfma).  Two calls give the same bits, host and device arguments give
+ *   the same bits, and a point gives the same bits alone as at any position of any sweep.
+ *   Refused (DAZIM_E_BAD_ARG, nothing written): what dazim_model_posterior refuses of A, m_data, nx, ny, nz; K < 1; a missing b, scale,
+ *   damp, chi2, reg2, xnorm2 or logdet_a; a negative or non-finite scale or damp; dof or gcv without want_dof; logdet_p or logev
+ *   without want_evidence; a regularisation row with entries in two blocks (found on the device); and a workspace the card's free
+ *   memory cannot hold (the message names the GiB needed): D, the work matrix and with want_dof C, n x n fp64 each, allocated for the
+ *   call and released before it returns.
+ *   Stats: "model_tradeoff" and its parts "model_trade.gram" (once per call), ".factor", ".solve", ".inverse" (summed over the points),
+ *   ".points", "model_trade.n".
+ * dazim_tradeoff_pick (host only): corner = the interior point of largest Menger curvature of the polyline (log chi2, log reg2sum)
+ *   through the points where both are finite, in the order given; igcv = the smallest finite gcv; iev = the largest finite logev (gcv,
+ *   logev nullable).  An index is -1 when there are fewer than three finite points (corner) or none (igcv, iev). */
+int dazim_model_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, const float *b, int nx, int ny, int nz, int joint, int K,
+                         const float *scale, const float *damp, int want_dof, int want_evidence, double *chi2, double *reg2,
+                         double *xnorm2, double *logdet_a, double *logdet_p, double *dof, double *gcv, double *logev, float *x,
+                         int *n_failed);
+int dazim_tradeoff_pick(int K, const double *chi2, const double *reg2sum, const double *gcv, const double *logev, int *corner,
+                        int *igcv, int *iev);
+
 /* ---- from the maps to a depth model, cell by cell (the second step of the two-step method) ------------------
  * dazim_vs_kernels: skern [nz][kmax][nx*ny] fp64 = sen_vp*coe_a + sen_rho*coe_rho + sen_vs at vel (the Brocher derivatives of the
  *   cell's velocity, inv/CalSurfG.f90:1339-1364): the table the 3-D rows of dazim_rays_build_G multiply, bit for bit (an iso row
