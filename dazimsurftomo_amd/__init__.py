@@ -89,6 +89,21 @@ def tradeoff_pick(chi2, reg2sum, gcv=None, logev=None):
     return dict(corner=ic.value, gcv=ig.value, evidence=ie.value)
 
 
+def map_tradeoff_total(mdata_p, chi2, reg2, dof=None, logev=None):
+    """the criteria of the whole block-diagonal system from Context.map_tradeoff's per-period arrays (dazim_map_tradeoff_total, host
+    only): dict(chi2, reg2sum, dof, gcv, logev), each [K], the sums over the periods; dof, gcv and logev None where not given"""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
+    mdata_p, chi2, reg2, dof, logev = np.ascontiguousarray(mdata_p, np.int64), f(chi2), f(reg2), f(dof), f(logev)
+    K, kmax, nblk = reg2.shape
+    new = lambda on: np.zeros(K, np.float64) if on else None
+    out = dict(chi2=new(True), reg2sum=new(True), dof=new(dof is not None), gcv=new(dof is not None), logev=new(logev is not None))
+    rc = load().dazim_map_tradeoff_total(K, kmax, nblk, _ptr(mdata_p, np.int64), _ptr(chi2), _ptr(reg2), _ptr(dof), _ptr(logev),
+                                         *[_ptr(out[k]) for k in ("chi2", "reg2sum", "dof", "gcv", "logev")])
+    if rc:
+        raise DazimError(rc, "bad arguments to dazim_map_tradeoff_total")
+    return out
+
+
 class Context:
     """One GPU context (`dazim_ctx`).  Raises if no GPU / no library: there is no CPU path."""
 
@@ -466,6 +481,45 @@ class Context:
                                                  f32("std_post"), f32("std_noise"), f32("rdiag"), f32("rsum"), f32("width"), f32("leak"),
                                                  nsel, _ptr(sel, np.int32), f32("rows"), f32("trace"), C.byref(nf)))
         out["n_failed"] = nf.value
+        return out
+
+    def map_tradeoff(self, A, m_data, b, nx, ny, kmax, azim, scale, damp, dof=True, evidence=True, x=False):
+        """the maps' linearised step solved exactly at K regularisation strengths, per period (dazim_map_tradeoff, DESIGN.md section
+        12.2): A, m_data as in map_posterior, b[m_data] the weighted right-hand side lsmr is given (numpy or torch-cuda), scale
+        [K][nblk] (or [K]: the same factor on every block) the factors on the stored regularisation rows, damp [K] (or one value).
+        Returns a dict of numpy arrays: mdata_p [kmax] int64; chi2, xnorm2, logdet_a [K][kmax] fp64; reg2 [K][kmax][nblk]; dof
+        [K][kmax][nblk] and gcv [K][kmax] (None unless dof); logdet_p and logev [K][kmax] (None unless evidence); x
+        [K][nblk][kmax][ny-2][nx-2] fp32 (None unless asked); n_failed [K][kmax] int32; total = dict(chi2, reg2sum, dof, gcv, logev),
+        each [K], the sums over the periods (dazim_map_tradeoff_total); pick = per period dict(corner, gcv, evidence), the indices
+        dazim_tradeoff_pick names (-1: none); pick_total the same from the totals."""
+        nblk = 3 if azim else 1
+        scale = np.asarray(scale, np.float32)
+        if scale.ndim == 1:
+            scale = np.repeat(scale[:, None], nblk, axis=1)
+        scale = np.ascontiguousarray(scale.reshape(-1, nblk))
+        K = scale.shape[0]
+        damp = np.ascontiguousarray(np.broadcast_to(np.asarray(damp, np.float32), (K,)))
+        if not _is_torch(b):
+            b = np.ascontiguousarray(b, np.float32)
+        assert b.shape[0] == m_data
+        new = lambda *shape: np.zeros(shape, np.float64)
+        out = dict(mdata_p=np.zeros(kmax, np.int64), chi2=new(K, kmax), reg2=new(K, kmax, nblk), xnorm2=new(K, kmax), logdet_a=new(K, kmax),
+                   logdet_p=new(K, kmax) if evidence else None, dof=new(K, kmax, nblk) if dof else None, gcv=new(K, kmax) if dof else None,
+                   logev=new(K, kmax) if evidence else None, x=np.zeros((K, nblk, kmax, ny - 2, nx - 2), np.float32) if x else None)
+        nf = np.zeros((K, kmax), np.int32)
+        f64 = lambda k: _ptr(out[k], np.float64)
+        self._check(self.lib.dazim_map_tradeoff(self._h, A._h, C.c_int64(int(m_data)), _ptr(b, np.float32), nx, ny, int(kmax), int(bool(azim)), K,
+                                                _ptr(scale, np.float32), _ptr(damp, np.float32), int(bool(dof)), int(bool(evidence)),
+                                                _ptr(out["mdata_p"], np.int64), f64("chi2"), f64("reg2"), f64("xnorm2"), f64("logdet_a"),
+                                                f64("logdet_p"), f64("dof"), f64("gcv"), f64("logev"), _ptr(out["x"], np.float32),
+                                                _ptr(nf, np.int32)))
+        out["n_failed"] = nf
+        out["total"] = map_tradeoff_total(out["mdata_p"], out["chi2"], out["reg2"], out["dof"], out["logev"])
+        reg2sum = out["reg2"].sum(axis=2)
+        col = lambda a, p: None if a is None else a[:, p]
+        out["pick"] = [tradeoff_pick(out["chi2"][:, p], reg2sum[:, p], col(out["gcv"], p), col(out["logev"], p)) for p in range(kmax)]
+        tot = out["total"]
+        out["pick_total"] = tradeoff_pick(tot["chi2"], tot["reg2sum"], tot["gcv"], tot["logev"])
         return out
 
     def model_posterior(self, A, m_data, nx, ny, nz, joint, damp, depz=None, sel=None, width=True):

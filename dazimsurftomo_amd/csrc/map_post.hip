@@ -15,8 +15,6 @@ namespace {
 
 constexpr int MP_EMAX = 8;  // entries of a regularisation row the row pass keeps in LDS (a longer row is read from memory again)
 
-__device__ __forceinline__ int mp_local(int c, int kn, int ncell) { return (c / kn) * ncell + c % ncell; }
-
 // period of every row (-1: a row without entries) and the range of cells it touches, span[2r] .. span[2r+1]; bad |= 1 for a row whose
 // columns lie in two periods, |= 2 for a row whose columns do not ascend strictly
 __global__ __launch_bounds__(MP_TB) void k_mp_row_period(int64_t m, const int64_t *rowptr, const int *col, int kn, int ncell, int *per,
@@ -74,44 +72,14 @@ __global__ __launch_bounds__(MP_TB) void k_mp_row_lists(int64_t m, int64_t m_dat
 }
 
 // row a of A_g (all n_g entries; the lower triangle is what the factorisation reads): sum over the period's rows r, ascending, of
-// r_a r_c, then damp^2 on the diagonal.  One wavefront per row a; a row of the matrix holds column a at most once.  Of 64 rows at a
-// time only those whose range of cells holds a's cell are read (a map row has about 130 of 2 704 cells, close together).
+// r_a r_c (mp_accum_rows), then damp^2 on the diagonal.  One wavefront per row a.
 __global__ __launch_bounds__(64) void k_mp_gram(int ng, int ncell, int kn, int p, int nrow, const int *list, const int *span,
                                                 const int64_t *rowptr, const int *col, const float *val, double d2, double *A) {
-  const int a = blockIdx.x, t = threadIdx.x, cell_a = a % ncell;
-  const int ga = (a / ncell) * kn + p * ncell + a % ncell;
+  const int a = blockIdx.x, t = threadIdx.x;
   double *Aa = A + (size_t)a * ng;
   for (int c = t; c < ng; c += 64) Aa[c] = 0.0;
   __syncthreads();
-  for (int i0 = 0; i0 < nrow; i0 += 64) {
-    long long mb = 0, me = 0;
-    bool near = false;
-    if (i0 + t < nrow) {
-      const int r = list[i0 + t];
-      mb = rowptr[r];
-      me = rowptr[r + 1];
-      near = span[2 * (size_t)r] <= cell_a && cell_a <= span[2 * (size_t)r + 1];
-    }
-    for (unsigned long long cand = __ballot(near); cand; cand &= cand - 1ull) {   // ascending rows
-      const int k = __ffsll((long long)cand) - 1;
-      const long long b = __shfl(mb, k), e = __shfl(me, k);
-      float va = 0.0f;
-      bool hit = false;
-      for (long long q = b + t; q < e; q += 64)
-        if (col[q] == ga) {
-          va = val[q];
-          hit = true;
-        }
-      const unsigned long long h = __ballot(hit);
-      if (!h) continue;
-      const double v = (double)__shfl(va, __ffsll((long long)h) - 1);
-      for (long long q = b + t; q < e; q += 64) {
-        const int lc = mp_local(col[q], kn, ncell);
-        if (lc <= a) Aa[lc] += v * (double)val[q];
-      }
-      __syncthreads();   // (the next row may hold the same columns in other lanes)
-    }
-  }
+  mp_accum_rows<false>(a, t, ncell, kn, p, nrow, list, span, rowptr, col, val, 1.0, Aa);
   if (t == 0) Aa[a] += d2;
 }
 
@@ -234,6 +202,32 @@ __global__ __launch_bounds__(MP_TB) void k_mp_trace(int ncell, int kmax, int p, 
 
 }  // namespace
 
+// ---- what dazim_map_tradeoff (map_tradeoff.hip) shares, declared in map_post_internal.h ----
+int dz_mp_period_rows(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int kmax, int kn, int ncell, int *per, int *span, int *cnt, int *list,
+                      std::vector<int> &hcnt) {
+  const int64_t m = A->m;
+  int *bad = cnt + 2 * kmax;
+  DZ_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(k_mp_row_period, dim3((unsigned)((m + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, m, A->rowptr, A->col, kn, ncell,
+                     per, span, bad);
+  DZ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_mp_row_lists, dim3((unsigned)kmax), dim3(MP_TB), 0, ctx->stream, m, m_data, per, cnt, (int *)nullptr);
+  DZ_HIP(hipGetLastError());
+  hcnt.assign((size_t)2 * kmax + 1, 0);
+  DZ_HIP(hipMemcpyAsync(hcnt.data(), cnt, hcnt.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (hcnt[2 * kmax]) return 0;
+  hipLaunchKernelGGL(k_mp_row_lists, dim3((unsigned)kmax), dim3(MP_TB), 0, ctx->stream, m, m_data, per, cnt, list);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
+int dz_mp_gram(dazim_ctx *ctx, int ng, int ncell, int kn, int p, int nrow, const int *list, const int *span, const dazim_csr *A, double d2, double *Ad) {
+  hipLaunchKernelGGL(k_mp_gram, dim3((unsigned)ng), dim3(64), 0, ctx->stream, ng, ncell, kn, p, nrow, list, span, A->rowptr, A->col, A->val, d2, Ad);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int nx, int ny, int kmax, int azim, float damp,
                                    float *std_post_u, float *std_noise_u, float *rdiag_u, float *rsum_u, float *width_u, float *leak_u,
                                    int nsel, const int *sel_u, float *rows_u, float *trace_u, int *n_failed) {
@@ -276,22 +270,11 @@ extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m
   DZ_HIP(hipFuncSetAttribute((const void *)k_mp_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (a refusal ends the call: no launch)
   if (nsel > 0 && (rc = dz_check_range(ctx, sel.dev, nsel, 0, ng - 1, "dazim_map_posterior: sel"))) return rc;
   // ---- the rows of every period ----
-  int *bad = cnt + 2 * kmax, hbad = 0;
-  DZ_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
   DZ_HIP(hipMemsetAsync(flags, 0, (size_t)kmax * sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(k_mp_row_period, dim3((unsigned)((m + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, m, A->rowptr, A->col, kn, ncell,
-                     per, span, bad);
-  DZ_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_mp_row_lists, dim3((unsigned)kmax), dim3(MP_TB), 0, ctx->stream, m, m_data, per, cnt, (int *)nullptr);
-  DZ_HIP(hipGetLastError());
-  std::vector<int> hcnt(2 * kmax + 1);
-  DZ_HIP(hipMemcpyAsync(hcnt.data(), cnt, hcnt.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  hbad = hcnt[2 * kmax];
-  if (hbad & 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: a row's columns lie in two periods");
-  if (hbad & 2) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: a row's columns do not ascend strictly");
-  hipLaunchKernelGGL(k_mp_row_lists, dim3((unsigned)kmax), dim3(MP_TB), 0, ctx->stream, m, m_data, per, cnt, list);
-  DZ_HIP(hipGetLastError());
+  std::vector<int> hcnt;
+  if ((rc = dz_mp_period_rows(ctx, A, m_data, kmax, kn, ncell, per, span, cnt, list, hcnt))) return rc;
+  if (hcnt[2 * kmax] & 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: a row's columns lie in two periods");
+  if (hcnt[2 * kmax] & 2) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: a row's columns do not ascend strictly");
   const bool mfma = dz_opt(ctx, "map_post.mfma", 1) != 0;
   const double d2 = (double)damp * (double)damp;
   const MpOut out = {sp.dev, sn.dev, rd.dev, rs.dev, wd.dev, lk.dev, rw.dev};
@@ -307,8 +290,7 @@ extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m
     off += nrow;
     {
       DzTimer t(ctx, "map_post.lap");
-      hipLaunchKernelGGL(k_mp_gram, dim3((unsigned)ng), dim3(64), 0, ctx->stream, ng, ncell, kn, p, nrow, lp, span, A->rowptr, A->col, A->val, d2, Ad);
-      DZ_HIP(hipGetLastError());
+      if ((rc = dz_mp_gram(ctx, ng, ncell, kn, p, nrow, lp, span, A, d2, Ad))) return rc;
       lap(0, t);
     }
     if ((rc = dz_mp_dense(ctx, ng, Ad, Cd, flags + p, mfma, "map_post.lap", sec + 1))) return rc;

@@ -1,9 +1,11 @@
 // map_post_internal.h -- what map_post.hip (dazim_map_posterior, one dense block per period), model_post.hip
-// (dazim_model_posterior, one dense block for the whole 3-D model) and model_tradeoff.hip (dazim_model_tradeoff, that block at every
-// point of a sweep over the regularisation weights) share: the sizes of the dense kernels, their two tile forms, the
+// (dazim_model_posterior, one dense block for the whole 3-D model), model_tradeoff.hip (dazim_model_tradeoff, that block at every
+// point of a sweep over the regularisation weights) and map_tradeoff.hip (dazim_map_tradeoff, the same sweep per period) share: the sizes of the dense kernels, their two tile forms, the
 // fixed-order sum of a workgroup, and the host driver of the dense part (map_post_dense.hip), which both entries call -- so a block
 // of the maps and the block of the model go through the same kernels in the same order, bit for bit.
 #pragma once
+#include <vector>
+
 #include "sparse_internal.h"
 
 constexpr int MP_NB = 32;   // panel width of the factorisation and of the inverse (stat map_post.nb)
@@ -77,6 +79,52 @@ __device__ __forceinline__ double mp_block_sum(double v, double *red) {
   return s;
 }
 
+// local index blk * ncell + cell of column c = blk * kn + p * ncell + cell of the maps' layout (kn = kmax ncell)
+__device__ __forceinline__ int mp_local(int c, int kn, int ncell) { return (c / kn) * ncell + c % ncell; }
+
+// One wavefront (lane t) adds to row a of a period's normal matrix, Aa[c] for c <= a in the local index, the rows list[0 .. nrow) of
+// period p in the order of the list: Aa[c] += r_a r_c (SCALED: f * (r_a r_c)).  A row of the matrix holds column a at most once.  Of
+// 64 rows at a time only those whose range of cells holds a's cell are read (a map row has about 130 of 2 704 cells, close together).
+// dazim_map_posterior's Gram pass takes all rows of the period; dazim_map_tradeoff the data rows once and the regularisation rows per
+// sweep point -- the same numbers added in the same order.
+template <bool SCALED>
+__device__ __forceinline__ void mp_accum_rows(int a, int t, int ncell, int kn, int p, int nrow, const int *list, const int *span,
+                                              const int64_t *rowptr, const int *col, const float *val, double f, double *Aa) {
+  const int cell_a = a % ncell, ga = (a / ncell) * kn + p * ncell + a % ncell;
+  for (int i0 = 0; i0 < nrow; i0 += 64) {
+    long long mb = 0, me = 0;
+    bool near = false;
+    if (i0 + t < nrow) {
+      const int r = list[i0 + t];
+      mb = rowptr[r];
+      me = rowptr[r + 1];
+      near = span[2 * (size_t)r] <= cell_a && cell_a <= span[2 * (size_t)r + 1];
+    }
+    for (unsigned long long cand = __ballot(near); cand; cand &= cand - 1ull) {   // ascending rows
+      const int k = __ffsll((long long)cand) - 1;
+      const long long b = __shfl(mb, k), e = __shfl(me, k);
+      float va = 0.0f;
+      bool hit = false;
+      for (long long q = b + t; q < e; q += 64)
+        if (col[q] == ga) {
+          va = val[q];
+          hit = true;
+        }
+      const unsigned long long h = __ballot(hit);
+      if (!h) continue;
+      const double v = (double)__shfl(va, __ffsll((long long)h) - 1);
+      for (long long q = b + t; q < e; q += 64) {
+        const int lc = mp_local(col[q], kn, ncell);
+        if (lc <= a) {
+          if (SCALED) Aa[lc] += f * (v * (double)val[q]);
+          else Aa[lc] += v * (double)val[q];
+        }
+      }
+      __syncthreads();   // (the next row may hold the same columns in other lanes)
+    }
+  }
+}
+
 constexpr int MO_UN = 4;    // row entries per lane in flight in mo_accum_row
 
 // One wavefront (lane t) adds to row a of a normal matrix, Aa[c] for c <= a, the entries [p0, p1) of column a in the transpose, rows
@@ -127,4 +175,21 @@ int dz_mo_regstart(dazim_ctx *ctx, const dazim_csr *A, int n, int64_t m_data, in
 // triangles; *flag (device) is set to 1 at a pivot that is not finite and > 0.  mfma: the tile form of the trailing update and of C.
 // The seconds of factor, inverse and C are ADDED to sec[0..2]; they are measured with the context's events under the stat `lap`.
 int dz_mp_dense(dazim_ctx *ctx, int ng, double *Ad, double *Cd, int *flag, bool mfma, const char *lap, double *sec);
+// map_post.hip, the rows of every period of the maps' layout (kn = kmax ncell), on the context's stream: per [m] the period of a row
+// (-1: no entries), span [2m] the range of cells it touches, list [m] the rows period by period, ascending; cnt [2 kmax + 1] (device)
+// and hcnt (host, after a synchronisation) the rows and the data rows of period p at 2p, 2p + 1, and at 2 kmax the bits 1 (a row in two
+// periods) and 2 (columns that do not ascend strictly).  With a bit set the list is not written.
+int dz_mp_period_rows(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int kmax, int kn, int ncell, int *per, int *span, int *cnt, int *list,
+                      std::vector<int> &hcnt);
+// k_mp_gram on the rows list[0 .. nrow) of period p: the lower triangle of sum_r r^T r + d2 I into Ad [ng][ng], zeros above it
+int dz_mp_gram(dazim_ctx *ctx, int ng, int ncell, int kn, int p, int nrow, const int *list, const int *span, const dazim_csr *A, double d2, double *Ad);
+// model_tradeoff.hip, one right-hand side on the factor R (lower triangle of Rd [n][n]), enqueued on the context's stream:
+// dz_mt_solve: y := R^-T R^-1 y by panels of MP_NB.  dz_mt_logdet_norm: *ld = 2 sum_i log R_ii and, with x, *xn = sum_i x_i^2.
+// dz_mt_mirror: D[c][a] = D[a][c] for c < a.  dz_mt_rowdot: rowdot[a] = sum_c C_ac D_ac.  dz_mt_sum: out[j] = sum_{i < count}
+// src[j step + i stride] for j < nout.  Every sum in a fixed order.
+int dz_mt_solve(dazim_ctx *ctx, int n, const double *Rd, double *y);
+int dz_mt_logdet_norm(dazim_ctx *ctx, int n, const double *Rd, const double *x, double *ld, double *xn);
+int dz_mt_mirror(dazim_ctx *ctx, int n, double *D);
+int dz_mt_rowdot(dazim_ctx *ctx, int n, const double *Cm, const double *D, double *rowdot);
+int dz_mt_sum(dazim_ctx *ctx, int nout, int64_t count, int stride, int64_t step, const double *src, double *out);
 #pragma GCC visibility pop

@@ -244,6 +244,48 @@ struct MtBig {   // the call's own allocations: released on every way out
 
 }  // namespace
 
+// ---- what dazim_map_tradeoff (map_tradeoff.hip) shares, declared in map_post_internal.h: the launches below, in this order ----
+int dz_mt_solve(dazim_ctx *ctx, int n, const double *Rd, double *y) {
+  for (int k0 = 0; k0 < n; k0 += MP_NB) {
+    const int nb = std::min(MP_NB, n - k0), rest = n - k0 - nb;
+    hipLaunchKernelGGL(k_mt_trsv_diag<false>, dim3(1), dim3(64), 0, ctx->stream, n, k0, nb, Rd, y);
+    if (rest > 0)
+      hipLaunchKernelGGL(k_mt_fwd_upd, dim3((unsigned)((rest + MP_TB / 32 - 1) / (MP_TB / 32))), dim3(MP_TB), 0, ctx->stream, n, k0, nb, Rd, y);
+  }
+  for (int k0 = ((n - 1) / MP_NB) * MP_NB; k0 >= 0; k0 -= MP_NB) {
+    const int nb = std::min(MP_NB, n - k0);
+    hipLaunchKernelGGL(k_mt_trsv_diag<true>, dim3(1), dim3(64), 0, ctx->stream, n, k0, nb, Rd, y);
+    if (k0 > 0) hipLaunchKernelGGL(k_mt_bwd_upd, dim3((unsigned)((k0 + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, n, k0, nb, Rd, y);
+  }
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
+int dz_mt_logdet_norm(dazim_ctx *ctx, int n, const double *Rd, const double *x, double *ld, double *xn) {
+  hipLaunchKernelGGL(k_mt_logdet_norm, dim3(x ? 2 : 1), dim3(MP_TB), 0, ctx->stream, n, Rd, x, ld, xn);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
+int dz_mt_mirror(dazim_ctx *ctx, int n, double *D) {
+  const unsigned ntr = (unsigned)((n + MT_TR - 1) / MT_TR);
+  hipLaunchKernelGGL(k_mt_mirror, dim3(ntr, ntr), dim3(MP_TB), 0, ctx->stream, n, D);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
+int dz_mt_rowdot(dazim_ctx *ctx, int n, const double *Cm, const double *D, double *rowdot) {
+  hipLaunchKernelGGL(k_mt_rowdot, dim3((unsigned)n), dim3(MP_TB), 0, ctx->stream, n, Cm, D, rowdot);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
+int dz_mt_sum(dazim_ctx *ctx, int nout, int64_t count, int stride, int64_t step, const double *src, double *out) {
+  hipLaunchKernelGGL(k_mt_sum, dim3((unsigned)nout), dim3(MP_TB), 0, ctx->stream, count, stride, step, src, out);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" int dazim_model_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, const float *b_u, int nx, int ny, int nz, int joint, int K,
                                     const float *scale, const float *damp, int want_dof, int want_evidence, double *chi2_u, double *reg2_u,
                                     double *xnorm2_u, double *logdet_a_u, double *logdet_p_u, double *dof_u, double *gcv_u, double *logev_u,
@@ -332,8 +374,7 @@ extern "C" int dazim_model_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t 
     DzTimer t(ctx, lapname);
     if ((rc = dz_mo_regstart(ctx, A, n, m_data, regstart))) return rc;
     hipLaunchKernelGGL(k_mt_gram_data, dim3((unsigned)n), dim3(64), 0, ctx->stream, n, A->colptr, regstart, A->row, A->tval, A->rowptr, A->col, A->val, Dd);
-    const unsigned ntr = (unsigned)((n + MT_TR - 1) / MT_TR);
-    hipLaunchKernelGGL(k_mt_mirror, dim3(ntr, ntr), dim3(MP_TB), 0, ctx->stream, n, Dd);
+    if ((rc = dz_mt_mirror(ctx, n, Dd))) return rc;
     hipLaunchKernelGGL(k_mt_rhs, dim3((unsigned)n), dim3(64), 0, ctx->stream, A->colptr, regstart, A->row, A->tval, bb.dev, g);
     DZ_HIP(hipMemsetAsync(Wd, 0, bA, ctx->stream));   // (the upper triangle of the work matrix is never written or read)
     DZ_HIP(hipGetLastError());
@@ -357,27 +398,16 @@ extern "C" int dazim_model_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t 
       DzTimer t(ctx, lapname);
       DZ_HIP(hipMemsetAsync(sc, 0, MT_NSC * sizeof(double), ctx->stream));
       DZ_HIP(hipMemcpyAsync(y, g, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      for (int k0 = 0; k0 < n; k0 += MP_NB) {
-        const int nb = std::min(MP_NB, n - k0), rest = n - k0 - nb;
-        hipLaunchKernelGGL(k_mt_trsv_diag<false>, dim3(1), dim3(64), 0, ctx->stream, n, k0, nb, Wd, y);
-        if (rest > 0)
-          hipLaunchKernelGGL(k_mt_fwd_upd, dim3((unsigned)((rest + MP_TB / 32 - 1) / (MP_TB / 32))), dim3(MP_TB), 0, ctx->stream, n, k0, nb, Wd, y);
-      }
-      for (int k0 = ((n - 1) / MP_NB) * MP_NB; k0 >= 0; k0 -= MP_NB) {
-        const int nb = std::min(MP_NB, n - k0);
-        hipLaunchKernelGGL(k_mt_trsv_diag<true>, dim3(1), dim3(64), 0, ctx->stream, n, k0, nb, Wd, y);
-        if (k0 > 0) hipLaunchKernelGGL(k_mt_bwd_upd, dim3((unsigned)((k0 + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, n, k0, nb, Wd, y);
-      }
-      hipLaunchKernelGGL(k_mt_logdet_norm, dim3(2), dim3(MP_TB), 0, ctx->stream, n, Wd, y, sc + MT_LDA, sc + MT_XN);
+      if ((rc = dz_mt_solve(ctx, n, Wd, y)) || (rc = dz_mt_logdet_norm(ctx, n, Wd, y, sc + MT_LDA, sc + MT_XN))) return rc;
       if (gdata > 0) {
         hipLaunchKernelGGL(k_mt_rows<false>, dim3((unsigned)((gdata + MP_TB / 64 - 1) / (MP_TB / 64))), dim3(MP_TB), 0, ctx->stream, (int64_t)0, m_data,
                            maxvp, A->rowptr, A->col, A->val, y, bb.dev, part);
-        hipLaunchKernelGGL(k_mt_sum, dim3(1), dim3(MP_TB), 0, ctx->stream, gdata, 3, (int64_t)1, part, sc + MT_CHI2);
+        if ((rc = dz_mt_sum(ctx, 1, gdata, 3, 1, part, sc + MT_CHI2))) return rc;
       }
       if (greg > 0) {
         hipLaunchKernelGGL(k_mt_rows<true>, dim3((unsigned)((greg + MP_TB / 64 - 1) / (MP_TB / 64))), dim3(MP_TB), 0, ctx->stream, m_data, mreg, maxvp,
                            A->rowptr, A->col, A->val, y, (const float *)nullptr, part);
-        hipLaunchKernelGGL(k_mt_sum, dim3((unsigned)nblk), dim3(MP_TB), 0, ctx->stream, greg, 3, (int64_t)1, part, sc + MT_REG2);
+        if ((rc = dz_mt_sum(ctx, nblk, greg, 3, 1, part, sc + MT_REG2))) return rc;
       }
       if (xo.dev) hipLaunchKernelGGL(k_mt_xout, dim3(nvb), dim3(MP_TB), 0, ctx->stream, n, y, fl, xo.dev + (size_t)k * n);
       DZ_HIP(hipGetLastError());
@@ -387,9 +417,7 @@ extern "C" int dazim_model_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t 
       double s3[3] = {0, 0, 0};
       if ((rc = dz_mp_inverse_c(ctx, n, Wd, Cd, mfma, lapname, s3))) return rc;
       DzTimer t(ctx, lapname);
-      hipLaunchKernelGGL(k_mt_rowdot, dim3((unsigned)n), dim3(MP_TB), 0, ctx->stream, n, Cd, Dd, rowdot);
-      hipLaunchKernelGGL(k_mt_sum, dim3((unsigned)nblk), dim3(MP_TB), 0, ctx->stream, (int64_t)maxvp, 1, (int64_t)maxvp, rowdot, sc + MT_DOF);
-      DZ_HIP(hipGetLastError());
+      if ((rc = dz_mt_rowdot(ctx, n, Cd, Dd, rowdot)) || (rc = dz_mt_sum(ctx, nblk, maxvp, 1, maxvp, rowdot, sc + MT_DOF))) return rc;
       lap(3, t);
       sec[3] += s3[1] + s3[2];
     }
@@ -403,8 +431,7 @@ extern "C" int dazim_model_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t 
       }
       if ((rc = dz_mp_factor(ctx, n, Wd, fl + 1, mfma, lapname, sec + 1))) return rc;
       DzTimer t(ctx, lapname);
-      hipLaunchKernelGGL(k_mt_logdet_norm, dim3(1), dim3(MP_TB), 0, ctx->stream, n, Wd, (const double *)nullptr, sc + MT_LDP, (double *)nullptr);
-      DZ_HIP(hipGetLastError());
+      if ((rc = dz_mt_logdet_norm(ctx, n, Wd, nullptr, sc + MT_LDP, nullptr))) return rc;
       lap(1, t);
     }
     hipLaunchKernelGGL(k_mt_final, dim3(1), dim3(1), 0, ctx->stream, k, nblk, m_data, s, d2, want_dof, want_evidence, fl, sc, out);

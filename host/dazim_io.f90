@@ -8,7 +8,7 @@ module dazim_io
   private
   public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
   public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
-  public :: write_resolution, uncertainty_weights, tradeoff_factor, write_tradeoff
+  public :: write_resolution, uncertainty_weights, tradeoff_factor, write_tradeoff, write_map_tradeoff
 
   real, parameter :: pi = 3.1415926535898
   real*8, parameter :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
@@ -303,6 +303,46 @@ contains
         else
           write (outs(q), '(a,i2,4a,i4,a,es12.4)') ' tradeoff sweep', sweep, ' (', label, '): ', trim(what(which))//' at point', idx(which) + 1, &
             ', factor', tradeoff_factor(idx(which) + 1, npoint)
+        end if
+      end do
+    end do
+  end subroutine
+
+  ! one sweep and one period of dazim_map_tradeoff into map_tradeoff.dat (unit u, open) and the program's log (unit ulog) and stdout;
+  ! per = 0: the totals over the periods (dazim_map_tradeoff_total; reg2, xnorm2 and dof summed over the periods by the caller).  A
+  ! line per point: sweep id, period (1-based; 0 for the totals), factor, the effective weights scale*weight per block and the
+  ! damping, m_p, chi2, reg2 per block, xnorm2, dof per block, gcv, logev.  Then three lines name the points (1-based, in the file's
+  ! order; `none` for -1) that dazim_tradeoff_pick chose: corner, igcv, iev are its 0-based indices.
+  subroutine write_map_tradeoff(u, ulog, sweep, label, per, tper, npoint, nblk, weights, scale, damp, mp, chi2, reg2, xnorm2, dof, gcv, logev, &
+                                corner, igcv, iev)
+    integer, intent(in) :: u, ulog, sweep, per, npoint, nblk, corner, igcv, iev
+    character(len=*), intent(in) :: label
+    real*8, intent(in) :: tper
+    integer(8), intent(in) :: mp
+    real, intent(in) :: weights(nblk), scale(nblk, npoint), damp(npoint)
+    real*8, intent(in) :: chi2(npoint), reg2(nblk, npoint), xnorm2(npoint), dof(nblk, npoint), gcv(npoint), logev(npoint)
+    integer :: k, q, which, idx(3), outs(2)
+    character(len=16), parameter :: what(3) = [character(len=16) :: 'L-curve corner', 'GCV minimum', 'evidence maximum']
+    character(len=64) :: fmt, where
+    write (fmt, '(a,i0,a)') '(i3,i5,', nblk + 2, 'es16.7e3,i10,30es16.7e3)'
+    do k = 1, npoint
+      write (u, fmt) sweep, per, tradeoff_factor(k, npoint), scale(:, k)*weights, damp(k), mp, chi2(k), reg2(:, k), xnorm2(k), dof(:, k), &
+        gcv(k), logev(k)
+    end do
+    if (per == 0) then
+      where = 'all periods'
+    else
+      write (where, '(a,i3,a,f8.2,a)') 'period', per, ' (', tper, ' s)'
+    end if
+    idx = [corner, igcv, iev]
+    outs = [6, ulog]
+    do q = 1, 2
+      do which = 1, 3
+        if (idx(which) < 0) then
+          write (outs(q), '(a,i2,6a)') ' map tradeoff sweep', sweep, ' (', label, '), ', trim(where), ': ', trim(what(which))//' none'
+        else
+          write (outs(q), '(a,i2,6a,i4,a,es12.4)') ' map tradeoff sweep', sweep, ' (', label, '), ', trim(where), ': ', &
+            trim(what(which))//' at point', idx(which) + 1, ', factor', tradeoff_factor(idx(which) + 1, npoint)
         end if
       end do
     end do

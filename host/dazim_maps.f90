@@ -1,7 +1,7 @@
 ! dazim_maps.f90 -- SurfPhaseMaps_amd: per-period Rayleigh phase-velocity maps and 2-psi anisotropy maps inverted from the data of
 ! the 3-D inversion program, period by period in one system, on one MI355X.
 !
-!   SurfPhaseMaps_amd para.in [weight_c [weight_a [uncertainty]]]
+!   SurfPhaseMaps_amd para.in [weight_c [weight_a [uncertainty [tradeoff]]]]
 !
 ! Inputs: the unchanged para.in, traveltime data file and MOD of DAzimSurfTomo_amd (the same readers, module dazim_io:
 ! read_para, read_data, read_mod).  Starting maps: MOD's dispersion curves (dazim_dispersion_kernels without kernels), the 3-D
@@ -29,6 +29,14 @@
 !                            per inner vertex and period in period_phaseV_map.dat's order
 !   log: per period trace(Rm) / ncell per block, the median std_post of c and (iso-mode F) the median leak of c; the periods that
 !                            could not be factored
+! tradeoff = K >= 3 (default 0: as without the argument): which weight_c and weight_a, per period and for all periods together.  On the
+! last iteration's [W G; L] and weighted right-hand side, dazim_map_tradeoff at the K factors 10^(-1 + 2k/(K-1)), k = 0 .. K-1, on
+! weight_c and weight_a together with para.in's damping, and in iso-mode F a second sweep on weight_a alone (c at factor 1); both
+! sweeps are the points of one call.  The maps the program inverts with do not change.
+!   map_tradeoff.dat       per sweep, period and point: sweep, period, factor, the effective weights per block and the damping, m_p,
+!                          chi2, |L x|^2 per block (the rows without their weight), |x|^2, tr(Rm) per block, GCV, log evidence; after a
+!                          sweep's periods its totals over the periods (dazim_map_tradeoff_total), with period 0
+!   log + stdout: per sweep and period, and for the totals, the L-curve corner, the GCV minimum and the evidence maximum
 program SurfPhaseMaps_amd
   use iso_c_binding
   use dazim_mod
@@ -59,11 +67,12 @@ program SurfPhaseMaps_amd
   integer :: iunc
   integer(c_int) :: nbad
   real, allocatable, target :: upost(:, :), utrace(:, :)
+  integer :: itrade                          ! tradeoff = K
 
   write (*, *)
   write (*, *) '                       SurfPhaseMaps'
   write (*, *)
-  if (command_argument_count() < 1) stop 'usage: SurfPhaseMaps_amd para.in [weight_c [weight_a [uncertainty]]]'
+  if (command_argument_count() < 1) stop 'usage: SurfPhaseMaps_amd para.in [weight_c [weight_a [uncertainty [tradeoff]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) stop 'unable to open the inputfile'
@@ -83,6 +92,13 @@ program SurfPhaseMaps_amd
     error stop 'bad argument'
   end if
   if (iunc == 1 .and. maxiter < 1) error stop 'uncertainty = 1 needs at least one iteration'
+  itrade = 0
+  call optional_arg(5, itrade)
+  if (itrade /= 0 .and. itrade < 3) then
+    write (*, '(a,i6)') ' ERROR: tradeoff is 0 or the number of sweep points, at least 3; it is', itrade
+    error stop 'bad tradeoff argument'
+  end if
+  if (itrade > 0 .and. maxiter < 1) error stop 'tradeoff > 0 needs at least one iteration'
   write (logfile, '(a,a)') trim(inputfile), '_map.log'
   open (66, file=logfile)
   write (66, *)
@@ -148,6 +164,7 @@ program SurfPhaseMaps_amd
                                            merge(c_null_ptr, c_loc(upost(:, 6)), iso_mod), 0_c_int, c_null_ptr, c_null_ptr, &
                                            c_loc(utrace), nbad), 'map posterior')
     end if
+    if (itrade > 0 .and. iter == maxiter) call tradeoff_sweeps()
     call dazim_check(dazim_phase_map_update(dazim_handle, nx, ny, kmax, merge(0_c_int, 1_c_int, iso_mod), pv, dm, minc, maxc, &
                                             a1, a2, ustats), 'map update')
     ! residual after: the data rows (weighted by datweight) times the applied update, unweighted again
@@ -234,6 +251,56 @@ program SurfPhaseMaps_amd
   call dazim_finalize()
 
 contains
+
+  ! map_tradeoff.dat and the log's lines: dazim_map_tradeoff on this iteration's [W G; L] and weighted right-hand side cbst (the
+  ! regularisation rows of G hold weight_c and weight_a, so the sweep's scale is the factor itself), before the matrix is freed.  The
+  ! sweeps are the points of ONE call, sweep after sweep, so the Gram matrix of a period's data rows is formed once for both.
+  subroutine tradeoff_sweeps()
+    integer :: nsw, npt, s, k1, p0, p1, t2
+    integer(c_int) :: corner, igcv, iev
+    real, allocatable :: tscale(:, :), tdamp(:), tw(:)
+    integer(c_int64_t), allocatable :: tmp(:)
+    real(c_double), allocatable :: tchi2(:, :), treg2(:, :, :), txn(:, :), tlda(:, :), tldp(:, :), tdof(:, :, :), tgcv(:, :), tlev(:, :)
+    real(c_double), allocatable :: tsum(:), schi2(:), ssum(:), sdof(:), sgcv(:), slev(:)
+    integer(c_int), allocatable :: tbad(:, :)
+    nsw = merge(1, 2, iso_mod)
+    npt = nsw*itrade
+    allocate (tscale(nblk, npt), tdamp(npt), tw(nblk), tmp(kmax), tchi2(kmax, npt), treg2(nblk, kmax, npt), txn(kmax, npt), tlda(kmax, npt), &
+              tldp(kmax, npt), tdof(nblk, kmax, npt), tgcv(kmax, npt), tlev(kmax, npt), tbad(kmax, npt), tsum(npt), schi2(npt), ssum(npt), &
+              sdof(npt), sgcv(npt), slev(npt))
+    tw(1) = weight_c
+    if (nblk == 3) tw(2:3) = weight_a
+    tdamp = damp
+    do s = 1, nsw
+      do k1 = 1, itrade
+        tscale(:, (s - 1)*itrade + k1) = tradeoff_factor(k1, itrade)
+        if (s == 2) tscale(1, itrade + k1) = 1.0
+      end do
+    end do
+    call dazim_check(dazim_map_tradeoff(dazim_handle, G, int(dall, c_int64_t), cbst, nx, ny, kmax, merge(0_c_int, 1_c_int, iso_mod), &
+                                        int(npt, c_int), tscale, tdamp, 1_c_int, 1_c_int, tmp, tchi2, treg2, txn, tlda, tldp, tdof, tgcv, &
+                                        tlev, c_null_ptr, tbad), 'map tradeoff')
+    call dazim_check(dazim_map_tradeoff_total(int(npt, c_int), int(kmax, c_int), int(nblk, c_int), tmp, tchi2, treg2, tdof, tlev, schi2, &
+                                              ssum, sdof, sgcv, slev), 'map tradeoff totals')
+    open (45, file='map_tradeoff.dat', status='replace', action='write')
+    do s = 1, nsw
+      p0 = (s - 1)*itrade + 1; p1 = s*itrade
+      do t2 = 1, kmax
+        tsum(p0:p1) = sum(treg2(:, t2, p0:p1), dim=1)
+        call dazim_check(dazim_tradeoff_pick(int(itrade, c_int), tchi2(t2, p0:p1), tsum(p0:p1), tgcv(t2, p0:p1), tlev(t2, p0:p1), corner, &
+                                             igcv, iev), 'tradeoff pick')
+        call write_map_tradeoff(45, 66, s, trim(merge('all blocks', 'a1 and a2 ', s == 1)), t2, tRc(t2), itrade, nblk, tw, tscale(:, p0:p1), &
+                                tdamp(p0:p1), int(tmp(t2), 8), tchi2(t2, p0:p1), treg2(:, t2, p0:p1), txn(t2, p0:p1), tdof(:, t2, p0:p1), &
+                                tgcv(t2, p0:p1), tlev(t2, p0:p1), int(corner), int(igcv), int(iev))
+      end do
+      call dazim_check(dazim_tradeoff_pick(int(itrade, c_int), schi2(p0:p1), ssum(p0:p1), sgcv(p0:p1), slev(p0:p1), corner, igcv, iev), &
+                       'tradeoff pick')
+      call write_map_tradeoff(45, 66, s, trim(merge('all blocks', 'a1 and a2 ', s == 1)), 0, 0d0, itrade, nblk, tw, tscale(:, p0:p1), &
+                              tdamp(p0:p1), int(sum(tmp), 8), schi2(p0:p1), sum(treg2(:, :, p0:p1), dim=2), sum(txn(:, p0:p1), dim=1), &
+                              sum(tdof(:, :, p0:p1), dim=2), sgcv(p0:p1), slev(p0:p1), int(corner), int(igcv), int(iev))
+    end do
+    close (45)
+  end subroutine
 
   ! the median of v (the lower of the two middle values for an even count), by a Shell sort of a copy
   real function median(v)

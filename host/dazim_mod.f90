@@ -33,7 +33,8 @@ module dazim_mod
             dazim_shard_fields, dazim_shard_rows, dazim_allsum
   ! the per-period map inversion (host/dazim_maps.f90)
   public :: dazim_dispersion_kernels, dazim_rays_build_G_maps, dazim_csr_append_laplacian2d, dazim_phase_map_update, &
-            dazim_assemble_G_maps, dazim_map_posterior, dazim_model_posterior, dazim_model_tradeoff, dazim_tradeoff_pick
+            dazim_assemble_G_maps, dazim_map_posterior, dazim_model_posterior, dazim_model_tradeoff, dazim_tradeoff_pick, &
+            dazim_map_tradeoff, dazim_map_tradeoff_total
   ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
   public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq, dazim_column_resolution
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
@@ -397,6 +398,27 @@ module dazim_mod
       real(c_float) :: b(*), scale(*), damp(*)
       real(c_double) :: chi2(*), reg2(*), xnorm2(*), logdet_a(*), logdet_p(*), dof(*), gcv(*), logev(*)
       integer(c_int) :: n_failed(*)
+    end function
+    ! scale [nblk, npoint]; chi2, xnorm2, logdet_a, logdet_p, gcv, logev, n_failed [kmax, npoint]; reg2, dof [nblk, kmax, npoint] (the C
+    ! layouts of include/dazim.h); x: c_loc of [n, npoint] or c_null_ptr
+    integer(c_int) function dazim_map_tradeoff(ctx, A, m_data, b, nx, ny, kmax, azim, npoint, scale, damp, want_dof, want_evidence, mdata_p, &
+        chi2, reg2, xnorm2, logdet_a, logdet_p, dof, gcv, logev, x, n_failed) bind(C, name="dazim_map_tradeoff")
+      import
+      type(c_ptr), value :: ctx, A, x
+      integer(c_int64_t), value :: m_data
+      integer(c_int), value :: nx, ny, kmax, azim, npoint, want_dof, want_evidence
+      real(c_float) :: b(*), scale(*), damp(*)
+      integer(c_int64_t) :: mdata_p(*)
+      real(c_double) :: chi2(*), reg2(*), xnorm2(*), logdet_a(*), logdet_p(*), dof(*), gcv(*), logev(*)
+      integer(c_int) :: n_failed(*)
+    end function
+    ! the sums over the periods [npoint] of dazim_map_tradeoff's arrays, and the GCV of the whole system (host only)
+    integer(c_int) function dazim_map_tradeoff_total(npoint, kmax, nblk, mdata_p, chi2, reg2, dof, logev, chi2_t, reg2sum_t, dof_t, gcv_t, &
+        logev_t) bind(C, name="dazim_map_tradeoff_total")
+      import
+      integer(c_int), value :: npoint, kmax, nblk
+      integer(c_int64_t) :: mdata_p(*)
+      real(c_double) :: chi2(*), reg2(*), dof(*), logev(*), chi2_t(*), reg2sum_t(*), dof_t(*), gcv_t(*), logev_t(*)
     end function
     ! corner, igcv, iev: 0-based indices, -1 for none
     integer(c_int) function dazim_tradeoff_pick(npoint, chi2, reg2sum, gcv, logev, corner, igcv, iev) bind(C, name="dazim_tradeoff_pick")

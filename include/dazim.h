@@ -299,6 +299,54 @@ int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int 
                         float *std_post, float *std_noise, float *rdiag, float *rsum, float *width, float *leak, int nsel,
                         const int *sel, float *rows, float *trace, int *n_failed);
 
+/* dazim_map_tradeoff: the maps' linearised step solved exactly at K regularisation strengths, per period, with what an L-curve,
+ * generalised cross-validation and the Bayesian evidence need at each.  A, m_data, nx, ny, kmax, azim, the
+ * column layout and nblk are dazim_map_posterior's: a row touches one period only and its columns ascend strictly.  Every
+ * regularisation row lies in one block (c, a1 or a2).  b [m_data] (host or device) is the weighted right-hand side of the data rows,
+ * as dazim_lsmr is given it; the regularisation rows have right-hand side 0.
+ *   scale [K][nblk], damp [K] (host): point k multiplies the stored regularisation rows of block blk by scale[k][blk], in every
+ *   period, and damps with damp[k].  Per period p and point k, with the local index a = blk*ncell + cell and m_p data rows in p:
+ *     D_p = sum_{data rows of p} r^T r    R_pb = sum_{regularisation rows of p in block b} l^T l    g_p = sum_{data rows of p} r^T b_r
+ *     P = sum_b scale[k][b]^2 R_pb + damp[k]^2 I        A = D_p + P = R R^T        x = A^-1 g_p (forward and back substitution)
+ *   Outputs (host or device; [K][kmax] unless noted):
+ *     mdata_p [kmax] (nullable)  m_p
+ *     chi2      |G_p x - b_p|^2 over the period's data rows     reg2 [K][kmax][nblk]  |L_pb x|^2, the rows as stored (unscaled)
+ *     xnorm2    |x|^2                                            logdet_a              2 sum_i log R_ii
+ *     logdet_p  (nullable; want_evidence) the same from a second factorisation, of P alone; NaN when P has a pivot that is not
+ *               finite and > 0, which does not count as a failure
+ *     dof [K][kmax][nblk] (nullable; want_dof)  sum_{a in block b} sum_c C_ac D_ac, C = A^-1: block b's share of tr(Rm)
+ *     gcv       (nullable; want_dof)      m_p chi2 / (m_p - sum_b dof[b])^2
+ *     logev     (nullable; want_evidence) -(chi2 + J)/2 + logdet_p/2 - logdet_a/2 - m_p log(2 pi)/2, J = sum_b scale[k][b]^2 reg2[b]
+ *               + damp[k]^2 xnorm2
+ *     x [K][n] fp32 (nullable)            the layout of dm, each value rounded once
+ *   A (point, period) whose A meets a pivot that is not finite and > 0 has NaN in every output and n_failed[k][p] (host, [K][kmax],
+ *   nullable) = 1, else 0; no other point and no other period is affected.  A period without data rows follows the formulas: x = 0,
+ *   chi2 = 0, dof = 0.
+ *   Arithmetic: fp64, every sum in a fixed order set by the problem alone, no floating-point atomics.  D_p is formed once per period
+ *   and call, by dazim_map_posterior's Gram kernel on the period's data rows; a point's work matrix is D_p's row, then the period's
+ *   regularisation rows in ascending row order, each product times the squared scale of the row's block, then damp^2 on the diagonal:
+ *   at scale 1 and dazim_map_posterior's damp, its numbers added in its order.  The factorisation, and with want_dof the inverse and
+ *   C, are its kernels (option map_post.mfma); the substitutions and fixed-order sums are dazim_model_tradeoff's.  Two calls give the
+ *   same bits, host and device arguments give the same bits, and a point gives the same bits alone as at any position of any sweep.
+ *   Refused (DAZIM_E_BAD_ARG, nothing written): what dazim_map_posterior refuses of A, m_data, nx, ny, kmax and n; K < 1; a missing b,
+ *   scale, damp, chi2, reg2, xnorm2 or logdet_a; a negative or non-finite scale or damp; dof or gcv without want_dof; logdet_p or
+ *   logev without want_evidence; a row in two periods or with columns that do not ascend strictly, a regularisation row in two
+ *   blocks (found on the device); and a workspace the card's free memory cannot hold (the message names the GiB needed): D_p, the
+ *   work matrix and with want_dof C, n_g x n_g fp64 each, allocated for the call and released before it returns.  There is no row
+ *   pass, so dazim_map_posterior's LDS bound on n_g does not apply.
+ *   Stats: "map_tradeoff" and its parts "map_trade.gram", ".factor", ".solve", ".inverse" (seconds, summed over periods and points),
+ *   "map_trade.points" (K), "map_trade.ng", "map_trade.grams" (the Gram passes of the call: kmax, whatever K).
+ * dazim_map_tradeoff_total (host only): the criteria of the whole block-diagonal system, for one weight on all periods.  Every total
+ *   [K] is the sum over the periods in ascending p (reg2sum_t and dof_t over p and then blk); gcv_t = M chi2_t / (M - dof_t)^2 with
+ *   M = sum_p m_p.  dof, logev and their outputs are nullable; a NaN period makes that point's totals NaN. */
+int dazim_map_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, const float *b, int nx, int ny, int kmax, int azim, int K,
+                       const float *scale, const float *damp, int want_dof, int want_evidence, int64_t *mdata_p, double *chi2,
+                       double *reg2, double *xnorm2, double *logdet_a, double *logdet_p, double *dof, double *gcv, double *logev,
+                       float *x, int *n_failed);
+int dazim_map_tradeoff_total(int K, int kmax, int nblk, const int64_t *mdata_p, const double *chi2, const double *reg2,
+                             const double *dof, const double *logev, double *chi2_t, double *reg2sum_t, double *dof_t, double *gcv_t,
+                             double *logev_t);
+
 /* dazim_model_posterior: how well the model of the direct 3-D inversion is known, per block (dVs, Gc, Gs), knot and inner cell, from the
  * matrix dazim_lsmr is given in an outer iteration.  The exact regularised solution of that linearised step is
  * what it describes; LSMR stopped at itnlim approximates that solution.
