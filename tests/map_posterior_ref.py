@@ -70,6 +70,65 @@ def problem(nx, ny, kmax, azim, smooth, damp, seed=0, rays_per_period=None, no_r
                 irow=(r + 1).astype(np.int32), icol=(c + 1).astype(np.int32), rw=v, dead=ncell - 1 if ncell > 1 else None)
 
 
+# ---- rows longer than one stride of the device loops (tests/test_long_rows_*.py) ----
+LONG_DATA_LENS = (63, 64, 65, 127, 128, 129, 200)          # both sides of one and two strides of 64 in mp_accum_rows, and a fourth stride
+LONG_REG_LENS = (7, 8, 9, 63, 64, 65, 66)                  # both sides of MP_EMAX = 8 in k_mp_rows and of a stride of 64
+LONG_SHAPES = {False: (17, 16), True: (12, 9)}             # n_g = 210: one block of 210, three of 70
+LONG_KMAX = 2
+LONG_REG_ROWS = 257                                        # period 0 gets the list again and again up to a second batch of MP_TB = 256
+
+
+def long_rows(nx, ny, kmax, azim, smooth, damp, data_lens, reg_lens, seed=0, through_dead=False):
+    """`problem` with more rows, of exactly the lengths given per period (data_lens[p], reg_lens[p]): data rows behind the data rows,
+    period by period (columns of one period, distinct and ascending, drawn over all blocks without the dead cell, values uniform in
+    +-3 / sqrt(len)), and regularisation rows behind the regularisation rows (row i of a period inside block i mod nblk, values
+    uniform in +-max(smooth, 0.3) / sqrt(len); they are there for smooth = 0 too).  through_dead: added data row i of a period holds
+    the dead cell's column of block i mod nblk, which no other data row does.  Triplets 1-based, sorted by (row, column)."""
+    prob = problem(nx, ny, kmax, azim, smooth, damp, seed=seed)
+    rng = np.random.default_rng(seed + 1000003)
+    ncell, nblk = (nx - 2) * (ny - 2), 3 if azim else 1
+    kn, dead, md0 = kmax * ncell, prob["dead"], prob["m_data"]
+    glob = lambda p, loc: (loc // ncell) * kn + p * ncell + loc % ncell     # (ascends with the local index blk * ncell + cell)
+    live = np.flatnonzero(np.arange(nblk * ncell) % ncell != dead)
+    nd = sum(len(l) for l in data_lens)
+    r, c, v = prob["irow"].astype(np.int64) - 1, prob["icol"].astype(np.int64) - 1, prob["rw"]
+    r = np.where(r >= md0, r + nd, r)
+    rs, cs, vs = [r], [c], [v]
+    row = md0
+    for p in range(kmax):
+        for i, ln in enumerate(data_lens[p]):
+            if through_dead:
+                loc = np.sort(np.append(rng.choice(live, size=ln - 1, replace=False), (i % nblk) * ncell + dead))
+            else:
+                loc = np.sort(rng.choice(live, size=ln, replace=False))
+            rs.append(np.full(ln, row))
+            cs.append(glob(p, loc))
+            vs.append((rng.uniform(-3.0, 3.0, ln) / np.sqrt(ln)).astype(np.float32))
+            row += 1
+    row = prob["m"] + nd
+    for p in range(kmax):
+        for i, ln in enumerate(reg_lens[p]):
+            rs.append(np.full(ln, row))
+            cs.append(glob(p, (i % nblk) * ncell + np.sort(rng.choice(ncell, size=ln, replace=False))))
+            vs.append((rng.uniform(-1.0, 1.0, ln) * max(smooth, 0.3) / np.sqrt(ln)).astype(np.float32))
+            row += 1
+    r, c, v = np.concatenate(rs), np.concatenate(cs), np.concatenate(vs)
+    order = np.lexsort((c, r))
+    prob.update(m=row, m_data=md0 + nd, irow=(r[order] + 1).astype(np.int32), icol=(c[order] + 1).astype(np.int32), rw=v[order])
+    return prob
+
+
+def long_case(azim, reg, through_dead=False):
+    """the long-row problem of the tests: LONG_SHAPES at LONG_KMAX periods, six data rows of each of LONG_DATA_LENS per period;
+    LONG_REG_LENS once per period, and in period 0 as often as brings its regularisation rows to LONG_REG_ROWS or more"""
+    nx, ny = LONG_SHAPES[azim]
+    base = (3 if azim else 1) * (nx - 2) * (ny - 2) if reg[0] > 0 else 0
+    reps = [max(1, -(-(LONG_REG_ROWS - base) // len(LONG_REG_LENS)))] + [1] * (LONG_KMAX - 1)
+    data = [tuple(l for l in LONG_DATA_LENS for _ in range(6))] * LONG_KMAX
+    return long_rows(nx, ny, LONG_KMAX, azim, reg[0], reg[1], data, [LONG_REG_LENS * k for k in reps], seed=nx * 100 + ny + 7 * azim + LONG_KMAX,
+                     through_dead=through_dead)
+
+
 def groups(prob):
     """per period: D, the regularisation rows (dense, in ascending row order) in the local index blk*ncell + cell; the number of data rows"""
     nvx, nvy, kmax = prob["nx"] - 2, prob["ny"] - 2, prob["kmax"]

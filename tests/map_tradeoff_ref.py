@@ -33,6 +33,12 @@ def with_rhs(prob, seed):
     return prob
 
 
+def long_case(azim, reg, **kw):
+    """mref.long_case with a right-hand side"""
+    nx, ny = mref.LONG_SHAPES[azim]
+    return with_rhs(mref.long_case(azim, reg, **kw), seed_of(nx, ny, azim, mref.LONG_KMAX) + 12345)
+
+
 def without_data(prob, period):
     """the problem without the data rows of one period: their triplets are removed, the rows stay (empty) and keep their b"""
     ncell = (prob["nx"] - 2) * (prob["ny"] - 2)
@@ -41,12 +47,12 @@ def without_data(prob, period):
     return dict(prob, irow=prob["irow"][keep], icol=prob["icol"][keep], rw=prob["rw"][keep])
 
 
-def sweep(prob):
+def sweep(prob, damp_factors=DAMP_FACTORS):
     """(scale [K][nblk], damp [K]) fp32: every scale on all blocks, with azim also on the a1/a2 blocks alone, crossed with the
     damping factors; the common-factor points of one damping factor are consecutive and ascend"""
     nblk = 3 if prob["azim"] else 1
     sc, dm = [], []
-    for f in DAMP_FACTORS:
+    for f in damp_factors:
         for s in SCALES:
             sc.append([s] * nblk)
             dm.append(f * prob["damp"])

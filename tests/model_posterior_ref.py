@@ -78,6 +78,70 @@ def problem(nx, ny, nz, joint, smooth, damp, seed=0, nray=None):
                 dead=ncell - 1 if ncell > 1 else None)
 
 
+# ---- rows longer than one pass of the device loops (tests/test_long_rows_*.py) ----
+# both sides of one and two passes of mo_accum_row (64 * MO_UN = 256 entries a pass), and 300: a second pass with padding lanes
+LONG_LENS = (255, 256, 257, 300, 511, 512, 513)
+LONG_REG_SHORT = (7, 8, 9, 63, 64, 65)
+LONG_SHAPES = {False: (13, 12, 6), True: (10, 9, 6)}       # iso n = 550, one block; joint n = 840, blocks of 280
+LONG_DATA = tuple(l for l in LONG_LENS for _ in range(12))
+LONG_REG = {False: tuple(l for l in LONG_LENS for _ in range(2)) + LONG_REG_SHORT,
+            True: tuple(l for l in LONG_LENS if l <= 257 for _ in range(2)) + LONG_REG_SHORT}
+
+
+def long_rows(nx, ny, nz, joint, smooth, damp, data_lens, reg_lens, seed=0):
+    """`problem` with more rows, of exactly the lengths given: data rows behind the data rows (columns distinct and ascending, drawn
+    over all blocks without the dead cell, values uniform in +-3 / sqrt(len)), and regularisation rows behind the regularisation rows
+    (row i inside block i mod nblk, values uniform in +-max(smooth, 0.3) / sqrt(len); they are there for smooth = 0 too).  Every added
+    data row holds the column prob["hub"]: the live column most of `problem`'s data rows hold, so that one column of the transpose is
+    long as well.  The added rows do not depend on smooth and damp but for that factor.  Triplets 1-based, sorted by (row, column)."""
+    prob = problem(nx, ny, nz, joint, smooth, damp, seed=seed)
+    rng = np.random.default_rng(seed + 1000003)
+    nvx, nvy, nlay, nblk, ncell, n = dims(prob)
+    maxvp = ncell * nlay
+    md0 = prob["m_data"]
+    r, c, v = prob["irow"].astype(np.int64) - 1, prob["icol"].astype(np.int64) - 1, prob["rw"]
+    live = np.flatnonzero(np.arange(n) % ncell != prob["dead"])
+    hub = int(np.argmax(np.bincount(c[r < md0], minlength=n)))
+    rest = live[live != hub]
+    r = np.where(r >= md0, r + len(data_lens), r)
+    rs, cs, vs = [r], [c], [v]
+    for i, ln in enumerate(data_lens):
+        rs.append(np.full(ln, md0 + i))
+        cs.append(np.sort(np.append(rng.choice(rest, size=ln - 1, replace=False), hub)))
+        vs.append((rng.uniform(-3.0, 3.0, ln) / np.sqrt(ln)).astype(np.float32))
+    m = prob["m"] + len(data_lens)
+    for i, ln in enumerate(reg_lens):
+        rs.append(np.full(ln, m + i))
+        cs.append((i % nblk) * maxvp + np.sort(rng.choice(maxvp, size=ln, replace=False)))
+        vs.append((rng.uniform(-1.0, 1.0, ln) * max(smooth, 0.3) / np.sqrt(ln)).astype(np.float32))
+    r, c, v = np.concatenate(rs), np.concatenate(cs), np.concatenate(vs)
+    order = np.lexsort((c, r))
+    prob.update(m=m + len(reg_lens), m_data=md0 + len(data_lens), hub=hub, irow=(r[order] + 1).astype(np.int32),
+                icol=(c[order] + 1).astype(np.int32), rw=v[order])
+    return prob
+
+
+def long_case(joint, reg):
+    """the long-row problem of the tests: LONG_SHAPES, twelve data rows of each of LONG_LENS, LONG_REG"""
+    nx, ny, nz = LONG_SHAPES[joint]
+    return long_rows(nx, ny, nz, joint, reg[0], reg[1], LONG_DATA, LONG_REG[joint], seed=nx * 10000 + ny * 100 + nz + 7 * joint)
+
+
+def truncated(prob, keep, reg_only=False):
+    """the problem without the entries behind the first `keep` of every row (reg_only: of every regularisation row): what a row
+    walk that stops after `keep` entries would see"""
+    row = prob["irow"].astype(np.int64) - 1
+    first = np.searchsorted(row, row, side="left")            # (the triplets are sorted by row)
+    on = (np.arange(len(row)) - first < keep) | ((row < prob["m_data"]) if reg_only else False)
+    return dict(prob, irow=prob["irow"][on], icol=prob["icol"][on], rw=prob["rw"][on])
+
+
+def row_lengths(prob):
+    """(lengths of the data rows, lengths of the regularisation rows)"""
+    ln = np.bincount(prob["irow"].astype(np.int64) - 1, minlength=prob["m"])
+    return ln[:prob["m_data"]], ln[prob["m_data"]:]
+
+
 def parts(prob):
     """D = sum of r^T r over the data rows, and the regularisation rows (dense, in ascending row order)"""
     n = dims(prob)[5]

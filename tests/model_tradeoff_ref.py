@@ -19,19 +19,29 @@ def seed_of(shape, joint):
 def problem(shape, joint, reg):
     """model_posterior_ref's problem of this shape and regulariser (the generator and seed of its tests) and b [m_data] fp32"""
     prob = mref.problem(shape[0], shape[1], shape[2], joint, reg[0], reg[1], seed=seed_of(shape, joint))
+    return with_rhs(prob, seed_of(shape, joint) + 12345)
+
+
+def with_rhs(prob, seed):
+    """b [m_data] fp32 = G x_true + unit noise on a ready problem (of `problem`'s or of mref.long_rows')"""
     G = dense(prob)[:prob["m_data"]]
-    rng = np.random.default_rng(seed_of(shape, joint) + 12345)
+    rng = np.random.default_rng(seed)
     x_true = rng.standard_normal(prob["n"])
     prob["b"] = (G @ x_true + rng.standard_normal(prob["m_data"])).astype(np.float32)
     return prob
 
 
-def sweep(prob):
+def long_case(joint, reg):
+    """mref.long_case with a right-hand side"""
+    return with_rhs(mref.long_case(joint, reg), seed_of(mref.LONG_SHAPES[joint], joint) + 12345)
+
+
+def sweep(prob, damp_factors=DAMP_FACTORS):
     """(scale [K][nblk], damp [K]) fp32: every scale on all blocks, in joint mode also on the Gc/Gs blocks alone, crossed with the
     damping factors; the common-factor points of one damping factor are consecutive and ascend"""
     nblk = 3 if prob["joint"] else 1
     sc, dm = [], []
-    for f in DAMP_FACTORS:
+    for f in damp_factors:
         for s in SCALES:
             sc.append([s] * nblk)
             dm.append(f * prob["damp"])
