@@ -104,6 +104,24 @@ def map_tradeoff_total(mdata_p, chi2, reg2, dof=None, logev=None):
     return out
 
 
+def _tradeoff_args(m_data, b, nblk, scale, damp, dof, evidence, lead):
+    """what Context.model_tradeoff and Context.map_tradeoff pass alike: (K, scale [K][nblk] fp32, damp [K] fp32, b, out) with out the
+    fp64 outputs, [K] + lead (reg2 and dof: + [nblk]), None where dof or evidence is off"""
+    scale = np.asarray(scale, np.float32)
+    if scale.ndim == 1:
+        scale = np.repeat(scale[:, None], nblk, axis=1)
+    scale = np.ascontiguousarray(scale.reshape(-1, nblk))
+    K = scale.shape[0]
+    damp = np.ascontiguousarray(np.broadcast_to(np.asarray(damp, np.float32), (K,)))
+    if not _is_torch(b):
+        b = np.ascontiguousarray(b, np.float32)
+    assert b.shape[0] == m_data
+    new = lambda on, *tail: np.zeros((K,) + tuple(lead) + tail, np.float64) if on else None
+    out = dict(chi2=new(True), reg2=new(True, nblk), xnorm2=new(True), logdet_a=new(True), logdet_p=new(evidence), dof=new(dof, nblk),
+               gcv=new(dof), logev=new(evidence))
+    return K, scale, damp, b, out
+
+
 class Context:
     """One GPU context (`dazim_ctx`).  Raises if no GPU / no library: there is no CPU path."""
 
@@ -493,19 +511,9 @@ class Context:
         each [K], the sums over the periods (dazim_map_tradeoff_total); pick = per period dict(corner, gcv, evidence), the indices
         dazim_tradeoff_pick names (-1: none); pick_total the same from the totals."""
         nblk = 3 if azim else 1
-        scale = np.asarray(scale, np.float32)
-        if scale.ndim == 1:
-            scale = np.repeat(scale[:, None], nblk, axis=1)
-        scale = np.ascontiguousarray(scale.reshape(-1, nblk))
-        K = scale.shape[0]
-        damp = np.ascontiguousarray(np.broadcast_to(np.asarray(damp, np.float32), (K,)))
-        if not _is_torch(b):
-            b = np.ascontiguousarray(b, np.float32)
-        assert b.shape[0] == m_data
-        new = lambda *shape: np.zeros(shape, np.float64)
-        out = dict(mdata_p=np.zeros(kmax, np.int64), chi2=new(K, kmax), reg2=new(K, kmax, nblk), xnorm2=new(K, kmax), logdet_a=new(K, kmax),
-                   logdet_p=new(K, kmax) if evidence else None, dof=new(K, kmax, nblk) if dof else None, gcv=new(K, kmax) if dof else None,
-                   logev=new(K, kmax) if evidence else None, x=np.zeros((K, nblk, kmax, ny - 2, nx - 2), np.float32) if x else None)
+        K, scale, damp, b, out = _tradeoff_args(m_data, b, nblk, scale, damp, dof, evidence, (kmax,))
+        out["mdata_p"] = np.zeros(kmax, np.int64)
+        out["x"] = np.zeros((K, nblk, kmax, ny - 2, nx - 2), np.float32) if x else None
         nf = np.zeros((K, kmax), np.int32)
         f64 = lambda k: _ptr(out[k], np.float64)
         self._check(self.lib.dazim_map_tradeoff(self._h, A._h, C.c_int64(int(m_data)), _ptr(b, np.float32), nx, ny, int(kmax), int(bool(azim)), K,
@@ -565,19 +573,8 @@ class Context:
         unless dof); logdet_p and logev [K] (None unless evidence); x [K][nblk][nz-1][ny-2][nx-2] fp32 (None unless asked); n_failed
         [K] int32; pick = dict(corner, gcv, evidence), the indices dazim_tradeoff_pick names (-1: none)."""
         nblk = 3 if joint else 1
-        scale = np.asarray(scale, np.float32)
-        if scale.ndim == 1:
-            scale = np.repeat(scale[:, None], nblk, axis=1)
-        scale = np.ascontiguousarray(scale.reshape(-1, nblk))
-        K = scale.shape[0]
-        damp = np.ascontiguousarray(np.broadcast_to(np.asarray(damp, np.float32), (K,)))
-        if not _is_torch(b):
-            b = np.ascontiguousarray(b, np.float32)
-        assert b.shape[0] == m_data
-        new = lambda *shape: np.zeros(shape, np.float64)
-        out = dict(chi2=new(K), reg2=new(K, nblk), xnorm2=new(K), logdet_a=new(K), logdet_p=new(K) if evidence else None,
-                   dof=new(K, nblk) if dof else None, gcv=new(K) if dof else None, logev=new(K) if evidence else None,
-                   x=np.zeros((K, nblk, nz - 1, ny - 2, nx - 2), np.float32) if x else None)
+        K, scale, damp, b, out = _tradeoff_args(m_data, b, nblk, scale, damp, dof, evidence, ())
+        out["x"] = np.zeros((K, nblk, nz - 1, ny - 2, nx - 2), np.float32) if x else None
         nf = np.zeros(K, np.int32)
         f64 = lambda k: _ptr(out[k], np.float64)
         self._check(self.lib.dazim_model_tradeoff(self._h, A._h, C.c_int64(int(m_data)), _ptr(b, np.float32), nx, ny, nz, int(bool(joint)), K,

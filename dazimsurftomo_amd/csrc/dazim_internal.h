@@ -351,3 +351,39 @@ struct DzTimer {
     ctx->ksec[name] = ms * 1e-3;
   }
 };
+
+// the seconds of a call's parts, sec[0 .. count), published under names[] and their sum under `total`; the lap stat they were
+// measured under is erased
+static inline void dz_publish_laps(dazim_ctx *ctx, const char *lap, const char *const *names, const double *sec, int count, const char *total) {
+  ctx->ksec.erase(lap);
+  double sum = 0.0;
+  for (int i = 0; i < count; i++) {
+    ctx->ksec[names[i]] = sec[i];
+    sum += sec[i];
+  }
+  ctx->ksec[total] = sum;
+}
+
+// up to three device allocations that belong to one call: released on every way out
+struct DzOwned {
+  void *p[3] = {nullptr, nullptr, nullptr};
+  ~DzOwned() {
+    for (void *q : p)
+      if (q) (void)hipFree(q);
+  }
+};
+
+// A call whose workspace of `need` bytes has to fit the card before its first launch: where it does not, the caches are trimmed, and
+// where it still does not the call is refused with "<entry>: <count> <what> need x GiB of device memory, y GiB are free".
+static inline int dz_need_device_bytes(dazim_ctx *ctx, size_t need, const char *entry, long long count, const char *what) {
+  size_t fre = 0, tot = 0;
+  DZ_HIP(hipMemGetInfo(&fre, &tot));
+  if (need > fre) {
+    (void)dz_trim_caches(ctx);
+    DZ_HIP(hipMemGetInfo(&fre, &tot));
+  }
+  if (need > fre)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: %lld %s need %.1f GiB of device memory, %.1f GiB are free", entry, count, what,
+                   (double)need / 1073741824.0, (double)fre / 1073741824.0);
+  return 0;
+}

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(MP_TB) void k_mp_trace(int ncell, int kmax, int p, 
 
 }  // namespace
 
-// ---- what dazim_map_tradeoff (map_tradeoff.hip) shares, declared in map_post_internal.h ----
+// ---- what dazim_map_tradeoff (tradeoff.hip) shares, declared in map_post_internal.h ----
 int dz_mp_period_rows(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int kmax, int kn, int ncell, int *per, int *span, int *cnt, int *list,
                       std::vector<int> &hcnt) {
   const int64_t m = A->m;
@@ -312,14 +312,8 @@ extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m
   int nf = 0;
   for (int p = 0; p < kmax; p++) nf += hflag[p] != 0;
   if (n_failed) *n_failed = nf;
-  ctx->ksec.erase("map_post.lap");
   static const char *names[5] = {"map_post.gram", "map_post.factor", "map_post.inverse", "map_post.c", "map_post.rows"};
-  double tot = 0.0;
-  for (int i = 0; i < 5; i++) {
-    ctx->ksec[names[i]] = sec[i];
-    tot += sec[i];
-  }
-  ctx->ksec["map_posterior"] = tot;
+  dz_publish_laps(ctx, "map_post.lap", names, sec, 5, "map_posterior");
   ctx->ksec["map_post.nb"] = MP_NB;
   ctx->ksec["map_post.mfma"] = mfma ? 1.0 : 0.0;
   return 0;

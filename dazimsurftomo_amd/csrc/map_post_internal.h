@@ -1,8 +1,9 @@
 // map_post_internal.h -- what map_post.hip (dazim_map_posterior, one dense block per period), model_post.hip
-// (dazim_model_posterior, one dense block for the whole 3-D model), model_tradeoff.hip (dazim_model_tradeoff, that block at every
-// point of a sweep over the regularisation weights) and map_tradeoff.hip (dazim_map_tradeoff, the same sweep per period) share: the sizes of the dense kernels, their two tile forms, the
-// fixed-order sum of a workgroup, and the host driver of the dense part (map_post_dense.hip), which both entries call -- so a block
-// of the maps and the block of the model go through the same kernels in the same order, bit for bit.
+// (dazim_model_posterior, one dense block for the whole 3-D model) and tradeoff.hip (dazim_model_tradeoff and dazim_map_tradeoff,
+// those blocks at every point of a sweep over the regularisation weights) share: the sizes of the dense kernels, their two tile
+// forms, the fixed-order sum of a workgroup, the two Gram accumulators (mp_accum_rows over a period's row list, mo_accum_row over a
+// column of the transpose), and the host driver of the dense part (map_post_dense.hip), which every entry calls -- so a block of
+// the maps and the block of the model go through the same kernels in the same order, bit for bit.
 #pragma once
 #include <vector>
 
@@ -82,20 +83,20 @@ __device__ __forceinline__ double mp_block_sum(double v, double *red) {
 // local index blk * ncell + cell of column c = blk * kn + p * ncell + cell of the maps' layout (kn = kmax ncell)
 __device__ __forceinline__ int mp_local(int c, int kn, int ncell) { return (c / kn) * ncell + c % ncell; }
 
-// One wavefront (lane t) adds to row a of a period's normal matrix, Aa[c] for c <= a in the local index, the rows list[0 .. nrow) of
-// period p in the order of the list: Aa[c] += r_a r_c (SCALED: f * (r_a r_c)).  A row of the matrix holds column a at most once.  Of
-// 64 rows at a time only those whose range of cells holds a's cell are read (a map row has about 130 of 2 704 cells, close together).
-// dazim_map_posterior's Gram pass takes all rows of the period; dazim_map_tradeoff the data rows once and the regularisation rows per
-// sweep point -- the same numbers added in the same order.
-template <bool SCALED>
-__device__ __forceinline__ void mp_accum_rows(int a, int t, int ncell, int kn, int p, int nrow, const int *list, const int *span,
-                                              const int64_t *rowptr, const int *col, const float *val, double f, double *Aa) {
+// One wavefront (lane t) finds, among the rows list[0 .. nrow) of period p, those that hold the local unknown a, in the order of the
+// list, and calls f(b, e, v, r) on every lane for each: row r has the entries b .. e and the value v at a's column.  A row of the
+// matrix holds column a at most once.  Of 64 rows at a time only those whose range of cells holds a's cell are read (a map row has
+// about 130 of 2 704 cells, close together).
+template <class F>
+__device__ __forceinline__ void mp_rows_with(int a, int t, int ncell, int kn, int p, int nrow, const int *list, const int *span,
+                                             const int64_t *rowptr, const int *col, const float *val, F f) {
   const int cell_a = a % ncell, ga = (a / ncell) * kn + p * ncell + a % ncell;
   for (int i0 = 0; i0 < nrow; i0 += 64) {
     long long mb = 0, me = 0;
+    int r = 0;
     bool near = false;
     if (i0 + t < nrow) {
-      const int r = list[i0 + t];
+      r = list[i0 + t];
       mb = rowptr[r];
       me = rowptr[r + 1];
       near = span[2 * (size_t)r] <= cell_a && cell_a <= span[2 * (size_t)r + 1];
@@ -112,17 +113,28 @@ __device__ __forceinline__ void mp_accum_rows(int a, int t, int ncell, int kn, i
         }
       const unsigned long long h = __ballot(hit);
       if (!h) continue;
-      const double v = (double)__shfl(va, __ffsll((long long)h) - 1);
-      for (long long q = b + t; q < e; q += 64) {
-        const int lc = mp_local(col[q], kn, ncell);
-        if (lc <= a) {
-          if (SCALED) Aa[lc] += f * (v * (double)val[q]);
-          else Aa[lc] += v * (double)val[q];
-        }
-      }
-      __syncthreads();   // (the next row may hold the same columns in other lanes)
+      f(b, e, (double)__shfl(va, __ffsll((long long)h) - 1), __shfl(r, k));
     }
   }
+}
+
+// One wavefront (lane t) adds to row a of a period's normal matrix, Aa[c] for c <= a in the local index, the rows list[0 .. nrow) of
+// period p in the order of the list: Aa[c] += r_a r_c (SCALED: f * (r_a r_c)).  dazim_map_posterior's Gram pass takes all rows of
+// the period; dazim_map_tradeoff the data rows once and the regularisation rows per sweep point -- the same numbers added in the
+// same order.
+template <bool SCALED>
+__device__ __forceinline__ void mp_accum_rows(int a, int t, int ncell, int kn, int p, int nrow, const int *list, const int *span,
+                                              const int64_t *rowptr, const int *col, const float *val, double f, double *Aa) {
+  mp_rows_with(a, t, ncell, kn, p, nrow, list, span, rowptr, col, val, [=](long long b, long long e, double v, int) {
+    for (long long q = b + t; q < e; q += 64) {
+      const int lc = mp_local(col[q], kn, ncell);
+      if (lc <= a) {
+        if (SCALED) Aa[lc] += f * (v * (double)val[q]);
+        else Aa[lc] += v * (double)val[q];
+      }
+    }
+    __syncthreads();   // (the next row may hold the same columns in other lanes)
+  });
 }
 
 constexpr int MO_UN = 4;    // row entries per lane in flight in mo_accum_row
@@ -183,13 +195,4 @@ int dz_mp_period_rows(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int km
                       std::vector<int> &hcnt);
 // k_mp_gram on the rows list[0 .. nrow) of period p: the lower triangle of sum_r r^T r + d2 I into Ad [ng][ng], zeros above it
 int dz_mp_gram(dazim_ctx *ctx, int ng, int ncell, int kn, int p, int nrow, const int *list, const int *span, const dazim_csr *A, double d2, double *Ad);
-// model_tradeoff.hip, one right-hand side on the factor R (lower triangle of Rd [n][n]), enqueued on the context's stream:
-// dz_mt_solve: y := R^-T R^-1 y by panels of MP_NB.  dz_mt_logdet_norm: *ld = 2 sum_i log R_ii and, with x, *xn = sum_i x_i^2.
-// dz_mt_mirror: D[c][a] = D[a][c] for c < a.  dz_mt_rowdot: rowdot[a] = sum_c C_ac D_ac.  dz_mt_sum: out[j] = sum_{i < count}
-// src[j step + i stride] for j < nout.  Every sum in a fixed order.
-int dz_mt_solve(dazim_ctx *ctx, int n, const double *Rd, double *y);
-int dz_mt_logdet_norm(dazim_ctx *ctx, int n, const double *Rd, const double *x, double *ld, double *xn);
-int dz_mt_mirror(dazim_ctx *ctx, int n, double *D);
-int dz_mt_rowdot(dazim_ctx *ctx, int n, const double *Cm, const double *D, double *rowdot);
-int dz_mt_sum(dazim_ctx *ctx, int nout, int64_t count, int stride, int64_t step, const double *src, double *out);
 #pragma GCC visibility pop

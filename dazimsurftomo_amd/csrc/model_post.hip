@@ -155,17 +155,9 @@ __global__ __launch_bounds__(MP_TB) void k_mo_trace(int ncell, const double *rd6
   if (threadIdx.x == 0) trace[blockIdx.x] = (float)s;
 }
 
-struct MoBig {   // the call's own allocations: released on every way out
-  void *p[3] = {nullptr, nullptr, nullptr};
-  ~MoBig() {
-    for (void *q : p)
-      if (q) (void)hipFree(q);
-  }
-};
-
 }  // namespace
 
-// what dazim_model_tradeoff (model_tradeoff.hip) asks of the same matrix before its own kernels: the row check and regstart
+// the row check and regstart, which dazim_model_tradeoff (tradeoff.hip) asks of the same matrix before its own kernels
 int dz_mo_check_rows(dazim_ctx *ctx, const dazim_csr *A, int n, int *bad) {
   if (A->m > 0)
     hipLaunchKernelGGL(k_mo_check, dim3((unsigned)((A->m + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, A->m, n, A->rowptr, A->col, bad);
@@ -204,18 +196,9 @@ extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t
   const int ngrid = (int)std::min<int64_t>(n, (int64_t)MO_WPC * ctx->num_cu);
   const size_t bA = (size_t)n * n * 8, bC = (size_t)n * (n > MP_NB ? n : MP_NB) * 8, bT = (size_t)ngrid * (size_t)(mreg > 0 ? mreg : 1) * 8;
   const size_t bTr = A->colptr ? 0 : (size_t)(n + 1) * 8 + (size_t)(A->nnz > 0 ? A->nnz : 1) * 12 * 3;   // (the transpose and its sort)
-  const size_t need = bA + bC + bT + bTr + ((size_t)64 << 20);
-  size_t fre = 0, tot = 0;
-  DZ_HIP(hipMemGetInfo(&fre, &tot));
-  if (need > fre) {
-    (void)dz_trim_caches(ctx);
-    DZ_HIP(hipMemGetInfo(&fre, &tot));
-  }
-  if (need > fre)
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: %lld unknowns need %.1f GiB of device memory, %.1f GiB are free", (long long)n64,
-                   (double)need / 1073741824.0, (double)fre / 1073741824.0);
+  if ((rc = dz_need_device_bytes(ctx, bA + bC + bT + bTr + ((size_t)64 << 20), "dazim_model_posterior", (long long)n64, "unknowns"))) return rc;
   if (!A->colptr && (rc = dz_build_transpose(ctx, const_cast<dazim_csr *>(A)))) return rc;
-  MoBig big;
+  DzOwned big;
   DZ_HIP(dz_malloc_retry(ctx, &big.p[0], bA));
   DZ_HIP(dz_malloc_retry(ctx, &big.p[1], bC));
   DZ_HIP(dz_malloc_retry(ctx, &big.p[2], bT));
@@ -238,8 +221,7 @@ extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t
   if (nsel > 0 && (rc = dz_check_range(ctx, sel.dev, nsel, 0, n - 1, "dazim_model_posterior: sel"))) return rc;
   int hflag[2] = {0, 0};
   DZ_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), ctx->stream));
-  if (m > 0) hipLaunchKernelGGL(k_mo_check, dim3((unsigned)((m + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, m, n, A->rowptr, A->col, flags + 1);
-  DZ_HIP(hipGetLastError());
+  if ((rc = dz_mo_check_rows(ctx, A, n, flags + 1))) return rc;
   DZ_HIP(hipMemcpyAsync(hflag, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   if (hflag[1]) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: a row's columns do not ascend strictly inside 0..n-1");
@@ -249,7 +231,7 @@ extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t
   double sec[5] = {0, 0, 0, 0, 0};
   {
     DzTimer t(ctx, "model_post.lap");
-    hipLaunchKernelGGL(k_mo_regstart, dim3((unsigned)((n + MP_TB - 1) / MP_TB)), dim3(MP_TB), 0, ctx->stream, n, m_data, A->colptr, A->row, regstart);
+    if ((rc = dz_mo_regstart(ctx, A, n, m_data, regstart))) return rc;
     hipLaunchKernelGGL(k_mo_gram, dim3((unsigned)n), dim3(64), 0, ctx->stream, n, A->colptr, A->row, A->tval, A->rowptr, A->col, A->val, d2, Ad);
     DZ_HIP(hipGetLastError());
     t.stop();
@@ -271,14 +253,8 @@ extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t
     return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   if (n_failed) *n_failed = hflag[0] != 0;
-  ctx->ksec.erase("model_post.lap");
   static const char *names[5] = {"model_post.gram", "model_post.factor", "model_post.inverse", "model_post.c", "model_post.rows"};
-  double total = 0.0;
-  for (int i = 0; i < 5; i++) {
-    ctx->ksec[names[i]] = sec[i];
-    total += sec[i];
-  }
-  ctx->ksec["model_posterior"] = total;
+  dz_publish_laps(ctx, "model_post.lap", names, sec, 5, "model_posterior");
   ctx->ksec["model_post.n"] = (double)n;
   return 0;
 }

@@ -4,12 +4,13 @@ tests/test_long_rows_ref_cpu.py takes the census, the condition and the sensitiv
 
 model: data and regularisation rows of 255 .. 513 entries about the 256 of a pass of mo_accum_row (k_mo_gram, k_mt_gram_data,
 k_mt_combine), a column of the transpose with more than 128 data rows (k_mt_rhs), row counts that are no multiple of the 16 rows of a
-wavefront (k_mt_rows).  maps: data rows of 63 .. 200 entries about the strides of 64 of mp_accum_rows (k_mp_gram, k_mpt_combine,
-k_mpt_rhs), regularisation rows of 7 .. 66 entries about the MP_EMAX = 8 of k_mp_rows, 259 of them in period 0 (its second batch of
+wavefront (k_mt_rows); these are tradeoff.hip's kernels over its view MtModel.  maps: data rows of 63 .. 200 entries about the strides
+of 64 of mp_accum_rows and of the row search mp_rows_with under it (k_mp_gram, and k_mt_combine and k_mt_rhs over the view MtPeriod),
+regularisation rows of 7 .. 66 entries about the MP_EMAX = 8 of k_mp_rows, 259 of them in period 0 (its second batch of
 MP_TB = 256), a column that only rows of a later ballot round hold.  Against numpy.linalg at the bars of the four entries' own tests.
 
 Tried on an MI355X with the walks cut short in the library: mo_accum_row after its first pass, mp_accum_rows' update or its search (and
-k_mpt_rhs's) after the first stride, k_mp_rows' long branch after 64 entries and its loop after the first batch.  Every test here fails
+the maps' k_mt_rhs's) after the first stride, k_mp_rows' long branch after 64 entries and its loop after the first batch.  Every test here fails
 under the cuts its entry runs through (errors of 1e-4 .. 3e-1); of the 313 tests of the four entries' own modules one fails each time,
 the synthetic survey's, whose rays are long enough."""
 import functools
@@ -203,7 +204,7 @@ def map_tradeoff_against_linalg(ctx, azim, through_dead, plain):
 def test_map_tradeoff_equals_numpy_linalg_and_dof_is_the_trace(ctx, azim):
     """the same problems with a right-hand side at smooth+damp, over the five scales at the problem's damping (azim: and on the
     a1/a2 blocks alone): every output and total within the bar of numpy.linalg, a second call the same bits, the plain tile form
-    with azim; at scale 1 dof per block and period is dazim_map_posterior's trace -- k_mpt_combine adds what k_mp_gram adds, stride
+    with azim; at scale 1 dof per block and period is dazim_map_posterior's trace -- k_mt_combine<MtPeriod> adds what k_mp_gram adds, stride
     by stride.
     Measured on an MI355X, largest of both cases: 4.5e-8, dof against the trace 3.0e-8 (bar 1e-6)."""
     map_tradeoff_against_linalg(ctx, azim, False, azim)
@@ -213,7 +214,7 @@ def test_map_tradeoff_equals_numpy_linalg_and_dof_is_the_trace(ctx, azim):
 def test_a_column_only_later_ballot_rounds_hold(ctx, azim):
     """map_posterior_ref.long_rows with through_dead: every added data row holds the dead cell's column of one block.  `problem`
     sends no data row through that cell and gives every period more than 64 rows (423 and 143 here), all of them in front of the
-    added ones in the period's list: the column stands only in rows 64 and later, which mp_accum_rows and k_mpt_rhs reach in their
+    added ones in the period's list: the column stands only in rows 64 and later, which mp_accum_rows and the maps' k_mt_rhs reach in their
     second round of 64 rows or later (tests/test_long_rows_ref_cpu.py asserts the positions).  The dead cells are in sel.
     Measured on an MI355X, largest of both cases and both entries: 4.9e-8, dof against the trace 3.5e-8 (bar 1e-6)."""
     prob, want = map_case(azim, pref.REGS[0], True)

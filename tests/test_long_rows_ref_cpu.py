@@ -240,7 +240,7 @@ def test_map_tradeoff_reference_sees_the_later_strides(azim, keep, reg_only):
 def test_map_column_behind_the_first_ballot_round(azim):
     """through_dead: `problem` sends no data row through the dead cell, and every period has more than 64 of its rows (143 or 423),
     all in front of the added ones, so the dead cell's columns stand only in rows 64 and later of a period's list -- in a later
-    round of the 64-row ballot of mp_accum_rows and k_mpt_rhs.  Without those entries the references move by 100 bars and more."""
+    round of the 64-row ballot of mp_rows_with (mp_accum_rows, the maps' k_mt_rhs).  Without those entries the references move by 100 bars and more."""
     prob, scale, damp, out = map_sweep(azim, True)
     nx, ny = pref.LONG_SHAPES[azim]
     ncell, nblk, kmax = (nx - 2) * (ny - 2), 3 if azim else 1, pref.LONG_KMAX
