@@ -231,6 +231,33 @@ class Context:
         self._check(rc)
         return pv, (sen if kernels else None), nf.value
 
+    def dispersion_kernels_typed(self, vel, depz, segments, sublayers, kernels=True):
+        """dazim_dispersion_kernels_typed: depthkernel for every wave type.  segments = [(iwave, igr, periods), ...] with iwave 1 Love /
+        2 Rayleigh and igr 0 phase / 1 group velocity; the tables are indexed by the K virtual periods, the segments' periods laid
+        end to end.  vel[nz][ny][nx] -> pv[K][nx*ny] and, if `kernels`, (sen_vs, sen_vp, sen_rho)[nz][K][nx*ny].
+        Returns (pv, sen, n_failed)."""
+        nz, ny, nx = vel.shape
+        depz = np.ascontiguousarray(depz, np.float32)
+        iw = np.ascontiguousarray([s[0] for s in segments], np.int32)
+        ig = np.ascontiguousarray([s[1] for s in segments], np.int32)
+        km = np.ascontiguousarray([len(s[2]) for s in segments], np.int32)
+        t = np.ascontiguousarray(np.concatenate([np.asarray(s[2], np.float64).ravel() for s in segments]) if len(segments) else np.zeros(0))
+        K = len(t)
+        if _is_torch(vel):
+            import torch
+            pv = torch.empty((K, nx * ny), dtype=torch.float64, device=vel.device)
+            sen = [torch.empty((nz, K, nx * ny), dtype=torch.float64, device=vel.device) for _ in range(3)] if kernels else None
+        else:
+            vel = np.ascontiguousarray(vel, np.float32)
+            pv = np.zeros((K, nx * ny), np.float64)
+            sen = [np.zeros((nz, K, nx * ny), np.float64) for _ in range(3)] if kernels else None
+        nf = C.c_int(0)
+        sp = [_ptr(a) for a in sen] if kernels else [None] * 3
+        rc = self.lib.dazim_dispersion_kernels_typed(self._h, nx, ny, nz, _ptr(vel, np.float32), _ptr(depz), C.c_float(sublayers), len(segments),
+                                                     _ptr(iw), _ptr(ig), _ptr(km), _ptr(t), _ptr(pv), sp[0], sp[1], sp[2], C.byref(nf))
+        self._check(rc)
+        return pv, sen, nf.value
+
     def surfdisp96(self, thk, vp, vs, rho, t, iflsph=1, iwave=2, mode=1, igr=0, nlayer=None):
         """surfdisp96 (inv/surfdisp96.f:52) with the subroutine's own arguments, for one model (1-D arrays) or a batch
         (thk, vp, vs, rho [nmodel][nlayer_max], `nlayer` [nmodel] if the models have different numbers of layers):

@@ -16,8 +16,11 @@
 #include <cmath>
 
 #include "dazim_internal.h"
+#include "surfdisp_device.h"
 
 namespace {
+
+using namespace dz_sd;   // var, dltar1, dltar4, getsol, nevill: surfdisp_device.h, shared with disp_typed.hip
 
 constexpr int NL = 200;  // inv/surfdisp96.f:57
 constexpr int NP = 60;   // inv/surfdisp96.f:59
@@ -42,320 +45,6 @@ struct Model {
   __device__ float B(int m) const { return b[(size_t)(m - 1) * stride]; }
   __device__ float R(int m) const { return rho[(size_t)(m - 1) * stride]; }
 };
-
-__device__ __forceinline__ double sgn(double x) { return copysign(1.0, x); }
-
-struct VarOut {
-  double w, cosp, a0, cpcq, cpy, cpz, cqw, cqx, xy, xz, wy, wz;
-};
-
-// var, inv/surfdisp96.f:868-985
-__device__ void var(double p, double q, double ra, double rb, double wvno, double xka, double xkb, double dpth, VarOut &o) {
-  double w = 0, x = 0, y = 0, z = 0, cosp = 0, cosq = 0, sinp, sinq, fac, pex = 0.0, sex = 0.0;
-  if (wvno < xka) {
-    sinp = sin(p);
-    w = sinp / ra;
-    x = -ra * sinp;
-    cosp = cos(p);
-  } else if (wvno == xka) {
-    cosp = 1.0;
-    w = dpth;
-    x = 0.0;
-  } else if (wvno > xka) {
-    pex = p;
-    fac = 0.0;
-    if (p < 16) fac = exp(-2.0 * p);
-    cosp = (1.0 + fac) * 0.5;
-    sinp = (1.0 - fac) * 0.5;
-    w = sinp / ra;
-    x = ra * sinp;
-  }
-  if (wvno < xkb) {
-    sinq = sin(q);
-    y = sinq / rb;
-    z = -rb * sinq;
-    cosq = cos(q);
-  } else if (wvno == xkb) {
-    cosq = 1.0;
-    y = dpth;
-    z = 0.0;
-  } else if (wvno > xkb) {
-    sex = q;
-    fac = 0.0;
-    if (q < 16) fac = exp(-2.0 * q);
-    cosq = (1.0 + fac) * 0.5;
-    sinq = (1.0 - fac) * 0.5;
-    y = sinq / rb;
-    z = rb * sinq;
-  }
-  const double exa = pex + sex;
-  o.a0 = 0.0;
-  if (exa < 60.0) o.a0 = exp(-exa);
-  o.w = w;
-  o.cosp = cosp;
-  o.cpcq = cosp * cosq;
-  o.cpy = cosp * y;
-  o.cpz = cosp * z;
-  o.cqw = cosq * w;
-  o.cqx = cosq * x;
-  o.xy = x * y;
-  o.xz = x * z;
-  o.wy = w * y;
-  o.wz = w * z;
-}
-
-// dltar4, inv/surfdisp96.f:767-865 with dnka (:1018-1062) and normc (:989-1014)
-__device__ double dltar4(const Model &M, double wvno, double omga) {
-  double e[5], ee[5], ca[5][5];
-  const int mmax = M.mmax;
-  double omega = omga;
-  if (omega < 1.0e-4) omega = 1.0e-4;
-  const double wvno2 = wvno * wvno;
-  double xka = omega / (double)M.A(mmax);
-  double xkb = omega / (double)M.B(mmax);
-  double wvnop = wvno + xka, wvnom = fabs(wvno - xka);
-  double ra = sqrt(wvnop * wvnom);
-  wvnop = wvno + xkb;
-  wvnom = fabs(wvno - xkb);
-  double rb = sqrt(wvnop * wvnom);
-  double t = (double)M.B(mmax) / omega;
-  double gammk = 2.0 * t * t;
-  double gam = gammk * wvno2;
-  double gamm1 = gam - 1.0;
-  double rho1 = (double)M.R(mmax);
-  e[0] = rho1 * rho1 * (gamm1 * gamm1 - gam * gammk * ra * rb);
-  e[1] = -rho1 * ra;
-  e[2] = rho1 * (gamm1 - gammk * ra * rb);
-  e[3] = rho1 * rb;
-  e[4] = wvno2 - ra * rb;
-  VarOut v;
-  for (int m = mmax - 1; m >= M.llw; m--) {
-    const double am = (double)M.A(m), bm = (double)M.B(m);
-    xka = omega / am;
-    xkb = omega / bm;
-    t = bm / omega;
-    gammk = 2.0 * t * t;
-    gam = gammk * wvno2;
-    wvnop = wvno + xka;
-    wvnom = fabs(wvno - xka);
-    ra = sqrt(wvnop * wvnom);
-    wvnop = wvno + xkb;
-    wvnom = fabs(wvno - xkb);
-    rb = sqrt(wvnop * wvnom);
-    const double dpth = (double)M.D(m);
-    rho1 = (double)M.R(m);
-    const double p = ra * dpth, q = rb * dpth;
-    var(p, q, ra, rb, wvno, xka, xkb, dpth, v);
-    gamm1 = gam - 1.0;
-    const double twgm1 = gam + gamm1, gmgmk = gam * gammk, gmgm1 = gam * gamm1, gm1sq = gamm1 * gamm1;
-    const double rho2 = rho1 * rho1, a0pq = v.a0 - v.cpcq;
-    ca[0][0] = v.cpcq - 2.0 * gmgm1 * a0pq - gmgmk * v.xz - wvno2 * gm1sq * v.wy;
-    ca[0][1] = (wvno2 * v.cpy - v.cqx) / rho1;
-    ca[0][2] = -(twgm1 * a0pq + gammk * v.xz + wvno2 * gamm1 * v.wy) / rho1;
-    ca[0][3] = (v.cpz - wvno2 * v.cqw) / rho1;
-    ca[0][4] = -(2.0 * wvno2 * a0pq + v.xz + wvno2 * wvno2 * v.wy) / rho2;
-    ca[1][0] = (gmgmk * v.cpz - gm1sq * v.cqw) * rho1;
-    ca[1][1] = v.cpcq;
-    ca[1][2] = gammk * v.cpz - gamm1 * v.cqw;
-    ca[1][3] = -v.wz;
-    ca[1][4] = ca[0][3];
-    ca[3][0] = (gm1sq * v.cpy - gmgmk * v.cqx) * rho1;
-    ca[3][1] = -v.xy;
-    ca[3][2] = gamm1 * v.cpy - gammk * v.cqx;
-    ca[3][3] = ca[1][1];
-    ca[3][4] = ca[0][1];
-    ca[4][0] = -(2.0 * gmgmk * gm1sq * a0pq + gmgmk * gmgmk * v.xz + gm1sq * gm1sq * v.wy) * rho2;
-    ca[4][1] = ca[3][0];
-    ca[4][2] = -(gammk * gamm1 * twgm1 * a0pq + gam * gammk * gammk * v.xz + gamm1 * gm1sq * v.wy) * rho1;
-    ca[4][3] = ca[1][0];
-    ca[4][4] = ca[0][0];
-    const double tt = -2.0 * wvno2;
-    ca[2][0] = tt * ca[4][2];
-    ca[2][1] = tt * ca[3][2];
-    ca[2][2] = v.a0 + 2.0 * (v.cpcq - ca[0][0]);
-    ca[2][3] = tt * ca[1][2];
-    ca[2][4] = tt * ca[0][2];
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-      double cr = 0.0;
-#pragma unroll
-      for (int j = 0; j < 5; j++) cr = cr + e[j] * ca[j][i];
-      ee[i] = cr;
-    }
-    double t1 = 0.0;
-#pragma unroll
-    for (int i = 0; i < 5; i++)
-      if (fabs(ee[i]) > t1) t1 = fabs(ee[i]);
-    if (t1 < 1.e-40) t1 = 1.0;
-#pragma unroll
-    for (int i = 0; i < 5; i++) e[i] = ee[i] / t1;
-  }
-  if (M.llw != 1) {  // water layer on top, :844-860
-    xka = omega / (double)M.A(1);
-    wvnop = wvno + xka;
-    wvnom = fabs(wvno - xka);
-    ra = sqrt(wvnop * wvnom);
-    const double dpth = (double)M.D(1);
-    rho1 = (double)M.R(1);
-    const double p = ra * dpth;
-    const double znul = 1.0e-05;
-    var(p, znul, ra, znul, wvno, xka, znul, dpth, v);
-    const double w0 = -rho1 * v.w;
-    return v.cosp * e[0] + w0 * e[1];
-  }
-  return e[0];
-}
-
-// dltar1: SH period equation, inv/surfdisp96.f:704-763
-__device__ double dltar1(const Model &M, double wvno, double omega) {
-  const int mmax = M.mmax;
-  double beta1 = (double)M.B(mmax);
-  double rho1 = (double)M.R(mmax);
-  double xkb = omega / beta1;
-  double wvnop = wvno + xkb, wvnom = fabs(wvno - xkb);
-  double rb = sqrt(wvnop * wvnom);
-  double e1 = rho1 * rb;
-  double e2 = 1.0 / (beta1 * beta1);
-  for (int m = mmax - 1; m >= M.llw; m--) {
-    beta1 = (double)M.B(m);
-    rho1 = (double)M.R(m);
-    const double dm = (double)M.D(m);
-    const double xmu = rho1 * beta1 * beta1;
-    xkb = omega / beta1;
-    wvnop = wvno + xkb;
-    wvnom = fabs(wvno - xkb);
-    rb = sqrt(wvnop * wvnom);
-    const double q = dm * rb;
-    double y, z, cosq, sinq, fac;
-    if (wvno < xkb) {
-      sinq = sin(q);
-      y = sinq / rb;
-      z = -rb * sinq;
-      cosq = cos(q);
-    } else if (wvno == xkb) {
-      cosq = 1.0;
-      y = dm;
-      z = 0.0;
-    } else {
-      fac = 0.0;
-      if (q < 16) fac = exp(-2.0 * q);
-      cosq = (1.0 + fac) * 0.5;
-      sinq = (1.0 - fac) * 0.5;
-      y = sinq / rb;
-      z = rb * sinq;
-    }
-    const double e10 = e1 * cosq + e2 * xmu * z;
-    const double e20 = e1 * y / xmu + e2 * cosq;
-    double xnor = fabs(e10);
-    const double ynor = fabs(e20);
-    if (ynor > xnor) xnor = ynor;
-    if (xnor < 1.e-40) xnor = 1.0;
-    e1 = e10 / xnor;
-    e2 = e20 / xnor;
-  }
-  return e1;
-}
-
-__device__ double dltar(const Model &M, double wvno, double omega, int kk) {  // :684-700
-  return kk == 1 ? dltar1(M, wvno, omega) : dltar4(M, wvno, omega);
-}
-
-constexpr double TWOPI = 2.0 * 3.141592653589793;
-
-// nevill, inv/surfdisp96.f:551-668 (half :670-680 inlined)
-__device__ double nevill(const Model &M, double t, double c1, double c2, double del1, double del2, int ifunc) {
-  double x[20], y[20];
-  const double omega = TWOPI / t;
-  double c3 = 0.5 * (c1 + c2);
-  double del3 = dltar(M, omega / c3, omega, ifunc);
-  int nev = 1, nctrl = 1, m = 1;
-  for (;;) {
-    nctrl++;
-    if (nctrl >= 100) break;
-    if (c3 < fmin(c1, c2) || c3 > fmax(c1, c2)) {
-      nev = 0;
-      c3 = 0.5 * (c1 + c2);
-      del3 = dltar(M, omega / c3, omega, ifunc);
-    }
-    const double s13 = del1 - del3, s32 = del3 - del2;
-    if (sgn(del3) * sgn(del1) < 0.0) {
-      c2 = c3;
-      del2 = del3;
-    } else {
-      c1 = c3;
-      del1 = del3;
-    }
-    if (fabs(c1 - c2) <= 1.e-6 * c1) break;
-    if (sgn(s13) != sgn(s32)) nev = 0;
-    const double ss1 = fabs(del1), s1 = (double)0.01f * ss1;
-    const double ss2 = fabs(del2), s2 = (double)0.01f * ss2;
-    bool halve = s1 > ss2 || s2 > ss1 || nev == 0;
-    if (!halve) {
-      if (nev == 2) {
-        x[m] = c3;
-        y[m] = del3;
-      } else {
-        x[0] = c1;
-        y[0] = del1;
-        x[1] = c2;
-        y[1] = del2;
-        m = 1;
-      }
-      for (int kk = 1; kk <= m; kk++) {
-        const int j = m - kk + 1;
-        const double denom = y[m] - y[j - 1];
-        if (fabs(denom) < 1.0e-10 * fabs(y[m])) {
-          halve = true;
-          break;
-        }
-        x[j - 1] = (-y[j - 1] * x[j] + y[m] * x[j - 1]) / denom;
-      }
-      if (!halve) {
-        c3 = x[0];
-        del3 = dltar(M, omega / c3, omega, ifunc);
-        nev = 2;
-        m = m + 1;
-        if (m > 10) m = 10;
-      }
-    }
-    if (halve) {
-      c3 = 0.5 * (c1 + c2);
-      del3 = dltar(M, omega / c3, omega, ifunc);
-      nev = 1;
-      m = 1;
-    }
-  }
-  return c3;
-}
-
-// getsol, inv/surfdisp96.f:384-476; del1st is its SAVE variable
-__device__ int getsol(const Model &M, double t1, double &c1, double clow, double dc, double cm, float betmx, int ifunc,
-                      int ifirst, double &del1st) {
-  double c2, del1, del2;
-  double omega = TWOPI / t1;
-  del1 = dltar(M, omega / c1, omega, ifunc);
-  if (ifirst == 1) del1st = del1;
-  const double plmn = sgn(del1st) * sgn(del1);
-  int idir = (ifirst == 1) ? 1 : (plmn >= 0.0 ? 1 : -1);
-  for (;;) {
-    c2 = (idir > 0) ? c1 + dc : c1 - dc;
-    if (c2 <= clow) {
-      idir = 1;
-      c1 = clow;
-      continue;
-    }
-    omega = TWOPI / t1;
-    del2 = dltar(M, omega / c2, omega, ifunc);
-    if (sgn(del1) != sgn(del2)) break;
-    c1 = c2;
-    del1 = del2;
-    if (c1 < cm) return -1;
-    if (c1 >= ((double)betmx + dc)) return -1;
-  }
-  c1 = nevill(M, t1, c1, c2, del1, del2, ifunc);
-  if (c1 > (double)betmx) return -1;
-  return 1;
-}
 
 // the loops over modes and periods, inv/surfdisp96.f:212-349, one lane per model
 __global__ __launch_bounds__(64) void surfdisp_kernel(SdArgs S) {
@@ -457,24 +146,6 @@ __global__ __launch_bounds__(64) void surfdisp_kernel(SdArgs S) {
   for (int i = 0; i < kmax; i++)
     if (cg[i] == 0.0) nz++;
   if (nz) atomicAdd(S.nfail, nz);
-}
-
-// gtsolh, inv/surfdisp96.f:361-382, all fp32 (host)
-float gtsolh(float a, float b) {
-  float c = 0.95f * b;
-  for (int i = 0; i < 5; i++) {
-    const float gamma = b / a;
-    const float kappa = c / b;
-    const float k2 = kappa * kappa;
-    const float gk2 = (gamma * kappa) * (gamma * kappa);
-    const float fac1 = sqrtf(1.0f - gk2);
-    const float fac2 = sqrtf(1.0f - k2);
-    const float fr = (2.0f - k2) * (2.0f - k2) - 4.0f * fac1 * fac2;
-    float frp = -4.0f * (2.0f - k2) * kappa + 4.0f * fac2 * gamma * gamma * kappa / fac1 + 4.0f * fac1 * kappa / fac2;
-    frp = frp / b;
-    c = c - fr / frp;
-  }
-  return c;
 }
 
 }  // namespace

@@ -85,7 +85,16 @@ program SurfDepthFromMaps_amd
   end if
   nlay = nz - 1
   if (nlay > 63) error stop 'SurfDepthFromMaps_amd inverts at most 63 layers (nz <= 64)'
-  if (kmax > 60) error stop 'SurfDepthFromMaps_amd takes at most 60 periods'
+  if (kmax > 60) then
+    write (*, '(a,i4,a)') ' ERROR: SurfDepthFromMaps_amd: para.in lists', kmax, ' periods over all wave types; the column solve holds at most 60'
+    error stop 'SurfDepthFromMaps_amd takes at most 60 periods'
+  end if
+  if (p%typed .and. .not. iso_mod) then
+    write (*, '(a)') ' ERROR: SurfDepthFromMaps_amd with iso_mod = F: para.in lists Rayleigh group or Love-wave periods; the Gc/Gs solve''s'
+    write (*, '(a)') ' kernels (Lsen_Gsc) exist for Rayleigh phase velocities only.  Run such maps with iso_mod = T.'
+    error stop 'the Gc/Gs solve takes Rayleigh phase velocities only'
+  end if
+  if (p%typed) call dazim_set_segments(p%nseg, p%seg_wavetp, p%seg_veltp, p%seg_kmax)
   write (logfile, '(a,a)') trim(inputfile), '_2step.log'
   open (66, file=logfile)
   write (66, *)
@@ -119,7 +128,7 @@ program SurfDepthFromMaps_amd
     write (q, '(a)') '  iter  cells  rms_c_before  rms_c_after   max|dVs|'
   end do
   do iter = 1, maxiter
-    call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_loc(svs), c_loc(svp), &
+    call dazim_check(dazim_dispersion_any(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_loc(svs), c_loc(svp), &
                                               c_loc(srho), nfail), 'dispersion and depth kernels')
     if (nfail > 0) write (6, *) 'WARNING:improper initial value in disper - no zero found', nfail
     call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kmax, vsf, svs, svp, srho, skern), 'dc/dVs table')
@@ -140,7 +149,7 @@ program SurfDepthFromMaps_amd
   end do
 
   ! ---- the final model's curves; its misfit --------------------------------------------------------------------------------------
-  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_null_ptr, c_null_ptr, &
+  call dazim_check(dazim_dispersion_any(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_null_ptr, c_null_ptr, &
                                             c_null_ptr, nfail), 'dispersion curves of the final model')
   call residual()
   do q = 6, 66, 60
@@ -150,7 +159,7 @@ program SurfDepthFromMaps_amd
   ! ---- how well that Vs is known (resolution = 1): kernels at the final model, the last solve's weights and regularisers ----------
   if (ires == 1) then
     allocate (res(nx - 2, ny - 2, nlay, 5), rtrace(nx - 2, ny - 2), pvk(nx*ny, kmax))
-    call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pvk, c_loc(svs), c_loc(svp), &
+    call dazim_check(dazim_dispersion_any(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pvk, c_loc(svs), c_loc(svp), &
                                               c_loc(srho), nfail), 'depth kernels of the final model')
     call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kmax, vsf, svs, svp, srho, skern), 'dc/dVs table of the final model')
     call dazim_check(dazim_column_resolution(dazim_handle, nx, ny, nlay, kmax, 0, c_loc(skern), w, smooth_vs, damp, depz, &

@@ -114,9 +114,11 @@ program SurfAAForward_amd
     if (line(1:1) == '#') then
       read (line, *) str1, sta1_lat, sta1_lon, period, wavetp, veltp
       if (wavetp == 2 .and. veltp == 0) knum = period
-      if (wavetp == 2 .and. veltp == 1) stop 'can not deal with Rayleigh wave group data'
-      if (wavetp == 1 .and. veltp == 0) stop 'can not deal with Love wave phase data'
-      if (wavetp == 1 .and. veltp == 1) stop 'can not deal with Love wave group data'
+      if (wavetp /= 2 .or. veltp /= 0) then
+        write (*, '(a)') ' ERROR: SurfAAForward_amd: the data file holds Rayleigh group or Love-wave headers; the synthetic azimuthal'
+        write (*, '(a)') ' times are formed with the 2-psi kernels, which exist for Rayleigh phase velocities only.'
+        stop 'SurfAAForward_amd takes Rayleigh phase velocities only'
+      end if
       if (knum < 1 .or. knum > kmax) stop 'period index in the data file exceeds kmaxRc'
       if (knum /= knumo) istep = 0
       istep = istep + 1

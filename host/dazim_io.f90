@@ -9,6 +9,7 @@ module dazim_io
   public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
   public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
   public :: write_resolution, uncertainty_weights, tradeoff_factor, write_tradeoff, write_map_tradeoff
+  public :: period_type, type_name
 
   real, parameter :: pi = 3.1415926535898
   real*8, parameter :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
@@ -19,7 +20,18 @@ module dazim_io
     real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp
     logical :: iso_mod
     real*8, allocatable :: tRc(:)            ! (size 0 when kmaxRc <= 0)
+    ! Wave types (DSurfTomo's dialect of para.in: after the Rayleigh phase periods up to three more optional blocks, kmaxRg, kmaxLc,
+    ! kmaxLg, each positive count followed by its periods line; end of file = 0).  Everything behind the readers indexes a period
+    ! number and never asks for its type, so with typed data kmaxRc and tRc hold the VIRTUAL periods: the types' periods laid end
+    ! to end in the order Rc, Rg, Lc, Lg.  type_kmax / type_off: count and first virtual period - 1 of each type in that order;
+    ! the segments are the types with a positive count (wavetp 2 Rayleigh / 1 Love, veltp 0 phase / 1 group, as in the data file).
+    integer :: type_kmax(4) = 0, type_off(4) = 0
+    integer :: nseg = 0, seg_wavetp(4) = 0, seg_veltp(4) = 0, seg_kmax(4) = 0
+    logical :: typed = .false.               ! a type other than Rayleigh phase has periods
   end type
+  integer, parameter :: type_wavetp(4) = [2, 2, 1, 1], type_veltp(4) = [0, 1, 0, 1]
+  character(len=14), parameter :: type_names(4) = ['Rayleigh phase', 'Rayleigh group', 'Love phase    ', 'Love group    ']
+  character(len=6), parameter :: type_lines(4) = ['kmaxRc', 'kmaxRg', 'kmaxLc', 'kmaxLg']
 
   interface optional_arg
     module procedure int_arg, int8_arg, real_arg
@@ -31,7 +43,8 @@ contains
     character(len=*), intent(in) :: inputfile
     type(para_t), intent(out) :: p
     character(len=40) :: dummy
-    integer :: u, i
+    integer :: u, i, it, err, cnt(4)
+    real*8 :: tt(60, 4)
     open (newunit=u, file=inputfile, status='old', action='read')
     read (u, '(a30)') dummy
     read (u, '(a30)') dummy
@@ -54,16 +67,70 @@ contains
     read (u, *) p%kmaxRc
     allocate (p%tRc(max(p%kmaxRc, 0)))
     if (p%kmaxRc > 0) read (u, *) (p%tRc(i), i=1, p%kmaxRc)
+    cnt = 0; cnt(1) = max(p%kmaxRc, 0)
+    do it = 2, 4                              ! kmaxRg, kmaxLc, kmaxLg: optional, end of file = 0
+      read (u, *, iostat=err) cnt(it)
+      if (err /= 0) then
+        cnt(it) = 0
+        exit
+      end if
+      if (cnt(it) > 60) error stop 'para.in: more than 60 periods of one wave type'
+      if (cnt(it) > 0) read (u, *) (tt(i, it), i=1, cnt(it))
+      cnt(it) = max(cnt(it), 0)
+    end do
     close (u)
+    p%type_kmax = cnt
+    do it = 1, 4
+      p%type_off(it) = sum(cnt(1:it - 1))
+      if (cnt(it) > 0) then
+        p%nseg = p%nseg + 1
+        p%seg_wavetp(p%nseg) = type_wavetp(it); p%seg_veltp(p%nseg) = type_veltp(it); p%seg_kmax(p%nseg) = cnt(it)
+      end if
+    end do
+    p%typed = any(cnt(2:4) > 0)
+    if (p%typed) then                         ! the virtual periods
+      if (cnt(1) > 60) error stop 'para.in: more than 60 periods of one wave type'
+      if (cnt(1) > 0) tt(1:cnt(1), 1) = p%tRc(1:cnt(1))
+      deallocate (p%tRc)
+      p%kmaxRc = sum(cnt)
+      allocate (p%tRc(p%kmaxRc))
+      do it = 1, 4
+        if (cnt(it) > 0) p%tRc(p%type_off(it) + 1:p%type_off(it) + cnt(it)) = tt(1:cnt(it), it)
+      end do
+    end if
   end subroutine
+
+  ! wave type of virtual period t1 in the data file's codes: wavetp 2 Rayleigh / 1 Love, veltp 0 phase / 1 group
+  subroutine period_type(p, t1, wavetp, veltp)
+    type(para_t), intent(in) :: p
+    integer, intent(in) :: t1
+    integer, intent(out) :: wavetp, veltp
+    integer :: it
+    wavetp = 2; veltp = 0
+    do it = 1, 4
+      if (t1 > p%type_off(it) .and. t1 <= p%type_off(it) + p%type_kmax(it)) then
+        wavetp = type_wavetp(it); veltp = type_veltp(it)
+      end if
+    end do
+  end subroutine
+
+  function type_name(wavetp, veltp) result(name)
+    integer, intent(in) :: wavetp, veltp
+    character(len=14) :: name
+    name = type_names(merge(1, 3, wavetp == 2) + merge(1, 0, veltp /= 0))
+  end function
 
   ! the traveltime data file, inv/Main_Jt.f90:240-318: sources and receivers per period as colatitude / longitude in radians,
   ! traveltimes obst = distance / velocity.  At most nsrc receivers per source.  Unit 66 is the caller's open log.
-  subroutine read_data(p, scxf, sczf, rcxf, rczf, periods, nrc1, nsrc1, obst, dist, dall)
+  ! The period index of a '#' header counts within its wave type (DSurfTomo's convention); the virtual period is the type's offset
+  ! plus that index, and `periods` holds virtual periods.  dper (optional): the virtual period of every datum, in file order.
+  subroutine read_data(p, scxf, sczf, rcxf, rczf, periods, nrc1, nsrc1, obst, dist, dall, dper)
     type(para_t), intent(in) :: p
     real, allocatable, intent(out) :: scxf(:, :), sczf(:, :), rcxf(:, :, :), rczf(:, :, :), obst(:), dist(:)
     integer, allocatable, intent(out) :: periods(:, :), nrc1(:, :), nsrc1(:)
     integer, intent(out) :: dall
+    integer, allocatable, intent(out), optional :: dper(:)
+    integer :: it
     character(len=200) :: line
     character :: str1
     logical :: ex
@@ -90,17 +157,29 @@ contains
     end do
     rewind (u)
     allocate (obst(dall), dist(dall))
+    if (present(dper)) allocate (dper(dall))
     dall = 0; istep = 0; istep1 = 0; knum = 0; knumo = 12345
     do
       read (u, '(a)', iostat=err) line
       if (err /= 0) exit
       if (line(1:1) == '#') then
         read (line, *) str1, sta1_lat, sta1_lon, period, wavetp, veltp
-        if (wavetp == 2 .and. veltp == 0) knum = period
-        if (wavetp == 2 .and. veltp == 1) stop 'can not deal with Rayleigh wave group data'
-        if (wavetp == 1 .and. veltp == 0) stop 'can not deal with Love wave phase data'
-        if (wavetp == 1 .and. veltp == 1) stop 'can not deal with Love wave group data'
-        if (knum < 1 .or. knum > kmax) stop 'period index in the data file exceeds kmaxRc'
+        if ((wavetp /= 1 .and. wavetp /= 2) .or. (veltp /= 0 .and. veltp /= 1)) &
+          stop 'wave type in the data file: wavetp 1 or 2, veltp 0 or 1'
+        it = merge(1, 3, wavetp == 2) + veltp
+        if (p%type_kmax(it) == 0 .and. it > 1) then
+          write (*, '(6a)') ' ERROR: the data file holds ', trim(type_names(it)), ' data, but para.in has no ', type_lines(it), &
+            ' line with a positive count and its periods (the blocks after the Rayleigh phase periods: kmaxRg, kmaxLc, kmaxLg)'
+          stop 'a wave type of the data file has no periods in para.in'
+        end if
+        if (.not. p%typed) then
+          knum = period
+          if (knum < 1 .or. knum > kmax) stop 'period index in the data file exceeds kmaxRc'
+        else
+          if (period < 1 .or. period > p%type_kmax(it)) &
+            stop 'period index in the data file exceeds the count of its wave type in para.in'
+          knum = p%type_off(it) + period
+        end if
         if (knum /= knumo) istep = 0
         istep = istep + 1
         if (istep > nsrc) stop 'more sources per period than para.in allows: increase max(sources, receivers)'
@@ -109,7 +188,7 @@ contains
         sta1_lon = sta1_lon*pi/180.0
         scxf(istep, knum) = sta1_lat
         sczf(istep, knum) = sta1_lon
-        periods(istep, knum) = period
+        periods(istep, knum) = knum
         nsrc1(knum) = istep
         knumo = knum
       else
@@ -124,6 +203,7 @@ contains
         call great_circle(sta1_lat, sta1_lon, sta2_lat, sta2_lon, dist1)
         dist(dall) = dist1
         obst(dall) = dist1/velvalue
+        if (present(dper)) dper(dall) = knum
         nrc1(istep, knum) = istep1
       end if
     end do
@@ -435,11 +515,16 @@ contains
     character(len=*), intent(in) :: fname
     type(para_t), intent(in) :: p
     real*8, intent(in) :: c(p%nx - 2, p%ny - 2, p%kmaxRc)
-    integer :: u, t1, j1, i1
+    integer :: u, t1, j1, i1, wt, vt
     open (newunit=u, file=fname)
     do t1 = 1, p%kmaxRc
+      call period_type(p, t1, wt, vt)
       do j1 = 1, p%ny - 2
         do i1 = 1, p%nx - 2
+          if (p%typed) then                   ! two trailing columns: wavetp veltp
+            write (u, '(4f10.4,2i3)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), c(i1, j1, t1), wt, vt
+            cycle
+          end if
           write (u, '(5f10.4)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), c(i1, j1, t1)
         end do
       end do
@@ -498,12 +583,18 @@ contains
 
   ! one line of a period_Azm_tomo file: lon lat period c, fast-axis angle, amplitude relative to c, amplitude, and the 2-psi terms
   ! c2, s2 themselves (isoC: c in fp32, as the reference holds it)
-  subroutine write_azm_line(u, lon, lat, period, isoC, c2, s2)
+  ! wavetp, veltp (both or neither): two trailing columns, written with typed data only
+  subroutine write_azm_line(u, lon, lat, period, isoC, c2, s2, wavetp, veltp)
     integer, intent(in) :: u
     real, intent(in) :: lon, lat, isoC, c2, s2
     real*8, intent(in) :: period
+    integer, intent(in), optional :: wavetp, veltp
     real :: amp
     amp = sqrt(c2**2 + s2**2)
+    if (present(wavetp) .and. present(veltp)) then
+      write (u, '(9f10.5,2i3)') lon, lat, period, isoC, fast_axis(c2, s2), amp/isoC, amp, c2, s2, wavetp, veltp
+      return
+    end if
     write (u, '(10f10.5)') lon, lat, period, isoC, fast_axis(c2, s2), amp/isoC, amp, c2, s2
   end subroutine
 
@@ -514,10 +605,11 @@ contains
     type(para_t), intent(in) :: p
     real, intent(in) :: lsen(p%nx*p%ny, p%kmaxRc, p%nz - 1), gc(:, :, :), gs(:, :, :)
     real*8, intent(in) :: c(p%nx - 2, p%ny - 2, p%kmaxRc)
-    integer :: u, t1, j1, i1, k1
+    integer :: u, t1, j1, i1, k1, wt, vt
     real :: c2, s2
     open (newunit=u, file=fname, status='replace', action='write')
     do t1 = 1, p%kmaxRc
+      call period_type(p, t1, wt, vt)
       do j1 = 1, p%ny - 2
         do i1 = 1, p%nx - 2
           c2 = 0.0; s2 = 0.0
@@ -525,7 +617,11 @@ contains
             c2 = c2 + lsen(j1*p%nx + i1 + 1, t1, k1)*gc(i1, j1, k1)
             s2 = s2 + lsen(j1*p%nx + i1 + 1, t1, k1)*gs(i1, j1, k1)
           end do
-          call write_azm_line(u, p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), real(c(i1, j1, t1)), c2, s2)
+          if (p%typed) then
+            call write_azm_line(u, p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), real(c(i1, j1, t1)), c2, s2, wt, vt)
+          else
+            call write_azm_line(u, p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, p%tRc(t1), real(c(i1, j1, t1)), c2, s2)
+          end if
         end do
       end do
     end do

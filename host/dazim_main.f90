@@ -41,6 +41,8 @@ program DAzimSurfTomo_amd
   character(len=80) :: datafile
   type(para_t) :: p
   logical :: ex, iso_mod
+  integer, allocatable :: dper(:)           ! virtual period of every datum (typed data: the type columns of Traveltime_statis)
+  integer :: wavetp_i, veltp_i
   logical, external :: ti_kernels_on_device
   integer :: nx, ny, nz, nsrc, nrc, maxiter, kmaxRc, kmax
   real :: goxd, gozd, dvxd, dvzd, minthk, Minvel, Maxvel, spfra, weightVs, weightGcs, damp
@@ -137,6 +139,12 @@ program DAzimSurfTomo_amd
   write (*, *) 'number of period'
   write (*, '(i6)') kmaxRc
   if (kmaxRc <= 0) stop 'Can only deal with Rayleigh wave phase velocity data!'
+  if (p%typed .and. .not. iso_mod) then
+    write (*, '(a)') ' ERROR: DAzimSurfTomo_amd, joint mode (iso_mod = F): para.in lists Rayleigh group or Love-wave periods; the 2-psi'
+    write (*, '(a)') ' depth kernels (Lsen_Gsc) exist for Rayleigh phase velocities only.  Invert such data in iso mode (iso_mod = T).'
+    stop 'joint mode takes Rayleigh phase velocities only'
+  end if
+  if (p%typed) call dazim_set_segments(p%nseg, p%seg_wavetp, p%seg_veltp, p%seg_kmax)
   write (logfile, '(a,a)') trim(inputfile), '_inv.log'
   open (66, file=logfile)
   write (66, *)
@@ -156,7 +164,7 @@ program DAzimSurfTomo_amd
   kmax = kmaxRc
 
   ! ---- traveltime data file, inv/Main_Jt.f90:240-318 -------------------------------------------------
-  call read_data(p, scxf, sczf, rcxf, rczf, periods, nrc1, nsrc1, obst, dist, dall)
+  call read_data(p, scxf, sczf, rcxf, rczf, periods, nrc1, nsrc1, obst, dist, dall, dper)
 
   maxvp = (nx - 2)*(ny - 2)*(nz - 1)
   maxnar = int(spfra*real(dall)*real(nx)*real(ny)*real(nz)*3.0, 8)     ! sparsity fraction, inv/Main_Jt.f90:324
@@ -308,6 +316,10 @@ program DAzimSurfTomo_amd
     write (66, '(a,3f8.2)') '  damp,  lamebda Gsc, lamebda Vs: ', damp, weightGcs, weightVs
     m = dall + count3
     n = maxm
+    if (p%typed) then                         ! (typed data only: the log of Rayleigh phase input keeps its bytes)
+      write (6, '(a,i9,a,i9,a,i12)') '  [G; L] rows m =', m, '  unknowns n =', n, '  entries nnz =', dazim_allsum_int8(int(nar1, 8)) + nreg
+      write (66, '(a,i9,a,i9,a,i12)') '  [G; L] rows m =', m, '  unknowns n =', n, '  entries nnz =', dazim_allsum_int8(int(nar1, 8)) + nreg
+    end if
 
     call tick(5)                             ! Tikhonov rows
     ! ---- LSMR on the device, inv/Main_Jt.f90:534-574 ----------------------------------------------------------------
@@ -383,10 +395,18 @@ program DAzimSurfTomo_amd
     if (iter == 1 .or. iter == maxiter) then            ! inv/Main_Jt.f90:701-718 (id stays '00' in the reference)
       open (88, file='Traveltime_statis_00th.dat')
       if (iso_mod) then
+        if (p%typed) then                     ! two trailing columns: wavetp veltp
+          write (88, '(7a)') '   Dist(km)   T_obs(s)  T_ref_iso   Res(in)   dT(dvs)   Res(out) wavetp veltp'
+          do i = 1, dall
+            call period_type(p, dper(i), wavetp_i, veltp_i)
+            write (88, '(3f10.3, 3e12.3, 2i3)') dist(i), obst(i), dsyn(i), Tdata(i), fwdTvs(i), resbst(i), wavetp_i, veltp_i
+          end do
+        else
         write (88, '(7a)') '   Dist(km)   T_obs(s)  T_ref_iso   Res(in)   dT(dvs)   Res(out)'
         do i = 1, dall
           write (88, '(3f10.3, 3e12.3)') dist(i), obst(i), dsyn(i), Tdata(i), fwdTvs(i), resbst(i)
         end do
+        end if
       else
         write (88, '(7a)') '          Dist(km)       T_obs(s)        T_ref-iso        Res(in)   ', &
           'dT(aa)        dT(dvs)        Res(out)'

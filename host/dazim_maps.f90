@@ -82,6 +82,7 @@ program SurfPhaseMaps_amd
   tRc = p%tRc
   if (nz <= 1) stop 'error nz value.'
   if (kmax <= 0) stop 'Can only deal with Rayleigh wave phase velocity data!'
+  if (p%typed) call dazim_set_segments(p%nseg, p%seg_wavetp, p%seg_veltp, p%seg_kmax)
   weight_c = p%weightVs; weight_a = p%weightGcs
   call optional_arg(2, weight_c)
   call optional_arg(3, weight_a)
@@ -122,8 +123,8 @@ program SurfPhaseMaps_amd
   ! ---- starting maps: MOD's dispersion curves (= the 3-D program's first-iteration pvRc) ----------------------------------------
   call dazim_init(0)
   allocate (pv(nx*ny, kmax))
-  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_null_ptr, c_null_ptr, &
-                                            c_null_ptr, nfail), 'starting maps')
+  call dazim_check(dazim_dispersion_any(dazim_handle, nx, ny, nz, vsf, depz, minthk, kmax, tRc, pv, c_null_ptr, c_null_ptr, &
+                                        c_null_ptr, nfail), 'starting maps')
   if (nfail > 0) write (6, *) 'WARNING:improper initial value in disper - no zero found', nfail
   allocate (dsyn(dall), Tdata(dall), datweight(dall), cbst(dall + nm), dm(nm), a1(ncell*kmax), a2(ncell*kmax), w(kmax*nblk))
   allocate (ustats(3, kmax, 3), y(dall + nm), after(dall), dws(nm), sfc(nm), ones(dall))

@@ -101,6 +101,11 @@ program SurfDepthMC_amd
   Minvel = p%Minvel; Maxvel = p%Maxvel; kmax = p%kmaxRc; tRc = p%tRc
   if (nz <= 1) error stop 'error nz value.'
   if (kmax <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
+  if (p%typed) then
+    write (*, '(a)') ' ERROR: SurfDepthMC_amd: para.in lists Rayleigh group or Love-wave periods; the Monte-Carlo forward model is the'
+    write (*, '(a)') ' Rayleigh phase-velocity kernel.  Use SurfDepthFromMaps_amd for maps of other wave types.'
+    error stop 'SurfDepthMC_amd takes Rayleigh phase velocities only'
+  end if
   nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1; proposal = 0; ntemp = 1; tmax = 16
   call optional_arg(2, nsample)
   call optional_arg(3, nchain)

@@ -37,6 +37,8 @@ module dazim_mod
             dazim_map_tradeoff, dazim_map_tradeoff_total
   ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
   public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq, dazim_column_resolution
+  ! depthkernel for every wave type: Rayleigh / Love, phase / group velocities in one table over virtual periods
+  public :: dazim_dispersion_kernels_typed, dazim_set_segments, dazim_typed, dazim_dispersion_any
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
   public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
             dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds, &
@@ -48,6 +50,10 @@ module dazim_mod
   real(8), save, public :: dazim_dev_seconds(5) = 0
 
   type(c_ptr), save :: dazim_handle = c_null_ptr
+  ! the wave types of the periods (dazim_set_segments, from para.in through dazim_io's read_para): segments of (iwave, igr, kmax) laid
+  ! end to end as virtual periods.  None set, or Rayleigh phase alone: every call below is the Rayleigh-phase call it always was.
+  integer, save :: seg_n = 0
+  integer(c_int), save :: seg_iwave(4) = 0, seg_igr(4) = 0, seg_kmax(4) = 0
   ! the matrix of the last aprod call (see aprod) and how often it had to be (re)built
   type(c_ptr), save :: aprod_A = c_null_ptr
   integer(c_intptr_t), save :: aprod_iw = 0, aprod_rw = 0
@@ -91,6 +97,18 @@ module dazim_mod
       type(c_ptr), value :: ctx, svs, svp, srho     ! all three c_loc(array), or all three c_null_ptr (phase velocities only)
       integer(c_int), value :: nx, ny, nz, kmax
       real(c_float), value :: sublayers
+      real(c_float) :: vel(*), depz(*)
+      real(c_double) :: periods(*), pv(*)
+      integer(c_int) :: nfail
+    end function
+    ! segments of (iwave, igr, kmax), periods [sum of seg_kmax] segment after segment; pv [K][nx*ny], svs / svp / srho [nz][K][nx*ny]
+    integer(c_int) function dazim_dispersion_kernels_typed(ctx, nx, ny, nz, vel, depz, sublayers, nseg, seg_iwave, seg_igr, seg_kmax, &
+        periods, pv, svs, svp, srho, nfail) bind(C, name="dazim_dispersion_kernels_typed")
+      import
+      type(c_ptr), value :: ctx, svs, svp, srho     ! all three c_loc(array), or all three c_null_ptr (velocities only)
+      integer(c_int), value :: nx, ny, nz, nseg
+      real(c_float), value :: sublayers
+      integer(c_int) :: seg_iwave(*), seg_igr(*), seg_kmax(*)
       real(c_float) :: vel(*), depz(*)
       real(c_double) :: periods(*), pv(*)
       integer(c_int) :: nfail
@@ -779,6 +797,37 @@ contains
     stop
   end subroutine
 
+  ! the wave types of the kmaxRc (virtual) periods every later call is given: nseg segments, iwave 1 Love / 2 Rayleigh, igr 0 phase /
+  ! 1 group velocity, kmax periods each (para_t's seg_wavetp, seg_veltp, seg_kmax)
+  subroutine dazim_set_segments(nseg, iwave, igr, kmax)
+    integer, intent(in) :: nseg, iwave(:), igr(:), kmax(:)
+    if (nseg < 0 .or. nseg > 4) stop 'dazim_set_segments: 0..4 segments'
+    seg_n = nseg
+    seg_iwave(1:nseg) = iwave(1:nseg); seg_igr(1:nseg) = igr(1:nseg); seg_kmax(1:nseg) = kmax(1:nseg)
+  end subroutine
+
+  logical function dazim_typed()            ! a segment other than Rayleigh phase is set
+    dazim_typed = any(seg_iwave(1:seg_n) /= 2 .or. seg_igr(1:seg_n) /= 0)
+  end function
+
+  ! dazim_dispersion_kernels' argument list for whatever the periods are: the typed entry when a segment other than Rayleigh
+  ! phase is set (kmax = the virtual periods), the plain call otherwise
+  integer(c_int) function dazim_dispersion_any(ctx, nx, ny, nz, vel, depz, sublayers, kmax, periods, pv, svs, svp, srho, nfail) result(rc)
+    type(c_ptr), value :: ctx, svs, svp, srho
+    integer(c_int), value :: nx, ny, nz, kmax
+    real(c_float), value :: sublayers
+    real(c_float) :: vel(*), depz(*)
+    real(c_double) :: periods(*), pv(*)
+    integer(c_int) :: nfail
+    if (dazim_typed()) then
+      if (sum(seg_kmax(1:seg_n)) /= kmax) stop 'dazim_dispersion_any: the segments do not add up to the number of periods'
+      rc = dazim_dispersion_kernels_typed(ctx, nx, ny, nz, vel, depz, sublayers, int(seg_n, c_int), seg_iwave, seg_igr, seg_kmax, &
+                                          periods, pv, svs, svp, srho, nfail)
+    else
+      rc = dazim_dispersion_kernels(ctx, nx, ny, nz, vel, depz, sublayers, kmax, periods, pv, svs, svp, srho, nfail)
+    end if
+  end function
+
   ! ---- inv/surfdisp96.f:52, the subroutine's own argument list (one model per call; dazim_surfdisp96 takes batches) ----
   subroutine surfdisp96(thkm, vpm, vsm, rhom, nlayer, iflsph, iwave, mode, igr, kmax, t, cg)
     integer :: nlayer, iflsph, iwave, mode, igr, kmax
@@ -799,11 +848,17 @@ contains
     real*8 :: pvRc(nx*ny, kmaxRc)
     real*8, target :: sen_vsRc(nx*ny, kmaxRc, nz), sen_vpRc(nx*ny, kmaxRc, nz), sen_rhoRc(nx*ny, kmaxRc, nz)
     real*8 :: tRc(kmaxRc)
-    integer(c_int) :: nfail
-    if (iwave /= 2 .or. igr /= 0) stop 'Can only deal with Rayleigh wave phase velocity data!'  ! inv/Main_Jt.f90:213
+    integer(c_int) :: nfail, s_iw(1), s_ig(1), s_km(1)
+    if ((iwave /= 1 .and. iwave /= 2) .or. (igr /= 0 .and. igr /= 1)) stop 'depthkernel: iwave 1 (Love) or 2 (Rayleigh), igr 0 or 1'
     call dazim_init(0)
-    call check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vel, depz, minthk, kmaxRc, tRc, pvRc, &
-                                        c_loc(sen_vsRc), c_loc(sen_vpRc), c_loc(sen_rhoRc), nfail), 'depthkernel')
+    if (iwave /= 2 .or. igr /= 0) then        ! one segment of that type (the reference's programs stop here, inv/Main_Jt.f90:213)
+      s_iw = iwave; s_ig = igr; s_km = kmaxRc
+      call check(dazim_dispersion_kernels_typed(dazim_handle, nx, ny, nz, vel, depz, minthk, 1_c_int, s_iw, s_ig, s_km, tRc, pvRc, &
+                                                c_loc(sen_vsRc), c_loc(sen_vpRc), c_loc(sen_rhoRc), nfail), 'depthkernel')
+    else
+      call check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vel, depz, minthk, kmaxRc, tRc, pvRc, &
+                                          c_loc(sen_vsRc), c_loc(sen_vpRc), c_loc(sen_rhoRc), nfail), 'depthkernel')
+    end if
     if (nfail > 0) write (6, *) 'WARNING:improper initial value in disper - no zero found', nfail   ! inv/surfdisp96.f:311
   end subroutine
 
@@ -988,8 +1043,15 @@ contains
     call check(dazim_set_option(dazim_handle, 'disp.async'//c_null_char, 1_c_int), 'option')
     ! several ranks: this rank's block of the model's rows (the reference's OMP loop over jj, inv/CalSurfG.f90:39-43), tables
     ! joined by all-gathers inside the library -- pvRc before the call returns, the depth kernels behind the perturbed copies
-    call check(dazim_dispersion_kernels_sharded(dazim_handle, nx, ny, nz, dvel, depz, minthk, kmaxRc, tRc, pv, p_svs, p_svp, &
-                                                p_srho, nfail), 'CalSurfG/depthkernel')
+    if (dazim_typed()) then                  ! (every rank computes the other wave types' segments in full)
+      if (joint) stop 'dazim_assemble_G: joint rows need the 2-psi kernels, which exist for Rayleigh phase velocities only'
+      if (sum(seg_kmax(1:seg_n)) /= kmaxRc) stop 'dazim_assemble_G: the segments do not add up to the number of periods'
+      call check(dazim_dispersion_kernels_typed(dazim_handle, nx, ny, nz, dvel, depz, minthk, int(seg_n, c_int), seg_iwave, seg_igr, &
+                                                seg_kmax, tRc, pv, p_svs, p_svp, p_srho, nfail), 'CalSurfG/depthkernel')
+    else
+      call check(dazim_dispersion_kernels_sharded(dazim_handle, nx, ny, nz, dvel, depz, minthk, kmaxRc, tRc, pv, p_svs, p_svp, &
+                                                  p_srho, nfail), 'CalSurfG/depthkernel')
+    end if
     call check(dazim_set_option(dazim_handle, 'disp.async'//c_null_char, 0_c_int), 'option')   ! (the handle is shared: only this call)
     if (nfail > 0) write (6, *) 'WARNING:improper initial value in disper - no zero found', nfail   ! inv/surfdisp96.f:311
     t_curves = max(dazim_last_kernel_seconds(dazim_handle, 'disp'//c_null_char), 0.0_c_double)

@@ -116,6 +116,24 @@ int dazim_surfdisp96(dazim_ctx *ctx, int nmodel, int nlayer_max, const int *nlay
                      const float *vs, const float *rho, int iflsph, int iwave, int mode, int igr, int kmax,
                      const double *periods, double *cg, int *n_failed);
 
+/* ---- K1 for every wave type: dispersion + depth kernels of Rayleigh / Love, phase / group velocities in one table -----------
+ * = depthkernel (inv/CalSurfG.f90:1-139) called once per segment with that segment's (iwave, igr): mode 1, iflsph 1, the same
+ *   Brocher / refineGrid2LayerMdl / +-0.5 % arithmetic as dazim_dispersion_kernels.  The tables are indexed by a "virtual period":
+ *   the segments' periods laid end to end, K = sum of seg_kmax, which is all that dazim_fmm_batch, dazim_rays_build_G*,
+ *   dazim_vs_kernels and the column solves see of a wave type.
+ *  nseg 1..4; seg_iwave [nseg] 1 Love / 2 Rayleigh; seg_igr [nseg] 0 phase / 1 group; seg_kmax [nseg] 1..60 (host arrays); a pair
+ *  (iwave, igr) may appear once.  periods [K] (host), segment after segment.  vel, depz, sublayers as for dazim_dispersion_kernels.
+ *  pv [K][nx*ny]; sen_vs, sen_vp, sen_rho [nz][K][nx*ny] fp64, nullable (all three or none; one or two of them: refused)
+ *  The Rayleigh-phase segment (2, 0) is computed by dazim_dispersion_kernels and its rows are that call's bits; a call whose only
+ *  segment it is IS that call.  The other segments run surfdisp96's own root search (the device functions of dazim_surfdisp96) on
+ *  layer stacks built on the device, one lane per (column, variant): equal, bit for bit, to depthkernel composed of
+ *  dazim_surfdisp96 calls.  sen_vp of a Love segment is 0.  A curve ends at its first period without a root (pv = 0 from there on,
+ *  as the subroutine leaves it; sen_* = 0 at those entries); n_failed counts such entries of all segments, nullable.
+ *  With a communicator attached every rank computes every segment in full.                                            */
+int dazim_dispersion_kernels_typed(dazim_ctx *ctx, int nx, int ny, int nz, const float *vel, const float *depz, float sublayers,
+                                   int nseg, const int *seg_iwave, const int *seg_igr, const int *seg_kmax, const double *periods,
+                                   double *pv, double *sen_vs, double *sen_vp, double *sen_rho, int *n_failed);
+
 /* ---- N1: TI eigenfunction partials -> azimuthal depth kernels ---------------------------------------
  * = depthkernelTI (inv/depthkernelTI.f90:2) calling tregn96 (inv/tregn96.f:52) once per column: Rayleigh fundamental-mode
  *   eigenfunctions of the flattened TI column (A=C=rho*Vp^2, L=N=rho*Vs^2, F=A-2L), partials dc/dah, dc/dbv, dc/dn with the
