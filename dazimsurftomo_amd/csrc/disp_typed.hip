@@ -14,7 +14,9 @@
 //           tables built by the wavefront from the column's knots -- a base table per column and, per lane, the few layers its one
 //           perturbed knot touches (the layout of disp.hip's TableLayers) -- with the thickness-only Earth-flattening factors of
 //           both wave types from a host table.  The layers are the ones the host prologue would have formed, bit for bit
-//           (tests/test_disp_typed_gpu.py compares the tables with dazim_surfdisp96 on host-built stacks: equal).
+//           (tests/test_disp_typed_gpu.py compares the tables with dazim_surfdisp96 on host-built stacks: equal).  The plans with
+//           fewer than 64 items per workgroup are run by tests/test_disp_typed_shapes_gpu.py; a curves-only call (one base table per
+//           item) takes them from 14 knots on at sublayers = 3 (32 items; 16 from 26 knots, 8 from 47).
 //   Love    does not read Vp except through the start value of the first search (gtsolh of the slowest layer), which moves a root
 //           by less than the search tolerance: sen_vp of a Love segment is defined as 0, and its 2 nz Vp copies are not run.
 // A period without a root ends the curve (zeros from there on, counted in n_failed); the depth kernels of such an entry are 0.
