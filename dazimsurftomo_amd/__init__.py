@@ -613,14 +613,16 @@ class Context:
         return out
 
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
-                  ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None, prior=None):
+                  ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None, prior=None, segments=None, noise_groups=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
         cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
         data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal).  ntemp > 1: parallel
         tempering with ntemp rungs up to temperature tmax and a swap round every nswap steps (MonteCarlo.set_tempering).  aniso: a
         dict of MonteCarlo.set_aniso's arguments (nthin, amap, wa, smooth, damp) switches the Gc/Gs posteriors on.  noise: (a0, b0)
         makes the data-noise scale of every cell an unknown with the prior lambda^2 ~ InverseGamma(a0, b0) (MonteCarlo.set_noise).
-        prior: (smooth, damp) or (smooth, damp, vref) adds the Gaussian smoothness prior to the box (MonteCarlo.set_prior)."""
+        prior: (smooth, damp) or (smooth, damp, vref) adds the Gaussian smoothness prior to the box (MonteCarlo.set_prior).
+        segments: [(iwave, igr, periods), ...] makes the kmax periods those of several wave types (MonteCarlo.set_segments).
+        noise_groups: (group_of_period, a0, b0) gives every group of periods a noise scale of its own (MonteCarlo.set_noise_groups)."""
         nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
         vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
         vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
@@ -641,6 +643,10 @@ class Context:
             mc.set_noise(*noise)
         if prior is not None:
             mc.set_prior(*prior)
+        if segments is not None:
+            mc.set_segments(segments)
+        if noise_groups is not None:
+            mc.set_noise_groups(*noise_groups)
         return mc
 
     def ray_paths(self):
@@ -890,6 +896,54 @@ class MonteCarlo:
         self.ctx._check(self.ctx.lib.dazim_mc_noise_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in ("lam_mean", "lam_std", "ndata"))))
         return r
 
+    def set_noise_groups(self, group_of_period, a0, b0):
+        """one noise scale per group of periods (dazim_mc_set_noise_groups): group_of_period[kmax] in 0..G-1, a0, b0[G], G <= 4; the
+        data std of a period of group g is lambda_g / w with lambda_g^2 ~ InverseGamma(a0[g], b0[g]), every lambda_g integrated out.
+        One group is set_noise(a0[0], b0[0]); every a0 0 is the default, the fixed noise level.  Refused once a step has been done"""
+        grp = np.ascontiguousarray(group_of_period, np.int32).ravel()
+        a0, b0 = np.ascontiguousarray(a0, np.float32).ravel(), np.ascontiguousarray(b0, np.float32).ravel()
+        if len(grp) != self.kmax or len(a0) != len(b0):
+            raise DazimError(DAZIM_E_BAD_ARG, f"set_noise_groups: {len(grp)} periods for a handle of {self.kmax}, {len(a0)} a0 and "
+                                              f"{len(b0)} b0")
+        self.ctx._check(self.ctx.lib.dazim_mc_set_noise_groups(self.ctx._h, self._h, len(a0), _ptr(grp), _ptr(a0), _ptr(b0)))
+
+    def noise_groups_state(self):
+        """the groups and, while a noise mode is on, copies of their record (dazim_mc_noise_groups_state): dict ngroup,
+        group_of_period[kmax], a0, b0[G], chi2g[G][ncol] (the chi2 of every chain's state per group), nsum[2][G][ncol], ncnt[ncol];
+        dict ngroup = 0 alone while it is off"""
+        ng = C.c_int(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_noise_groups_state(self.ctx._h, self._h, C.byref(ng), None, None, None, None, None, None))
+        G = ng.value
+        if G == 0:
+            return dict(ngroup=0)
+        out = dict(ngroup=G, group_of_period=np.zeros(self.kmax, np.int32), a0=np.zeros(G, np.float32), b0=np.zeros(G, np.float32),
+                   chi2g=np.zeros((G, self.ncol), np.float64), nsum=np.zeros((2, G, self.ncol), np.float64),
+                   ncnt=np.zeros(self.ncol, np.int64))
+        self.ctx._check(self.ctx.lib.dazim_mc_noise_groups_state(self.ctx._h, self._h, None, *(_ptr(out[k]) for k in
+                                                                 ("group_of_period", "a0", "b0", "chi2g", "nsum", "ncnt"))))
+        return out
+
+    def noise_groups_result(self):
+        """the posterior of every group's noise scale per inner cell (dazim_mc_noise_groups_result): dict lam_mean, lam_std
+        [G][ny-2][nx-2] (fp32) and ndata [G][ny-2][nx-2] (int32), the cell's periods with data in the group"""
+        ng = C.c_int(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_noise_groups_state(self.ctx._h, self._h, C.byref(ng), None, None, None, None, None, None))
+        shp = (max(ng.value, 1), self.ny - 2, self.nx - 2)
+        r = dict(lam_mean=np.zeros(shp, np.float32), lam_std=np.zeros(shp, np.float32), ndata=np.zeros(shp, np.int32))
+        self.ctx._check(self.ctx.lib.dazim_mc_noise_groups_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in
+                                                                                           ("lam_mean", "lam_std", "ndata"))))
+        return r
+
+    def set_segments(self, segments):
+        """typed data (dazim_mc_set_segments): segments = [(iwave, igr, periods), ...] as Context.dispersion_kernels_typed takes them
+        (iwave 1 Love / 2 Rayleigh, igr 0 phase / 1 group; periods an array or its length); the handle's kmax periods are the
+        segments' laid end to end, and run() then takes those virtual periods.  [(2, 0, t)] is the default.  Refused once a step has
+        been done"""
+        iw = np.ascontiguousarray([s[0] for s in segments], np.int32)
+        ig = np.ascontiguousarray([s[1] for s in segments], np.int32)
+        km = np.ascontiguousarray([s[2] if np.isscalar(s[2]) else len(s[2]) for s in segments], np.int32)
+        self.ctx._check(self.ctx.lib.dazim_mc_set_segments(self.ctx._h, self._h, len(segments), _ptr(iw), _ptr(ig), _ptr(km)))
+
     def set_prior(self, smooth, damp, vref=None):
         """Gaussian smoothness prior (dazim_mc_set_prior): column_lsq's regulariser as a prior of precision smooth^2 L^T L +
         damp^2 I about vref[nz-1][ny-2][nx-2] (None: vel0's knots), truncated by the box; every decision is then taken on the energy
@@ -923,7 +977,7 @@ class MonteCarlo:
 
     def run(self, depz, sublayers, periods, nburn, nsample):
         """nburn burn-in and nsample recorded steps with the dispersion forward model (dazim_mc_run); returns the proposals without
-        a root"""
+        a root.  After set_segments, periods are the virtual periods, segment after segment"""
         depz = np.ascontiguousarray(depz, np.float32)
         periods = np.ascontiguousarray(periods, np.float64)
         assert len(depz) == self.nz and len(periods) == self.kmax

@@ -103,6 +103,14 @@ def load():
     lib.dazim_mc_noise_state.argtypes = [C.c_void_p] * 6
     lib.dazim_mc_noise_result.restype = C.c_int
     lib.dazim_mc_noise_result.argtypes = [C.c_void_p] * 5
+    lib.dazim_mc_set_noise_groups.restype = C.c_int
+    lib.dazim_mc_set_noise_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dazim_mc_noise_groups_state.restype = C.c_int
+    lib.dazim_mc_noise_groups_state.argtypes = [C.c_void_p] * 9
+    lib.dazim_mc_noise_groups_result.restype = C.c_int
+    lib.dazim_mc_noise_groups_result.argtypes = [C.c_void_p] * 5
+    lib.dazim_mc_set_segments.restype = C.c_int
+    lib.dazim_mc_set_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dazim_mc_set_prior.restype = C.c_int
     lib.dazim_mc_set_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.dazim_mc_prior_state.restype = C.c_int

@@ -20,6 +20,14 @@
 // in place of chi^2 (mc_energy), each recorded rung-0 lane adds sqrt(B) and B = b0 + chi^2 / 2 of its state to its own column, and
 // k_mc_noise_final turns those sums into the posterior mean and std of lambda per cell (Rao-Blackwellisation again).
 //
+// One noise scale per group of periods (dazim_mc_set_noise_groups, G >= 2 groups): lambda_g^2 ~ InverseGamma(a0_g, b0_g), each integrated
+// out as above, so the energy is X = sum_g 2 a_g log(b0_g + chi^2_g / 2) over the groups with data in the cell.  k_mc_step<KIND, TEMPER, 2>
+// forms chi^2_g beside chi^2 in the one loop over the periods, keeps the chi^2_g of every chain's state in chi2g [G][ncol] and records
+// sqrt(B_g) and B_g per group; k_mc_noise_groups_final is k_mc_noise_final per (group, cell).  One group is the mode above itself.
+//
+// Typed data (dazim_mc_set_segments): dazim_mc_run computes the proposals' curves with dazim_dispersion_kernels_typed, the handle's
+// periods being the virtual periods of the segments laid end to end; the step never asks what kind of wave a period is.
+//
 // Gaussian smoothness prior (dazim_mc_set_prior): dazim_column_lsq's regulariser read as a prior, exp(-Q / 2) with Q = d^T (smooth^2
 // L^T L + damp^2 I) d, d the state's knots minus a reference, inside the box.  k_mc_step<KIND, TEMPER, NOISE, 1> takes every decision
 // on E + Q in place of E (mc_prior_q; a rung samples (likelihood x Gaussian prior)^beta) and keeps the Q of every chain's state
@@ -37,6 +45,47 @@ template <int NOISE>
 __device__ __forceinline__ double mc_energy(const McDev &M, double a, double chi2) {
   if constexpr (NOISE) return 2.0 * a * log((double)M.nb0 + 0.5 * chi2);
   else return chi2;
+}
+
+// NOISE 2: X = sum over the groups g < ngrp with ndg[g] > 0, in group order, of 2 a_g log(B_g(chi^2_g)), a_g = a0_g + ndg[g] / 2; +inf
+// where the total chi^2 is (a chi^2_g is +inf only then)
+__device__ __forceinline__ double mc_energy_groups(const McDev &M, const int (&ndg)[MC_MAXGRP], const double (&cg)[MC_MAXGRP], double chi2) {
+  if (isinf(chi2)) return INFINITY;
+  double x = 0.0;
+#pragma unroll
+  for (int g = 0; g < MC_MAXGRP; g++)
+    if (g < M.ngrp && ndg[g] > 0) x += 2.0 * ((double)M.ga0[g] + 0.5 * ndg[g]) * log((double)M.gb0[g] + 0.5 * cg[g]);
+  return x;
+}
+
+// NOISE 2: the total chi^2 of column col's curves, today's sum in period order, and beside it chi^2_g of every group (each in period
+// order within its group: the other groups add nothing) and nd_g, the group's periods with data in the cell.  A period with data and
+// no root makes the total and its group +inf
+__device__ __forceinline__ double mc_chi2_groups(const McDev &M, const double *__restrict__ pv, int cell, long col, double (&cgp)[MC_MAXGRP],
+                                                 int (&ndg)[MC_MAXGRP]) {
+  double chi2p = 0.0;
+  for (int p = 0; p < M.kmax; p++) {
+    const float w = M.wdat[(long)p * M.ncell + cell];
+    if (w == 0.0f) continue;
+    const int gp = M.grp[p];
+#pragma unroll
+    for (int g = 0; g < MC_MAXGRP; g++) ndg[g] += gp == g;
+    const double c = pv[(long)p * M.ncol + col];
+    if (c == 0.0) {
+      chi2p = INFINITY;
+#pragma unroll
+      for (int g = 0; g < MC_MAXGRP; g++)
+        if (gp == g) cgp[g] = INFINITY;
+      continue;
+    }
+    const double r = (double)w * ((double)M.cobs[(long)p * M.ncell + cell] - c);
+    const double rr = r * r;
+    chi2p += rr;
+#pragma unroll
+    for (int g = 0; g < MC_MAXGRP; g++)
+      if (gp == g) cgp[g] += rr;
+  }
+  return chi2p;
 }
 
 // the prior energy Q = ps2 |L d|^2 + pd2 |d|^2 of column col of v [nz][ncol] (cur or prop), d = v - pref over the nlay sampled knots;
@@ -239,6 +288,10 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
 // the rung-0 lanes record.  Each lane carries its chi^2 in a register from the decision through the swap.
 // NOISE 1 (dazim_mc_set_noise): the lane counts the cell's nd in its weight loop, the decision and the swap compare mc_energy of the
 // two chi^2, and a recorded lane adds sqrt(B) and B of its state to its own column of nsum.  The handle keeps raw chi^2 throughout.
+// NOISE 2 (dazim_mc_set_noise_groups, ngrp >= 2): the weight loop also forms chi^2_g and nd_g of every group (cgp, ndg), the decision
+// compares mc_energy_groups of the two states, each lane carries the chi^2_g of its state (cgs, 4 doubles) and its energy through the
+// swap, whose rule compares the two lanes' own energies (a_g is the cell's, so the partner's value is the one this lane would form),
+// the chi^2_g change lanes with the knots, and a recorded lane adds sqrt(B_g) and B_g per group with data.  chi2 stays the total.
 // PRIOR 1 (dazim_mc_set_prior): the lane walks its column of prop for Q', the decision and the swap compare energy + Q (the rules
 // for +inf still test chi^2 alone), Q travels beside chi^2 through the swap's shuffles, and pq keeps the Q of the lane's state.
 template <int KIND, int TEMPER, int NOISE, int PRIOR>
@@ -259,22 +312,29 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
   double chi2s = INFINITY;   // TEMPER: the chain's chi^2 after the decision, then after the swap
   unsigned wswap = 0u;       // TEMPER: word 1 of block(step, gid, 0), the swap uniform of a pair's lower chain
   double qp = 0.0, qs = 0.0;   // PRIOR: Q of the proposal; Q of the chain's state after the decision, then after the swap
+  double cgp[MC_MAXGRP] = {0.0, 0.0, 0.0, 0.0};   // NOISE 2: chi^2_g of the proposal
+  double cgs[MC_MAXGRP] = {INFINITY, INFINITY, INFINITY, INFINITY};   // ... of the chain's state after the decision, then the swap
+  int ndg[MC_MAXGRP] = {0, 0, 0, 0};              // ... the cell's periods with data per group
   bool acc = false;
   if (act) {
-    for (int p = 0; p < M.kmax; p++) {
-      const float w = M.wdat[(long)p * M.ncell + cell];
-      if (w == 0.0f) continue;
-      nd++;
-      const double c = pv[(long)p * M.ncol + col];
-      if (c == 0.0) {   // no root at a period with data
-        chi2p = INFINITY;
-        if constexpr (NOISE) continue;   // (nd needs the rest of the loop; +inf stays)
-        else break;
+    if constexpr (NOISE == 2) {
+      chi2p = mc_chi2_groups(M, pv, cell, col, cgp, ndg);
+    } else {
+      for (int p = 0; p < M.kmax; p++) {
+        const float w = M.wdat[(long)p * M.ncell + cell];
+        if (w == 0.0f) continue;
+        nd++;
+        const double c = pv[(long)p * M.ncol + col];
+        if (c == 0.0) {   // no root at a period with data
+          chi2p = INFINITY;
+          if constexpr (NOISE) continue;   // (nd needs the rest of the loop; +inf stays)
+          else break;
+        }
+        const double r = (double)w * ((double)M.cobs[(long)p * M.ncell + cell] - c);
+        chi2p += r * r;
       }
-      const double r = (double)w * ((double)M.cobs[(long)p * M.ncell + cell] - c);
-      chi2p += r * r;
     }
-    if constexpr (NOISE) na = (double)M.na0 + 0.5 * nd;
+    if constexpr (NOISE == 1) na = (double)M.na0 + 0.5 * nd;
     if constexpr (PRIOR) qp = mc_prior_q(M, M.prop, col, cell);
     if (first) {
       acc = true;
@@ -282,7 +342,17 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       // a chain without a curve takes the first proposal that has one; else Metropolis on the energies at the rung's beta (1 without
       // a ladder, which leaves the product's bits alone).  Where the first rule decides only a ladder draws block 0, for its word 1
       const double chi2c = M.chi2[col];
-      const double xp = mc_energy<NOISE>(M, na, chi2p), xc = mc_energy<NOISE>(M, na, chi2c);
+      double xp, xc;
+      if constexpr (NOISE == 2) {
+#pragma unroll
+        for (int g = 0; g < MC_MAXGRP; g++)
+          if (g < M.ngrp) cgs[g] = M.chi2g[(long)g * M.ncol + col];
+        xp = mc_energy_groups(M, ndg, cgp, chi2p);
+        xc = mc_energy_groups(M, ndg, cgs, chi2c);
+      } else {
+        xp = mc_energy<NOISE>(M, na, chi2p);
+        xc = mc_energy<NOISE>(M, na, chi2c);
+      }
       double beta = 1.0;
       if constexpr (TEMPER) beta = M.beta[rung];
       unsigned w[4] = {0u, 0u, 0u, 0u};
@@ -300,6 +370,13 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       for (int k = 0; k < M.nlay; k++) M.cur[k * M.ncol + col] = M.prop[k * M.ncol + col];
       M.chi2[col] = chi2p;
       chi2s = chi2p;
+      if constexpr (NOISE == 2) {
+#pragma unroll
+        for (int g = 0; g < MC_MAXGRP; g++) {
+          cgs[g] = cgp[g];
+          if (g < M.ngrp) M.chi2g[(long)g * M.ncol + col] = cgp[g];
+        }
+      }
       if constexpr (PRIOR) {
         M.pq[col] = qp;
         qs = qp;
@@ -322,11 +399,19 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         qup = __shfl_down(qs, 1);
         qdn = __shfl_up(qs, 1);
       }
+      double xs = 0.0, xup = 0.0;   // NOISE 2: the energy of the lane's state, and of the upper neighbour's
+      if constexpr (NOISE == 2) {
+        xs = mc_energy_groups(M, ndg, cgs, chi2s);
+        xup = __shfl_down(xs, 1);
+      }
       int sw = 0;
       if (lower) {
         if (isinf(chi2s)) sw = !isinf(cup);
         else if (!isinf(cup)) {
-          if constexpr (PRIOR)
+          if constexpr (NOISE == 2) {
+            if constexpr (PRIOR) sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) * ((xs + qs) - (xup + qup));
+            else sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) * (xs - xup);
+          } else if constexpr (PRIOR)
             sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) *
                                               ((mc_energy<NOISE>(M, na, chi2s) + qs) - (mc_energy<NOISE>(M, na, cup) + qup));
           else
@@ -341,6 +426,16 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         const float v = act ? M.cur[k * M.ncol + col] : 0.0f;
         const float vp = __shfl(v, partner);
         if (swp) M.cur[k * M.ncol + col] = vp;
+      }
+      if constexpr (NOISE == 2) {
+#pragma unroll
+        for (int g = 0; g < MC_MAXGRP; g++) {
+          const double cp = __shfl(cgs[g], partner);
+          if (swp) {
+            cgs[g] = cp;
+            if (g < M.ngrp) M.chi2g[(long)g * M.ncol + col] = cp;
+          }
+        }
       }
       if (swp) {
         chi2s = lower ? cup : cdn;
@@ -391,7 +486,18 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         b = b < 0 ? 0 : (b >= M.nbin ? M.nbin - 1 : b);
         atomicAdd(&M.hist[((long)cs * M.nlay + k) * M.nbin + b], 1u);
       }
-      if constexpr (NOISE) {
+      if constexpr (NOISE == 2) {
+        if (!isinf(M.chi2[col])) {   // (cgs: the state's chi^2_g, after the decision and the swap)
+#pragma unroll
+          for (int g = 0; g < MC_MAXGRP; g++)
+            if (g < M.ngrp && ndg[g] > 0) {
+              const double B = (double)M.gb0[g] + 0.5 * cgs[g];
+              M.nsum[(long)g * M.ncol + col] += sqrt(B);
+              M.nsum[((long)M.ngrp + g) * M.ncol + col] += B;
+            }
+          M.ncnt[col] += 1;
+        }
+      } else if constexpr (NOISE) {
         const double c2 = M.chi2[col];   // the lane's own store, after the decision and the swap
         if (!isinf(c2)) {
           const double B = (double)M.nb0 + 0.5 * c2;
@@ -581,12 +687,52 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_noise_final(McDev M, float *__re
   lam_std[cell] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
 }
 
+// the noise scales' posteriors (dazim_mc_noise_groups_result), one lane per (group, inner cell): k_mc_noise_final with the group's
+// periods, prior, sums and table; the record's count is the cell's.  With one group: k_mc_noise_final's values, bit for bit
+__global__ __launch_bounds__(MC_WAVE) void k_mc_noise_groups_final(McDev M, float *__restrict__ lam_mean, float *__restrict__ lam_std,
+                                                                   int *__restrict__ ndata) {
+  const long i = (long)blockIdx.x * MC_WAVE + threadIdx.x;
+  if (i >= (long)M.ngrp * M.ncell) return;
+  const int g = (int)(i / M.ncell), cell = (int)(i - (long)g * M.ncell);
+  const int cs = M.cs_of[cell];
+  int nd = 0;
+  for (int p = 0; p < M.kmax; p++) nd += M.grp[p] == g && M.wdat[(long)p * M.ncell + cell] != 0.0f;
+  ndata[i] = nd;
+  if (cs < 0 || nd == 0) {
+    lam_mean[i] = 0.0f;
+    lam_std[i] = 0.0f;
+    return;
+  }
+  long long n = 0;
+  double s0 = 0.0, s1 = 0.0;
+  for (int ch = 0; ch < M.nchain; ch += M.ntemp) {
+    const long col = (long)cs * M.nchain + ch;
+    n += M.ncnt[col];
+    s0 += M.nsum[(long)g * M.ncol + col];
+    s1 += M.nsum[((long)M.ngrp + g) * M.ncol + col];
+  }
+  if (n == 0) {
+    lam_mean[i] = NAN;
+    lam_std[i] = NAN;
+    return;
+  }
+  float a0 = 0.0f;
+#pragma unroll
+  for (int q = 0; q < MC_MAXGRP; q++)
+    if (q == g) a0 = M.ga0[q];
+  const double a = (double)a0 + 0.5 * nd, dn = (double)n;
+  const double lm = M.ngam[g * (MC_MAXPER + 1) + nd] * s0 / dn;
+  lam_mean[i] = (float)lm;
+  lam_std[i] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
+}
+
 // the step kernel of a handle: [prior][noise][kind][tempered]
 using McStepKernel = void (*)(McDev, const double *, long long, int, int, int, int);
 #define MC_STEP_SET(P)                                                                            \
   {{{k_mc_step<0, 0, 0, P>, k_mc_step<0, 1, 0, P>}, {k_mc_step<1, 0, 0, P>, k_mc_step<1, 1, 0, P>}}, \
-   {{k_mc_step<0, 0, 1, P>, k_mc_step<0, 1, 1, P>}, {k_mc_step<1, 0, 1, P>, k_mc_step<1, 1, 1, P>}}}
-constexpr McStepKernel MC_STEP[2][2][2][2] = {MC_STEP_SET(0), MC_STEP_SET(1)};
+   {{k_mc_step<0, 0, 1, P>, k_mc_step<0, 1, 1, P>}, {k_mc_step<1, 0, 1, P>, k_mc_step<1, 1, 1, P>}}, \
+   {{k_mc_step<0, 0, 2, P>, k_mc_step<0, 1, 2, P>}, {k_mc_step<1, 0, 2, P>, k_mc_step<1, 1, 2, P>}}}
+constexpr McStepKernel MC_STEP[2][3][2][2] = {MC_STEP_SET(0), MC_STEP_SET(1)};
 #undef MC_STEP_SET
 
 // the Q of every chain's state into pq (dazim_mc_set_prior; the step keeps it from there on), lane = chain
@@ -847,6 +993,58 @@ int dazim_mc_temper_state(dazim_ctx *ctx, dazim_mc *mc, int *ntemp, float *tmax,
   return 0;
 }
 
+// the noise mode of a handle that has not stepped: G = 0 off, else G groups with the validated priors (a0[g], b0[g]) and the group
+// grp[p] of every period (null: group 0).  The arrays are sized for MC_MAXGRP groups at the first call, so that a later one allocates
+// nothing but chi2g, which one group does not need
+static int mc_noise_setup(dazim_ctx *ctx, dazim_mc *mc, int G, const int *grp, const float *a0, const float *b0) {
+  McDev &M = mc->d;
+  int rc;
+  if (G == 0) {
+    M.na0 = M.nb0 = 0.0f;
+    M.ngrp = 0;
+    for (int g = 0; g < MC_MAXGRP; g++) M.ga0[g] = M.gb0[g] = 0.0f;
+    mc->noise = 0;
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  const size_t nc = (size_t)M.ncol;
+  if (!M.nsum) {
+    double *g;
+    int *q;
+    if ((rc = mc_alloc(mc, 2 * MC_MAXGRP * nc, &M.nsum)) || (rc = mc_alloc(mc, nc, &M.ncnt)) ||
+        (rc = mc_alloc(mc, (size_t)MC_MAXGRP * (MC_MAXPER + 1), &g)) || (rc = mc_alloc(mc, (size_t)M.kmax, &q)))
+      return rc;
+    M.ngam = g;
+    M.grp = q;
+  }
+  if (G > 1 && !M.chi2g && (rc = mc_alloc(mc, MC_MAXGRP * nc, &M.chi2g))) return rc;
+  // g(a) = Gamma(a - 1/2) / Gamma(a) at a = a0 + nd / 2 for every nd a cell can have: one table, so that host and device agree
+  std::vector<double> gam((size_t)G * (MC_MAXPER + 1));
+  for (int g = 0; g < G; g++)
+    for (int nd = 0; nd <= MC_MAXPER; nd++) {
+      const double a = (double)a0[g] + 0.5 * nd;
+      gam[(size_t)g * (MC_MAXPER + 1) + nd] = std::exp(std::lgamma(a - 0.5) - std::lgamma(a));
+    }
+  std::vector<int> gp((size_t)M.kmax, 0);
+  if (grp) gp.assign(grp, grp + M.kmax);
+  DZ_HIP(hipMemcpyAsync((void *)M.ngam, gam.data(), gam.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  DZ_HIP(hipMemcpyAsync((void *)M.grp, gp.data(), gp.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  DZ_HIP(hipMemsetAsync(M.nsum, 0, (2 * MC_MAXGRP * nc ? 2 * MC_MAXGRP * nc : 1) * sizeof(double), ctx->stream));
+  DZ_HIP(hipMemsetAsync(M.ncnt, 0, (nc ? nc : 1) * sizeof(long long), ctx->stream));
+  const std::vector<double> inf(G > 1 ? (size_t)G * nc : 0, (double)INFINITY);
+  if (!inf.empty()) DZ_HIP(hipMemcpyAsync(M.chi2g, inf.data(), inf.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  for (int g = 0; g < MC_MAXGRP; g++) {
+    M.ga0[g] = g < G ? a0[g] : 0.0f;
+    M.gb0[g] = g < G ? b0[g] : 0.0f;
+  }
+  M.na0 = G == 1 ? a0[0] : 0.0f;
+  M.nb0 = G == 1 ? b0[0] : 0.0f;
+  M.ngrp = G;
+  mc->noise = G == 1 ? 1 : 2;
+  return 0;
+}
+
 int dazim_mc_set_noise(dazim_ctx *ctx, dazim_mc *mc, float a0, float b0) {
   int rc;
   if ((rc = mc_check(ctx, mc, "dazim_mc_set_noise"))) return rc;
@@ -854,33 +1052,120 @@ int dazim_mc_set_noise(dazim_ctx *ctx, dazim_mc *mc, float a0, float b0) {
   if (a0 > 0.0f && !(std::isfinite(b0) && b0 > 0.0f))
     return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise: b0 %g is not finite and > 0", b0);
   if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise: the handle has done %lld steps", (long long)mc->nstep);
-  McDev &M = mc->d;
-  if (a0 == 0.0f) {
-    mc->noise = 0;
-    M.na0 = M.nb0 = 0.0f;
+  return mc_noise_setup(ctx, mc, a0 == 0.0f ? 0 : 1, nullptr, &a0, &b0);
+}
+
+int dazim_mc_set_noise_groups(dazim_ctx *ctx, dazim_mc *mc, int ngroup, const int *group_of_period, const float *a0, const float *b0) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_set_noise_groups"))) return rc;
+  if (!group_of_period || !a0 || !b0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_set_noise_groups");
+  if (dz_is_device_ptr(group_of_period) || dz_is_device_ptr(a0) || dz_is_device_ptr(b0))
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise_groups: group_of_period, a0 and b0 are host arrays");
+  if (ngroup < 1 || ngroup > MC_MAXGRP)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise_groups: ngroup %d outside 1..%d", ngroup, MC_MAXGRP);
+  for (int p = 0; p < mc->d.kmax; p++)
+    if (group_of_period[p] < 0 || group_of_period[p] >= ngroup)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise_groups: period %d is in group %d of %d", p, group_of_period[p], ngroup);
+  int npos = 0;
+  for (int g = 0; g < ngroup; g++) {
+    if (!(std::isfinite(a0[g]) && a0[g] >= 0.0f))
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise_groups: a0 %g of group %d is not finite and >= 0", a0[g], g);
+    npos += a0[g] > 0.0f;
+  }
+  if (npos != 0 && npos != ngroup)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise_groups: a0 is 0 for %d of the %d groups: all of them or none", ngroup - npos,
+                   ngroup);
+  for (int g = 0; g < ngroup && npos; g++)
+    if (!(std::isfinite(b0[g]) && b0[g] > 0.0f))
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise_groups: b0 %g of group %d is not finite and > 0", b0[g], g);
+  if (mc->nstep > 0)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_noise_groups: the handle has done %lld steps", (long long)mc->nstep);
+  return mc_noise_setup(ctx, mc, npos ? ngroup : 0, ngroup > 1 ? group_of_period : nullptr, a0, b0);
+}
+
+int dazim_mc_noise_groups_state(dazim_ctx *ctx, dazim_mc *mc, int *ngroup, int *group_of_period, float *a0, float *b0, double *chi2g,
+                                double *nsum, int64_t *ncnt) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_noise_groups_state"))) return rc;
+  const McDev &M = mc->d;
+  if (ngroup) *ngroup = M.ngrp;
+  if (!mc->noise) {
+    if (group_of_period || a0 || b0 || chi2g || nsum || ncnt)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_groups_state: no noise scale is switched on");
     return 0;
   }
+  if (dz_is_device_ptr(a0) || dz_is_device_ptr(b0))
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_groups_state: a0 and b0 are host arrays");
+  for (int g = 0; g < M.ngrp; g++) {
+    if (a0) a0[g] = M.ga0[g];
+    if (b0) b0[g] = M.gb0[g];
+  }
   DZ_HIP(hipSetDevice(ctx->device));
-  const size_t nc = (size_t)M.ncol;
-  if (!M.nsum) {
-    double *g;
-    if ((rc = mc_alloc(mc, 2 * nc, &M.nsum)) || (rc = mc_alloc(mc, nc, &M.ncnt)) || (rc = mc_alloc(mc, (size_t)MC_MAXPER + 1, &g)))
-      return rc;
-    M.ngam = g;
-  }
-  // g(a) = Gamma(a - 1/2) / Gamma(a) at a = a0 + nd / 2 for every nd a cell can have: one table, so that host and device agree
-  double gam[MC_MAXPER + 1];
-  for (int nd = 0; nd <= MC_MAXPER; nd++) {
-    const double a = (double)a0 + 0.5 * nd;
-    gam[nd] = std::exp(std::lgamma(a - 0.5) - std::lgamma(a));
-  }
-  DZ_HIP(hipMemcpyAsync((void *)M.ngam, gam, sizeof(gam), hipMemcpyHostToDevice, ctx->stream));
-  DZ_HIP(hipMemsetAsync(M.nsum, 0, (2 * nc ? 2 * nc : 1) * sizeof(double), ctx->stream));
-  DZ_HIP(hipMemsetAsync(M.ncnt, 0, (nc ? nc : 1) * sizeof(long long), ctx->stream));
+  DZ_HIP(mc_get(ctx, group_of_period, M.grp, (size_t)M.kmax * 4));
+  DZ_HIP(mc_get(ctx, chi2g, M.ngrp > 1 ? M.chi2g : M.chi2, (size_t)M.ngrp * M.ncol * 8));   // (one group's chi^2_g is chi^2)
+  DZ_HIP(mc_get(ctx, nsum, M.nsum, (size_t)2 * M.ngrp * M.ncol * 8));
+  DZ_HIP(mc_get(ctx, ncnt, M.ncnt, (size_t)M.ncol * 8));
   DZ_HIP(hipStreamSynchronize(ctx->stream));
-  M.na0 = a0;
-  M.nb0 = b0;
-  mc->noise = 1;
+  return 0;
+}
+
+int dazim_mc_noise_groups_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u, float *lam_std_u, int *ndata_u) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_noise_groups_result"))) return rc;
+  if (!lam_mean_u || !lam_std_u || !ndata_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_noise_groups_result");
+  if (!mc->noise) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_groups_result: no noise scale is switched on");
+  if (mc->d.ncs > 0 && mc->nrec < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_groups_result: no recorded step yet");
+  DZ_HIP(hipSetDevice(ctx->device));
+  const McDev &M = mc->d;
+  const size_t n = (size_t)M.ngrp * M.ncell;
+  DzBuf<float> lm, ls;
+  DzBuf<int> nd;
+  if ((rc = lm.init(ctx, lam_mean_u, n, false, true)) || (rc = ls.init(ctx, lam_std_u, n, false, true)) ||
+      (rc = nd.init(ctx, ndata_u, n, false, true)))
+    return rc;
+  hipLaunchKernelGGL(k_mc_noise_groups_final, dim3((unsigned)((n + MC_WAVE - 1) / MC_WAVE)), dim3(MC_WAVE), 0, ctx->stream, M, lm.dev,
+                     ls.dev, nd.dev);
+  DZ_HIP(hipGetLastError());
+  if ((rc = lm.finish()) || (rc = ls.finish()) || (rc = nd.finish())) return rc;
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int dazim_mc_set_segments(dazim_ctx *ctx, dazim_mc *mc, int nseg, const int *seg_iwave, const int *seg_igr, const int *seg_kmax) {
+  int rc;
+  if ((rc = mc_check(ctx, mc, "dazim_mc_set_segments"))) return rc;
+  if (!seg_iwave || !seg_igr || !seg_kmax) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_set_segments");
+  if (dz_is_device_ptr(seg_iwave) || dz_is_device_ptr(seg_igr) || dz_is_device_ptr(seg_kmax))
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: seg_iwave, seg_igr and seg_kmax are host arrays");
+  if (nseg < 1 || nseg > MC_MAXSEG) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: nseg %d outside 1..%d", nseg, MC_MAXSEG);
+  int K = 0;
+  for (int s = 0; s < nseg; s++) {
+    if (seg_iwave[s] != 1 && seg_iwave[s] != 2)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: segment %d: iwave %d is neither 1 (Love) nor 2 (Rayleigh)", s, seg_iwave[s]);
+    if (seg_igr[s] != 0 && seg_igr[s] != 1)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: segment %d: igr %d is neither 0 (phase) nor 1 (group)", s, seg_igr[s]);
+    if (seg_kmax[s] < 1 || seg_kmax[s] > MC_MAXPER)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: segment %d: %d periods outside 1..%d", s, seg_kmax[s], MC_MAXPER);
+    for (int q = 0; q < s; q++)
+      if (seg_iwave[q] == seg_iwave[s] && seg_igr[q] == seg_igr[s])
+        return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: segments %d and %d are the same wave type", q, s);
+    K += seg_kmax[s];
+  }
+  if (K != mc->d.kmax)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: the segments hold %d periods, the handle %d", K, mc->d.kmax);
+  if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_segments: the handle has done %lld steps", (long long)mc->nstep);
+  const bool typed = !(nseg == 1 && seg_iwave[0] == 2 && seg_igr[0] == 0);
+  if (typed && mc->nthin > 0)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG,
+                   "dazim_mc_set_segments: the handle samples Gc/Gs (dazim_mc_set_aniso), whose kernel Lsen_Gsc is Rayleigh-phase: "
+                   "other segments than Rayleigh phase alone are refused");
+  mc->nseg = nseg;
+  for (int s = 0; s < MC_MAXSEG; s++) {
+    mc->seg_iwave[s] = s < nseg ? seg_iwave[s] : 0;
+    mc->seg_igr[s] = s < nseg ? seg_igr[s] : 0;
+    mc->seg_kmax[s] = s < nseg ? seg_kmax[s] : 0;
+  }
+  mc->typed = typed;
   return 0;
 }
 
@@ -890,7 +1175,7 @@ int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, dou
   const McDev &M = mc->d;
   if (a0) *a0 = M.na0;
   if (b0) *b0 = M.nb0;
-  if (!mc->noise) {
+  if (mc->noise != 1) {   // (with several groups a0 = b0 = 0 here: the record is dazim_mc_noise_groups_state's)
     if (nsum || ncnt) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_state: dazim_mc_set_noise has not switched the noise scale on");
     return 0;
   }
@@ -905,7 +1190,8 @@ int dazim_mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u, float
   int rc;
   if ((rc = mc_check(ctx, mc, "dazim_mc_noise_result"))) return rc;
   if (!lam_mean_u || !lam_std_u || !ndata_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_noise_result");
-  if (!mc->noise) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_result: dazim_mc_set_noise has not switched the noise scale on");
+  if (mc->noise != 1)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_result: dazim_mc_set_noise has not switched the noise scale on");
   if (mc->d.ncs > 0 && mc->nrec < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_result: no recorded step yet");
   DZ_HIP(hipSetDevice(ctx->device));
   const McDev &M = mc->d;
@@ -1027,14 +1313,23 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
     if (rc) return rc;
   }
   const int nstep = nburn + nsample;
+  bool has_rc = false;   // a Rayleigh-phase segment among the typed ones: both dispersion timers run
+  for (int q = 0; q < mc->nseg; q++) has_rc = has_rc || (mc->seg_iwave[q] == 2 && mc->seg_igr[q] == 0);
   for (int s = 0; s < nstep && mc->d.ncs > 0; s++) {
     int nf = 0;
     // curves only, one column per chain: nx = ncol, ny = 1 (the call ends with a wait for the stream: the step enqueued before it
     // has finished when it returns)
-    if ((rc = dazim_dispersion_kernels(ctx, (int)mc->d.ncol, 1, mc->d.nz, mc->d.prop, depz, sublayers, mc->d.kmax, periods, mc->pv,
-                                       nullptr, nullptr, nullptr, &nf)))
-      return rc;
-    t_disp += ctx->ksec["disp"];
+    if (mc->typed) {   // (every segment's curves; a Rayleigh-phase segment goes through the call below inside it)
+      if ((rc = dazim_dispersion_kernels_typed(ctx, (int)mc->d.ncol, 1, mc->d.nz, mc->d.prop, depz, sublayers, mc->nseg, mc->seg_iwave,
+                                               mc->seg_igr, mc->seg_kmax, periods, mc->pv, nullptr, nullptr, nullptr, &nf)))
+        return rc;
+      t_disp += ctx->ksec["disp_typed"] + (has_rc ? ctx->ksec["disp"] : 0.0);
+    } else {
+      if ((rc = dazim_dispersion_kernels(ctx, (int)mc->d.ncol, 1, mc->d.nz, mc->d.prop, depz, sublayers, mc->d.kmax, periods, mc->pv,
+                                         nullptr, nullptr, nullptr, &nf)))
+        return rc;
+      t_disp += ctx->ksec["disp"];
+    }
     if (s > 0) {
       float ms = 0.0f;
       DZ_HIP(hipEventElapsedTime(&ms, mc->e0, mc->e1));
@@ -1098,6 +1393,7 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
   ctx->ksec["mc.swap_med"] = swap_med;
   ctx->ksec["mc.proposal"] = mc->kind;
   ctx->ksec["mc.noise"] = mc->noise;
+  ctx->ksec["mc.noise_groups"] = mc->d.ngrp;
   ctx->ksec["mc.prior"] = mc->prior;
   ctx->ksec["mc.cov_cells"] = cov_cells;
   if (n_no_root) *n_no_root = (int64_t)(c1[0] - c0[0]);

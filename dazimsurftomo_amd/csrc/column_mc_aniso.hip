@@ -193,6 +193,10 @@ int dazim_mc_set_aniso(dazim_ctx *ctx, dazim_mc *mc, int nthin, const float *ama
     mc->nthin = 0;
     return 0;
   }
+  if (mc->typed)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG,
+                   "dazim_mc_set_aniso: the Gc/Gs kernel Lsen_Gsc is Rayleigh-phase, and the handle's segments (dazim_mc_set_segments) "
+                   "are not Rayleigh phase alone");
   if (!amap_u || !wa_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_set_aniso");
   if (!(smooth >= 0.0f) || !(damp >= 0.0f)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: negative smoothing or damping");
   if (smooth == 0.0f && damp == 0.0f) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: smoothing and damping both 0");

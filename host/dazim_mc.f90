@@ -3,7 +3,7 @@
 ! section 14), where SurfDepthFromMaps_amd returns one linearised model.
 !
 !   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a
-!                            [noise_a0 [noise_b0 [smooth_vs [damp_vs]]]]]]]]]]]]]]]
+!                            [noise_a0 [noise_b0 [smooth_vs [damp_vs [types]]]]]]]]]]]]]]]]
 !
 ! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
 ! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
@@ -36,6 +36,14 @@
 !                                dazim_column_resolution at the posterior-mean model (its kernels, the run's weights, smooth_vs,
 !                                damp_vs: SurfDepthFromMaps_amd's resolution block) and their ratio (0 where std_post is 0)
 ! With noise_a0 > 0 sigma_c is not the data std, the linearised std has nothing to stand on, and the file is not written.
+! types 0 (default): a para.in that lists Rayleigh group or Love-wave periods is refused.  types 1: the maps of every wave type that
+! para.in lists are sampled together (period_phaseV_map.dat as SurfPhaseMaps_amd writes it for typed data, one map per virtual
+! period); the chains' forward model is dazim_dispersion_kernels_typed (dazim_mc_set_segments).  With noise_a0 > 0 every wave type
+! gets a noise scale of its own, lambda_type^2 ~ InverseGamma(noise_a0, noise_b0) each (dazim_mc_set_noise_groups):
+! noise_posterior_mc.dat then holds one block per type, its lines ending in the type's wavetp veltp, period_phaseV_mc.dat ends in
+! those two columns as every typed map file does, and the log gets one line per type: its periods, the mean |c residual| of the
+! best model and the median lambda.  aniso_thin > 0 is refused with typed data: the Gc/Gs kernel Lsen_Gsc is Rayleigh-phase.
+! Rayleigh-phase input writes the same bytes with types 0 and 1.
 !
 ! Outputs (names of their own, so that the three programs can share a directory):
 !   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
@@ -67,6 +75,12 @@ program SurfDepthMC_amd
   integer(c_int) :: nempty_res, nbad
   real, allocatable :: lam_mean(:, :), lam_std(:, :)
   integer(c_int), allocatable :: ndata(:, :)
+  integer :: types, ngrp, g, wavetp, veltp
+  logical :: typed
+  integer(c_int), allocatable :: grp(:)
+  real(c_float) :: ga0(4), gb0(4)
+  real, allocatable :: glam_mean(:, :, :), glam_std(:, :, :)
+  integer(c_int), allocatable :: gndata(:, :, :)
   integer, parameter :: nswap = 1
   real :: tmax
   real(c_double), allocatable, target :: beta(:)
@@ -92,7 +106,7 @@ program SurfDepthMC_amd
   write (*, *)
   if (command_argument_count() < 1) error stop &
     'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a '// &
-    '[noise_a0 [noise_b0 [smooth_vs [damp_vs]]]]]]]]]]]]]]]'
+    '[noise_a0 [noise_b0 [smooth_vs [damp_vs [types]]]]]]]]]]]]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -101,11 +115,16 @@ program SurfDepthMC_amd
   Minvel = p%Minvel; Maxvel = p%Maxvel; kmax = p%kmaxRc; tRc = p%tRc
   if (nz <= 1) error stop 'error nz value.'
   if (kmax <= 0) error stop 'Can only deal with Rayleigh wave phase velocity data!'
-  if (p%typed) then
+  types = 0
+  call optional_arg(17, types)
+  if (types /= 0 .and. types /= 1) error stop 'types must be 0 or 1'
+  if (p%typed .and. types == 0) then
     write (*, '(a)') ' ERROR: SurfDepthMC_amd: para.in lists Rayleigh group or Love-wave periods; the Monte-Carlo forward model is the'
     write (*, '(a)') ' Rayleigh phase-velocity kernel.  Use SurfDepthFromMaps_amd for maps of other wave types.'
+    write (*, '(a)') ' Or pass types = 1, the sixteenth argument after para.in, to sample the maps of every wave type together.'
     error stop 'SurfDepthMC_amd takes Rayleigh phase velocities only'
   end if
+  typed = p%typed
   nsample = 2000; nchain = 32; width = 0; sigma_c = 0.01; seed = 1; proposal = 0; ntemp = 1; tmax = 16
   call optional_arg(2, nsample)
   call optional_arg(3, nchain)
@@ -135,6 +154,11 @@ program SurfDepthMC_amd
   if (mod(nchain, ntemp) /= 0) error stop 'ntemp must be 1..nchain and divide nchain'
   if (ntemp > 1 .and. .not. (tmax > 1 .and. tmax <= huge(tmax))) error stop 'tmax must be a finite temperature above 1'
   if (aniso_thin < 0) error stop 'aniso_thin must not be negative'
+  if (aniso_thin > 0 .and. typed) then
+    write (*, '(a)') ' ERROR: aniso_thin > 0 with types = 1: para.in lists Rayleigh group or Love-wave periods, and the Gc/Gs kernel'
+    write (*, '(a)') ' (Lsen_Gsc) exists for Rayleigh phase velocities only.'
+    error stop 'aniso_thin > 0 takes Rayleigh phase velocities only'
+  end if
   if (aniso_thin > 0 .and. p%iso_mod) then
     write (*, '(a)') ' ERROR: aniso_thin > 0 needs the 2-psi maps of iso-mode F; para.in has iso-mode T'
     error stop 'aniso_thin > 0 with iso-mode T'
@@ -152,6 +176,7 @@ program SurfDepthMC_amd
   ncell = (nx - 2)*(ny - 2)
   if (nlay > 63) error stop 'SurfDepthMC_amd samples at most 63 knots (nz <= 64)'
   if (kmax > 60) error stop 'SurfDepthMC_amd takes at most 60 periods'
+  if (typed) call dazim_set_segments(p%nseg, p%seg_wavetp, p%seg_veltp, p%seg_kmax)
   if (.not. (Minvel < Maxvel)) error stop 'para.in''s Vs range is empty'
   write (logfile, '(a,a)') trim(inputfile), '_mc.log'
   open (66, file=logfile)
@@ -175,8 +200,19 @@ program SurfDepthMC_amd
       ', a swap round every', nswap, ' step(s);', ncold, ' chains per cell at T = 1 are recorded'
     if (aniso_thin > 0) write (q, '(a,i6,a,f8.3,a,f8.3,a,f8.4)') ' Gc/Gs posteriors: one sample of every recorded chain per', &
       aniso_thin, ' recorded steps;  smoothing', smooth_gcs, '  damping', p%damp, '  sigma_a (km/s)', sigma_a
-    if (noise_a0 > 0) write (q, '(a,f9.4,a,f9.4,a)') ' hierarchical noise: data std lambda * sigma_c per cell, lambda^2 ~ InverseGamma(', &
-      noise_a0, ',', noise_b0, '), integrated out of the chains'' target'
+    if (typed) then
+      do g = 1, p%nseg
+        write (q, '(a,a,a,i3,a,i3)') ' wave type ', trim(type_name(p%seg_wavetp(g), p%seg_veltp(g))), ':', p%seg_kmax(g), &
+          ' periods from virtual period', sum(p%seg_kmax(1:g - 1)) + 1
+      end do
+    end if
+    if (noise_a0 > 0 .and. typed) then
+      write (q, '(a,f9.4,a,f9.4,a)') ' hierarchical noise: data std lambda_type * sigma_c per cell and wave type, each lambda^2 ~ '// &
+        'InverseGamma(', noise_a0, ',', noise_b0, '), integrated out of the chains'' target'
+    else if (noise_a0 > 0) then
+      write (q, '(a,f9.4,a,f9.4,a)') ' hierarchical noise: data std lambda * sigma_c per cell, lambda^2 ~ InverseGamma(', &
+        noise_a0, ',', noise_b0, '), integrated out of the chains'' target'
+    end if
     if (prior_on) write (q, '(a,f8.3,a,f8.3,a)') ' Gaussian prior about MOD inside the box: smoothing', smooth_vs, '  damping', &
       damp_vs, ' (precision smooth^2 L^T L + damp^2 I)'
   end do
@@ -227,7 +263,21 @@ program SurfDepthMC_amd
   end if
   if (aniso_thin > 0) call dazim_check(dazim_mc_set_aniso(dazim_handle, mc, aniso_thin, amap, wa, smooth_gcs, p%damp), &
                                        'Gc/Gs posteriors')
-  if (noise_a0 > 0) call dazim_check(dazim_mc_set_noise(dazim_handle, mc, noise_a0, noise_b0), 'hierarchical noise')
+  ngrp = 0
+  if (typed) then
+    call dazim_check(dazim_mc_set_segments(dazim_handle, mc, p%nseg, p%seg_wavetp, p%seg_veltp, p%seg_kmax), 'wave types')
+    if (noise_a0 > 0) then                    ! one noise scale per wave type: the group of a period is its segment
+      ngrp = p%nseg
+      allocate (grp(kmax))
+      do g = 1, ngrp
+        grp(sum(p%seg_kmax(1:g - 1)) + 1:sum(p%seg_kmax(1:g))) = g - 1
+      end do
+      ga0 = noise_a0; gb0 = noise_b0
+      call dazim_check(dazim_mc_set_noise_groups(dazim_handle, mc, ngrp, grp, ga0, gb0), 'hierarchical noise per wave type')
+    end if
+  else if (noise_a0 > 0) then
+    call dazim_check(dazim_mc_set_noise(dazim_handle, mc, noise_a0, noise_b0), 'hierarchical noise')
+  end if
   if (prior_on) call dazim_check(dazim_mc_set_prior(dazim_handle, mc, smooth_vs, damp_vs, c_null_ptr), 'Gaussian prior')
   call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
   t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
@@ -251,7 +301,10 @@ program SurfDepthMC_amd
       gmean = 0; gstd = 0; gstdb = 0; gcov = 0; nsamp = 0
     end if
   end if
-  if (noise_a0 > 0) then
+  if (ngrp > 0) then
+    allocate (glam_mean(nx - 2, ny - 2, ngrp), glam_std(nx - 2, ny - 2, ngrp), gndata(nx - 2, ny - 2, ngrp))
+    call dazim_check(dazim_mc_noise_groups_result(dazim_handle, mc, glam_mean, glam_std, gndata), 'noise-scale posteriors')
+  else if (noise_a0 > 0) then
     allocate (lam_mean(nx - 2, ny - 2), lam_std(nx - 2, ny - 2), ndata(nx - 2, ny - 2))
     call dazim_check(dazim_mc_noise_result(dazim_handle, mc, lam_mean, lam_std, ndata), 'noise-scale posterior')
   end if
@@ -262,18 +315,18 @@ program SurfDepthMC_amd
   vmc = vsf; vbest = vsf
   vmc(2:nx - 1, 2:ny - 1, 1:nlay) = mean
   vbest(2:nx - 1, 2:ny - 1, 1:nlay) = best
-  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vmc, depz, minthk, kmax, tRc, pvm, c_null_ptr, c_null_ptr, &
-                                            c_null_ptr, nfail), 'dispersion curves of the mean model')
-  call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vbest, depz, minthk, kmax, tRc, pvb, c_null_ptr, c_null_ptr, &
-                                            c_null_ptr, nfail), 'dispersion curves of the best model')
+  call dazim_check(dazim_dispersion_any(dazim_handle, nx, ny, nz, vmc, depz, minthk, kmax, tRc, pvm, c_null_ptr, c_null_ptr, &
+                                        c_null_ptr, nfail), 'dispersion curves of the mean model')
+  call dazim_check(dazim_dispersion_any(dazim_handle, nx, ny, nz, vbest, depz, minthk, kmax, tRc, pvb, c_null_ptr, c_null_ptr, &
+                                        c_null_ptr, nfail), 'dispersion curves of the best model')
   allocate (rms_b(nx - 2, ny - 2), rms_m(nx - 2, ny - 2), sampled(nx - 2, ny - 2))
   sampled = any(wcov /= 0.0, dim=3)
   ! ---- the chains' std against the linearised std_post at the posterior-mean model (SurfDepthFromMaps_amd's resolution block) ------
   if (prior_on .and. .not. noise_a0 > 0) then
     allocate (svs(nx*ny, kmax, nz), svp(nx*ny, kmax, nz), srho(nx*ny, kmax, nz), skern(nx*ny, kmax, nz), pvk(nx*ny, kmax))
     allocate (res(nx - 2, ny - 2, nlay, 5), rtrace(nx - 2, ny - 2), ratio(nx - 2, ny - 2, nlay))
-    call dazim_check(dazim_dispersion_kernels(dazim_handle, nx, ny, nz, vmc, depz, minthk, kmax, tRc, pvk, c_loc(svs), c_loc(svp), &
-                                              c_loc(srho), nfail), 'depth kernels of the mean model')
+    call dazim_check(dazim_dispersion_any(dazim_handle, nx, ny, nz, vmc, depz, minthk, kmax, tRc, pvk, c_loc(svs), c_loc(svp), &
+                                          c_loc(srho), nfail), 'depth kernels of the mean model')
     call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kmax, vmc, svs, svp, srho, skern), 'dc/dVs table of the mean model')
     call dazim_check(dazim_column_resolution(dazim_handle, nx, ny, nlay, kmax, 0, c_loc(skern), wcov, smooth_vs, damp_vs, depz, &
                                              res(:, :, :, 1), res(:, :, :, 2), res(:, :, :, 3), res(:, :, :, 4), res(:, :, :, 5), &
@@ -348,7 +401,40 @@ program SurfDepthMC_amd
       write (q, '(a,2f9.4)') ' R-hat over (cell, knot), median and maximum:', sorted(max(1, (nr + 1)/2)), sorted(max(nr, 1))
     end do
   end if
-  if (noise_a0 > 0) then
+  if (typed) then   ! per wave type: its periods, the mean |c residual| of the best model and, with the noise scales, the median lambda
+    do g = 1, p%nseg
+      s0 = 0; cnt = 0
+      do t = sum(p%seg_kmax(1:g - 1)) + 1, sum(p%seg_kmax(1:g))
+        do j = 1, ny - 2
+          do i = 1, nx - 2
+            if (wcov(i, j, t) /= 0.0) then
+              s0 = s0 + abs(real(cmap(i, j, t), 8) - pvb(j*nx + i + 1, t))
+              cnt = cnt + 1
+            end if
+          end do
+        end do
+      end do
+      if (cnt > 0) s0 = s0/cnt
+      if (allocated(sorted)) deallocate (sorted)
+      nr = 0
+      if (ngrp > 0) nr = count(gndata(:, :, g) > 0 .and. glam_mean(:, :, g) == glam_mean(:, :, g))
+      allocate (sorted(max(nr, 1)))
+      sorted = 0
+      if (nr > 0) sorted(1:nr) = pack(glam_mean(:, :, g), gndata(:, :, g) > 0 .and. glam_mean(:, :, g) == glam_mean(:, :, g))
+      call sort(sorted)
+      do q = 6, 66, 60
+        if (ngrp > 0) then
+          write (q, '(a,a,a,i3,a,f10.5,a,f9.3)') ' ', trim(type_name(p%seg_wavetp(g), p%seg_veltp(g))), ':', p%seg_kmax(g), &
+            ' periods, best model mean |c residual| (km/s)', s0, ', median of the mean of lambda over cells', sorted(max(1, (nr + 1)/2))
+        else
+          write (q, '(a,a,a,i3,a,f10.5)') ' ', trim(type_name(p%seg_wavetp(g), p%seg_veltp(g))), ':', p%seg_kmax(g), &
+            ' periods, best model mean |c residual| (km/s)', s0
+        end if
+      end do
+      deallocate (sorted)
+    end do
+  end if
+  if (noise_a0 > 0 .and. ngrp == 0) then
     nr = count(sampled .and. lam_mean == lam_mean)
     if (allocated(sorted)) deallocate (sorted)
     allocate (sorted(max(nr, 1)))
@@ -420,7 +506,19 @@ program SurfDepthMC_amd
     end do
     close (64)
   end if
-  if (noise_a0 > 0) then
+  if (ngrp > 0) then   ! one block per wave type, in para.in's order; the lines end in the type's wavetp veltp
+    open (64, file='noise_posterior_mc.dat')
+    do g = 1, ngrp
+      wavetp = p%seg_wavetp(g); veltp = p%seg_veltp(g)
+      do j = 1, ny - 2
+        do i = 1, nx - 2
+          write (64, '(2f10.4,3f12.6,i6,2i3)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, glam_mean(i, j, g), glam_std(i, j, g), &
+            sigma_c*glam_mean(i, j, g), gndata(i, j, g), wavetp, veltp
+        end do
+      end do
+    end do
+    close (64)
+  else if (noise_a0 > 0) then
     open (64, file='noise_posterior_mc.dat')
     do j = 1, ny - 2
       do i = 1, nx - 2

@@ -43,7 +43,8 @@ module dazim_mod
   public :: dazim_mc_create, dazim_mc_proposals, dazim_mc_step, dazim_mc_run, dazim_mc_state, dazim_mc_result, dazim_mc_free, &
             dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds, &
             dazim_mc_set_aniso, dazim_mc_aniso_step, dazim_mc_aniso_state, dazim_mc_aniso_result, dazim_mc_set_noise, &
-            dazim_mc_noise_state, dazim_mc_noise_result, dazim_mc_set_prior, dazim_mc_prior_state
+            dazim_mc_noise_state, dazim_mc_noise_result, dazim_mc_set_prior, dazim_mc_prior_state, dazim_mc_set_segments, &
+            dazim_mc_set_noise_groups, dazim_mc_noise_groups_state, dazim_mc_noise_groups_result
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -374,6 +375,35 @@ module dazim_mod
       type(c_ptr), value :: ctx, mc
       real(c_float) :: lam_mean(*), lam_std(*)
       integer(c_int) :: ndata(*)
+    end function
+    ! one noise scale per group of periods: group_of_period(kmax) in 0..ngroup-1, a0, b0 (ngroup); results (nx-2, ny-2, ngroup)
+    integer(c_int) function dazim_mc_set_noise_groups(ctx, mc, ngroup, group_of_period, a0, b0) &
+        bind(C, name="dazim_mc_set_noise_groups")
+      import
+      type(c_ptr), value :: ctx, mc
+      integer(c_int), value :: ngroup
+      integer(c_int) :: group_of_period(*)
+      real(c_float) :: a0(*), b0(*)
+    end function
+    ! every argument after mc may be c_null_ptr (c_loc of a variable or an array otherwise)
+    integer(c_int) function dazim_mc_noise_groups_state(ctx, mc, ngroup, group_of_period, a0, b0, chi2g, nsum, ncnt) &
+        bind(C, name="dazim_mc_noise_groups_state")
+      import
+      type(c_ptr), value :: ctx, mc, ngroup, group_of_period, a0, b0, chi2g, nsum, ncnt
+    end function
+    integer(c_int) function dazim_mc_noise_groups_result(ctx, mc, lam_mean, lam_std, ndata) &
+        bind(C, name="dazim_mc_noise_groups_result")
+      import
+      type(c_ptr), value :: ctx, mc
+      real(c_float) :: lam_mean(*), lam_std(*)
+      integer(c_int) :: ndata(*)
+    end function
+    ! the wave types of the handle's periods, as dazim_dispersion_kernels_typed takes them: dazim_mc_run then calls that entry
+    integer(c_int) function dazim_mc_set_segments(ctx, mc, nseg, seg_iwave, seg_igr, seg_kmax) bind(C, name="dazim_mc_set_segments")
+      import
+      type(c_ptr), value :: ctx, mc
+      integer(c_int), value :: nseg
+      integer(c_int) :: seg_iwave(*), seg_igr(*), seg_kmax(*)
     end function
     integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
         bind(C, name="dazim_phase_map_update")

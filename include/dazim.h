@@ -633,6 +633,38 @@ int dazim_column_resolution(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, 
  *   device).  DAZIM_E_BAD_ARG when the mode is off and an array is requested.
  *   dazim_mc_noise_result: lam_mean, lam_std [ny-2][nx-2] fp32 and ndata [ny-2][nx-2] int32 (host or device).  Refused with the
  *   mode off or before the first recorded step.
+ * One noise scale per group of periods (dazim_mc_set_noise_groups; one group is dazim_mc_set_noise itself, the same kernel and the
+ *   same bits): joint data of several wave types do not share a noise level, so every period p is given a group grp[p] in 0..G-1,
+ *   G <= 4, and the data std of period p in a cell is lambda_g / w_p, g = grp[p], lambda_g^2 ~ InverseGamma(a0_g, b0_g), the groups
+ *   independent a priori.  Each lambda_g integrates out as above, which is exact: the likelihood factorises over the groups.
+ *   Per sampled cell nd_g = the periods of group g with w != 0, a_g = (double)a0_g + 0.5 * nd_g.  Per chain, beside chi2 (the total,
+ *   the one sum over all periods in period order as above, unchanged), chi2_g = the same terms summed per group, each in period
+ *   order from 0.0; a period with data and no root makes chi2 and its group's chi2_g +inf.  B_g = (double)b0_g + 0.5 * chi2_g.
+ *   Energy: X = sum over g = 0..G-1 in that order from 0.0, over the groups with nd_g > 0, of 2.0 * a_g * log(B_g), fp64; X = +inf
+ *   where chi2 = +inf.  Step: the hierarchical one above with this X (and E = X under the smoothness prior); the rules for +inf still
+ *   test the total chi2.  The handle keeps the chi2_g of every chain's state in chi2g [G][ncol] (+inf before the first step); an
+ *   accepted proposal stores its chi2_g and a swap exchanges them with the knots and chi2.  chi2, best, best_chi2 keep their meaning.
+ *   Noise record: a recorded rung-0 chain with finite chi2 adds, for every g with nd_g > 0, nsum[0][g][col] += sqrt(B_g) and
+ *   nsum[1][g][col] += B_g, and ncnt[col] += 1; nsum is [2][G][ncol].
+ *   Result (dazim_mc_noise_groups_result), one lane per (group, inner cell), as dazim_mc_noise_result with the group's a_g, sums and
+ *   table row: lam_mean, lam_std [G][ny-2][nx-2] fp32 and ndata [G][ny-2][nx-2] int32 = nd_g; 0 for a cell without data and for a
+ *   group without data in a sampled cell, NaN where nothing was recorded, lam_std NaN where a_g <= 1.
+ *   Stat "mc.noise" of dazim_mc_run is 2 with G >= 2 groups, and "mc.noise_groups" is G (0 off, 1 for dazim_mc_set_noise).
+ *   dazim_mc_set_noise_groups: ngroup in 1..4, group_of_period [kmax] in 0..ngroup-1, a0, b0 [ngroup], host arrays.  Every a0 == 0
+ *   restores the default.  DAZIM_E_BAD_ARG for ngroup outside 1..4, a group index out of range, a non-finite or negative a0, a0 zero
+ *   for some groups and positive for others, a positive a0 with b0 not finite or <= 0, or once a step has been done.  While G >= 2
+ *   groups are on, dazim_mc_noise_state gives a0 = b0 = 0 and dazim_mc_noise_result is refused.
+ *   dazim_mc_noise_groups_state: ngroup (0 while no noise mode is on) and copies of group_of_period [kmax], a0, b0 [ngroup] (host),
+ *   chi2g [ngroup][ncol] (one group: chi2 itself), nsum [2][ngroup][ncol], ncnt [ncol] (each nullable; host or device unless stated).
+ *   DAZIM_E_BAD_ARG when no mode is on and an array is requested.
+ * Typed data (dazim_mc_set_segments; without it, or with the one segment (2, 0), every launch and every result is the one above,
+ *   unchanged): the handle's kmax periods are the virtual periods of nseg segments laid end to end, segment s being seg_kmax[s]
+ *   periods of wave seg_iwave[s] (1 Love, 2 Rayleigh) and velocity seg_igr[s] (0 phase, 1 group), under the rules of
+ *   dazim_dispersion_kernels_typed (host arrays, nseg in 1..4, no type twice); the lengths sum to kmax.  dazim_mc_run then computes
+ *   the proposals' curves with dazim_dispersion_kernels_typed (curves only, nx = ncol, ny = 1, device arrays), "mc.disp" summing
+ *   the seconds of both dispersion timers.  The step itself does not look at the type of a period.  Refused once a step has been
+ *   done.  The Gc/Gs kernel Lsen_Gsc is Rayleigh-phase: dazim_mc_set_aniso on a handle with other segments, and other segments on a
+ *   handle with Gc/Gs on, are refused.
  * Gaussian smoothness prior (dazim_mc_set_prior; without it, or with smooth = damp = 0, every launch and every result is the one
  *   above, unchanged): dazim_column_lsq's regulariser read as the prior that dazim_column_resolution reads it as, a Gaussian of
  *   precision P = smooth^2 L^T L + damp^2 I about a reference column vref, so that the chains' spread means what std_post means and
@@ -705,6 +737,11 @@ int dazim_mc_aniso_result(dazim_ctx *ctx, dazim_mc *mc, float *mean, float *std,
 int dazim_mc_set_noise(dazim_ctx *ctx, dazim_mc *mc, float a0, float b0);
 int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, double *nsum, int64_t *ncnt);
 int dazim_mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean, float *lam_std, int *ndata);
+int dazim_mc_set_noise_groups(dazim_ctx *ctx, dazim_mc *mc, int ngroup, const int *group_of_period, const float *a0, const float *b0);
+int dazim_mc_noise_groups_state(dazim_ctx *ctx, dazim_mc *mc, int *ngroup, int *group_of_period, float *a0, float *b0, double *chi2g,
+                                double *nsum, int64_t *ncnt);
+int dazim_mc_noise_groups_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean, float *lam_std, int *ndata);
+int dazim_mc_set_segments(dazim_ctx *ctx, dazim_mc *mc, int nseg, const int *seg_iwave, const int *seg_igr, const int *seg_kmax);
 int dazim_mc_set_prior(dazim_ctx *ctx, dazim_mc *mc, float smooth, float damp, const float *vref);
 int dazim_mc_prior_state(dazim_ctx *ctx, dazim_mc *mc, float *smooth, float *damp, float *vref, double *q);
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);

@@ -7,6 +7,7 @@
     python tools/mc_step.py --program --noise A0 B0 [--dir D] [--proposal K] [--ntemp R [--tmax T]]
     python tools/mc_step.py --prior S D [--steps S] [--proposal K] [--ntemp R [--tmax T]] [--noise A0 B0]
     python tools/mc_step.py --program --prior S D [--dir D] [--proposal K] [--ntemp R [--tmax T]] [--noise A0 B0]
+    python tools/mc_step.py --typed [--steps S] [--big N] [--runs R]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -37,7 +38,14 @@ run with arguments 13 and 14, the log's noise lines among those kept.
 
 --prior S D: the Gaussian smoothness prior (dazim_mc_set_prior, smooth S and damp D about the start model) at S-256 with 32 chains:
 five pairs of runs, the prior off then on, alternating, as for --noise (with --noise the mode is on in both runs of a pair;
-profiles/depth_mc_prior.md).  With --program: the default run with arguments 15 and 16, the log's prior lines among those kept."""
+profiles/depth_mc_prior.md).  With --program: the default run with arguments 15 and 16, the log's prior lines among those kept.
+
+--typed: typed data (dazim_mc_set_segments) at S-256 with 32 chains and on the big grid with 8: Rayleigh phase alone at the model's
+16 periods (the default run above, through set_segments) and at every other one of them, then Rayleigh and Love, phase and group
+velocities together at those 8 periods each (32 virtual periods; four times 16 would pass the sampler's 60); R runs (default 3) of S
+steps per case, each on a fresh handle after its warm-up run; reports the ms per step of "mc", "mc.disp" and "mc.step" of every run.
+At S-256 two more cases on the four types: the one noise scale (dazim_mc_set_noise) and one per type (dazim_mc_set_noise_groups),
+whose "mc.step" are the two step kernels side by side (profiles/mc_typed.md)."""
 import argparse
 import json
 import os
@@ -81,6 +89,44 @@ def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None, prior=Non
             "mc_step_ms_per_step": ms(stp), "other_ms_per_step": ms(wall - disp - stp), "mc_step_share": stp / wall,
             "curves_per_s": mc.ncol * steps / wall, "accept": ctx.stat("mc.accept"), "no_root": nr,
             "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
+
+
+def typed_case(ctx, n, nchain, steps, name, runs):
+    import bench
+    bench.NX = bench.NY = n
+    vel = bench.s256_model().astype(np.float32)
+    depz, periods = np.asarray(bench.DEPZ, np.float32), np.asarray(bench.PERIODS, np.float64)
+    nz, nlay = len(depz), len(depz) - 1
+    kinds = {"rc16": [(2, 0, periods)], "rc8": [(2, 0, periods[::2])]}
+    four = [(2, 0, periods[::2]), (2, 1, periods[::2]), (1, 0, periods[::2]), (1, 1, periods[::2])]
+    segs = kinds.get(name, four)
+    virt = np.concatenate([s[2] for s in segs])
+    K = len(virt)
+    pv, _, _ = ctx.dispersion_kernels_typed(vel, depz, segs, bench.MINTHK, kernels=False)
+    cobs = pv.reshape(K, n, n)[:, 1:-1, 1:-1].astype(np.float32)
+    inner = vel[:nlay, 1:-1, 1:-1]
+    vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
+    wdat = np.where(cobs != 0, np.float32(100.0), np.float32(0)).astype(np.float32)
+    out = {"case": name, "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nz} knots ({nlay} sampled), {K} virtual periods",
+           "segments": [(iw, ig, len(t)) for iw, ig, t in segs], "nchain": nchain, "steps": steps, "ms_per_step": [],
+           "disp_ms_per_step": [], "mc_step_ms_per_step": []}
+    for _ in range(runs):
+        mc = ctx.mc_create(n, n, nz, K, nchain, 100, 1, vel, vmin, vmax, cobs, wdat)
+        mc.set_segments(segs)
+        if name == "four_noise":
+            mc.set_noise(2.0, 1.0)
+        elif name == "four_groups":
+            mc.set_noise_groups(np.repeat(np.arange(4), K // 4), [2.0] * 4, [1.0] * 4)
+        mc.run(depz, bench.MINTHK, virt, 5, 0)                    # warm-up: code objects, scratch buffers
+        out["no_root"] = mc.run(depz, bench.MINTHK, virt, steps // 2, steps - steps // 2)
+        for key, stat in (("ms_per_step", "mc"), ("disp_ms_per_step", "mc.disp"), ("mc_step_ms_per_step", "mc.step")):
+            out[key].append(1e3 * ctx.stat(stat) / steps)
+        out["curves_per_step"] = mc.ncol
+        out["noise_groups"] = int(ctx.stat("mc.noise_groups"))
+        mc.free()
+    for key in ("ms_per_step", "disp_ms_per_step", "mc_step_ms_per_step"):
+        out[key + "_median"] = float(np.median(out[key]))
+    return out
 
 
 def noise_cases(ctx, steps, proposal, ntemp, tmax, noise, pairs=5, prior=None):
@@ -216,8 +262,16 @@ def main():
     ap.add_argument("--aniso", type=int, default=0)
     ap.add_argument("--noise", type=float, nargs=2, default=None, metavar=("A0", "B0"))
     ap.add_argument("--prior", type=float, nargs=2, default=None, metavar=("S", "D"))
+    ap.add_argument("--typed", action="store_true")
+    ap.add_argument("--runs", type=int, default=3)
     a = ap.parse_args()
     ctx = dz.Context(0)
+    if a.typed:
+        for n, nchain, names in ((54, 32, ("rc16", "rc8", "four", "four_noise", "four_groups")), (a.big, 8, ("rc16", "rc8", "four"))):
+            for name in names:
+                print(json.dumps(typed_case(ctx, n, nchain, a.steps, name, a.runs)), flush=True)
+        ctx.close()
+        return
     if a.aniso > 0:
         for n, nchain in ((54, 32), (a.big, 8)):
             print(json.dumps(aniso_case(ctx, n, nchain, a.steps, a.aniso)), flush=True)
