@@ -15,22 +15,20 @@
 // Gc/Gs posteriors (dazim_mc_set_aniso) are column_mc_aniso.hip's: a pass that only reads the chains, and that dazim_mc_run reaches
 // through mc_internal.h, which also holds the handle, its device view McDev, the constants and the random numbers.
 //
-// Hierarchical data noise (dazim_mc_set_noise): the data std of a cell is lambda / w_p with lambda^2 ~ InverseGamma(a0, b0), and
-// lambda is integrated out in closed form: k_mc_step<KIND, TEMPER, 1> takes every decision on the energy X = 2 a log(b0 + chi^2 / 2)
-// in place of chi^2 (mc_energy), each recorded rung-0 lane adds sqrt(B) and B = b0 + chi^2 / 2 of its state to its own column, and
-// k_mc_noise_final turns those sums into the posterior mean and std of lambda per cell (Rao-Blackwellisation again).
-//
-// One noise scale per group of periods (dazim_mc_set_noise_groups, G >= 2 groups): lambda_g^2 ~ InverseGamma(a0_g, b0_g), each integrated
-// out as above, so the energy is X = sum_g 2 a_g log(b0_g + chi^2_g / 2) over the groups with data in the cell.  k_mc_step<KIND, TEMPER, 2>
-// forms chi^2_g beside chi^2 in the one loop over the periods, keeps the chi^2_g of every chain's state in chi2g [G][ncol] and records
-// sqrt(B_g) and B_g per group; k_mc_noise_groups_final is k_mc_noise_final per (group, cell).  One group is the mode above itself.
+// Noise scales integrated out (dazim_mc_set_noise_groups, G <= 4 groups of periods; dazim_mc_set_noise is the one group of every
+// period): the data std of a period of group g is lambda_g / w_p with lambda_g^2 ~ InverseGamma(a0_g, b0_g), and every lambda_g is
+// integrated out in closed form.  k_mc_step<KIND, TEMPER, NG> takes every decision on the energy X = sum_g 2 a_g log(B_g), B_g = b0_g +
+// chi^2_g / 2, a_g = a0_g + nd_g / 2, over the groups with data in the cell, in place of chi^2 (mc_energy); mc_chi2 forms chi^2_g
+// beside chi^2 in the one loop over the periods, chi2g [G][ncol] keeps the chi^2_g of every chain's state (G >= 2; one group's is
+// chi2), each recorded rung-0 lane adds sqrt(B_g) and B_g of its state to its own columns, and k_mc_noise_final turns those sums into
+// the posterior mean and std of lambda_g per (group, cell) (Rao-Blackwellisation again).
 //
 // Typed data (dazim_mc_set_segments): dazim_mc_run computes the proposals' curves with dazim_dispersion_kernels_typed, the handle's
 // periods being the virtual periods of the segments laid end to end; the step never asks what kind of wave a period is.
 //
 // Gaussian smoothness prior (dazim_mc_set_prior): dazim_column_lsq's regulariser read as a prior, exp(-Q / 2) with Q = d^T (smooth^2
-// L^T L + damp^2 I) d, d the state's knots minus a reference, inside the box.  k_mc_step<KIND, TEMPER, NOISE, 1> takes every decision
-// on E + Q in place of E (mc_prior_q; a rung samples (likelihood x Gaussian prior)^beta) and keeps the Q of every chain's state
+// L^T L + damp^2 I) d, d the state's knots minus a reference, inside the box.  k_mc_step<KIND, TEMPER, NG, 1> takes every decision
+// on E + Q in place of E (mc_total, mc_prior_q; a rung samples (likelihood x Gaussian prior)^beta) and keeps the Q of every chain's state
 // in pq [ncol].  The best model stays the one of lowest raw chi^2: the best-fitting model, not the maximum a posteriori.
 #include "mc_internal.h"
 
@@ -40,52 +38,63 @@
 
 namespace {
 
-// the energy a decision is taken on: chi^2 itself, or with the noise scale integrated out X = 2 a log(B(chi^2)), +inf at +inf
-template <int NOISE>
-__device__ __forceinline__ double mc_energy(const McDev &M, double a, double chi2) {
-  if constexpr (NOISE) return 2.0 * a * log((double)M.nb0 + 0.5 * chi2);
-  else return chi2;
-}
+// NG: the compile-time bound of the noise groups, 0 (the fixed noise level), 1 or MC_MAXGRP; group g < NG is on
+template <int NG>
+__device__ __forceinline__ bool mc_group_on(const McDev &M, int g) { return NG == 1 || g < M.ngrp; }
 
-// NOISE 2: X = sum over the groups g < ngrp with ndg[g] > 0, in group order, of 2 a_g log(B_g(chi^2_g)), a_g = a0_g + ndg[g] / 2; +inf
-// where the total chi^2 is (a chi^2_g is +inf only then)
-__device__ __forceinline__ double mc_energy_groups(const McDev &M, const int (&ndg)[MC_MAXGRP], const double (&cg)[MC_MAXGRP], double chi2) {
-  if (isinf(chi2)) return INFINITY;
-  double x = 0.0;
-#pragma unroll
-  for (int g = 0; g < MC_MAXGRP; g++)
-    if (g < M.ngrp && ndg[g] > 0) x += 2.0 * ((double)M.ga0[g] + 0.5 * ndg[g]) * log((double)M.gb0[g] + 0.5 * cg[g]);
-  return x;
-}
-
-// NOISE 2: the total chi^2 of column col's curves, today's sum in period order, and beside it chi^2_g of every group (each in period
+// the total chi^2 of column col's curves, the sum in period order, and for NG >= 1 beside it chi^2_g of every group (each in period
 // order within its group: the other groups add nothing) and nd_g, the group's periods with data in the cell.  A period with data and
-// no root makes the total and its group +inf
-__device__ __forceinline__ double mc_chi2_groups(const McDev &M, const double *__restrict__ pv, int cell, long col, double (&cgp)[MC_MAXGRP],
-                                                 int (&ndg)[MC_MAXGRP]) {
-  double chi2p = 0.0;
+// no root makes the total and its group +inf (NG 0 stops there: nothing else is counted)
+template <int NG>
+__device__ __forceinline__ double mc_chi2(const McDev &M, const double *__restrict__ pv, int cell, long col, double (&cg)[NG ? NG : 1],
+                                          int (&ndg)[NG ? NG : 1]) {
+  double chi2 = 0.0;
   for (int p = 0; p < M.kmax; p++) {
     const float w = M.wdat[(long)p * M.ncell + cell];
     if (w == 0.0f) continue;
-    const int gp = M.grp[p];
+    const int gp = NG > 1 ? M.grp[p] : 0;
 #pragma unroll
-    for (int g = 0; g < MC_MAXGRP; g++) ndg[g] += gp == g;
+    for (int g = 0; g < NG; g++) ndg[g] += gp == g;
     const double c = pv[(long)p * M.ncol + col];
     if (c == 0.0) {
-      chi2p = INFINITY;
+      chi2 = INFINITY;
+      if constexpr (NG == 0) break;
 #pragma unroll
-      for (int g = 0; g < MC_MAXGRP; g++)
-        if (gp == g) cgp[g] = INFINITY;
+      for (int g = 0; g < NG; g++)
+        if (gp == g) cg[g] = INFINITY;
       continue;
     }
     const double r = (double)w * ((double)M.cobs[(long)p * M.ncell + cell] - c);
     const double rr = r * r;
-    chi2p += rr;
+    chi2 += rr;
 #pragma unroll
-    for (int g = 0; g < MC_MAXGRP; g++)
-      if (gp == g) cgp[g] += rr;
+    for (int g = 0; g < NG; g++)
+      if (gp == g) cg[g] += rr;
   }
-  return chi2p;
+  return chi2;
+}
+
+// the energy a decision is taken on: chi^2 itself, or with the noise scales integrated out X = sum over the groups with ndg[g] > 0, in
+// group order from 0.0, of 2 a_g log(B_g(chi^2_g)), a_g = a0_g + ndg[g] / 2; +inf where the total chi^2 is (a chi^2_g is +inf only then)
+template <int NG>
+__device__ __forceinline__ double mc_energy(const McDev &M, const int (&ndg)[NG ? NG : 1], const double (&cg)[NG ? NG : 1], double chi2) {
+  if constexpr (NG == 0) {
+    return chi2;
+  } else {
+    if (isinf(chi2)) return INFINITY;
+    double x = 0.0;
+#pragma unroll
+    for (int g = 0; g < NG; g++)
+      if (mc_group_on<NG>(M, g) && ndg[g] > 0) x += 2.0 * ((double)M.ga0[g] + 0.5 * ndg[g]) * log((double)M.gb0[g] + 0.5 * cg[g]);
+    return x;
+  }
+}
+
+// what a decision compares: the energy, with the prior plus Q
+template <int PRIOR>
+__device__ __forceinline__ double mc_total(double x, double q) {
+  if constexpr (PRIOR) return x + q;
+  else return x;
 }
 
 // the prior energy Q = ps2 |L d|^2 + pd2 |d|^2 of column col of v [nz][ncol] (cur or prop), d = v - pref over the nlay sampled knots;
@@ -286,15 +295,13 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
 // TEMPER 1 (a ladder of ntemp > 1 rungs): the decision of rung r takes beta_r, the scale and its window are per rung (lane r < ntemp
 // keeps rung r's, counting its chains in the ballot), neighbouring rungs swap states by lane shuffles after the decision, and only
 // the rung-0 lanes record.  Each lane carries its chi^2 in a register from the decision through the swap.
-// NOISE 1 (dazim_mc_set_noise): the lane counts the cell's nd in its weight loop, the decision and the swap compare mc_energy of the
-// two chi^2, and a recorded lane adds sqrt(B) and B of its state to its own column of nsum.  The handle keeps raw chi^2 throughout.
-// NOISE 2 (dazim_mc_set_noise_groups, ngrp >= 2): the weight loop also forms chi^2_g and nd_g of every group (cgp, ndg), the decision
-// compares mc_energy_groups of the two states, each lane carries the chi^2_g of its state (cgs, 4 doubles) and its energy through the
-// swap, whose rule compares the two lanes' own energies (a_g is the cell's, so the partner's value is the one this lane would form),
-// the chi^2_g change lanes with the knots, and a recorded lane adds sqrt(B_g) and B_g per group with data.  chi2 stays the total.
-// PRIOR 1 (dazim_mc_set_prior): the lane walks its column of prop for Q', the decision and the swap compare energy + Q (the rules
-// for +inf still test chi^2 alone), Q travels beside chi^2 through the swap's shuffles, and pq keeps the Q of the lane's state.
-template <int KIND, int TEMPER, int NOISE, int PRIOR>
+// NG >= 1 (noise scales, at most NG groups): the weight loop also forms chi^2_g and nd_g of every group (cgp, ndg), the decision and
+// the swap compare mc_energy of two states, each lane carries the chi^2_g of its state (cgs) through the swap, whose rule compares
+// the two lanes' own energies (a_g is the cell's, so the partner's value is the one this lane would form), the chi^2_g change lanes
+// with the knots, and a recorded lane adds sqrt(B_g) and B_g per group with data to its own columns of nsum.  chi2 stays the total.
+// PRIOR 1 (dazim_mc_set_prior): the lane walks its column of prop for Q', the decision and the swap compare energy + Q (mc_total; the
+// rules for +inf still test chi^2 alone), Q travels beside chi^2 through the swap's shuffles, and pq keeps the Q of the lane's state.
+template <int KIND, int TEMPER, int NG, int PRIOR>
 __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__restrict__ pv, long long step, int first, int record,
                                                      int adapt, int nadapt) {
   __shared__ float s_scale;
@@ -307,34 +314,20 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
   const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
   const int nt = TEMPER ? M.ntemp : 1, rung = ch % nt;
   double chi2p = 0.0;
-  int nd = 0;                // NOISE: the cell's periods with data, and a = a0 + nd / 2
-  double na = 0.0;
   double chi2s = INFINITY;   // TEMPER: the chain's chi^2 after the decision, then after the swap
   unsigned wswap = 0u;       // TEMPER: word 1 of block(step, gid, 0), the swap uniform of a pair's lower chain
   double qp = 0.0, qs = 0.0;   // PRIOR: Q of the proposal; Q of the chain's state after the decision, then after the swap
-  double cgp[MC_MAXGRP] = {0.0, 0.0, 0.0, 0.0};   // NOISE 2: chi^2_g of the proposal
-  double cgs[MC_MAXGRP] = {INFINITY, INFINITY, INFINITY, INFINITY};   // ... of the chain's state after the decision, then the swap
-  int ndg[MC_MAXGRP] = {0, 0, 0, 0};              // ... the cell's periods with data per group
+  double cgp[NG ? NG : 1], cgs[NG ? NG : 1];   // NG: chi^2_g of the proposal; of the chain's state after the decision, then the swap
+  int ndg[NG ? NG : 1];                        // ... the cell's periods with data per group
+#pragma unroll
+  for (int g = 0; g < (NG ? NG : 1); g++) {
+    cgp[g] = 0.0;
+    cgs[g] = INFINITY;
+    ndg[g] = 0;
+  }
   bool acc = false;
   if (act) {
-    if constexpr (NOISE == 2) {
-      chi2p = mc_chi2_groups(M, pv, cell, col, cgp, ndg);
-    } else {
-      for (int p = 0; p < M.kmax; p++) {
-        const float w = M.wdat[(long)p * M.ncell + cell];
-        if (w == 0.0f) continue;
-        nd++;
-        const double c = pv[(long)p * M.ncol + col];
-        if (c == 0.0) {   // no root at a period with data
-          chi2p = INFINITY;
-          if constexpr (NOISE) continue;   // (nd needs the rest of the loop; +inf stays)
-          else break;
-        }
-        const double r = (double)w * ((double)M.cobs[(long)p * M.ncell + cell] - c);
-        chi2p += r * r;
-      }
-    }
-    if constexpr (NOISE == 1) na = (double)M.na0 + 0.5 * nd;
+    chi2p = mc_chi2<NG>(M, pv, cell, col, cgp, ndg);
     if constexpr (PRIOR) qp = mc_prior_q(M, M.prop, col, cell);
     if (first) {
       acc = true;
@@ -342,40 +335,27 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       // a chain without a curve takes the first proposal that has one; else Metropolis on the energies at the rung's beta (1 without
       // a ladder, which leaves the product's bits alone).  Where the first rule decides only a ladder draws block 0, for its word 1
       const double chi2c = M.chi2[col];
-      double xp, xc;
-      if constexpr (NOISE == 2) {
 #pragma unroll
-        for (int g = 0; g < MC_MAXGRP; g++)
-          if (g < M.ngrp) cgs[g] = M.chi2g[(long)g * M.ncol + col];
-        xp = mc_energy_groups(M, ndg, cgp, chi2p);
-        xc = mc_energy_groups(M, ndg, cgs, chi2c);
-      } else {
-        xp = mc_energy<NOISE>(M, na, chi2p);
-        xc = mc_energy<NOISE>(M, na, chi2c);
-      }
+      for (int g = 0; g < NG; g++)
+        if (mc_group_on<NG>(M, g)) cgs[g] = NG > 1 ? M.chi2g[(long)g * M.ncol + col] : chi2c;   // (one group's chi^2_g is chi^2)
+      const double xp = mc_energy<NG>(M, ndg, cgp, chi2p), xc = mc_energy<NG>(M, ndg, cgs, chi2c);
       double beta = 1.0;
       if constexpr (TEMPER) beta = M.beta[rung];
       unsigned w[4] = {0u, 0u, 0u, 0u};
       if (TEMPER || !isinf(chi2c)) mc_block(w, step, gid, 0u, M.seed);
       wswap = w[1];
       chi2s = chi2c;
-      if constexpr (PRIOR) {
-        qs = M.pq[col];
-        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * beta * ((xp + qp) - (xc + qs));
-      } else {
-        acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * beta * (xp - xc);
-      }
+      if constexpr (PRIOR) qs = M.pq[col];
+      acc = isinf(chi2c) ? !isinf(chi2p) : log(mc_uniform(w[0])) < -0.5 * beta * (mc_total<PRIOR>(xp, qp) - mc_total<PRIOR>(xc, qs));
     }
     if (acc) {
       for (int k = 0; k < M.nlay; k++) M.cur[k * M.ncol + col] = M.prop[k * M.ncol + col];
       M.chi2[col] = chi2p;
       chi2s = chi2p;
-      if constexpr (NOISE == 2) {
 #pragma unroll
-        for (int g = 0; g < MC_MAXGRP; g++) {
-          cgs[g] = cgp[g];
-          if (g < M.ngrp) M.chi2g[(long)g * M.ncol + col] = cgp[g];
-        }
+      for (int g = 0; g < NG; g++) {
+        cgs[g] = cgp[g];
+        if (NG > 1 && g < M.ngrp) M.chi2g[(long)g * M.ncol + col] = cgp[g];
       }
       if constexpr (PRIOR) {
         M.pq[col] = qp;
@@ -399,25 +379,12 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         qup = __shfl_down(qs, 1);
         qdn = __shfl_up(qs, 1);
       }
-      double xs = 0.0, xup = 0.0;   // NOISE 2: the energy of the lane's state, and of the upper neighbour's
-      if constexpr (NOISE == 2) {
-        xs = mc_energy_groups(M, ndg, cgs, chi2s);
-        xup = __shfl_down(xs, 1);
-      }
+      const double xs = mc_energy<NG>(M, ndg, cgs, chi2s), xup = __shfl_down(xs, 1);   // the lane's energy, the upper neighbour's
       int sw = 0;
       if (lower) {
         if (isinf(chi2s)) sw = !isinf(cup);
-        else if (!isinf(cup)) {
-          if constexpr (NOISE == 2) {
-            if constexpr (PRIOR) sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) * ((xs + qs) - (xup + qup));
-            else sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) * (xs - xup);
-          } else if constexpr (PRIOR)
-            sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) *
-                                              ((mc_energy<NOISE>(M, na, chi2s) + qs) - (mc_energy<NOISE>(M, na, cup) + qup));
-          else
-            sw = log(mc_uniform(wswap)) <
-                 0.5 * (M.beta[rung] - M.beta[rung + 1]) * (mc_energy<NOISE>(M, na, chi2s) - mc_energy<NOISE>(M, na, cup));
-        }
+        else if (!isinf(cup))
+          sw = log(mc_uniform(wswap)) < 0.5 * (M.beta[rung] - M.beta[rung + 1]) * (mc_total<PRIOR>(xs, qs) - mc_total<PRIOR>(xup, qup));
       }
       const int swu = __shfl_up(sw, 1);
       const bool swp = lower ? sw != 0 : (upper && swu != 0);
@@ -427,14 +394,12 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         const float vp = __shfl(v, partner);
         if (swp) M.cur[k * M.ncol + col] = vp;
       }
-      if constexpr (NOISE == 2) {
 #pragma unroll
-        for (int g = 0; g < MC_MAXGRP; g++) {
-          const double cp = __shfl(cgs[g], partner);
-          if (swp) {
-            cgs[g] = cp;
-            if (g < M.ngrp) M.chi2g[(long)g * M.ncol + col] = cp;
-          }
+      for (int g = 0; g < NG; g++) {
+        const double cp = __shfl(cgs[g], partner);
+        if (swp) {
+          cgs[g] = cp;
+          if (NG > 1 && g < M.ngrp) M.chi2g[(long)g * M.ncol + col] = cp;
         }
       }
       if (swp) {
@@ -486,23 +451,15 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         b = b < 0 ? 0 : (b >= M.nbin ? M.nbin - 1 : b);
         atomicAdd(&M.hist[((long)cs * M.nlay + k) * M.nbin + b], 1u);
       }
-      if constexpr (NOISE == 2) {
+      if constexpr (NG >= 1) {
         if (!isinf(M.chi2[col])) {   // (cgs: the state's chi^2_g, after the decision and the swap)
 #pragma unroll
-          for (int g = 0; g < MC_MAXGRP; g++)
-            if (g < M.ngrp && ndg[g] > 0) {
+          for (int g = 0; g < NG; g++)
+            if (mc_group_on<NG>(M, g) && ndg[g] > 0) {
               const double B = (double)M.gb0[g] + 0.5 * cgs[g];
               M.nsum[(long)g * M.ncol + col] += sqrt(B);
               M.nsum[((long)M.ngrp + g) * M.ncol + col] += B;
             }
-          M.ncnt[col] += 1;
-        }
-      } else if constexpr (NOISE) {
-        const double c2 = M.chi2[col];   // the lane's own store, after the decision and the swap
-        if (!isinf(c2)) {
-          const double B = (double)M.nb0 + 0.5 * c2;
-          M.nsum[col] += sqrt(B);
-          M.nsum[M.ncol + col] += B;
           M.ncnt[col] += 1;
         }
       }
@@ -653,44 +610,11 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_final(McDev M, long long nrec, l
   }
 }
 
-// the noise scale's posterior (dazim_mc_noise_result), one lane per inner cell: conditional on a state lambda^2 ~ IG(a, B), so
-// E[lambda] = g(a) E[sqrt(B)] and E[lambda^2] = E[B] / (a - 1); the cell's cold columns in column order inside the lane
+// the noise scales' posteriors (dazim_mc_noise_result, dazim_mc_noise_groups_result), one lane per (group, inner cell): conditional on
+// a state lambda_g^2 ~ IG(a_g, B_g), so E[lambda_g] = g(a_g) E[sqrt(B_g)] and E[lambda_g^2] = E[B_g] / (a_g - 1); the cell's cold
+// columns in column order inside the lane, the record's count the cell's; 0 for a group without data in the cell
 __global__ __launch_bounds__(MC_WAVE) void k_mc_noise_final(McDev M, float *__restrict__ lam_mean, float *__restrict__ lam_std,
                                                             int *__restrict__ ndata) {
-  const int cell = blockIdx.x * MC_WAVE + threadIdx.x;
-  if (cell >= M.ncell) return;
-  const int cs = M.cs_of[cell];
-  int nd = 0;
-  for (int p = 0; p < M.kmax; p++) nd += M.wdat[(long)p * M.ncell + cell] != 0.0f;
-  ndata[cell] = nd;
-  if (cs < 0) {
-    lam_mean[cell] = 0.0f;
-    lam_std[cell] = 0.0f;
-    return;
-  }
-  long long n = 0;
-  double s0 = 0.0, s1 = 0.0;
-  for (int ch = 0; ch < M.nchain; ch += M.ntemp) {
-    const long col = (long)cs * M.nchain + ch;
-    n += M.ncnt[col];
-    s0 += M.nsum[col];
-    s1 += M.nsum[M.ncol + col];
-  }
-  if (n == 0) {
-    lam_mean[cell] = NAN;
-    lam_std[cell] = NAN;
-    return;
-  }
-  const double a = (double)M.na0 + 0.5 * nd, dn = (double)n;
-  const double lm = M.ngam[nd] * s0 / dn;
-  lam_mean[cell] = (float)lm;
-  lam_std[cell] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
-}
-
-// the noise scales' posteriors (dazim_mc_noise_groups_result), one lane per (group, inner cell): k_mc_noise_final with the group's
-// periods, prior, sums and table; the record's count is the cell's.  With one group: k_mc_noise_final's values, bit for bit
-__global__ __launch_bounds__(MC_WAVE) void k_mc_noise_groups_final(McDev M, float *__restrict__ lam_mean, float *__restrict__ lam_std,
-                                                                   int *__restrict__ ndata) {
   const long i = (long)blockIdx.x * MC_WAVE + threadIdx.x;
   if (i >= (long)M.ngrp * M.ncell) return;
   const int g = (int)(i / M.ncell), cell = (int)(i - (long)g * M.ncell);
@@ -726,14 +650,13 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_noise_groups_final(McDev M, floa
   lam_std[i] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
 }
 
-// the step kernel of a handle: [prior][noise][kind][tempered]
+// the step kernel of a handle: [prior][noise: off, one group, more][kind][tempered]
 using McStepKernel = void (*)(McDev, const double *, long long, int, int, int, int);
-#define MC_STEP_SET(P)                                                                            \
-  {{{k_mc_step<0, 0, 0, P>, k_mc_step<0, 1, 0, P>}, {k_mc_step<1, 0, 0, P>, k_mc_step<1, 1, 0, P>}}, \
-   {{k_mc_step<0, 0, 1, P>, k_mc_step<0, 1, 1, P>}, {k_mc_step<1, 0, 1, P>, k_mc_step<1, 1, 1, P>}}, \
-   {{k_mc_step<0, 0, 2, P>, k_mc_step<0, 1, 2, P>}, {k_mc_step<1, 0, 2, P>, k_mc_step<1, 1, 2, P>}}}
+#define MC_STEP_NG(G, P) {{k_mc_step<0, 0, G, P>, k_mc_step<0, 1, G, P>}, {k_mc_step<1, 0, G, P>, k_mc_step<1, 1, G, P>}}
+#define MC_STEP_SET(P) {MC_STEP_NG(0, P), MC_STEP_NG(1, P), MC_STEP_NG(MC_MAXGRP, P)}
 constexpr McStepKernel MC_STEP[2][3][2][2] = {MC_STEP_SET(0), MC_STEP_SET(1)};
 #undef MC_STEP_SET
+#undef MC_STEP_NG
 
 // the Q of every chain's state into pq (dazim_mc_set_prior; the step keeps it from there on), lane = chain
 __global__ __launch_bounds__(MC_WAVE) void k_mc_prior_q(McDev M) {
@@ -756,7 +679,7 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
     DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
     const size_t lds =
         mc->kind == 1 ? ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double) : 0;
-    const McStepKernel kern = MC_STEP[mc->prior][mc->noise][mc->kind][mc->d.ntemp > 1];
+    const McStepKernel kern = MC_STEP[mc->prior][std::min(mc->d.ngrp, 2)][mc->kind][mc->d.ntemp > 1];
     hipLaunchKernelGGL(kern, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record, (int)adapt,
                        mc->nadapt);
     DZ_HIP(hipGetLastError());
@@ -1000,10 +923,8 @@ static int mc_noise_setup(dazim_ctx *ctx, dazim_mc *mc, int G, const int *grp, c
   McDev &M = mc->d;
   int rc;
   if (G == 0) {
-    M.na0 = M.nb0 = 0.0f;
     M.ngrp = 0;
     for (int g = 0; g < MC_MAXGRP; g++) M.ga0[g] = M.gb0[g] = 0.0f;
-    mc->noise = 0;
     return 0;
   }
   DZ_HIP(hipSetDevice(ctx->device));
@@ -1038,10 +959,7 @@ static int mc_noise_setup(dazim_ctx *ctx, dazim_mc *mc, int G, const int *grp, c
     M.ga0[g] = g < G ? a0[g] : 0.0f;
     M.gb0[g] = g < G ? b0[g] : 0.0f;
   }
-  M.na0 = G == 1 ? a0[0] : 0.0f;
-  M.nb0 = G == 1 ? b0[0] : 0.0f;
   M.ngrp = G;
-  mc->noise = G == 1 ? 1 : 2;
   return 0;
 }
 
@@ -1089,7 +1007,7 @@ int dazim_mc_noise_groups_state(dazim_ctx *ctx, dazim_mc *mc, int *ngroup, int *
   if ((rc = mc_check(ctx, mc, "dazim_mc_noise_groups_state"))) return rc;
   const McDev &M = mc->d;
   if (ngroup) *ngroup = M.ngrp;
-  if (!mc->noise) {
+  if (!M.ngrp) {
     if (group_of_period || a0 || b0 || chi2g || nsum || ncnt)
       return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_groups_state: no noise scale is switched on");
     return 0;
@@ -1109,12 +1027,14 @@ int dazim_mc_noise_groups_state(dazim_ctx *ctx, dazim_mc *mc, int *ngroup, int *
   return 0;
 }
 
-int dazim_mc_noise_groups_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u, float *lam_std_u, int *ndata_u) {
+// dazim_mc_noise_result (single: exactly one group is on) and dazim_mc_noise_groups_result
+static int mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, const char *what, bool single, float *lam_mean_u, float *lam_std_u, int *ndata_u) {
   int rc;
-  if ((rc = mc_check(ctx, mc, "dazim_mc_noise_groups_result"))) return rc;
-  if (!lam_mean_u || !lam_std_u || !ndata_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_noise_groups_result");
-  if (!mc->noise) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_groups_result: no noise scale is switched on");
-  if (mc->d.ncs > 0 && mc->nrec < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_groups_result: no recorded step yet");
+  if ((rc = mc_check(ctx, mc, what))) return rc;
+  if (!lam_mean_u || !lam_std_u || !ndata_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to %s", what);
+  if (single && mc->d.ngrp != 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: dazim_mc_set_noise has not switched the noise scale on", what);
+  if (!mc->d.ngrp) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: no noise scale is switched on", what);
+  if (mc->d.ncs > 0 && mc->nrec < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: no recorded step yet", what);
   DZ_HIP(hipSetDevice(ctx->device));
   const McDev &M = mc->d;
   const size_t n = (size_t)M.ngrp * M.ncell;
@@ -1123,12 +1043,16 @@ int dazim_mc_noise_groups_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u
   if ((rc = lm.init(ctx, lam_mean_u, n, false, true)) || (rc = ls.init(ctx, lam_std_u, n, false, true)) ||
       (rc = nd.init(ctx, ndata_u, n, false, true)))
     return rc;
-  hipLaunchKernelGGL(k_mc_noise_groups_final, dim3((unsigned)((n + MC_WAVE - 1) / MC_WAVE)), dim3(MC_WAVE), 0, ctx->stream, M, lm.dev,
-                     ls.dev, nd.dev);
+  hipLaunchKernelGGL(k_mc_noise_final, dim3((unsigned)((n + MC_WAVE - 1) / MC_WAVE)), dim3(MC_WAVE), 0, ctx->stream, M, lm.dev, ls.dev,
+                     nd.dev);
   DZ_HIP(hipGetLastError());
   if ((rc = lm.finish()) || (rc = ls.finish()) || (rc = nd.finish())) return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+int dazim_mc_noise_groups_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u, float *lam_std_u, int *ndata_u) {
+  return mc_noise_result(ctx, mc, "dazim_mc_noise_groups_result", false, lam_mean_u, lam_std_u, ndata_u);
 }
 
 int dazim_mc_set_segments(dazim_ctx *ctx, dazim_mc *mc, int nseg, const int *seg_iwave, const int *seg_igr, const int *seg_kmax) {
@@ -1173,9 +1097,9 @@ int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, dou
   int rc;
   if ((rc = mc_check(ctx, mc, "dazim_mc_noise_state"))) return rc;
   const McDev &M = mc->d;
-  if (a0) *a0 = M.na0;
-  if (b0) *b0 = M.nb0;
-  if (mc->noise != 1) {   // (with several groups a0 = b0 = 0 here: the record is dazim_mc_noise_groups_state's)
+  if (a0) *a0 = M.ngrp == 1 ? M.ga0[0] : 0.0f;
+  if (b0) *b0 = M.ngrp == 1 ? M.gb0[0] : 0.0f;
+  if (M.ngrp != 1) {   // (with several groups a0 = b0 = 0 here: the record is dazim_mc_noise_groups_state's)
     if (nsum || ncnt) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_state: dazim_mc_set_noise has not switched the noise scale on");
     return 0;
   }
@@ -1187,25 +1111,7 @@ int dazim_mc_noise_state(dazim_ctx *ctx, dazim_mc *mc, float *a0, float *b0, dou
 }
 
 int dazim_mc_noise_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean_u, float *lam_std_u, int *ndata_u) {
-  int rc;
-  if ((rc = mc_check(ctx, mc, "dazim_mc_noise_result"))) return rc;
-  if (!lam_mean_u || !lam_std_u || !ndata_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_mc_noise_result");
-  if (mc->noise != 1)
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_result: dazim_mc_set_noise has not switched the noise scale on");
-  if (mc->d.ncs > 0 && mc->nrec < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_noise_result: no recorded step yet");
-  DZ_HIP(hipSetDevice(ctx->device));
-  const McDev &M = mc->d;
-  DzBuf<float> lm, ls;
-  DzBuf<int> nd;
-  if ((rc = lm.init(ctx, lam_mean_u, (size_t)M.ncell, false, true)) || (rc = ls.init(ctx, lam_std_u, (size_t)M.ncell, false, true)) ||
-      (rc = nd.init(ctx, ndata_u, (size_t)M.ncell, false, true)))
-    return rc;
-  hipLaunchKernelGGL(k_mc_noise_final, dim3((unsigned)((M.ncell + MC_WAVE - 1) / MC_WAVE)), dim3(MC_WAVE), 0, ctx->stream, M, lm.dev,
-                     ls.dev, nd.dev);
-  DZ_HIP(hipGetLastError());
-  if ((rc = lm.finish()) || (rc = ls.finish()) || (rc = nd.finish())) return rc;
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
-  return 0;
+  return mc_noise_result(ctx, mc, "dazim_mc_noise_result", true, lam_mean_u, lam_std_u, ndata_u);
 }
 
 int dazim_mc_set_prior(dazim_ctx *ctx, dazim_mc *mc, float smooth, float damp, const float *vref_u) {
@@ -1392,7 +1298,7 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
   ctx->ksec["mc.swap_min"] = swap_min;
   ctx->ksec["mc.swap_med"] = swap_med;
   ctx->ksec["mc.proposal"] = mc->kind;
-  ctx->ksec["mc.noise"] = mc->noise;
+  ctx->ksec["mc.noise"] = std::min(mc->d.ngrp, 2);
   ctx->ksec["mc.noise_groups"] = mc->d.ngrp;
   ctx->ksec["mc.prior"] = mc->prior;
   ctx->ksec["mc.cov_cells"] = cov_cells;

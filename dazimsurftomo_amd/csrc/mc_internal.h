@@ -75,17 +75,15 @@ struct McDev {
   float *tscale;               // [ncs][ntemp]
   int *tacc_win;               // [ncs][ntemp]
   long long *swap_try, *swap_acc;   // [ncs][ntemp - 1]
-  // hierarchical noise only (null otherwise): lambda^2 ~ InverseGamma(na0, nb0) a priori
-  float na0, nb0;
-  double *nsum;                // [2][ncol]: sums of sqrt(B) and of B over the recorded states, B = nb0 + chi^2 / 2
-  long long *ncnt;             // [ncol]: states in them
-  const double *ngam;          // [MC_MAXPER + 1]: exp(lgamma(a - 0.5) - lgamma(a)) at a = na0 + nd / 2, made on the host
-  // ... in ngrp groups of periods (0 while the mode is off; 1: the mode above, ga0[0] = na0, gb0[0] = nb0; >= 2: na0 = nb0 = 0 and
-  // lambda_g^2 ~ InverseGamma(ga0[g], gb0[g]), nsum [2][ngrp][ncol], B_g = gb0[g] + chi^2_g / 2, ngam [ngrp][MC_MAXPER + 1])
+  // noise scales only (ngrp = 0 and null otherwise): ngrp groups of periods (dazim_mc_set_noise: the one group of every period),
+  // lambda_g^2 ~ InverseGamma(ga0[g], gb0[g]) a priori
   int ngrp;
   float ga0[MC_MAXGRP], gb0[MC_MAXGRP];
   const int *grp;              // [kmax]: the group of every period
   double *chi2g;               // [ngrp][ncol], ngrp >= 2 only: chi^2_g of every chain's state (+inf before the first step)
+  double *nsum;                // [2][ngrp][ncol]: sums of sqrt(B_g) and of B_g over the recorded states, B_g = gb0[g] + chi^2_g / 2
+  long long *ncnt;             // [ncol]: states in them
+  const double *ngam;          // [ngrp][MC_MAXPER + 1]: exp(lgamma(a - 0.5) - lgamma(a)) at a = ga0[g] + nd / 2, made on the host
   // Gaussian smoothness prior only (null and 0 otherwise): precision ps2 L^T L + pd2 I about pref, truncated by the box
   double ps2, pd2;             // (double)smooth^2, (double)damp^2
   const float *pref;           // [nlay][ncell]: the prior's centre
@@ -119,7 +117,6 @@ struct dazim_mc {
   int nthin = 0;            // Gc/Gs: 0 = off, else one pass per nthin recorded steps of dazim_mc_run
   McAniso an{};             // ... its maps and sums (sized for ntemp = 1, so that any ladder fits)
   int64_t naniso = 0;       // ... samples taken
-  int noise = 0;            // hierarchical noise: 0 = off, 1 = one scale (d.na0, d.nb0 hold the prior), 2 = d.ngrp >= 2 scales
   int nseg = 1;             // dazim_mc_set_segments: the segments of the kmax periods (the default: Rayleigh phase alone)
   int seg_iwave[MC_MAXSEG] = {2, 0, 0, 0}, seg_igr[MC_MAXSEG] = {0, 0, 0, 0}, seg_kmax[MC_MAXSEG] = {0, 0, 0, 0};
   bool typed = false;       // ... other than Rayleigh phase alone: dazim_mc_run calls dazim_dispersion_kernels_typed

@@ -1,15 +1,16 @@
-"""NumPy restatement of the Monte-Carlo step with one noise scale per group of periods (dazim_mc_set_noise_groups, include/dazim.h,
-DESIGN.md section 14): chi2_g beside chi2, the energy X = sum_g 2 a_g log(b0_g + chi2_g / 2), the record per group and its result.
-Everything the groups do not touch is tests/mc_ref.py's: the random numbers, the proposals, the ladder, the covariance sums and the Vs
-statistics.  With one group every function here returns the bytes of its mc_ref counterpart (tests/test_mc_groups_ref_cpu.py)."""
+"""NumPy restatement of the noise scales of the Monte-Carlo step, one per group of periods (dazim_mc_set_noise_groups and, as one
+group, dazim_mc_set_noise; include/dazim.h): chi2_g beside chi2, the energy X = sum_g 2 a_g log(b0_g + chi2_g /
+2), the record per group and its result, as tests/mc_ref.py's step and sample use them; and the linear problem of the group tests."""
 import math
 
 import numpy as np
 
-from tests import mc_ref
-from tests.mc_ref import BRANCHES, COV_MIN, block, cholesky, covariance, layout, pairs, uniform
-
 MAXGRP = 4
+
+
+def gamma_ratio(a):
+    """g(a) = Gamma(a - 1/2) / Gamma(a) as the library's table forms it"""
+    return math.exp(math.lgamma(a - 0.5) - math.lgamma(a))
 
 
 def chi2_groups(pv, cobs, wdat, grp, G):
@@ -48,126 +49,6 @@ def empty_groups(grp, a0, b0, ncol):
                 ncnt=np.zeros(ncol, np.int64))
 
 
-def step(st, tp, cov, gs, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nchain, lo, hi, cobs, wdat, nbin, seed):
-    """mc_ref.step with the noise groups `gs` (MonteCarlo.noise_groups_state(), or empty_groups) in place of its noise record: the
-    same arguments, the same returns with the new groups' state (chi2g, nsum, ncnt) fourth"""
-    nz, ncol = prop.shape
-    nlay = nz - 1
-    nt, nswap, beta = tp["ntemp"], tp["nswap"], tp["beta"]
-    ncold = nchain // nt
-    ncs, cs, rung, gid = layout(ncol, nchain, nt, gcell)
-    G, grp, a0, b0 = gs["ngroup"], gs["group_of_period"], gs["a0"], gs["b0"]
-    ndg = ndata_groups(wdat, grp, G)
-    chi2p, cgp = chi2_groups(pv, cobs, wdat, grp, G)
-    first = t == 1
-    if first:
-        acc = np.ones(ncol, bool)
-    else:
-        c = st["chi2"]
-        u = uniform(block(t, gid, 0, seed)[..., 0])
-        xp, xc = energy_groups(chi2p, cgp, ndg, a0, b0), energy_groups(c, gs["chi2g"], ndg, a0, b0)
-        with np.errstate(invalid="ignore"):
-            acc = np.where(np.isinf(c), ~np.isinf(chi2p), np.log(u) < -0.5 * beta[rung] * (xp - xc))
-    cur = st["cur"].copy()
-    cur[:nlay, acc] = prop[:nlay, acc]
-    ch2 = np.where(acc, chi2p, st["chi2"])
-    cg = np.where(acc[None, :], cgp, gs["chi2g"])
-    # the scale and the window of every (cell, rung)
-    scale = tp["scale"].copy()
-    acc_win = acc_win.copy()
-    set0 = cov["cov_set"].copy() if cov is not None else np.zeros(ncs, np.int32)
-    root = np.sqrt(np.float32(nlay))
-    if not record:
-        if not first:
-            np.add.at(acc_win, (cs, rung), acc.astype(np.int64))
-        if adapt:
-            rate = acc_win.astype(np.float64) / (float(nadapt) * float(ncold))
-            s = np.where(rate > 0.40, scale * np.float32(1.25), np.where(rate < 0.20, scale / np.float32(1.25), scale)).astype(np.float32)
-            cap = np.where(set0 == 1, np.float32(2.0) / root, np.float32(0.5)).astype(np.float32)[:, None]
-            scale = np.minimum(np.maximum(s, np.float32(1e-3)), cap).astype(np.float32)
-            acc_win[:] = 0
-    # the swap round, on the energies of the states; the chi2_g change columns with the knots and chi2
-    swap_try, swap_acc = tp["swap_try"].copy(), tp["swap_acc"].copy()
-    seen = dict.fromkeys(BRANCHES, 0)
-    if nt > 1 and not first and t % nswap == 0:
-        w = t // nswap
-        cl = np.nonzero((rung % 2 == w % 2) & (rung + 1 < nt))[0]
-        cu = cl + 1
-        u = uniform(block(t, gid[cl], 0, seed)[..., 1])
-        ca, cb = ch2[cl], ch2[cu]
-        xs = energy_groups(ch2, cg, ndg, a0, b0)
-        with np.errstate(invalid="ignore"):
-            D = 0.5 * (beta[rung[cl]] - beta[rung[cl] + 1]) * (xs[cl] - xs[cu])
-            sw = np.where(~np.isinf(ca) & ~np.isinf(cb), np.log(u) < D, np.isinf(ca) & ~np.isinf(cb))
-        for name, m in zip(BRANCHES, (~np.isinf(ca) & ~np.isinf(cb), np.isinf(ca) & ~np.isinf(cb), ~np.isinf(ca) & np.isinf(cb),
-                                      np.isinf(ca) & np.isinf(cb))):
-            seen[name] = int(m.sum())
-        l, h = cl[sw], cu[sw]
-        cur[:nlay, l], cur[:nlay, h] = cur[:nlay, h].copy(), cur[:nlay, l].copy()
-        ch2[l], ch2[h] = ch2[h].copy(), ch2[l].copy()
-        cg[:, l], cg[:, h] = cg[:, h].copy(), cg[:, l].copy()
-        np.add.at(swap_try, (cs[cl], rung[cl]), 1)
-        np.add.at(swap_acc, (cs[cl], rung[cl]), sw.astype(np.int64))
-    # the records: the rung-0 chains; the best model over every chain, by raw chi2
-    sums, hist, accepted = st["sums"].copy(), st["hist"].copy(), st["accepted"].copy()
-    best, best_chi2 = st["best"].copy(), st["best_chi2"].copy()
-    nsum, ncnt = gs["nsum"].copy(), gs["ncnt"].copy()
-    cold = rung == 0
-    if record:
-        if not first:
-            accepted += acc & cold
-        c2 = ch2.reshape(ncs, nchain)
-        win = np.argmin(c2, axis=1)
-        m = c2[np.arange(ncs), win]
-        upd = m < best_chi2
-        wcol = np.arange(ncs) * nchain + win
-        best[:, upd] = cur[:nlay, wcol[upd]]
-        best_chi2 = np.where(upd, m, best_chi2)
-        v = cur[:nlay, cold].astype(np.float64)
-        sums[0][:, cold] += v
-        sums[1][:, cold] += v * v
-        b = ((v - lo[:, cold]) / (hi[:, cold] - lo[:, cold]) * float(nbin)).astype(np.int64)
-        b = np.clip(b, 0, nbin - 1)
-        for k in range(nlay):
-            np.add.at(hist, (cs[cold], k, b[k]), 1)
-        rec = cold & ~np.isinf(ch2)
-        for g in range(G):   # B_g at the state of every rung-0 chain with a finite chi2, for the groups with data
-            rg = rec & (ndg[g] > 0)
-            B = float(np.float32(b0[g])) + 0.5 * cg[g, rg]
-            nsum[0, g, rg] += np.sqrt(B)
-            nsum[1, g, rg] += B
-        ncnt[rec] += 1
-    # kind 1: the sums over the rung-0 chains in chain order, the factor at an adaptation point
-    factored = {}
-    if cov is not None:
-        cov = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in cov.items()}
-        if not record and not first:
-            u = (cur[:nlay].astype(np.float64) - lo) / (hi - lo)
-            pa, pc = pairs(nlay)
-            for col in np.nonzero(cold)[0]:
-                cov["cov_s1"][cs[col]] += u[:, col]
-                cov["cov_s2"][cs[col]] += u[pa, col] * u[pc, col]
-            cov["cov_n"] += ncold
-            if adapt:
-                for e in range(ncs):
-                    if cov["cov_n"][e] < COV_MIN * nlay:
-                        continue
-                    Cm = covariance(cov["cov_n"][e], cov["cov_s1"][e], cov["cov_s2"][e], nlay)
-                    ok, L = cholesky(Cm)
-                    factored[e] = Cm
-                    if ok:
-                        cov["chol"][e] = L
-                        if set0[e] == 0:
-                            cov["cov_set"][e] = 1
-                            scale[e, :] = np.float32(1.0) / root
-                    cov["cov_n"][e] = 0
-                    cov["cov_s1"][e] = 0.0
-                    cov["cov_s2"][e] = 0.0
-    new = dict(cur=cur, chi2=ch2, scale=scale[:, 0].copy(), step=t, sums=sums, hist=hist, accepted=accepted, best=best, best_chi2=best_chi2)
-    ntp = dict(tp, scale=scale, swap_try=swap_try, swap_acc=swap_acc)
-    return new, ntp, cov, dict(gs, chi2g=cg, nsum=nsum, ncnt=ncnt), acc, acc_win, factored, seen
-
-
 def result(gs, wdat_cells, cells, ncell, nchain, ntemp):
     """dazim_mc_noise_groups_result from the groups' record: wdat_cells [kmax][ncell] fp32 (the inner cells), cells the sampled
     inner-cell indices.  Returns dict lam_mean, lam_std [G][ncell] fp32 and ndata [G][ncell] int32"""
@@ -189,45 +70,10 @@ def result(gs, wdat_cells, cells, ncell, nchain, ntemp):
                 lam_mean[g, cell] = lam_std[g, cell] = np.nan
                 continue
             a = a0 + 0.5 * int(nd[g, cell])
-            lm = mc_ref.gamma_ratio(a) * s0 / float(n)
+            lm = gamma_ratio(a) * s0 / float(n)
             lam_mean[g, cell] = np.float32(lm)
             lam_std[g, cell] = np.nan if a <= 1.0 else np.float32(math.sqrt(max(s1 / (float(n) * (a - 1.0)) - lm * lm, 0.0)))
     return dict(lam_mean=lam_mean, lam_std=lam_std, ndata=nd)
-
-
-def sample(forward, nburn, nsample, nadapt, gcell, nchain, vmin, vmax, vlast, cobs, wdat, nbin, seed, grp, a0, b0, step0=0.05, ntemp=1,
-           tmax=1.0, nswap=1, kind=0):
-    """mc_ref.sample with the groups (grp [kmax], a0, b0 [G]) in place of its (a0, b0).  Returns (state, ladder, groups' state)"""
-    nlay, ncs = vmin.shape
-    ncol = ncs * nchain
-    rep = lambda x: np.repeat(x, nchain, axis=-1)
-    lo, hi = rep(vmin.astype(np.float64)), rep(vmax.astype(np.float64))
-    cb, wd = rep(cobs), rep(wdat)
-    _, _, _, gid = layout(ncol, nchain, ntemp, gcell)
-    prop = np.concatenate([mc_ref.start_models(gid, lo, hi, seed), rep(vlast.astype(np.float32))[None]])
-    st = dict(cur=prop.copy(), chi2=np.full(ncol, np.inf), scale=np.full(ncs, step0, np.float32), step=0,
-              sums=np.zeros((2, nlay, ncol)), hist=np.zeros((ncs, nlay, nbin), np.uint32), accepted=np.zeros(ncol, np.int64),
-              best=np.zeros((nlay, ncs), np.float32), best_chi2=np.full(ncs, np.inf))
-    tp = dict(ntemp=ntemp, tmax=tmax, nswap=nswap)
-    if ntemp > 1:
-        tp.update(beta=mc_ref.ladder(ntemp, tmax), scale=np.full((ncs, ntemp), step0, np.float32),
-                  swap_try=np.zeros((ncs, ntemp - 1), np.int64), swap_acc=np.zeros((ncs, ntemp - 1), np.int64))
-    tp = mc_ref.ladder_state(st, tp)
-    cov = mc_ref.empty_cov(ncs, nlay) if kind == 1 else None
-    gs = empty_groups(grp, a0, b0, ncol)
-    acc_win = np.zeros((ncs, ntemp), np.int64)
-    nbd = 0
-    for t in range(1, nburn + nsample + 1):
-        record = t > nburn
-        adapt = False
-        if not record and t > 1:
-            nbd += 1
-            adapt = nbd % nadapt == 0
-        pv = forward(prop)
-        st, tp, cov, gs, _, acc_win, _, _ = step(st, tp, cov, gs, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nchain, lo, hi, cb,
-                                                 wd, nbin, seed)
-        prop = mc_ref.proposals(st["cur"], tp["scale"], cov, prop, t, gcell, nchain, lo, hi, seed)
-    return st, tp, gs
 
 
 # ---- the linear problem of the group tests, and its posterior by quadrature ---------------------------------------------------------
@@ -274,7 +120,7 @@ def quadrature(pb, n):
         mu[c] = p @ V
         sd[c] = np.sqrt(p @ (V - mu[c]) ** 2)
         for g in range(G):
-            lam1[g, c] = mc_ref.gamma_ratio(a[g]) * (p @ np.sqrt(B[g]))
+            lam1[g, c] = gamma_ratio(a[g]) * (p @ np.sqrt(B[g]))
             lam2[g, c] = (p @ B[g]) / (a[g] - 1.0)
     return dict(mu=mu, sd=sd, lam_mean=lam1, lam_std=np.sqrt(lam2 - lam1 ** 2))
 

@@ -1,13 +1,16 @@
 """NumPy restatement of the Monte-Carlo step of dazim_mc (include/dazim.h): Philox4x32-10, the draws, and one
 step from a copy of the handle's state, in every mode: proposal kind 0 or 1 (the covariance sums, the factor at the adaptation
 points, y = L z), a ladder of rungs or none (the decision at rung r, the scale per rung, the swaps, the records of the rung-0 chains),
-the fixed noise level or the hierarchical one (the energy X = 2 a log(b0 + chi2 / 2) wherever a decision is taken, the noise record
-and its result).  An untempered handle is a ladder of one rung with beta = 1, which leaves every product unchanged.  Every operation
-is the library's in the same order and precision (the library is compiled without FMA contraction); only log, sqrt, cos and sin may
-differ in the last bit, and lgamma and exp of the noise result's table in the last few."""
-import math
-
+the fixed noise level or noise scales integrated out (every scale a group of periods, tests/mc_groups_ref.py: the energy X = sum_g
+2 a_g log(b0_g + chi2_g / 2) wherever a decision is taken, the noise record and its result), the Gaussian prior or none (X + Q in
+place of X, tests/mc_prior_ref.py).  An untempered handle is a ladder of one rung with beta = 1, which leaves every product
+unchanged.  Every operation is the library's in the same order and precision (the library is compiled without FMA contraction); only
+log, sqrt, cos and sin may differ in the last bit, and lgamma and exp of the noise result's table in the last few."""
 import numpy as np
+
+from tests import mc_groups_ref
+from tests.mc_groups_ref import chi2_groups, empty_groups, energy_groups, gamma_ratio, ndata_groups  # noqa: F401
+from tests.mc_prior_ref import empty_prior, prior_q
 
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 W0, W1 = np.uint32(0x9E3779B9), np.uint32(0xBB67AE85)
@@ -169,36 +172,60 @@ def empty_noise(a0, b0, ncol):
     return dict(a0=float(np.float32(a0)), b0=float(np.float32(b0)), nsum=np.zeros((2, ncol)), ncnt=np.zeros(ncol, np.int64))
 
 
-def step(st, tp, cov, ns, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nchain, lo, hi, cobs, wdat, nbin, seed):
+def as_groups(ns, chi2, kmax):
+    """the noise record in the groups' form: None (the fixed level) and a groups record (noise_groups_state(), empty_groups()) as they
+    are; the single-scale record (noise_state(), empty_noise()) as its one group of every period, whose chi2_g is chi2 itself"""
+    if ns is None or "ngroup" in ns:
+        return ns
+    return dict(ngroup=1, group_of_period=np.zeros(kmax, np.int32), a0=np.float32([ns["a0"]]), b0=np.float32([ns["b0"]]),
+                chi2g=None if chi2 is None else chi2[None], nsum=ns["nsum"][:, None], ncnt=ns["ncnt"])
+
+
+def step(st, tp, cov, ns, pr, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nchain, lo, hi, cobs, wdat, nbin, seed):
     """one step from the state `st` (MonteCarlo.state()), the ladder `tp` (ladder_state(): one rung = untempered), `cov`
-    (MonteCarlo.cov_state() for kind 1, None for kind 0) and the noise record `ns` (MonteCarlo.noise_state(); None for the fixed noise
-    level: the energy is chi2 itself) and the proposals prop [nz][ncol]; gcell [ncs] the inner-cell index of each sampled cell; lo, hi
-    [nlay][ncol] fp64 and cobs, wdat [kmax][ncol] per column; acc_win [ncs][ntemp] the burn-in window counts.
-    Returns (new state, new ladder state, new cov with the restated factor or None, new noise record or None, accept decisions
-    [ncol], acc_win, {cs: C} of the cells factored in this step, {branch: pairs} of the swap rule's four cases).  The next proposals
-    come from proposals(), so that a test can form them from the library's factor."""
+    (MonteCarlo.cov_state() for kind 1, None for kind 0), the noise record `ns` (None for the fixed noise level: the energy is chi2
+    itself; MonteCarlo.noise_state() or empty_noise(); MonteCarlo.noise_groups_state() or empty_groups(): every scale is a group,
+    as_groups()), the prior record `pr` (empty_prior(), or MonteCarlo.prior_state() with vref per column; None: off) and the
+    proposals prop [nz][ncol]; gcell [ncs] the inner-cell index of each sampled cell; lo, hi [nlay][ncol] fp64 and cobs, wdat
+    [kmax][ncol] per column; acc_win [ncs][ntemp] the burn-in window counts.
+    Returns a dict: st, tp, cov (with the restated factor, or None), ns (in the form it came in, or None), pr (or None), acc (the
+    decisions [ncol]), acc_win, factored ({cs: C} of the cells factored in this step), seen ({branch: pairs} of the swap rule's four
+    cases) and diff ({"dec", "swap"}: decisions and swap rules that the prior made other than the energies alone would have).  The
+    next proposals come from proposals(), so that a test can form them from the library's factor."""
     nz, ncol = prop.shape
     nlay = nz - 1
     nt, nswap, beta = tp["ntemp"], tp["nswap"], tp["beta"]
     ncold = nchain // nt
     ncs, cs, rung, gid = layout(ncol, nchain, nt, gcell)
-    if ns is None:
-        X = lambda c2, sel=slice(None): c2
+    gs = as_groups(ns, st["chi2"], pv.shape[0])
+    if gs is None:
+        chi2p, cgp, cg = chi2(pv, cobs, wdat), None, None
+        X = lambda c2, g: c2
     else:
-        a = float(np.float32(ns["a0"])) + 0.5 * ndata(wdat)            # [ncol]
-        X = lambda c2, sel=slice(None): energy(c2, a[sel], ns["b0"])
-    chi2p = chi2(pv, cobs, wdat)
+        G = gs["ngroup"]
+        ndg = ndata_groups(wdat, gs["group_of_period"], G)
+        chi2p, cgp = chi2_groups(pv, cobs, wdat, gs["group_of_period"], G)
+        X = lambda c2, g: energy_groups(c2, g, ndg, gs["a0"], gs["b0"])
+    qp = prior_q(prop[:nlay], pr["vref"], pr["smooth"], pr["damp"]) if pr is not None else None
+    total = (lambda x, q: x + q) if pr is not None else (lambda x, q: x)
+    diff = dict(dec=0, swap=0)
     first = t == 1
     if first:
         acc = np.ones(ncol, bool)
     else:
         c = st["chi2"]
         u = uniform(block(t, gid, 0, seed)[..., 0])
+        xp, xc = X(chi2p, cgp), X(c, gs["chi2g"] if gs else None)
         with np.errstate(invalid="ignore"):
-            acc = np.where(np.isinf(c), ~np.isinf(chi2p), np.log(u) < -0.5 * beta[rung] * (X(chi2p) - X(c)))
+            rule = lambda d: np.where(np.isinf(c), ~np.isinf(chi2p), np.log(u) < -0.5 * beta[rung] * d)
+            acc = rule(total(xp, qp) - total(xc, pr["q"] if pr else None))
+            diff["dec"] = int((acc != rule(xp - xc)).sum())
     cur = st["cur"].copy()
     cur[:nlay, acc] = prop[:nlay, acc]
     ch2 = np.where(acc, chi2p, st["chi2"])
+    if gs is not None:
+        cg = np.where(acc[None, :], cgp, gs["chi2g"])
+    q = np.where(acc, qp, pr["q"]) if pr is not None else None
     # the scale and the window of every (cell, rung)
     scale = tp["scale"].copy()
     acc_win = acc_win.copy()
@@ -213,7 +240,7 @@ def step(st, tp, cov, ns, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nc
             cap = np.where(set0 == 1, np.float32(2.0) / root, np.float32(0.5)).astype(np.float32)[:, None]
             scale = np.minimum(np.maximum(s, np.float32(1e-3)), cap).astype(np.float32)
             acc_win[:] = 0
-    # the swap round, on the energies
+    # the swap round, on the totals of the states; chi2, the chi2_g and Q change columns with the knots
     swap_try, swap_acc = tp["swap_try"].copy(), tp["swap_acc"].copy()
     seen = dict.fromkeys(BRANCHES, 0)
     if nt > 1 and not first and t % nswap == 0:
@@ -222,21 +249,26 @@ def step(st, tp, cov, ns, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nc
         cu = cl + 1
         u = uniform(block(t, gid[cl], 0, seed)[..., 1])
         ca, cb = ch2[cl], ch2[cu]
+        both = ~np.isinf(ca) & ~np.isinf(cb)
+        xs = X(ch2, cg)
         with np.errstate(invalid="ignore"):
-            D = 0.5 * (beta[rung[cl]] - beta[rung[cl] + 1]) * (X(ca, cl) - X(cb, cl))
-            sw = np.where(~np.isinf(ca) & ~np.isinf(cb), np.log(u) < D, np.isinf(ca) & ~np.isinf(cb))
-        for name, m in zip(BRANCHES, (~np.isinf(ca) & ~np.isinf(cb), np.isinf(ca) & ~np.isinf(cb), ~np.isinf(ca) & np.isinf(cb),
-                                      np.isinf(ca) & np.isinf(cb))):
+            rule = lambda d: np.where(both, np.log(u) < 0.5 * (beta[rung[cl]] - beta[rung[cl] + 1]) * d, np.isinf(ca) & ~np.isinf(cb))
+            sw = rule(total(xs[cl], q[cl] if pr else None) - total(xs[cu], q[cu] if pr else None))
+            diff["swap"] = int((sw != rule(xs[cl] - xs[cu])).sum())
+        for name, m in zip(BRANCHES, (both, np.isinf(ca) & ~np.isinf(cb), ~np.isinf(ca) & np.isinf(cb), np.isinf(ca) & np.isinf(cb))):
             seen[name] = int(m.sum())
         l, h = cl[sw], cu[sw]
-        cur[:nlay, l], cur[:nlay, h] = cur[:nlay, h].copy(), cur[:nlay, l].copy()
-        ch2[l], ch2[h] = ch2[h].copy(), ch2[l].copy()
+        for v in (cur[:nlay], ch2, cg, q):
+            if v is not None:
+                v[..., l], v[..., h] = v[..., h].copy(), v[..., l].copy()
         np.add.at(swap_try, (cs[cl], rung[cl]), 1)
         np.add.at(swap_acc, (cs[cl], rung[cl]), sw.astype(np.int64))
     # the records: the rung-0 chains; the best model over every chain, by raw chi2
     sums, hist, accepted = st["sums"].copy(), st["hist"].copy(), st["accepted"].copy()
     best, best_chi2 = st["best"].copy(), st["best_chi2"].copy()
     cold = rung == 0
+    if gs is not None:
+        nsum, ncnt = gs["nsum"].copy(), gs["ncnt"].copy()
     if record:
         if not first:
             accepted += acc & cold
@@ -255,14 +287,14 @@ def step(st, tp, cov, ns, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nc
         b = np.clip(b, 0, nbin - 1)
         for k in range(nlay):
             np.add.at(hist, (cs[cold], k, b[k]), 1)
-        if ns is not None:   # the noise record: B at the state of every rung-0 chain with a finite chi2
-            nsum, ncnt = ns["nsum"].copy(), ns["ncnt"].copy()
+        if gs is not None:   # the noise record: B_g at the state of every rung-0 chain with a finite chi2, for the groups with data
             rec = cold & ~np.isinf(ch2)
-            B = float(np.float32(ns["b0"])) + 0.5 * ch2[rec]
-            nsum[0, rec] += np.sqrt(B)
-            nsum[1, rec] += B
+            for g in range(G):
+                rg = rec & (ndg[g] > 0)
+                B = float(np.float32(gs["b0"][g])) + 0.5 * cg[g, rg]
+                nsum[0, g, rg] += np.sqrt(B)
+                nsum[1, g, rg] += B
             ncnt[rec] += 1
-            ns = dict(ns, nsum=nsum, ncnt=ncnt)
     # kind 1: the sums over the rung-0 chains in chain order, the factor at an adaptation point
     factored = {}
     if cov is not None:
@@ -290,8 +322,10 @@ def step(st, tp, cov, ns, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nc
                     cov["cov_s1"][e] = 0.0
                     cov["cov_s2"][e] = 0.0
     new = dict(cur=cur, chi2=ch2, scale=scale[:, 0].copy(), step=t, sums=sums, hist=hist, accepted=accepted, best=best, best_chi2=best_chi2)
-    ntp = dict(tp, scale=scale, swap_try=swap_try, swap_acc=swap_acc)
-    return new, ntp, cov, ns, acc, acc_win, factored, seen
+    if ns is not None:   # back in the form it came in
+        ns = dict(ns, chi2g=cg, nsum=nsum, ncnt=ncnt) if "ngroup" in ns else dict(ns, nsum=nsum[:, 0], ncnt=ncnt)
+    return dict(st=new, tp=dict(tp, scale=scale, swap_try=swap_try, swap_acc=swap_acc), cov=cov, ns=ns,
+                pr=dict(pr, q=q) if pr is not None else None, acc=acc, acc_win=acc_win, factored=factored, seen=seen, diff=diff)
 
 
 def proposals(cur, tscale, cov, prop, t, gcell, nchain, lo, hi, seed):
@@ -373,39 +407,19 @@ def final(st, vmin, vmax, vel0_knots, cells, ncell, nchain, ntemp, nrec, ndec, n
     return out
 
 
-def gamma_ratio(a):
-    """g(a) = Gamma(a - 1/2) / Gamma(a) as the library's table forms it"""
-    return math.exp(math.lgamma(a - 0.5) - math.lgamma(a))
-
-
 def result(ns, wdat_cells, cells, ncell, nchain, ntemp):
-    """dazim_mc_noise_result from a noise record: wdat_cells [kmax][ncell] fp32 (the inner cells), cells the sampled inner-cell
-    indices.  Returns dict lam_mean, lam_std [ncell] fp32 and ndata [ncell] int32."""
-    nd = ndata(wdat_cells).astype(np.int32)
-    lam_mean, lam_std = np.zeros(ncell, np.float32), np.zeros(ncell, np.float32)
-    a0 = float(np.float32(ns["a0"]))
-    for cs, cell in enumerate(cells):
-        n, s0, s1 = 0, 0.0, 0.0
-        for ch in range(0, nchain, ntemp):
-            col = cs * nchain + ch
-            n += int(ns["ncnt"][col])
-            s0 += ns["nsum"][0, col]
-            s1 += ns["nsum"][1, col]
-        if n == 0:
-            lam_mean[cell] = lam_std[cell] = np.nan
-            continue
-        a = a0 + 0.5 * int(nd[cell])
-        lm = gamma_ratio(a) * s0 / float(n)
-        lam_mean[cell] = np.float32(lm)
-        lam_std[cell] = np.nan if a <= 1.0 else np.float32(math.sqrt(max(s1 / (float(n) * (a - 1.0)) - lm * lm, 0.0)))
-    return dict(lam_mean=lam_mean, lam_std=lam_std, ndata=nd)
+    """dazim_mc_noise_result from a single-scale noise record: the one-group row of mc_groups_ref.result.  Returns dict lam_mean,
+    lam_std [ncell] fp32 and ndata [ncell] int32."""
+    r = mc_groups_ref.result(as_groups(ns, None, wdat_cells.shape[0]), wdat_cells, cells, ncell, nchain, ntemp)
+    return {k: v[0] for k, v in r.items()}
 
 
-def sample(forward, nburn, nsample, nadapt, gcell, nchain, vmin, vmax, vlast, cobs, wdat, nbin, seed, a0, b0, step0=0.05, ntemp=1,
-           tmax=1.0, nswap=1, kind=0):
+def sample(forward, nburn, nsample, nadapt, gcell, nchain, vmin, vmax, vlast, cobs, wdat, nbin, seed, noise=None, prior=None, step0=0.05,
+           ntemp=1, tmax=1.0, nswap=1, kind=0, each=None):
     """the whole sampler from the restatement alone, no library: vmin, vmax [nlay][ncs], vlast [ncs], cobs, wdat [kmax][ncs] fp32 of
-    the sampled cells gcell; forward(prop [nz][ncol] fp32) -> curves [kmax][ncol] fp64.  a0 = 0: the fixed noise level (the energy
-    is chi2 itself, and no noise record).  Returns (state, ladder, noise record or None)."""
+    the sampled cells gcell; forward(prop [nz][ncol] fp32) -> curves [kmax][ncol] fp64.  noise: None (the fixed level), (a0, b0) (the
+    single-scale record) or (grp, a0, b0) (the groups' record); prior: None or (smooth, damp, vref [nlay][ncs]); each(t, r) sees every
+    step's returned dict.  Returns (state, ladder, noise record or None)."""
     nlay, ncs = vmin.shape
     ncol = ncs * nchain
     rep = lambda x: np.repeat(x, nchain, axis=-1)
@@ -422,7 +436,8 @@ def sample(forward, nburn, nsample, nadapt, gcell, nchain, vmin, vmax, vlast, co
                   swap_try=np.zeros((ncs, ntemp - 1), np.int64), swap_acc=np.zeros((ncs, ntemp - 1), np.int64))
     tp = ladder_state(st, tp)
     cov = empty_cov(ncs, nlay) if kind == 1 else None
-    ns = None if a0 == 0 else empty_noise(a0, b0, ncol)
+    ns = None if noise is None else (empty_noise if len(noise) == 2 else empty_groups)(*noise, ncol)
+    pr = None if prior is None else empty_prior(prior[0], prior[1], rep(prior[2]), prop)
     acc_win = np.zeros((ncs, ntemp), np.int64)
     nbd = 0
     for t in range(1, nburn + nsample + 1):
@@ -431,9 +446,10 @@ def sample(forward, nburn, nsample, nadapt, gcell, nchain, vmin, vmax, vlast, co
         if not record and t > 1:
             nbd += 1
             adapt = nbd % nadapt == 0
-        pv = forward(prop)
-        st, tp, cov, ns, _, acc_win, _, _ = step(st, tp, cov, ns, prop, pv, t, record, adapt, nadapt, acc_win, gcell, nchain, lo, hi, cb,
-                                                 wd, nbin, seed)
+        r = step(st, tp, cov, ns, pr, prop, forward(prop), t, record, adapt, nadapt, acc_win, gcell, nchain, lo, hi, cb, wd, nbin, seed)
+        st, tp, cov, ns, pr, acc_win = (r[k] for k in ("st", "tp", "cov", "ns", "pr", "acc_win"))
+        if each:
+            each(t, r)
         prop = proposals(st["cur"], tp["scale"], cov, prop, t, gcell, nchain, lo, hi, seed)
     return st, tp, ns
 

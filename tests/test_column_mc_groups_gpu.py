@@ -1,8 +1,9 @@
 """-m gpu: one noise scale per group of periods and typed data in the Monte-Carlo sampler (dazim_mc_set_noise_groups,
 dazim_mc_set_segments).
 
-The step with the energy X = sum_g 2 a_g log(b0_g + chi2_g / 2) against its NumPy restatement (tests/mc_groups_ref.py) at the shapes
-of tests/test_column_mc_noise_gpu.py with two interleaved and four contiguous groups; one group, all-zero a0 and a repeated seed as
+The step with the energy X = sum_g 2 a_g log(b0_g + chi2_g / 2) against its NumPy restatement (tests/mc_ref.py, driven by
+tests/mc_step_check.py) at the shapes of tests/test_column_mc_noise_gpu.py with two interleaved and four contiguous groups, and at two
+of them with the smoothness prior beside the groups; one group, all-zero a0 and a repeated seed as
 bytes; the linear problem of tests/test_mc_groups_ref_cpu.py through the library; dazim_mc_run's typed forward call against a hand
 loop; four wave types against Rayleigh phase alone on exact curves; noisier Love data; and the refused calls."""
 import numpy as np
@@ -11,7 +12,7 @@ import pytest
 import dazimsurftomo_amd as dz
 from tests import mc_groups_ref as gr
 from tests import mc_ref
-from tests.mc_step_check import STATE, check_final, ulps
+from tests.mc_step_check import check_final, drive, ulps
 from tests.test_column_mc_gpu import create, disp_setup, per_column
 from tests.test_column_mc_noise_gpu import NADAPT, NREC, SHAPES, everything
 from tests.test_column_mc_temper_gpu import host_forward, step_problem
@@ -32,64 +33,6 @@ def ctx():
 
 # the group of step_problem's period 3, the one weighted period of its cell 0, has a0 = 0.25: a = 0.75 there, lam_std NaN
 GROUPS = {2: (np.arange(8) % 2, [0.5, 0.25], [0.5, 1.0]), 4: (np.arange(8) // 2, [0.5, 0.25, 0.75, 1.0], [0.5, 1.0, 0.75, 2.0])}
-
-
-def snapshot(mc):
-    """(state, ladder, cov or None for kind 0, groups' state) as mc_groups_ref.step takes them"""
-    st, cov = mc.state(), mc.cov_state()
-    return st, mc_ref.ladder_state(st, mc.temper_state()), cov if cov["kind"] == 1 else None, mc.noise_groups_state()
-
-
-def drive_groups(mc, forward, nburn, nrec, nadapt, lo, hi, cb, wd, nbin, seed, moved):
-    """tests/mc_step_check.drive with the groups' state in place of the noise record: every step restated from the library's own
-    state; state, ladder, covariance sums, chi2g, nsum and ncnt bit for bit, the factor to 1e-9, the next proposals within one fp32
-    ulp and inside the box; without swaps the decisions themselves"""
-    nlay, nchain = mc.nlay, mc.nchain
-    acc_win = np.zeros((mc.ncs, mc.temper_state()["ntemp"]), np.int64)
-    out = dict(seen=dict.fromkeys(mc_ref.BRANCHES, 0), ndec=0, ninf_group=0)
-    nbd = 0
-    for t in range(1, nburn + nrec + 1):
-        st, tp, cov, gs = snapshot(mc)
-        assert st["step"] == t - 1
-        prop = mc.proposals().cpu().numpy()
-        record = t > nburn
-        adapt = False
-        if not record and t > 1:
-            nbd += 1
-            adapt = nbd % nadapt == 0
-        pv = forward(t)
-        exp, etp, ecov, egs, acc, acc_win, factored, br = gr.step(st, tp, cov, gs, prop, pv, t, record, adapt, nadapt, acc_win, mc._cells,
-                                                                  nchain, lo, hi, cb, wd, nbin, seed)
-        for k in br:
-            out["seen"][k] += br[k]
-        mc.step(pv, int(record))
-        got, gtp, gcov, ggs = snapshot(mc)
-        gprop = mc.proposals().cpu().numpy()
-        if moved:
-            mv = (got["cur"][:nlay] == prop[:nlay]).all(axis=0) & ((got["cur"][:nlay] != st["cur"][:nlay]).any(axis=0) | (t == 1))
-            assert np.array_equal(mv, acc), t
-        for k in STATE:
-            assert np.array_equal(got[k], exp[k]), (t, k)
-        for k in ("scale", "swap_try", "swap_acc"):
-            assert np.array_equal(gtp[k], etp[k]), (t, k)
-        for k in ("chi2g", "nsum", "ncnt"):
-            assert np.array_equal(ggs[k], egs[k]), (t, k)
-        # a state's chi2_g are +inf where its total is, and only there
-        assert np.array_equal(np.isinf(ggs["chi2g"]).any(axis=0), np.isinf(got["chi2"])), t
-        out["ninf_group"] += int((np.isinf(ggs["chi2g"]).sum(axis=0) == 1).sum())
-        if cov is not None:
-            for k in ("cov_n", "cov_s1", "cov_s2", "cov_set"):
-                assert np.array_equal(gcov[k], ecov[k]), (t, k)
-            for Cm in factored.values():
-                assert np.linalg.cond(Cm) <= 1e6, t
-            assert np.abs(gcov["chol"] - ecov["chol"]).max() <= 1e-9 * np.abs(ecov["chol"]).max(), t
-        nxt = mc_ref.proposals(got["cur"], gtp["scale"], gcov, prop, t, mc._cells, nchain, lo, hi, seed)
-        assert ulps(gprop, nxt).max() <= 1, (t, ulps(gprop, nxt).max())
-        assert (gprop[:nlay] >= lo).all() and (gprop[:nlay] <= hi).all()
-        if t > 1:
-            out["ndec"] += int(acc.sum())
-    out.update(got=got, gtp=gtp, gcov=gcov, ggs=ggs)
-    return out
 
 
 @pytest.mark.parametrize("G", [2, 4])
@@ -120,8 +63,8 @@ def test_groups_step_against_numpy(ctx, shape, G):
     assert mc.noise_state() == dict(a0=0.0, b0=0.0)                  # the single scale is not what is on
     lo, hi = per_column(vmin.astype(np.float64), mc), per_column(vmax.astype(np.float64), mc)
     cb, wd = per_column(cobs, mc), per_column(wdat, mc)
-    run = drive_groups(mc, lambda t: host_forward(rng, cb, t, nswap), nburn, NREC, NADAPT, lo, hi, cb, wd, nbin, seed, ntemp == 1)
-    got, gtp, gcov, ggs, seen = run["got"], run["gtp"], run["gcov"], run["ggs"], run["seen"]
+    run = drive(mc, lambda t: host_forward(rng, cb, t, nswap), nburn, NREC, NADAPT, lo, hi, cb, wd, nbin, seed, moved=ntemp == 1)
+    got, gtp, gcov, ggs, seen = run["got"], run["gtp"], run["gcov"], run["gns"], run["seen"]
     hot = (np.arange(mc.ncol) % nchain) % ntemp != 0
     assert not ggs["nsum"][:, :, hot].any() and not ggs["ncnt"][hot].any()
     assert 0 < ggs["ncnt"].sum() <= NREC * ncs * (nchain // ntemp) and ggs["ncnt"].max() == NREC
@@ -149,6 +92,40 @@ def test_groups_step_against_numpy(ctx, shape, G):
     check_final(mc, got, vmin, vmax, vel0, ntemp, NREC, nbin, roots=False)
     print(f"\n[measured] {shape}, {G} groups: swap cases {seen}; recorded noise states {ggs['ncnt'].sum()}; states with one group at "
           f"+inf {run['ninf_group']}; lam_mean {np.nanmin(lm[nd > 0]):.3f}..{np.nanmax(lm):.3f}")
+    mc.free()
+
+
+@pytest.mark.parametrize("shape,G", [("untempered", 4), ("odd1", 2)])
+def test_groups_with_prior_step_against_numpy(ctx, shape, G):
+    """k_mc_step with several groups and the prior together, step by step: everything tests/mc_step_check.drive compares (state,
+    ladder, covariance sums, chi2g, nsum, ncnt and q bit for bit, q against Q of the new states, the factor, the proposals) with
+    GROUPS' priors and smooth 3, damp 4 about a random reference inside the boxes, as in test_prior_step_against_numpy; some
+    decisions come out otherwise than the energies alone would have made them, some states have exactly one group at +inf, and the
+    ladder meets every case of the swap rule (tests/test_mc_groups_ref_cpu.py reaches these counts with the restatement alone)"""
+    (nz, nchain, ntemp, nswap, kind), nburn = SHAPES[shape]
+    rng, nx, ny, kmax, vel0, vmin, vmax, cobs, wdat = step_problem(nz)
+    grp, a0, b0 = GROUPS[G]
+    nbin, seed, tmax = 20, 0x1234_5678_9ABC, 16.0
+    vref = (vmin + np.random.default_rng(nz).uniform(0.1, 0.9, vmin.shape) * (vmax - vmin)).astype(np.float32)
+    mc = create(ctx, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, 0.05, NADAPT)
+    mc.set_noise_groups(grp, a0, b0)
+    if kind == 1:
+        mc.set_proposal(1)
+    if ntemp > 1:
+        mc.set_tempering(ntemp, tmax, nswap)
+    mc.set_prior(3.0, 4.0, vref)
+    lo, hi = per_column(vmin.astype(np.float64), mc), per_column(vmax.astype(np.float64), mc)
+    cb, wd, vr = per_column(cobs, mc), per_column(wdat, mc), per_column(vref, mc)
+    run = drive(mc, lambda t: host_forward(rng, cb, t, nswap), nburn, NREC, NADAPT, lo, hi, cb, wd, nbin, seed, moved=ntemp == 1, vref=vr)
+    print(f"\n[measured] {shape}, {G} groups and the prior: decisions {run['ndec']} accepted, {run['ndiff_dec']} other than the energies "
+          f"alone, {run['ndiff_swap']} swap rules; states with one group at +inf {run['ninf_group']}; swap cases {run['seen']}")
+    assert run["gns"]["ngroup"] == G and run["gpr"] is not None and run["gns"]["ncnt"].sum() > 0
+    assert run["ndec"] > 0 and run["ndiff_dec"] > 0
+    assert run["ninf_group"] > 0
+    if ntemp > 1:
+        assert all(run["seen"][k] > 0 for k in mc_ref.BRANCHES), run["seen"]
+    if kind == 1:
+        assert (run["gcov"]["cov_set"] == 1).all()
     mc.free()
 
 

@@ -1,6 +1,6 @@
 """-m gpu: the Gaussian smoothness prior of the Monte-Carlo sampler (dazim_mc_set_prior).
 
-The step with E + Q against its NumPy restatement (tests/mc_prior_ref.py, driven by tests/mc_prior_check.py) in all eight mode
+The step with E + Q against its NumPy restatement (tests/mc_ref.py with tests/mc_prior_ref.py's Q, driven by tests/mc_step_check.py) in all eight mode
 triples; a linear-Gaussian problem that the data alone do not determine, on which the chains, dazim_column_lsq and
 dazim_column_resolution stand against one analytic posterior; the unchanged default; the dispersion forward model with and without
 the prior; and the refused calls."""
@@ -10,8 +10,7 @@ import pytest
 import dazimsurftomo_amd as dz
 from tests import mc_prior_ref
 from tests.bars import within
-from tests.mc_prior_check import drive
-from tests.mc_step_check import check_final
+from tests.mc_step_check import check_final, drive
 from tests.test_column_mc_gpu import create, disp_setup, per_column
 from tests.test_column_mc_noise_gpu import everything
 from tests.test_column_mc_temper_gpu import host_forward, step_problem
@@ -72,7 +71,7 @@ def test_prior_step_against_numpy(ctx, shape):
     cb, wd, vr = per_column(cobs, mc), per_column(wdat, mc), per_column(vref, mc)
     # before the first step the states are the start models
     assert np.array_equal(ps["q"], mc_prior_ref.prior_q(mc.state()["cur"][:nlay], vr, SMOOTH, DAMP))
-    run = drive(mc, lambda t: host_forward(rng, cb, t, nswap), NBURN, NREC, NADAPT, lo, hi, cb, wd, vr, nbin, seed)
+    run = drive(mc, lambda t: host_forward(rng, cb, t, nswap), NBURN, NREC, NADAPT, lo, hi, cb, wd, nbin, seed, vref=vr)
     got, gtp, gcov, gpr, seen = run["got"], run["gtp"], run["gcov"], run["gpr"], run["seen"]
     q = gpr["q"]
     print(f"\n[measured] {shape}: decisions {run['ndec']} accepted, {run['ndiff_dec']} other than chi2 alone; swaps "

@@ -1,5 +1,5 @@
-"""CPU: the restatement of the sampler with one noise scale per group of periods (tests/mc_groups_ref.py) alone: with one group it
-is tests/mc_ref.py byte for byte, and on a linear problem with two groups of unequal noise it meets the bars of
+"""CPU: the restatement of the sampler with one noise scale per group of periods (tests/mc_ref.py with tests/mc_groups_ref.py) alone:
+the single-scale record and a one-group record drive it to the same bytes, and on a linear problem with two groups of unequal noise it meets the bars of
 tests/test_mc_noise_ref_cpu.check_linear, per group, against quadrature over the box: the bars are reachable by the arithmetic before
 the device is involved (tests/test_column_mc_groups_gpu.py runs the same problem through the library)."""
 import numpy as np
@@ -51,16 +51,18 @@ def forward_with_gaps(rng, kmax):
 
 
 def test_one_group_is_mc_ref_sample_and_result():
-    """sample() with one group against mc_ref.sample(), tempered and kind 1, with periods without data and without a root: state,
-    ladder, record and result byte for byte"""
+    """sample() driven with the single-scale record against sample() driven with a one-group record, tempered and kind 1, with
+    periods without data and without a root: state, ladder, record and result byte for byte"""
     for ntemp, kind in ((1, 0), (3, 1)):
         ncs, nchain, nlay, kmax = 3, 6, 3, 5
         ncol, rep, vmin, vmax, cobs, wdat = small_problem(np.random.default_rng(3), ncs, nchain, nlay, kmax)
         cells = np.array([0, 2, 5])
         args = (30, 8, 4, cells, nchain, vmin, vmax, np.full(ncs, 4.0, np.float32), cobs, wdat, 12, 99)
         kw = dict(ntemp=ntemp, tmax=8.0, nswap=2, kind=kind)
-        st, tp, ns = mc_ref.sample(forward_with_gaps(np.random.default_rng(4), kmax), *args, 0.25, 0.5, **kw)
-        gst, gtp, gs = gr.sample(forward_with_gaps(np.random.default_rng(4), kmax), *args, np.zeros(kmax, np.int32), [0.25], [0.5], **kw)
+        st, tp, ns = mc_ref.sample(forward_with_gaps(np.random.default_rng(4), kmax), *args, (0.25, 0.5), **kw)
+        gst, gtp, gs = mc_ref.sample(forward_with_gaps(np.random.default_rng(4), kmax), *args, (np.zeros(kmax, np.int32), [0.25], [0.5]),
+                                     **kw)
+        assert "ngroup" not in ns and gs["ngroup"] == 1                  # each record came back in the form it went in
         for k in st:
             assert np.asarray(st[k]).tobytes() == np.asarray(gst[k]).tobytes(), k
         for k in ("scale", "swap_try", "swap_acc"):
@@ -107,8 +109,8 @@ def test_linear_two_groups_restated():
     ncell, kmax, nlay, K = pb["ncell"], pb["kmax"], pb["nlay"], pb["K"]
     cells = np.arange(ncell)
     wdat = np.full((kmax, ncell), pb["w"], np.float32)
-    st, tp, gs = gr.sample(lambda prop: K @ prop[:nlay].astype(np.float64), NBURN, NSAMPLE, 50, cells, NCHAIN, pb["vmin"].T, pb["vmax"].T,
-                           np.full(ncell, 3.5, np.float32), pb["cobs"].T, wdat, NBIN, SEED, pb["grp"], pb["a0"], pb["b0"])
+    st, tp, gs = mc_ref.sample(lambda prop: K @ prop[:nlay].astype(np.float64), NBURN, NSAMPLE, 50, cells, NCHAIN, pb["vmin"].T,
+                               pb["vmax"].T, np.full(ncell, 3.5, np.float32), pb["cobs"].T, wdat, NBIN, SEED, (pb["grp"], pb["a0"], pb["b0"]))
     r = mc_ref.final(st, pb["vmin"].T.copy(), pb["vmax"].T.copy(), np.full((nlay, ncell), 3.5, np.float32), cells, ncell, NCHAIN, 1,
                      NSAMPLE, NSAMPLE, NBIN)
     nr = gr.result(gs, wdat, cells, ncell, NCHAIN, 1)
@@ -117,3 +119,39 @@ def test_linear_two_groups_restated():
           f"{ref['lam_mean'][1].min():.2f}..{ref['lam_mean'][1].max():.2f}")
     assert np.median(ref["lam_mean"][1]) > 2 * np.median(ref["lam_mean"][0])      # the problem does separate the two levels
     check_linear_groups(pb, ref, sd_fixed, r["mean"].T, r["std"].T, r["rhat"], nr["lam_mean"], nr["lam_std"], "restatement")
+
+
+def test_groups_with_prior_counts_restated():
+    """the shapes of tests/test_column_mc_groups_gpu.test_groups_with_prior_step_against_numpy on host_forward's curves, by the
+    restatement alone: decisions other than the energies alone would take, states with exactly one group at +inf and, with the
+    ladder, every case of the swap rule do occur, so the GPU test may ask for them"""
+    from tests.test_column_mc_groups_gpu import GROUPS
+    from tests.test_column_mc_noise_gpu import NADAPT, NREC, SHAPES
+    from tests.test_column_mc_temper_gpu import host_forward, step_problem
+    for shape, G in (("untempered", 4), ("odd1", 2)):
+        (nz, nchain, ntemp, nswap, kind), nburn = SHAPES[shape]
+        rng, nx, ny, kmax, vel0, vmin, vmax, cobs, wdat = step_problem(nz)
+        nlay = nz - 1
+        cells = np.nonzero((wdat.reshape(kmax, -1) != 0).any(axis=0))[0]
+        pick = lambda x: x.reshape(x.shape[0], -1)[:, cells]
+        vref = (vmin + np.random.default_rng(nz).uniform(0.1, 0.9, vmin.shape) * (vmax - vmin)).astype(np.float32)
+        cb = np.repeat(pick(cobs), nchain, axis=-1)
+        n = dict(dec=0, swap=0, ninf_group=0, seen=dict.fromkeys(mc_ref.BRANCHES, 0), t=0)
+
+        def each(t, r):
+            n["dec"] += r["diff"]["dec"]
+            n["swap"] += r["diff"]["swap"]
+            n["ninf_group"] += int((np.isinf(r["ns"]["chi2g"]).sum(axis=0) == 1).sum())
+            for k in r["seen"]:
+                n["seen"][k] += r["seen"][k]
+
+        def forward(prop):
+            n["t"] += 1
+            return host_forward(rng, cb, n["t"], nswap)
+        mc_ref.sample(forward, nburn, NREC, NADAPT, cells, nchain, pick(vmin), pick(vmax), pick(vel0[nlay:, 1:-1, 1:-1])[0], pick(cobs),
+                      pick(wdat), 20, 0x1234_5678_9ABC, GROUPS[G], (3.0, 4.0, pick(vref)), ntemp=ntemp, tmax=16.0, nswap=nswap, kind=kind,
+                      each=each)
+        print(f"\n[measured] {shape}, {G} groups and the prior, restated: {n}")
+        assert n["dec"] > 0 and n["ninf_group"] > 0
+        if ntemp > 1:
+            assert all(v > 0 for v in n["seen"].values()), n["seen"]

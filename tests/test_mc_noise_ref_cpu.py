@@ -33,7 +33,7 @@ def test_linear_student_t_posterior_restated():
     cells = np.arange(ncell)
     wdat = np.full((kmax, ncell), pb["w"], np.float32)
     st, tp, ns = mc_ref.sample(lambda prop: K @ prop[:nlay].astype(np.float64), NBURN, NSAMPLE, 50, cells, NCHAIN, pb["vmin"].T,
-                                     pb["vmax"].T, np.full(ncell, 3.5, np.float32), pb["cobs"].T, wdat, NBIN, SEED, pb["a0"], pb["b0"])
+                                     pb["vmax"].T, np.full(ncell, 3.5, np.float32), pb["cobs"].T, wdat, NBIN, SEED, (pb["a0"], pb["b0"]))
     r = mc_ref.final(st, pb["vmin"].T.copy(), pb["vmax"].T.copy(), np.full((nlay, ncell), 3.5, np.float32), cells, ncell, NCHAIN, 1,
                         NSAMPLE, NSAMPLE, NBIN)
     nr = mc_ref.result(ns, wdat, cells, ncell, NCHAIN, 1)

@@ -8,6 +8,7 @@
     python tools/mc_step.py --prior S D [--steps S] [--proposal K] [--ntemp R [--tmax T]] [--noise A0 B0]
     python tools/mc_step.py --program --prior S D [--dir D] [--proposal K] [--ntemp R [--tmax T]] [--noise A0 B0]
     python tools/mc_step.py --typed [--steps S] [--big N] [--runs R]
+    python tools/mc_step.py --shapes [--noise A0 B0 | --groups] [--prior S D] [--steps S] [--big N] [--runs R]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -45,7 +46,12 @@ profiles/depth_mc_prior.md).  With --program: the default run with arguments 15 
 velocities together at those 8 periods each (32 virtual periods; four times 16 would pass the sampler's 60); R runs (default 3) of S
 steps per case, each on a fresh handle after its warm-up run; reports the ms per step of "mc", "mc.disp" and "mc.step" of every run.
 At S-256 two more cases on the four types: the one noise scale (dazim_mc_set_noise) and one per type (dazim_mc_set_noise_groups),
-whose "mc.step" are the two step kernels side by side (profiles/mc_typed.md)."""
+whose "mc.step" are the two step kernels side by side (profiles/mc_typed.md).
+
+--shapes: one mode of the step kernel at S-256 with 32 chains and on the big grid with 8, R runs (default 3) of S steps each on a
+fresh handle after its warm-up run, for comparing two builds (DAZIM_LIB; profiles/mc_noise_once.md): the fixed noise level, --noise
+A0 B0, or --groups, one noise scale per type on the four types of --typed (dazim_mc_set_noise_groups); each with --prior S D as well.
+Reports the ms per step of "mc", "mc.disp" and "mc.step" of every run."""
 import argparse
 import json
 import os
@@ -91,7 +97,7 @@ def one_case(ctx, n, nchain, steps, proposal, ntemp, tmax, noise=None, prior=Non
             "median_std_km_s": float(np.median(r["std"])), "median_rhat": float(np.nanmedian(r["rhat"]))}
 
 
-def typed_case(ctx, n, nchain, steps, name, runs):
+def typed_case(ctx, n, nchain, steps, name, runs, prior=None):
     import bench
     bench.NX = bench.NY = n
     vel = bench.s256_model().astype(np.float32)
@@ -117,6 +123,8 @@ def typed_case(ctx, n, nchain, steps, name, runs):
             mc.set_noise(2.0, 1.0)
         elif name == "four_groups":
             mc.set_noise_groups(np.repeat(np.arange(4), K // 4), [2.0] * 4, [1.0] * 4)
+        if prior:
+            mc.set_prior(*prior)
         mc.run(depz, bench.MINTHK, virt, 5, 0)                    # warm-up: code objects, scratch buffers
         out["no_root"] = mc.run(depz, bench.MINTHK, virt, steps // 2, steps - steps // 2)
         for key, stat in (("ms_per_step", "mc"), ("disp_ms_per_step", "mc.disp"), ("mc_step_ms_per_step", "mc.step")):
@@ -127,6 +135,21 @@ def typed_case(ctx, n, nchain, steps, name, runs):
     for key in ("ms_per_step", "disp_ms_per_step", "mc_step_ms_per_step"):
         out[key + "_median"] = float(np.median(out[key]))
     return out
+
+
+def shape_cases(ctx, a):
+    """--shapes: the mode given by --noise / --groups / --prior at the two shapes of profiles/mc_typed.md"""
+    for n, nchain in ((54, 32), (a.big, 8)):
+        if a.groups:
+            out = typed_case(ctx, n, nchain, a.steps, "four_groups", a.runs, a.prior)
+        else:
+            runs = [one_case(ctx, n, nchain, a.steps, a.proposal, a.ntemp, a.tmax, tuple(a.noise) if a.noise else None,
+                             tuple(a.prior) if a.prior else None) for _ in range(a.runs)]
+            out = {k: runs[-1][k] for k in ("grid", "nchain", "noise", "proposal", "ntemp", "steps", "curves_per_step")}
+            for key in ("ms_per_step", "disp_ms_per_step", "mc_step_ms_per_step"):
+                out[key] = [r[key] for r in runs]
+        out["prior"] = list(a.prior) if a.prior else None
+        print(json.dumps(out), flush=True)
 
 
 def noise_cases(ctx, steps, proposal, ntemp, tmax, noise, pairs=5, prior=None):
@@ -264,8 +287,14 @@ def main():
     ap.add_argument("--prior", type=float, nargs=2, default=None, metavar=("S", "D"))
     ap.add_argument("--typed", action="store_true")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--shapes", action="store_true")
+    ap.add_argument("--groups", action="store_true")
     a = ap.parse_args()
     ctx = dz.Context(0)
+    if a.shapes:
+        shape_cases(ctx, a)
+        ctx.close()
+        return
     if a.typed:
         for n, nchain, names in ((54, 32, ("rc16", "rc8", "four", "four_noise", "four_groups")), (a.big, 8, ("rc16", "rc8", "four"))):
             for name in names:
