@@ -13,12 +13,18 @@
 // and the Earth-flattening factors, which depend on the
 // layer thicknesses only, come from a host table (same libm log/powf the CPU reference calls).
 // fp64 VALU + transcendental bound; no MFMA, negligible HBM traffic.
+// This unit's own: the tuned dltar4, the lockstep search, layer_model with its division-free forms.  What it runs of the subroutine
+// beside them -- brocher, gtsolh and the start-up scan on the device, the flattening, the density factor and the knots' layer ranges
+// on the host -- are surfdisp_device.h's functions, the ones surfdisp.hip and disp_typed.hip call.
 #include <algorithm>
 #include <cmath>
 
 #include "dazim_internal.h"
+#include "surfdisp_device.h"
 
 namespace {
+
+using dz_sd::brocher;
 
 constexpr int NL = 200;       // inv/surfdisp96.f:57
 constexpr int NP = 60;        // inv/surfdisp96.f:59
@@ -348,59 +354,12 @@ __device__ double dltar4(const LS &S, int mmax, double wvno, double omga, bool e
   return e0;
 }
 
-// inv/surfdisp96.f:361-382, all fp32
-__device__ float gtsolh(float a, float b) {
-  float c = 0.95f * b;
-  for (int i = 0; i < 5; i++) {
-    const float gamma = b / a;
-    const float kappa = c / b;
-    const float k2 = kappa * kappa;
-    const float gk2 = (gamma * kappa) * (gamma * kappa);
-    const float fac1 = sqrtf(1.0f - gk2);
-    const float fac2 = sqrtf(1.0f - k2);
-    const float fr = (2.0f - k2) * (2.0f - k2) - 4.0f * fac1 * fac2;
-    float frp = -4.0f * (2.0f - k2) * kappa + 4.0f * fac2 * gamma * gamma * kappa / fac1 + 4.0f * fac1 * kappa / fac2;
-    frp = frp / b;
-    c = c - fr / frp;
-  }
-  return c;
-}
-
-__device__ __forceinline__ void brocher(float vs, float &vp, float &rho) {  // inv/CalSurfG.f90:49-53
-  const float v2 = vs * vs, v3 = v2 * vs, v4 = v3 * vs;
-  const float p = 0.9409f + 2.0947f * vs - 0.8206f * v2 + 0.2683f * v3 - 0.0251f * v4;
-  const float p2 = p * p, p3 = p2 * p, p4 = p3 * p, p5 = p4 * p;
-  vp = p;
-  rho = 1.6612f * p - 0.4721f * p2 + 0.0671f * p3 - 0.0043f * p4 + 0.000106f * p5;
-}
-
 enum { P_G1, P_G2, P_N0, P_NA, P_NB, P_GV, P_GW, P_DONE };
 
-// start-up of surfdisp96 (:134-216): extremal velocities of the layer stack and the start value of the first period's search
+// start-up of surfdisp96 (:134-216) on a layer source LS: extremal velocities of the stack and the start value of the first period's search
 template <class LS>
 __device__ __forceinline__ void startup(const LS &S, int mmax, float &betmx, float &cc1) {
-  float betmn = 1.e20f, a_mn = 1.0f, b_mn = 1.0f;
-  betmx = -1.e20f;
-  int jsol = 1;
-  for (int m = 1; m <= mmax; m++) {
-    float fa, fb, fr, fd;
-    S.get(m, fa, fb, fr, fd);
-    if (fb > 0.01f && fb < betmn) {
-      betmn = fb;
-      a_mn = fa;
-      b_mn = fb;
-      jsol = 1;
-    } else if (fb <= 0.01f && fa < betmn) {
-      betmn = fa;
-      a_mn = fa;
-      b_mn = fb;
-      jsol = 0;
-    }
-    if (fb > betmx) betmx = fb;
-  }
-  cc1 = jsol == 0 ? betmn : gtsolh(a_mn, b_mn);
-  cc1 = .95f * cc1;
-  cc1 = .90f * cc1;
+  dz_sd::startup(mmax, [&](int m, float &fa, float &fb) { float fr, fd; S.get(m, fa, fb, fr, fd); }, betmx, cc1);
 }
 
 // The bracket search of the FIRST period starts far below the root (0.855 x the Rayleigh velocity of the slowest layer) and walks
@@ -1082,41 +1041,21 @@ struct DispCall {
   int layers() {
     kernels = svs_u && svp_u && srho_u;
     ncol = nx * ny, nvar = kernels ? 1 + 6 * nz : 1, nk = (size_t)nz * kmax * ncol;
+    std::vector<float> thk;
     for (const DzRefinedLayer &R : dz_refine_layers(depz, nz, minthk0)) {
       Layer L;
-      L.d = R.thk, L.iv = R.iv, L.fm = R.fm, L.den = R.den, L.rden = 1.0f / R.den;
+      L.iv = R.iv, L.fm = R.fm, L.den = R.den, L.rden = 1.0f / R.den;
       lay.push_back(L);
+      thk.push_back(R.thk);
     }
     form = disp_pick_form(lay, ctx), mmax = (int)lay.size();
     if (mmax > NL) return dz_fail(ctx, DAZIM_E_BAD_ARG, "refined model has %d layers > NL=%d", mmax, NL);
-    const double ar = 6370.0;
-    double dr = 0.0, r0 = ar;
-    lay[mmax - 1].d = 1.0f;
-    for (int i = 0; i < mmax; i++) {
-      dr = dr + (double)lay[i].d;
-      const double r1 = ar - dr;
-      const double z0 = ar * log(ar / r0), z1 = ar * log(ar / r1);
-      lay[i].d = (float)(z1 - z0);
-      const double tmp = (ar + ar) / (r0 + r1);
-      lay[i].tmp = tmp;
-      lay[i].rfac = powf((float)tmp, -2.275f);
-      r0 = r1;
-    }
-    lay[mmax - 1].d = 0.0f;
-    // shared layer stacks (TableLayers): the contiguous range of layers that knot pi touches -- the sublayers of intervals pi - 1 and
-    // pi, for the last knot those of the last interval and the half-space -- and the longest such range
+    std::vector<double> tmp(mmax);
+    dz_sd::sphere_flatten(mmax, 6370.0, thk.data(), tmp.data());
+    for (int i = 0; i < mmax; i++) lay[i].d = thk[i], lay[i].tmp = tmp[i], lay[i].rfac = dz_sd::rho_factor_rayleigh(tmp[i]);
+    // shared layer stacks (TableLayers): the layers each knot touches; a lane's patch table has a row at least
     krange.assign(2 * (nz + 1), 0);
-    A.npatch = 1;
-    for (int pi = 1; pi <= nz; pi++) {
-      int lo = 0, hi = 0;
-      for (int m = 1; m <= mmax; m++)
-        if ((pi > 1 && lay[m - 1].iv == pi - 1) || lay[m - 1].iv == pi || (pi == nz && lay[m - 1].iv == 0)) {
-          if (!lo) lo = m;
-          hi = m;
-        }
-      krange[2 * pi] = lo, krange[2 * pi + 1] = lo ? hi - lo + 1 : 0;
-      if (krange[2 * pi + 1] > A.npatch) A.npatch = krange[2 * pi + 1];
-    }
+    A.npatch = std::max(1, dz_sd::knot_layer_ranges(lay, nz, krange.data()));
     return 0;
   }
   int buffers() {

@@ -8,12 +8,13 @@
 //   others  typed_kernel below.  Work item = (segment, column, variant), one lane each; a workgroup is one wavefront that holds
 //           up to 64 consecutive variants of one or a few columns of ONE segment, so the layer loop of the secular function has the
 //           same trip count on every lane.  The root search is the subroutine's own, in the subroutine's order, by the functions
-//           dazim_surfdisp96 runs (surfdisp_device.h: dltar1, dltar4, getsol, nevill; plain IEEE fp64, no fused or reciprocal
-//           forms), with the subroutine's period loop for mode 1 restated here (typed_curve).  What differs from
+//           dazim_surfdisp96 runs (surfdisp_device.h: dltar1, dltar4, getsol, nevill and period_step, one period of the period
+//           loop; plain IEEE fp64, no fused or reciprocal forms); typed_curve is that loop for mode 1.  What differs from
 //           dazim_surfdisp96 is where the layers come from: not per-model global arrays filled by a host prologue, but two LDS
 //           tables built by the wavefront from the column's knots -- a base table per column and, per lane, the few layers its one
 //           perturbed knot touches (the layout of disp.hip's TableLayers) -- with the thickness-only Earth-flattening factors of
-//           both wave types from a host table.  The layers are the ones the host prologue would have formed, bit for bit
+//           both wave types from a host table, filled by the functions that prologue calls (surfdisp_device.h: sphere_flatten,
+//           rho_factor_*; also brocher, startup and the knots' layer ranges).  The layers are the ones the host prologue would have formed, bit for bit
 //           (tests/test_disp_typed_gpu.py compares the tables with dazim_surfdisp96 on host-built stacks: equal).  The plans with
 //           fewer than 64 items per workgroup are run by tests/test_disp_typed_shapes_gpu.py; a curves-only call (one base table per
 //           item) takes them from 14 knots on at sublayers = 3 (32 items; 16 from 26 knots, 8 from 47).
@@ -59,14 +60,6 @@ struct TypedArgs {
   long long cgoff[MAXSEG];
 };
 
-__device__ __forceinline__ void brocher(float vs, float &vp, float &rho) {  // inv/CalSurfG.f90:49-53
-  const float v2 = vs * vs, v3 = v2 * vs, v4 = v3 * vs;
-  const float p = 0.9409f + 2.0947f * vs - 0.8206f * v2 + 0.2683f * v3 - 0.0251f * v4;
-  const float p2 = p * p, p3 = p2 * p, p4 = p3 * p, p5 = p4 * p;
-  vp = p;
-  rho = 1.6612f * p - 0.4721f * p2 + 0.0671f * p3 - 0.0043f * p4 + 0.000106f * p5;
-}
-
 // flattened layer m: Vp a, Vs b, density rho as surfdisp96 holds them after refineGrid2LayerMdl + sphere(0,0) + sphere(ifunc,1), from
 // the column's knots kn [3][nz] (vs, vp, rho) with knot pi's quantity pq replaced by pval (pi = 0: none)
 __device__ __forceinline__ void layer_model(const float *kn, int nz, int pi, int pq, float pval, const TLayer &L, bool love, float &a,
@@ -111,53 +104,16 @@ struct ColModel {
 // the loop over the periods of surfdisp96 for mode 1 (inv/surfdisp96.f:212-349 as surfdisp.hip's surfdisp_kernel states it, with
 // iq = 1 only: the previous mode's roots are 0, the previous period's root is carried in a register); cg [kmax] fp32 = sngl(c) or U
 __device__ void typed_curve(const ColModel &M, int ifunc, int igr, int kmax, const double *t, float betmx, float cc1, float *cg) {
-  const float ddc = 0.005f, h = 0.005f, sone = 1.500f;
-  const double one = 1.0e-2, onea = (double)sone;
   const double cc = (double)cc1;
   const double dc = fabs((double)ddc);
   const double cm = cc;
-  double c1 = cc, clow = cc, del1st = 0.0, cprev = 0.0;
+  double del1st = 0.0, cprev = 0.0, cb;
   int k;
   for (k = 1; k <= kmax; k++) {
-    double t1 = t[k - 1];
-    float t1a, t1b = 0.0f;
-    if (igr > 0) {
-      t1a = (float)(t1 / (double)(1.f + h));
-      t1b = (float)(t1 / (double)(1.f - h));
-      t1 = (double)t1a;
-    } else {
-      t1a = (float)t1;
-    }
-    int ifirst;
-    if (k == 1) {
-      c1 = cc;
-      clow = cc;
-      ifirst = 1;
-    } else {
-      ifirst = 0;
-      c1 = cprev - onea * dc;
-      clow = cm;
-    }
-    int iret = getsol(M, t1, c1, clow, dc, cm, betmx, ifunc, ifirst, del1st);
-    if (iret == -1) break;
-    const double ck = c1;
-    cprev = ck;
-    if (igr > 0) {
-      t1 = (double)t1b;
-      clow = 0.0 + one * dc;
-      c1 = c1 - onea * dc;
-      iret = getsol(M, t1, c1, clow, dc, cm, betmx, ifunc, 0, del1st);
-      if (iret == -1) c1 = ck;
-    } else {
-      c1 = 0.0;
-    }
-    const float cc0 = (float)ck;
-    const float ccb = (float)c1;
-    if (igr == 0) {
-      cg[k - 1] = cc0;
-    } else {
-      cg[k - 1] = (1 / t1a - 1 / t1b) / (1 / (t1a * cc0) - 1 / (t1b * ccb));
-    }
+    const bool first = k == 1;
+    if (!period_step(M, t[k - 1], igr, ifunc, first ? 1 : 0, first ? cc : cprev - onea * dc, first ? cc : cm, 0.0 + one * dc, dc, cm, betmx,
+                     del1st, cprev, cb, cg[k - 1]))
+      break;
   }
   for (int i = k; i <= kmax; i++) cg[i - 1] = 0.0f;  // :1700-1770: no root at period k ends the curve
 }
@@ -239,27 +195,8 @@ __global__ __launch_bounds__(TW) void typed_kernel(TypedArgs A) {
   }
   __syncthreads();
   if (!active) return;
-  // start-up of surfdisp96 (:134-216): extremal velocities of the stack, start value of the first search
-  float betmx = -1.e20f, betmn = 1.e20f, a_mn = 1.0f, b_mn = 1.0f;
-  int jsol = 1;
-  for (int m = 1; m <= mmax; m++) {
-    const float fa = M.A(m), fb = M.B(m);
-    if (fb > 0.01f && fb < betmn) {
-      betmn = fb;
-      a_mn = fa;
-      b_mn = fb;
-      jsol = 1;
-    } else if (fb <= 0.01f && fa < betmn) {
-      betmn = fa;
-      a_mn = fa;
-      b_mn = fb;
-      jsol = 0;
-    }
-    if (fb > betmx) betmx = fb;
-  }
-  float cc1 = jsol == 0 ? betmn : gtsolh(a_mn, b_mn);
-  cc1 = .95f * cc1;
-  cc1 = .90f * cc1;
+  float betmx, cc1;
+  startup(mmax, [&](int m, float &fa, float &fb) { fa = M.A(m), fb = M.B(m); }, betmx, cc1);
   typed_curve(M, A.iwave[seg], A.igr[seg], kmax, A.t + A.koff[seg], betmx, cc1, A.cg + A.cgoff[seg] + (size_t)w * kmax);
 }
 
@@ -359,44 +296,24 @@ extern "C" int dazim_dispersion_kernels_typed(dazim_ctx *ctx, int nx, int ny, in
   }
   // ---- the other segments: geometry-only layer table, refineGrid2LayerMdl (inv/CalSurfG.f90:2339-2365) + sphere (:510-545) ----
   std::vector<TLayer> lay;
+  std::vector<float> thk;
   for (const DzRefinedLayer &R : dz_refine_layers(depz, nz, sublayers)) {
     TLayer L{};
-    L.d = R.thk, L.iv = R.iv, L.fm = R.fm, L.den = R.den;
+    L.iv = R.iv, L.fm = R.fm, L.den = R.den;
     lay.push_back(L);
+    thk.push_back(R.thk);
   }
   const int mmax = (int)lay.size();
   if (mmax > NL) return dz_fail(ctx, DAZIM_E_BAD_ARG, "refined model has %d layers > NL=%d", mmax, NL);
-  {
-    const double ar = 6370.0;
-    double dr = 0.0, r0 = ar;
-    lay[mmax - 1].d = 1.0f;
-    for (int i = 0; i < mmax; i++) {
-      dr = dr + (double)lay[i].d;
-      const double r1 = ar - dr;
-      const double z0 = ar * log(ar / r0), z1 = ar * log(ar / r1);
-      lay[i].d = (float)(z1 - z0);
-      const double tmp = (ar + ar) / (r0 + r1);
-      lay[i].tmp = tmp;
-      const float x = (float)tmp, x2 = x * x;
-      lay[i].rfac_r = powf(x, -2.275f);
-      lay[i].rfac_l = 1.0f / (x2 * x2 * x);
-      r0 = r1;
-    }
-    lay[mmax - 1].d = 0.0f;
-  }
+  std::vector<double> tmp(mmax);
+  sphere_flatten(mmax, 6370.0, thk.data(), tmp.data());
+  for (int i = 0; i < mmax; i++)
+    lay[i].d = thk[i], lay[i].tmp = tmp[i], lay[i].rfac_r = rho_factor_rayleigh(tmp[i]), lay[i].rfac_l = rho_factor_love(tmp[i]);
   TypedArgs A{};
-  A.ncol = ncol, A.nz = nz, A.mmax = mmax, A.npatch = 0;
-  std::vector<int> krange(2 * (NZMAX + 1), 0);   // per knot the contiguous range of layers it touches, and the longest such range
-  for (int pi = 1; pi <= nz; pi++) {
-    int lo = 0, hi = 0;
-    for (int m = 1; m <= mmax; m++)
-      if ((pi > 1 && lay[m - 1].iv == pi - 1) || lay[m - 1].iv == pi || (pi == nz && lay[m - 1].iv == 0)) {
-        if (!lo) lo = m;
-        hi = m;
-      }
-    krange[2 * pi] = lo, krange[2 * pi + 1] = lo ? hi - lo + 1 : 0;
-    if (kernels) A.npatch = std::max(A.npatch, krange[2 * pi + 1]);
-  }
+  A.ncol = ncol, A.nz = nz, A.mmax = mmax;
+  std::vector<int> krange(2 * (NZMAX + 1), 0);
+  const int longest = knot_layer_ranges(lay, nz, krange.data());
+  A.npatch = kernels ? longest : 0;   // (a curves-only call has no perturbed knots: no patch table)
   int nvar_min = 1 << 30;
   size_t ncg = 0;
   for (int s = 0; s < nseg; s++) {

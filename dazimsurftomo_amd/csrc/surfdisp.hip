@@ -9,8 +9,10 @@
 // What runs where: the subroutine's prologue -- Earth flattening (sphere :480-547), the extremal velocities and the start
 // value of the search (gtsolh :361-382), a few hundred host flops per model with the host libm's log / powf the reference
 // calls -- is done on the host; the root searches (getsol :384-476, nevill :551-668 and the period equations) run on the
-// device in plain IEEE fp64, the reference's operations in the reference's order (this file is built with
-// -ffp-contract=off like the rest of the library; no reciprocal / fused forms as in disp.hip's tuned dltar4).  What can
+// device.  Both halves are surfdisp_device.h's functions, which disp_typed.hip and (the prologue's) disp.hip call as well; this
+// file holds the subroutine's argument checks, the per-model arrays and the loops over modes and periods.  The device half is
+// plain IEEE fp64, the reference's operations in the reference's order (this file is built with -ffp-contract=off like the
+// rest of the library; no reciprocal / fused forms as in disp.hip's tuned dltar4).  What can
 // differ from the reference is the last bit of the device's sin / cos / exp, i.e. roots that differ by ~1e-9 km/s before
 // they are rounded to fp32: tests/test_surfdisp_full_gpu.py states the resulting bars.
 #include <cmath>
@@ -20,7 +22,7 @@
 
 namespace {
 
-using namespace dz_sd;   // var, dltar1, dltar4, getsol, nevill: surfdisp_device.h, shared with disp_typed.hip
+using namespace dz_sd;   // surfdisp_device.h: everything of the subroutine that another unit runs as well
 
 constexpr int NL = 200;  // inv/surfdisp96.f:57
 constexpr int NP = 60;   // inv/surfdisp96.f:59
@@ -60,8 +62,6 @@ __global__ __launch_bounds__(64) void surfdisp_kernel(SdArgs S) {
   M.llw = S.llw[im];
   const int ifunc = S.iwave, kmax = S.kmax, igr = S.igr;
   const float betmx = S.betmx[im];
-  const float ddc = 0.005f, h = 0.005f, sone = 1.500f;
-  const double one = 1.0e-2, onea = (double)sone;
   const double cc = S.cc[im];
   const double dc = fabs((double)ddc);
   const double cm = cc;
@@ -83,16 +83,7 @@ __global__ __launch_bounds__(64) void surfdisp_kernel(SdArgs S) {
         failed = true;
         break;
       }
-      double t1 = S.t[k - 1];
-      float t1a, t1b = 0.0f;
-      if (igr > 0) {
-        t1a = (float)(t1 / (double)(1.f + h));
-        t1b = (float)(t1 / (double)(1.f - h));
-        t1 = (double)t1a;
-      } else {
-        t1a = (float)t1;
-      }
-      int ifirst;
+      int ifirst;   // the start values of mode iq at period k: from the previous period's root and the previous mode's (:247-266)
       if (k == is && iq == 1) {
         c1 = cc;
         clow = cc;
@@ -111,31 +102,16 @@ __global__ __launch_bounds__(64) void surfdisp_kernel(SdArgs S) {
         c1 = c[(k - 2) * st] - onea * dc;
         clow = cm;
       }
-      int iret = getsol(M, t1, c1, clow, dc, cm, betmx, ifunc, ifirst, del1st);
-      if (iret == -1) {
+      double ck, ckb;
+      float val;
+      if (!period_step(M, S.t[k - 1], igr, ifunc, ifirst, c1, clow, igr > 0 ? cb[(k - 1) * st] + one * dc : 0.0, dc, cm, betmx, del1st,
+                       ck, ckb, val)) {
         failed = true;
         break;
       }
-      const double ck = c1;
       c[(k - 1) * st] = ck;
-      if (igr > 0) {
-        t1 = (double)t1b;
-        clow = cb[(k - 1) * st] + one * dc;
-        c1 = c1 - onea * dc;
-        iret = getsol(M, t1, c1, clow, dc, cm, betmx, ifunc, 0, del1st);
-        if (iret == -1) c1 = ck;
-        cb[(k - 1) * st] = c1;
-      } else {
-        c1 = 0.0;
-      }
-      const float cc0 = (float)ck;
-      const float cc1 = (float)c1;
-      if (igr == 0) {
-        cg[k - 1] = (double)cc0;
-      } else {
-        const float gvel = (1 / t1a - 1 / t1b) / (1 / (t1a * cc0) - 1 / (t1b * cc1));
-        cg[k - 1] = (double)gvel;
-      }
+      if (igr > 0) cb[(k - 1) * st] = ckb;
+      cg[k - 1] = (double)val;
     }
     if (failed) {  // :1700-1770
       ift = k;
@@ -188,7 +164,7 @@ extern "C" int dazim_surfdisp96(dazim_ctx *ctx, int nmodel, int nlayer_max, cons
   for (int im = 0; im < nmodel; im++) {
     const int mmax = h_n[im];
     if (mmax < 1 || mmax > nlayer_max) return dz_fail(ctx, DAZIM_E_BAD_ARG, "model %d: nlayer=%d outside 1..%d", im, mmax, nlayer_max);
-    float d[NL], a[NL], b[NL], r[NL], rtp[NL], btp[NL];
+    float d[NL], a[NL], b[NL], r[NL];
     for (int i = 0; i < mmax; i++) {
       const size_t s = (size_t)im * nlayer_max + i;
       b[i] = h_vs[s];
@@ -199,52 +175,16 @@ extern "C" int dazim_surfdisp96(dazim_ctx *ctx, int nmodel, int nlayer_max, cons
     int llw = 1;
     if (b[0] <= 0.0f) llw = 2;
     if (iflsph == 1) {  // sphere(0,0) then sphere(ifunc,1), :480-547
-      const double ar = 6370.0;
-      double dr = 0.0, r0 = ar;
-      d[mmax - 1] = 1.0f;
-      for (int i = 0; i < mmax; i++) rtp[i] = r[i];
+      double tmp[NL];
+      sphere_flatten(mmax, 6370.0, d, tmp);
       for (int i = 0; i < mmax; i++) {
-        dr = dr + (double)d[i];
-        const double r1 = ar - dr;
-        const double z0 = ar * log(ar / r0), z1 = ar * log(ar / r1);
-        d[i] = (float)(z1 - z0);
-        const double tmp = (ar + ar) / (r0 + r1);
-        a[i] = (float)((double)a[i] * tmp);
-        b[i] = (float)((double)b[i] * tmp);
-        btp[i] = (float)tmp;
-        r0 = r1;
+        a[i] = (float)((double)a[i] * tmp[i]);
+        b[i] = (float)((double)b[i] * tmp[i]);
+        r[i] = r[i] * (iwave == 1 ? rho_factor_love(tmp[i]) : rho_factor_rayleigh(tmp[i]));
       }
-      d[mmax - 1] = 0.0f;
     }
-    float betmx = -1.e20f, betmn = 1.e20f;
-    int jmn = 1, jsol = 1;
-    for (int i = 0; i < mmax; i++) {
-      if (b[i] > 0.01f && b[i] < betmn) {
-        betmn = b[i];
-        jmn = i + 1;
-        jsol = 1;
-      } else if (b[i] <= 0.01f && a[i] < betmn) {
-        betmn = a[i];
-        jmn = i + 1;
-        jsol = 0;
-      }
-      if (b[i] > betmx) betmx = b[i];
-    }
-    if (iflsph == 1) {
-      for (int i = 0; i < mmax; i++) {
-        if (iwave == 1) {   // btp**(-5): reciprocal of the integer power, as the reference's build forms it
-          const float x = btp[i];
-          const float x2 = x * x;
-          r[i] = rtp[i] * (1.0f / (x2 * x2 * x));
-        } else {
-          r[i] = rtp[i] * powf(btp[i], -2.275f);
-        }
-      }
-      d[mmax - 1] = 0.0f;
-    }
-    float cc1 = (jsol == 0) ? betmn : gtsolh(a[jmn - 1], b[jmn - 1]);
-    cc1 = .95f * cc1;
-    cc1 = .90f * cc1;
+    float betmx, cc1;
+    startup(mmax, [&](int m, float &fa, float &fb) { fa = a[m - 1], fb = b[m - 1]; }, betmx, cc1);
     f_cc[im] = (double)cc1;
     f_betmx[im] = betmx;
     f_llw[im] = llw;

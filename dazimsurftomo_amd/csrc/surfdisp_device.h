@@ -1,13 +1,21 @@
-// surfdisp_device.h -- the device functions of the reference's surfdisp96 that more than one unit runs: the period equations
-// (dltar1, Love; dltar4 with var, Rayleigh) and the root search (getsol, nevill), the reference's operations in the reference's
-// order in plain IEEE fp64 (units that include this are built with -ffp-contract=off like the rest of the library).
-// surfdisp.hip (dazim_surfdisp96: one lane per model, layers in global arrays) and disp_typed.hip (dazim_dispersion_kernels_typed:
-// one lane per (column, variant), layers in LDS tables) instantiate them on their own model type MD, which offers
-//   float D(m), A(m), B(m), R(m)   thickness, Vp, Vs and density of layer m (1-based) after the Earth flattening
-//   int mmax, llw                  number of layers; first solid layer (2 with a water layer on top, else 1)
-// so that both evaluate the same expressions and return the same bits for the same layers.
+// surfdisp_device.h -- what more than one unit runs of the reference's surfdisp96 and of depthkernel's model prologue, each piece
+// stated once, so that the units return the same bits for the same layers (they are built with -ffp-contract=off like the rest of
+// the library: an inline function here rounds as a copy of its text in the unit would).
+//   host      the prologue that depends on the layer thicknesses only: the Earth flattening of a thickness stack (sphere_flatten),
+//             the density factors of the two wave types (rho_factor_rayleigh, rho_factor_love) and the layers a knot touches
+//             (knot_layer_ranges): disp.hip (DispCall::layers), disp_typed.hip (entry point), surfdisp.hip (host prologue)
+//   both      brocher (also ti.hip), gtsolh and the start-up scan (startup): the surfdisp.hip host prologue, typed_kernel, disp.hip
+//   device    the period equations (dltar1, Love; dltar4 with var, Rayleigh), the root search (getsol, nevill) and one period of
+//             the period loop (period_step), the reference's operations in the reference's order in plain IEEE fp64.
+//             surfdisp.hip (dazim_surfdisp96: one lane per model, layers in global arrays) and disp_typed.hip
+//             (dazim_dispersion_kernels_typed: one lane per (column, variant), layers in LDS tables) instantiate them on their own
+//             model type MD, which offers
+//               float D(m), A(m), B(m), R(m)   thickness, Vp, Vs and density of layer m (1-based) after the Earth flattening
+//               int mmax, llw                  number of layers; first solid layer (2 with a water layer on top, else 1)
+//             (disp.hip keeps its tuned dltar4 and its lockstep search)
 #pragma once
 #include <cmath>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -332,7 +340,7 @@ __device__ int getsol(const MD &M, double t1, double &c1, double clow, double dc
   return 1;
 }
 
-// gtsolh, inv/surfdisp96.f:361-382, all fp32: the start value of the first search, from the slowest layer (host in surfdisp.hip, device in disp_typed.hip)
+// gtsolh, inv/surfdisp96.f:361-382, all fp32: the start value of the first search, from the slowest layer
 __host__ __device__ inline float gtsolh(float a, float b) {
   float c = 0.95f * b;
   for (int i = 0; i < 5; i++) {
@@ -348,6 +356,134 @@ __host__ __device__ inline float gtsolh(float a, float b) {
     c = c - fr / frp;
   }
   return c;
+}
+
+// Brocher's Vs -> Vp, rho of depthkernel (inv/CalSurfG.f90:49-53) and depthkernelTI (inv/depthkernelTI.f90:48-53), fp32 in the
+// reference's order: every power by repeated multiplication, every sum from the left
+__host__ __device__ __forceinline__ void brocher(float vs, float &vp, float &rho) {
+  const float v2 = vs * vs, v3 = v2 * vs, v4 = v3 * vs;
+  const float p = 0.9409f + 2.0947f * vs - 0.8206f * v2 + 0.2683f * v3 - 0.0251f * v4;
+  const float p2 = p * p, p3 = p2 * p, p4 = p3 * p, p5 = p4 * p;
+  vp = p;
+  rho = 1.6612f * p - 0.4721f * p2 + 0.0671f * p3 - 0.0043f * p4 + 0.000106f * p5;
+}
+
+// start-up of surfdisp96 (:134-216): the extremal velocities of the stack and the start value of the first period's search, from
+// the slowest layer.  layer(m, a, b) gives Vp and Vs of layer m = 1 .. mmax after the flattening
+template <class F>
+__host__ __device__ __forceinline__ void startup(int mmax, F &&layer, float &betmx, float &cc1) {
+  float betmn = 1.e20f, a_mn = 1.0f, b_mn = 1.0f;
+  betmx = -1.e20f;
+  int jsol = 1;
+  for (int m = 1; m <= mmax; m++) {
+    float fa, fb;
+    layer(m, fa, fb);
+    if (fb > 0.01f && fb < betmn) {
+      betmn = fb;
+      a_mn = fa;
+      b_mn = fb;
+      jsol = 1;
+    } else if (fb <= 0.01f && fa < betmn) {
+      betmn = fa;
+      a_mn = fa;
+      b_mn = fb;
+      jsol = 0;
+    }
+    if (fb > betmx) betmx = fb;
+  }
+  cc1 = jsol == 0 ? betmn : gtsolh(a_mn, b_mn);
+  cc1 = .95f * cc1;
+  cc1 = .90f * cc1;
+}
+
+// the constants of surfdisp96's period loop (:118-131, :184-185): the step of the bracket search, the relative period offset of a group
+// velocity, and how far below the last root (x dc) the next search starts; `one` x dc above the previous mode's root
+constexpr float ddc = 0.005f, h = 0.005f, sone = 1.500f;
+constexpr double one = 1.0e-2, onea = (double)sone;
+
+// One period of the period loop (:225-233, :270-304): the root ck at t (igr = 0) or at t / (1 + h), from the caller's start c1 and lower bound
+// clow; for a group velocity the second root cb at t / (1 - h), searched from ck - onea dc with the lower bound clowb (ck where
+// there is none, iret = -1 at :285), else cb = 0; val = sngl(ck) or the fp32 group velocity (:292-301).  Returns false, with the
+// outputs untouched, where the first search fails: the curve ends.  del1st is getsol's SAVE variable.
+template <class MD>
+__device__ __forceinline__ bool period_step(const MD &M, double t1, int igr, int ifunc, int ifirst, double c1, double clow, double clowb,
+                                            double dc, double cm, float betmx, double &del1st, double &ck, double &cb, float &val) {
+  float t1a, t1b = 0.0f;
+  if (igr > 0) {
+    t1a = (float)(t1 / (double)(1.f + h));
+    t1b = (float)(t1 / (double)(1.f - h));
+    t1 = (double)t1a;
+  } else {
+    t1a = (float)t1;
+  }
+  int iret = getsol(M, t1, c1, clow, dc, cm, betmx, ifunc, ifirst, del1st);
+  if (iret == -1) return false;
+  ck = c1;
+  if (igr > 0) {
+    t1 = (double)t1b;
+    c1 = c1 - onea * dc;
+    iret = getsol(M, t1, c1, clowb, dc, cm, betmx, ifunc, 0, del1st);
+    if (iret == -1) c1 = ck;
+  } else {
+    c1 = 0.0;
+  }
+  cb = c1;
+  const float cc0 = (float)ck;
+  const float cc1 = (float)c1;
+  if (igr == 0) {
+    val = cc0;
+  } else {
+    val = (1 / t1a - 1 / t1b) / (1 / (t1a * cc0) - 1 / (t1b * cc1));
+  }
+  return true;
+}
+
+// ---- host: the part of the prologue that depends on the layer thicknesses only, with the host libm's log / powf the reference calls ----
+
+// sphere(0,0), inv/surfdisp96.f:132, :510-530: the thicknesses d [mmax] of a spherical stack of radius ar become those of the flat one, in
+// place; tmp [mmax] receives the factor (ar+ar)/(r0+r1) that scales a layer's velocities (:528) and enters its density factor.
+// The half-space counts with the dummy thickness 1 (:513) and ends with 0 (:545).
+inline void sphere_flatten(int mmax, double ar, float *d, double *tmp) {
+  double dr = 0.0, r0 = ar;
+  d[mmax - 1] = 1.0f;
+  for (int i = 0; i < mmax; i++) {
+    dr = dr + (double)d[i];
+    const double r1 = ar - dr;
+    const double z0 = ar * log(ar / r0), z1 = ar * log(ar / r1);
+    d[i] = (float)(z1 - z0);
+    tmp[i] = (ar + ar) / (r0 + r1);
+    r0 = r1;
+  }
+  d[mmax - 1] = 0.0f;
+}
+
+// sphere(ifunc,1), :169, :536-545: what a layer's density is multiplied by, btp = sngl(tmp)
+inline float rho_factor_rayleigh(double tmp) { return powf((float)tmp, -2.275f); }   // btp**(-2.275), :541
+inline float rho_factor_love(double tmp) {   // btp**(-5), :539: reciprocal of the integer power, as the reference's build forms it
+  const float x = (float)tmp;
+  const float x2 = x * x;
+  return 1.0f / (x2 * x2 * x);
+}
+
+// Per knot pi = 1 .. nz the contiguous range of refined layers (anything with the interval iv of dz_refine_layers) it touches -- the
+// sublayers of intervals pi - 1 and pi, for the last knot those of the last interval and the half-space --: krange [nz + 1][2] = first
+// layer (1-based) and number of layers, row 0 = none.  Returns the longest range.
+template <class L>
+inline int knot_layer_ranges(const std::vector<L> &lay, int nz, int *krange) {
+  const int mmax = (int)lay.size();
+  int longest = 0;
+  krange[0] = krange[1] = 0;
+  for (int pi = 1; pi <= nz; pi++) {
+    int lo = 0, hi = 0;
+    for (int m = 1; m <= mmax; m++)
+      if ((pi > 1 && lay[m - 1].iv == pi - 1) || lay[m - 1].iv == pi || (pi == nz && lay[m - 1].iv == 0)) {
+        if (!lo) lo = m;
+        hi = m;
+      }
+    krange[2 * pi] = lo, krange[2 * pi + 1] = lo ? hi - lo + 1 : 0;
+    if (krange[2 * pi + 1] > longest) longest = krange[2 * pi + 1];
+  }
+  return longest;
 }
 
 }  // namespace dz_sd

@@ -3,7 +3,7 @@
 // = depthkernelTI (inv/depthkernelTI.f90:2-106) -> tregn96 (inv/tregn96.f:52-722), live branch only: Rayleigh,
 //   fundamental mode, solid layers, flattened model (iflsph=1), causal-Q phase shift (Qp=150, Qs=50, fref=1 Hz),
 //   source/receiver depth 0.  The phase velocities are an input (pvRc of dazim_dispersion_kernels, which runs the same
-//   surfdisp96 on the same layered columns).
+//   surfdisp96 on the same layered columns); Brocher's Vp and rho are depthkernel's function (surfdisp_device.h).
 //
 // One lane per (column, period).  fp64 throughout, like the reference.  Three sweeps over the layers of a lane:
 //   up   : Dunkin compound vector from the half-space to the surface (up, :1834).  The 5x5 layer matrix of
@@ -15,8 +15,11 @@
 //   out  : normalisation, gammap (:3711), sprayl (:1235), fp32 rounding (chksiz) and the depthkernelTI sum.
 // HBM scratch is [layer][value][lane], so every access of a wavefront is one contiguous 512-byte run.
 #include "dazim_internal.h"
+#include "surfdisp_device.h"
 
 namespace {
+
+using dz_sd::brocher;   // Vs -> Vp, rho of depthkernelTI (:48-53), the expressions of depthkernel: surfdisp_device.h
 
 constexpr int NLMAX = 200;  // inv/tregn96.f: NL
 constexpr int TT = 64;      // lanes per workgroup
@@ -233,12 +236,6 @@ struct TiArgs {
   float *lsen;             // [nz-1][kmax][ncol]
   int *bad;                // fluid layer seen
 };
-
-__device__ __forceinline__ void brocher(float vs, float &vp, float &rho) {  // inv/depthkernelTI.f90:48-53
-  vp = 0.9409f + 2.0947f * vs - 0.8206f * (vs * vs) + 0.2683f * (vs * vs * vs) - 0.0251f * (vs * vs * vs * vs);
-  rho = 1.6612f * vp - 0.4721f * (vp * vp) + 0.0671f * (vp * vp * vp) - 0.0043f * (vp * vp * vp * vp) +
-        0.000106f * (vp * vp * vp * vp * vp);
-}
 
 // per column: knots -> layers (refineLayerMdl, inv/CalSurfGAniso_Joint.f90:146), TI moduli (depthkernelTI :71-78) and
 // their flattened fp64 copies (sphere_tdisp96, inv/tregn96.f:774; TF is not transformed there)
