@@ -122,6 +122,18 @@ def _tradeoff_args(m_data, b, nblk, scale, damp, dof, evidence, lead):
     return K, scale, damp, b, out
 
 
+def _posterior_args(sel, shape):
+    """what Context.map_posterior and Context.model_posterior pass alike: (new, sel, nsel, out) with new(*shape) an fp32 array where
+    the outputs live (torch-cuda with a torch-cuda sel, numpy otherwise), sel as the call takes it and out the four mandatory arrays"""
+    if sel is not None and _is_torch(sel):
+        import torch
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=sel.device)
+    else:
+        new = lambda *shape: np.zeros(shape, np.float32)
+        sel = None if sel is None else np.ascontiguousarray(sel, np.int32)
+    return new, sel, 0 if sel is None else int(sel.shape[0]), {k: new(*shape) for k in ("std_post", "std_noise", "rdiag", "rsum")}
+
+
 class Context:
     """One GPU context (`dazim_ctx`).  Raises if no GPU / no library: there is no CPU path."""
 
@@ -508,14 +520,7 @@ class Context:
         sel); n_failed."""
         nblk = 3 if azim else 1
         ng = nblk * (nx - 2) * (ny - 2)
-        if sel is not None and _is_torch(sel):
-            import torch
-            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=sel.device)
-        else:
-            new = lambda *shape: np.zeros(shape, np.float32)
-            sel = None if sel is None else np.ascontiguousarray(sel, np.int32)
-        nsel = 0 if sel is None else int(sel.shape[0])
-        out = {k: new(nblk, kmax, ny - 2, nx - 2) for k in ("std_post", "std_noise", "rdiag", "rsum")}
+        new, sel, nsel, out = _posterior_args(sel, (nblk, kmax, ny - 2, nx - 2))
         out["width"] = new(nblk, kmax, ny - 2, nx - 2) if width else None
         out["leak"] = new(nblk, kmax, ny - 2, nx - 2) if azim else None
         out["rows"] = new(kmax, nsel, ng) if nsel else None
@@ -566,18 +571,11 @@ class Context:
         n_failed."""
         nblk = 3 if joint else 1
         n = nblk * (nx - 2) * (ny - 2) * (nz - 1)
-        if sel is not None and _is_torch(sel):
-            import torch
-            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=sel.device)
-        else:
-            new = lambda *shape: np.zeros(shape, np.float32)
-            sel = None if sel is None else np.ascontiguousarray(sel, np.int32)
+        shape = (nblk, nz - 1, ny - 2, nx - 2)
+        new, sel, nsel, out = _posterior_args(sel, shape)
         if depz is not None and not _is_torch(depz):
             depz = np.ascontiguousarray(depz, np.float32)
             assert depz.size == nz - 1
-        nsel = 0 if sel is None else int(sel.shape[0])
-        shape = (nblk, nz - 1, ny - 2, nx - 2)
-        out = {k: new(*shape) for k in ("std_post", "std_noise", "rdiag", "rsum")}
         out["width_h"] = new(*shape) if width else None
         out["width_z"] = new(*shape) if width and depz is not None else None
         out["leak"] = new(*shape) if joint else None

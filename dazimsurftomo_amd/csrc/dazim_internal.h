@@ -350,6 +350,10 @@ struct DzTimer {
     (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     ctx->ksec[name] = ms * 1e-3;
   }
+  void lap(double &sum) {   // stop, and add the seconds to those of a part of the call
+    stop();
+    sum += ctx->ksec[name];
+  }
 };
 
 // the seconds of a call's parts, sec[0 .. count), published under names[] and their sum under `total`; the lap stat they were

@@ -84,10 +84,6 @@ __global__ __launch_bounds__(64) void k_mp_gram(int ng, int ncell, int kn, int p
 }
 
 // ---- row pass ----------------------------------------------------------------------------------------------------------------------
-struct MpOut {
-  float *std_post, *std_noise, *rdiag, *rsum, *width, *leak, *rows;
-};
-
 // workgroup a: Rm_a. = e_a - sum_l (C_a. l) l - damp^2 C_a. over the period's regularisation rows l in ascending order, and what is
 // summed along that row.  Dynamic LDS: rm [ng] | tb [MP_TB] | eval [MP_TB][MP_EMAX] | ebeg [MP_TB] | ecol [MP_TB][MP_EMAX] | elen [MP_TB]
 __global__ __launch_bounds__(MP_TB) void k_mp_rows(int ng, int ncell, int nvx, int kn, int p, int nreg, const int *reglist,
@@ -102,17 +98,7 @@ __global__ __launch_bounds__(MP_TB) void k_mp_rows(int ng, int ncell, int nvx, i
   const int blk = a / ncell, cell = a % ncell;
   const size_t o = (size_t)blk * kn + (size_t)p * ncell + cell;
   if (*flag) {
-    const float v = nanf("");
-    if (t == 0) {
-      out.std_post[o] = out.std_noise[o] = out.rdiag[o] = out.rsum[o] = v;
-      if (out.width) out.width[o] = v;
-      if (out.leak) out.leak[o] = v;
-      rd64[a] = (double)v;
-    }
-    if (out.rows)
-      for (int s = 0; s < nsel; s++)
-        if (sel[s] == a)
-          for (int c = t; c < ng; c += MP_TB) out.rows[((size_t)p * nsel + s) * ng + c] = v;
+    mp_fill_nan(out, o, rd64, a, t, nsel, sel, (size_t)p * nsel, ng);
     return;
   }
   const double *Ca = Cm + (size_t)a * ng;
@@ -156,48 +142,27 @@ __global__ __launch_bounds__(MP_TB) void k_mp_rows(int ng, int ncell, int nvx, i
   for (int c = t; c < ng; c += MP_TB) rm[c] -= d2 * Ca[c];
   __syncthreads();
   const int ia = cell % nvx, ja = cell / nvx;
-  double rs = 0.0, nv = 0.0, own = 0.0, oth = 0.0, num = 0.0;
+  MpRowSum<false> sum;
   for (int c = t; c < ng; c += MP_TB) {
-    const double r = rm[c];
-    rs += r;
-    nv += r * Ca[c];
-    if (c / ncell == blk) {
-      const int cc = c % ncell;
-      const double di = (double)(cc % nvx - ia), dj = (double)(cc / nvx - ja);
-      own += r * r;
-      num += r * r * (di * di + dj * dj);
-    } else {
-      oth += r * r;
-    }
+    const int cc = c % ncell;
+    const double di = (double)(cc % nvx - ia), dj = (double)(cc / nvx - ja);
+    sum.add(rm[c], Ca[c], c / ncell == blk, di * di + dj * dj, 0.0);
   }
-  rs = mp_block_sum(rs, red);
-  nv = mp_block_sum(nv, red);
-  own = mp_block_sum(own, red);
-  oth = mp_block_sum(oth, red);
-  num = mp_block_sum(num, red);
-  if (t == 0) {
-    out.std_post[o] = (float)sqrt(Ca[a]);
-    out.std_noise[o] = (float)sqrt(fmax(nv, 0.0));
-    out.rdiag[o] = (float)rm[a];
-    out.rsum[o] = (float)rs;
-    if (out.width) out.width[o] = own > 0.0 ? (float)sqrt(num / own) : 0.0f;
-    if (out.leak) out.leak[o] = own + oth > 0.0 ? (float)(oth / (own + oth)) : 0.0f;
-    rd64[a] = rm[a];
-  }
+  sum.reduce(red);
+  if (t == 0) sum.write(out, o, Ca[a], rm[a], rd64, a);
   if (out.rows)
     for (int s = 0; s < nsel; s++)
       if (sel[s] == a)
         for (int c = t; c < ng; c += MP_TB) out.rows[((size_t)p * nsel + s) * ng + c] = (float)rm[c];
 }
 
-// trace[blk][p] = sum of Rm_aa over the block's cells (workgroup blk)
-__global__ __launch_bounds__(MP_TB) void k_mp_trace(int ncell, int kmax, int p, const double *rd64, float *trace) {
+// trace[b * stride + off] = sum of Rm_aa over the ncell unknowns b * ncell .. of workgroup b: the maps' [blk][p], the model's [blk][k]
+__global__ __launch_bounds__(MP_TB) void k_mp_trace(int ncell, int stride, int off, const double *rd64, float *trace) {
   __shared__ double red[MP_TB / 64];
-  const int blk = blockIdx.x;
   double s = 0.0;
-  for (int c = threadIdx.x; c < ncell; c += MP_TB) s += rd64[(size_t)blk * ncell + c];
+  for (int c = threadIdx.x; c < ncell; c += MP_TB) s += rd64[(size_t)blockIdx.x * ncell + c];
   s = mp_block_sum(s, red);
-  if (threadIdx.x == 0) trace[blk * kmax + p] = (float)s;
+  if (threadIdx.x == 0) trace[blockIdx.x * stride + off] = (float)s;
 }
 
 }  // namespace
@@ -228,24 +193,28 @@ int dz_mp_gram(dazim_ctx *ctx, int ng, int ncell, int kn, int p, int nrow, const
   return 0;
 }
 
+void dz_mp_trace(dazim_ctx *ctx, int nb, int ncell, int stride, int off, const double *rd64, float *trace) {
+  hipLaunchKernelGGL(k_mp_trace, dim3((unsigned)nb), dim3(MP_TB), 0, ctx->stream, ncell, stride, off, rd64, trace);
+}
+
+// dazim_map_posterior and dazim_model_posterior (model_post.hip) share their argument checks, output buffers and row-pass pieces
+// (map_post_internal.h).  What differs on the host and stays: the maps keep their matrices in the context's scratch (dz_scratch), the
+// model allocates its own for the call (DzOwned); the model finishes the eikonal work (dz_fmm_finish) before dz_join_aux, the maps do
+// not; the stats map_post.nb and map_post.mfma are published here only, model_post.n there only.
 extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m_data, int nx, int ny, int kmax, int azim, float damp,
                                    float *std_post_u, float *std_noise_u, float *rdiag_u, float *rsum_u, float *width_u, float *leak_u,
                                    int nsel, const int *sel_u, float *rows_u, float *trace_u, int *n_failed) {
   if (!ctx || !A || nx < 3 || ny < 3 || kmax < 1 || !std_post_u || !std_noise_u || !rdiag_u || !rsum_u)
     return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_map_posterior");
-  if (m_data < 0 || m_data > A->m) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: m_data %lld outside 0..%lld", (long long)m_data, (long long)A->m);
   const int nblk = azim ? 3 : 1;
   const int64_t ncell64 = (int64_t)(nx - 2) * (ny - 2), ng64 = nblk * ncell64;
-  if (A->n != ng64 * kmax)
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: n %lld is not nblk * kmax * ncell = %lld", (long long)A->n, (long long)(ng64 * kmax));
-  if (!azim && leak_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: leak without azim");
-  if (!(damp >= 0.0f) || !std::isfinite(damp)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: damp negative or not finite");
-  if (nsel < 0 || (nsel > 0 && !sel_u)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: nsel without sel");
-  if (rows_u && nsel < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: rows without sel");
+  int rc;
+  if ((rc = dz_post_check_args(ctx, "dazim_map_posterior", A, m_data, A->n == ng64 * kmax, "nblk * kmax * ncell", ng64 * kmax, azim != 0, "azim", leak_u,
+                               nullptr, damp, nsel, sel_u, rows_u)))
+    return rc;
   const size_t lds = (size_t)ng64 * 8 + (size_t)MP_TB * (8 + MP_EMAX * 8 + 8 + MP_EMAX * 4 + 4);
   if (lds > 160 * 1024) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: %lld unknowns per period do not fit the row pass's LDS", (long long)ng64);
   DZ_HIP(hipSetDevice(ctx->device));
-  int rc;
   if ((rc = dz_join_aux(ctx))) return rc;
   const int ncell = (int)ncell64, ng = (int)ng64, kn = kmax * ncell, nvx = nx - 2;
   const int64_t m = A->m;
@@ -258,14 +227,10 @@ extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m
       (rc = dz_scratch(ctx, "mpost.list", (size_t)m, &list)) || (rc = dz_scratch(ctx, "mpost.cnt", (size_t)2 * kmax + 1, &cnt)) ||
       (rc = dz_scratch(ctx, "mpost.flags", (size_t)kmax, &flags)))
     return rc;
-  DzBuf<float> sp, sn, rd, rs, wd, lk, rw, tr;
+  MpOutBufs ob;
   DzBuf<int> sel;
-  if ((rc = sel.init(ctx, sel_u, (size_t)nsel, true, false)) || (rc = sp.init(ctx, std_post_u, no, false, true)) ||
-      (rc = sn.init(ctx, std_noise_u, no, false, true)) || (rc = rd.init(ctx, rdiag_u, no, false, true)) ||
-      (rc = rs.init(ctx, rsum_u, no, false, true)) || (rc = wd.init(ctx, width_u, width_u ? no : 0, false, true)) ||
-      (rc = lk.init(ctx, leak_u, leak_u ? no : 0, false, true)) ||
-      (rc = rw.init(ctx, rows_u, rows_u ? (size_t)kmax * nsel * ng : 0, false, true)) ||
-      (rc = tr.init(ctx, trace_u, trace_u ? (size_t)nblk * kmax : 0, false, true)))
+  if ((rc = sel.init(ctx, sel_u, (size_t)nsel, true, false)) ||
+      (rc = ob.init(ctx, std_post_u, std_noise_u, rdiag_u, rsum_u, width_u, nullptr, leak_u, rows_u, trace_u, no, (size_t)kmax * nsel * ng, (size_t)nblk * kmax)))
     return rc;
   DZ_HIP(hipFuncSetAttribute((const void *)k_mp_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (a refusal ends the call: no launch)
   if (nsel > 0 && (rc = dz_check_range(ctx, sel.dev, nsel, 0, ng - 1, "dazim_map_posterior: sel"))) return rc;
@@ -277,12 +242,8 @@ extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m
   if (hcnt[2 * kmax] & 2) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_map_posterior: a row's columns do not ascend strictly");
   const bool mfma = dz_opt(ctx, "map_post.mfma", 1) != 0;
   const double d2 = (double)damp * (double)damp;
-  const MpOut out = {sp.dev, sn.dev, rd.dev, rs.dev, wd.dev, lk.dev, rw.dev};
+  const MpOut out = ob.dev();
   double sec[5] = {0, 0, 0, 0, 0};
-  auto lap = [&](int which, DzTimer &t) {
-    t.stop();
-    sec[which] += ctx->ksec["map_post.lap"];
-  };
   int off = 0;
   for (int p = 0; p < kmax; p++) {
     const int nrow = hcnt[2 * p], ndat = hcnt[2 * p + 1];
@@ -291,23 +252,21 @@ extern "C" int dazim_map_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t m
     {
       DzTimer t(ctx, "map_post.lap");
       if ((rc = dz_mp_gram(ctx, ng, ncell, kn, p, nrow, lp, span, A, d2, Ad))) return rc;
-      lap(0, t);
+      t.lap(sec[0]);
     }
     if ((rc = dz_mp_dense(ctx, ng, Ad, Cd, flags + p, mfma, "map_post.lap", sec + 1))) return rc;
     {
       DzTimer t(ctx, "map_post.lap");
       hipLaunchKernelGGL(k_mp_rows, dim3((unsigned)ng), dim3(MP_TB), lds, ctx->stream, ng, ncell, nvx, kn, p, nrow - ndat, lp + ndat, A->rowptr,
                          A->col, A->val, d2, Cd, flags + p, out, nsel, sel.dev, rd64);
-      if (tr.dev) hipLaunchKernelGGL(k_mp_trace, dim3((unsigned)nblk), dim3(MP_TB), 0, ctx->stream, ncell, kmax, p, rd64, tr.dev);
+      if (ob.tr.dev) dz_mp_trace(ctx, nblk, ncell, kmax, p, rd64, ob.tr.dev);
       DZ_HIP(hipGetLastError());
-      lap(4, t);
+      t.lap(sec[4]);
     }
   }
   std::vector<int> hflag(kmax);
   DZ_HIP(hipMemcpyAsync(hflag.data(), flags, (size_t)kmax * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = sp.finish()) || (rc = sn.finish()) || (rc = rd.finish()) || (rc = rs.finish()) || (rc = wd.finish()) || (rc = lk.finish()) ||
-      (rc = rw.finish()) || (rc = tr.finish()))
-    return rc;
+  if ((rc = ob.finish())) return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   int nf = 0;
   for (int p = 0; p < kmax; p++) nf += hflag[p] != 0;

@@ -250,16 +250,11 @@ int dz_mp_factor(dazim_ctx *ctx, int ng, double *Ad, int *flag, bool mfma, const
     }
   }
   DZ_HIP(hipGetLastError());
-  t.stop();
-  sec[0] += ctx->ksec[lapname];
+  t.lap(sec[0]);
   return 0;
 }
 
 int dz_mp_inverse_c(dazim_ctx *ctx, int ng, double *Ad, double *Cd, bool mfma, const char *lapname, double *sec) {
-  auto lap = [&](int which, DzTimer &t) {
-    t.stop();
-    sec[which] += ctx->ksec[lapname];
-  };
   {
     DzTimer t(ctx, lapname);
     for (int jb = ((ng - 1) / MP_NB) * MP_NB; jb >= 0; jb -= MP_NB) {
@@ -271,7 +266,7 @@ int dz_mp_inverse_c(dazim_ctx *ctx, int ng, double *Ad, double *Cd, bool mfma, c
       }
     }
     DZ_HIP(hipGetLastError());
-    lap(1, t);
+    t.lap(sec[1]);
   }
   {
     DzTimer t(ctx, lapname);
@@ -279,7 +274,7 @@ int dz_mp_inverse_c(dazim_ctx *ctx, int ng, double *Ad, double *Cd, bool mfma, c
     if (mfma) hipLaunchKernelGGL(k_mp_ctc<MpMfma>, dim3(nt, nt), dim3(MP_TB), 0, ctx->stream, ng, Ad, Cd);
     else hipLaunchKernelGGL(k_mp_ctc<MpPlain>, dim3(nt, nt), dim3(MP_TB), 0, ctx->stream, ng, Ad, Cd);
     DZ_HIP(hipGetLastError());
-    lap(2, t);
+    t.lap(sec[2]);
   }
   return 0;
 }

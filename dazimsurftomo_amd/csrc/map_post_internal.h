@@ -3,8 +3,11 @@
 // those blocks at every point of a sweep over the regularisation weights) share: the sizes of the dense kernels, their two tile
 // forms, the fixed-order sum of a workgroup, the two Gram accumulators (mp_accum_rows over a period's row list, mo_accum_row over a
 // column of the transpose), and the host driver of the dense part (map_post_dense.hip), which every entry calls -- so a block of
-// the maps and the block of the model go through the same kernels in the same order, bit for bit.
+// the maps and the block of the model go through the same kernels in the same order, bit for bit.  The two posterior entries share
+// what follows an entry of Rm in their row passes too (MpOut, MpRowSum, mp_fill_nan, the trace kernel) and their host side's
+// argument checks and output buffers (dz_post_check_args, MpOutBufs).
 #pragma once
+#include <cmath>
 #include <vector>
 
 #include "sparse_internal.h"
@@ -78,6 +81,69 @@ __device__ __forceinline__ double mp_block_sum(double v, double *red) {
   double s = 0.0;
   for (int i = 0; i < MP_TB / 64; i++) s += red[i];
   return s;
+}
+
+// ---- the row pass of dazim_map_posterior (k_mp_rows) and dazim_model_posterior (k_mo_rows) ------------------------------------------
+// The two kernels obtain an entry Rm_ac by different routes (LDS scatter in the maps, transpose gather in the model); the rest is here.
+struct MpOut {   // per-unknown outputs (width_h is the maps' width; width_z, leak and rows may be null) and the selected rows of Rm
+  float *std_post, *std_noise, *rdiag, *rsum, *width_h, *width_z, *leak, *rows;
+};
+
+// One thread's part of what is summed along row a of Rm.  DEPTH: the vertical width too (the model); without it the struct has no
+// sixth sum, so the maps' pass keeps five block sums.
+template <bool DEPTH>
+struct MpRowSum {
+  double rs = 0.0, nv = 0.0, own = 0.0, oth = 0.0, numh = 0.0, numz = 0.0;
+  // r = Rm_ac, cac = C_ac; same_block: c lies in a's block, dh2 and dz2 its squared horizontal and vertical distance from a
+  __device__ __forceinline__ void add(double r, double cac, bool same_block, double dh2, double dz2) {
+    rs += r;
+    nv += r * cac;
+    double o = own, x = oth;   // (locals: a store to own or oth by a selected address would put the struct into scratch)
+    if (same_block) {
+      o += r * r;
+      numh += r * r * dh2;
+      if (DEPTH) numz += r * r * dz2;
+    } else {
+      x += r * r;
+    }
+    own = o;
+    oth = x;
+  }
+  __device__ __forceinline__ void reduce(double *red) {
+    rs = mp_block_sum(rs, red);
+    nv = mp_block_sum(nv, red);
+    own = mp_block_sum(own, red);
+    oth = mp_block_sum(oth, red);
+    numh = mp_block_sum(numh, red);
+    if (DEPTH) numz = mp_block_sum(numz, red);
+  }
+  // one thread, after reduce: the outputs of unknown a at o; caa = C_aa, rdiag = Rm_aa
+  __device__ __forceinline__ void write(MpOut out, size_t o, double caa, double rdiag, double *rd64, int a) const {
+    out.std_post[o] = (float)sqrt(caa);
+    out.std_noise[o] = (float)sqrt(fmax(nv, 0.0));
+    out.rdiag[o] = (float)rdiag;
+    out.rsum[o] = (float)rs;
+    if (out.width_h) out.width_h[o] = own > 0.0 ? (float)sqrt(numh / own) : 0.0f;
+    if (DEPTH && out.width_z) out.width_z[o] = own > 0.0 ? (float)sqrt(numz / own) : 0.0f;
+    if (out.leak) out.leak[o] = own + oth > 0.0 ? (float)(oth / (own + oth)) : 0.0f;
+    rd64[a] = rdiag;
+  }
+};
+
+// unknown a (outputs at o) of a block that could not be factored: NaN in every output, rd64 and a's rows s0 + s of out.rows, n long
+__device__ __forceinline__ void mp_fill_nan(MpOut out, size_t o, double *rd64, int a, int t, int nsel, const int *sel, size_t s0, int n) {
+  const float v = nanf("");
+  if (t == 0) {
+    out.std_post[o] = out.std_noise[o] = out.rdiag[o] = out.rsum[o] = v;
+    if (out.width_h) out.width_h[o] = v;
+    if (out.width_z) out.width_z[o] = v;
+    if (out.leak) out.leak[o] = v;
+    rd64[a] = (double)v;
+  }
+  if (out.rows)
+    for (int s = 0; s < nsel; s++)
+      if (sel[s] == a)
+        for (int c = t; c < n; c += MP_TB) out.rows[(s0 + s) * n + c] = v;
 }
 
 // local index blk * ncell + cell of column c = blk * kn + p * ncell + cell of the maps' layout (kn = kmax ncell)
@@ -173,7 +239,48 @@ __device__ __forceinline__ void mo_accum_row(int a, int t, int n, int64_t p0, in
   }
 }
 
+// The argument checks the two posterior entries share, in their order, under the entry's name: n_is words the product A->n has
+// to equal (n_ok: it does), `coupled` the mode without which there is no leak, `also` a refusal only one entry knows (NULL: none).
+static inline int dz_post_check_args(dazim_ctx *ctx, const char *entry, const dazim_csr *A, int64_t m_data, bool n_ok, const char *n_is, int64_t n_want,
+                                     bool is_coupled, const char *coupled, const float *leak_u, const char *also, float damp, int nsel,
+                                     const int *sel_u, const float *rows_u) {
+  if (m_data < 0 || m_data > A->m) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: m_data %lld outside 0..%lld", entry, (long long)m_data, (long long)A->m);
+  if (!n_ok) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: n %lld is not %s = %lld", entry, (long long)A->n, n_is, (long long)n_want);
+  if (!is_coupled && leak_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: leak without %s", entry, coupled);
+  if (also) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: %s", entry, also);
+  if (!(damp >= 0.0f) || !std::isfinite(damp)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: damp negative or not finite", entry);
+  if (nsel < 0 || (nsel > 0 && !sel_u)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: nsel without sel", entry);
+  if (rows_u && nsel < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "%s: rows without sel", entry);
+  return 0;
+}
+
+// The outputs of a posterior entry, each where the user keeps it (host or device): `no` values per unknown, nrows * no_row of the
+// selected rows, ntrace of the trace; an output the user did not ask for has no buffer.
+struct MpOutBufs {
+  DzBuf<float> sp, sn, rd, rs, wh, wz, lk, rw, tr;
+  int init(dazim_ctx *ctx, float *std_post_u, float *std_noise_u, float *rdiag_u, float *rsum_u, float *width_h_u, float *width_z_u, float *leak_u,
+           float *rows_u, float *trace_u, size_t no, size_t nrows, size_t ntrace) {
+    int rc;
+    if ((rc = sp.init(ctx, std_post_u, no, false, true)) || (rc = sn.init(ctx, std_noise_u, no, false, true)) ||
+        (rc = rd.init(ctx, rdiag_u, no, false, true)) || (rc = rs.init(ctx, rsum_u, no, false, true)) ||
+        (rc = wh.init(ctx, width_h_u, width_h_u ? no : 0, false, true)) || (rc = wz.init(ctx, width_z_u, width_z_u ? no : 0, false, true)) ||
+        (rc = lk.init(ctx, leak_u, leak_u ? no : 0, false, true)) || (rc = rw.init(ctx, rows_u, rows_u ? nrows : 0, false, true)) ||
+        (rc = tr.init(ctx, trace_u, trace_u ? ntrace : 0, false, true)))
+      return rc;
+    return 0;
+  }
+  MpOut dev() const { return {sp.dev, sn.dev, rd.dev, rs.dev, wh.dev, wz.dev, lk.dev, rw.dev}; }
+  int finish() {
+    for (DzBuf<float> *b : {&sp, &sn, &rd, &rs, &wh, &wz, &lk, &rw, &tr})
+      if (int rc = b->finish()) return rc;
+    return 0;
+  }
+};
+
 #pragma GCC visibility push(hidden)
+// map_post.hip: trace[b * stride + off] = sum of rd64[b * ncell .. (b+1) * ncell) for b < nb, one workgroup each, enqueued on the
+// context's stream without a check of its own.  The maps call it per period p with (kmax, p), the model once with (1, 0).
+void dz_mp_trace(dazim_ctx *ctx, int nb, int ncell, int stride, int off, const double *rd64, float *trace);
 // dz_mp_dense's two halves: the factorisation alone (seconds ADDED to sec[0]), and inverse and C (sec[1], sec[2]).  dz_mp_dense is
 // the first followed by the second: the same launches in the same order.
 int dz_mp_factor(dazim_ctx *ctx, int ng, double *Ad, int *flag, bool mfma, const char *lap, double *sec);

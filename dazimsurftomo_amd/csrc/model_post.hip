@@ -55,10 +55,6 @@ __global__ __launch_bounds__(64) void k_mo_gram(int n, const int64_t *colptr, co
   if (t == 0) Aa[a] += d2;
 }
 
-struct MoOut {
-  float *std_post, *std_noise, *rdiag, *rsum, *width_h, *width_z, *leak, *rows;
-};
-
 // Workgroup g takes the unknowns a = g, g + gridDim.x, ...  For one a: t_l = sum_e C_ae l_e for every regularisation row l (one
 // thread per row, ascending e; row a of C is contiguous) into the workgroup's vector tb in memory, then thread t forms
 // Rm_ac = delta_ac - sum_l t_l l_c - damp^2 C_ac for c = t, t + MP_TB, ... over column c's regularisation entries in the transpose
@@ -66,7 +62,7 @@ struct MoOut {
 __global__ __launch_bounds__(MP_TB) void k_mo_rows(int n, int ncell, int nvx, int maxvp, int64_t m_data, int64_t mreg, const int64_t *rowptr,
                                                    const int *col, const float *val, const int64_t *colptr, const int64_t *regstart,
                                                    const int *row, const float *tval, double d2, const double *Cm, const int *flag,
-                                                   const float *depz, MoOut out, int nsel, const int *sel, double *tbuf, double *rd64) {
+                                                   const float *depz, MpOut out, int nsel, const int *sel, double *tbuf, double *rd64) {
   __shared__ double red[MP_TB / 64];
   __shared__ double rdg;
   const int t = threadIdx.x;
@@ -77,18 +73,7 @@ __global__ __launch_bounds__(MP_TB) void k_mo_rows(int n, int ncell, int nvx, in
     if (out.rows)
       for (int s = 0; s < nsel; s++) nmatch += sel[s] == a;
     if (failed) {
-      const float v = nanf("");
-      if (t == 0) {
-        out.std_post[a] = out.std_noise[a] = out.rdiag[a] = out.rsum[a] = v;
-        if (out.width_h) out.width_h[a] = v;
-        if (out.width_z) out.width_z[a] = v;
-        if (out.leak) out.leak[a] = v;
-        rd64[a] = (double)v;
-      }
-      if (nmatch)
-        for (int s = 0; s < nsel; s++)
-          if (sel[s] == a)
-            for (int c = t; c < n; c += MP_TB) out.rows[(size_t)s * n + c] = v;
+      mp_fill_nan(out, (size_t)a, rd64, a, t, nsel, sel, 0, n);
       continue;
     }
     const double *Ca = Cm + (size_t)a * n;
@@ -100,59 +85,25 @@ __global__ __launch_bounds__(MP_TB) void k_mo_rows(int n, int ncell, int nvx, in
     __syncthreads();
     const int blk = a / maxvp, ka = (a % maxvp) / ncell, cella = a % ncell, ia = cella % nvx, ja = cella / nvx;
     const double za = depz ? (double)depz[ka] : 0.0;
-    double rs = 0.0, nv = 0.0, own = 0.0, oth = 0.0, numh = 0.0, numz = 0.0;
+    MpRowSum<true> sum;
     for (int c = t; c < n; c += MP_TB) {
       double r = c == a ? 1.0 : 0.0;
       const int64_t qe = colptr[c + 1];
       for (int64_t q = regstart[c]; q < qe; q++) r -= tb[(int64_t)row[q] - m_data] * (double)tval[q];
       const double cac = Ca[c];
       r -= d2 * cac;
-      rs += r;
-      nv += r * cac;
-      if (c / maxvp == blk) {
-        const int kc = (c % maxvp) / ncell, cc = c % ncell;
-        const double di = (double)(cc % nvx - ia), dj = (double)(cc / nvx - ja);
-        own += r * r;
-        numh += r * r * (di * di + dj * dj);
-        if (depz) {
-          const double dz = (double)depz[kc] - za;
-          numz += r * r * (dz * dz);
-        }
-      } else {
-        oth += r * r;
-      }
+      const int kc = (c % maxvp) / ncell, cc = c % ncell;
+      const double di = (double)(cc % nvx - ia), dj = (double)(cc / nvx - ja), dz = depz ? (double)depz[kc] - za : 0.0;
+      sum.add(r, cac, c / maxvp == blk, di * di + dj * dj, dz * dz);
       if (c == a) rdg = r;
       if (nmatch)
         for (int s = 0; s < nsel; s++)
           if (sel[s] == a) out.rows[(size_t)s * n + c] = (float)r;
     }
-    rs = mp_block_sum(rs, red);
-    nv = mp_block_sum(nv, red);
-    own = mp_block_sum(own, red);
-    oth = mp_block_sum(oth, red);
-    numh = mp_block_sum(numh, red);
-    numz = mp_block_sum(numz, red);
-    if (t == 0) {
-      out.std_post[a] = (float)sqrt(Ca[a]);
-      out.std_noise[a] = (float)sqrt(fmax(nv, 0.0));
-      out.rdiag[a] = (float)rdg;
-      out.rsum[a] = (float)rs;
-      if (out.width_h) out.width_h[a] = own > 0.0 ? (float)sqrt(numh / own) : 0.0f;
-      if (out.width_z) out.width_z[a] = own > 0.0 ? (float)sqrt(numz / own) : 0.0f;
-      if (out.leak) out.leak[a] = own + oth > 0.0 ? (float)(oth / (own + oth)) : 0.0f;
-      rd64[a] = rdg;
-    }
+    sum.reduce(red);
+    if (t == 0) sum.write(out, (size_t)a, Ca[a], rdg, rd64, a);
     __syncthreads();   // (tb and rdg belong to the next unknown from here on)
   }
-}
-
-// trace[blk][k] = sum of Rm_aa over the cells of block blk and knot k (workgroup blk * nlay + k)
-__global__ __launch_bounds__(MP_TB) void k_mo_trace(int ncell, const double *rd64, float *trace) {
-  __shared__ double red[MP_TB / 64];
-  double s = 0.0;
-  for (int c = threadIdx.x; c < ncell; c += MP_TB) s += rd64[(size_t)blockIdx.x * ncell + c];
-  s = mp_block_sum(s, red);
-  if (threadIdx.x == 0) trace[blockIdx.x] = (float)s;
 }
 
 }  // namespace
@@ -176,20 +127,15 @@ extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t
                                      float *trace_u, int *n_failed) {
   if (!ctx || !A || nx < 3 || ny < 3 || nz < 2 || !std_post_u || !std_noise_u || !rdiag_u || !rsum_u)
     return dz_fail(ctx, DAZIM_E_BAD_ARG, "bad arguments to dazim_model_posterior");
-  if (m_data < 0 || m_data > A->m)
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: m_data %lld outside 0..%lld", (long long)m_data, (long long)A->m);
   const int nblk = joint ? 3 : 1, nlay = nz - 1;
   const int64_t ncell64 = (int64_t)(nx - 2) * (ny - 2), n64 = nblk * ncell64 * nlay;
-  if (A->n != n64 || n64 > (int64_t)1 << 30)
-    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: n %lld is not nblk * (nx-2)(ny-2)(nz-1) = %lld", (long long)A->n, (long long)n64);
-  if (!joint && leak_u) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: leak without joint");
-  if ((width_z_u != nullptr) != (depz_u != nullptr)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: width_z and depz go together");
-  if (!(damp >= 0.0f) || !std::isfinite(damp)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: damp negative or not finite");
-  if (nsel < 0 || (nsel > 0 && !sel_u)) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: nsel without sel");
-  if (rows_u && nsel < 1) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: rows without sel");
-  DZ_HIP(hipSetDevice(ctx->device));
   int rc;
-  if ((rc = dz_fmm_finish(ctx)) || (rc = dz_join_aux(ctx))) return rc;
+  if ((rc = dz_post_check_args(ctx, "dazim_model_posterior", A, m_data, A->n == n64 && n64 <= (int64_t)1 << 30, "nblk * (nx-2)(ny-2)(nz-1)", n64, joint != 0,
+                               "joint", leak_u, (width_z_u != nullptr) != (depz_u != nullptr) ? "width_z and depz go together" : nullptr, damp, nsel,
+                               sel_u, rows_u)))
+    return rc;
+  DZ_HIP(hipSetDevice(ctx->device));
+  if ((rc = dz_fmm_finish(ctx)) || (rc = dz_join_aux(ctx))) return rc;   // (what differs from dazim_map_posterior's host side: map_post.hip)
   const int ncell = (int)ncell64, n = (int)n64, maxvp = ncell * nlay, nvx = nx - 2;
   const int64_t m = A->m, mreg = m - m_data;
   // ---- the workspace: refused before the first launch when the card cannot hold it ----
@@ -208,15 +154,11 @@ extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t
   if ((rc = dz_scratch(ctx, "mopost.rd", (size_t)n, &rd64)) || (rc = dz_scratch(ctx, "mopost.reg", (size_t)n, &regstart)) ||
       (rc = dz_scratch(ctx, "mopost.flags", (size_t)2, &flags)))
     return rc;
-  DzBuf<float> sp, sn, rd, rs, wh, wz, lk, rw, tr, dz;
+  MpOutBufs ob;
+  DzBuf<float> dz;
   DzBuf<int> sel;
-  const size_t no = (size_t)n;
   if ((rc = sel.init(ctx, sel_u, (size_t)nsel, true, false)) || (rc = dz.init(ctx, depz_u, depz_u ? (size_t)nlay : 0, true, false)) ||
-      (rc = sp.init(ctx, std_post_u, no, false, true)) || (rc = sn.init(ctx, std_noise_u, no, false, true)) ||
-      (rc = rd.init(ctx, rdiag_u, no, false, true)) || (rc = rs.init(ctx, rsum_u, no, false, true)) ||
-      (rc = wh.init(ctx, width_h_u, width_h_u ? no : 0, false, true)) || (rc = wz.init(ctx, width_z_u, width_z_u ? no : 0, false, true)) ||
-      (rc = lk.init(ctx, leak_u, leak_u ? no : 0, false, true)) || (rc = rw.init(ctx, rows_u, rows_u ? (size_t)nsel * n : 0, false, true)) ||
-      (rc = tr.init(ctx, trace_u, trace_u ? (size_t)nblk * nlay : 0, false, true)))
+      (rc = ob.init(ctx, std_post_u, std_noise_u, rdiag_u, rsum_u, width_h_u, width_z_u, leak_u, rows_u, trace_u, (size_t)n, (size_t)nsel * n, (size_t)nblk * nlay)))
     return rc;
   if (nsel > 0 && (rc = dz_check_range(ctx, sel.dev, nsel, 0, n - 1, "dazim_model_posterior: sel"))) return rc;
   int hflag[2] = {0, 0};
@@ -227,30 +169,26 @@ extern "C" int dazim_model_posterior(dazim_ctx *ctx, const dazim_csr *A, int64_t
   if (hflag[1]) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_model_posterior: a row's columns do not ascend strictly inside 0..n-1");
   const bool mfma = dz_opt(ctx, "map_post.mfma", 1) != 0;
   const double d2 = (double)damp * (double)damp;
-  const MoOut out = {sp.dev, sn.dev, rd.dev, rs.dev, wh.dev, wz.dev, lk.dev, rw.dev};
+  const MpOut out = ob.dev();
   double sec[5] = {0, 0, 0, 0, 0};
   {
     DzTimer t(ctx, "model_post.lap");
     if ((rc = dz_mo_regstart(ctx, A, n, m_data, regstart))) return rc;
     hipLaunchKernelGGL(k_mo_gram, dim3((unsigned)n), dim3(64), 0, ctx->stream, n, A->colptr, A->row, A->tval, A->rowptr, A->col, A->val, d2, Ad);
     DZ_HIP(hipGetLastError());
-    t.stop();
-    sec[0] = ctx->ksec["model_post.lap"];
+    t.lap(sec[0]);
   }
   if ((rc = dz_mp_dense(ctx, n, Ad, Cd, flags, mfma, "model_post.lap", sec + 1))) return rc;
   {
     DzTimer t(ctx, "model_post.lap");
     hipLaunchKernelGGL(k_mo_rows, dim3((unsigned)ngrid), dim3(MP_TB), 0, ctx->stream, n, ncell, nvx, maxvp, m_data, mreg, A->rowptr, A->col, A->val,
                        A->colptr, regstart, A->row, A->tval, d2, Cd, flags, dz.dev, out, nsel, sel.dev, tbuf, rd64);
-    if (tr.dev) hipLaunchKernelGGL(k_mo_trace, dim3((unsigned)(nblk * nlay)), dim3(MP_TB), 0, ctx->stream, ncell, rd64, tr.dev);
+    if (ob.tr.dev) dz_mp_trace(ctx, nblk * nlay, ncell, 1, 0, rd64, ob.tr.dev);
     DZ_HIP(hipGetLastError());
-    t.stop();
-    sec[4] = ctx->ksec["model_post.lap"];
+    t.lap(sec[4]);
   }
   DZ_HIP(hipMemcpyAsync(hflag, flags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = sp.finish()) || (rc = sn.finish()) || (rc = rd.finish()) || (rc = rs.finish()) || (rc = wh.finish()) || (rc = wz.finish()) ||
-      (rc = lk.finish()) || (rc = rw.finish()) || (rc = tr.finish()))
-    return rc;
+  if ((rc = ob.finish())) return rc;
   DZ_HIP(hipStreamSynchronize(ctx->stream));
   if (n_failed) *n_failed = hflag[0] != 0;
   static const char *names[5] = {"model_post.gram", "model_post.factor", "model_post.inverse", "model_post.c", "model_post.rows"};

@@ -354,10 +354,6 @@ struct MtSweep {
   float *x;                    // [K][xstride] in the layout of dm, or nullptr
   size_t xstride;
   double sec[4] = {0, 0, 0, 0};   // gram, factor, solve, inverse
-  void lap(int which, DzTimer &t) {
-    t.stop();
-    sec[which] += ctx->ksec[lapname];
-  }
 };
 
 // g[a] of the view's block into w.g
@@ -388,7 +384,7 @@ int mt_sweep_block(MtSweep &w, const V &v, int64_t m_data, const float *b, Slot 
       DzTimer t(ctx, w.lapname);
       hipLaunchKernelGGL(k_mt_combine<V>, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, (const double *)w.D, s, d2, w.W);
       DZ_HIP(hipGetLastError());
-      w.lap(1, t);
+      t.lap(w.sec[1]);
     }
     if ((rc = dz_mp_factor(ctx, n, w.W, fl, w.mfma, w.lapname, w.sec + 1))) return rc;
     {
@@ -408,7 +404,7 @@ int mt_sweep_block(MtSweep &w, const V &v, int64_t m_data, const float *b, Slot 
       }
       if (w.x) hipLaunchKernelGGL(k_mt_xout<V>, dim3(nvb), dim3(MP_TB), 0, ctx->stream, v, (const double *)w.y, (const int *)fl, w.x + (size_t)k * w.xstride);
       DZ_HIP(hipGetLastError());
-      w.lap(2, t);
+      t.lap(w.sec[2]);
     }
     if (w.want_dof) {
       double s3[3] = {0, 0, 0};
@@ -417,7 +413,7 @@ int mt_sweep_block(MtSweep &w, const V &v, int64_t m_data, const float *b, Slot 
       hipLaunchKernelGGL(k_mt_rowdot, dim3((unsigned)n), dim3(MP_TB), 0, ctx->stream, n, (const double *)w.C, (const double *)w.D, w.rowdot);
       DZ_HIP(hipGetLastError());
       if ((rc = mt_sum(ctx, nblk, n / nblk, 1, n / nblk, w.rowdot, w.sc + MT_DOF))) return rc;
-      w.lap(3, t);
+      t.lap(w.sec[3]);
       w.sec[3] += s3[1] + s3[2];
     }
     if (w.want_ev) {
@@ -425,12 +421,12 @@ int mt_sweep_block(MtSweep &w, const V &v, int64_t m_data, const float *b, Slot 
         DzTimer t(ctx, w.lapname);
         hipLaunchKernelGGL(k_mt_combine<V>, dim3((unsigned)n), dim3(64), 0, ctx->stream, v, (const double *)nullptr, s, d2, w.W);
         DZ_HIP(hipGetLastError());
-        w.lap(1, t);
+        t.lap(w.sec[1]);
       }
       if ((rc = dz_mp_factor(ctx, n, w.W, fl + 1, w.mfma, w.lapname, w.sec + 1))) return rc;
       DzTimer t(ctx, w.lapname);
       if ((rc = mt_logdet_norm(ctx, n, w.W, nullptr, w.sc + MT_LDP, nullptr))) return rc;
-      w.lap(1, t);
+      t.lap(w.sec[1]);
     }
     hipLaunchKernelGGL(k_mt_final, dim3(1), dim3(1), 0, ctx->stream, kp, nblk, m_data, s, d2, w.want_dof, w.want_ev, (const int *)fl,
                        (const double *)w.sc, w.out);
@@ -546,7 +542,7 @@ extern "C" int dazim_model_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t 
     hipLaunchKernelGGL(k_mt_gram_data, dim3((unsigned)n), dim3(64), 0, ctx->stream, n, A->colptr, regstart, A->row, A->tval, A->rowptr, A->col, A->val, w.D);
     if ((rc = mt_mirror(ctx, n, w.D)) || (rc = mt_rhs(w, v, u.bb.dev))) return rc;
     DZ_HIP(hipMemsetAsync(w.W, 0, bA, ctx->stream));   // (the upper triangle of the work matrix is never written or read)
-    w.lap(0, t);
+    t.lap(w.sec[0]);
   }
   if ((rc = mt_sweep_block(w, v, m_data, u.bb.dev, [](int k) { return k; }))) return rc;
   DZ_HIP(hipMemcpyAsync(hflag.data(), w.flags, (size_t)(2 * K) * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -627,7 +623,7 @@ extern "C" int dazim_map_tradeoff(dazim_ctx *ctx, const dazim_csr *A, int64_t m_
       if ((rc = dz_mp_gram(ctx, ng, ncell, kn, p, ndat, lp, span, A, 0.0, w.D)) || (rc = mt_mirror(ctx, ng, w.D))) return rc;
       grams++;
       if ((rc = mt_rhs(w, v, u.bb.dev))) return rc;
-      w.lap(0, t);
+      t.lap(w.sec[0]);
     }
     if ((rc = mt_sweep_block(w, v, (int64_t)ndat, u.bb.dev, [=](int k) { return k * kmax + p; }))) return rc;
   }

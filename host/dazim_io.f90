@@ -8,7 +8,7 @@ module dazim_io
   private
   public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
   public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
-  public :: write_resolution, uncertainty_weights, tradeoff_factor, write_tradeoff, write_map_tradeoff
+  public :: write_resolution, uncertainty_weights, tradeoff_factor, write_tradeoff, write_map_tradeoff, write_uncertainty, median
   public :: period_type, type_name
 
   real, parameter :: pi = 3.1415926535898
@@ -430,6 +430,79 @@ contains
 
   ! optional numeric command-line argument n: v keeps its value when there are fewer than n arguments; text that is not a
   ! number ends the program
+  ! The uncertainty file of a posterior entry and the lines of stdout and the log (unit 66), for the 3-D model (axis 'depth', names
+  ! 'Vs Gc Gs', ncol 6) and the maps ('period', 'c a1 a2', 5).  upost(:, 1:ncol): std_post, std_noise, rdiag, rsum and the width(s),
+  ! upost(:, ncol+1) the leak, per unknown blk*size(axis)*ncell + (k-1)*ncell + (j-1)*(nx-2) + i; utrace per axis value and block.
+  ! each_axis: an axis value is not factored where its trace is NaN, and the count nbad gets a line; otherwise nbad > 0 marks them all.
+  subroutine write_uncertainty(fname, p, entry, axis_word, axis, names, ncol, upost, utrace, nbad, each_axis)
+    character(len=*), intent(in) :: fname, entry, axis_word, names
+    type(para_t), intent(in) :: p
+    real*8, intent(in) :: axis(:)
+    integer, intent(in) :: ncol, nbad
+    real, intent(in) :: upost(:, :), utrace(:, :)
+    logical, intent(in) :: each_axis
+    integer :: k1, j1, i1, q, u, ncell, nb
+    character(len=:), allocatable :: head, one
+    ncell = (p%nx - 2)*(p%ny - 2)
+    nb = size(axis)*ncell
+    head = ' uncertainty '//axis_word
+    one = names(1:index(names, ' ') - 1)
+    open (44, file=fname, status='replace', action='write')
+    do k1 = 1, size(axis)
+      do j1 = 1, p%ny - 2
+        do i1 = 1, p%nx - 2
+          q = (k1 - 1)*ncell + (j1 - 1)*(p%nx - 2) + i1
+          if (size(utrace, 2) == 1) then
+            write (44, '(3f10.4,6es14.5)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, axis(k1), upost(q, 1:ncol)
+          else
+            write (44, '(3f10.4,11es14.5)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, axis(k1), upost(q, 1:ncol), &
+              upost(nb + q, 1), upost(nb + q, 3), upost(2*nb + q, 1), upost(2*nb + q, 3), upost(q, ncol + 1)
+          end if
+        end do
+      end do
+    end do
+    close (44)
+    do u = 6, 66, 60
+      write (u, '(a)') ' uncertainty: posterior std and resolution of the last linearised step ('//entry//')'
+      do k1 = 1, size(axis)
+        q = (k1 - 1)*ncell
+        if (merge(utrace(k1, 1) /= utrace(k1, 1), nbad > 0, each_axis)) then
+          write (u, '(a,f8.2,a)') head, axis(k1), ': not factored'
+        else if (size(utrace, 2) == 1) then
+          write (u, '(a,f8.2,a,f9.5,a,es12.4)') head, axis(k1), ': trace(Rm)/ncell '//one, utrace(k1, 1)/ncell, &
+            '  median std_post '//one, median(upost(q + 1:q + ncell, 1))
+        else
+          write (u, '(a,f8.2,a,3f9.5,a,es12.4,a,f8.4)') head, axis(k1), ': trace(Rm)/ncell '//names, utrace(k1, :)/ncell, &
+            '  median std_post '//one, median(upost(q + 1:q + ncell, 1)), '  median leak '//one, median(upost(q + 1:q + ncell, ncol + 1))
+        end if
+      end do
+      if (each_axis .and. nbad > 0) write (u, '(a,i4)') ' uncertainty: '//axis_word//'s not factored', nbad
+    end do
+  end subroutine
+
+  ! the median of v (the lower of the two middle values for an even count), by a Shell sort of a copy
+  real function median(v)
+    real, intent(in) :: v(:)
+    real, allocatable :: s(:)
+    real :: x
+    integer :: m, gap, i2, j2
+    s = v
+    m = size(s)
+    gap = m/2
+    do while (gap > 0)
+      do i2 = gap + 1, m
+        x = s(i2); j2 = i2
+        do while (j2 > gap)
+          if (s(j2 - gap) <= x) exit
+          s(j2) = s(j2 - gap); j2 = j2 - gap
+        end do
+        s(j2) = x
+      end do
+      gap = gap/2
+    end do
+    median = s((m + 1)/2)
+  end function
+
   subroutine int_arg(n, v)
     integer, intent(in) :: n
     integer, intent(inout) :: v

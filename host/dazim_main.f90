@@ -72,7 +72,7 @@ program DAzimSurfTomo_amd
   real(8) :: tph(9) = 0                      ! wall seconds per phase, printed when DAZIM_TIMING is set (tools/run_test4_program.sh)
   character(len=8) :: timing_env
   ! uncertainty = 1
-  integer :: iunc, ngpu_env, nblk_u, ncell_u, q_u
+  integer :: iunc, ngpu_env, nblk_u
   integer(c_int) :: nbad
   character(len=32) :: ngpu_val
   real, allocatable, target :: upost(:, :), utrace(:, :), udepz(:)
@@ -463,7 +463,9 @@ program DAzimSurfTomo_amd
   call write_phase_map('phaseV_FWD.dat', p, tRcV)
   write (*, '(a)') '  Begin forward calculate period azimuthal A1, A2.'
   call write_period_azimuthal('period_Azm_tomo.inv', p, Lsen_Gsc, gcf, gsf, tRcV)
-  if (iunc == 1 .and. allocated(upost)) call write_uncertainty()
+  if (iunc == 1 .and. allocated(upost)) &   ! (nbad > 0: the one matrix was not factored, so no depth is)
+    call write_uncertainty('model_uncertainty.dat', p, 'dazim_model_posterior', 'depth', real(depz(1:nz - 1), 8), 'Vs Gc Gs', 6, upost, utrace, &
+                           int(nbad), .false.)
   write (66, *) '  -----------------------------------------------------------'
   write (*, *) '  Program finishes successfully'
   write (66, *) '  Program finishes successfully'
@@ -529,66 +531,6 @@ contains
     end do
     close (45)
   end subroutine
-
-  ! model_uncertainty.dat and the log's lines from dazim_model_posterior's arrays (upost: std_post, std_noise, rdiag, rsum, width_h,
-  ! width_z, leak per unknown blk*maxvp + (k-1)*ncell + (j-1)*(nx-2) + i; utrace per knot and block)
-  subroutine write_uncertainty()
-    integer :: k1, j1, i1, u
-    ncell_u = (nx - 2)*(ny - 2)
-    open (44, file='model_uncertainty.dat', status='replace', action='write')
-    do k1 = 1, nz - 1
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          q_u = (k1 - 1)*ncell_u + (j1 - 1)*(nx - 2) + i1
-          if (iso_mod) then
-            write (44, '(3f10.4,6es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1), upost(q_u, 1:6)
-          else
-            write (44, '(3f10.4,11es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, depz(k1), upost(q_u, 1:6), &
-              upost(maxvp + q_u, 1), upost(maxvp + q_u, 3), upost(2*maxvp + q_u, 1), upost(2*maxvp + q_u, 3), upost(q_u, 7)
-          end if
-        end do
-      end do
-    end do
-    close (44)
-    do u = 6, 66, 60
-      write (u, '(a)') ' uncertainty: posterior std and resolution of the last linearised step (dazim_model_posterior)'
-      do k1 = 1, nz - 1
-        if (nbad > 0) then
-          write (u, '(a,f8.2,a)') ' uncertainty depth', depz(k1), ': not factored'
-        else if (iso_mod) then
-          write (u, '(a,f8.2,a,f9.5,a,es12.4)') ' uncertainty depth', depz(k1), ': trace(Rm)/ncell Vs', utrace(k1, 1)/ncell_u, &
-            '  median std_post Vs', median(upost((k1 - 1)*ncell_u + 1:k1*ncell_u, 1))
-        else
-          write (u, '(a,f8.2,a,3f9.5,a,es12.4,a,f8.4)') ' uncertainty depth', depz(k1), ': trace(Rm)/ncell Vs Gc Gs', &
-            utrace(k1, :)/ncell_u, '  median std_post Vs', median(upost((k1 - 1)*ncell_u + 1:k1*ncell_u, 1)), '  median leak Vs', &
-            median(upost((k1 - 1)*ncell_u + 1:k1*ncell_u, 7))
-        end if
-      end do
-    end do
-  end subroutine
-
-  ! the median of v (the lower of the two middle values for an even count), by a Shell sort of a copy
-  real function median(v)
-    real, intent(in) :: v(:)
-    real, allocatable :: s(:)
-    real :: x
-    integer :: mm, gap, i2, j2
-    s = v
-    mm = size(s)
-    gap = mm/2
-    do while (gap > 0)
-      do i2 = gap + 1, mm
-        x = s(i2); j2 = i2
-        do while (j2 > gap)
-          if (s(j2 - gap) <= x) exit
-          s(j2) = s(j2 - gap); j2 = j2 - gap
-        end do
-        s(j2) = x
-      end do
-      gap = gap/2
-    end do
-    median = s((mm + 1)/2)
-  end function
 
   ! scaled 2-norm like the reference's dnrm2 (inv/lsmrblas.f90:247)
   real function nrm2(nn, x)

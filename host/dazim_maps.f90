@@ -213,39 +213,8 @@ program SurfPhaseMaps_amd
     end do
   end do
   close (43)
-  if (iunc == 1) then
-    open (44, file='period_map_uncertainty.dat', status='replace', action='write')
-    do t1 = 1, kmax
-      do j1 = 1, ny - 2
-        do i1 = 1, nx - 2
-          q = (t1 - 1)*ncell + (j1 - 1)*(nx - 2) + i1
-          if (iso_mod) then
-            write (44, '(3f10.4,5es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), upost(q, 1:5)
-          else
-            write (44, '(3f10.4,10es14.5)') gozd + (j1 - 1)*dvzd, goxd - (i1 - 1)*dvxd, tRc(t1), upost(q, 1:5), &
-              upost(kmax*ncell + q, 1), upost(kmax*ncell + q, 3), upost(2*kmax*ncell + q, 1), upost(2*kmax*ncell + q, 3), upost(q, 6)
-          end if
-        end do
-      end do
-    end do
-    close (44)
-    do q = 6, 66, 60
-      write (q, '(a)') ' uncertainty: posterior std and resolution of the last linearised step (dazim_map_posterior)'
-      do t1 = 1, kmax
-        if (utrace(t1, 1) /= utrace(t1, 1)) then
-          write (q, '(a,f8.2,a)') ' uncertainty period', tRc(t1), ': not factored'
-        else if (iso_mod) then
-          write (q, '(a,f8.2,a,f9.5,a,es12.4)') ' uncertainty period', tRc(t1), ': trace(Rm)/ncell c', utrace(t1, 1)/ncell, &
-            '  median std_post c', median(upost((t1 - 1)*ncell + 1:t1*ncell, 1))
-        else
-          write (q, '(a,f8.2,a,3f9.5,a,es12.4,a,f8.4)') ' uncertainty period', tRc(t1), ': trace(Rm)/ncell c a1 a2', utrace(t1, :)/ncell, &
-            '  median std_post c', median(upost((t1 - 1)*ncell + 1:t1*ncell, 1)), '  median leak c', &
-            median(upost((t1 - 1)*ncell + 1:t1*ncell, 6))
-        end if
-      end do
-      if (nbad > 0) write (q, '(a,i4)') ' uncertainty: periods not factored', nbad
-    end do
-  end if
+  if (iunc == 1) &                            ! (a period is not factored where its trace is NaN)
+    call write_uncertainty('period_map_uncertainty.dat', p, 'dazim_map_posterior', 'period', tRc, 'c a1 a2', 5, upost, utrace, int(nbad), .true.)
   write (*, *) '  Program finishes successfully'
   write (66, *) '  Program finishes successfully'
   close (66)
@@ -302,27 +271,4 @@ contains
     end do
     close (45)
   end subroutine
-
-  ! the median of v (the lower of the two middle values for an even count), by a Shell sort of a copy
-  real function median(v)
-    real, intent(in) :: v(:)
-    real, allocatable :: s(:)
-    real :: x
-    integer :: m, gap, i2, j2
-    s = v
-    m = size(s)
-    gap = m/2
-    do while (gap > 0)
-      do i2 = gap + 1, m
-        x = s(i2); j2 = i2
-        do while (j2 > gap)
-          if (s(j2 - gap) <= x) exit
-          s(j2) = s(j2 - gap); j2 = j2 - gap
-        end do
-        s(j2) = x
-      end do
-      gap = gap/2
-    end do
-    median = s((m + 1)/2)
-  end function
 end program

@@ -4,6 +4,7 @@ the independent reference (numpy.linalg.inv(A), inv(A) @ K^T W^2 K and, for the 
 cells of a kernel table laid out as dazim_column_lsq reads it."""
 import numpy as np
 
+from tests import dense_ref
 from tests.test_column_lsq_gpu import depth_rule
 
 OUTPUTS = ("std_post", "std_noise", "rdiag", "rsum", "width", "rows", "trace")
@@ -39,16 +40,10 @@ def route(K, w, smooth, damp, depz=None):
     n = K.shape[1]
     P = penalty(n, smooth, damp)
     A = (K * (w * w)[:, None]).T @ K + P
-    R = np.tril(A)
-    for c in range(n):                                   # right-looking Cholesky, column c
-        if not (np.isfinite(R[c, c]) and R[c, c] > 0):
-            return None
-        R[c, c] = np.sqrt(R[c, c])
-        R[c + 1:, c] /= R[c, c]
-        R[c + 1:, c + 1:] -= np.tril(np.outer(R[c + 1:, c], R[c + 1:, c]))
-    M = np.zeros((n, n))                                 # M = R^-1: every column by forward substitution on its unit vector
-    for i in range(n):
-        M[i, :i + 1] = ((np.arange(i + 1) == i) - R[i, :i] @ M[:i, :i + 1]) / R[i, i]
+    R = dense_ref.cholesky(A)
+    if R is None:
+        return None
+    M = dense_ref.inverse_factor(R)
     C = M.T @ M
     Rm = np.eye(n) - C @ P
     # (Rm C)_aa = (C K^T W^2 K C)_aa as the sum of squares sum_p w_p^2 (C k_p)_a^2: the difference C - C P C loses what is small

@@ -4,6 +4,8 @@ kernels (right-looking Cholesky, M = R^-1 by forward substitution, C = M^T M, Rm
 by one and the damping last).  Both return the arrays of Context.map_posterior in fp64."""
 import numpy as np
 
+from tests import dense_ref
+
 PER_UNKNOWN = ("std_post", "std_noise", "rdiag", "rsum", "width", "leak")
 OUTPUTS = PER_UNKNOWN + ("trace", "rows")
 
@@ -162,18 +164,13 @@ def derived(prob, per_period, sel):
     out["n_failed"] = 0
     blk = np.arange(ng) // ncell
     ci, cj = (np.arange(ng) % ncell) % nvx, (np.arange(ng) % ncell) // nvx
-    d2 = (ci[None, :] - ci[:, None]) ** 2 + (cj[None, :] - cj[:, None]) ** 2
-    same = blk[None, :] == blk[:, None]
     for p, one in enumerate(per_period):
         if one is None:
             out["n_failed"] += 1
             continue
         C, Rm = one
-        sq = Rm ** 2
-        own, alls = (sq * same).sum(axis=1), sq.sum(axis=1)
-        vals = dict(std_post=np.sqrt(np.diag(C)), std_noise=np.sqrt(np.maximum(np.einsum("ac,ca->a", Rm, C), 0.0)), rdiag=np.diag(Rm).copy(),
-                    rsum=Rm.sum(axis=1), width=np.where(own > 0, np.sqrt((sq * same * d2).sum(axis=1) / np.where(own > 0, own, 1.0)), 0.0),
-                    leak=np.where(alls > 0, (sq * ~same).sum(axis=1) / np.where(alls > 0, alls, 1.0), 0.0))
+        vals = dense_ref.per_unknown(C, Rm, blk, ci, cj)
+        vals["width"] = vals.pop("width_h")
         for k, v in vals.items():
             out[k][:, p] = v.reshape(nblk, nvy, nvx)
         out["trace"][:, p] = np.diag(Rm).reshape(nblk, ncell).sum(axis=1)
@@ -205,26 +202,12 @@ def linalg(prob, sel=None):
 def route(prob, sel=None):
     per = []
     for D, L, _ in groups(prob):
-        n = len(D)
-        R = np.tril(normal_matrix(prob, D, L))
-        ok = True
-        for c in range(n):                                   # right-looking Cholesky, column c
-            if not (np.isfinite(R[c, c]) and R[c, c] > 0):
-                ok = False
-                break
-            R[c, c] = np.sqrt(R[c, c])
-            R[c + 1:, c] /= R[c, c]
-            R[c + 1:, c + 1:] -= np.tril(np.outer(R[c + 1:, c], R[c + 1:, c]))
-        if not ok:
+        R = dense_ref.cholesky(normal_matrix(prob, D, L))
+        if R is None:
             per.append(None)
             continue
-        M = np.zeros((n, n))                                 # M = R^-1, row by row (forward substitution on every unit vector)
-        for i in range(n):
-            M[i, :i + 1] = ((np.arange(i + 1) == i) - R[i, :i] @ M[:i, :i + 1]) / R[i, i]
-        C = np.zeros((n, n))                                 # C_ac = sum_{i >= max(a, c)} M_ia M_ic, ascending i
-        for i in range(n):
-            C[:i + 1, :i + 1] += np.outer(M[i, :i + 1], M[i, :i + 1])
-        Rm = np.eye(n)
+        C = dense_ref.gram_of_inverse(dense_ref.inverse_factor(R))
+        Rm = np.eye(len(D))
         for l in L:                                          # the regularisation rows one by one, ascending, every row a at once
             e = np.flatnonzero(l)
             t = C[:, e] @ l[e]
@@ -234,16 +217,5 @@ def route(prob, sel=None):
     return derived(prob, per, sel)
 
 
-def worst(got, ref):
-    """per output max |got - ref| / max(1, max |ref|) over the finite reference values; NaN must sit where the reference has NaN"""
-    res = {}
-    for k in OUTPUTS:
-        if ref[k] is None:
-            assert got[k] is None, k
-            continue
-        g, r = np.asarray(got[k], np.float64), np.asarray(ref[k], np.float64)
-        assert g.shape == r.shape, (k, g.shape, r.shape)
-        bad = np.isnan(r)
-        assert np.array_equal(np.isnan(g), bad), k
-        res[k] = float(np.abs(g - r)[~bad].max() / max(1.0, np.abs(r[~bad]).max())) if (~bad).any() else 0.0
-    return res
+def worst(got, ref, keys=OUTPUTS):
+    return dense_ref.worst(got, ref, keys)

@@ -155,5 +155,4 @@ def brute_evidence(G, b, P):
 
 
 def worst(got, ref, keys=OUTPUTS):
-    """per output max |got - ref| / max(1, max |ref|) over the finite reference values; NaN must sit where the reference has NaN"""
     return tref.worst(got, ref, keys)

@@ -4,6 +4,8 @@ tests run on.  `linalg` is the independent reference (numpy.linalg.inv of the no
 the damping last).  Both return the arrays of Context.model_posterior in fp64."""
 import numpy as np
 
+from tests import dense_ref
+
 PER_UNKNOWN = ("std_post", "std_noise", "rdiag", "rsum", "width_h", "width_z", "leak")
 OUTPUTS = PER_UNKNOWN + ("trace", "rows")
 
@@ -169,18 +171,7 @@ def derived(prob, one, sel):
         C, Rm = one
         a = np.arange(n)
         blk, k, cell = a // maxvp, (a % maxvp) // ncell, a % ncell
-        ci, cj, z = cell % nvx, cell // nvx, prob["depz"].astype(np.float64)[k]
-        dh = (ci[None, :] - ci[:, None]) ** 2 + (cj[None, :] - cj[:, None]) ** 2
-        dz = (z[None, :] - z[:, None]) ** 2
-        same = blk[None, :] == blk[:, None]
-        sq = Rm ** 2
-        own, alls = (sq * same).sum(axis=1), sq.sum(axis=1)
-        safe = np.where(own > 0, own, 1.0)
-        vals = dict(std_post=np.sqrt(np.diag(C)), std_noise=np.sqrt(np.maximum(np.einsum("ac,ca->a", Rm, C), 0.0)), rdiag=np.diag(Rm).copy(),
-                    rsum=Rm.sum(axis=1), width_h=np.where(own > 0, np.sqrt((sq * same * dh).sum(axis=1) / safe), 0.0),
-                    width_z=np.where(own > 0, np.sqrt((sq * same * dz).sum(axis=1) / safe), 0.0),
-                    leak=np.where(alls > 0, (sq * ~same).sum(axis=1) / np.where(alls > 0, alls, 1.0), 0.0))
-        for key, val in vals.items():
+        for key, val in dense_ref.per_unknown(C, Rm, blk, cell % nvx, cell // nvx, prob["depz"].astype(np.float64)[k]).items():
             out[key] = val.reshape(shape)
         out["trace"] = np.diag(Rm).reshape(nblk, nlay, ncell).sum(axis=2)
         if sel is not None:
@@ -204,19 +195,10 @@ def linalg(prob, sel=None):
 def route(prob, sel=None):
     D, L = parts(prob)
     n = len(D)
-    R = np.tril(normal_matrix(prob, D, L))
-    for c in range(n):                                   # right-looking Cholesky, column c
-        if not (np.isfinite(R[c, c]) and R[c, c] > 0):
-            return derived(prob, None, sel)
-        R[c, c] = np.sqrt(R[c, c])
-        R[c + 1:, c] /= R[c, c]
-        R[c + 1:, c + 1:] -= np.tril(np.outer(R[c + 1:, c], R[c + 1:, c]))
-    M = np.zeros((n, n))                                 # M = R^-1, row by row (forward substitution on every unit vector)
-    for i in range(n):
-        M[i, :i + 1] = ((np.arange(i + 1) == i) - R[i, :i] @ M[:i, :i + 1]) / R[i, i]
-    C = np.zeros((n, n))                                 # C_ac = sum_{i >= max(a, c)} M_ia M_ic, ascending i
-    for i in range(n):
-        C[:i + 1, :i + 1] += np.outer(M[i, :i + 1], M[i, :i + 1])
+    R = dense_ref.cholesky(normal_matrix(prob, D, L))
+    if R is None:
+        return derived(prob, None, sel)
+    C = dense_ref.gram_of_inverse(dense_ref.inverse_factor(R))
     T = C @ L.T                                          # t_l of every unknown a: T[a, l] = sum_e C_ae l_e
     Rm = np.eye(n)
     for c in range(n):                                   # the gather: column c's regularisation entries, ascending rows
@@ -227,15 +209,4 @@ def route(prob, sel=None):
 
 
 def worst(got, ref, keys=OUTPUTS):
-    """per output max |got - ref| / max(1, max |ref|) over the finite reference values; NaN must sit where the reference has NaN"""
-    res = {}
-    for k in keys:
-        if ref[k] is None:
-            assert got[k] is None, k
-            continue
-        g, r = np.asarray(got[k], np.float64), np.asarray(ref[k], np.float64)
-        assert g.shape == r.shape, (k, g.shape, r.shape)
-        bad = np.isnan(r)
-        assert np.array_equal(np.isnan(g), bad), k
-        res[k] = float(np.abs(g - r)[~bad].max() / max(1.0, np.abs(r[~bad]).max())) if (~bad).any() else 0.0
-    return res
+    return dense_ref.worst(got, ref, keys)

@@ -4,6 +4,7 @@ model_posterior_ref's shapes and regularisers with a right-hand side b = G x_tru
 log N(b; 0, I + G P^-1 G^T) without the closed form, `pick` the three rules of dazim_tradeoff_pick."""
 import numpy as np
 
+from tests import dense_ref
 from tests import model_posterior_ref as mref
 
 SCALES = (0.25, 0.5, 1.0, 2.0, 4.0)
@@ -173,11 +174,5 @@ def check_pick(fn):
 
 
 def worst(got, ref, keys=OUTPUTS):
-    """per output max |got - ref| / max(1, max |ref|) over the finite reference values; NaN must sit where the reference has NaN"""
-    res = {}
-    for k in keys:
-        g, r = np.asarray(got[k], np.float64).reshape(np.shape(ref[k])), np.asarray(ref[k], np.float64)
-        bad = np.isnan(r)
-        assert np.array_equal(np.isnan(g), bad), k
-        res[k] = float(np.abs(g - r)[~bad].max() / max(1.0, np.abs(r[~bad]).max())) if (~bad).any() else 0.0
-    return res
+    """dense_ref.worst with every output taken in the reference's layout (x [K][n], and the maps' arrays against the model's)"""
+    return dense_ref.worst(got, ref, keys, reshaped=keys)

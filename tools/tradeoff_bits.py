@@ -1,5 +1,5 @@
-"""Every array the two trade-off sweeps and the two posterior entries return on the tests' problems, for a byte comparison of two
-builds of the library (profiles/tradeoff_sweep_refactor.md).
+"""Every array the two trade-off sweeps return on the tests' problems, for a byte comparison of two builds of the library
+(profiles/tradeoff_sweep_refactor.md; tools/posterior_bits.py does the same for the two posterior entries).
 
     DAZIM_LIB=<one build> python tools/tradeoff_bits.py --out a.npz
     DAZIM_LIB=<other build> python tools/tradeoff_bits.py --out b.npz
@@ -8,8 +8,8 @@ builds of the library (profiles/tradeoff_sweep_refactor.md).
 One process per library.  The problems are those of tests/test_map_tradeoff_gpu.py and tests/test_model_tradeoff_gpu.py (CASES x REGS
 with the sweep of their `case`), the long-row problems of tests/test_long_rows_gpu.py, and the period that cannot be factored, the
 prior that is not positive definite and the period without data; the sweeps with dof and the evidence, without either, with x, and
-with the option map_post.mfma at 1 and 0; dazim_map_posterior and dazim_model_posterior on the same matrices.  --compare names every
-array whose bytes differ (NaNs count by their bit pattern) and exits with 1 if there is one."""
+with the option map_post.mfma at 1 and 0.  --compare names every array whose bytes differ (NaNs count by their bit pattern) and exits
+with 1 if there is one."""
 import argparse
 import os
 import sys
@@ -52,24 +52,18 @@ def record(store):
     from tests import map_tradeoff_ref as ptref
     from tests import model_posterior_ref as mref
     from tests import model_tradeoff_ref as mtref
-    from tests import test_map_posterior_gpu as mp
     from tests import test_map_tradeoff_gpu as mpt
-    from tests import test_model_posterior_gpu as mo
     from tests import test_model_tradeoff_gpu as mt
     ctx = dz.Context(0)
 
-    def maps(tag, prob, scale, damp, post=True, tiles=(1, 0)):
+    def maps(tag, prob, scale, damp, tiles=(1, 0)):
         A = mpt.matrix(ctx, prob)
         sweeps(ctx, store, tag, lambda s, d, **kw: mpt.call(ctx, A, prob, s, d, **kw), scale, damp, tiles)
-        if post:
-            keep(store, f"{tag}/post", mp.call(ctx, A, prob, mp.some_sel(prob)), pref.OUTPUTS + ("n_failed",))
         A.free()
 
-    def model(tag, prob, scale, damp, post=True, tiles=(1, 0)):
+    def model(tag, prob, scale, damp, tiles=(1, 0)):
         A = mt.matrix(ctx, prob)
         sweeps(ctx, store, tag, lambda s, d, **kw: mt.call(ctx, A, prob, s, d, **kw), scale, damp, tiles)
-        if post:
-            keep(store, f"{tag}/post", mo.call(ctx, A, prob, mo.some_sel(prob["n"])), mref.OUTPUTS + ("n_failed",))
         A.free()
 
     for (shape, azim, kmax), cid in zip(mpt.CASES, mpt.CASE_IDS):
@@ -88,13 +82,13 @@ def record(store):
             maps(f"map/long-{int(mode)}-dead{int(through_dead)}", prob, *ptref.sweep(prob, (1.0,)))
     ones, holes = np.ones((3, 3), np.float32), np.array([0.5, 0.0, 0.3], np.float32)
     semi = np.array([[1, 1, 1], [1, 0, 1], [2, 2, 2]], np.float32), np.array([0.3, 0.0, 0.3], np.float32)
-    maps("map/unfactorable", ptref.problem(9, 5, 3, True, (0.8, 0.0), no_reg_period=1), ones, holes, post=False)
-    maps("map/semidefinite", ptref.problem(3, 3, 3, True, (0.7, 0.3)), *semi, post=False)
+    maps("map/unfactorable", ptref.problem(9, 5, 3, True, (0.8, 0.0), no_reg_period=1), ones, holes)
+    maps("map/semidefinite", ptref.problem(3, 3, 3, True, (0.7, 0.3)), *semi)
     prob = ptref.without_data(ptref.problem(9, 5, 3, True, pref.REGS[0]), 1)
     scale, damp = ptref.sweep(prob)
-    maps("map/no-data", prob, scale[:5], damp[:5], post=False)
-    model("model/unfactorable", mtref.problem((9, 5, 3), True, (0.0, 0.5)), ones, holes, post=False)
-    model("model/semidefinite", mtref.problem((3, 3, 2), True, (0.7, 0.3)), *semi, post=False)
+    maps("map/no-data", prob, scale[:5], damp[:5])
+    model("model/unfactorable", mtref.problem((9, 5, 3), True, (0.0, 0.5)), ones, holes)
+    model("model/semidefinite", mtref.problem((3, 3, 2), True, (0.7, 0.3)), *semi)
     ctx.close()
 
 
