@@ -512,6 +512,67 @@ class Context:
         out["n_empty"], out["n_failed"] = ne.value, nf.value
         return out
 
+    @staticmethod
+    def _radial_args(nlay, kern_v, kern_h, *f32):
+        """what column_lsq_radial and column_resolution_radial pass alike: (kv, kh, whether the arrays are torch-cuda, kern_v, kern_h, the fp32 arrays), NumPy
+        arrays made contiguous; a kernel table that is None or has no period counts as absent"""
+        absent = lambda k: k is None or k.shape[1] == 0
+        kern_v, kern_h = (None if absent(k) else k for k in (kern_v, kern_h))
+        on_dev = any(a is not None and _is_torch(a) for a in (kern_v, kern_h))
+        if not on_dev:
+            kern_v, kern_h = (None if k is None else np.ascontiguousarray(k, np.float64) for k in (kern_v, kern_h))
+            f32 = [None if a is None else np.ascontiguousarray(a, np.float32) for a in f32]
+        for k in (kern_v, kern_h):
+            assert k is None or k.shape[0] >= nlay
+        return (0 if kern_v is None else kern_v.shape[1], 0 if kern_h is None else kern_h.shape[1], on_dev, kern_v, kern_h, *f32)
+
+    def column_lsq_radial(self, nx, ny, nlay, kern_v, kern_h, rhs_v, rhs_h, w_v=None, w_h=None, d0=None, smooth=0.0, damp=0.0,
+                          couple=0.0):
+        """Vsv and Vsh updates per inner cell, tied by a prior towards isotropy (dazim_column_lsq_radial): kern_v[>=nlay][kv][nx*ny]
+        over the Rayleigh periods, kern_h[>=nlay][kh][nx*ny] over the Love periods (fp64; None for a wave type without periods),
+        rhs_* and w_*[kv|kh][ny-2][nx-2] (w None: all ones), d0[nlay][ny-2][nx-2] the current Vsh - Vsv (None: 0).
+        Returns (x[2][nlay][ny-2][nx-2] fp32 = dVsv, dVsh, n_empty, stats[kv+kh][2], the Rayleigh periods first)."""
+        kv, kh, on_dev, kern_v, kern_h, rhs_v, rhs_h, w_v, w_h, d0 = self._radial_args(nlay, kern_v, kern_h, rhs_v, rhs_h, w_v, w_h, d0)
+        if on_dev:
+            import torch
+            x = torch.empty((2, nlay, ny - 2, nx - 2), dtype=torch.float32, device=(kern_v if kv else kern_h).device)
+        else:
+            x = np.zeros((2, nlay, ny - 2, nx - 2), np.float32)
+        ne = C.c_int(0)
+        st = np.zeros((kv + kh, 2), np.float32)
+        f32 = lambda a: _ptr(a, np.float32)
+        self._check(self.lib.dazim_column_lsq_radial(self._h, nx, ny, int(nlay), kv, _ptr(kern_v, np.float64), kh, _ptr(kern_h, np.float64),
+                                                     f32(rhs_v if kv else None), f32(rhs_h if kh else None), f32(w_v if kv else None),
+                                                     f32(w_h if kh else None), f32(d0), C.c_float(smooth), C.c_float(damp),
+                                                     C.c_float(couple), f32(x), C.byref(ne), _ptr(st)))
+        return x, ne.value, st
+
+    def column_resolution_radial(self, nx, ny, nlay, kern_v, kern_h, w_v=None, w_h=None, smooth=0.0, damp=0.0, couple=0.0, rows=False):
+        """posterior std, Vsv-Vsh covariance and resolution of column_lsq_radial's problem per inner cell and knot
+        (dazim_column_resolution_radial), arguments as there.  numpy in -> numpy out, torch-cuda kernels -> torch-cuda arrays.
+        Returns a dict: std, rdiag, rsum, cross [2][nlay][ny-2][nx-2] (Vsv, then Vsh); cov_vh [nlay][ny-2][nx-2]; trace
+        [2][ny-2][nx-2]; rows [2 nlay][2 nlay][ny-2][nx-2] (None unless asked); n_empty, n_failed."""
+        kv, kh, on_dev, kern_v, kern_h, w_v, w_h = self._radial_args(nlay, kern_v, kern_h, w_v, w_h)
+        if on_dev:
+            import torch
+            dev = (kern_v if kv else kern_h).device
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        else:
+            new = lambda *shape: np.zeros(shape, np.float32)
+        out = {k: new(2, nlay, ny - 2, nx - 2) for k in ("std", "rdiag", "rsum", "cross")}
+        out["cov_vh"] = new(nlay, ny - 2, nx - 2)
+        out["trace"] = new(2, ny - 2, nx - 2)
+        out["rows"] = new(2 * nlay, 2 * nlay, ny - 2, nx - 2) if rows else None
+        ne, nf = C.c_int(0), C.c_int(0)
+        f32 = lambda a: _ptr(a, np.float32)
+        self._check(self.lib.dazim_column_resolution_radial(self._h, nx, ny, int(nlay), kv, _ptr(kern_v, np.float64), kh,
+                                                            _ptr(kern_h, np.float64), f32(w_v if kv else None), f32(w_h if kh else None),
+                                                            C.c_float(smooth), C.c_float(damp), C.c_float(couple),
+                                                            *[f32(out[k]) for k in ("std", "cov_vh", "rdiag", "rsum", "cross", "trace", "rows")],
+                                                            C.byref(ne), C.byref(nf)))
+        out["n_empty"], out["n_failed"] = ne.value, nf.value
+        return out
+
     def map_posterior(self, A, m_data, nx, ny, kmax, azim, damp, sel=None, width=True):
         """posterior std and resolution of the per-period maps (dazim_map_posterior) from the matrix lsmr is given: A a SparseMatrix
         whose first m_data rows are the weighted data rows, damp lsmr's damping, sel local indices blk*ncell + cell whose rows of

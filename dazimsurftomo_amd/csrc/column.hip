@@ -234,6 +234,12 @@ __global__ __launch_bounds__(CL_WAVE) void k_column_res(int nx, int ny, int n, i
 
 }  // namespace
 
+int dz_column_stats(dazim_ctx *ctx, int ncell, int nrp, int kmax, const float *wdat, const double *part, float *out) {
+  hipLaunchKernelGGL(k_column_stats, dim3((unsigned)nrp), dim3(CL_STATS_TB), 0, ctx->stream, ncell, kmax, wdat, part, out);
+  DZ_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 int dazim_vs_kernels(dazim_ctx *ctx, int nx, int ny, int nz, int kmax, const float *vel_u, const double *svs_u, const double *svp_u,
@@ -299,11 +305,7 @@ int dazim_column_lsq(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, int ker
       hipLaunchKernelGGL(k_column_lsq<double>, dim3((unsigned)ncell), dim3(CL_WAVE), lds, ctx->stream, nx, ny, nlay, kmax, kd.dev,
                          nrhs, rhs.dev, wdat.dev, s2, d2, x.dev, (int *)pe, (double *)pp);
     DZ_HIP(hipGetLastError());
-    if (stats) {
-      hipLaunchKernelGGL(k_column_stats, dim3((unsigned)(nrhs * kmax)), dim3(CL_STATS_TB), 0, ctx->stream, ncell, kmax, wdat.dev,
-                         (const double *)pp, (float *)ps);
-      DZ_HIP(hipGetLastError());
-    }
+    if (stats && (rc = dz_column_stats(ctx, ncell, nrhs * kmax, kmax, wdat.dev, (const double *)pp, (float *)ps))) return rc;
     t.stop();
   }
   int ne = 0;

@@ -244,6 +244,11 @@ __device__ __forceinline__ double dz_column_inverse_factor(int k, int n, double 
   return dg;
 }
 
+// The RMS statistics of a column solve (column.hip), enqueued on the context's stream: out [nrp][2] = per (right-hand side, period)
+// rp the RMS over the cells with wdat [kmax][ncell] != 0 (NULL: all) of r and of r - K x, from the solve kernel's partial sums
+// part [nrp][ncell][2], period rp % kmax, in a fixed order.  dazim_column_lsq and dazim_column_lsq_radial (once per wave type) call it.
+int dz_column_stats(dazim_ctx *ctx, int ncell, int nrp, int kmax, const float *wdat, const double *part, float *out);
+
 // The refined layer table of a column model, refineGrid2LayerMdl (inv/CalSurfG.f90:2339-2365) in its fp32 expressions: the interval
 // between knots i and i + 1 (iv = i, 1-based) becomes nsub sublayers, sublayer j with the weights fm / den = (2j - 1) / (2 nsub) and the
 // thickness thk; the last row is the half-space (iv = 0).  dazim_dispersion_kernels and dazim_ti_kernels build their tables on it.

@@ -9,7 +9,7 @@ module dazim_io
   public :: para_t, read_para, read_data, read_mod, read_map, great_circle, inner_cells, coverage_weights, optional_arg
   public :: write_mod, write_vs_model, write_phase_map, write_azimuthal, write_period_azimuthal, write_azm_line, fast_axis
   public :: write_resolution, uncertainty_weights, tradeoff_factor, write_tradeoff, write_map_tradeoff, write_uncertainty, median
-  public :: period_type, type_name
+  public :: period_type, type_name, write_radial_model, write_radial_resolution
 
   real, parameter :: pi = 3.1415926535898
   real*8, parameter :: pi8 = real(3.1415926535898, 8)   ! the reference widens the fp32 literal too
@@ -620,6 +620,53 @@ contains
           write (u, '(3f10.4)', advance='no') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, depz(k1)
           if (present(vs)) write (u, '(f8.4)', advance='no') vs(i1 + 1, j1 + 1, k1)
           write (u, '(2f10.5,2f10.4,f10.2)') res(i1, j1, k1, 1:5)
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! lon lat depth Vsv Vsh Voigt-Vs xi on the whole grid in write_vs_model's order: Voigt-Vs = sqrt((2 Vsv^2 + Vsh^2) / 3),
+  ! xi = (Vsh / Vsv)^2
+  subroutine write_radial_model(fname, p, depz, vsv, vsh)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real, intent(in) :: depz(:), vsv(:, :, :), vsh(:, :, :)
+    integer :: u, i, j, k
+    open (newunit=u, file=fname, status='replace', action='write')
+    do k = 1, p%nz
+      do j = 1, p%ny
+        do i = 1, p%nx
+          write (u, '(6f8.4,f9.5)') p%gozd + (j - 2)*p%dvzd, p%goxd - (i - 2)*p%dvxd, depz(k), vsv(i, j, k), vsh(i, j, k), &
+            sqrt((2*vsv(i, j, k)**2 + vsh(i, j, k)**2)/3), (vsh(i, j, k)/vsv(i, j, k))**2
+        end do
+      end do
+    end do
+    close (u)
+  end subroutine
+
+  ! dazim_column_resolution_radial's numbers, one line per inner cell and inverted knot in write_resolution's order: lon lat depth Vsv
+  ! Vsh xi std_vsv std_vsh corr std_xi rdiag_v rdiag_h cross_v cross_h.  sd, rdiag, cross (:, :, knot, 1 Vsv / 2 Vsh), cov the Vsv-Vsh
+  ! covariance of a knot; corr = cov / (std_vsv std_vsh) (0 where a std is 0) and, to first order in the errors,
+  ! std_xi = 2 xi sqrt(max(0, (std_vsh / Vsh)^2 + (std_vsv / Vsv)^2 - 2 cov / (Vsv Vsh)))
+  subroutine write_radial_resolution(fname, p, depz, vsv, vsh, sd, cov, rdiag, cross)
+    character(len=*), intent(in) :: fname
+    type(para_t), intent(in) :: p
+    real, intent(in) :: depz(:), vsv(:, :, :), vsh(:, :, :), sd(:, :, :, :), cov(:, :, :), rdiag(:, :, :, :), cross(:, :, :, :)
+    integer :: u, k1, j1, i1
+    real :: v, h, xi, corr, sxi
+    open (newunit=u, file=fname, status='replace', action='write')
+    do k1 = 1, size(cov, 3)
+      do j1 = 1, p%ny - 2
+        do i1 = 1, p%nx - 2
+          v = vsv(i1 + 1, j1 + 1, k1); h = vsh(i1 + 1, j1 + 1, k1)
+          xi = (h/v)**2
+          corr = 0
+          if (sd(i1, j1, k1, 1) > 0 .and. sd(i1, j1, k1, 2) > 0) corr = cov(i1, j1, k1)/(sd(i1, j1, k1, 1)*sd(i1, j1, k1, 2))
+          sxi = 2*xi*sqrt(max(0.0, (sd(i1, j1, k1, 2)/h)**2 + (sd(i1, j1, k1, 1)/v)**2 - 2*cov(i1, j1, k1)/(v*h)))
+          write (u, '(3f10.4,2f8.4,f9.5,2f10.5,f9.5,f10.5,4f10.4)') p%gozd + (j1 - 1)*p%dvzd, p%goxd - (i1 - 1)*p%dvxd, depz(k1), v, h, &
+            xi, sd(i1, j1, k1, 1), sd(i1, j1, k1, 2), corr, sxi, rdiag(i1, j1, k1, 1), rdiag(i1, j1, k1, 2), cross(i1, j1, k1, 1), &
+            cross(i1, j1, k1, 2)
         end do
       end do
     end do

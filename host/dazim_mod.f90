@@ -36,7 +36,8 @@ module dazim_mod
             dazim_assemble_G_maps, dazim_map_posterior, dazim_model_posterior, dazim_model_tradeoff, dazim_tradeoff_pick, &
             dazim_map_tradeoff, dazim_map_tradeoff_total
   ! the second step, maps -> depth model cell by cell (host/dazim_depth.f90)
-  public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq, dazim_column_resolution
+  public :: dazim_ti_kernels, dazim_vs_kernels, dazim_column_lsq, dazim_column_resolution, dazim_column_lsq_radial, &
+            dazim_column_resolution_radial
   ! depthkernel for every wave type: Rayleigh / Love, phase / group velocities in one table over virtual periods
   public :: dazim_dispersion_kernels_typed, dazim_set_segments, dazim_typed, dazim_dispersion_any
   ! Monte-Carlo Vs per map cell (host/dazim_mc.f90)
@@ -247,6 +248,28 @@ module dazim_mod
       integer(c_int), value :: nx, ny, nlay, kmax, kern_fp32
       real(c_float), value :: smooth, damp
       real(c_float) :: wdat(*), depz(*), std_post(*), std_noise(*), rdiag(*), rsum(*), width(*), trace(*)
+      integer(c_int) :: n_empty, n_failed
+    end function
+    ! radial anisotropy: kern_v / kern_h c_loc of the Vsv model's skern over the Rayleigh periods / the Vsh model's over the Love
+    ! periods (c_null_ptr exactly when the count is 0); x [nx-2][ny-2][nlay][2] = dVsv, dVsh; stats [2][kv + kh]
+    integer(c_int) function dazim_column_lsq_radial(ctx, nx, ny, nlay, kv, kern_v, kh, kern_h, rhs_v, rhs_h, w_v, w_h, d0, smooth, damp, &
+        couple, x, n_empty, stats) bind(C, name="dazim_column_lsq_radial")
+      import
+      type(c_ptr), value :: ctx, kern_v, kern_h
+      integer(c_int), value :: nx, ny, nlay, kv, kh
+      real(c_float), value :: smooth, damp, couple
+      real(c_float) :: rhs_v(*), rhs_h(*), w_v(*), w_h(*), d0(*), x(*), stats(*)
+      integer(c_int) :: n_empty
+    end function
+    ! std, rdiag, rsum, cross [nx-2][ny-2][nlay][2], cov_vh [nx-2][ny-2][nlay], trace [nx-2][ny-2][2]; rows: c_loc of an
+    ! [nx-2][ny-2][2 nlay][2 nlay] array, or c_null_ptr
+    integer(c_int) function dazim_column_resolution_radial(ctx, nx, ny, nlay, kv, kern_v, kh, kern_h, w_v, w_h, smooth, damp, couple, &
+        std, cov_vh, rdiag, rsum, cross, trace, rows, n_empty, n_failed) bind(C, name="dazim_column_resolution_radial")
+      import
+      type(c_ptr), value :: ctx, kern_v, kern_h, rows
+      integer(c_int), value :: nx, ny, nlay, kv, kh
+      real(c_float), value :: smooth, damp, couple
+      real(c_float) :: w_v(*), w_h(*), std(*), cov_vh(*), rdiag(*), rsum(*), cross(*), trace(*)
       integer(c_int) :: n_empty, n_failed
     end function
     ! Monte-Carlo Vs per map cell (include/dazim.h): mc is the opaque handle; arrays in the C layouts given there

@@ -484,6 +484,47 @@ int dazim_column_resolution(dazim_ctx *ctx, int nx, int ny, int nlay, int kmax, 
                             float smooth, float damp, const float *depz, float *std_post, float *std_noise, float *rdiag, float *rsum,
                             float *width, float *rows, float *trace, int *n_empty, int *n_failed);
 
+/* ---- radial anisotropy: Vsv from the Rayleigh maps, Vsh from the Love maps, cell by cell -------------------
+ * dazim_column_lsq_radial: per inner cell the updates x = [xv; xh] of the Vsv and the Vsh knots (nlay each, N = 2 nlay) that minimise
+ *     ||Wv (Kv xv - rv)||^2 + ||Wh (Kh xh - rh)||^2 + smooth^2 (||L xv||^2 + ||L xh||^2) + damp^2 ||x||^2
+ *       + couple^2 ||xh - xv + d0||^2
+ *   Kv [kv][nlay] the cell's slice of kern_v (dazim_vs_kernels of the Vsv model over the Rayleigh periods), Kh [kh][nlay] that of
+ *   kern_h (the Vsh model over the Love periods), L the depth rule of dazim_column_lsq, d0 the current Vsh - Vsv at the knots: the
+ *   smoothing and the damping act on the update, the coupling on the model.  Normal equations, with m2 = couple^2 and
+ *   P = smooth^2 L^T L + damp^2 I:
+ *     A = [[Kv^T Wv^2 Kv + P + m2 I, -m2 I], [-m2 I, Kh^T Wh^2 Kh + P + m2 I]] = R R^T
+ *     b = [Kv^T Wv^2 rv + m2 d0; Kh^T Wh^2 rh - m2 d0]
+ *   kern_v [>= nlay][kv][nx*ny], kern_h [>= nlay][kh][nx*ny] fp64, NULL exactly when the count is 0; rhs_v, rhs_h and w_v, w_h
+ *   [kv | kh][ny-2][nx-2] (w = 1/sigma, 0 = no data, NULL = all ones); d0 [nlay][ny-2][nx-2] (NULL = 0).
+ *   x out [2][nlay][ny-2][nx-2]: dVsv, then dVsh, each a dVs block of dazim_model_update.  A cell without a non-zero weight in
+ *   either block gets x = 0 exactly and is counted in n_empty (host, nullable); a cell with data in one block only is solved, and
+ *   with couple > 0 the other profile follows through the coupling.  stats (host, nullable) [kv + kh][2] as dazim_column_lsq's, the
+ *   Rayleigh periods first.  With couple = 0 each block goes through the operations of dazim_column_lsq on that block alone.
+ * dazim_column_resolution_radial: how well that answer is known, from the same factor.  With
+ *   P2 = [[P + m2 I, -m2 I], [-m2 I, P + m2 I]], M = R^-1, C = A^-1 = M^T M and Rm = I - C P2 (x_est = Rm x_true for noise-free data
+ *   and d0 = 0), index a = blk*nlay + knot (blk 0 Vsv, 1 Vsh):
+ *     std [2][nlay][ny-2][nx-2]   = sqrt(C_aa)            cov_vh [nlay][ny-2][nx-2] = C_{a, nlay + a}, the Vsv-Vsh covariance of a knot
+ *     rdiag [2][nlay][..]         = Rm_aa                 rsum [2][nlay][..] = sum over all 2 nlay columns of Rm_ac
+ *     cross [2][nlay][..]         = sum_{c in the other block} |Rm_ac| / sum_{all c} |Rm_ac|: the share of the knot's averaging kernel
+ *                                   that lies in the other profile; 0 if the denominator is 0
+ *     trace [2][ny-2][nx-2] (nullable) = sum_a Rm_aa per block      rows [2 nlay][2 nlay][ny-2][nx-2] (nullable): rows[a][c] = Rm_ac
+ *   M_ij = -(sum_{l = j+1..i} M_il R_lj) / R_jj in ascending l; C_ac = sum_{i >= max(a, c)} M_ia M_ic in ascending i; Rm_ac takes the
+ *   five entries of P + m2 I in c's block in ascending order, then -m2 at c's knot in the other block.  A cell without data gets 0 in
+ *   every output (n_empty), a cell with a pivot that is not finite and > 0 NaN in every output (n_failed; both host, nullable).
+ * Both: fp64 throughout, every sum in a fixed order, each value rounded to fp32 once; host and device arguments give the same bits.
+ *   Refused (DAZIM_E_BAD_ARG): nlay outside 1..63, kv < 0, kh < 0, kv + kh outside 1..60, a negative smooth, damp or couple,
+ *   smooth == damp == 0 (A would not be definite whatever couple is), a kernel table missing for a count that is not 0 or given for a
+ *   count of 0, a missing right-hand side, a missing x, std, cov_vh, rdiag, rsum or cross.  One launch, one workgroup per cell
+ *   (64 lanes up to nlay = 32, 128 beyond), A as a packed lower triangle in LDS: 8 (N (N + 1) / 2 + (kv + kh)(nlay + 2) + N) bytes,
+ *   96 216 at nlay = 63, kv + kh = 60.                                                                                             */
+int dazim_column_lsq_radial(dazim_ctx *ctx, int nx, int ny, int nlay, int kv, const double *kern_v, int kh, const double *kern_h,
+                            const float *rhs_v, const float *rhs_h, const float *w_v, const float *w_h, const float *d0, float smooth,
+                            float damp, float couple, float *x, int *n_empty, float *stats);
+int dazim_column_resolution_radial(dazim_ctx *ctx, int nx, int ny, int nlay, int kv, const double *kern_v, int kh, const double *kern_h,
+                                   const float *w_v, const float *w_h, float smooth, float damp, float couple, float *std,
+                                   float *cov_vh, float *rdiag, float *rsum, float *cross, float *trace, float *rows, int *n_empty,
+                                   int *n_failed);
+
 /* ---- Monte-Carlo Vs per map cell: posterior mean, spread and credible interval ----------------------------
  * Random-walk Metropolis chains on the knots 0..nlay-1 (nlay = nz - 1) of each inner cell's Vs column, the last knot held at vel0's
  * value; the forward model is dazim_dispersion_kernels with sen_* = NULL.  Prior: uniform on [vmin, vmax] per cell and knot.

@@ -1,6 +1,6 @@
 """Times of the second step of the two-step method (profiles/depth_from_maps.md).
 
-    python tools/depth_step.py [--reps R] [--big N]
+    python tools/depth_step.py [--reps R] [--big N] [--radial]
 
 On bench.py's S-256 model grid (54 x 54 columns, 12 knots, 16 periods) and on an N x N grid of the same model (default 202: 200 x 200
 inner cells), every array on the device, R rounds of: the dispersion call with kernels (kernel seconds "disp"; "disp.copies" too
@@ -10,7 +10,12 @@ same table with the same weights and regularisers, without and with the rows ("c
 dazim_last_kernel_seconds (HIP events on the context stream).  Prints one JSON line per grid with the medians and the ratio solve /
 dispersion, then one line for the solve and the resolution call at nlay 31, 32, 33 and 63 on random tables (16 periods, the big
 grid): an even nlay is where the lanes' reads along the rows of the [nlay][nlay] matrix meet in the same LDS banks
-(profiles/depth_resolution.md)."""
+(profiles/depth_resolution.md).
+--radial: instead, on the same two grids, an iteration of the radial-anisotropy mode with the 16 periods as
+Rayleigh phase periods of the model (Vsv) and again as Love phase periods of the model times 1.03 (Vsh): the two typed dispersion
+calls ("disp" + "disp.copies" for the Rayleigh segment, "disp_typed" for the Love segment), dazim_column_lsq_radial ("column_lsq_radial"), dazim_column_resolution_radial without the rows
+("column_resolution_radial"), and beside them the two dazim_column_lsq calls on the same two tables, which is what couple = 0
+computes."""
 import argparse
 import json
 import os
@@ -70,6 +75,54 @@ def one_grid(ctx, n, reps):
             "runs": runs}
 
 
+def radial_grid(ctx, n, reps):
+    import torch
+    import bench
+    bench.NX = bench.NY = n
+    dev = torch.device("cuda:0")
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    vsv = bench.s256_model()
+    vsh = vsv.copy()
+    vsh[:-1] *= np.float32(1.03)
+    vsv, vsh = T(vsv), T(vsh)
+    kmax, nlay = len(bench.PERIODS), len(bench.DEPZ) - 1
+    rng = np.random.default_rng(1)
+    rv, rh = (T(0.05 * rng.standard_normal((kmax, n - 2, n - 2)).astype(np.float32)) for _ in range(2))
+    w = T(np.full((kmax, n - 2, n - 2), 100.0, np.float32))
+    d0 = (vsh - vsv)[:nlay, 1:-1, 1:-1].contiguous()
+    seg = {"v": [(2, 0, bench.PERIODS)], "h": [(1, 0, bench.PERIODS)]}
+    runs = {"disp_typed_rayleigh_s": [], "disp_typed_love_s": [], "column_lsq_radial_s": [], "column_resolution_radial_s": [],
+            "column_lsq_rayleigh_s": [], "column_lsq_love_s": []}
+    for rep in range(reps + 1):   # (round 0: warm-up)
+        t, kern = {}, {}
+        for key, vel, name in (("v", vsv, "rayleigh"), ("h", vsh, "love")):
+            pv, sen, nf = ctx.dispersion_kernels_typed(vel, bench.DEPZ, seg[key], bench.MINTHK)
+            ctx.sync()
+            # (a Rayleigh-phase segment is a dazim_dispersion_kernels call: its seconds are under "disp" and "disp.copies")
+            t[f"disp_typed_{name}_s"] = (ctx.kernel_seconds("disp") + max(ctx.kernel_seconds("disp.copies"), 0.0) if key == "v"
+                                         else ctx.kernel_seconds("disp_typed"))
+            kern[key] = ctx.vs_kernels(vel, sen)
+            assert nf == 0
+        x, ne, _ = ctx.column_lsq_radial(n, n, nlay, kern["v"], kern["h"], rv, rh, w, w, d0, 2.0, 0.0, 5.0)
+        t["column_lsq_radial_s"] = ctx.kernel_seconds("column_lsq_radial")
+        res = ctx.column_resolution_radial(n, n, nlay, kern["v"], kern["h"], w, w, 2.0, 0.0, 5.0)
+        t["column_resolution_radial_s"] = ctx.kernel_seconds("column_resolution_radial")
+        ctx.column_lsq(n, n, nlay, kern["v"], rv[None], w, 2.0, 0.0)
+        t["column_lsq_rayleigh_s"] = ctx.kernel_seconds("column_lsq")
+        ctx.column_lsq(n, n, nlay, kern["h"], rh[None], w, 2.0, 0.0)
+        t["column_lsq_love_s"] = ctx.kernel_seconds("column_lsq")
+        if rep:
+            for k, v in t.items():
+                runs[k].append(v)
+    med = {k: float(np.median(v)) for k, v in runs.items()}
+    assert ne == 0 and torch.isfinite(x).all() and torch.isfinite(res["std"]).all() and res["n_failed"] == 0
+    lds = 8 * (nlay * (2 * nlay + 1) + 2 * kmax * (nlay + 2) + 2 * nlay)
+    return {"grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nlay} knots per profile, {kmax} Rayleigh + {kmax} Love periods",
+            "reps": reps, "lds_bytes_per_workgroup": lds, "median": med,
+            "radial_over_two_column_lsq": med["column_lsq_radial_s"] / (med["column_lsq_rayleigh_s"] + med["column_lsq_love_s"]),
+            "runs": runs}
+
+
 def nlay_sweep(ctx, n, reps, kmax=16):
     """the solve and the resolution call at nlay 31, 32, 33 and 63, random fp64 tables: medians of `reps` rounds after a warm-up"""
     import torch
@@ -103,11 +156,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--big", type=int, default=202)
+    ap.add_argument("--radial", action="store_true")
     a = ap.parse_args()
     ctx = dz.Context(0)
     for n in (54, a.big):
-        print(json.dumps(one_grid(ctx, n, a.reps)), flush=True)
-    print(json.dumps(nlay_sweep(ctx, a.big, a.reps)), flush=True)
+        print(json.dumps((radial_grid if a.radial else one_grid)(ctx, n, a.reps)), flush=True)
+    if not a.radial:
+        print(json.dumps(nlay_sweep(ctx, a.big, a.reps)), flush=True)
     ctx.close()
 
 
