@@ -12,21 +12,26 @@ from tests import synth
 pytestmark = pytest.mark.gpu
 
 
-def _run_case(ctx, orc, nx, ny, kmax, nsrc, seed, goxd=30.0, gozd=100.0, dv=0.25, edge_sources=False, shrink=0.3, rough=False):
-    pv = synth.phase_velocity_maps(nx, ny, kmax, seed)
-    if rough:   # every inversion cell drawn independently: strong, short-wavelength contrasts (caustics, many ties broken)
-        pv = np.random.default_rng(seed).uniform(2.0, 4.8, pv.shape).astype(np.float32).astype(np.float64)
-    lat, lon = synth.stations(nx, ny, goxd, gozd, dv, dv, nsrc, seed + 1, shrink=0.02 if edge_sources else shrink)
+def _run_case(ctx, orc, nx, ny, kmax, nsrc, seed, goxd=30.0, gozd=100.0, dv=0.25, edge_sources=False, shrink=0.3, rough=False,
+              dvz=None, stations=synth.stations, pv=None):
+    """dv: the spacing in latitude, and in longitude too unless dvz is given; stations: synth.stations or a function with its
+    signature; pv: a map of the caller's instead of the seeded one.  Returns the device's outputs and the sources."""
+    dvx, dvz = dv, (dv if dvz is None else dvz)
+    if pv is None:
+        pv = synth.phase_velocity_maps(nx, ny, kmax, seed)
+        if rough:   # every inversion cell drawn independently: strong, short-wavelength contrasts (caustics, many ties broken)
+            pv = np.random.default_rng(seed).uniform(2.0, 4.8, pv.shape).astype(np.float32).astype(np.float64)
+    lat, lon = stations(nx, ny, goxd, gozd, dvx, dvz, nsrc, seed + 1, shrink=0.02 if edge_sources else shrink)
     if edge_sources:  # corners and exact node positions exercise the clipped refined boxes
-        lat[:4] = [goxd, goxd, goxd - (nx - 3) * dv, goxd - (nx - 3) * dv]
-        lon[:4] = [gozd, gozd + (ny - 3) * dv, gozd, gozd + (ny - 3) * dv]
-        lat[4], lon[4] = goxd - 5 * dv, gozd + 7 * dv
+        lat[:4] = [goxd, goxd, goxd - (nx - 3) * dvx, goxd - (nx - 3) * dvx]
+        lon[:4] = [gozd, gozd + (ny - 3) * dvz, gozd, gozd + (ny - 3) * dvz]
+        lat[4], lon[4] = goxd - 5 * dvx, gozd + 7 * dvz
     sx, sz = synth.radians(lat, lon)
     scx = np.tile(sx, kmax)
     scz = np.tile(sz, kmax)
     per = np.repeat(np.arange(1, kmax + 1, dtype=np.int32), nsrc)
-    out = ctx.fmm_batch(nx, ny, goxd, gozd, dv, dv, pv, scx, scz, per)
-    g = orc.geometry(nx, ny, goxd, gozd, dv, dv)
+    out = ctx.fmm_batch(nx, ny, goxd, gozd, dvx, dvz, pv, scx, scz, per)
+    g = orc.geometry(nx, ny, goxd, gozd, dvx, dvz)
     assert (g.nnx, g.nnz) == (out["geom"].nnx, out["geom"].nnz)
     for k in range(kmax):
         veln = orc.gridder(g, pv[k])
@@ -43,6 +48,7 @@ def _run_case(ctx, orc, nx, ny, kmax, nsrc, seed, goxd=30.0, gozd=100.0, dv=0.25
             live = nstsr >= 0
             assert np.array_equal(out["ttnr"][f][live], ttnr[live]), f"ttnr field {f}"
             assert np.array_equal(out["ttn"][f], ttn), f"ttn field {f}: max diff {np.abs(out['ttn'][f]-ttn).max()}"
+    return out, scx, scz
 
 
 def test_fmm_test1_scale(ctx, orc):

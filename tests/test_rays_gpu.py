@@ -26,10 +26,12 @@ from tests.test_disp_gpu import model
 pytestmark = pytest.mark.gpu
 
 
-def build_case(nx, ny, depz, kmax, nsta, nrc, seed, goxd=30.0, gozd=100.0, dv=0.25):
+def build_case(nx, ny, depz, kmax, nsta, nrc, seed, goxd=30.0, gozd=100.0, dv=0.25, dvz=None, stations=synth.stations):
+    """dv: the spacing in latitude, and in longitude too unless dvz is given; stations(nx, ny, goxd, gozd, dvx, dvz, n, seed)
+    -> (lat, lon) in degrees"""
     rng = np.random.default_rng(seed)
     vel = model(nx, ny, depz, seed)
-    lat, lon = synth.stations(nx, ny, goxd, gozd, dv, dv, nsta, seed)
+    lat, lon = stations(nx, ny, goxd, gozd, dv, dv if dvz is None else dvz, nsta, seed)
     sx, sz = synth.radians(lat, lon)
     nsrc = nsta
     scxf = np.zeros((kmax, nsrc), np.float32); sczf = scxf.copy()
