@@ -672,7 +672,7 @@ class Context:
         return out
 
     def mc_create(self, nx, ny, nz, kmax, nchain, nbin, seed, vel0, vmin, vmax, cobs, wdat, step=0.05, nadapt=50, proposal=0,
-                  ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None, prior=None, segments=None, noise_groups=None):
+                  ntemp=1, tmax=1.0, nswap=1, aniso=None, noise=None, prior=None, segments=None, noise_groups=None, radial=None):
         """Monte-Carlo Vs per inner cell (dazim_mc_create): vel0[nz][ny][nx], vmin, vmax[nz-1][ny-2][nx-2],
         cobs, wdat[kmax][ny-2][nx-2].  Returns a MonteCarlo handle (draws the start models); its n_empty counts the cells without
         data.  proposal: 0 isotropic in box units, 1 shaped by the chains' covariance (MonteCarlo.set_proposal).  ntemp > 1: parallel
@@ -681,7 +681,8 @@ class Context:
         makes the data-noise scale of every cell an unknown with the prior lambda^2 ~ InverseGamma(a0, b0) (MonteCarlo.set_noise).
         prior: (smooth, damp) or (smooth, damp, vref) adds the Gaussian smoothness prior to the box (MonteCarlo.set_prior).
         segments: [(iwave, igr, periods), ...] makes the kmax periods those of several wave types (MonteCarlo.set_segments).
-        noise_groups: (group_of_period, a0, b0) gives every group of periods a noise scale of its own (MonteCarlo.set_noise_groups)."""
+        noise_groups: (group_of_period, a0, b0) gives every group of periods a noise scale of its own (MonteCarlo.set_noise_groups).
+        radial: couple makes the knots the stacked [Vsv, Vsh, deepest] of radial anisotropy (MonteCarlo.set_radial; needs segments)."""
         nlay, ncell = nz - 1, (nx - 2) * (ny - 2)
         vel0 = np.ascontiguousarray(vel0, np.float32).reshape(nz, ny, nx)
         vmin, vmax = (np.ascontiguousarray(a, np.float32).reshape(nlay, ny - 2, nx - 2) for a in (vmin, vmax))
@@ -706,6 +707,8 @@ class Context:
             mc.set_segments(segments)
         if noise_groups is not None:
             mc.set_noise_groups(*noise_groups)
+        if radial is not None:
+            mc.set_radial(radial)
         return mc
 
     def ray_paths(self):
@@ -1017,13 +1020,68 @@ class MonteCarlo:
         s, d = C.c_float(0), C.c_float(0)
         self.ctx._check(self.ctx.lib.dazim_mc_prior_state(self.ctx._h, self._h, C.byref(s), C.byref(d), None, None))
         out = dict(smooth=s.value, damp=d.value)
-        if s.value == 0 and d.value == 0:
+        if s.value == 0 and d.value == 0 and self._radial()[1] == 0:      # (a radial handle's coupling alone keeps the prior on)
             return out
         vref = np.zeros((self.nlay, self.ny - 2, self.nx - 2), np.float32)
         q = np.zeros(self.ncol, np.float64)
         self.ctx._check(self.ctx.lib.dazim_mc_prior_state(self.ctx._h, self._h, None, None, _ptr(vref), _ptr(q)))
         out.update(vref=vref, q=q)
         return out
+
+    def set_radial(self, couple):
+        """radial anisotropy (dazim_mc_set_radial): the handle's knots are the stacked vector [Vsv_0..Vsv_{n-1}, Vsh_0..Vsh_{n-1},
+        deepest] (create it with nz = 2n + 1), run() computes the Rayleigh segments' curves from the Vsv model and the Love segments'
+        from the Vsh model (depz then has n + 1 entries), the prior gains couple^2 |Vsh - Vsv|^2, and every recorded state adds
+        xi = (Vsh / Vsv)^2, the Voigt average and Vsv Vsh to the radial record.  Needs set_segments with Rayleigh before Love;
+        refused once a step has been done"""
+        self.ctx._check(self.ctx.lib.dazim_mc_set_radial(self.ctx._h, self._h, float(couple)))
+
+    def _radial(self):
+        n, c = C.c_int(0), C.c_float(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_radial_state(self.ctx._h, self._h, C.byref(n), C.byref(c), None, None, None))
+        return n.value, c.value
+
+    def radial_models(self):
+        """the two models run()'s dispersion calls read (dazim_mc_radial_models): torch views (vsv, vsh), each [n+1][ncol] (fp32, on
+        the context's device), no copy; valid after set_radial and after every step, invalid once free() has run"""
+        import torch
+        pv, ph, nc = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        self.ctx._check(self.ctx.lib.dazim_mc_radial_models(self._h, C.byref(pv), C.byref(ph), C.byref(nc)))
+        n = self.nlay // 2
+        dev = torch.device("cuda", self.ctx.device)
+        if nc.value == 0:
+            return tuple(torch.zeros((n + 1, 0), dtype=torch.float32, device=dev) for _ in range(2))
+
+        def view(p):
+            class _Cai:
+                __cuda_array_interface__ = dict(shape=(n + 1, nc.value), typestr="<f4", data=(p.value, False), version=2, strides=None)
+            return torch.as_tensor(_Cai(), device=dev)
+        return view(pv), view(ph)
+
+    def radial_state(self):
+        """the radial mode and, while it is on, copies of its record (dazim_mc_radial_state): dict n, couple, rsum[5][n][ncol] (sums
+        of xi, xi^2, Vsv Vsh, V, V^2), ngt1[n][ncol] (states with xi > 1), xhist[sampled cells][n][nbin]; dict n = 0, couple = 0
+        alone on a handle that is not radial"""
+        n, c = self._radial()
+        out = dict(n=n, couple=c)
+        if n == 0:
+            return out
+        rsum = np.zeros((5, n, self.ncol), np.float64)
+        ngt1 = np.zeros((n, self.ncol), np.int64)
+        xhist = np.zeros((self.ncs, n, self.nbin), np.uint32)
+        self.ctx._check(self.ctx.lib.dazim_mc_radial_state(self.ctx._h, self._h, None, None, _ptr(rsum), _ptr(ngt1), _ptr(xhist)))
+        out.update(rsum=rsum, ngt1=ngt1, xhist=xhist)
+        return out
+
+    def radial_result(self):
+        """posterior statistics of the derived quantities (dazim_mc_radial_result): dict xi_mean, xi_std, xi_rhat, p_gt1 (the
+        posterior probability of xi > 1), corr_vh (the Vsv-Vsh correlation), voigt_mean, voigt_std [n][ny-2][nx-2] and xi_q
+        [3][n][ny-2][nx-2] (2.5 / 50 / 97.5 %)"""
+        shp = (self.nlay // 2, self.ny - 2, self.nx - 2)
+        keys = ("xi_mean", "xi_std", "xi_q", "xi_rhat", "p_gt1", "corr_vh", "voigt_mean", "voigt_std")
+        r = {k: np.zeros(((3,) if k == "xi_q" else ()) + shp, np.float32) for k in keys}
+        self.ctx._check(self.ctx.lib.dazim_mc_radial_result(self.ctx._h, self._h, *(_ptr(r[k]) for k in keys)))
+        return r
 
     def step(self, pv, record):
         """one step on pv[kmax][ncol] (fp64; numpy or torch-cuda), the curves of proposals(); record 0 = burn-in"""
@@ -1036,10 +1094,12 @@ class MonteCarlo:
 
     def run(self, depz, sublayers, periods, nburn, nsample):
         """nburn burn-in and nsample recorded steps with the dispersion forward model (dazim_mc_run); returns the proposals without
-        a root.  After set_segments, periods are the virtual periods, segment after segment"""
+        a root.  After set_segments, periods are the virtual periods, segment after segment; after set_radial depz has the n + 1
+        knot depths of one profile"""
         depz = np.ascontiguousarray(depz, np.float32)
         periods = np.ascontiguousarray(periods, np.float64)
-        assert len(depz) == self.nz and len(periods) == self.kmax
+        nrad = self._radial()[0]
+        assert len(depz) == (nrad + 1 if nrad else self.nz) and len(periods) == self.kmax
         nr = C.c_int64(0)
         self.ctx._check(self.ctx.lib.dazim_mc_run(self.ctx._h, self._h, _ptr(depz), C.c_float(sublayers), _ptr(periods), int(nburn),
                                                   int(nsample), C.byref(nr)))

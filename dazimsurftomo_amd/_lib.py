@@ -115,5 +115,13 @@ def load():
     lib.dazim_mc_set_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     lib.dazim_mc_prior_state.restype = C.c_int
     lib.dazim_mc_prior_state.argtypes = [C.c_void_p] * 6
+    lib.dazim_mc_set_radial.restype = C.c_int
+    lib.dazim_mc_set_radial.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
+    lib.dazim_mc_radial_models.restype = C.c_int
+    lib.dazim_mc_radial_models.argtypes = [C.c_void_p] * 4
+    lib.dazim_mc_radial_state.restype = C.c_int
+    lib.dazim_mc_radial_state.argtypes = [C.c_void_p] * 7
+    lib.dazim_mc_radial_result.restype = C.c_int
+    lib.dazim_mc_radial_result.argtypes = [C.c_void_p] * 10
     _lib = lib
     return lib

@@ -30,6 +30,11 @@
 // L^T L + damp^2 I) d, d the state's knots minus a reference, inside the box.  k_mc_step<KIND, TEMPER, NG, 1> takes every decision
 // on E + Q in place of E (mc_total, mc_prior_q; a rung samples (likelihood x Gaussian prior)^beta) and keeps the Q of every chain's state
 // in pq [ncol].  The best model stays the one of lowest raw chi^2: the best-fitting model, not the maximum a posteriori.
+//
+// Radial anisotropy (dazim_mc_set_radial, column_mc_radial.hip): the knots are the stacked [Vsv, Vsh, deepest], which the step samples
+// as any knots.  k_mc_step<KIND, TEMPER, NG, PRIOR, 1> takes Q from mc_prior_q_radial, records xi = (Vsh / Vsv)^2, the Voigt average and
+// Vsv Vsh of every recorded state, and stores a proposed Vsv knot to the Vsv model as well, which dazim_mc_run computes the Rayleigh
+// segments' curves from (the Love segments' come from rows n..2n of the proposals): two dazim_dispersion_kernels_typed calls per step.
 #include "mc_internal.h"
 
 #include <algorithm>
@@ -114,6 +119,33 @@ __device__ __forceinline__ double mc_prior_q(const McDev &M, const float *__rest
   return M.ps2 * q1 + M.pd2 * q2;
 }
 
+// the same of a radial handle's stacked knots (dazim_mc_set_radial): q1 and q2 run on through both profiles in knot order, L's rule
+// inside each profile of n knots (knots n - 1 and n are ends: no row crosses the boundary), and qc = |vh - vv|^2 over the n pairs in
+// knot order; Q = (ps2 q1 + pd2 q2) + pm2 qc
+__device__ __forceinline__ double mc_prior_q_radial(const McDev &M, const float *__restrict__ v, long col, int cell) {
+  const int n = M.nrad;
+  double q1 = 0.0, q2 = 0.0, qc = 0.0;
+  for (int h = 0; h < 2; h++) {
+    const int k0 = h * n;
+    double dm = 0.0;
+    double d = (double)v[k0 * M.ncol + col] - (double)M.pref[(long)k0 * M.ncell + cell];
+    for (int a = 0; a < n; a++) {
+      const double dp =
+          a + 1 < n ? (double)v[(k0 + a + 1) * M.ncol + col] - (double)M.pref[(long)(k0 + a + 1) * M.ncell + cell] : 0.0;
+      const double t = (a == 0 || a == n - 1) ? 2.0 * d : (2.0 * d - dm) - dp;
+      q1 += t * t;
+      q2 += d * d;
+      dm = d;
+      d = dp;
+    }
+  }
+  for (int a = 0; a < n; a++) {
+    const double c = (double)v[(n + a) * M.ncol + col] - (double)v[a * M.ncol + col];
+    qc += c * c;
+  }
+  return (M.ps2 * q1 + M.pd2 * q2) + M.pm2 * qc;
+}
+
 // the lanes of rung r: chains r, r + ntemp, ..
 __device__ __forceinline__ unsigned long long mc_rung_mask(int nchain, int ntemp, int r) {
   unsigned long long m = 0ull;
@@ -139,23 +171,30 @@ __device__ __forceinline__ McNormals mc_normals(const McDev &M, long long step, 
   return {{r0 * cos(t0), r0 * sin(t0), r1 * cos(t1), r1 * sin(t1)}};
 }
 
-// knot k of the next proposal of column col: v' = v + s (vmax - vmin) y in fp64, reflected into the box, fp32
+// knot k of the next proposal of column col: v' = v + s (vmax - vmin) y in fp64, reflected into the box, fp32.  RAD (a radial
+// handle): a Vsv knot goes to the Vsv model too, which the Rayleigh curves of dazim_mc_run are computed from
+template <int RAD>
 __device__ __forceinline__ void mc_store_proposal(const McDev &M, int cell, long col, int k, float s, double y) {
   const McBox b = mc_box(M, cell, k);
   const double d = (double)s * (b.hi - b.lo);
   double v = (double)M.cur[k * M.ncol + col] + d * y;
   for (int r = 0; r < MC_MAXFOLD && (v < b.lo || v > b.hi); r++) v = v < b.lo ? 2.0 * b.lo - v : 2.0 * b.hi - v;
-  M.prop[k * M.ncol + col] = (float)fmin(fmax(v, b.lo), b.hi);
+  const float vf = (float)fmin(fmax(v, b.lo), b.hi);
+  M.prop[k * M.ncol + col] = vf;
+  if constexpr (RAD) {
+    if (k < M.nrad) M.vsv[k * M.ncol + col] = vf;
+  }
 }
 
 // the next proposal of chain (cs, ch) from its current state, isotropic in box units: y = z
+template <int RAD>
 __device__ void mc_propose(const McDev &M, int cs, int ch, long long step, float s) {
   const int cell = M.cell_of[cs];
   const long col = (long)cs * M.nchain + ch;
   const unsigned gid = (unsigned)((long)cell * M.nchain + ch);
   for (int q = 0; q * 4 < M.nlay; q++) {
     const McNormals n = mc_normals(M, step, gid, q);
-    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) mc_store_proposal(M, cell, col, q * 4 + i, s, n.z[i]);
+    for (int i = 0; i < 4 && q * 4 + i < M.nlay; i++) mc_store_proposal<RAD>(M, cell, col, q * 4 + i, s, n.z[i]);
   }
 }
 
@@ -237,6 +276,7 @@ __device__ bool mc_cov_factor(const McDev &M, int cs, int ch, long long cn, doub
 
 // kind 1, a cell with a factor: v' = v + s (vmax - vmin) y, y = L z with the normals of mc_propose, y_k summed in j order in fp64.
 // zs [nlay][nchain] (LDS) takes the chain's normals; L is read at one address by every lane (a broadcast).
+template <int RAD>
 __device__ void mc_propose_cov(const McDev &M, int cs, int ch, long long step, float s, const double *L, double *zs) {
   const int cell = M.cell_of[cs], nc = M.nchain;
   const long col = (long)cs * M.nchain + ch;
@@ -249,7 +289,7 @@ __device__ void mc_propose_cov(const McDev &M, int cs, int ch, long long step, f
     const double *Lk = L + k * (k + 1) / 2;
     double y = 0.0;
     for (int j = 0; j <= k; j++) y += Lk[j] * zs[j * nc + ch];
-    mc_store_proposal(M, cell, col, k, s, y);
+    mc_store_proposal<RAD>(M, cell, col, k, s, y);
   }
 }
 
@@ -301,7 +341,10 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_init(McDev M, float step0) {
 // with the knots, and a recorded lane adds sqrt(B_g) and B_g per group with data to its own columns of nsum.  chi2 stays the total.
 // PRIOR 1 (dazim_mc_set_prior): the lane walks its column of prop for Q', the decision and the swap compare energy + Q (mc_total; the
 // rules for +inf still test chi^2 alone), Q travels beside chi^2 through the swap's shuffles, and pq keeps the Q of the lane's state.
-template <int KIND, int TEMPER, int NG, int PRIOR>
+// RAD 1 (dazim_mc_set_radial): Q is the stacked knots' (mc_prior_q_radial), a recorded lane adds xi, xi^2, vv vh, V, V^2 of every knot
+// pair of its state to its own columns of rsum, counts xi > 1 there and xi into the cell's rhist, and a proposed Vsv knot goes to the
+// Vsv model as well (mc_store_proposal).
+template <int KIND, int TEMPER, int NG, int PRIOR, int RAD>
 __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__restrict__ pv, long long step, int first, int record,
                                                      int adapt, int nadapt) {
   __shared__ float s_scale;
@@ -328,7 +371,7 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
   bool acc = false;
   if (act) {
     chi2p = mc_chi2<NG>(M, pv, cell, col, cgp, ndg);
-    if constexpr (PRIOR) qp = mc_prior_q(M, M.prop, col, cell);
+    if constexpr (PRIOR) qp = RAD ? mc_prior_q_radial(M, M.prop, col, cell) : mc_prior_q(M, M.prop, col, cell);
     if (first) {
       acc = true;
     } else {
@@ -451,6 +494,26 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
         b = b < 0 ? 0 : (b >= M.nbin ? M.nbin - 1 : b);
         atomicAdd(&M.hist[((long)cs * M.nlay + k) * M.nbin + b], 1u);
       }
+      if constexpr (RAD) {
+        const int n = M.nrad;
+        const long nn = (long)n * M.ncol;
+        for (int a = 0; a < n; a++) {
+          const double vv = (double)M.cur[a * M.ncol + col], vh = (double)M.cur[(n + a) * M.ncol + col];
+          const double r = vh / vv, xi = r * r, V = sqrt((2.0 * vv * vv + vh * vh) / 3.0);
+          const long o = (long)a * M.ncol + col;
+          M.rsum[o] += xi;
+          M.rsum[nn + o] += xi * xi;
+          M.rsum[2 * nn + o] += vv * vh;
+          M.rsum[3 * nn + o] += V;
+          M.rsum[4 * nn + o] += V * V;
+          if (xi > 1.0) M.rgt1[o] += 1;
+          const McBox bv = mc_box(M, cell, a), bh = mc_box(M, cell, n + a);
+          const double rl = bh.lo / bv.hi, rh = bh.hi / bv.lo, xlo = rl * rl, xhi = rh * rh;
+          int b = (int)((xi - xlo) / (xhi - xlo) * (double)M.nbin);
+          b = b < 0 ? 0 : (b >= M.nbin ? M.nbin - 1 : b);
+          atomicAdd(&M.rhist[((long)cs * n + a) * M.nbin + b], 1u);
+        }
+      }
       if constexpr (NG >= 1) {
         if (!isinf(M.chi2[col])) {   // (cgs: the state's chi^2_g, after the decision and the swap)
 #pragma unroll
@@ -524,13 +587,13 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_step(McDev M, const double *__re
       if (!have)
         for (int e = ch; e < npair; e += MC_WAVE) L[e] = M.chol[(long)cs * npair + e];
       __syncthreads();
-      if (act) mc_propose_cov(M, cs, ch, step, s, L, zs);
+      if (act) mc_propose_cov<RAD>(M, cs, ch, step, s, L, zs);
     } else if (act) {
-      mc_propose(M, cs, ch, step, s);
+      mc_propose<RAD>(M, cs, ch, step, s);
     }
   } else {
     __syncthreads();
-    if (act) mc_propose(M, cs, ch, step, TEMPER ? s_rscale[rung] : s_scale);
+    if (act) mc_propose<RAD>(M, cs, ch, step, TEMPER ? s_rscale[rung] : s_scale);
   }
 }
 
@@ -650,11 +713,11 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_noise_final(McDev M, float *__re
   lam_std[i] = a <= 1.0 ? NAN : (float)sqrt(fmax(s1 / (dn * (a - 1.0)) - lm * lm, 0.0));
 }
 
-// the step kernel of a handle: [prior][noise: off, one group, more][kind][tempered]
+// the step kernel of a handle: [radial][prior][noise: off, one group, more][kind][tempered]
 using McStepKernel = void (*)(McDev, const double *, long long, int, int, int, int);
-#define MC_STEP_NG(G, P) {{k_mc_step<0, 0, G, P>, k_mc_step<0, 1, G, P>}, {k_mc_step<1, 0, G, P>, k_mc_step<1, 1, G, P>}}
-#define MC_STEP_SET(P) {MC_STEP_NG(0, P), MC_STEP_NG(1, P), MC_STEP_NG(MC_MAXGRP, P)}
-constexpr McStepKernel MC_STEP[2][3][2][2] = {MC_STEP_SET(0), MC_STEP_SET(1)};
+#define MC_STEP_NG(G, P, R) {{k_mc_step<0, 0, G, P, R>, k_mc_step<0, 1, G, P, R>}, {k_mc_step<1, 0, G, P, R>, k_mc_step<1, 1, G, P, R>}}
+#define MC_STEP_SET(P, R) {MC_STEP_NG(0, P, R), MC_STEP_NG(1, P, R), MC_STEP_NG(MC_MAXGRP, P, R)}
+constexpr McStepKernel MC_STEP[2][2][3][2][2] = {{MC_STEP_SET(0, 0), MC_STEP_SET(1, 0)}, {MC_STEP_SET(0, 1), MC_STEP_SET(1, 1)}};
 #undef MC_STEP_SET
 #undef MC_STEP_NG
 
@@ -663,10 +726,23 @@ __global__ __launch_bounds__(MC_WAVE) void k_mc_prior_q(McDev M) {
   const int cs = blockIdx.x, ch = threadIdx.x;
   if (ch >= M.nchain) return;
   const long col = (long)cs * M.nchain + ch;
-  M.pq[col] = mc_prior_q(M, M.cur, col, M.cell_of[cs]);
+  M.pq[col] = M.nrad ? mc_prior_q_radial(M, M.cur, col, M.cell_of[cs]) : mc_prior_q(M, M.cur, col, M.cell_of[cs]);
 }
 
 // one step on the curves pv (device) of the current proposals; enqueued on the ctx stream, no host wait
+// vel0's knots at the inner cells [nlay][ncell]: the prior's centre where the caller names none
+int mc_vel0_knots(dazim_ctx *ctx, dazim_mc *mc, std::vector<float> &knots) {
+  const McDev &M = mc->d;
+  std::vector<float> vel0;
+  int rc;
+  if ((rc = mc_to_host(ctx, M.vel0, (size_t)M.nz * M.nx * M.ny, vel0))) return rc;
+  knots.resize((size_t)M.nlay * M.ncell);
+  const int nvx = M.nx - 2;
+  for (int k = 0; k < M.nlay; k++)
+    for (int c = 0; c < M.ncell; c++) knots[(size_t)k * M.ncell + c] = vel0[((size_t)k * M.ny + (c / nvx + 1)) * M.nx + (c % nvx + 1)];
+  return 0;
+}
+
 int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
   const bool first = mc->nstep == 0;
   bool adapt = false;
@@ -679,7 +755,7 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
     DZ_HIP(hipEventRecord(mc->e0, ctx->stream));
     const size_t lds =
         mc->kind == 1 ? ((size_t)mc->d.nlay * (mc->d.nlay + 1) / 2 + (size_t)mc->d.nlay * mc->d.nchain) * sizeof(double) : 0;
-    const McStepKernel kern = MC_STEP[mc->prior][std::min(mc->d.ngrp, 2)][mc->kind][mc->d.ntemp > 1];
+    const McStepKernel kern = MC_STEP[mc->d.nrad > 0][mc->prior][std::min(mc->d.ngrp, 2)][mc->kind][mc->d.ntemp > 1];
     hipLaunchKernelGGL(kern, dim3((unsigned)mc->d.ncs), dim3(MC_WAVE), lds, ctx->stream, mc->d, pv, step, (int)first, record, (int)adapt,
                        mc->nadapt);
     DZ_HIP(hipGetLastError());
@@ -693,6 +769,35 @@ int mc_launch_step(dazim_ctx *ctx, dazim_mc *mc, const double *pv, int record) {
   return 0;
 }
 }  // namespace
+
+int mc_prior_refresh(dazim_ctx *ctx, dazim_mc *mc, const std::vector<float> *vref) {
+  McDev &M = mc->d;
+  if (mc->psmooth == 0.0f && mc->pdamp == 0.0f && !(M.nrad > 0 && mc->couple != 0.0f)) {
+    mc->prior = 0;
+    return 0;
+  }
+  DZ_HIP(hipSetDevice(ctx->device));
+  int rc;
+  const size_t nk = (size_t)M.nlay * M.ncell;
+  std::vector<float> knots;
+  if (!vref && !M.pref) {
+    if ((rc = mc_vel0_knots(ctx, mc, knots))) return rc;
+    vref = &knots;
+  }
+  if (!M.pq) {
+    float *r;
+    if ((rc = mc_alloc(mc, nk, &r)) || (rc = mc_alloc(mc, (size_t)M.ncol, &M.pq))) return rc;
+    M.pref = r;
+  }
+  if (vref) DZ_HIP(hipMemcpyAsync((void *)M.pref, vref->data(), nk * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (M.ncs > 0) {   // the start models are the states until the first step
+    hipLaunchKernelGGL(k_mc_prior_q, dim3((unsigned)M.ncs), dim3(MC_WAVE), 0, ctx->stream, M);
+    DZ_HIP(hipGetLastError());
+  }
+  DZ_HIP(hipStreamSynchronize(ctx->stream));
+  mc->prior = 1;
+  return 0;
+}
 
 extern "C" {
 
@@ -1083,6 +1188,19 @@ int dazim_mc_set_segments(dazim_ctx *ctx, dazim_mc *mc, int nseg, const int *seg
     return dz_fail(ctx, DAZIM_E_BAD_ARG,
                    "dazim_mc_set_segments: the handle samples Gc/Gs (dazim_mc_set_aniso), whose kernel Lsen_Gsc is Rayleigh-phase: "
                    "other segments than Rayleigh phase alone are refused");
+  if (mc->d.nrad > 0) {   // a radial handle keeps Rayleigh before Love, both present
+    int nr = 0;
+    while (nr < nseg && seg_iwave[nr] == 2) nr++;
+    bool ok = nr > 0 && nr < nseg;
+    for (int s = nr; s < nseg; s++) ok = ok && seg_iwave[s] == 1;
+    if (!ok)
+      return dz_fail(ctx, DAZIM_E_BAD_ARG,
+                     "dazim_mc_set_segments: the handle is radial (dazim_mc_set_radial): at least one Rayleigh and one Love segment, "
+                     "every Rayleigh segment before every Love segment");
+    mc->rad_nr = nr;
+    mc->rad_kr = 0;
+    for (int s = 0; s < nr; s++) mc->rad_kr += seg_kmax[s];
+  }
   mc->nseg = nseg;
   for (int s = 0; s < MC_MAXSEG; s++) {
     mc->seg_iwave[s] = s < nseg ? seg_iwave[s] : 0;
@@ -1121,11 +1239,10 @@ int dazim_mc_set_prior(dazim_ctx *ctx, dazim_mc *mc, float smooth, float damp, c
     return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_prior: smooth %g or damp %g is not finite and >= 0", smooth, damp);
   if (mc->nstep > 0) return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_prior: the handle has done %lld steps", (long long)mc->nstep);
   McDev &M = mc->d;
-  if (smooth == 0.0f && damp == 0.0f) {
-    mc->prior = 0;
+  if (smooth == 0.0f && damp == 0.0f) {   // (a radial handle with a coupling keeps its prior: vref stays what it was)
     mc->psmooth = mc->pdamp = 0.0f;
     M.ps2 = M.pd2 = 0.0;
-    return 0;
+    return mc_prior_refresh(ctx, mc, nullptr);
   }
   DZ_HIP(hipSetDevice(ctx->device));
   const size_t nk = (size_t)M.nlay * M.ncell;
@@ -1136,32 +1253,14 @@ int dazim_mc_set_prior(dazim_ctx *ctx, dazim_mc *mc, float smooth, float damp, c
       if (!std::isfinite(vref[e]))
         return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_prior: a non-finite vref at knot %d, cell %d", (int)(e / M.ncell),
                        (int)(e % M.ncell));
-  } else {   // vel0's knots at the inner cells
-    std::vector<float> vel0;
-    if ((rc = mc_to_host(ctx, M.vel0, (size_t)M.nz * M.nx * M.ny, vel0))) return rc;
-    vref.resize(nk);
-    const int nvx = M.nx - 2;
-    for (int k = 0; k < M.nlay; k++)
-      for (int c = 0; c < M.ncell; c++)
-        vref[(size_t)k * M.ncell + c] = vel0[((size_t)k * M.ny + (c / nvx + 1)) * M.nx + (c % nvx + 1)];
-  }
-  if (!M.pq) {
-    float *r;
-    if ((rc = mc_alloc(mc, nk, &r)) || (rc = mc_alloc(mc, (size_t)M.ncol, &M.pq))) return rc;
-    M.pref = r;
+  } else if ((rc = mc_vel0_knots(ctx, mc, vref))) {
+    return rc;
   }
   M.ps2 = (double)smooth * (double)smooth;
   M.pd2 = (double)damp * (double)damp;
-  DZ_HIP(hipMemcpyAsync((void *)M.pref, vref.data(), nk * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  if (M.ncs > 0) {   // the start models are the states until the first step
-    hipLaunchKernelGGL(k_mc_prior_q, dim3((unsigned)M.ncs), dim3(MC_WAVE), 0, ctx->stream, M);
-    DZ_HIP(hipGetLastError());
-  }
-  DZ_HIP(hipStreamSynchronize(ctx->stream));
   mc->psmooth = smooth;
   mc->pdamp = damp;
-  mc->prior = 1;
-  return 0;
+  return mc_prior_refresh(ctx, mc, &vref);
 }
 
 int dazim_mc_prior_state(dazim_ctx *ctx, dazim_mc *mc, float *smooth, float *damp, float *vref, double *q) {
@@ -1225,7 +1324,20 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
     int nf = 0;
     // curves only, one column per chain: nx = ncol, ny = 1 (the call ends with a wait for the stream: the step enqueued before it
     // has finished when it returns)
-    if (mc->typed) {   // (every segment's curves; a Rayleigh-phase segment goes through the call below inside it)
+    if (mc->d.nrad > 0) {   // the Rayleigh segments on the Vsv model, the Love segments on the Vsh model (rows n..2n of prop)
+      const int n = mc->d.nrad, nr = mc->rad_nr, kr = mc->rad_kr;
+      int nfh = 0;
+      if ((rc = dazim_dispersion_kernels_typed(ctx, (int)mc->d.ncol, 1, n + 1, mc->d.vsv, depz, sublayers, nr, mc->seg_iwave, mc->seg_igr,
+                                               mc->seg_kmax, periods, mc->pv, nullptr, nullptr, nullptr, &nf)))
+        return rc;
+      t_disp += (nr > 1 || !has_rc ? ctx->ksec["disp_typed"] : 0.0) + (has_rc ? ctx->ksec["disp"] : 0.0);
+      if ((rc = dazim_dispersion_kernels_typed(ctx, (int)mc->d.ncol, 1, n + 1, mc->d.prop + (size_t)n * mc->d.ncol, depz, sublayers,
+                                               mc->nseg - nr, mc->seg_iwave + nr, mc->seg_igr + nr, mc->seg_kmax + nr, periods + kr,
+                                               mc->pv + (size_t)kr * mc->d.ncol, nullptr, nullptr, nullptr, &nfh)))
+        return rc;
+      t_disp += ctx->ksec["disp_typed"];
+      nf += nfh;
+    } else if (mc->typed) {   // (every segment's curves; a Rayleigh-phase segment goes through the call below inside it)
       if ((rc = dazim_dispersion_kernels_typed(ctx, (int)mc->d.ncol, 1, mc->d.nz, mc->d.prop, depz, sublayers, mc->nseg, mc->seg_iwave,
                                                mc->seg_igr, mc->seg_kmax, periods, mc->pv, nullptr, nullptr, nullptr, &nf)))
         return rc;
@@ -1301,6 +1413,7 @@ int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayer
   ctx->ksec["mc.noise"] = std::min(mc->d.ngrp, 2);
   ctx->ksec["mc.noise_groups"] = mc->d.ngrp;
   ctx->ksec["mc.prior"] = mc->prior;
+  ctx->ksec["mc.radial"] = mc->d.nrad > 0;
   ctx->ksec["mc.cov_cells"] = cov_cells;
   if (n_no_root) *n_no_root = (int64_t)(c1[0] - c0[0]);
   return 0;

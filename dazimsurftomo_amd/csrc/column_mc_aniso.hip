@@ -193,6 +193,8 @@ int dazim_mc_set_aniso(dazim_ctx *ctx, dazim_mc *mc, int nthin, const float *ama
     mc->nthin = 0;
     return 0;
   }
+  if (mc->d.nrad > 0)
+    return dz_fail(ctx, DAZIM_E_BAD_ARG, "dazim_mc_set_aniso: the handle is radial (dazim_mc_set_radial): Gc/Gs takes one Vs profile");
   if (mc->typed)
     return dz_fail(ctx, DAZIM_E_BAD_ARG,
                    "dazim_mc_set_aniso: the Gc/Gs kernel Lsen_Gsc is Rayleigh-phase, and the handle's segments (dazim_mc_set_segments) "

@@ -1,5 +1,5 @@
-// mc_internal.h -- what column_mc.hip (the handle, the step and the Vs and noise results) and column_mc_aniso.hip (the Gc/Gs pass)
-// share: the sampler's constants, the device view of a handle, the handle itself, the random numbers and the host helpers.
+// mc_internal.h -- what column_mc.hip (the handle, the step and the Vs and noise results), column_mc_aniso.hip (the Gc/Gs pass) and
+// column_mc_radial.hip (the radial handle's setter, record state and result) share: the sampler's constants, the device view of a handle, the handle itself, the random numbers and the host helpers.
 #pragma once
 #include "dazim_internal.h"
 
@@ -88,6 +88,13 @@ struct McDev {
   double ps2, pd2;             // (double)smooth^2, (double)damp^2
   const float *pref;           // [nlay][ncell]: the prior's centre
   double *pq;                  // [ncol]: the prior energy Q of every chain's state
+  // radial anisotropy only (dazim_mc_set_radial; 0 and null otherwise): the knots are [Vsv_0..Vsv_{n-1}, Vsh_0..Vsh_{n-1}, deepest]
+  int nrad;                    // n = nlay / 2
+  double pm2;                  // (double)couple^2: the prior's mu^2 |vh - vv|^2
+  float *vsv;                  // [n + 1][ncol]: the Vsv knots of prop beside a copy of its deepest row (rows n..2n of prop are Vsh's)
+  double *rsum;                // [5][n][ncol]: sums of xi, xi^2, vv vh, V, V^2 over the recorded states
+  long long *rgt1;             // [n][ncol]: recorded states with xi > 1
+  unsigned *rhist;             // [ncs][n][nbin]: counts of xi over [(vmin_h / vmax_v)^2, (vmax_h / vmin_v)^2]
 };
 
 // Gc/Gs (dazim_mc_set_aniso).  Cold column cs * ncold + g is chain g * ntemp of sampled cell cs.
@@ -122,6 +129,8 @@ struct dazim_mc {
   bool typed = false;       // ... other than Rayleigh phase alone: dazim_mc_run calls dazim_dispersion_kernels_typed
   int prior = 0;            // Gaussian smoothness prior: 0 = off (d.ps2, d.pd2, d.pref hold it while it is on)
   float psmooth = 0.0f, pdamp = 0.0f;
+  float couple = 0.0f;      // dazim_mc_set_radial's mu (d.nrad > 0 marks a radial handle)
+  int rad_nr = 0, rad_kr = 0;   // ... its Rayleigh segments (the first rad_nr) and their periods (rows [0, rad_kr) of pv)
   std::vector<void *> blocks;
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
@@ -176,4 +185,8 @@ inline hipError_t mc_get(dazim_ctx *ctx, void *dst, const void *src, size_t byte
 // one pass: the rung-0 states -> their curves -> their Lsen_Gsc -> one sample, in blocks of whole cells
 int mc_aniso_pass(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods);
 int64_t mc_aniso_skipped(dazim_ctx *ctx, dazim_mc *mc, int *rc);   // the samples skipped so far, over all cold columns
+// ---- the prior's record as dazim_mc_set_prior and dazim_mc_set_radial (column_mc_radial.hip) both bring it up to date ------------
+// mc->prior from smooth, damp and couple; while it is on: pref (vref, or where the handle has none yet vel0's knots) and the Q of
+// every chain's state into pq
+int mc_prior_refresh(dazim_ctx *ctx, dazim_mc *mc, const std::vector<float> *vref);
 #pragma GCC visibility pop

@@ -627,18 +627,24 @@ contains
   end subroutine
 
   ! lon lat depth Vsv Vsh Voigt-Vs xi on the whole grid in write_vs_model's order: Voigt-Vs = sqrt((2 Vsv^2 + Vsh^2) / 3),
-  ! xi = (Vsh / Vsv)^2
-  subroutine write_radial_model(fname, p, depz, vsv, vsh)
+  ! xi = (Vsh / Vsv)^2; with xi_in (inner cells, sampled knots: SurfDepthMC_amd's posterior mean of xi) that value there
+  subroutine write_radial_model(fname, p, depz, vsv, vsh, xi_in)
     character(len=*), intent(in) :: fname
     type(para_t), intent(in) :: p
     real, intent(in) :: depz(:), vsv(:, :, :), vsh(:, :, :)
+    real, intent(in), optional :: xi_in(:, :, :)
     integer :: u, i, j, k
+    real :: xi
     open (newunit=u, file=fname, status='replace', action='write')
     do k = 1, p%nz
       do j = 1, p%ny
         do i = 1, p%nx
+          xi = (vsh(i, j, k)/vsv(i, j, k))**2
+          if (present(xi_in)) then
+            if (i > 1 .and. i < p%nx .and. j > 1 .and. j < p%ny .and. k <= size(xi_in, 3)) xi = xi_in(i - 1, j - 1, k)
+          end if
           write (u, '(6f8.4,f9.5)') p%gozd + (j - 2)*p%dvzd, p%goxd - (i - 2)*p%dvxd, depz(k), vsv(i, j, k), vsh(i, j, k), &
-            sqrt((2*vsv(i, j, k)**2 + vsh(i, j, k)**2)/3), (vsh(i, j, k)/vsv(i, j, k))**2
+            sqrt((2*vsv(i, j, k)**2 + vsh(i, j, k)**2)/3), xi
         end do
       end do
     end do

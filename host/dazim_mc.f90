@@ -3,7 +3,7 @@
 ! section 14), where SurfDepthFromMaps_amd returns one linearised model.
 !
 !   SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a
-!                            [noise_a0 [noise_b0 [smooth_vs [damp_vs [types]]]]]]]]]]]]]]]]
+!                            [noise_a0 [noise_b0 [smooth_vs [damp_vs [types [radial [sigma_hv]]]]]]]]]]]]]]]]]]
 !
 ! Inputs and weights are SurfDepthFromMaps_amd's: the unchanged para.in and MOD, period_phaseV_map.dat and, if present,
 ! period_map_coverage.dat (weight 1/sigma_c where DWS > 0, else 0).  Knots 1..nz-1 are sampled, the last one keeps MOD's value.
@@ -44,6 +44,21 @@
 ! those two columns as every typed map file does, and the log gets one line per type: its periods, the mean |c residual| of the
 ! best model and the median lambda.  aniso_thin > 0 is refused with typed data: the Gc/Gs kernel Lsen_Gsc is Rayleigh-phase.
 ! Rayleigh-phase input writes the same bytes with types 0 and 1.
+! radial 0 (default): one Vs profile per cell, every file and log byte as before.  radial 1 (needs types 1, Rayleigh and Love periods
+! in para.in, aniso_thin 0 and nz - 1 <= 31): radial anisotropy (DESIGN.md sections 13.1 and 14.2).  The chains sample Vsv and Vsh
+! together (dazim_mc_set_radial): the Rayleigh maps see Vsv, the Love maps Vsh, both profiles start from MOD and share its box, the
+! deepest knot is MOD's for both, and the prior gains (Vsh - Vsv)^2 / sigma_hv^2 per knot (sigma_hv default 0.2 km/s; 0: no
+! coupling).  smooth_vs and damp_vs act on each profile about MOD.  MOD_mc, DSurfTomo_mc.inv and Vs_posterior_mc.dat then hold Vsv,
+! period_phaseV_mc.dat the Rayleigh periods of the mean Vsv and the Love periods of the mean Vsh, cell_mc.dat's misfits are those of
+! the two best and the two mean profiles, and there are more files:
+!   MOD_Vsh_mc, Vsh_posterior_mc.dat   the posterior mean of Vsh and its statistics, as MOD_mc and Vs_posterior_mc.dat
+!   xi_posterior_mc.dat          per inner cell and sampled knot: lon lat depth, xi = (Vsh / Vsv)^2 mean std p2.5 p50 p97.5 R-hat
+!                                P(xi > 1), the Vsv-Vsh correlation of the chains, the Voigt average sqrt((2 Vsv^2 + Vsh^2) / 3) mean std
+!   Vsv_Vsh_model_mc.inv         the posterior means on the whole grid, as Vsv_Vsh_model_2step.inv; its xi is the posterior mean of xi
+!   Vsv_Vsh_prior_check_mc.dat   (smooth_vs or damp_vs > 0, noise_a0 0) per inner cell and sampled knot: lon lat depth, then for Vsv
+!                                and for Vsh the chains' std, dazim_column_resolution_radial's std at the posterior-mean models and
+!                                their ratio (0 where the linearised std is 0)
+! The log gains the settings line, R-hat of xi and the share of sampled (cell, knot)s whose P(xi > 1) lies outside [0.025, 0.975].
 !
 ! Outputs (names of their own, so that the three programs can share a directory):
 !   MOD_mc, DSurfTomo_mc.inv     the posterior mean, as MOD_2step and DSurfTomo_2step.inv
@@ -82,6 +97,8 @@ program SurfDepthMC_amd
   real, allocatable :: glam_mean(:, :, :), glam_std(:, :, :)
   integer(c_int), allocatable :: gndata(:, :, :)
   integer, parameter :: nswap = 1
+  integer :: radial
+  real :: sigma_hv
   real :: tmax
   real(c_double), allocatable, target :: beta(:)
   integer(c_int64_t), allocatable, target :: swap_try(:, :), swap_acc(:, :)
@@ -106,7 +123,7 @@ program SurfDepthMC_amd
   write (*, *)
   if (command_argument_count() < 1) error stop &
     'usage: SurfDepthMC_amd para.in [nsample [nchain [width [sigma_c [seed [proposal [ntemp [tmax [aniso_thin [smooth_gcs [sigma_a '// &
-    '[noise_a0 [noise_b0 [smooth_vs [damp_vs [types]]]]]]]]]]]]]]]]'
+    '[noise_a0 [noise_b0 [smooth_vs [damp_vs [types [radial [sigma_hv]]]]]]]]]]]]]]]]]]'
   call get_command_argument(1, inputfile)
   inquire (file=inputfile, exist=ex)
   if (.not. ex) error stop 'unable to open the inputfile'
@@ -171,6 +188,33 @@ program SurfDepthMC_amd
   if (.not. (smooth_vs >= 0 .and. smooth_vs <= huge(smooth_vs))) error stop 'smooth_vs must be finite and not negative'
   if (.not. (damp_vs >= 0 .and. damp_vs <= huge(damp_vs))) error stop 'damp_vs must be finite and not negative'
   prior_on = smooth_vs > 0 .or. damp_vs > 0
+  radial = 0; sigma_hv = 0.2
+  call optional_arg(18, radial)
+  call optional_arg(19, sigma_hv)
+  if (radial /= 0 .and. radial /= 1) error stop 'radial must be 0 or 1'
+  if (radial == 1) then
+    if (types /= 1) then
+      write (*, '(a)') ' ERROR: radial = 1 needs types = 1: Vsv comes from the Rayleigh maps and Vsh from the Love maps.'
+      error stop 'radial = 1 needs types = 1'
+    end if
+    if (sum(p%type_kmax(3:4)) == 0) then
+      write (*, '(a)') ' ERROR: radial = 1: para.in lists no Love periods (kmaxLc, kmaxLg); Vsh is what the Love maps constrain.'
+      error stop 'radial = 1 needs Love periods'
+    end if
+    if (sum(p%type_kmax(1:2)) == 0) then
+      write (*, '(a)') ' ERROR: radial = 1: para.in lists no Rayleigh periods (kmaxRc, kmaxRg); Vsv is what the Rayleigh maps constrain.'
+      error stop 'radial = 1 needs Rayleigh periods'
+    end if
+    if (aniso_thin > 0) then
+      write (*, '(a)') ' ERROR: radial = 1 with aniso_thin > 0: Gc/Gs together with radial anisotropy is not supported.'
+      error stop 'radial = 1 needs aniso_thin = 0'
+    end if
+    if (nz - 1 > 31) then
+      write (*, '(a)') ' ERROR: radial = 1 samples 2 (nz - 1) knots per cell, 62 at most: nz <= 32.'
+      error stop 'radial = 1 needs nz - 1 <= 31'
+    end if
+    if (.not. (sigma_hv >= 0 .and. sigma_hv <= huge(sigma_hv))) error stop 'sigma_hv must be finite and not negative'
+  end if
   ncold = nchain/ntemp
   nlay = nz - 1
   ncell = (nx - 2)*(ny - 2)
@@ -215,6 +259,8 @@ program SurfDepthMC_amd
     end if
     if (prior_on) write (q, '(a,f8.3,a,f8.3,a)') ' Gaussian prior about MOD inside the box: smoothing', smooth_vs, '  damping', &
       damp_vs, ' (precision smooth^2 L^T L + damp^2 I)'
+    if (radial == 1) write (q, '(a,i3,a,i3,a,f8.4)') ' radial anisotropy: Vsv from the', sum(p%type_kmax(1:2)), &
+      ' Rayleigh periods, Vsh from the', sum(p%type_kmax(3:4)), ' Love periods, both from MOD; sigma_hv (km/s)', sigma_hv
   end do
 
   call read_mod('MOD', p, depz, vsf)
@@ -242,6 +288,15 @@ program SurfDepthMC_amd
   if (any(.not. (vmin < vmax))) then
     write (*, '(a)') ' ERROR: MOD lies outside para.in''s Vs range by more than width: an empty prior box'
     error stop 'empty prior box'
+  end if
+
+  if (radial == 1) then
+    call radial_run()
+    write (*, *) '  Program finishes successfully'
+    write (66, *) '  Program finishes successfully'
+    close (66)
+    call dazim_finalize()
+    stop
   end if
 
   ! ---- the chains ----------------------------------------------------------------------------------------------------------------
@@ -553,6 +608,310 @@ program SurfDepthMC_amd
   call dazim_finalize()
 
 contains
+
+  ! radial = 1: the chains on the stacked knots (Vsv, Vsh, deepest), their statistics, the log's summary and every file
+  subroutine radial_run()
+    integer :: n, kv, kh, nsv, nsh, a
+    real :: couple, share
+    real, allocatable :: vst(:, :, :), lo2(:, :, :), hi2(:, :, :), vmh(:, :, :), vbh(:, :, :)
+    real, allocatable :: mean2(:, :, :), std2(:, :, :), qq2(:, :, :, :), best2(:, :, :), rhat2(:, :, :)
+    real, allocatable, target :: xim(:, :, :), xis(:, :, :), xiq(:, :, :, :), xir(:, :, :), pg(:, :, :), cvh(:, :, :), vgm(:, :, :), &
+                                 vgs(:, :, :)
+    real*8, allocatable, target :: skv(:, :, :), skh(:, :, :)
+    real, allocatable :: sd(:, :, :, :), cov(:, :, :), rd(:, :, :, :), rsm(:, :, :, :), cross(:, :, :, :), tr(:, :, :), rat(:, :, :, :)
+    n = nlay
+    kv = sum(p%type_kmax(1:2)); kh = sum(p%type_kmax(3:4))
+    nsv = count(p%seg_wavetp(1:p%nseg) == 2); nsh = p%nseg - nsv
+    couple = 0
+    if (sigma_hv > 0) couple = 1/sigma_hv
+    if (any(.not. (vmin > 0))) error stop 'radial = 1 needs a positive lower bound of Vs (Minvel, MOD - width)'
+    allocate (vst(nx, ny, 2*n + 1), lo2(nx - 2, ny - 2, 2*n), hi2(nx - 2, ny - 2, 2*n))
+    vst(:, :, 1:n) = vsf(:, :, 1:n); vst(:, :, n + 1:2*n) = vsf(:, :, 1:n); vst(:, :, 2*n + 1) = vsf(:, :, nz)
+    lo2(:, :, 1:n) = vmin; lo2(:, :, n + 1:2*n) = vmin
+    hi2(:, :, 1:n) = vmax; hi2(:, :, n + 1:2*n) = vmax
+    call dazim_init(0)
+    call dazim_check(dazim_mc_create(dazim_handle, nx, ny, 2*n + 1, kmax, nchain, nbin, seed, vst, lo2, hi2, cmap, wcov, step0, nadapt, &
+                                     mc, nempty), 'Monte-Carlo chains')
+    do q = 6, 66, 60
+      write (q, '(a,i8,a,i8)') ' cells sampled', ncell - nempty, '  cells without data (start model kept)', nempty
+    end do
+    if (proposal /= 0) call dazim_check(dazim_mc_set_proposal(dazim_handle, mc, proposal), 'Monte-Carlo proposal')
+    if (ntemp > 1) then
+      allocate (beta(ntemp), swap_try(ntemp - 1, ncell - nempty), swap_acc(ntemp - 1, ncell - nempty))
+      call dazim_check(dazim_mc_set_tempering(dazim_handle, mc, ntemp, tmax, nswap), 'Monte-Carlo tempering')
+      call dazim_check(dazim_mc_temper_state(dazim_handle, mc, c_null_ptr, c_null_ptr, c_null_ptr, c_loc(beta), c_null_ptr, &
+                                             c_null_ptr, c_null_ptr), 'tempering ladder')
+      do q = 6, 66, 60
+        write (q, '(a,64f8.3)') ' ladder, temperatures 1 / beta:', (1.0d0/beta(i), i=1, ntemp)
+      end do
+    end if
+    call dazim_check(dazim_mc_set_segments(dazim_handle, mc, p%nseg, p%seg_wavetp, p%seg_veltp, p%seg_kmax), 'wave types')
+    ngrp = 0
+    if (noise_a0 > 0) then                      ! one noise scale per wave type, as without radial anisotropy
+      ngrp = p%nseg
+      allocate (grp(kmax))
+      do g = 1, ngrp
+        grp(sum(p%seg_kmax(1:g - 1)) + 1:sum(p%seg_kmax(1:g))) = g - 1
+      end do
+      ga0 = noise_a0; gb0 = noise_b0
+      call dazim_check(dazim_mc_set_noise_groups(dazim_handle, mc, ngrp, grp, ga0, gb0), 'hierarchical noise per wave type')
+    end if
+    call dazim_check(dazim_mc_set_radial(dazim_handle, mc, couple), 'radial anisotropy')
+    if (prior_on) call dazim_check(dazim_mc_set_prior(dazim_handle, mc, smooth_vs, damp_vs, c_null_ptr), 'Gaussian prior')
+    call dazim_check(dazim_mc_run(dazim_handle, mc, depz, minthk, tRc, nsample, nsample, nnoroot), 'Monte-Carlo run')
+    t_run = real(dazim_last_kernel_seconds(dazim_handle, 'mc'//c_null_char))
+    t_disp = real(dazim_last_kernel_seconds(dazim_handle, 'mc.disp'//c_null_char))
+    t_step = real(dazim_last_kernel_seconds(dazim_handle, 'mc.step'//c_null_char))
+    ncov = nint(dazim_last_kernel_seconds(dazim_handle, 'mc.cov_cells'//c_null_char))
+    allocate (mean2(nx - 2, ny - 2, 2*n), std2(nx - 2, ny - 2, 2*n), qq2(nx - 2, ny - 2, 2*n, 3), best2(nx - 2, ny - 2, 2*n))
+    allocate (rhat2(nx - 2, ny - 2, 2*n), acc(nx - 2, ny - 2), chi2b(nx - 2, ny - 2))
+    call dazim_check(dazim_mc_result(dazim_handle, mc, mean2, std2, qq2, best2, rhat2, acc, chi2b), 'posterior statistics')
+    allocate (xim(nx - 2, ny - 2, n), xis(nx - 2, ny - 2, n), xiq(nx - 2, ny - 2, n, 3), xir(nx - 2, ny - 2, n), pg(nx - 2, ny - 2, n))
+    allocate (cvh(nx - 2, ny - 2, n), vgm(nx - 2, ny - 2, n), vgs(nx - 2, ny - 2, n))
+    call dazim_check(dazim_mc_radial_result(dazim_handle, mc, c_loc(xim), c_loc(xis), c_loc(xiq), c_loc(xir), c_loc(pg), c_loc(cvh), &
+                                            c_loc(vgm), c_loc(vgs)), 'posterior statistics of xi')
+    if (ntemp > 1) call dazim_check(dazim_mc_temper_state(dazim_handle, mc, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                                                          c_null_ptr, c_loc(swap_try), c_loc(swap_acc)), 'swap counts')
+    if (ngrp > 0) then
+      allocate (glam_mean(nx - 2, ny - 2, ngrp), glam_std(nx - 2, ny - 2, ngrp), gndata(nx - 2, ny - 2, ngrp))
+      call dazim_check(dazim_mc_noise_groups_result(dazim_handle, mc, glam_mean, glam_std, gndata), 'noise-scale posteriors')
+    end if
+    call dazim_check(dazim_mc_free(dazim_handle, mc), 'Monte-Carlo chains')
+
+    ! ---- the curves of the mean and of the best models: the Rayleigh periods of Vsv, then the Love periods of Vsh ------------------
+    allocate (vmc(nx, ny, nz), vmh(nx, ny, nz), vbest(nx, ny, nz), vbh(nx, ny, nz), pvm(nx*ny, kmax), pvb(nx*ny, kmax))
+    vmc = vsf; vmh = vsf; vbest = vsf; vbh = vsf
+    vmc(2:nx - 1, 2:ny - 1, 1:n) = mean2(:, :, 1:n); vmh(2:nx - 1, 2:ny - 1, 1:n) = mean2(:, :, n + 1:2*n)
+    vbest(2:nx - 1, 2:ny - 1, 1:n) = best2(:, :, 1:n); vbh(2:nx - 1, 2:ny - 1, 1:n) = best2(:, :, n + 1:2*n)
+    allocate (rms_b(nx - 2, ny - 2), rms_m(nx - 2, ny - 2), sampled(nx - 2, ny - 2))
+    sampled = any(wcov /= 0.0, dim=3)
+    call curves(vbest, vbh, pvb, .false.)
+    if (prior_on .and. .not. noise_a0 > 0) then   ! the chains' stds against dazim_column_resolution_radial's at the mean models
+      allocate (svs(nx*ny, max(kv, kh), nz), svp(nx*ny, max(kv, kh), nz), srho(nx*ny, max(kv, kh), nz))
+      allocate (skv(nx*ny, kv, nz), skh(nx*ny, kh, nz))
+      call curves(vmc, vmh, pvm, .true.)
+      allocate (sd(nx - 2, ny - 2, n, 2), cov(nx - 2, ny - 2, n), rd(nx - 2, ny - 2, n, 2), rsm(nx - 2, ny - 2, n, 2))
+      allocate (cross(nx - 2, ny - 2, n, 2), tr(nx - 2, ny - 2, 2), rat(nx - 2, ny - 2, n, 2))
+      call dazim_check(dazim_column_resolution_radial(dazim_handle, nx, ny, n, kv, c_loc(skv), kh, c_loc(skh), wcov(:, :, 1:kv), &
+                                                      wcov(:, :, kv + 1:kmax), smooth_vs, damp_vs, couple, sd, cov, rd, rsm, cross, tr, &
+                                                      c_null_ptr, nempty_res, nbad), 'column resolution (Vsv, Vsh) at the mean models')
+      rat = 0
+      where (sd(:, :, :, 1) > 0) rat(:, :, :, 1) = std2(:, :, 1:n)/sd(:, :, :, 1)
+      where (sd(:, :, :, 2) > 0) rat(:, :, :, 2) = std2(:, :, n + 1:2*n)/sd(:, :, :, 2)
+    else
+      call curves(vmc, vmh, pvm, .false.)
+    end if
+    s0 = 0; cnt = 0
+    do j = 1, ny - 2
+      do i = 1, nx - 2
+        rms_b(i, j) = cell_rms(pvb, i, j)
+        rms_m(i, j) = cell_rms(pvm, i, j)
+        do t = 1, kmax
+          if (wcov(i, j, t) /= 0.0) then
+            s0 = s0 + (real(cmap(i, j, t), 8) - pvm(j*nx + i + 1, t))**2
+            cnt = cnt + 1
+          end if
+        end do
+      end do
+    end do
+    rms_all = 0
+    if (cnt > 0) rms_all = real(sqrt(s0/cnt))
+
+    ! ---- summary -----------------------------------------------------------------------------------------------------------------
+    ns = count(sampled)
+    do q = 6, 66, 60
+      write (q, '(a,i12,a,i12)') ' proposals without a root:', nnoroot, ' of', int(2*nsample, 8)*ns*nchain
+      write (q, '(a,f9.2,a,f9.2,a,f9.3,a)') ' run', t_run, ' s (dispersion calls', t_disp, ' s, step kernels', t_step, ' s)'
+      if (proposal == 1) write (q, '(a,i8,a,i8)') ' cells with an adapted covariance:', ncov, ' of', ns
+    end do
+    if (ntemp > 1 .and. ns > 0) then
+      nr = count(swap_try > 0)
+      allocate (sorted(max(nr, 1)))
+      sorted = 0
+      if (nr > 0) sorted(1:nr) = pack(real(swap_acc)/real(max(swap_try, 1_c_int64_t)), swap_try > 0)
+      call sort(sorted)
+      do q = 6, 66, 60
+        write (q, '(a,4f8.3)') ' swap acceptance over (cell, rung pair), minimum and quartiles 25/50/75 %:', sorted(1), &
+          sorted(max(1, nint(0.25*nr))), sorted(max(1, nint(0.5*nr))), sorted(max(1, nint(0.75*nr)))
+        write (q, '(a,i3,a,i3,a)') ' the statistics below are of the', ncold, ' chains per cell at T = 1 (of', nchain, ')'
+      end do
+      deallocate (sorted)
+    end if
+    if (ns > 0) then
+      allocate (sorted(ns))
+      sorted = pack(acc, sampled)
+      call sort(sorted)
+      do q = 6, 66, 60
+        write (q, '(a,3f8.3)') ' acceptance over cells, quartiles 25/50/75 %:', sorted(max(1, nint(0.25*ns))), &
+          sorted(max(1, nint(0.5*ns))), sorted(max(1, nint(0.75*ns)))
+      end do
+      deallocate (sorted)
+      nr = count(spread(sampled, 3, 2*n) .and. rhat2 == rhat2)
+      allocate (sorted(max(nr, 1)))
+      sorted = 0
+      if (nr > 0) sorted(1:nr) = pack(rhat2, spread(sampled, 3, 2*n) .and. rhat2 == rhat2)
+      call sort(sorted)
+      do q = 6, 66, 60
+        write (q, '(a,2f9.4)') ' R-hat over (cell, Vsv and Vsh knot), median and maximum:', sorted(max(1, (nr + 1)/2)), sorted(max(nr, 1))
+      end do
+      deallocate (sorted)
+      nr = count(spread(sampled, 3, n) .and. xir == xir)
+      allocate (sorted(max(nr, 1)))
+      sorted = 0
+      if (nr > 0) sorted(1:nr) = pack(xir, spread(sampled, 3, n) .and. xir == xir)
+      call sort(sorted)
+      share = real(count(spread(sampled, 3, n) .and. (pg < 0.025 .or. pg > 0.975)))/real(ns*n)
+      do q = 6, 66, 60
+        write (q, '(a,2f9.4)') ' R-hat of xi over (cell, knot), median and maximum:', sorted(max(1, (nr + 1)/2)), sorted(max(nr, 1))
+        write (q, '(a,f8.4)') ' share of sampled (cell, knot)s with P(xi > 1) outside [0.025, 0.975]:', share
+      end do
+      deallocate (sorted)
+    end if
+    do g = 1, p%nseg   ! per wave type: its periods, the mean |c residual| of the best models and, with the noise scales, the median lambda
+      s0 = 0; cnt = 0
+      do t = sum(p%seg_kmax(1:g - 1)) + 1, sum(p%seg_kmax(1:g))
+        do j = 1, ny - 2
+          do i = 1, nx - 2
+            if (wcov(i, j, t) /= 0.0) then
+              s0 = s0 + abs(real(cmap(i, j, t), 8) - pvb(j*nx + i + 1, t))
+              cnt = cnt + 1
+            end if
+          end do
+        end do
+      end do
+      if (cnt > 0) s0 = s0/cnt
+      nr = 0
+      if (ngrp > 0) nr = count(gndata(:, :, g) > 0 .and. glam_mean(:, :, g) == glam_mean(:, :, g))
+      allocate (sorted(max(nr, 1)))
+      sorted = 0
+      if (nr > 0) sorted(1:nr) = pack(glam_mean(:, :, g), gndata(:, :, g) > 0 .and. glam_mean(:, :, g) == glam_mean(:, :, g))
+      call sort(sorted)
+      do q = 6, 66, 60
+        if (ngrp > 0) then
+          write (q, '(a,a,a,i3,a,f10.5,a,f9.3)') ' ', trim(type_name(p%seg_wavetp(g), p%seg_veltp(g))), ':', p%seg_kmax(g), &
+            ' periods, best model mean |c residual| (km/s)', s0, ', median of the mean of lambda over cells', sorted(max(1, (nr + 1)/2))
+        else
+          write (q, '(a,a,a,i3,a,f10.5)') ' ', trim(type_name(p%seg_wavetp(g), p%seg_veltp(g))), ':', p%seg_kmax(g), &
+            ' periods, best model mean |c residual| (km/s)', s0
+        end if
+      end do
+      deallocate (sorted)
+    end do
+    if (prior_on .and. noise_a0 > 0) then
+      do q = 6, 66, 60
+        write (q, '(a)') ' Gaussian prior: Vsv_Vsh_prior_check_mc.dat is not written, with the noise scale unknown sigma_c is not the data std'
+      end do
+    else if (prior_on) then
+      do a = 1, 2
+        nr = count(spread(sampled, 3, n) .and. rat(:, :, :, a) > 0)
+        allocate (sorted(max(nr, 1)))
+        sorted = 0
+        if (nr > 0) sorted(1:nr) = pack(rat(:, :, :, a), spread(sampled, 3, n) .and. rat(:, :, :, a) > 0)
+        call sort(sorted)
+        do q = 6, 66, 60
+          write (q, '(a,a,a,3f9.4)') ' Gaussian prior: chains'' std / linearised std of ', merge('Vsv', 'Vsh', a == 1), &
+            ' over (cell, knot), quartiles 25/50/75 %:', sorted(max(1, nint(0.25*nr))), sorted(max(1, (nr + 1)/2)), &
+            sorted(max(1, nint(0.75*nr)))
+        end do
+        deallocate (sorted)
+      end do
+    end if
+    do q = 6, 66, 60
+      write (q, '(a,f12.5)') ' posterior-mean models: rms_c', rms_all
+    end do
+
+    ! ---- output files ------------------------------------------------------------------------------------------------------------
+    call write_mod('MOD_mc', depz, vmc)
+    call write_mod('MOD_Vsh_mc', depz, vmh)
+    call write_vs_model('DSurfTomo_mc.inv', p, depz, vmc)
+    call write_posterior('Vs_posterior_mc.dat', 0)
+    call write_posterior('Vsh_posterior_mc.dat', n)
+    open (64, file='xi_posterior_mc.dat')
+    do k = 1, n
+      do j = 1, ny - 2
+        do i = 1, nx - 2
+          write (64, '(3f10.4,5f10.5,f10.4,f9.4,f9.4,2f10.4)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, depz(k), xim(i, j, k), &
+            xis(i, j, k), xiq(i, j, k, 1), xiq(i, j, k, 2), xiq(i, j, k, 3), xir(i, j, k), pg(i, j, k), cvh(i, j, k), vgm(i, j, k), &
+            vgs(i, j, k)
+        end do
+      end do
+    end do
+    close (64)
+    call write_radial_model('Vsv_Vsh_model_mc.inv', p, depz, vmc, vmh, xim)
+    call write_phase_map('period_phaseV_mc.dat', p, inner_cells(nx, ny, kmax, pvm))
+    if (ngrp > 0) then
+      open (64, file='noise_posterior_mc.dat')
+      do g = 1, ngrp
+        wavetp = p%seg_wavetp(g); veltp = p%seg_veltp(g)
+        do j = 1, ny - 2
+          do i = 1, nx - 2
+            write (64, '(2f10.4,3f12.6,i6,2i3)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, glam_mean(i, j, g), glam_std(i, j, g), &
+              sigma_c*glam_mean(i, j, g), gndata(i, j, g), wavetp, veltp
+          end do
+        end do
+      end do
+      close (64)
+    end if
+    if (prior_on .and. .not. noise_a0 > 0) then
+      open (64, file='Vsv_Vsh_prior_check_mc.dat')
+      do k = 1, n
+        do j = 1, ny - 2
+          do i = 1, nx - 2
+            write (64, '(3f10.4,2(2f12.6,f12.5))') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, depz(k), std2(i, j, k), sd(i, j, k, 1), &
+              rat(i, j, k, 1), std2(i, j, n + k), sd(i, j, k, 2), rat(i, j, k, 2)
+          end do
+        end do
+      end do
+      close (64)
+    end if
+    open (78, file='cell_mc.dat')
+    do j = 1, ny - 2
+      do i = 1, nx - 2
+        write (78, '(3f10.4,2f10.5)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, acc(i, j), rms_b(i, j), rms_m(i, j)
+      end do
+    end do
+    close (78)
+
+  contains
+
+    ! the Rayleigh curves of vv into pv(:, 1:kv) and the Love curves of vh into pv(:, kv+1:kmax); with kernels their dc/dVs tables
+    subroutine curves(vv, vh, pv, kernels)
+      real, intent(in) :: vv(:, :, :), vh(:, :, :)
+      real*8, intent(out) :: pv(:, :)
+      logical, intent(in) :: kernels
+      type(c_ptr) :: ka, kb, kc
+      ka = c_null_ptr; kb = c_null_ptr; kc = c_null_ptr
+      if (kernels) then
+        ka = c_loc(svs); kb = c_loc(svp); kc = c_loc(srho)
+      end if
+      call dazim_check(dazim_dispersion_kernels_typed(dazim_handle, nx, ny, nz, vv, depz, minthk, int(nsv, c_int), &
+                                                      int(p%seg_wavetp(1:nsv), c_int), int(p%seg_veltp(1:nsv), c_int), &
+                                                      int(p%seg_kmax(1:nsv), c_int), tRc(1:kv), pv(:, 1:kv), ka, kb, kc, nfail), &
+                       'Rayleigh curves of Vsv')
+      if (kernels) call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kv, vv, svs, svp, srho, skv), 'dc/dVsv table')
+      call dazim_check(dazim_dispersion_kernels_typed(dazim_handle, nx, ny, nz, vh, depz, minthk, int(nsh, c_int), &
+                                                      int(p%seg_wavetp(nsv + 1:p%nseg), c_int), int(p%seg_veltp(nsv + 1:p%nseg), c_int), &
+                                                      int(p%seg_kmax(nsv + 1:p%nseg), c_int), tRc(kv + 1:kmax), pv(:, kv + 1:kmax), ka, &
+                                                      kb, kc, nfail), 'Love curves of Vsh')
+      if (kernels) call dazim_check(dazim_vs_kernels(dazim_handle, nx, ny, nz, kh, vh, svs, svp, srho, skh), 'dc/dVsh table')
+    end subroutine
+
+    ! Vs_posterior_mc.dat's lines for the knots k0 + 1 .. k0 + n of the stacked statistics
+    subroutine write_posterior(fname, k0)
+      character(len=*), intent(in) :: fname
+      integer, intent(in) :: k0
+      open (64, file=fname)
+      do k = 1, n
+        do j = 1, ny - 2
+          do i = 1, nx - 2
+            write (64, '(3f10.4,7f10.4)') gozd + (j - 1)*dvzd, goxd - (i - 1)*dvxd, depz(k), mean2(i, j, k0 + k), std2(i, j, k0 + k), &
+              qq2(i, j, k0 + k, 1), qq2(i, j, k0 + k, 2), qq2(i, j, k0 + k, 3), best2(i, j, k0 + k), rhat2(i, j, k0 + k)
+          end do
+        end do
+      end do
+      close (64)
+    end subroutine
+  end subroutine
 
   ! RMS over the periods with a weight of cmap - c at inner cell (i1, j1); 0 for a cell without data
   real function cell_rms(pv, i1, j1)

@@ -45,7 +45,8 @@ module dazim_mod
             dazim_mc_set_proposal, dazim_mc_cov_state, dazim_mc_set_tempering, dazim_mc_temper_state, dazim_last_kernel_seconds, &
             dazim_mc_set_aniso, dazim_mc_aniso_step, dazim_mc_aniso_state, dazim_mc_aniso_result, dazim_mc_set_noise, &
             dazim_mc_noise_state, dazim_mc_noise_result, dazim_mc_set_prior, dazim_mc_prior_state, dazim_mc_set_segments, &
-            dazim_mc_set_noise_groups, dazim_mc_noise_groups_state, dazim_mc_noise_groups_result
+            dazim_mc_set_noise_groups, dazim_mc_noise_groups_state, dazim_mc_noise_groups_result, dazim_mc_set_radial, &
+            dazim_mc_radial_models, dazim_mc_radial_state, dazim_mc_radial_result
   integer, save :: dazim_nranks = 1, dazim_rank = 0
   ! device seconds of dazim_assemble_G's calls, summed over its calls (HIP events of the library): the column curves of this rank's
   ! block of the model, its perturbed copies (auxiliary stream), the TI kernels, the eikonal launch, the ray kernels
@@ -427,6 +428,28 @@ module dazim_mod
       type(c_ptr), value :: ctx, mc
       integer(c_int), value :: nseg
       integer(c_int) :: seg_iwave(*), seg_igr(*), seg_kmax(*)
+    end function
+    ! radial anisotropy: the handle's knots are (Vsv_1..Vsv_n, Vsh_1..Vsh_n, deepest), created with nz = 2n + 1; couple = 1 / sigma_hv
+    integer(c_int) function dazim_mc_set_radial(ctx, mc, couple) bind(C, name="dazim_mc_set_radial")
+      import
+      type(c_ptr), value :: ctx, mc
+      real(c_float), value :: couple
+    end function
+    ! the device arrays (n + 1, ncol) that dazim_mc_run's two dispersion calls read; vsv_dev, vsh_dev, ncol may be c_null_ptr
+    integer(c_int) function dazim_mc_radial_models(mc, vsv_dev, vsh_dev, ncol) bind(C, name="dazim_mc_radial_models")
+      import
+      type(c_ptr), value :: mc, vsv_dev, vsh_dev, ncol
+    end function
+    ! every argument after mc may be c_null_ptr (c_loc of a variable or an array otherwise)
+    integer(c_int) function dazim_mc_radial_state(ctx, mc, n, couple, rsum, ngt1, xhist) bind(C, name="dazim_mc_radial_state")
+      import
+      type(c_ptr), value :: ctx, mc, n, couple, rsum, ngt1, xhist
+    end function
+    ! results (nx-2, ny-2, n), xi_q (nx-2, ny-2, n, 3); every array may be c_null_ptr
+    integer(c_int) function dazim_mc_radial_result(ctx, mc, xi_mean, xi_std, xi_q, xi_rhat, p_gt1, corr_vh, voigt_mean, voigt_std) &
+        bind(C, name="dazim_mc_radial_result")
+      import
+      type(c_ptr), value :: ctx, mc, xi_mean, xi_std, xi_q, xi_rhat, p_gt1, corr_vh, voigt_mean, voigt_std
     end function
     integer(c_int) function dazim_phase_map_update(ctx, nx, ny, kmax, azim, pv, dm, minc, maxc, a1, a2, stats) &
         bind(C, name="dazim_phase_map_update")

@@ -728,6 +728,49 @@ int dazim_column_resolution_radial(dazim_ctx *ctx, int nx, int ny, int nlay, int
  *   step has been done.
  *   dazim_mc_prior_state: smooth, damp (0, 0 while the prior is off) and copies of vref and of q [ncol], the Q of the chains' current
  *   states (each pointer nullable, the arrays host or device).  DAZIM_E_BAD_ARG when the prior is off and an array is requested.
+ * Radial anisotropy (dazim_mc_set_radial; without it every launch and every result is the one above, unchanged): the handle's knots
+ *   are read as the stacked vector [Vsv_0..Vsv_{n-1}, Vsh_0..Vsh_{n-1}, deepest], nlay = 2n <= 62, of dazim_column_lsq_radial:
+ *   dazim_mc_create is called with nz = 2n + 1, vel0 [2n+1][ny][nx] the Vsv start knots, then the Vsh start knots, then the one
+ *   deepest knot both profiles keep, vmin / vmax [2n][ny-2][nx-2] likewise.  The step does not ask what a knot means: the draws, the
+ *   proposals, the covariance sums and factor (which pick up the Vsv-Vsh correlation), the ladder, the noise groups, sums, hist and
+ *   R-hat are the ones above on 2n knots.  What changes:
+ *   Forward model (dazim_mc_run; depz has n + 1 entries): the physics of dazim_column_lsq_radial with the same neglect of the
+ *   cross-sensitivities.  Per step two dazim_dispersion_kernels_typed calls, curves only, nx = ncol, ny = 1, nz = n + 1: the
+ *   Rayleigh segments (the first ones, kR periods) on the Vsv model [n+1][ncol] into rows [0, kR) of the curves, the Love segments on
+ *   the Vsh model into rows [kR, kmax).  The Vsh model is rows n..2n of the proposals as they lie; the Vsv model is an array of the
+ *   handle's that holds the Vsv knots beside a copy of the deepest row: the step stores every proposed Vsv knot to both, so there is
+ *   no copy and no host wait between a step and the next dispersion call.  dazim_mc_radial_models hands out both device arrays (the
+ *   ones the run's calls read; valid after dazim_mc_set_radial and after every step).  "mc.disp" sums both calls, n_no_root counts a
+ *   proposal whose Rayleigh or Love curve has no root once; stat "mc.radial" is 1.
+ *   Prior: with d = v - vref per profile, Q = s2 (|L dv|^2 + |L dh|^2) + d2 (|dv|^2 + |dh|^2) + m2 |vh - vv|^2, the precision
+ *   [[P + m2 I, -m2 I], [-m2 I, P + m2 I]] of dazim_column_resolution_radial (the coupling on the model, the rest about vref); s2, d2
+ *   from dazim_mc_set_prior, whose vref is [2n][ny-2][nx-2], m2 = (double)couple * (double)couple.  Sum order, fp64, no contraction:
+ *   q1 = q2 = 0.0; for the profile of Vsv (knots k0 = 0) and then of Vsh (k0 = n), for a = 0..n-1: d_a = (double)v_{k0+a} - (double)
+ *   vref_{k0+a}, t_a = 2.0 * d_a for a == 0 or a == n-1, else (2.0 * d_a - d_{a-1}) - d_{a+1} (L inside the profile: no row crosses
+ *   the boundary), q1 += t_a * t_a, q2 += d_a * d_a; then qc = 0.0 and for a = 0..n-1: c_a = (double)v_{n+a} - (double)v_a, qc +=
+ *   c_a * c_a; Q = (s2 * q1 + d2 * q2) + m2 * qc.  The prior path (E + Q, above) is on when any of smooth, damp, couple is non-zero;
+ *   dazim_mc_set_prior and dazim_mc_set_radial give the same Q of the start models in either order, and with smooth = damp = 0 vref
+ *   stays what it was (vel0's knots where there was none).
+ *   Record: a recorded rung-0 chain adds, per knot pair a < n of its state after the decision and any swap, with vv = (double)v_a,
+ *   vh = (double)v_{n+a}, r = vh / vv, xi = r * r, V = sqrt((2.0 * vv * vv + vh * vh) / 3.0) (the Voigt average): rsum[0..4][a][col]
+ *   += xi, xi * xi, vv * vh, V, V * V (fp64); ngt1[a][col] += 1 where xi > 1.0 (int64); xhist[cs][a][b] += 1, b = (int)((xi - lo) /
+ *   (hi - lo) * nbin) clamped to 0..nbin-1 over the pair's exact range lo = rl * rl, rl = (double)vmin_{n+a} / (double)vmax_a, hi =
+ *   rh * rh, rh = (double)vmax_{n+a} / (double)vmin_a.  All 0 at the start; the columns of the other rungs stay 0.
+ *   dazim_mc_set_radial: couple = mu >= 0 (1 / the std of Vsh - Vsv; 0 = no coupling).  DAZIM_E_BAD_ARG once a step has been done,
+ *   when nz - 1 is odd, for a negative or non-finite couple, unless dazim_mc_set_segments has given at least one Rayleigh and one
+ *   Love segment with every Rayleigh segment before every Love segment (later dazim_mc_set_segments calls are held to the same),
+ *   on a handle with dazim_mc_set_aniso on (and dazim_mc_set_aniso is refused on a radial handle), and when any vmin is <= 0 (xi
+ *   would have no range).  A radial handle stays radial.
+ *   dazim_mc_radial_state: n (0 on a handle that is not radial), couple, and copies of rsum [5][n][ncol], ngt1 [n][ncol] (int64) and
+ *   xhist [sampled cells][n][nbin] (each nullable, host or device).  DAZIM_E_BAD_ARG when an array is asked of a handle that is not
+ *   radial.
+ *   dazim_mc_radial_result, one lane per (inner cell, knot pair), every fp64 sum over the rung-0 chains in chain order, tot = N *
+ *   ncold: xi_mean = S0 / tot, xi_std = sqrt(max(S1 / tot - mean^2, 0)); xi_q [3] from xhist as dazim_mc_result's q, linear inside
+ *   a bin, over [lo, hi] above; xi_rhat the R-hat above from the chains' rsum[0] and rsum[1]; p_gt1 = sum ngt1 / tot; corr_vh =
+ *   (S2 / tot - Ev * Eh) / (sdv * sdh) with Ev, Eh, sdv, sdh the fp64 mean and population std of the two knots from sums (NaN where
+ *   a std is 0); voigt_mean = S3 / tot, voigt_std likewise from S4.  All [n][ny-2][nx-2] fp32 (xi_q [3][n][ny-2][nx-2]), each
+ *   nullable, host or device, rounded once.  A cell without data: xi and V of vel0's knots, std 0, the quantiles at that xi, NaN
+ *   for xi_rhat, p_gt1 and corr_vh.  Refused on a handle that is not radial and before the first recorded step.
  * dazim_mc_create: vel0 [nz][ny][nx] (the last knot; the result of cells without data), vmin, vmax [nlay][ny-2][nx-2], cobs, wdat
  *   [kmax][ny-2][nx-2] (the layout of dazim_column_lsq), step = the initial s, nadapt >= 1.  Draws the start models.  Refused
  *   (DAZIM_E_BAD_ARG): nchain outside 1..64, nlay outside 1..63, kmax outside 1..60, nbin < 2, a non-finite vmin, vmax, cobs or
@@ -785,6 +828,11 @@ int dazim_mc_noise_groups_result(dazim_ctx *ctx, dazim_mc *mc, float *lam_mean, 
 int dazim_mc_set_segments(dazim_ctx *ctx, dazim_mc *mc, int nseg, const int *seg_iwave, const int *seg_igr, const int *seg_kmax);
 int dazim_mc_set_prior(dazim_ctx *ctx, dazim_mc *mc, float smooth, float damp, const float *vref);
 int dazim_mc_prior_state(dazim_ctx *ctx, dazim_mc *mc, float *smooth, float *damp, float *vref, double *q);
+int dazim_mc_set_radial(dazim_ctx *ctx, dazim_mc *mc, float couple);
+int dazim_mc_radial_models(dazim_mc *mc, float **vsv_dev, float **vsh_dev, int64_t *ncol);
+int dazim_mc_radial_state(dazim_ctx *ctx, dazim_mc *mc, int *n, float *couple, double *rsum, int64_t *ngt1, unsigned *xhist);
+int dazim_mc_radial_result(dazim_ctx *ctx, dazim_mc *mc, float *xi_mean, float *xi_std, float *xi_q, float *xi_rhat, float *p_gt1,
+                           float *corr_vh, float *voigt_mean, float *voigt_std);
 int dazim_mc_step(dazim_ctx *ctx, dazim_mc *mc, int kmax, int64_t ncol, const double *pv, int record);
 int dazim_mc_run(dazim_ctx *ctx, dazim_mc *mc, const float *depz, float sublayers, const double *periods, int nburn, int nsample,
                  int64_t *n_no_root);

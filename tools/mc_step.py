@@ -9,6 +9,7 @@
     python tools/mc_step.py --program --prior S D [--dir D] [--proposal K] [--ntemp R [--tmax T]] [--noise A0 B0]
     python tools/mc_step.py --typed [--steps S] [--big N] [--runs R]
     python tools/mc_step.py --shapes [--noise A0 B0 | --groups] [--prior S D] [--steps S] [--big N] [--runs R]
+    python tools/mc_step.py --radial [--steps S] [--runs R] [--proposal K]
 
 On bench.py's S-256 model (54 x 54 columns: 2 704 inner cells, 12 knots, 16 periods) with 8, 32 and 64 chains per cell, and on an
 N x N grid of the same model (default 202: 200 x 200 inner cells) with 8 chains: one dazim_mc_run of S steps (S/2 burn-in, S/2
@@ -51,7 +52,12 @@ whose "mc.step" are the two step kernels side by side (profiles/mc_typed.md).
 --shapes: one mode of the step kernel at S-256 with 32 chains and on the big grid with 8, R runs (default 3) of S steps each on a
 fresh handle after its warm-up run, for comparing two builds (DAZIM_LIB; profiles/mc_noise_once.md): the fixed noise level, --noise
 A0 B0, or --groups, one noise scale per type on the four types of --typed (dazim_mc_set_noise_groups); each with --prior S D as well.
-Reports the ms per step of "mc", "mc.disp" and "mc.step" of every run."""
+Reports the ms per step of "mc", "mc.disp" and "mc.step" of every run.
+
+--radial: radial anisotropy (dazim_mc_set_radial, sigma_hv 0.2) at S-256 with 32 chains and the model's 16 periods as Rayleigh phase
+and again as Love phase (32 virtual periods, 22 sampled knots): R runs (default 3) of S steps, each on a fresh handle after its warm-up
+run, with the ms per step of "mc", "mc.disp" and "mc.step"; beside them, on the last handle's own two models, S repeats of the two
+dazim_dispersion_kernels_typed calls alone: their wall time per repeat and the kernel timers' share (profiles/mc_radial.md)."""
 import argparse
 import json
 import os
@@ -131,6 +137,53 @@ def typed_case(ctx, n, nchain, steps, name, runs, prior=None):
             out[key].append(1e3 * ctx.stat(stat) / steps)
         out["curves_per_step"] = mc.ncol
         out["noise_groups"] = int(ctx.stat("mc.noise_groups"))
+        mc.free()
+    for key in ("ms_per_step", "disp_ms_per_step", "mc_step_ms_per_step"):
+        out[key + "_median"] = float(np.median(out[key]))
+    return out
+
+
+def radial_case(ctx, steps, runs, proposal):
+    import bench
+    import torch
+    n = bench.NX = bench.NY = 54
+    vel = bench.s256_model().astype(np.float32)
+    depz, periods = np.asarray(bench.DEPZ, np.float32), np.asarray(bench.PERIODS, np.float64)
+    nz, nl = len(depz), len(depz) - 1
+    segs = [(2, 0, periods), (1, 0, periods)]
+    virt = np.concatenate([periods, periods])
+    K = len(virt)
+    pv, _, _ = ctx.dispersion_kernels_typed(vel, depz, segs, bench.MINTHK, kernels=False)
+    cobs = pv.reshape(K, n, n)[:, 1:-1, 1:-1].astype(np.float32)
+    wdat = np.where(cobs != 0, np.float32(100.0), np.float32(0)).astype(np.float32)
+    vel0 = np.concatenate([vel[:nl], vel[:nl], vel[nl:]])
+    inner = vel0[:-1, 1:-1, 1:-1]
+    vmin, vmax = (inner - 0.4).astype(np.float32), (inner + 0.4).astype(np.float32)
+    out = {"case": "radial", "grid": f"{n}x{n} columns ({(n - 2) ** 2} inner cells), {nl} + {nl} sampled knots, {K} virtual periods",
+           "nchain": 32, "steps": steps, "proposal": proposal, "ms_per_step": [], "disp_ms_per_step": [], "mc_step_ms_per_step": []}
+    sync = lambda: torch.cuda.synchronize(ctx.device)
+    for r in range(runs):
+        mc = ctx.mc_create(n, n, 2 * nl + 1, K, 32, 100, 1, vel0, vmin, vmax, cobs, wdat, nadapt=5 if proposal else 50, proposal=proposal,
+                           segments=segs, radial=5.0)
+        mc.run(depz, bench.MINTHK, virt, 5, 0)                    # warm-up: code objects, scratch buffers
+        out["no_root"] = mc.run(depz, bench.MINTHK, virt, steps // 2, steps - steps // 2)
+        for key, stat in (("ms_per_step", "mc"), ("disp_ms_per_step", "mc.disp"), ("mc_step_ms_per_step", "mc.step")):
+            out[key].append(1e3 * ctx.stat(stat) / steps)
+        out["curves_per_step"] = mc.ncol
+        if r == runs - 1:                                         # the two typed calls alone, on the handle's own models
+            vsv, vsh = (m.reshape(nl + 1, 1, -1) for m in mc.radial_models())
+            walls, kern = [], 0.0
+            for _ in range(steps):
+                sync()
+                t0 = time.perf_counter()
+                ctx.dispersion_kernels_typed(vsv, depz, segs[:1], bench.MINTHK, kernels=False)
+                kern += ctx.stat("disp")
+                ctx.dispersion_kernels_typed(vsh, depz, segs[1:], bench.MINTHK, kernels=False)
+                kern += ctx.stat("disp_typed")
+                sync()
+                walls.append(1e3 * (time.perf_counter() - t0))
+            out["two_typed_calls_wall_ms_median"] = float(np.median(walls))
+            out["two_typed_calls_kernel_ms"] = 1e3 * kern / steps
         mc.free()
     for key in ("ms_per_step", "disp_ms_per_step", "mc_step_ms_per_step"):
         out[key + "_median"] = float(np.median(out[key]))
@@ -289,8 +342,13 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--shapes", action="store_true")
     ap.add_argument("--groups", action="store_true")
+    ap.add_argument("--radial", action="store_true")
     a = ap.parse_args()
     ctx = dz.Context(0)
+    if a.radial:
+        print(json.dumps(radial_case(ctx, a.steps, a.runs, a.proposal)), flush=True)
+        ctx.close()
+        return
     if a.shapes:
         shape_cases(ctx, a)
         ctx.close()
